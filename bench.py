@@ -15,6 +15,12 @@ inside the timed region and amortised over its iterations.
 
 value = LM iterations of all ranks' work / wall time (max over ranks).  N>1: the single graph is sharded
 over the ranks (strong scaling; islam_amd/dist_pvgo.py), interface blocks exchanged over RCCL.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line.  Everything else the benchmark measures
+(rooflines and the latency model, the reject-heavy / trust-region-moving variants, the N = 300 007 graph, the per-rank and
+independent-graph figures of N>1, the stereo-VIO front end, the CPU baselines) runs only with --full.
+--dump-outputs DIR writes what the last timed step handed its caller (the optimised nodes and velocities, the final loss, the
+optimizer-step and LM-trial counts) as DIR/<name>.npy in float64; the inputs are the same from run to run.
 """
 import argparse
 import json
@@ -590,14 +596,39 @@ def front_end_kernel_rooflines(device):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, nodes, vels, loss, lm_steps, lm_trials):
+    """--dump-outputs: what the timed path handed its caller in its last step, as float64 .npy files -- nodes (N, 7) and vels (N, 3)
+    (the optimised iterate, run_pvgo works in place), loss (1,) and lm_counts (2,) = [optimizer steps, LM trials].  Above 64 MB in
+    all, nodes / vels keep a fixed, seeded sample of rows, whose indices go to rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    nodes = nodes.detach().double().cpu().numpy()
+    vels = vels.detach().double().cpu().numpy()
+    arrays = {'loss': np.array([float(loss)]), 'lm_counts': np.array([float(lm_steps), float(lm_trials)])}
+    row_bytes = (nodes.shape[1] + vels.shape[1] + 1) * 8
+    if nodes.shape[0] * row_bytes > DUMP_MAX_BYTES - 4096:
+        rows = np.sort(np.random.default_rng(0).choice(nodes.shape[0], (DUMP_MAX_BYTES - 4096) // row_bytes, replace=False))
+        nodes, vels = nodes[rows], vels[rows]
+        arrays['rows'] = rows.astype(np.float64)
+    arrays.update(nodes=nodes, vels=vels)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)       # one step = one full run_pvgo LM loop (~0.8 ms on one MI355X)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--frames', type=int, default=N_FRAMES)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-frontend', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (rooflines, LM variants, large graph, stereo-VIO, CPU baselines)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-frontend', action='store_true', help='with --full: skip the stereo-VIO front end')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step to DIR/<name>.npy (float64)')
     args = ap.parse_args()
 
     # stdout carries ONE JSON line and nothing else: libraries that print banners to file descriptor 1 while they initialise (RCCL's
@@ -639,12 +670,12 @@ def main():
     N = prob['init_nodes'].shape[0]
     prm = ops.pvgo_default_params(LOSS_WEIGHT, radius=1e4)
 
-    # The timed region is PASSES x (exactly --steps steps): one pass is the contract's K steps between barrier + synchronize on both sides
-    # (max over ranks); with the driver's --steps 20 one pass is ~11 ms, where one scheduler hiccup moves the figure by percent, so the
-    # K steps are timed `passes` times back to back (>= 0.1 s in total) and the MEDIAN pass is reported -- steps / ms_per_step keep their
-    # meaning.
-    passes = max(1, int(os.environ.get('ISLAM_BENCH_PASSES', str(-(-200 // max(args.steps, 1))))))
+    # The timed region is one pass of exactly --steps steps between barrier + synchronize on both sides (max over ranks).
+    # ISLAM_BENCH_PASSES=P (opt-in) times the K steps P times back to back and reports the MEDIAN pass, for short K where one
+    # scheduler hiccup moves a single pass by percent -- steps / ms_per_step keep their meaning.
+    passes = max(1, int(os.environ.get('ISLAM_BENCH_PASSES', '1')))
     rccl_ranks_seen = None
+    last = {}          # what the most recent step handed its caller: (nodes, vels, loss, optimizer steps, LM trials)
     if world == 1 and not force_sharded:
         ws = ops.pvgo_workspace(N, device)
         # run_pvgo works IN PLACE on the iterate, so every step gets its own copy of the initial state, resident in HBM before
@@ -656,6 +687,7 @@ def main():
             nodes, vels = next(state_iter)
             res, _ = ops.pvgo_run_chain(nodes, vels, prob['vo'], prob['drots'], prob['dtrans'], prob['dvels'], prob['dts'],
                                         prm, workspace=ws)
+            last['out'] = (nodes, vels, res.loss, res.steps, res.trials)
             return res.trials, res.steps
     else:
         # N > 1: ONE graph sharded over the ranks, the whole LM loop inside the library on RCCL (islam_pvgo_run_chain_sharded,
@@ -670,6 +702,7 @@ def main():
 
             def step():
                 r = solver.run()
+                last['out'] = (r['nodes'], r['vels'], r['loss'], r['steps'], r['trials'])
                 return r['trials'], r['steps']
             sharded_info['loop'] = 'python stage calls + torch.distributed'
         else:
@@ -680,8 +713,9 @@ def main():
             sharded_info['rccl'] = dict(zip(('ranks', 'rank', 'device'), comm.info()))
 
             def step():
-                _, _, res, xb = dist_pvgo.run_chain_sharded(comm, prob['init_nodes'], prob['init_vels'], prob['vo'], prob['drots'],
-                                                            prob['dtrans'], prob['dvels'], prob['dts'], LOSS_WEIGHT, radius=1e4)
+                nodes, vels, res, xb = dist_pvgo.run_chain_sharded(comm, prob['init_nodes'], prob['init_vels'], prob['vo'], prob['drots'],
+                                                                   prob['dtrans'], prob['dvels'], prob['dts'], LOSS_WEIGHT, radius=1e4)
+                last['out'] = (nodes, vels, res.loss, res.steps, res.trials)
                 sharded_info['exchange_bytes_per_lm_iter'] = xb / max(res.trials, 1)
                 return res.trials, res.steps
             sharded_info['loop'] = 'islam_pvgo_run_chain_sharded (C, RCCL): fused trial + level-0 elimination kernel, one all-reduce per LM trial'
@@ -710,13 +744,15 @@ def main():
         pass_s.append(el_p)
         trials, steps_lm = tr_p, st_p            # (every pass does the same work from the same initial states)
     elapsed = float(np.median(pass_s))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last['out'])
 
     # ---- a second strong-scaling point on a graph LARGE enough for sharding to pay: the 5000-frame
     # graph of the headline is one 57 us chain of dependent launches per LM iteration -- a latency-bound all-reduce per trial costs
     # about as much -- while at N = 300 007 one iteration is 1.3 ms of work on one GPU.  Same code path as the headline at every world
-    # size (fused single-GPU loop at world 1, islam_pvgo_run_chain_sharded otherwise); ISLAM_BENCH_LARGE_N=0 skips it.
+    # size (fused single-GPU loop at world 1, islam_pvgo_run_chain_sharded otherwise); --full only, ISLAM_BENCH_LARGE_N=0 skips it there.
     large = None
-    big_n = int(os.environ.get('ISLAM_BENCH_LARGE_N', '300007'))
+    big_n = int(os.environ.get('ISLAM_BENCH_LARGE_N', '300007')) if args.full else 0
     if big_n > 0:
         try:
             t_b = time.perf_counter()
@@ -781,8 +817,8 @@ def main():
 
     # ---- N > 1 (and the 1-GPU self-test of that path): what a SCALE record is checked against, line by line
     # (profiles/r05/scaling_model_r05.json: t(P) = t_fused(N / P) + t_shard + t_allreduce).  Every rank times the FUSED single-GPU loop on
-    # a chain of its own stretch's length (N / P nodes, same generator): t_fused(N / P) measured where the sharded run ran.
-    if dist is not None:
+    # a chain of its own stretch's length (N / P nodes, same generator): t_fused(N / P) measured where the sharded run ran.  --full only.
+    if dist is not None and args.full:
         n_loc = (N - 1) // world + 1
         prob_l, _ = build_problem(device, n_loc)
         ws_l = ops.pvgo_workspace(n_loc, device)
@@ -805,9 +841,9 @@ def main():
         del prob_l, ws_l, st_l
 
     # ---- N > 1 only: the same graph solved independently on every GPU (one trajectory per GPU, SURVEY 8(e) row 4: no
-    # data-path collective), reported NEXT to the headline sharded-graph figure, never instead of it
+    # data-path collective), reported NEXT to the headline sharded-graph figure, never instead of it.  --full only.
     replicas = None
-    if dist is not None:
+    if dist is not None and args.full:
         # (no try / except: collectives inside -- a rank that dropped out would leave the others waiting; the launcher tears the job down)
         ws_r = ops.pvgo_workspace(N, device)
         n_r, v_r = torch.empty_like(prob['init_nodes']), torch.empty_like(prob['init_vels'])
@@ -837,7 +873,8 @@ def main():
                             '(independent trajectories, no collective); all ranks\' iterations / max-over-ranks time' % N}
 
     out = None
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream
         lin, _ = ops.pvgo_linearize(prob['init_nodes'], prob['init_vels'], prob['vo'], prob['drots'], prob['dtrans'],
                                     prob['dvels'], prob['dts'])
@@ -915,6 +952,7 @@ def main():
                     'latency_model': latency_model(ops, Hd, Ho, rhs, levels, device, us_iter),
                     'note': 'latency / issue-bound: the up-sweep is a chain of dependent 9x9 block pivots (one wavefront per half segment), '
                             'the SE(3) linearisation in front of it runs on 25 lanes per CU'}
+    if rank == 0:
         value = trials / elapsed
         out = {
             'metric': 'pvgo_lm_iters_per_sec', 'value': value, 'unit': 'LM iters/s', 'n_gpus': world, 'steps': args.steps,
@@ -926,12 +964,13 @@ def main():
             'lm_iters_per_step': trials / args.steps, 'optimizer_steps_per_step': steps_lm / args.steps,
             'us_per_lm_iter': elapsed / trials * 1e6,
             'timed_passes': {'passes': passes, 'pass_ms': {'median': elapsed * 1e3, 'min': min(pass_s) * 1e3, 'max': max(pass_s) * 1e3},
-                             'what': 'the K = --steps steps are timed `passes` times back to back, each pass between barrier + synchronize; '
-                                     'value / ms_per_step / us_per_lm_iter are those of the MEDIAN pass'},
+                             'what': 'the K = --steps steps are timed `passes` times back to back (1 unless ISLAM_BENCH_PASSES is set), each pass '
+                                     'between barrier + synchronize; value / ms_per_step / us_per_lm_iter are those of the MEDIAN pass'},
             'rccl_ranks_seen': rccl_ranks_seen,
-            'roofline': roofline,
         }
-        if world == 1 and not force_sharded:
+        if roofline is not None:
+            out['roofline'] = roofline
+        if args.full and world == 1 and not force_sharded:
             for key, fn in (('reject_heavy', lambda: reject_heavy_rate(ops, prob, device)),
                             ('trust_region_moving', lambda: trust_region_moving_rate(ops, prob, prm, device))):
                 try:
@@ -944,7 +983,7 @@ def main():
             out['independent_graphs'] = replicas
         if world > 1 or force_sharded:
             out['sharded'] = sharded_info
-        if not args.no_frontend and world == 1:
+        if args.full and not args.no_frontend and world == 1:
             try:
                 out['stereo_vio'] = vio_frames_per_sec(device)
             except Exception as e:           # the headline metric must still be reported
@@ -959,7 +998,7 @@ def main():
                 out['front_end_per_launch'] = front_end_kernel_rooflines(device)
             except Exception as e:
                 out['front_end_per_launch'] = {'error': repr(e)[:300]}
-        if not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N=1 only
             host = {k: v.cpu().numpy() for k, v in (('init_nodes', prob['init_nodes']), ('init_vels', prob['init_vels']),
                                                      ('vo_motions', prob['vo']), ('imu_drots', prob['drots']),
                                                      ('imu_dtrans', prob['dtrans']), ('imu_dvels', prob['dvels']),

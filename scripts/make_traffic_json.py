@@ -45,7 +45,7 @@ for name, needle in (('trial_elim_kernel', 'trial_elim_kernel'), ('bt_eliminate_
                      'traffic_bytes_per_launch': (2.0 * f[1]['live_avg_kb'] + w[1]['live_avg_kb']) * 1024.0,
                      'rocprof_live_avg_duration_ns': d[1]['live_avg_ns'] if d else None, 'dispatch': f[0]}
 json.dump({'pvgo_hip_sha16': sha, 'kernels': kernels,
-           'command': 'rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-frontend '
+           'command': 'rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-frontend '
                       '(separate passes, scripts/gpu_profile.sh)',
            'correction': 'FETCH_SIZE doubled (128-B requests counted at 64 B on gfx950), WRITE_SIZE as reported, KB = 1024 B; live dispatches only',
            'source': src}, open(out, 'w'), indent=1)

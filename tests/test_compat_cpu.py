@@ -1,9 +1,8 @@
 """The drop-in claim "train.py runs unchanged" (SURVEY.md section 8b): after islam_amd.compat.install() every PyPose name the
 reference's kept files touch resolves on the shim, the replaced modules import under the reference's module names with the
-reference's call signatures, and -- in the build container, where /root/reference exists -- the reference's own
-Datasets/transformation.py executes on top of the shim and agrees with islam_amd.transformation.
+reference's call signatures, and islam_amd.transformation agrees with the reference's own Datasets/transformation.py executed on
+top of the shim (tests/golden/transformation_ref.npz, tests/golden/make_transformation_golden.py).
 tests/golden/pypose_names.json is produced by tests/golden/make_pypose_names.py (ast over the reference)."""
-import importlib
 import inspect
 import json
 import os
@@ -82,28 +81,21 @@ def test_replaced_modules_import_under_the_reference_names(installed):
     from Network.PWC.correlation import FunctionCorrelation                            # noqa: F401  (PWCNet.py import)
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/Datasets/transformation.py'), reason='build container only: needs /root/reference')
 def test_reference_transformation_module_runs_on_the_shim(installed):
-    """The reference's OWN Datasets/transformation.py:72-124, executed on top of the shim, against islam_amd.transformation."""
+    """The reference's OWN Datasets/transformation.py:72-124, executed on top of the shim (stored results:
+    tests/golden/make_transformation_golden.py), against islam_amd.transformation on the same inputs."""
     from islam_amd import lietensor as pp, transformation as tf
-    spec = importlib.util.spec_from_file_location('_ref_transformation', '/root/reference/Datasets/transformation.py')
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    g = torch.Generator().manual_seed(0)
-    m6 = torch.randn(7, 6, generator=g, dtype=torch.float64) * 0.3
+    ref = np.load(os.path.join(G, 'transformation_ref.npz'))
+    m6 = torch.from_numpy(ref['in_m6'])
+    T0 = pp.SE3(torch.from_numpy(ref['in_T0']))
     for fn in ('cvtSE3_pypose', 'tartan2kitti_pypose'):
-        a, b = getattr(ref, fn)(m6), getattr(tf, fn)(m6)
-        assert isinstance(a, pp.LieTensor)
-        np.testing.assert_array_equal(a.tensor().numpy(), b.tensor().numpy())
-    K = ref.tartan2kitti_pypose(m6)
-    T0 = pp.se3(torch.randn(6, generator=g, dtype=torch.float64) * 0.2).Exp()
-    Pa, Pb = ref.motion2pose_pypose(K, T0), tf.motion2pose_pypose(K, T0)
-    np.testing.assert_array_equal(Pa.tensor().numpy(), Pb.tensor().numpy())
-    np.testing.assert_array_equal(ref.pose2motion_pypose(Pa).tensor().numpy(), tf.pose2motion_pypose(Pb).tensor().numpy())
+        b = getattr(tf, fn)(m6)
+        assert isinstance(b, pp.LieTensor)
+        np.testing.assert_array_equal(ref[fn], b.tensor().numpy())
+    Pb = tf.motion2pose_pypose(tf.tartan2kitti_pypose(m6), T0)
+    np.testing.assert_array_equal(ref['motion2pose_pypose'], Pb.tensor().numpy())
+    np.testing.assert_array_equal(ref['pose2motion_pypose'], tf.pose2motion_pypose(Pb).tensor().numpy())
     # se3 / SE3 inputs and the gradient path train.py relies on (motions carry grad into motion2pose)
     m = m6.clone().requires_grad_(True)
-    ref.motion2pose_pypose(ref.tartan2kitti_pypose(m), T0).tensor().sum().backward()
-    ga = m.grad.clone()
-    m.grad = None
     tf.motion2pose_pypose(tf.tartan2kitti_pypose(m), T0).tensor().sum().backward()
-    np.testing.assert_allclose(ga.numpy(), m.grad.numpy(), atol=1e-14)
+    np.testing.assert_allclose(ref['grad_m6'], m.grad.numpy(), atol=1e-14)
