@@ -500,6 +500,29 @@ int islam_pvgo_trial_elim_burst(const double* nodes, const double* vels, const d
                                 const double* dtrans, const double* dvels, const double* dts, int N,
                                 const islam_pvgo_params* prm, void* workspace, size_t workspace_bytes, int launches,
                                 float* us_per_launch, int* info, void* stream);
+/* ---- marginal covariances of a chain (no reference counterpart: new capability).
+ * A = J^T W J is the UNDAMPED Gauss-Newton matrix of the graph at a state: islam_pvgo_linearize + islam_pvgo_build_normal with
+ * vmin = 0, vmax = +inf (no damping, no diagonal clamp), plus the reprojection factor's node blocks when it is used.  Per node
+ * the solver's dx ordering [rho (3), phi (3), v (3)]; the pose part is the left perturbation X <- Exp([rho, phi]) X of the
+ * retraction.  The graph has a 6-DoF gauge (a common left perturbation of all poses is in the null space of J); it is fixed
+ * by an ANCHOR node a: the 6 pose rows and columns of node a are removed from A, A is inverted, and the anchor's pose rows and
+ * columns of Sigma are zero.  anchor = -1: no gauge fix, the matrix must be positive definite on its own.
+ * Sd (N,9,9) = diagonal blocks, So (N-1,9,9) = blocks (k,k+1) of (Hd,Ho anchored)^-1 (rows node k, columns node k+1, the
+ * layout of Ho); Hd, Ho are not modified.  ISLAM_ENOTPD if the anchored matrix is not positive definite (Sd, So then zero).
+ * Partitioned selected inversion on the solver's level tree: one up-sweep and one down-sweep launch per level below the top,
+ * one launch for the top level and one to finish (a chain the plan keeps on one level, such as N = 9: one launch in all).  seg_len as for islam_pvgo_solve_chain.
+ * Argument errors (N < 1, anchor outside [-1, N), workspace too small) return ISLAM_EARG before any HIP call. */
+size_t islam_pvgo_marginals_workspace_bytes(int N);
+int islam_pvgo_marginals(const double* Hd, const double* Ho, int N, int anchor, const int seg_len[2],
+                         void* workspace, size_t workspace_bytes, double* Sd, double* So, void* stream);
+/* Stream-ordered variant: enqueue only, no read-back and no synchronisation; status (device int, may be NULL) receives
+ * ISLAM_OK or ISLAM_ENOTPD when the call has run. */
+int islam_pvgo_marginals_enqueue(const double* Hd, const double* Ho, int N, int anchor, const int seg_len[2],
+                                 void* workspace, size_t workspace_bytes, double* Sd, double* So, int* status, void* stream);
+/* The level plan of islam_pvgo_marginals, in the format of islam_pvgo_plan (the last int: the top level); returns the level
+ * count.  Launches per call: 2 * levels (up- and down-sweep of every level below the top, the top, the finishing launch);
+ * one for a one-level plan. */
+int islam_pvgo_marginals_plan(int N, const int seg_len[2], int* plan9);
 /* ---- multi-GPU building blocks (islam_amd/dist_pvgo.py; no reference counterpart: the reference is single-GPU).
  * plan9 (3*ISLAM_PVGO_MAX_LEVELS+1 ints) receives (nodes, segment length, segments) per level (unused = 0) and, last,
  * the first level that runs inside the single-workgroup top kernel; returns the level count. */

@@ -134,6 +134,12 @@ SIGNATURES = {
     'islam_pvgo_trial_elim_burst': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), c_void_p, c_size_t, c_int,
                                                              ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_void_p]),
     'islam_pvgo_plan': (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'islam_pvgo_marginals_workspace_bytes': (c_size_t, [c_int]),
+    'islam_pvgo_marginals': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_void_p]),
+    'islam_pvgo_marginals_enqueue': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    'islam_pvgo_marginals_plan': (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'islam_dist_unique_id': (c_int, [c_void_p]),
     'islam_dist_comm_init': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
     'islam_dist_comm_destroy': (c_int, [c_void_p]),

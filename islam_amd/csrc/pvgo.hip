@@ -588,3 +588,5 @@ int islam_pvgo_trial_elim_burst(const double* nodes, const double* vels, const d
 }
 
 }  // extern "C"
+
+#include "pvgo_marginals.inl"   // marginal covariances: partitioned selected inversion

@@ -936,6 +936,46 @@ def pvgo_solve_chain_timed(Hd, Ho, rhs, damping, seg_len=(0, 0), workspace=None)
     return dx, dict(zip(names, [ms[i] for i in range(nl.value)])), levels
 
 
+def pvgo_marginals_workspace(N, device):
+    nbytes = lib().islam_pvgo_marginals_workspace_bytes(N)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def pvgo_marginals(Hd, Ho, anchor=0, seg_len=(0, 0), workspace=None, status=None):
+    """Diagonal blocks Sd (N,9,9) and neighbour blocks So (N-1,9,9) of the inverse of the block-tridiagonal (Hd, Ho) with the pose
+    DoF of node ``anchor`` held fixed (None: no gauge fix).  Hd, Ho are float64 device tensors and are not modified.
+    status=None: synchronous, raises IslamHipError (ISLAM_ENOTPD) on a matrix that is not positive definite; status = a device int32
+    tensor of one element: stream-ordered, no synchronisation, the status lands there."""
+    require_cuda(Hd, Ho)
+    assert Hd.dtype == torch.float64 and Ho.dtype == torch.float64 and Hd.is_contiguous() and Ho.is_contiguous()
+    N = Hd.shape[0]
+    assert Hd.shape == (N, 9, 9) and Ho.shape[1:] == (9, 9) and Ho.shape[0] >= N - 1
+    if workspace is None:
+        workspace = pvgo_marginals_workspace(N, Hd.device)
+    ws, nbytes = workspace
+    a = -1 if anchor is None else int(anchor)
+    Sd = torch.empty((N, 9, 9), dtype=torch.float64, device=Hd.device)
+    So = torch.empty((max(N - 1, 0), 9, 9), dtype=torch.float64, device=Hd.device)
+    sl = (c_int * 2)(int(seg_len[0]), int(seg_len[1]))
+    if status is None:
+        check(lib().islam_pvgo_marginals(ptr(Hd), ptr(Ho), N, a, sl, ptr(ws), c_size_t(nbytes), ptr(Sd), ptr(So),
+                                         stream_ptr(Hd.device)))
+    else:
+        check(lib().islam_pvgo_marginals_enqueue(ptr(Hd), ptr(Ho), N, a, sl, ptr(ws), c_size_t(nbytes), ptr(Sd), ptr(So),
+                                                 ptr(status), stream_ptr(Hd.device)))
+    return Sd, So
+
+
+def pvgo_marginals_plan(N, seg_len=(0, 0)):
+    """[(nodes, segment length, segments) per level] of pvgo_marginals; launches per call = 2 * len(levels) (1 for one level)."""
+    sl = (c_int * 2)(int(seg_len[0]), int(seg_len[1]))
+    plan = (c_int * (3 * _lib.MAX_LEVELS + 1))()
+    nl = lib().islam_pvgo_marginals_plan(N, sl, plan)
+    if nl < 1:
+        check(nl)
+    return [(plan[3 * l], plan[3 * l + 1], plan[3 * l + 2]) for l in range(nl)]
+
+
 def pvgo_retract(nodes, vels, dx, sign=1.0):
     N = nodes.shape[0]
     no, vo = torch.empty_like(nodes), torch.empty_like(vels)

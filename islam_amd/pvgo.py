@@ -27,23 +27,85 @@ def _is_canonical_chain(links, n_nodes):
         np.array_equal(l[:, 1], np.arange(1, n_nodes))
 
 
+def _reproj_struct(reproj, loss_weight, dev):
+    """The 5th residual (pvgo.py:53-61,130-143) of a SparseReprojectionLoss-like object as the library's struct (None: none)."""
+    if reproj is None:
+        return None
+    w5 = (loss_weight[4] / reproj.N) ** 2                                                      # pvgo.py:131
+    K = reproj.K.detach().cpu().double()
+    return ops.pvgo_reproj_struct(reproj.point3d.detach().to(dev, torch.float64).contiguous(),
+                                  reproj.target.detach().to(dev, torch.float64).contiguous(),
+                                  (K[0, 0], K[1, 1], K[0, 2], K[1, 2]),
+                                  pp._plain(reproj.rgb2imu_pose).detach().cpu().double().reshape(7).tolist(), w5,
+                                  getattr(reproj, 'compat_first_motion', True))
+
+
+class PvgoMarginals:
+    """Marginal covariances of a chain's poses and velocities (float64, on the device).
+
+    node_cov (N,9,9): Sigma_kk in the solver's per-node ordering [rho, phi, v] -- the pose part is the left perturbation
+    X <- Exp([rho, phi]) X; cross (N-1,9,9): Sigma_k,k+1 (rows node k, columns node k+1); pose_cov (N,6,6) and vel_cov (N,3,3):
+    the pose and velocity blocks of node_cov.  The gauge is fixed at node ``anchor`` (its pose rows / columns are zero)."""
+
+    def __init__(self, node_cov, cross, anchor, status=None):
+        self.node_cov, self.cross, self.anchor = node_cov, cross, anchor
+        self.status = status             # (run_pvgo: device int32 ISLAM_OK / ISLAM_ENOTPD of the stream-ordered call)
+
+    @property
+    def pose_cov(self):
+        return self.node_cov[:, :6, :6]
+
+    @property
+    def vel_cov(self):
+        return self.node_cov[:, 6:, 6:]
+
+
+def _marginals_at(nodes, vels, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, seg_len=(0, 0), status=None):
+    """A = J^T W J at (nodes, vels) -- undamped, unclamped, + the reprojection factor's node blocks -- and its selected inverse."""
+    N = nodes.shape[0]
+    lin, _ = ops.pvgo_linearize(nodes, vels, poses, drots, dtrans, dvels, dts)
+    w4 = [float(x) ** 2 for x in loss_weight[:4]]
+    Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, w4, vmin=0.0, vmax=float('inf'))
+    if rp is not None:
+        from .pvgo_dense import _ReprojTerms
+        _ReprojTerms(nodes, rp).add_to_chain(Hd, Ho, rhs)
+    Sd, So = ops.pvgo_marginals(Hd, Ho, anchor=anchor, seg_len=seg_len, status=status)
+    return PvgoMarginals(Sd, So, anchor, status)
+
+
+def pvgo_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight=(1, 1, 1, 1), reproj=None,
+                   anchor=0):
+    """Marginal covariances of the poses and velocities of a canonical chain (links[k] = [k, k+1], N-1 VO motions) at the given
+    state: Sigma = A^-1 with A = J^T W J the undamped Gauss-Newton matrix of run_pvgo's graph (the PyPose-compatible Jacobians,
+    the reprojection factor when ``reproj`` is given), the pose DoF of node ``anchor`` held fixed (None: no gauge fix).
+    Returns a PvgoMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
+    t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(torch.float64).contiguous()
+    n64 = t64(nodes)
+    dev = n64.device
+    if dev.type != 'cuda':
+        raise RuntimeError('islam_amd.pvgo_marginals runs on the MI355X only; there is no CPU fallback')
+    d = lambda x: t64(x).to(dev)
+    v64, poses, drots, dtrans, dvels = d(vels), d(vo_motions), d(imu_drots), d(imu_dtrans), d(imu_dvels)
+    dts64 = d(dts).reshape(-1)
+    N = n64.shape[0]
+    if poses.shape[0] != N - 1:
+        raise UnsupportedGraphError('pvgo_marginals serves canonical chains: %d VO motions for %d nodes' % (poses.shape[0], N))
+    return _marginals_at(n64, v64, poses, drots, dtrans, dvels, dts64, loss_weight, _reproj_struct(reproj, loss_weight, dev),
+                         anchor)
+
+
 def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels,
              device='cuda:0', radius=1e4, loss_weight=(1, 1, 1, 1), reproj=None, target='vo', seg_len=(0, 0),
-             return_info=False, general_solver='auto'):
+             return_info=False, general_solver='auto', marginals=False):
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError("islam_amd.run_pvgo runs on the MI355X only (device=%r); there is no CPU fallback" % (device,))
     N = len(init_nodes)
     chain = _is_canonical_chain(links, N)
-    rp = None
-    if reproj is not None:               # 5th residual (pvgo.py:53-61,130-143): SparseReprojectionLoss-like object
-        w5 = (loss_weight[4] / reproj.N) ** 2                                                  # pvgo.py:131
-        K = reproj.K.detach().cpu().double()
-        rp = ops.pvgo_reproj_struct(reproj.point3d.detach().to(dev, torch.float64).contiguous(),
-                                    reproj.target.detach().to(dev, torch.float64).contiguous(),
-                                    (K[0, 0], K[1, 1], K[0, 2], K[1, 2]),
-                                    pp._plain(reproj.rgb2imu_pose).detach().cpu().double().reshape(7).tolist(), w5,
-                                    getattr(reproj, 'compat_first_motion', True))
+    if marginals and not chain:
+        raise UnsupportedGraphError('marginals=True serves canonical chains (links[k] = [k, k+1]) only; covariances of '
+                                    'loop-closure graphs are not implemented')
+    rp = _reproj_struct(reproj, loss_weight, dev)
     out_dtype = pp._plain(init_nodes).dtype if isinstance(init_nodes, torch.Tensor) else torch.get_default_dtype()
     t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(dev, torch.float64).contiguous()
     nodes, vels = t64(init_nodes).clone(), t64(init_vels).clone()
@@ -87,12 +149,23 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
         raise ValueError("target must be 'vo' or 'imu'")
 
     an, av = ops.pvgo_align(nodes, vels, target0)
+    marg = None
+    if marginals:        # at the aligned fp64 state the caller receives; stream-ordered, its status rides on the host copy below
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        marg = _marginals_at(an, av, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, seg_len=seg_len, status=status)
     # ONE device -> host copy for everything the caller reads on the host: aligned poses, velocities and the two loss vectors (their
     # host values ride along as ``.host`` on the returned loss tensors, so that a caller that only wants to report the loss does not
     # pay another synchronising read: BilevelLoop.step)
     E = trans_loss.shape[0]
-    host = torch.cat([an.reshape(-1), av.reshape(-1), trans_loss.detach().to(torch.float64).reshape(-1),
-                      rot_loss.detach().to(torch.float64).reshape(-1)]).cpu()
+    parts = [an.reshape(-1), av.reshape(-1), trans_loss.detach().to(torch.float64).reshape(-1),
+             rot_loss.detach().to(torch.float64).reshape(-1)]
+    if marg is not None:
+        parts.append(marg.status.to(torch.float64))
+    host = torch.cat(parts).cpu()
+    if marg is not None and host[-1].item() != 0:
+        from ._lib import IslamHipError
+        raise IslamHipError(int(host[-1].item()), 'run_pvgo(marginals=True): the Gauss-Newton matrix at the solution is not '
+                                                  'positive definite')
     nodes_out = pp.SE3(host[:7 * N].view(N, 7).to(out_dtype))
     vels_out = host[7 * N:10 * N].view(N, 3).to(out_dtype)
     trans_loss.host, rot_loss.host = host[10 * N:10 * N + E], host[10 * N + E:10 * N + 2 * E]
@@ -102,6 +175,5 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
             'transvel': np.ones(n1) * loss_weight[3] ** 2}
     if reproj is not None:
         covs['reproj'] = np.ones(n1) * (loss_weight[4] / reproj.N) ** 2                        # pvgo.py:202-203
-    if return_info:
-        return trans_loss, rot_loss, nodes_out, vels_out, covs, res
-    return trans_loss, rot_loss, nodes_out, vels_out, covs
+    out = (trans_loss, rot_loss, nodes_out, vels_out, covs) + ((res,) if return_info else ()) + ((marg,) if marginals else ())
+    return out
