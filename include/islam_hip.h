@@ -456,6 +456,36 @@ int islam_pvgo_run_chain_reproj(double* nodes, double* vels, const double* poses
                                 const islam_pvgo_params* prm, const islam_pvgo_reproj* reproj, void* workspace,
                                 size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap,
                                 void* stream);
+/* Robust kernels on the chain LM: what PyPose's pp.optim.LM(kernel=...) with pp.optim.kernel.Huber / Cauchy and its
+ * FastTriggs corrector stand for.  The factor groups are the four model outputs, in the order of w[]: 0 VO (6 rows per link),
+ * 1 velocity, 2 IMU rotation, 3 translation-velocity (3 rows each).  For a factor with residual r, s = |r|^2 (unweighted):
+ *   loss (accept test, TrustRegion, StopOnPlateau) = sum rho(s);  its rows of J^T W J, J^T W r and of the trust-region term
+ *   are scaled by c = rho'(s) at the linearisation point (= r and J scaled by sqrt(c)).
+ *   ISLAM_ROBUST_NONE:   rho = s
+ *   ISLAM_ROBUST_HUBER:  rho = s (s <= d^2), 2 d sqrt(s) - d^2 otherwise
+ *   ISLAM_ROBUST_CAUCHY: rho = d^2 log(1 + s / d^2)
+ * Damping, diagonal clamp, reject limit and StopOnPlateau are unchanged. */
+#define ISLAM_ROBUST_NONE 0
+#define ISLAM_ROBUST_HUBER 1
+#define ISLAM_ROBUST_CAUCHY 2
+typedef struct {
+    int kind[4];          /* ISLAM_ROBUST_* per factor group */
+    double delta[4];      /* kernel scale d > 0 (ignored for ISLAM_ROBUST_NONE) */
+} islam_pvgo_robust;
+
+/* islam_pvgo_run_chain under robust kernels (robust == NULL or all ISLAM_ROBUST_NONE: identical to islam_pvgo_run_chain).
+ * Runs the launch-per-stage loop (like the reprojection factor).  ISLAM_EARG for an unknown kind or d <= 0. */
+int islam_pvgo_run_chain_robust(double* nodes, double* vels, const double* poses, const double* drots,
+                                const double* dtrans, const double* dvels, const double* dts, int N,
+                                const islam_pvgo_params* prm, const islam_pvgo_robust* robust, void* workspace,
+                                size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap,
+                                void* stream);
+/* General topology: the multipliers c of every VO edge from vo (24,E) (islam_pvgo_linearize_edges) -> c_vo (E), and of the three
+ * IMU-side factors of every link from lin (42,M) -> c_imu (3,M) [velocity | rotation | translation-velocity]; rho_part
+ * ((max(E,M)+63)/64) = partial sums of rho over both.  c_vo / c_imu may be NULL (loss only). */
+int islam_pvgo_robust_weights(const double* vo, int E, const double* lin, int M, const islam_pvgo_robust* robust,
+                              double* c_vo, double* c_imu, double* rho_part, void* stream);
+
 /* Stage-level: per-link reduction over the K keypoints at nodes (dx == NULL) or at Exp(dx)*nodes (dx (N,9)):
  * red (N-1, ISLAM_REPROJ_REC) = [ J^T J upper triangle (21, row-major) | J^T r (6) | r^T r (1) | pad ], J = d err / d eta
  * for the left perturbation T_k <- Exp(eta) T_k (unweighted). */
@@ -470,6 +500,10 @@ int islam_pvgo_linearize(const double* nodes, const double* vels, const double* 
 /* block-tridiagonal normal equations: Hd (N,9,9), Ho (N-1,9,9) [rows k, cols k+1], rhs (N,9) = -J^T W r, diag clamped */
 int islam_pvgo_build_normal(const double* lin, const double* dts, int N, const double w[4], double vmin, double vmax,
                             double* Hd, double* Ho, double* rhs, void* stream);
+/* islam_pvgo_build_normal with robust multipliers per link for groups 1-3: c_imu (3, N-1) [velocity | rotation |
+ * translation-velocity] (islam_pvgo_robust_weights) scale w[1], w[2], w[3] of link k. */
+int islam_pvgo_build_normal_scaled(const double* lin, const double* dts, int N, const double w[4], const double* c_imu,
+                                   double vmin, double vmax, double* Hd, double* Ho, double* rhs, void* stream);
 /* Hd.diag += Hd.diag*damping (in place, cumulative), then solve -> dx (N,9).  status (device int[4]). */
 int islam_pvgo_solve_chain(double* Hd, const double* Ho, const double* rhs, double damping, int N,
                            const int seg_len[2], void* workspace, size_t workspace_bytes, double* dx, void* stream);
@@ -602,6 +636,11 @@ int islam_pvgo_linearize_edges(const double* nodes, const int64_t* edges, const 
 int islam_pvgo_assemble_dense(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
                               const int64_t* edges, const int64_t* node_ptr, const int64_t* node_adj, double w0,
                               int N, int E, double* A, double* rhs, void* stream);
+/* islam_pvgo_assemble_dense with a robust multiplier per VO edge: edge e enters with weight w0 * c_vo[e]
+ * (c_vo from islam_pvgo_robust_weights). */
+int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
+                                     const double* c_vo, const int64_t* edges, const int64_t* node_ptr,
+                                     const int64_t* node_adj, double w0, int N, int E, double* A, double* rhs, void* stream);
 /* vo_loss forward/backward (pvgo.py:67-78 with PyPose's left-tangent gradient convention).
  * fwd: e (E,6) = Log(P^-1 Xi^-1 Xj); trans_loss, rot_loss (E).  bwd: grad_poses (E,7), last column 0. */
 int islam_pvgo_vo_loss_fwd(const double* nodes, const int64_t* edges, const double* poses, int E,

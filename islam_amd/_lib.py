@@ -39,6 +39,10 @@ class PvgoReproj(ctypes.Structure):
 
 REPROJ_REC = 32         # ISLAM_REPROJ_REC
 
+
+class PvgoRobust(ctypes.Structure):
+    _fields_ = [('kind', c_int * 4), ('delta', c_double * 4)]
+
 # name -> (restype, argtypes); every symbol include/islam_hip.h declares
 SIGNATURES = {
     'islam_last_error': (ctypes.c_char_p, []),
@@ -117,10 +121,16 @@ SIGNATURES = {
     'islam_pvgo_run_chain_reproj': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), ctypes.POINTER(PvgoReproj),
                                                              c_void_p, c_size_t, ctypes.POINTER(PvgoResult), c_void_p, c_int,
                                                              c_void_p]),
+    'islam_pvgo_run_chain_robust': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), ctypes.POINTER(PvgoRobust),
+                                                             c_void_p, c_size_t, ctypes.POINTER(PvgoResult), c_void_p, c_int,
+                                                             c_void_p]),
+    'islam_pvgo_robust_weights': (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(PvgoRobust)] + [c_void_p] * 4),
     'islam_pvgo_reproj_reduce': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(PvgoReproj), c_void_p, c_void_p]),
     'islam_pvgo_linearize': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 3),
     'islam_pvgo_build_normal': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_double), c_double, c_double] +
                                 [c_void_p] * 4),
+    'islam_pvgo_build_normal_scaled': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_double), c_void_p, c_double, c_double] +
+                                       [c_void_p] * 4),
     'islam_pvgo_solve_chain': (c_int, [c_void_p] * 3 + [c_double, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
                                                         c_void_p, c_void_p]),
     'islam_pvgo_solve_chain_enqueue': (c_int, [c_void_p] * 3 + [c_double, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
@@ -159,6 +169,7 @@ SIGNATURES = {
     'islam_pvgo_retract': (c_int, [c_void_p] * 3 + [c_double, c_int] + [c_void_p] * 3),
     'islam_pvgo_linearize_edges': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
     'islam_pvgo_assemble_dense': (c_int, [c_void_p] * 7 + [c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'islam_pvgo_assemble_dense_scaled': (c_int, [c_void_p] * 8 + [c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'islam_pvgo_vo_loss_fwd': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
     'islam_pvgo_vo_loss_bwd': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 2),
     'islam_pvgo_align': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),

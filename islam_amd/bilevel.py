@@ -24,8 +24,13 @@ PREFETCH_FIRST = _os.environ.get('ISLAM_PREFETCH_FIRST', '1') == '1'
 
 class BilevelLoop:
     def __init__(self, tartanvo, imu_module, rgb2imu_pose, imu_init, loss_weight=(1, 0.1, 10, 0.1), rot_w=1.0,
-                 trans_w=0.1, lr=3e-6, batch_size=8, device='cuda:0', train_imu_denoiser=False):
+                 trans_w=0.1, lr=3e-6, batch_size=8, device='cuda:0', train_imu_denoiser=False, pvgo_kernel=None):
         self.vo, self.imu, self.T_IL = tartanvo, imu_module, rgb2imu_pose
+        # robust kernel(s) of the PVGO back-end (run_pvgo's ``kernel``, islam_amd.robust); None: plain least squares
+        self.pvgo_kernel = pvgo_kernel
+        if pvgo_kernel is not None:
+            from .robust import parse_kernel
+            parse_kernel(pvgo_kernel)                     # (a bad argument fails here, not in the first step)
         self.loss_weight, self.rot_w, self.trans_w, self.bs, self.device = loss_weight, rot_w, trans_w, batch_size, device
         self.optimizer = torch.optim.Adam(tartanvo.vonet.flowPoseNet.parameters(), lr=lr)        # train.py:115-116
         self.imu_optimizer = None
@@ -131,9 +136,10 @@ class BilevelLoop:
         sync(); t2 = time.perf_counter()
 
         links = sample['link'] - self.current_idx
+        robust = {} if self.pvgo_kernel is None else {'kernel': self.pvgo_kernel}
         trans_loss, rot_loss, pgo_poses, pgo_vels, _ = run_pvgo(imu_poses, imu_vels, motions, links, sample['dt'], imu_drots,
                                                                  imu_dtrans, imu_dvels, device=dev, radius=1e4,
-                                                                 loss_weight=self.loss_weight, target=target)
+                                                                 loss_weight=self.loss_weight, target=target, **robust)
         pgo_poses_np, pgo_vels_np = pgo_poses.numpy(), pgo_vels.numpy()
         self.pgo_motions.extend(pose2motion_pypose(pgo_poses).numpy())                          # train.py:264-266
         self.pgo_poses.extend(pgo_poses_np[1:])

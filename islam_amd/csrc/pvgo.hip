@@ -138,8 +138,17 @@ int islam_pvgo_linearize(const double* nodes, const double* vels, const double* 
 int islam_pvgo_build_normal(const double* lin, const double* dts, int N, const double w[4], double vmin, double vmax,
                             double* Hd, double* Ho, double* rhs, void* stream) {
     if (N < 2) return fail(ISLAM_EARG, "islam_pvgo_build_normal: N=%d < 2", N);
-    hipLaunchKernelGGL(build_normal_kernel, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, w[0], w[1],
-                       w[2], w[3], vmin, vmax, Hd, Ho, rhs);
+    hipLaunchKernelGGL(build_normal_kernel<false>, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, w[0], w[1],
+                       w[2], w[3], vmin, vmax, Hd, Ho, rhs, (const double*)nullptr);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+int islam_pvgo_build_normal_scaled(const double* lin, const double* dts, int N, const double w[4], const double* c_imu,
+                                   double vmin, double vmax, double* Hd, double* Ho, double* rhs, void* stream) {
+    if (N < 2 || !c_imu) return fail(ISLAM_EARG, "islam_pvgo_build_normal_scaled: N=%d < 2 or null c_imu", N);
+    hipLaunchKernelGGL(build_normal_kernel<true>, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, w[0], w[1],
+                       w[2], w[3], vmin, vmax, Hd, Ho, rhs, c_imu);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
@@ -330,6 +339,23 @@ static int reproj_dev(const islam_pvgo_reproj* r, ReprojDev& d) {
     return ISLAM_OK;
 }
 
+// islam_pvgo_robust -> RobustDev; returns whether any group has a kernel in *active (NONE everywhere: the plain loop)
+static int robust_dev(const islam_pvgo_robust* r, RobustDev& d, bool* active = nullptr) {
+    bool any = false;
+    for (int g = 0; g < 4; ++g) {
+        const int k = r->kind[g];
+        if (k != ISLAM_ROBUST_NONE && k != ISLAM_ROBUST_HUBER && k != ISLAM_ROBUST_CAUCHY)
+            return fail(ISLAM_EARG, "islam_pvgo_robust: unknown kind %d for factor group %d", k, g);
+        if (k != ISLAM_ROBUST_NONE && !(r->delta[g] > 0.0 && std::isfinite(r->delta[g])))
+            return fail(ISLAM_EARG, "islam_pvgo_robust: delta %g of factor group %d is not a finite positive number", r->delta[g], g);
+        d.kind[g] = k;
+        d.delta[g] = k != ISLAM_ROBUST_NONE ? r->delta[g] : 1.0;
+        any = any || k != ISLAM_ROBUST_NONE;
+    }
+    if (active) *active = any;
+    return ISLAM_OK;
+}
+
 static void enqueue_reproj_reduce(const double* nodes, const double* dx, int M, const ReprojDev& rp, double* red, hipStream_t s,
                                   Gate gate = Gate{nullptr, 0.0}) {
     const int waves = std::min(4, std::max(1, (rp.K + 127) / 128));
@@ -366,8 +392,10 @@ static int ensure_linbuild_lds() {
     int dev_i = 0;
     ISLAM_HIP_CHECK(hipGetDevice(&dev_i));
     if (dev_i >= 0 && dev_i < 64 && !lb_attr_set[dev_i]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)linbuild_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_lin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
+        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)linbuild_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
+        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_lin_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
+        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)linbuild_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
+        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_lin_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
         lb_attr_set[dev_i] = true;
     }
     return ISLAM_OK;
@@ -424,9 +452,36 @@ int islam_pvgo_assemble_dense(const double* Hd, const double* Ho, const double* 
     if (N < 2 || E < 0) return fail(ISLAM_EARG, "islam_pvgo_assemble_dense: N=%d E=%d", N, E);
     hipStream_t s = as_stream(stream);
     ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
-    hipLaunchKernelGGL(dense_nodes_kernel, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, node_ptr, node_adj, w0, N, E, A,
-                       rhs);
-    if (E > 0) hipLaunchKernelGGL(dense_edges_kernel, dim3((E + 63) / 64), dim3(64), 0, s, vo, edges, w0, N, E, A);
+    hipLaunchKernelGGL(dense_nodes_kernel<false>, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, node_ptr, node_adj, w0, N, E, A,
+                       rhs, (const double*)nullptr);
+    if (E > 0) hipLaunchKernelGGL(dense_edges_kernel<false>, dim3((E + 63) / 64), dim3(64), 0, s, vo, edges, w0, N, E, A, (const double*)nullptr);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
+                                     const double* c_vo, const int64_t* edges, const int64_t* node_ptr,
+                                     const int64_t* node_adj, double w0, int N, int E, double* A, double* rhs, void* stream) {
+    if (N < 2 || E < 0 || (E > 0 && !c_vo)) return fail(ISLAM_EARG, "islam_pvgo_assemble_dense_scaled: N=%d E=%d, c_vo %p", N, E, (const void*)c_vo);
+    hipStream_t s = as_stream(stream);
+    ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
+    hipLaunchKernelGGL(dense_nodes_kernel<true>, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, node_ptr, node_adj, w0, N, E, A,
+                       rhs, c_vo);
+    if (E > 0) hipLaunchKernelGGL(dense_edges_kernel<true>, dim3((E + 63) / 64), dim3(64), 0, s, vo, edges, w0, N, E, A, c_vo);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+int islam_pvgo_robust_weights(const double* vo, int E, const double* lin, int M, const islam_pvgo_robust* robust, double* c_vo,
+                              double* c_imu, double* rho_part, void* stream) {
+    if (E < 0 || M < 0 || E + M < 1 || !robust || !rho_part || (E > 0 && !vo) || (M > 0 && !lin))
+        return fail(ISLAM_EARG, "islam_pvgo_robust_weights: E=%d M=%d or a null input", E, M);
+    RobustDev rb{};
+    const int rc = robust_dev(robust, rb);
+    if (rc != ISLAM_OK) return rc;
+    const int n = std::max(E, M);
+    hipLaunchKernelGGL(robust_weights_kernel, dim3((n + 63) / 64), dim3(64), 0, as_stream(stream), vo, E, lin, M, rb, c_vo, c_imu,
+                       rho_part);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
@@ -486,14 +541,13 @@ __global__ void close_gate_kernel(double* __restrict__ st) {
 static int run_chain_impl(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
                           const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
                           const islam_pvgo_reproj* reproj, const ReprojDev& rp, Workspace& w, hipStream_t s,
-                          islam_pvgo_result* result, double* trace, int trace_cap);
+                          islam_pvgo_result* result, double* trace, int trace_cap, const RobustDev* robust = nullptr);
 
-extern "C" {
-
-int islam_pvgo_run_chain_reproj(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
-                                const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
-                                const islam_pvgo_reproj* reproj, void* workspace, size_t workspace_bytes,
-                                islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
+// validation, workspace and the error path shared by the islam_pvgo_run_chain_* entry points
+static int run_chain_entry(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                           const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                           const islam_pvgo_reproj* reproj, const islam_pvgo_robust* robust, void* workspace,
+                           size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
     if (N < 2) return fail(ISLAM_EARG, "islam_pvgo_run_chain: N=%d < 2", N);
     if (!prm || !result) return fail(ISLAM_EARG, "islam_pvgo_run_chain: null params/result");
     ReprojDev rp{};
@@ -501,12 +555,19 @@ int islam_pvgo_run_chain_reproj(double* nodes, double* vels, const double* poses
         int rc = reproj_dev(reproj, rp);
         if (rc != ISLAM_OK) return rc;
     }
+    RobustDev rb{};
+    bool robust_on = false;
+    if (robust) {
+        int rc = robust_dev(robust, rb, &robust_on);
+        if (rc != ISLAM_OK) return rc;
+    }
     if (workspace_bytes < islam_pvgo_workspace_bytes(N))
         return fail(ISLAM_EARG, "islam_pvgo_run_chain: workspace %zu < %zu bytes", workspace_bytes,
                     islam_pvgo_workspace_bytes(N));
     Workspace w = carve((void*)align_up((size_t)workspace), N);
     hipStream_t s = as_stream(stream);
-    const int rc = run_chain_impl(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, reproj, rp, w, s, result, trace, trace_cap);
+    const int rc = run_chain_impl(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, reproj, rp, w, s, result, trace, trace_cap,
+                                  robust_on ? &rb : nullptr);
     if (rc != ISLAM_OK) {
         // A failed enqueue or status wait leaves epoch-gated kernels of the run-ahead chain queued: they would still write the pinned
         // status block and the workspace the NEXT call reuses.  Close the gate and drain the stream before handing the error up (the
@@ -516,6 +577,25 @@ int islam_pvgo_run_chain_reproj(double* nodes, double* vels, const double* poses
         (void)hipGetLastError();
     }
     return rc;
+}
+
+extern "C" {
+
+int islam_pvgo_run_chain_reproj(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                                const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                                const islam_pvgo_reproj* reproj, void* workspace, size_t workspace_bytes,
+                                islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
+    return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, reproj, nullptr, workspace, workspace_bytes, result,
+                           trace, trace_cap, stream);
+}
+
+// robust kernels: the launch-per-stage loop with linbuild_robust_kernel / trial_lin_robust_kernel
+int islam_pvgo_run_chain_robust(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                                const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                                const islam_pvgo_robust* robust, void* workspace, size_t workspace_bytes,
+                                islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
+    return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, robust, workspace, workspace_bytes, result,
+                           trace, trace_cap, stream);
 }
 
 }  // extern "C"
@@ -548,8 +628,8 @@ int islam_pvgo_trial_elim_burst(const double* nodes, const double* vels, const d
     hipLaunchKernelGGL(control_init_kernel, dim3(1), dim3(64), 0, s, w.state, w.flags, prm->radius, prm->down, (uint4*)nullptr, 0u);
     const LinWeights W{prm->w[0], prm->w[1], prm->w[2], prm->w[3], prm->vmin, prm->vmax};
     const int nlb = (N + LB_NODES - 1) / LB_NODES;
-    hipLaunchKernelGGL(linbuild_kernel, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, nodes, vels, poses, drots, dtrans, dvels, dts, N,
-                       W, w.lin, w.loss_part, w.Hd, w.Ho, w.rhs, (const double*)nullptr, ReprojDev{}, Gate{nullptr, 0.0});
+    hipLaunchKernelGGL(linbuild_kernel<false>, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, nodes, vels, poses, drots, dtrans, dvels,
+                       dts, N, W, w.lin, w.loss_part, w.Hd, w.Ho, w.rhs, (const double*)nullptr, ReprojDev{}, Gate{nullptr, 0.0}, RobustDev{});
     hipLaunchKernelGGL(control_begin_kernel, dim3(1), dim3(64), 0, s, w.loss_part, nlb, w.state, w.flags);
     LevelSrc src{};
     src.level0 = 1; src.Hd = w.Hd; src.Ho = w.Ho; src.rhs0 = w.rhs; src.state = w.state; src.hist = 1;

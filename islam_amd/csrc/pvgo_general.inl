@@ -82,11 +82,41 @@ __device__ __forceinline__ EdgeNormal edge_normal(const double* __restrict__ vo,
     return o;
 }
 
+// Robust multipliers of a general-topology linearisation (islam_pvgo_robust_weights): lane k takes VO edge k (rows 0-5 of vo)
+// and link k (velocity rows 36-38, rotation 24-26, translation-velocity 39-41 of lin); one partial sum of rho per workgroup
+__global__ __launch_bounds__(64) void robust_weights_kernel(const double* __restrict__ vo, int E, const double* __restrict__ lin, int M,
+                                                             RobustDev rb, double* __restrict__ c_vo, double* __restrict__ c_imu,
+                                                             double* __restrict__ rho_part) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    double l = 0.0, c;
+    if (k < E) {
+        const V3<double> er{vo[k], vo[(size_t)E + k], vo[2 * (size_t)E + k]};
+        const V3<double> ep{vo[3 * (size_t)E + k], vo[4 * (size_t)E + k], vo[5 * (size_t)E + k]};
+        l += robust_rho(rb.kind[0], rb.delta[0], dot(er, er) + dot(ep, ep), c);
+        if (c_vo) c_vo[k] = c;
+    }
+    if (k < M) {
+        const int rows[3] = {36, 24, 39};
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const double* p = lin + (size_t)rows[g] * M + k;
+            const V3<double> r{p[0], p[M], p[2 * (size_t)M]};
+            l += robust_rho(rb.kind[g + 1], rb.delta[g + 1], dot(r, r), c);
+            if (c_imu) c_imu[(size_t)g * M + k] = c;
+        }
+    }
+    l = wave_sum(l);
+    if (threadIdx.x == 0) rho_part[blockIdx.x] = l;
+}
+
 // one lane per node: diagonal block + right-hand side (fixed summation order over the node's edge ends), chain coupling
+// SCALED: edge e enters with weight w0 * c_vo[e] (islam_pvgo_assemble_dense_scaled)
+template <bool SCALED>
 __global__ __launch_bounds__(64) void dense_nodes_kernel(const double* __restrict__ Hd, const double* __restrict__ Ho,
                                                           const double* __restrict__ rhs_chain, const double* __restrict__ vo,
                                                           const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ node_adj,
-                                                          double w0, int N, int E, double* __restrict__ A, double* __restrict__ rhs) {
+                                                          double w0, int N, int E, double* __restrict__ A, double* __restrict__ rhs,
+                                                          const double* __restrict__ c_vo) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= N) return;
     const size_t ld = (size_t)9 * N;
@@ -96,8 +126,14 @@ __global__ __launch_bounds__(64) void dense_nodes_kernel(const double* __restric
     for (int64_t a = node_ptr[k]; a < node_ptr[k + 1]; ++a) {
         const int64_t code = node_adj[a];
         const EdgeNormal en = edge_normal(vo, E, (int)(code >> 1));
-        Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
-        if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
+        if constexpr (SCALED) {
+            const double ce = c_vo[code >> 1];
+            Srr = Srr + ce * en.Srr; Srp = Srp + ce * en.Srp; Spp = Spp + ce * en.Spp;
+            if (code & 1) { gr = gr + ce * en.gr; gp = gp + ce * en.gp; } else { gr = gr - ce * en.gr; gp = gp - ce * en.gp; }
+        } else {
+            Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
+            if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
+        }
     }
     double blk[81];
 #pragma unroll
@@ -137,13 +173,15 @@ __global__ __launch_bounds__(64) void dense_nodes_kernel(const double* __restric
     }
 }
 
-// one lane per edge: the two off-diagonal blocks -w0 S (and its transpose) of an arbitrary edge (i, j)
+// one lane per edge: the two off-diagonal blocks -w0 S (and its transpose) of an arbitrary edge (i, j) (SCALED: -w0 c_vo[e] S)
+template <bool SCALED>
 __global__ __launch_bounds__(64) void dense_edges_kernel(const double* __restrict__ vo, const int64_t* __restrict__ edges, double w0,
-                                                          int N, int E, double* __restrict__ A) {
+                                                          int N, int E, double* __restrict__ A, const double* __restrict__ c_vo) {
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= E) return;
     const int64_t i = edges[2 * e], j = edges[2 * e + 1];
     if (i == j) return;
+    if constexpr (SCALED) w0 *= c_vo[e];
     const EdgeNormal en = edge_normal(vo, E, e);
     double S[36];       // row-major 6x6 [[Srr, Srp],[Srp^T, Spp]]
     const M3<double> Spr = transpose(en.Srp);

@@ -92,10 +92,12 @@ __device__ __forceinline__ void put3x3(double* H, int r0, int c0, M3<double> a) 
 }
 
 // one lane per node: gather the two adjacent links into Hd[k], Ho[k] (coupling k -> k+1), rhs[k] = -J^T W r
+// SCALED: w1, w2, w3 of link k are multiplied by its robust multipliers c_imu[0..2][k] (islam_pvgo_build_normal_scaled)
+template <bool SCALED>
 __global__ __launch_bounds__(64) void build_normal_kernel(const double* __restrict__ lin, const double* __restrict__ dts,
                                                            int N, double w0, double w1, double w2, double w3, double vmin,
                                                            double vmax, double* __restrict__ Hd, double* __restrict__ Ho,
-                                                           double* __restrict__ rhs) {
+                                                           double* __restrict__ rhs, const double* __restrict__ c_imu) {
     int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= N) return;
     const int M = N - 1;
@@ -104,25 +106,28 @@ __global__ __launch_bounds__(64) void build_normal_kernel(const double* __restri
     M3<double> Hrr = Z, Hrp = Z, Hpp = Z;
     V3<double> gr{0, 0, 0}, gp{0, 0, 0}, gv{0, 0, 0};
     double hvv = 0.0, hrv = 0.0;
+    auto wl = [&](double w, int g, int l) { if constexpr (SCALED) return w * c_imu[(size_t)g * M + l]; else return w; };
     if (k > 0) {                       // link k-1, this node is its "j" end
-        LinkNormal L = link_normal(lin, M, k - 1, w0, w1, w2, w3);
+        const double w1l = wl(w1, 0, k - 1);
+        LinkNormal L = link_normal(lin, M, k - 1, w0, w1l, wl(w2, 1, k - 1), wl(w3, 2, k - 1));
         Hrr = Hrr + L.Srr; Hrp = Hrp + L.Srp; Hpp = Hpp + L.Spp;
         gr = gr + L.gr; gp = gp + L.gp;
-        gv = gv - w1 * L.rv;
-        hvv += w1;
+        gv = gv - w1l * L.rv;
+        hvv += w1l;
     }
     double* o = Ho + (size_t)k * 81;
     if (k < M) {                       // link k, this node is its "i" end
-        LinkNormal L = link_normal(lin, M, k, w0, w1, w2, w3);
+        const double w1l = wl(w1, 0, k), w3l = wl(w3, 2, k);
+        LinkNormal L = link_normal(lin, M, k, w0, w1l, wl(w2, 1, k), w3l);
         double dt = dts[k];
         Hrr = Hrr + L.Srr; Hrp = Hrp + L.Srp; Hpp = Hpp + L.Spp;
         gr = gr - L.gr; gp = gp - L.gp;
-        gv = gv + w1 * L.rv - (w3 * dt) * L.rt;
-        hvv += w1 + w3 * dt * dt;
-        hrv = w3 * dt;
+        gv = gv + w1l * L.rv - (w3l * dt) * L.rt;
+        hvv += w1l + w3l * dt * dt;
+        hrv = w3l * dt;
         put3x3(o, 0, 0, -1.0 * L.Srr); put3x3(o, 0, 3, -1.0 * L.Srp); put3x3(o, 0, 6, Z);
         put3x3(o, 3, 0, -1.0 * transpose(L.Srp)); put3x3(o, 3, 3, -1.0 * L.Spp); put3x3(o, 3, 6, Z);
-        put3x3(o, 6, 0, (-w3 * dt) * I); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, (-w1) * I);
+        put3x3(o, 6, 0, (-w3l * dt) * I); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, (-w1l) * I);
     }
     double* h = Hd + (size_t)k * 81;
     put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, hrv * I);
@@ -261,6 +266,39 @@ constexpr int LB_REC = 41;          // Srr 9 | Srp 9 | Spp 9 | gr 3 | gp 3 | rv 
 
 struct LinWeights { double w0, w1, w2, w3, vmin, vmax; };
 
+// Robust kernels of the four factor groups (VO, velocity, IMU rotation, translation-velocity): islam_pvgo_robust by value.
+// rho(s) of the unweighted squared norm s of one factor's residual, c = rho'(s) (PyPose's pp.optim.kernel + FastTriggs).
+struct RobustDev { int kind[4]; double delta[4]; };
+constexpr int LB_REC_ROBUST = 43;   // LB_REC + c1 w1 | c3 w3 (the weights nodes_build_copy applies), +1 pad: odd row stride
+
+__device__ __forceinline__ double robust_rho(int kind, double delta, double s, double& c) {
+    if (kind == ISLAM_ROBUST_HUBER) {
+        const double d2 = delta * delta;
+        if (s <= d2) { c = 1.0; return s; }
+        const double r = sqrt(s);
+        c = delta / r;
+        return 2.0 * delta * r - d2;
+    }
+    if (kind == ISLAM_ROBUST_CAUCHY) {
+        const double d2 = delta * delta;
+        const double u = s / d2;
+        c = 1.0 / (1.0 + u);
+        return d2 * log1p(u);
+    }
+    c = 1.0;
+    return s;
+}
+
+// sum of rho over the four factors of one link and their multipliers c[4] (residuals: erho, ephi | rv | er | rt)
+__device__ __forceinline__ double robust_link(const RobustDev& rb, V3<double> erho, V3<double> ephi, V3<double> rv, V3<double> er,
+                                              V3<double> rt, double c[4]) {
+    double l = robust_rho(rb.kind[0], rb.delta[0], dot(erho, erho) + dot(ephi, ephi), c[0]);
+    l += robust_rho(rb.kind[1], rb.delta[1], dot(rv, rv), c[1]);
+    l += robust_rho(rb.kind[2], rb.delta[2], dot(er, er), c[2]);
+    l += robust_rho(rb.kind[3], rb.delta[3], dot(rt, rt), c[3]);
+    return l;
+}
+
 // Jacobian blocks of one link at its residuals: d pgerr / d delta_j = [[G, C],[0, G]], d imuroterr / d phi_j = B
 __device__ __forceinline__ void link_jacobians(const LinkRes& r, M3<double>& G, M3<double>& C, M3<double>& B) {
     const M3<double> Ji = so3_Jl_inv(r.ephi);
@@ -310,9 +348,12 @@ __device__ __forceinline__ void link_emit(const LinkRes& r, const M3<double>& G,
 // After the link pieces are in `sl` (workgroup barrier done by the caller): waves 0-2 build Hd / Ho / rhs of the
 // workgroup's 63 nodes in LDS (node k = links k-1 in slot lane and k in slot lane+1), then all waves copy the three
 // contiguous ranges out with lane-contiguous addresses (a lane-per-node store of a 9x9 block touches 64 cache lines).
-__device__ __forceinline__ void nodes_build_copy(const double (*sl)[LB_REC], double* __restrict__ lb_out, int blk, int N,
+// (REC == LB_REC_ROBUST: the velocity and translation-velocity weights are per link, c w1 at [40] and c w3 at [41] of its record)
+template <int REC>
+__device__ __forceinline__ void nodes_build_copy(const double (*sl)[REC], double* __restrict__ lb_out, int blk, int N,
                                                  const LinWeights& W, double* __restrict__ Hd, double* __restrict__ Ho,
                                                  double* __restrict__ rhs) {
+    constexpr bool per_link = REC == LB_REC_ROBUST;
     double* const oHd = lb_out;
     double* const oHo = lb_out + LB_NODES * 81;
     double* const oR = lb_out + 2 * LB_NODES * 81;
@@ -326,18 +367,20 @@ __device__ __forceinline__ void nodes_build_copy(const double (*sl)[LB_REC], dou
         const M3<double> I = m3_identity<double>();
         const double* a0 = sl[lane];
         const double* a1 = sl[lane + 1];
+        auto w1_of = [&](const double* a) { if constexpr (per_link) return a[40]; else return w1; };
+        auto w3_of = [&](const double* a) { if constexpr (per_link) return a[41]; else return w3; };
         if (wave == 0) {                                            // Hd
             M3<double> Hrr = Z, Hrp = Z, Hpp = Z;
             double hvv = 0.0, hrv = 0.0;
             if (k > 0) {
                 Hrr = Hrr + m3_load(a0); Hrp = Hrp + m3_load(a0 + 9); Hpp = Hpp + m3_load(a0 + 18);
-                hvv += w1;
+                hvv += w1_of(a0);
             }
             if (k < M) {
                 const double dt = a1[39];
                 Hrr = Hrr + m3_load(a1); Hrp = Hrp + m3_load(a1 + 9); Hpp = Hpp + m3_load(a1 + 18);
-                hvv += w1 + w3 * dt * dt;
-                hrv = w3 * dt;
+                hvv += w1_of(a1) + w3_of(a1) * dt * dt;
+                hrv = w3_of(a1) * dt;
             }
             double h[81];
             put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, hrv * I);
@@ -354,7 +397,7 @@ __device__ __forceinline__ void nodes_build_copy(const double (*sl)[LB_REC], dou
                 double o[81];
                 put3x3(o, 0, 0, -1.0 * Srr); put3x3(o, 0, 3, -1.0 * Srp); put3x3(o, 0, 6, Z);
                 put3x3(o, 3, 0, -1.0 * transpose(Srp)); put3x3(o, 3, 3, -1.0 * Spp); put3x3(o, 3, 6, Z);
-                put3x3(o, 6, 0, (-w3 * dt) * I); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, (-w1) * I);
+                put3x3(o, 6, 0, (-w3_of(a1) * dt) * I); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, (-w1_of(a1)) * I);
 #pragma unroll
                 for (int e = 0; e < 81; ++e) oHo[lane * 81 + e] = o[e];
             }
@@ -362,12 +405,12 @@ __device__ __forceinline__ void nodes_build_copy(const double (*sl)[LB_REC], dou
             V3<double> gr{0, 0, 0}, gp{0, 0, 0}, gv{0, 0, 0};
             if (k > 0) {
                 gr = gr + ld3(a0 + 27); gp = gp + ld3(a0 + 30);
-                gv = gv - w1 * ld3(a0 + 33);
+                gv = gv - w1_of(a0) * ld3(a0 + 33);
             }
             if (k < M) {
                 const double dt = a1[39];
                 gr = gr - ld3(a1 + 27); gp = gp - ld3(a1 + 30);
-                gv = gv + w1 * ld3(a1 + 33) - (w3 * dt) * ld3(a1 + 36);
+                gv = gv + w1_of(a1) * ld3(a1 + 33) - (w3_of(a1) * dt) * ld3(a1 + 36);
             }
             double* bb = oR + lane * 9;
             bb[0] = -gr.x; bb[1] = -gr.y; bb[2] = -gr.z; bb[3] = -gp.x; bb[4] = -gp.y; bb[5] = -gp.z;
@@ -382,6 +425,9 @@ __device__ __forceinline__ void nodes_build_copy(const double (*sl)[LB_REC], dou
     for (int e = threadIdx.x; e < nR; e += LB_THREADS) rhs[node0 * 9 + e] = oR[e];
 }
 
+// ROBUST: wave 0 also forms s_k and c_k of the link's four factors in registers, sums rho into loss_part and hands c-scaled
+// pieces (and c w1, c w3) to the node builders; the default instantiation is the plain least-squares kernel.
+template <bool ROBUST>
 __global__ __launch_bounds__(LB_THREADS) void linbuild_kernel(const double* __restrict__ nodes, const double* __restrict__ vels,
                                                                const double* __restrict__ poses, const double* __restrict__ drots,
                                                                const double* __restrict__ dtrans, const double* __restrict__ dvels,
@@ -389,8 +435,9 @@ __global__ __launch_bounds__(LB_THREADS) void linbuild_kernel(const double* __re
                                                                double* __restrict__ lin, double* __restrict__ loss_part,
                                                                double* __restrict__ Hd, double* __restrict__ Ho,
                                                                double* __restrict__ rhs, const double* __restrict__ red,
-                                                               ReprojDev rp, Gate gate) {
-    __shared__ double sl[64][LB_REC];
+                                                               ReprojDev rp, Gate gate, RobustDev rb) {
+    constexpr int REC = ROBUST ? LB_REC_ROBUST : LB_REC;
+    __shared__ double sl[64][REC];
     extern __shared__ __attribute__((aligned(16))) double lb_out[];   // staged Hd (63x81) | Ho (63x81) | rhs (63x9)
     const int M = N - 1;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -407,11 +454,21 @@ __global__ __launch_bounds__(LB_THREADS) void linbuild_kernel(const double* __re
             M3<double> G, C, B;
             link_jacobians(r, G, C, B);
             const bool owns = lane > 0 || blk == 0;
-            if (owns) {
-                sq = dot(r.erho, r.erho) + dot(r.ephi, r.ephi) + dot(r.rv, r.rv) + dot(r.er, r.er) + dot(r.rt, r.rt);
-                if (red) sq += red[(size_t)L * RP_REC + 27];
+            if constexpr (ROBUST) {
+                double c[4];
+                const double rho = robust_link(rb, r.erho, r.ephi, r.rv, r.er, r.rt, c);
+                if (owns) sq = rho + (red ? red[(size_t)L * RP_REC + 27] : 0.0);
+                const LinWeights Wl{W.w0 * c[0], W.w1 * c[1], W.w2 * c[2], W.w3 * c[3], W.vmin, W.vmax};
+                link_emit(r, G, C, B, dt, L, M, owns, Wl, lin, sl[lane], red, rp, Xi);
+                sl[lane][40] = Wl.w1;
+                sl[lane][41] = Wl.w3;
+            } else {
+                if (owns) {
+                    sq = dot(r.erho, r.erho) + dot(r.ephi, r.ephi) + dot(r.rv, r.rv) + dot(r.er, r.er) + dot(r.rt, r.rt);
+                    if (red) sq += red[(size_t)L * RP_REC + 27];
+                }
+                link_emit(r, G, C, B, dt, L, M, owns, W, lin, sl[lane], red, rp, Xi);
             }
-            link_emit(r, G, C, B, dt, L, M, owns, W, lin, sl[lane], red, rp, Xi);
         }
         sq = wave_sum(sq);
         if (lane == 0) loss_part[blk] = sq;
@@ -419,4 +476,3 @@ __global__ __launch_bounds__(LB_THREADS) void linbuild_kernel(const double* __re
     __syncthreads();
     nodes_build_copy(sl, lb_out, blk, N, W, Hd, Ho, rhs);
 }
-

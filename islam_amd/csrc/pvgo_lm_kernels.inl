@@ -108,6 +108,10 @@ __global__ __launch_bounds__(64) void trial_kernel(const double* __restrict__ no
 // bumps the ticket without waiting for it.  The decision is taken by one extra workgroup that polls the ticket -- on
 // nobody's critical path -- so the host learns the verdict while the linearisation is still being written.
 // Then as linbuild_kernel: Jacobians, weighted pieces, node blocks, coalesced copy.
+// ROBUST (trial_lin_robust_kernel): wave 0 sums rho at the trial point; wave 1 recomputes each c_k of the linearisation point
+// from the residual rows of its `lin` record (0-5, 24-26, 36-41) and scales that factor's trust-region term by it; the
+// linearisation at the trial point is linbuild_body<true>'s.
+template <bool ROBUST>
 __global__ __launch_bounds__(LB_THREADS) void trial_lin_kernel(
     const double* __restrict__ nodes, const double* __restrict__ vels, const double* __restrict__ dx,
     const double* __restrict__ poses, const double* __restrict__ drots, const double* __restrict__ dtrans,
@@ -115,8 +119,9 @@ __global__ __launch_bounds__(LB_THREADS) void trial_lin_kernel(
     double* __restrict__ nodes_t, double* __restrict__ vels_t, double* part, double* st, int* flags, unsigned* ticket,
     TRParams tr, double* report, double seq, const double* __restrict__ red_lin, const double* __restrict__ red_trial,
     ReprojDev rp, LinWeights W, double* __restrict__ lin_o, double* __restrict__ Hd_o, double* __restrict__ Ho_o,
-    double* __restrict__ rhs_o, Gate gate, int* eflag2 = nullptr) {
-    __shared__ double sl[64][LB_REC];
+    double* __restrict__ rhs_o, Gate gate, int* eflag2, RobustDev rb) {
+    constexpr int REC = ROBUST ? LB_REC_ROBUST : LB_REC;
+    __shared__ double sl[64][REC];
     __shared__ double s_sq;
     extern __shared__ __attribute__((aligned(16))) double lb_out[];
     const int M = N - 1;
@@ -184,7 +189,12 @@ __global__ __launch_bounds__(LB_THREADS) void trial_lin_kernel(
                                ld3(dvels + 3 * L), dt);
             PROBE_WALL(pr, 402);
             if (owns) {
-                sq = dot(r.erho, r.erho) + dot(r.ephi, r.ephi) + dot(r.rv, r.rv) + dot(r.er, r.er) + dot(r.rt, r.rt);
+                if constexpr (ROBUST) {
+                    double c[4];
+                    sq = robust_link(rb, r.erho, r.ephi, r.rv, r.er, r.rt, c);
+                } else {
+                    sq = dot(r.erho, r.erho) + dot(r.ephi, r.ephi) + dot(r.rv, r.rv) + dot(r.er, r.er) + dot(r.rt, r.rt);
+                }
                 if (red_lin) sq += red_trial[(size_t)L * RP_REC + 27];
             }
         }
@@ -207,8 +217,15 @@ __global__ __launch_bounds__(LB_THREADS) void trial_lin_kernel(
             const V3<double> j0 = G * ddr + C * ddp, j1 = G * ddp, j2 = dvi - dvj, j3 = B * ddp, j4 = ddr - dtl * dvi;
             const V3<double> R0{rec[0], rec[1], rec[2]}, R1{rec[3], rec[4], rec[5]}, R2{rec[36], rec[37], rec[38]},
                 R3{rec[24], rec[25], rec[26]}, R4{rec[39], rec[40], rec[41]};
-            qd = dot(j0, 2.0 * R0 + j0) + dot(j1, 2.0 * R1 + j1) + dot(j2, 2.0 * R2 + j2) + dot(j3, 2.0 * R3 + j3) +
-                 dot(j4, 2.0 * R4 + j4);
+            if constexpr (ROBUST) {
+                double c[4];
+                (void)robust_link(rb, R0, R1, R2, R3, R4, c);
+                qd = c[0] * (dot(j0, 2.0 * R0 + j0) + dot(j1, 2.0 * R1 + j1)) + c[1] * dot(j2, 2.0 * R2 + j2) +
+                     c[2] * dot(j3, 2.0 * R3 + j3) + c[3] * dot(j4, 2.0 * R4 + j4);
+            } else {
+                qd = dot(j0, 2.0 * R0 + j0) + dot(j1, 2.0 * R1 + j1) + dot(j2, 2.0 * R2 + j2) + dot(j3, 2.0 * R3 + j3) +
+                     dot(j4, 2.0 * R4 + j4);
+            }
             if (red_lin) {       // reprojection rows: u^T (2 b + S u), u = Ad(C^-1 X_i^-1)(d_j - d_i)
                 double u[RP_NSUM];
 #pragma unroll
@@ -249,7 +266,16 @@ __global__ __launch_bounds__(LB_THREADS) void trial_lin_kernel(
         M3<double> G, C, B;
         link_jacobians(r, G, C, B);
         PROBE_WALL(pr, 407);
-        link_emit(r, G, C, B, dt, L, M, owns, W, lin_o, sl[lane], red_trial, rp, Xi);
+        if constexpr (ROBUST) {
+            double c[4];
+            (void)robust_link(rb, r.erho, r.ephi, r.rv, r.er, r.rt, c);
+            const LinWeights Wl{W.w0 * c[0], W.w1 * c[1], W.w2 * c[2], W.w3 * c[3], W.vmin, W.vmax};
+            link_emit(r, G, C, B, dt, L, M, owns, Wl, lin_o, sl[lane], red_trial, rp, Xi);
+            sl[lane][40] = Wl.w1;
+            sl[lane][41] = Wl.w3;
+        } else {
+            link_emit(r, G, C, B, dt, L, M, owns, W, lin_o, sl[lane], red_trial, rp, Xi);
+        }
         PROBE_WALL(pr, 408);
     }
     __syncthreads();

@@ -3,7 +3,7 @@
 static int run_chain_impl(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
                           const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
                           const islam_pvgo_reproj* reproj, const ReprojDev& rp, Workspace& w, hipStream_t s,
-                          islam_pvgo_result* result, double* trace, int trace_cap) {
+                          islam_pvgo_result* result, double* trace, int trace_cap, const RobustDev* robust) {
     const int M = N - 1;
     // status blocks in pinned, device-visible host memory: the deciding wave of trial_lin_kernel writes one per trial
     // (two slots, alternating with the trial number), the host polls its sequence number (no stream synchronisation,
@@ -44,9 +44,14 @@ static int run_chain_impl(double* nodes, double* vels, const double* poses, cons
     // red_ready: RED[b] already holds the reduction at (xn)
     auto enqueue_linbuild = [&](const double* xn, const double* xv, int b, bool red_ready) {
         if (reproj && !red_ready) enqueue_reproj_reduce(xn, nullptr, M, rp, RED[b], s);
-        hipLaunchKernelGGL(linbuild_kernel, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, xn, xv, poses, drots, dtrans, dvels,
-                           dts, N, W, LIN[b], w.loss_part, HD[b], HO[b], RH[b], reproj ? RED[b] : (const double*)nullptr, rp,
-                           Gate{nullptr, 0.0});
+        if (robust)
+            hipLaunchKernelGGL(linbuild_kernel<true>, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, xn, xv, poses, drots, dtrans,
+                               dvels, dts, N, W, LIN[b], w.loss_part, HD[b], HO[b], RH[b], reproj ? RED[b] : (const double*)nullptr, rp,
+                               Gate{nullptr, 0.0}, *robust);
+        else
+            hipLaunchKernelGGL(linbuild_kernel<false>, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, xn, xv, poses, drots, dtrans,
+                               dvels, dts, N, W, LIN[b], w.loss_part, HD[b], HO[b], RH[b], reproj ? RED[b] : (const double*)nullptr, rp,
+                               Gate{nullptr, 0.0}, RobustDev{});
     };
     // one pass of PyPose's inner `while self.last <= self.loss`: damped solve on buffer pb, then trial + linearisation at
     // the trial point into buffer 1-pb; every kernel is gated on `epoch`
@@ -59,10 +64,18 @@ static int run_chain_impl(double* nodes, double* vels, const double* poses, cons
         // the next linearisation if the trial is accepted
         if (reproj) enqueue_reproj_reduce(c.cur_n, w.dx, M, rp, RED[1 - c.pb], s, gate);
         double* rep_slot = report + 16 * ((long long)seq & 1);
-        hipLaunchKernelGGL(trial_lin_kernel, dim3(xcd_grid(nlb) + 1), dim3(LB_THREADS), LB_DYN_BYTES, s, c.cur_n, c.cur_v, w.dx, poses, drots,
-                           dtrans, dvels, dts, LIN[c.pb], N, c.tri_n, c.tri_v, w.part, w.state, w.flags, ticket, tr, rep_slot, seq,
-                           reproj ? RED[c.pb] : (const double*)nullptr, reproj ? RED[1 - c.pb] : (const double*)nullptr, rp, W,
-                           LIN[1 - c.pb], HD[1 - c.pb], HO[1 - c.pb], RH[1 - c.pb], gate);
+        if (robust)
+            hipLaunchKernelGGL(trial_lin_kernel<true>, dim3(xcd_grid(nlb) + 1), dim3(LB_THREADS), LB_DYN_BYTES, s, c.cur_n, c.cur_v, w.dx,
+                               poses, drots, dtrans, dvels, dts, LIN[c.pb], N, c.tri_n, c.tri_v, w.part, w.state, w.flags, ticket, tr,
+                               rep_slot, seq, reproj ? RED[c.pb] : (const double*)nullptr,
+                               reproj ? RED[1 - c.pb] : (const double*)nullptr, rp, W, LIN[1 - c.pb], HD[1 - c.pb], HO[1 - c.pb],
+                               RH[1 - c.pb], gate, (int*)nullptr, *robust);
+        else
+            hipLaunchKernelGGL(trial_lin_kernel<false>, dim3(xcd_grid(nlb) + 1), dim3(LB_THREADS), LB_DYN_BYTES, s, c.cur_n, c.cur_v, w.dx,
+                               poses, drots, dtrans, dvels, dts, LIN[c.pb], N, c.tri_n, c.tri_v, w.part, w.state, w.flags, ticket, tr,
+                               rep_slot, seq, reproj ? RED[c.pb] : (const double*)nullptr,
+                               reproj ? RED[1 - c.pb] : (const double*)nullptr, rp, W, LIN[1 - c.pb], HD[1 - c.pb], HO[1 - c.pb],
+                               RH[1 - c.pb], gate, (int*)nullptr, RobustDev{});
         ISLAM_LAUNCH_CHECK();
         return ISLAM_OK;
     };
@@ -73,8 +86,8 @@ static int run_chain_impl(double* nodes, double* vels, const double* poses, cons
     double epoch = 1.0;
     // ---- the fused loop (default): trial t, the linearisation at its trial point and the level-0 elimination of solve t+1 in
     // ONE launch (trial_elim_kernel), under a speculated damping the deciding workgroup validates.  Plans it does not cover
-    // (one-sided levels, segments longer than FZ_MAXM, a single level), the reprojection factor and ISLAM_PVGO_NO_FUSE=1 take
-    // the launch-per-stage loop below.
+    // (one-sided levels, segments longer than FZ_MAXM, a single level), the reprojection factor, robust kernels and
+    // ISLAM_PVGO_NO_FUSE=1 take the launch-per-stage loop below.
     SolvePlan sp;
     plan_levels(N, prm->seg_len, sp, solve_twisted());
     const bool no_fuse = [] { const char* e = std::getenv("ISLAM_PVGO_NO_FUSE"); return e && e[0] == '1'; }();      // (read per call: A/B tests)
@@ -86,7 +99,7 @@ static int run_chain_impl(double* nodes, double* vels, const double* poses, cons
     // (small graphs -- the reference's own per-batch problem is 9 nodes, run_kitti.sh -- stay on the launch-per-stage loop: its launches
     // are cheaper than the fused kernel's fixed cost and a rejected trial costs no mis-speculated chain.  Measured per run_pvgo, fused /
     // launch-per-stage: N = 9 (18 trials) 1059 / 723 us, N = 65 206 / 190 us, N = 129 203 / 236 us, N = 513 443 / 508 us.)
-    const bool fused = !no_fuse && !reproj && N > 96 && sp.twisted && sp.nl >= 2 && sp.top == sp.nl - 1 && sp.lv[0].m <= FZ_MAXM &&
+    const bool fused = !no_fuse && !reproj && !robust && N > 96 && sp.twisted && sp.nl >= 2 && sp.top == sp.nl - 1 && sp.lv[0].m <= FZ_MAXM &&
                        prm->reject < STATE_DOUBLES - STATE_HIST - 1 && (sp.lv[0].P + fz_nwg - 1) / fz_nwg <= FZ_S;
     if (fused) {
         static bool fz_attr_set[64] = {};                        // per device: the attribute lives in the device's code object
@@ -131,10 +144,10 @@ static int run_chain_impl(double* nodes, double* vels, const double* poses, cons
                     hipLaunchKernelGGL(control_begin_kernel, dim3(1), dim3(64), 0, s, w.loss_part, nlb, w.state, w.flags);
                     begin_pending = false;
                 }
-                hipLaunchKernelGGL(trial_lin_kernel, dim3(xcd_grid(nlb) + 1), dim3(LB_THREADS), LB_DYN_BYTES, s, c.cur_n, c.cur_v, w.dx, poses,
-                                   drots, dtrans, dvels, dts, LIN[c.pb], N, c.tri_n, c.tri_v, w.part, w.state, w.flags, ticket, tr, rep_slot,
-                                   seq, (const double*)nullptr, (const double*)nullptr, rp, W, (double*)nullptr, (double*)nullptr,
-                                   (double*)nullptr, (double*)nullptr, gate, eprev);
+                hipLaunchKernelGGL(trial_lin_kernel<false>, dim3(xcd_grid(nlb) + 1), dim3(LB_THREADS), LB_DYN_BYTES, s, c.cur_n, c.cur_v, w.dx,
+                                   poses, drots, dtrans, dvels, dts, LIN[c.pb], N, c.tri_n, c.tri_v, w.part, w.state, w.flags, ticket, tr,
+                                   rep_slot, seq, (const double*)nullptr, (const double*)nullptr, rp, W, (double*)nullptr, (double*)nullptr,
+                                   (double*)nullptr, (double*)nullptr, gate, eprev, RobustDev{});
                 ISLAM_LAUNCH_CHECK();
                 return ISLAM_OK;
             }
@@ -242,7 +255,7 @@ static int run_chain_impl(double* nodes, double* vels, const double* poses, cons
     // (one wave eliminates the window's nodes one after the other, ~2 us each: beyond a couple of dozen nodes the level tree of the
     // launch-per-stage loop is faster -- N = 65 takes 190 us per run there)
     constexpr int SMALL_MAX_N = 16;
-    if (!no_small && !reproj && N <= SMALL_MAX_N) {
+    if (!no_small && !reproj && !robust && N <= SMALL_MAX_N) {
         constexpr int SMALL_LDS = LB_DYN_BYTES + 2 * LDS_PER_WAVE * (int)sizeof(double);
         static bool small_attr_set[64] = {};
         int dev_i = 0;

@@ -520,8 +520,8 @@ int linbuild_gated(const double* nodes, const double* vels, const double* poses,
     if (reproj && (rc = reproj_dev_local(reproj, link0, rp)) != ISLAM_OK) return rc;
     const LinWeights W{prm->w[0], prm->w[1], prm->w[2], prm->w[3], prm->vmin, prm->vmax};
     const int nlb = (N + LB_NODES - 1) / LB_NODES;
-    hipLaunchKernelGGL(linbuild_kernel, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, nodes, vels, poses, drots, dtrans, dvels, dts,
-                       N, W, lin, loss_part, Hd, Ho, rhs, reproj ? red : (const double*)nullptr, rp, gate);
+    hipLaunchKernelGGL(linbuild_kernel<false>, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, nodes, vels, poses, drots, dtrans, dvels,
+                       dts, N, W, lin, loss_part, Hd, Ho, rhs, reproj ? red : (const double*)nullptr, rp, gate, RobustDev{});
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

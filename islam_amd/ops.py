@@ -839,9 +839,12 @@ def pvgo_reproj_reduce(nodes, reproj, dx=None):
     return red
 
 
-def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, workspace=None, trace_cap=0, reproj=None):
-    """In-place LM on float64 device tensors.  Returns (PvgoResult, trace ndarray (trials,3) or None)."""
+def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, workspace=None, trace_cap=0, reproj=None, robust=None):
+    """In-place LM on float64 device tensors.  Returns (PvgoResult, trace ndarray (trials,3) or None).
+    robust: islam_amd.robust.RobustSpec (or None) -- islam_pvgo_run_chain_robust; not combinable with ``reproj``."""
     require_cuda(nodes, vels, poses, drots, dtrans, dvels, dts)
+    if robust is not None and reproj is not None:
+        raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
     for t in (nodes, vels, poses, drots, dtrans, dvels, dts):
         assert t.dtype == torch.float64 and t.is_contiguous()
     N = nodes.shape[0]
@@ -853,10 +856,15 @@ def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, worksp
     res = _lib.PvgoResult()
     trace = np.zeros((trace_cap, 3), dtype=np.float64) if trace_cap > 0 else None
     tp = trace.ctypes.data_as(c_void_p) if trace is not None else c_void_p(0)
-    check(lib().islam_pvgo_run_chain_reproj(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
-                                            ctypes.byref(params), ctypes.byref(reproj) if reproj is not None else None,
-                                            ptr(ws), c_size_t(nbytes), ctypes.byref(res), tp, trace_cap,
-                                            stream_ptr(nodes.device)))
+    if robust is not None:
+        check(lib().islam_pvgo_run_chain_robust(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
+                                                ctypes.byref(params), ctypes.byref(robust.struct()), ptr(ws), c_size_t(nbytes),
+                                                ctypes.byref(res), tp, trace_cap, stream_ptr(nodes.device)))
+    else:
+        check(lib().islam_pvgo_run_chain_reproj(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
+                                                ctypes.byref(params), ctypes.byref(reproj) if reproj is not None else None,
+                                                ptr(ws), c_size_t(nbytes), ctypes.byref(res), tp, trace_cap,
+                                                stream_ptr(nodes.device)))
     if trace is not None:
         trace = trace[:min(res.trials, trace_cap)]
     return res, trace
@@ -872,15 +880,35 @@ def pvgo_linearize(nodes, vels, poses, drots, dtrans, dvels, dts):
     return lin, part
 
 
-def pvgo_build_normal(lin, dts, N, w4, vmin=1e-4, vmax=1e32):
+def pvgo_build_normal(lin, dts, N, w4, vmin=1e-4, vmax=1e32, c_imu=None):
+    """c_imu (3, N-1): robust multipliers of the velocity, rotation and translation-velocity factors (islam_pvgo_build_normal_scaled)."""
     dev = lin.device
     Hd = torch.zeros((N, 9, 9), dtype=torch.float64, device=dev)
     Ho = torch.zeros((N, 9, 9), dtype=torch.float64, device=dev)
     rhs = torch.zeros((N, 9), dtype=torch.float64, device=dev)
     w = (c_double * 4)(*[float(x) for x in w4])
+    if c_imu is not None:
+        assert c_imu.shape == (3, N - 1) and c_imu.dtype == torch.float64 and c_imu.is_contiguous()
+        check(lib().islam_pvgo_build_normal_scaled(ptr(lin), ptr(dts), N, w, ptr(c_imu), c_double(vmin), c_double(vmax), ptr(Hd),
+                                                   ptr(Ho), ptr(rhs), stream_ptr(dev)))
+        return Hd, Ho, rhs
     check(lib().islam_pvgo_build_normal(ptr(lin), ptr(dts), N, w, c_double(vmin), c_double(vmax), ptr(Hd), ptr(Ho),
                                         ptr(rhs), stream_ptr(dev)))
     return Hd, Ho, rhs
+
+
+def pvgo_robust_weights(vo, lin, robust, with_weights=True):
+    """Robust multipliers and loss of a general-topology linearisation (islam_pvgo_robust_weights): vo (24,E) of
+    islam_pvgo_linearize_edges, lin (42,M) of islam_pvgo_linearize, robust a RobustSpec.  Returns (c_vo (E,), c_imu (3,M), rho)
+    with rho the device scalar sum of rho over every factor (c_vo, c_imu None when with_weights=False)."""
+    require_cuda(vo, lin)
+    E, M, dev = vo.shape[1], lin.shape[1], vo.device
+    c_vo = torch.empty((E,), dtype=torch.float64, device=dev) if with_weights else None
+    c_imu = torch.empty((3, M), dtype=torch.float64, device=dev) if with_weights else None
+    part = torch.empty(((max(E, M) + 63) // 64,), dtype=torch.float64, device=dev)
+    check(lib().islam_pvgo_robust_weights(ptr(vo), E, ptr(lin), M, ctypes.byref(robust.struct()), ptr(c_vo), ptr(c_imu), ptr(part),
+                                          stream_ptr(dev)))
+    return c_vo, c_imu, part.sum()
 
 
 def pvgo_solve_chain(Hd, Ho, rhs, damping, seg_len=(0, 0), workspace=None):

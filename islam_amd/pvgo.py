@@ -9,6 +9,8 @@ What runs where:
     reference release).
 The information matrices of pvgo.py:125-143 are scalar multiples of the identity; they enter as four scalars (five with
 the optional sparse reprojection factor ``reproj``, islam_amd/dense_ba.py).
+``kernel`` (islam_amd.robust.Huber / Cauchy, one for all four factor groups or a sequence of four) puts robust kernels on the LM,
+like PyPose's ``pp.optim.LM(kernel=...)``; None keeps the plain least-squares loop.
 """
 import numpy as np
 import torch
@@ -96,10 +98,18 @@ def pvgo_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvel
 
 def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels,
              device='cuda:0', radius=1e4, loss_weight=(1, 1, 1, 1), reproj=None, target='vo', seg_len=(0, 0),
-             return_info=False, general_solver='auto', marginals=False):
+             return_info=False, general_solver='auto', marginals=False, kernel=None):
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError("islam_amd.run_pvgo runs on the MI355X only (device=%r); there is no CPU fallback" % (device,))
+    robust = None
+    if kernel is not None:
+        from .robust import parse_kernel
+        robust = parse_kernel(kernel)
+        if reproj is not None:
+            raise NotImplementedError('run_pvgo: robust kernels on the reprojection factor (kernel with reproj) are not implemented')
+        if marginals:
+            raise NotImplementedError('run_pvgo: marginals under a robust kernel (kernel with marginals=True) are not implemented')
     N = len(init_nodes)
     chain = _is_canonical_chain(links, N)
     if marginals and not chain:
@@ -116,7 +126,7 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
 
     if chain:            # the topology train.py produces: block-tridiagonal fast path, whole LM loop in one library call
         prm = ops.pvgo_default_params(loss_weight, radius=radius, seg_len=seg_len)
-        res, _ = ops.pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts64, prm, reproj=rp)
+        res, _ = ops.pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts64, prm, reproj=rp, robust=robust)
     else:                # loop closures / arbitrary links: dense formulation on the device (islam_amd/pvgo_dense.py)
         from .pvgo_dense import off_band_edges, run_lm_band_pcg, run_lm_dense
         k_off = len(off_band_edges(np.asarray(edges.cpu())))
@@ -124,12 +134,14 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
         if how == 'auto':        # a long chain with a few loop closures: block-tridiagonal solver + low-rank correction (PCG)
             how = 'band_pcg' if (N > 512 and k_off <= 64) else 'dense'
         if how == 'band_pcg':
-            nodes, vels, res = run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp)
+            nodes, vels, res = run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp,
+                                               kernel=robust)
         elif how == 'dense':
             if N > 12000:
                 raise UnsupportedGraphError('dense general-topology path is sized for N <= 12000 nodes, (9N)^2 doubles (got %d '
                                             'nodes, %d off-band edges; general_solver="band_pcg" has no such limit)' % (N, k_off))
-            nodes, vels, res = run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp)
+            nodes, vels, res = run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp,
+                                            kernel=robust)
         else:
             raise ValueError("general_solver must be 'auto', 'dense' or 'band_pcg'")
 

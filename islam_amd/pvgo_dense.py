@@ -17,7 +17,11 @@ couple consecutive nodes and a VO edge (i, j) adds S = w J^T J to the diagonal b
   A = B + R,  B = block-tridiagonal (all diagonal blocks, the couplings |i-j| = 1),  R = the off-band blocks of the k long edges,
 B is positive definite on its own, rank(R) <= 12 k, and conjugate gradients preconditioned with B^-1 -- the block-tridiagonal
 solver of the chain path, islam_pvgo_solve_chain, ~60 us per application at N = 5001 -- reaches the solution of the SAME
-normal equations in at most 12 k + 1 iterations.  Same LM control, same trial / trust-region evaluation; memory O(N + k)."""
+normal equations in at most 12 k + 1 iterations.  Same LM control, same trial / trust-region evaluation; memory O(N + k).
+
+Robust kernels (``kernel``, an islam_amd.robust.RobustSpec): islam_pvgo_robust_weights gives the multiplier
+c = rho'(s) of every VO edge and IMU-side factor and the loss sum rho(s); the scaled assembly entry points and the trust-region
+term apply c per factor.  Both solvers use the same multipliers and the same loss."""
 import numpy as np
 import torch
 
@@ -51,8 +55,9 @@ def _node_adjacency(edges_host, N):
     return np.cumsum(ptr_), order.astype(np.int64)
 
 
-def _quality_term(vo, lin, edges, dts, D):
-    """(J D)^T (2 R + J D) with the unweighted J, R of the linearisation point, factor by factor."""
+def _quality_term(vo, lin, edges, dts, D, c_vo=None, c_imu=None):
+    """(J D)^T (2 R + J D) with the unweighted J, R of the linearisation point, factor by factor (each factor's term scaled by its
+    robust multiplier when c_vo (E,), c_imu (3,M) are given)."""
     D6, Dv = D[:, :6], D[:, 6:]
     E = edges.shape[0]
     dp = D6[edges[:, 1]] - D6[edges[:, 0]]
@@ -69,6 +74,10 @@ def _quality_term(vo, lin, edges, dts, D):
     j4 = dc[:, :3] - dts[:, None] * Dv[:-1]
     R0, R1 = vo[0:3].t(), vo[3:6].t()
     R2, R3, R4 = lin[36:39].t(), lin[24:27].t(), lin[39:42].t()
+    if c_vo is not None:
+        t = lambda j, r: (j * (2 * r + j)).sum(1)
+        return (c_vo * (t(j0, R0) + t(j1, R1))).sum() + (c_imu[0] * t(j2, R2)).sum() + (c_imu[1] * t(j3, R3)).sum() + \
+            (c_imu[2] * t(j4, R4)).sum()
     q = 0.0
     for j, r in ((j0, R0), (j1, R1), (j2, R2), (j3, R3), (j4, R4)):
         q = q + (j * (2 * r + j)).sum()
@@ -121,9 +130,11 @@ class _ReprojTerms:
 
 
 def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
-                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None):
-    """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None.  Returns (nodes, vels, info dict)."""
+                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None):
+    """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None.
+    Returns (nodes, vels, info dict)."""
     N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
+    _check_kernel(kernel, reproj)
     if E != M:
         raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, M))
     dev = nodes.device
@@ -139,14 +150,21 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
     while ctl.continual:
         vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
         rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
+        c_vo = c_imu = None
+        if kernel is not None:
+            c_vo, c_imu, rho = ops.pvgo_robust_weights(vo, lin, kernel)
         if not ctl.has_loss:
-            ctl.set_initial_loss(float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
+            ctl.set_initial_loss(float(rho) if kernel is not None else float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
         ctl.begin_step()
-        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP)     # IMU factors
+        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
-        check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(edges), ptr(nptr), ptr(nadj),
-                                              c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
+        if kernel is not None:
+            check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), ptr(edges), ptr(nptr), ptr(nadj),
+                                                         c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
+        else:
+            check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(edges), ptr(nptr), ptr(nadj),
+                                                  c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
         d = A.diagonal().clamp(vmin, vmax).clone()                    # A.diagonal().clamp_(min, max)
         while True:
             d = d + d * ctl.damping                                   # cumulative, like A.diagonal().add_(...)
@@ -161,7 +179,7 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
             del L
             nt, vt = ops.pvgo_retract(nodes, vels, D, 1.0)
             vo_t, lin_t = _linearize(nt, vt, edges, poses, drots, dtrans, dvels, dts, dummy)
-            st, qt = _loss(vo_t, lin_t), _quality_term(vo, lin, edges, dts, D)
+            st, qt = _trial_loss(vo_t, lin_t, kernel), _quality_term(vo, lin, edges, dts, D, c_vo, c_imu)
             if rpt is not None:
                 st, qt = st + _ReprojTerms(nodes, reproj, D).rr, qt + rpt.quality(D)
             s, q = torch.stack([st, qt]).tolist()
@@ -172,9 +190,20 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
     return nodes, vels, dict(steps=ctl.steps, trials=trials, loss=ctl.loss, trace=ctl.trace)
 
 
+def _check_kernel(kernel, reproj):
+    if kernel is not None and reproj is not None:
+        raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
+
+
+def _trial_loss(vo, lin, kernel):
+    """The LM loss at a trial point: the plain sum of squares, or sum rho under a robust kernel (islam_pvgo_robust_weights)."""
+    return _loss(vo, lin) if kernel is None else ops.pvgo_robust_weights(vo, lin, kernel, with_weights=False)[2]
+
+
 # ------------------------------------------------------------------------------------------ band + low-rank (PCG)
-def _edge_blocks(vo, w0):
-    """Per VO edge: S = w0 J^T J (E,6,6) and g = w0 J^T r (E,6), J = [[G, C], [0, G]] (edge_normal in csrc/pvgo.hip)."""
+def _edge_blocks(vo, w0, c_vo=None):
+    """Per VO edge: S = w0 J^T J (E,6,6) and g = w0 J^T r (E,6), J = [[G, C], [0, G]] (edge_normal in csrc/pvgo.hip); with robust
+    multipliers c_vo (E,) the weight of edge e is w0 c_vo[e]."""
     E = vo.shape[1]
     G = vo[6:15].t().reshape(E, 3, 3)
     C = vo[15:24].t().reshape(E, 3, 3)
@@ -182,6 +211,9 @@ def _edge_blocks(vo, w0):
     J[:, :3, :3], J[:, :3, 3:], J[:, 3:, 3:] = G, C, G
     r = vo[0:6].t()
     Jt = J.transpose(1, 2)
+    if c_vo is not None:
+        we = w0 * c_vo
+        return we[:, None, None] * (Jt @ J), we[:, None] * (Jt @ r[:, :, None])[:, :, 0]
     return w0 * (Jt @ J), w0 * (Jt @ r[:, :, None])[:, :, 0]
 
 
@@ -194,12 +226,12 @@ def off_band_edges(edges_host):
 class _BandSystem:
     """A = B + R of one linearisation: B as (Hd, Ho) of the chain solver, R as the list of off-band 6x6 blocks."""
 
-    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt=None):
+    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt=None, c_vo=None, c_imu=None):
         dev = vo.device
-        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP)     # IMU factors
+        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
-        S, g = _edge_blocks(vo, w[0])
+        S, g = _edge_blocks(vo, w[0], c_vo)
         E = S.shape[0]
         i, j = edges[:, 0], edges[:, 1]
         Sp = torch.zeros((E, 9, 9), dtype=S.dtype, device=dev)
@@ -272,11 +304,12 @@ def _pcg(sysm, ws, rtol=1e-13, check_every=6):
 
 
 def run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
-                    decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None):
+                    decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None):
     """The LM of run_lm_dense on the band + low-rank form of the same normal equations.  In: float64 contiguous device
     tensors.  Returns (nodes, vels, info dict)."""
     from ._lib import IslamHipError
     N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
+    _check_kernel(kernel, reproj)
     if E != M:
         raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, M))
     dev = nodes.device
@@ -295,10 +328,13 @@ def run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_w
     while ctl.continual:
         vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
         rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
+        c_vo = c_imu = None
+        if kernel is not None:
+            c_vo, c_imu, rho = ops.pvgo_robust_weights(vo, lin, kernel)
         if not ctl.has_loss:
-            ctl.set_initial_loss(float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
+            ctl.set_initial_loss(float(rho) if kernel is not None else float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
         ctl.begin_step()
-        sysm = _BandSystem(vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt)
+        sysm = _BandSystem(vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt, c_vo, c_imu)
         d = sysm.diag0
         while True:
             d = d + d * ctl.damping                                   # cumulative, like A.diagonal().add_(...)
@@ -320,7 +356,7 @@ def run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_w
                 break
             nt, vt = ops.pvgo_retract(nodes, vels, D.contiguous(), 1.0)
             vo_t, lin_t = _linearize(nt, vt, edges, poses, drots, dtrans, dvels, dts, dummy)
-            st, qt = _loss(vo_t, lin_t), _quality_term(vo, lin, edges, dts, D)
+            st, qt = _trial_loss(vo_t, lin_t, kernel), _quality_term(vo, lin, edges, dts, D, c_vo, c_imu)
             if rpt is not None:
                 st, qt = st + _ReprojTerms(nodes, reproj, D.contiguous()).rr, qt + rpt.quality(D)
             s, q = torch.stack([st, qt]).tolist()
