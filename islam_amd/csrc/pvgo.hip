@@ -31,6 +31,9 @@
 //      bumps on any verdict other than "accepted, continue") and only polls the verdicts.
 // linearize_kernel / build_normal_kernel / trial_kernel / bt_top_kernel / bt_backsub_kernel are the
 // stage-level versions behind the islam_pvgo_* entry points the sharded driver and the tests call.
+//
+// Layout of this translation unit: device parts, host helpers and planner, the loop drivers (single GPU, then sharded), ONE
+// extern "C" block with every entry point, the marginal covariances.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +41,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "common.h"
 #include "lie_dev.h"
@@ -101,8 +105,41 @@ __device__ __forceinline__ double ld_coherent(const double* p) {
 #include "pvgo_solver.inl"   // partitioned / twisted block-tridiagonal LDL^T
 #include "pvgo_lm_kernels.inl"   // device side of the LM loop
 #include "pvgo_general.inl"   // control kernels, retraction, arbitrary-topology assembly, vo_loss / imu_loss forward + backward, align_to
-#include "pvgo_host.inl"   // host side
 }  // namespace
+
+// error path of a run (abandon_run): an epoch no enqueued kernel carries turns everything still queued into no-ops
+__global__ void close_gate_kernel(double* __restrict__ st) {
+    if (threadIdx.x == 0) st[14] = -1.0;
+}
+
+namespace {
+#include "pvgo_host.inl"   // host side: planner, workspace, launchers, what the loop drivers and the entry points share
+#include "pvgo_lm_loop.inl"   // the single-GPU LM loop: run_chain_impl and its three drivers
+
+// validation, workspace and the error path shared by the islam_pvgo_run_chain_* entry points
+int run_chain_entry(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                    const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                    const islam_pvgo_reproj* reproj, const islam_pvgo_robust* robust, void* workspace,
+                    size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
+    if (N < 2) return fail(ISLAM_EARG, "islam_pvgo_run_chain: N=%d < 2", N);
+    if (!prm || !result) return fail(ISLAM_EARG, "islam_pvgo_run_chain: null params/result");
+    int rc;
+    ReprojDev rp{};
+    if (reproj && (rc = reproj_dev(reproj, rp)) != ISLAM_OK) return rc;
+    RobustDev rb{};
+    bool robust_on = false;
+    if (robust && (rc = robust_dev(robust, rb, &robust_on)) != ISLAM_OK) return rc;
+    Workspace w;
+    rc = workspace_or_fail("islam_pvgo_run_chain: workspace %zu < %zu bytes", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
+    hipStream_t s = as_stream(stream);
+    rc = run_chain_impl(nodes, vels, ChainData{poses, drots, dtrans, dvels, dts, N}, prm, reproj, rp, w, s, result, trace, trace_cap,
+                        robust_on ? &rb : nullptr);
+    return rc == ISLAM_OK ? rc : abandon_run(w.state, s, rc);
+}
+}  // namespace
+
+#include "pvgo_sharded.inl"   // the sharded LM loop: ranges of a rank, gated stages, run_chain_sharded_fused
 
 extern "C" {
 
@@ -156,14 +193,13 @@ int islam_pvgo_build_normal_scaled(const double* lin, const double* dts, int N, 
 int islam_pvgo_solve_chain(double* Hd, const double* Ho, const double* rhs, double damping, int N, const int seg_len[2],
                            void* workspace, size_t workspace_bytes, double* dx, void* stream) {
     if (N < 1) return fail(ISLAM_EARG, "islam_pvgo_solve_chain: N=%d < 1", N);
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N))
-        return fail(ISLAM_EARG, "islam_pvgo_solve_chain: workspace %zu < %zu bytes", workspace_bytes,
-                    islam_pvgo_workspace_bytes(N));
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
+    Workspace w;
+    int rc = workspace_or_fail("islam_pvgo_solve_chain: workspace %zu < %zu bytes", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
     hipStream_t s = as_stream(stream);
     ISLAM_HIP_CHECK(hipMemsetAsync(w.flags, 0, 4 * sizeof(double), s));
     ISLAM_HIP_CHECK(hipMemsetAsync(w.ready, 0, w.ready_bytes, s));
-    int rc = enqueue_solve(w, Hd, Ho, rhs, nullptr, damping, N, seg_len, dx, s);
+    rc = enqueue_solve(w, Hd, Ho, rhs, nullptr, damping, N, seg_len, dx, s);
     if (rc != ISLAM_OK) return rc;
     int flag = 0;
     ISLAM_HIP_CHECK(hipMemcpyAsync(&flag, w.flags, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -178,10 +214,9 @@ int islam_pvgo_solve_chain(double* Hd, const double* Ho, const double* rhs, doub
 int islam_pvgo_solve_chain_enqueue(double* Hd, const double* Ho, const double* rhs, double damping, int N, const int seg_len[2],
                                    void* workspace, size_t workspace_bytes, double* dx, void* stream) {
     if (N < 1) return fail(ISLAM_EARG, "islam_pvgo_solve_chain_enqueue: N=%d < 1", N);
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N))
-        return fail(ISLAM_EARG, "islam_pvgo_solve_chain_enqueue: workspace %zu < %zu bytes", workspace_bytes,
-                    islam_pvgo_workspace_bytes(N));
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
+    Workspace w;
+    const int rc = workspace_or_fail("islam_pvgo_solve_chain_enqueue: workspace %zu < %zu bytes", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
     return enqueue_solve(w, Hd, Ho, rhs, nullptr, damping, N, seg_len, dx, as_stream(stream));
 }
 
@@ -207,27 +242,23 @@ int islam_pvgo_solve_chain_timed(double* Hd, const double* Ho, const double* rhs
                                  const int seg_len[2], void* workspace, size_t workspace_bytes, double* dx, float* ms,
                                  int* plan_out, int* nlaunch, void* stream) {
     if (N < 1) return fail(ISLAM_EARG, "islam_pvgo_solve_chain_timed: N=%d < 1", N);
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N)) return fail(ISLAM_EARG, "islam_pvgo_solve_chain_timed: workspace too small");
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
+    Workspace w;
+    int rc = workspace_or_fail("islam_pvgo_solve_chain_timed: workspace too small", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
     hipStream_t s = as_stream(stream);
     ISLAM_HIP_CHECK(hipMemsetAsync(w.ready, 0, w.ready_bytes, s));
     hipEvent_t evs[2 * MAXL + 2];
     for (auto& e : evs) ISLAM_HIP_CHECK(hipEventCreate(&e));
     ISLAM_HIP_CHECK(hipMemsetAsync(w.flags, 0, 4 * sizeof(double), s));
     int ne = 0;
-    int rc = enqueue_solve(w, Hd, Ho, rhs, nullptr, damping, N, seg_len, dx, s, evs, &ne);
+    rc = enqueue_solve(w, Hd, Ho, rhs, nullptr, damping, N, seg_len, dx, s, evs, &ne);
     if (rc != ISLAM_OK) return rc;
     ISLAM_HIP_CHECK(hipStreamSynchronize(s));
     for (int i = 0; i + 1 < ne; ++i) ISLAM_HIP_CHECK(hipEventElapsedTime(&ms[i], evs[i], evs[i + 1]));
     for (auto& e : evs) (void)hipEventDestroy(e);
     SolvePlan sp;
-    const int nl = plan_levels(N, seg_len, sp, solve_twisted());
-    for (int l = 0; l < MAXL; ++l) {
-        plan_out[3 * l] = l < nl ? sp.lv[l].n : 0;
-        plan_out[3 * l + 1] = l < nl ? sp.lv[l].m : 0;
-        plan_out[3 * l + 2] = l < nl ? sp.lv[l].P : 0;
-    }
-    plan_out[3 * MAXL] = sp.top;
+    plan_levels(N, seg_len, sp, solve_twisted());
+    write_plan(sp, plan_out);
     *nlaunch = ne - 1;
     return ISLAM_OK;
 }
@@ -237,10 +268,11 @@ int islam_pvgo_solve_chain_timed(double* Hd, const double* Ho, const double* rhs
 int islam_pvgo_eliminate_level0(double* Hd, const double* Ho, const double* rhs, double damping, int N, const int seg_len[2],
                                 void* workspace, size_t workspace_bytes, void* stream) {
     if (N < 1) return fail(ISLAM_EARG, "islam_pvgo_eliminate_level0: N=%d < 1", N);
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N)) return fail(ISLAM_EARG, "islam_pvgo_eliminate_level0: workspace too small");
+    Workspace w;
+    const int rc = workspace_or_fail("islam_pvgo_eliminate_level0: workspace too small", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
     SolvePlan sp;
     if (plan_levels(N, seg_len, sp, solve_twisted()) < 2) return fail(ISLAM_EARG, "islam_pvgo_eliminate_level0: single-level problem");
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
     LevelSrc src{};
     src.level0 = 1; src.Hd = Hd; src.Ho = Ho; src.rhs0 = rhs; src.state = nullptr; src.damping_override = damping;
     launch_eliminate(sp.lv[0], sp.twisted != 0, src, level_dst(w.lv[0], w.lv[0].x), w.flags, as_stream(stream), Gate{nullptr, 0.0});
@@ -248,73 +280,12 @@ int islam_pvgo_eliminate_level0(double* Hd, const double* Ho, const double* rhs,
     return ISLAM_OK;
 }
 
-// ---- sharded (multi-GPU) building blocks
-// The sharded entry points plan like the single-GPU solve (twisted elimination wherever every level qualifies).
-static int shard_plan(int N, const int seg_len[2], SolvePlan& sp) { return plan_levels(N, seg_len, sp, solve_twisted()); }
-
 int islam_pvgo_plan(int N, const int seg_len[2], int* plan9) {
     if (N < 1) return fail(ISLAM_EARG, "islam_pvgo_plan: N=%d < 1", N);
     SolvePlan sp;
     const int nl = shard_plan(N, seg_len, sp);
-    for (int l = 0; l < MAXL; ++l) {
-        plan9[3 * l] = l < nl ? sp.lv[l].n : 0;
-        plan9[3 * l + 1] = l < nl ? sp.lv[l].m : 0;
-        plan9[3 * l + 2] = l < nl ? sp.lv[l].P : 0;
-    }
-    plan9[3 * MAXL] = sp.top;
+    write_plan(sp, plan9);
     return nl;
-}
-
-static void products_view(double* base, int P, LevelBufs& b) {
-    b.Dsep = base; b.rsep = base + 81 * (size_t)P; b.cL = base + 90 * (size_t)P; b.cR = base + 171 * (size_t)P;
-    b.fill = base + 252 * (size_t)P; b.cgL = base + 333 * (size_t)P; b.cgR = base + 342 * (size_t)P;
-}
-
-// ---- sharding at a HIGHER level of the tree: the interface-only exchange of SURVEY section 8e.
-// A rank owns a contiguous range of the segments of the EXCHANGE level xl (the highest level below the root that still has
-// one segment per rank) and, below it, everything between the two outer separators of that range: at level l-1 the segments
-// whose separators are its level-l nodes.  Levels 0 .. xl are eliminated locally (every block a node needs comes from the
-// rank's own segments), only the products of level xl -- 351 doubles per segment, P_xl segments -- are summed over the
-// ranks, the few levels above are solved redundantly, and the back-substitution of levels xl .. 0 is local again.
-struct ShardRanges { int xl; int seg0[MAXL], nseg[MAXL]; };
-
-static int shard_ranges(const SolvePlan& sp, int world, int rank, ShardRanges& R) {
-    if (world < 1 || rank < 0 || rank >= world) return -1;
-    int xl = -1;
-    for (int l = 0; l < sp.nl - 1; ++l)
-        if (sp.lv[l].P >= world) xl = l;
-    if (xl < 0) return -1;
-    R.xl = xl;
-    const int P = sp.lv[xl].P;
-    const int s0 = (int)((long long)rank * P / world), s1 = (int)((long long)(rank + 1) * P / world);
-    for (int l = 0; l < MAXL; ++l) { R.seg0[l] = 0; R.nseg[l] = 0; }
-    R.seg0[xl] = s0;
-    R.nseg[xl] = s1 - s0;
-    for (int l = xl; l > 0; --l) {
-        const int m = sp.lv[l].m, n = sp.lv[l].n;
-        const int a = R.seg0[l] * (m + 1);                                                   // first owned node of level l
-        const int b = std::min(n - 1, (R.seg0[l] + R.nseg[l] - 1) * (m + 1) + m - 1);       // last one
-        R.seg0[l - 1] = a;                                                                    // segment a: right separator = node a
-        R.nseg[l - 1] = std::min(b + 1, sp.lv[l - 1].P - 1) - a + 1;                          // ... segment b+1: left separator = node b
-        // the last rank owns the chain to its end: when level l closes with a trailing separator (a node of the level above)
-        // the level-(l-1) segment beyond it still feeds that separator's block, which the rank's last segment composes
-        if (R.seg0[l] + R.nseg[l] == sp.lv[l].P) R.nseg[l - 1] = sp.lv[l - 1].P - a;
-    }
-    return 0;
-}
-
-// The block of an outer separator that a rank hands up (Dsep / rsep of the last segment of each of its levels) is composed
-// level by level as  own block - (Schur contribution of the segment on its left) - (that of the segment on its RIGHT); the
-// segment on the right belongs to the next rank.  The composition is additive, so the next rank subtracts its share -- the
-// left-separator contributions cL / cgL of its first segment of every level below xl -- from the same rows of the exchange
-// buffer, and the sum over the ranks is the complete block.
-struct OuterFix { const double* cL[MAXL]; const double* cgL[MAXL]; double* Dsep; double* rsep; int n; };
-__global__ void outer_block_kernel(OuterFix f, Gate gate) {
-    const int t = threadIdx.x;
-    if (t >= 90 || gate_closed(gate)) return;
-    double v = 0.0;
-    for (int i = 0; i < f.n; ++i) v += t < 81 ? f.cL[i][t] : f.cgL[i][t - 81];
-    if (t < 81) f.Dsep[t] = -v; else f.rsep[t - 81] = -v;       // a row of the PREVIOUS rank's segment: nothing else is written there locally
 }
 
 int islam_pvgo_shard_ranges(int N, const int seg_len[2], int world, int rank, int* out) {
@@ -328,84 +299,6 @@ int islam_pvgo_shard_ranges(int N, const int seg_len[2], int world, int rank, in
     for (int l = 0; l < MAXL; ++l) { out[2 + 2 * l] = R.seg0[l]; out[3 + 2 * l] = R.nseg[l]; }
     return ISLAM_OK;
 }
-
-static int reproj_dev(const islam_pvgo_reproj* r, ReprojDev& d) {
-    if (!r->points || !r->targets || r->K < 1) return fail(ISLAM_EARG, "islam_pvgo_reproj: null points/targets or K=%d < 1", r->K);
-    d.points = r->points; d.targets = r->targets; d.K = r->K;
-    d.fx = r->fx; d.fy = r->fy; d.cx = r->cx; d.cy = r->cy;
-    d.C = {{r->rgb2imu[0], r->rgb2imu[1], r->rgb2imu[2]}, {r->rgb2imu[3], r->rgb2imu[4], r->rgb2imu[5], r->rgb2imu[6]}};
-    d.weight = r->weight;
-    d.compat_first = r->compat_first_motion;
-    return ISLAM_OK;
-}
-
-// islam_pvgo_robust -> RobustDev; returns whether any group has a kernel in *active (NONE everywhere: the plain loop)
-static int robust_dev(const islam_pvgo_robust* r, RobustDev& d, bool* active = nullptr) {
-    bool any = false;
-    for (int g = 0; g < 4; ++g) {
-        const int k = r->kind[g];
-        if (k != ISLAM_ROBUST_NONE && k != ISLAM_ROBUST_HUBER && k != ISLAM_ROBUST_CAUCHY)
-            return fail(ISLAM_EARG, "islam_pvgo_robust: unknown kind %d for factor group %d", k, g);
-        if (k != ISLAM_ROBUST_NONE && !(r->delta[g] > 0.0 && std::isfinite(r->delta[g])))
-            return fail(ISLAM_EARG, "islam_pvgo_robust: delta %g of factor group %d is not a finite positive number", r->delta[g], g);
-        d.kind[g] = k;
-        d.delta[g] = k != ISLAM_ROBUST_NONE ? r->delta[g] : 1.0;
-        any = any || k != ISLAM_ROBUST_NONE;
-    }
-    if (active) *active = any;
-    return ISLAM_OK;
-}
-
-static void enqueue_reproj_reduce(const double* nodes, const double* dx, int M, const ReprojDev& rp, double* red, hipStream_t s,
-                                  Gate gate = Gate{nullptr, 0.0}) {
-    const int waves = std::min(4, std::max(1, (rp.K + 127) / 128));
-    hipLaunchKernelGGL(reproj_reduce_kernel, dim3(xcd_grid(M)), dim3(64 * waves), 64 * waves * (RP_NSUM + 1) * sizeof(double), s, nodes,
-                       dx, M, rp, red, gate);
-}
-
-// the factor as a rank of the sharded loop sees it: keypoints / targets of its local link 0 = global link `link0`; the frozen
-// first motion (pvgo.py:57) belongs to global link 0
-static int reproj_dev_local(const islam_pvgo_reproj* r, int link0, ReprojDev& d) {
-    const int rc = reproj_dev(r, d);
-    if (rc != ISLAM_OK) return rc;
-    d.points += (size_t)link0 * d.K * 3;
-    d.targets += (size_t)link0 * d.K * 2;
-    if (link0 != 0) d.compat_first = 0;
-    return ISLAM_OK;
-}
-
-static int device_cus() {
-    static int cus[64] = {};
-    int dev_i = 0;
-    if (hipGetDevice(&dev_i) != hipSuccess || dev_i < 0 || dev_i >= 64) return 0;
-    if (cus[dev_i] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_i) != hipSuccess) return 0;
-        cus[dev_i] = v;
-    }
-    return cus[dev_i];
-}
-
-// linbuild_kernel / trial_lin_kernel stage their node blocks in dynamic LDS above the default limit (once per device)
-static int ensure_linbuild_lds() {
-    static bool lb_attr_set[64] = {};                        // per device: the attribute lives in the device's code object
-    int dev_i = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev_i));
-    if (dev_i >= 0 && dev_i < 64 && !lb_attr_set[dev_i]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)linbuild_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_lin_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)linbuild_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_lin_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_DYN_BYTES));
-        lb_attr_set[dev_i] = true;
-    }
-    return ISLAM_OK;
-}
-
-}  // extern "C"
-
-#include "pvgo_sharded.inl"   // the sharded LM loop
-
-extern "C" {
 
 int islam_pvgo_shard_upsweep(double* Hd, const double* Ho, const double* rhs, double damping, int N, const int seg_len[2], int world,
                              int rank, int node0, void* workspace, size_t workspace_bytes, double* exchange, int* flags,
@@ -527,59 +420,9 @@ int islam_pvgo_reproj_reduce(const double* nodes, const double* dx, int N, const
 int islam_pvgo_run_chain(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
                          const double* dvels, const double* dts, int N, const islam_pvgo_params* prm, void* workspace,
                          size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
-    return islam_pvgo_run_chain_reproj(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, workspace,
-                                       workspace_bytes, result, trace, trace_cap, stream);
+    return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, nullptr, workspace, workspace_bytes, result,
+                           trace, trace_cap, stream);
 }
-
-}  // extern "C"
-
-// error path of the run: an epoch no enqueued kernel carries turns everything still queued into no-ops
-__global__ void close_gate_kernel(double* __restrict__ st) {
-    if (threadIdx.x == 0) st[14] = -1.0;
-}
-
-static int run_chain_impl(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
-                          const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
-                          const islam_pvgo_reproj* reproj, const ReprojDev& rp, Workspace& w, hipStream_t s,
-                          islam_pvgo_result* result, double* trace, int trace_cap, const RobustDev* robust = nullptr);
-
-// validation, workspace and the error path shared by the islam_pvgo_run_chain_* entry points
-static int run_chain_entry(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
-                           const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
-                           const islam_pvgo_reproj* reproj, const islam_pvgo_robust* robust, void* workspace,
-                           size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
-    if (N < 2) return fail(ISLAM_EARG, "islam_pvgo_run_chain: N=%d < 2", N);
-    if (!prm || !result) return fail(ISLAM_EARG, "islam_pvgo_run_chain: null params/result");
-    ReprojDev rp{};
-    if (reproj) {
-        int rc = reproj_dev(reproj, rp);
-        if (rc != ISLAM_OK) return rc;
-    }
-    RobustDev rb{};
-    bool robust_on = false;
-    if (robust) {
-        int rc = robust_dev(robust, rb, &robust_on);
-        if (rc != ISLAM_OK) return rc;
-    }
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N))
-        return fail(ISLAM_EARG, "islam_pvgo_run_chain: workspace %zu < %zu bytes", workspace_bytes,
-                    islam_pvgo_workspace_bytes(N));
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
-    hipStream_t s = as_stream(stream);
-    const int rc = run_chain_impl(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, reproj, rp, w, s, result, trace, trace_cap,
-                                  robust_on ? &rb : nullptr);
-    if (rc != ISLAM_OK) {
-        // A failed enqueue or status wait leaves epoch-gated kernels of the run-ahead chain queued: they would still write the pinned
-        // status block and the workspace the NEXT call reuses.  Close the gate and drain the stream before handing the error up (the
-        // message of the original failure is kept) -- the same rule as the sharded loop (pvgo_dist.hip).
-        hipLaunchKernelGGL(close_gate_kernel, dim3(1), dim3(64), 0, s, w.state);
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-
-extern "C" {
 
 int islam_pvgo_run_chain_reproj(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
                                 const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
@@ -598,12 +441,6 @@ int islam_pvgo_run_chain_robust(double* nodes, double* vels, const double* poses
                            trace, trace_cap, stream);
 }
 
-}  // extern "C"
-
-#include "pvgo_lm_loop.inl"   // run_chain_impl
-
-extern "C" {
-
 // Measurement hook (bench.py's roofline leg): the LM loop's dominant launch, trial_elim_kernel, exactly as islam_pvgo_run_chain
 // launches it in its steady state -- after one linearisation and one damped solve of the given problem (so that `dx` and the old
 // linearisation are real), `launches` back-to-back launches between ONE pair of HIP events on `stream`; *us_per_launch = their
@@ -613,48 +450,40 @@ int islam_pvgo_trial_elim_burst(const double* nodes, const double* vels, const d
                                 const double* dvels, const double* dts, int N, const islam_pvgo_params* prm, void* workspace,
                                 size_t workspace_bytes, int launches, float* us_per_launch, int* info, void* stream) {
     if (N < 2 || !prm || !us_per_launch || launches < 1) return fail(ISLAM_EARG, "islam_pvgo_trial_elim_burst: bad argument");
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N)) return fail(ISLAM_EARG, "islam_pvgo_trial_elim_burst: workspace too small");
+    Workspace w;
+    int rc = workspace_or_fail("islam_pvgo_trial_elim_burst: workspace too small", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
     SolvePlan sp;
     plan_levels(N, prm->seg_len, sp, solve_twisted());
+    // (unlike run_chain_impl: always 16 spare CUs, whatever ISLAM_FZ_SPARE says, and no lower bound on N -- the hook measures the
+    // launch wherever the kernel can run)
     const int fz_nwg = std::min(sp.lv[0].P, std::max(device_cus() - 16, 1));
-    if (!(sp.twisted && sp.nl >= 2 && sp.top == sp.nl - 1 && sp.lv[0].m <= FZ_MAXM && (sp.lv[0].P + fz_nwg - 1) / fz_nwg <= FZ_S))
+    if (!(sp.nl >= 2 && fused_plan_core(sp, sp.lv[0].P, fz_nwg)))
         return fail(ISLAM_EARG, "islam_pvgo_trial_elim_burst: the fused loop does not cover N=%d", N);
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
     hipStream_t s = as_stream(stream);
-    int rc = ensure_linbuild_lds();
-    if (rc != ISLAM_OK) return rc;
-    ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_elim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FZ_LDS_BYTES));
+    if ((rc = ensure_linbuild_lds()) != ISLAM_OK) return rc;
+    if ((rc = ensure_fused_lds()) != ISLAM_OK) return rc;
+    // (the kernel only reads the current iterate; no verdict block: nobody waits for these trials)
+    ChainRun r = chain_run(const_cast<double*>(nodes), const_cast<double*>(vels), ChainData{poses, drots, dtrans, dvels, dts, N}, prm, w, s);
+    r.fz_m = sp.lv[0].m; r.fz_P = sp.lv[0].P; r.fz_nwg = fz_nwg;
     ISLAM_HIP_CHECK(hipMemsetAsync(w.ready, 0, w.ready_bytes, s));
     hipLaunchKernelGGL(control_init_kernel, dim3(1), dim3(64), 0, s, w.state, w.flags, prm->radius, prm->down, (uint4*)nullptr, 0u);
-    const LinWeights W{prm->w[0], prm->w[1], prm->w[2], prm->w[3], prm->vmin, prm->vmax};
-    const int nlb = (N + LB_NODES - 1) / LB_NODES;
-    hipLaunchKernelGGL(linbuild_kernel<false>, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, nodes, vels, poses, drots, dtrans, dvels,
-                       dts, N, W, w.lin, w.loss_part, w.Hd, w.Ho, w.rhs, (const double*)nullptr, ReprojDev{}, Gate{nullptr, 0.0}, RobustDev{});
-    hipLaunchKernelGGL(control_begin_kernel, dim3(1), dim3(64), 0, s, w.loss_part, nlb, w.state, w.flags);
+    enqueue_linbuild(r, nodes, vels, 0, false);
+    hipLaunchKernelGGL(control_begin_kernel, dim3(1), dim3(64), 0, s, w.loss_part, r.nlb, w.state, w.flags);
     LevelSrc src{};
     src.level0 = 1; src.Hd = w.Hd; src.Ho = w.Ho; src.rhs0 = w.rhs; src.state = w.state; src.hist = 1;
     rc = enqueue_levels(w, sp, 0, src, nullptr, w.dx, w.flags, s, nullptr, nullptr);
     if (rc != ISLAM_OK) return rc;
-    FusedArgs fa{};
-    fa.nodes = nodes; fa.vels = vels; fa.dx = w.dx; fa.poses = poses; fa.drots = drots; fa.dtrans = dtrans; fa.dvels = dvels; fa.dts = dts;
-    fa.lin = w.lin; fa.N = N; fa.nodes_t = w.nodes_t; fa.vels_t = w.vels_t; fa.part = w.part; fa.st = w.state; fa.flags = w.flags;
-    fa.ticket = reinterpret_cast<unsigned*>(w.flags + 2);
-    fa.tr = TRParams{prm->high, prm->low, prm->up, prm->down, prm->factor, prm->rmin, prm->rmax, prm->reject, prm->max_steps, prm->patience,
-                     prm->decreasing};
-    fa.report = nullptr; fa.seq = 1.0; fa.W = W;
-    fa.lin_o = w.lin2; fa.Hd_o = w.Hd2; fa.Ho_o = w.Ho2; fa.rhs_o = w.rhs2;
-    fa.dst = level_dst(w.lv[0], w.dx);
-    fa.m = sp.lv[0].m; fa.P = sp.lv[0].P; fa.nwg = fz_nwg;
-    fa.eflag = w.flags + 4; fa.eflag_prev = w.flags + 6;
-    fa.Ms = N - 1;
+    const IterCfg c{0, r.nodes, r.vels, w.nodes_t, w.vels_t};
+    const FusedArgs fa = fused_args(r, c, FUSED_TRIAL_ELIM, 1.0, r.eflag_none());
     const Gate open{nullptr, 0.0};
-    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(trial_elim_kernel, dim3(xcd_grid(fz_nwg) + 1), dim3(FZ_THREADS), FZ_LDS_BYTES, s, fa, open);
+    for (int i = 0; i < 3; ++i) launch_fused(r, fa, open);
     hipEvent_t e0, e1;
     ISLAM_HIP_CHECK(hipEventCreate(&e0));
     ISLAM_HIP_CHECK(hipEventCreate(&e1));
     ISLAM_HIP_CHECK(hipStreamSynchronize(s));
     ISLAM_HIP_CHECK(hipEventRecord(e0, s));
-    for (int i = 0; i < launches; ++i) hipLaunchKernelGGL(trial_elim_kernel, dim3(xcd_grid(fz_nwg) + 1), dim3(FZ_THREADS), FZ_LDS_BYTES, s, fa, open);
+    for (int i = 0; i < launches; ++i) launch_fused(r, fa, open);
     ISLAM_HIP_CHECK(hipEventRecord(e1, s));
     ISLAM_HIP_CHECK(hipStreamSynchronize(s));
     float ms = 0.f;

@@ -189,6 +189,207 @@ int shard_of(int N, const int seg_len[2], int world, int rank, Shard& sh) {
 
 inline size_t a256(size_t n) { return align_up(n * sizeof(double)) / sizeof(double); }
 
+// One rank's run of the launch-per-stage sharded loop: what its stages share and the stages themselves.
+struct IterCfg { double *cur_n, *cur_v, *tri_n, *tri_v; };
+struct StagedRun {
+    const Reducer* red;
+    int world, rank, N;
+    const islam_pvgo_params* prm; const islam_pvgo_reproj* reproj;
+    void* workspace; size_t workspace_bytes;
+    hipStream_t s;
+    Shard sh;
+    int a, b, nloc, Mloc, n_own, first_local, nblk, nmsg;       // local rows [a, b] of the chain; n_own links are the rank's own
+    double *lin, *loss_part, *Hd, *Ho, *rhs, *dx, *nl, *nt, *vl, *vt, *part, *msg, *full, *ex_own, *ex, *state, *rp_lin, *rp_tri;
+    int* flags;
+    const double *lp, *lr, *ltr, *lv, *ldt;                     // the measurements of the local links
+    TRParams tr;
+    bool halo;
+    long long iter_bytes, xbytes;
+    VerdictBlock vb;
+    IterCfg A;                                                  // the iteration whose verdict is awaited
+    islam_pvgo_result t;                                        // ... and what the verdicts have said so far
+    double epoch;
+
+
+    void carve_scratch(void* scratch) {
+        a = sh.node0; b = sh.node1; nloc = b - a + 1; Mloc = nloc - 1; n_own = sh.n_own;
+        first_local = sh.first - a; nblk = (n_own + 63) / 64; nmsg = 3 + 10 * world;
+        double* p = (double*)align_up((size_t)scratch);
+        auto take = [&](size_t n) { double* r = p; p += a256(n); return r; };
+        const size_t nn = (size_t)N + 2;
+        lin = take(LIN_C * nn);
+        loss_part = take(nn / 8 + 4);
+        Hd = take(81 * nn); Ho = take(81 * nn); rhs = take(9 * nn); dx = take(9 * nn);
+        nl = take(7 * nn); nt = take(7 * nn); vl = take(3 * nn); vt = take(3 * nn);
+        part = take(2 * (nn / 64 + 2));
+        msg = take(nmsg);
+        full = take(10 * nn);
+        ex_own = take(351 * (nn / 5 + 2));        // own rows of the exchange level, everything else stays zero (zeroed once)
+        ex = world > 1 ? take(351 * (nn / 5 + 2)) : ex_own;      // the sum over the ranks
+        flags = (int*)take(64);
+        state = take(STATE_DOUBLES);
+        rp_lin = take(ISLAM_REPROJ_REC * nn);      // reprojection factor: per-link reductions at the linearisation point ...
+        rp_tri = take(ISLAM_REPROJ_REC * nn);      // ... and at the trial point
+    }
+
+    // device state, zeroed buffers, the local stretch of the iterate and of the measurements
+    int begin(const double* nodes, const double* vels, const double* poses, const double* drots, const double* dtrans, const double* dvels,
+                         const double* dts) {
+        hipLaunchKernelGGL(state_init_kernel, dim3(1), dim3(64), 0, s, state, prm->radius, prm->down);     // (no host->device copy: see pvgo.hip)
+        ISLAM_HIP_CHECK(hipMemsetAsync(flags, 0, 64 * sizeof(double), s));
+        ISLAM_HIP_CHECK(hipMemsetAsync(workspace, 0, workspace_bytes, s));     // product rows of other ranks' segments read as zero
+        ISLAM_HIP_CHECK(hipMemsetAsync(ex_own, 0, sizeof(double) * 351 * (size_t)sh.Pxl, s));
+        ISLAM_HIP_CHECK(hipMemcpyAsync(nl, nodes + (size_t)a * 7, sizeof(double) * 7 * nloc, hipMemcpyDeviceToDevice, s));
+        ISLAM_HIP_CHECK(hipMemcpyAsync(vl, vels + (size_t)a * 3, sizeof(double) * 3 * nloc, hipMemcpyDeviceToDevice, s));
+        ISLAM_HIP_CHECK(hipMemcpyAsync(nt, nl, sizeof(double) * 7 * nloc, hipMemcpyDeviceToDevice, s));     // rows no trial writes (a last
+        ISLAM_HIP_CHECK(hipMemcpyAsync(vt, vl, sizeof(double) * 3 * nloc, hipMemcpyDeviceToDevice, s));     // rank's unused tail) stay defined
+        lp = poses + (size_t)a * 7; lr = drots + (size_t)a * 4; ltr = dtrans + (size_t)a * 3; lv = dvels + (size_t)a * 3; ldt = dts + a;
+        tr = tr_params(prm);
+        halo = sh.has_right && rank + 1 < world && b > a + n_own;
+        iter_bytes = (world > 1) ? 8LL * (351LL * sh.Pxl + nmsg) : 0;
+        xbytes = 0;
+        t = islam_pvgo_result{};
+        epoch = 1.0;
+        A = IterCfg{nl, vl, nt, vt};
+        return ISLAM_OK;
+    }
+
+    // one pass of PyPose's inner `while self.last <= self.loss`; relin: the iterate changed, linearise first
+    int enqueue_iter(const IterCfg& c, double seq, double ep, bool relin) {
+        const Gate gate{state, ep};
+        int r;
+        if (relin) {
+            if (reproj && (r = reproj_reduce_gated(c.cur_n, nullptr, Mloc, reproj, a, rp_lin, gate, s)) != ISLAM_OK) return r;
+            if ((r = linbuild_gated(c.cur_n, c.cur_v, lp, lr, ltr, lv, ldt, nloc, prm, lin, loss_part, Hd, Ho, rhs, rp_lin, reproj, a, gate, s)) != ISLAM_OK) return r;
+        }
+        if ((r = shard_upsweep_gated(Hd, Ho, rhs, 0.0, state, N, prm->seg_len, world, rank, a, workspace, workspace_bytes, ex_own, false, flags, gate, s)) != ISLAM_OK) return r;
+        if (world > 1 && (r = red->sum_to(ex_own, ex, 351 * (size_t)sh.Pxl, s)) != ISLAM_OK) return r;
+        if ((r = shard_downsweep_gated(ex, N, prm->seg_len, world, rank, a, workspace, workspace_bytes, dx, flags, gate, s)) != ISLAM_OK) return r;
+        // (the reduction at the trial point covers the rank's own links: the step of the halo node is not known here)
+        if (reproj && (r = reproj_reduce_gated(c.cur_n, dx, n_own, reproj, a, rp_tri, gate, s)) != ISLAM_OK) return r;
+        if ((r = trial_gated(c.cur_n, c.cur_v, dx, lp, lr, ltr, lv, ldt, lin, Mloc, n_own, c.tri_n, c.tri_v, part, rp_lin, rp_tri, reproj, a, gate, s)) != ISLAM_OK) return r;
+        double* rep = vb.dev_slot(seq);
+        hipLaunchKernelGGL(msg_kernel, dim3(1), dim3(64), 0, s, part, nblk, flags, c.tri_n, c.tri_v, first_local, rank, world, msg,
+                           world == 1 ? 1 : 0, state, tr, rep, seq, c.tri_n, c.tri_v, gate);
+        if (world > 1) {
+            if ((r = red->sum(msg, nmsg, s)) != ISLAM_OK) return r;
+            hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(64), 0, s, msg, state, flags, tr, rep, seq, c.tri_n, c.tri_v,
+                               halo ? msg + 3 + 10 * (rank + 1) : (const double*)nullptr, b - a, gate);
+        }
+        ISLAM_LAUNCH_CHECK();
+        xbytes += iter_bytes;
+        return ISLAM_OK;
+    }
+
+    int loop() {
+        int rc;
+        // first linearisation and the loss of the initial iterate
+        const Gate open{nullptr, 0.0};
+        if (reproj && (rc = reproj_reduce_gated(nl, nullptr, Mloc, reproj, a, rp_lin, open, s)) != ISLAM_OK) return rc;
+        if ((rc = linbuild_gated(nl, vl, lp, lr, ltr, lv, ldt, nloc, prm, lin, loss_part, Hd, Ho, rhs, rp_lin, reproj, a, open, s)) != ISLAM_OK) return rc;
+        hipLaunchKernelGGL(own_loss_kernel, dim3(1), dim3(256), 0, s, lin, Mloc, n_own, reproj ? rp_lin : (const double*)nullptr, msg);
+        if (world > 1 && (rc = red->sum(msg, 1, s)) != ISLAM_OK) return rc;
+        hipLaunchKernelGGL(begin_kernel, dim3(1), dim3(64), 0, s, msg, state, flags);
+
+        if ((rc = enqueue_iter(A, 1.0, epoch, false)) != ISLAM_OK) return rc;
+        for (;;) {
+            const double seq = (double)(t.trials + 1);
+            // run ahead: the next iteration under the assumption "trial accepted, loop continues"
+            const IterCfg B{A.tri_n, A.tri_v, A.cur_n, A.cur_v};
+            if (t.steps + 1 < prm->max_steps && (rc = enqueue_iter(B, seq + 1.0, epoch, true)) != ISLAM_OK) return rc;
+            volatile double* hs = vb.slot(seq);
+            if ((rc = wait_verdict(hs, seq, s, "islam_pvgo_run_chain_sharded: no status from the device (trial %d)")) != ISLAM_OK) return rc;
+            const int verdict = take_verdict(t, hs);
+            if (verdict == 0) { A = B; continue; }          // accepted, continue: B is the iteration now in flight
+            epoch += 1.0;                                   // any other verdict bumped the device epoch: B's kernels are no-ops
+            if (verdict == 1) {                             // rejected: same iterate, same (cumulatively damped) linearisation
+                if ((rc = enqueue_iter(A, seq + 1.0, epoch, false)) != ISLAM_OK) return rc;
+                continue;
+            }
+            if (verdict == 2) { A = B; break; }             // accepted, StopOnPlateau says stop
+            t.status = ISLAM_ENOTPD;                        // "Linear solver failed. Breaking optimization step..."
+            if (verdict == 4) break;
+            if ((rc = enqueue_iter(A, seq + 1.0, epoch, true)) != ISLAM_OK) return rc;      // same iterate, new linearisation
+        }
+        return ISLAM_OK;
+    }
+};
+
+// the full solution on every rank: rows [r0, r1) of the local arrays (-> global rows a + r), summed over the ranks; the ranks leave
+// together
+int gather_solution(const Reducer& red, int world, const double* cur_n, const double* cur_v, int r0, int r1, int a, double* full, int N,
+                    double* nodes, double* vels, hipStream_t s) {
+    int rc;
+    ISLAM_HIP_CHECK(hipMemsetAsync(full, 0, sizeof(double) * 10 * (size_t)N, s));
+    hipLaunchKernelGGL(scatter_full_kernel, dim3(((r1 - r0) * 10 + 255) / 256), dim3(256), 0, s, cur_n, cur_v, r0, r1, a, full);
+    if (world > 1 && (rc = red.sum(full, 10 * (size_t)N, s)) != ISLAM_OK) return rc;
+    hipLaunchKernelGGL(unpack_full_kernel, dim3((N * 10 + 255) / 256), dim3(256), 0, s, full, N, nodes, vels);
+    ISLAM_LAUNCH_CHECK();
+    ISLAM_HIP_CHECK(hipStreamSynchronize(s));
+    return ISLAM_OK;
+}
+
+// ---- the loop on the fused trial + elimination kernel, one collective per trial (pvgo.hip: run_chain_sharded_fused); *taken = 0:
+// the plan is one it does not cover -- the caller runs the launch-per-stage loop
+int run_fused_path(const Reducer& red, int world, int rank, double* nodes, double* vels, const double* poses, const double* drots,
+                   const double* dtrans, const double* dvels, const double* dts, int N, const islam_pvgo_params* prm, void* workspace,
+                   size_t workspace_bytes, void* scratch, size_t scratch_bytes, double* full, islam_pvgo_result* res,
+                   long long* exchanged_bytes, hipStream_t s, int* taken) {
+    ShardSum sum{[](void* self, const double* send, double* recv, size_t count, hipStream_t st) -> int {
+                     return static_cast<const Reducer*>(self)->sum_to(send, recv, count, st);
+                 },
+                 const_cast<Reducer*>(&red)};
+    int own0 = 0, own1 = 0;
+    const double *fin_n = nullptr, *fin_v = nullptr;
+    const int rc = run_chain_sharded_fused(sum, world, rank, nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, workspace, workspace_bytes, scratch,
+                                           scratch_bytes, res, exchanged_bytes, s, taken, &fin_n, &fin_v, &own0, &own1);
+    if (rc != ISLAM_OK || !*taken) return rc;
+    // (one rank: stream-ordered like islam_pvgo_run_chain -- the result block comes from the pinned verdicts, nothing to wait for)
+    if (world == 1) return copy_back_if_moved(nodes, vels, fin_n, fin_v, N, s);
+    return gather_solution(red, world, fin_n, fin_v, own0, own1, 0, full, N, nodes, vels, s);
+}
+
+int run_sharded(const Reducer& red, int world, int rank, double* nodes, double* vels, const double* poses, const double* drots,
+                const double* dtrans, const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                const islam_pvgo_reproj* reproj, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                islam_pvgo_result* res, long long* exchanged_bytes, void* stream) {
+    if (!prm || !res || N < 2 || world < 1 || rank < 0 || rank >= world) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: bad argument");
+    if (world > 1 && !red.comm && !red.fn) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: world=%d needs a communicator", world);
+    if (scratch_bytes < islam_pvgo_sharded_scratch_bytes(N, world)) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: scratch too small");
+    StagedRun r{};
+    r.red = &red; r.world = world; r.rank = rank; r.N = N; r.prm = prm; r.reproj = reproj; r.workspace = workspace;
+    r.workspace_bytes = workspace_bytes; r.s = as_stream(stream);
+    int rc = shard_of(N, prm->seg_len, world, rank, r.sh);
+    if (rc != ISLAM_OK) return rc;
+    r.carve_scratch(scratch);
+    // plans the fused loop does not cover and the reprojection factor take the launch-per-stage loop below
+    if (!reproj) {
+        int taken = 0;
+        rc = run_fused_path(red, world, rank, nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, workspace, workspace_bytes, scratch,
+                            scratch_bytes, r.full, res, exchanged_bytes, r.s, &taken);
+        if (rc != ISLAM_OK || taken) return rc;
+    }
+    if ((rc = r.vb.acquire()) != ISLAM_OK) return rc;
+    if ((rc = r.begin(nodes, vels, poses, drots, dtrans, dvels, dts)) != ISLAM_OK) return rc;
+    rc = r.loop();
+    // own rows (the left outer separator belongs to the previous rank)
+    if (rc == ISLAM_OK) rc = gather_solution(red, world, r.A.cur_n, r.A.cur_v, r.sh.has_left ? 1 : 0, r.n_own + 1, r.a, r.full, N, nodes, vels, r.s);
+    if (rc != ISLAM_OK) {
+        // A failed enqueue / collective / status wait leaves gated kernels (and possibly collectives) of the run-ahead chain in
+        // flight: they would still write the pinned verdict block and the scratch the NEXT call reuses.  Close the gate (any
+        // epoch no enqueued kernel carries) and drain the stream before handing the error up; the message of the original
+        // failure is kept.  After a collective error the peers may be blocked in their next collective: the caller must destroy
+        // (abort) the communicator.
+        hipLaunchKernelGGL(close_gate_kernel, dim3(1), dim3(64), 0, r.s, r.state, r.epoch + 2.0);
+        (void)hipStreamSynchronize(r.s);
+        (void)hipGetLastError();
+        return rc;
+    }
+    *res = r.t;
+    if (exchanged_bytes) *exchanged_bytes = r.xbytes;
+    return ISLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -234,191 +435,6 @@ size_t islam_pvgo_sharded_scratch_bytes(int N, int world) {
     size_t d = a256(LIN_C * n) + a256(n / 8 + 4) + 2 * a256(81 * n) + 2 * a256(9 * n) + 2 * a256(7 * n) + 2 * a256(3 * n) +
                a256(2 * (n / 64 + 2)) + a256(3 + 10 * (size_t)world) + a256(10 * n) + 2 * a256(351 * (n / 5 + 2)) + a256(64) + a256(STATE_DOUBLES) + 2 * a256(ISLAM_REPROJ_REC * n);
     return d * sizeof(double) + 512;
-}
-
-static int run_sharded(const Reducer& red, int world, int rank, double* nodes, double* vels, const double* poses, const double* drots,
-                       const double* dtrans, const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
-                       const islam_pvgo_reproj* reproj, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
-                       islam_pvgo_result* res, long long* exchanged_bytes, void* stream) {
-    if (!prm || !res || N < 2 || world < 1 || rank < 0 || rank >= world) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: bad argument");
-    if (world > 1 && !red.comm && !red.fn) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: world=%d needs a communicator", world);
-    if (scratch_bytes < islam_pvgo_sharded_scratch_bytes(N, world)) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: scratch too small");
-    Shard sh;
-    int rc = shard_of(N, prm->seg_len, world, rank, sh);
-    if (rc != ISLAM_OK) return rc;
-    hipStream_t s = as_stream(stream);
-    const int a = sh.node0, b = sh.node1, nloc = b - a + 1, Mloc = nloc - 1, n_own = sh.n_own;
-    const int first_local = sh.first - a, nblk = (n_own + 63) / 64, nmsg = 3 + 10 * world;
-    // scratch carve
-    double* p = (double*)align_up((size_t)scratch);
-    auto take = [&](size_t n) { double* r = p; p += a256(n); return r; };
-    const size_t nn = (size_t)N + 2;
-    double* lin = take(LIN_C * nn);
-    double* loss_part = take(nn / 8 + 4);
-    double* Hd = take(81 * nn); double* Ho = take(81 * nn); double* rhs = take(9 * nn); double* dx = take(9 * nn);
-    double* nl = take(7 * nn); double* nt = take(7 * nn); double* vl = take(3 * nn); double* vt = take(3 * nn);
-    double* part = take(2 * (nn / 64 + 2));
-    double* msg = take(nmsg);
-    double* full = take(10 * nn);
-    double* ex_own = take(351 * (nn / 5 + 2));        // own rows of the exchange level, everything else stays zero (zeroed once)
-    double* ex = world > 1 ? take(351 * (nn / 5 + 2)) : ex_own;      // the sum over the ranks
-    int* flags = (int*)take(64);
-    double* state = take(STATE_DOUBLES);
-    double* rp_lin = take(ISLAM_REPROJ_REC * nn);      // reprojection factor: per-link reductions at the linearisation point ...
-    double* rp_tri = take(ISLAM_REPROJ_REC * nn);      // ... and at the trial point
-    // verdicts in pinned, device-visible host memory (two slots, alternating with the trial number); the host polls the
-    // sequence number -- no stream synchronisation, no copy
-    static thread_local double* host_state = nullptr;
-    if (!host_state) ISLAM_HIP_CHECK(hipHostMalloc((void**)&host_state, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocPortable));   // portable: one buffer per thread serves calls on any device
-    double* report = nullptr;
-    ISLAM_HIP_CHECK(hipHostGetDevicePointer((void**)&report, host_state, 0));
-    volatile double* hs_all = host_state;
-    hs_all[15] = 0.0;
-    hs_all[31] = 0.0;
-    // ---- the loop on the fused trial + elimination kernel, one collective per trial (pvgo.hip: run_chain_sharded_fused); plans it
-    // does not cover and the reprojection factor take the launch-per-stage loop below
-    if (!reproj) {
-        ShardSum sum{[](void* self, const double* send, double* recv, size_t count, hipStream_t st) -> int {
-                         return static_cast<const Reducer*>(self)->sum_to(send, recv, count, st);
-                     },
-                     const_cast<Reducer*>(&red)};
-        int taken = 0, own0 = 0, own1 = 0;
-        const double *fin_n = nullptr, *fin_v = nullptr;
-        rc = run_chain_sharded_fused(sum, world, rank, nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, workspace, workspace_bytes, scratch,
-                                     scratch_bytes, res, exchanged_bytes, s, &taken, &fin_n, &fin_v, &own0, &own1);
-        if (rc != ISLAM_OK) return rc;
-        if (taken) {
-            if (world == 1) {
-                if (fin_n != nodes) {
-                    ISLAM_HIP_CHECK(hipMemcpyAsync(nodes, fin_n, sizeof(double) * 7 * (size_t)N, hipMemcpyDeviceToDevice, s));
-                    ISLAM_HIP_CHECK(hipMemcpyAsync(vels, fin_v, sizeof(double) * 3 * (size_t)N, hipMemcpyDeviceToDevice, s));
-                }
-            } else {
-                ISLAM_HIP_CHECK(hipMemsetAsync(full, 0, sizeof(double) * 10 * (size_t)N, s));
-                hipLaunchKernelGGL(scatter_full_kernel, dim3(((own1 - own0) * 10 + 255) / 256), dim3(256), 0, s, fin_n, fin_v, own0, own1, 0, full);
-                if ((rc = red.sum(full, 10 * (size_t)N, s)) != ISLAM_OK) return rc;
-                hipLaunchKernelGGL(unpack_full_kernel, dim3((N * 10 + 255) / 256), dim3(256), 0, s, full, N, nodes, vels);
-                ISLAM_LAUNCH_CHECK();
-                ISLAM_HIP_CHECK(hipStreamSynchronize(s));       // (as the launch-per-stage loop below: the ranks leave together)
-            }
-            // (one rank: stream-ordered like islam_pvgo_run_chain -- the result block comes from the pinned verdicts, nothing to wait for)
-            return ISLAM_OK;
-        }
-    }
-    hipLaunchKernelGGL(state_init_kernel, dim3(1), dim3(64), 0, s, state, prm->radius, prm->down);     // (no host->device copy: see pvgo.hip)
-    ISLAM_HIP_CHECK(hipMemsetAsync(flags, 0, 64 * sizeof(double), s));
-    ISLAM_HIP_CHECK(hipMemsetAsync(workspace, 0, workspace_bytes, s));     // product rows of other ranks' segments read as zero
-    ISLAM_HIP_CHECK(hipMemsetAsync(ex_own, 0, sizeof(double) * 351 * (size_t)sh.Pxl, s));
-    ISLAM_HIP_CHECK(hipMemcpyAsync(nl, nodes + (size_t)a * 7, sizeof(double) * 7 * nloc, hipMemcpyDeviceToDevice, s));
-    ISLAM_HIP_CHECK(hipMemcpyAsync(vl, vels + (size_t)a * 3, sizeof(double) * 3 * nloc, hipMemcpyDeviceToDevice, s));
-    ISLAM_HIP_CHECK(hipMemcpyAsync(nt, nl, sizeof(double) * 7 * nloc, hipMemcpyDeviceToDevice, s));     // rows no trial writes (a last
-    ISLAM_HIP_CHECK(hipMemcpyAsync(vt, vl, sizeof(double) * 3 * nloc, hipMemcpyDeviceToDevice, s));     // rank's unused tail) stay defined
-    const double *lp = poses + (size_t)a * 7, *lr = drots + (size_t)a * 4, *ltr = dtrans + (size_t)a * 3, *lv = dvels + (size_t)a * 3,
-                 *ldt = dts + a;
-    const TRParams tr{prm->high, prm->low, prm->up, prm->down, prm->factor, prm->rmin, prm->rmax, prm->reject,
-                      prm->max_steps, prm->patience, prm->decreasing};
-    const bool halo = sh.has_right && rank + 1 < world && b > a + n_own;
-    const long long iter_bytes = (world > 1) ? 8LL * (351LL * sh.Pxl + nmsg) : 0;
-    long long xbytes = 0;
-
-    struct IterCfg { double *cur_n, *cur_v, *tri_n, *tri_v; };
-    // one pass of PyPose's inner `while self.last <= self.loss`; relin: the iterate changed, linearise first
-    auto enqueue_iter = [&](const IterCfg& c, double seq, double epoch, bool relin) -> int {
-        const Gate gate{state, epoch};
-        int r;
-        if (relin) {
-            if (reproj && (r = reproj_reduce_gated(c.cur_n, nullptr, Mloc, reproj, a, rp_lin, gate, s)) != ISLAM_OK) return r;
-            if ((r = linbuild_gated(c.cur_n, c.cur_v, lp, lr, ltr, lv, ldt, nloc, prm, lin, loss_part, Hd, Ho, rhs, rp_lin, reproj, a, gate, s)) != ISLAM_OK) return r;
-        }
-        if ((r = shard_upsweep_gated(Hd, Ho, rhs, 0.0, state, N, prm->seg_len, world, rank, a, workspace, workspace_bytes, ex_own, false, flags, gate, s)) != ISLAM_OK) return r;
-        if (world > 1 && (r = red.sum_to(ex_own, ex, 351 * (size_t)sh.Pxl, s)) != ISLAM_OK) return r;
-        if ((r = shard_downsweep_gated(ex, N, prm->seg_len, world, rank, a, workspace, workspace_bytes, dx, flags, gate, s)) != ISLAM_OK) return r;
-        // (the reduction at the trial point covers the rank's own links: the step of the halo node is not known here)
-        if (reproj && (r = reproj_reduce_gated(c.cur_n, dx, n_own, reproj, a, rp_tri, gate, s)) != ISLAM_OK) return r;
-        if ((r = trial_gated(c.cur_n, c.cur_v, dx, lp, lr, ltr, lv, ldt, lin, Mloc, n_own, c.tri_n, c.tri_v, part, rp_lin, rp_tri, reproj, a, gate, s)) != ISLAM_OK) return r;
-        double* rep = report + 16 * ((long long)seq & 1);
-        hipLaunchKernelGGL(msg_kernel, dim3(1), dim3(64), 0, s, part, nblk, flags, c.tri_n, c.tri_v, first_local, rank, world, msg,
-                           world == 1 ? 1 : 0, state, tr, rep, seq, c.tri_n, c.tri_v, gate);
-        if (world > 1) {
-            if ((r = red.sum(msg, nmsg, s)) != ISLAM_OK) return r;
-            hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(64), 0, s, msg, state, flags, tr, rep, seq, c.tri_n, c.tri_v,
-                               halo ? msg + 3 + 10 * (rank + 1) : (const double*)nullptr, b - a, gate);
-        }
-        ISLAM_LAUNCH_CHECK();
-        xbytes += iter_bytes;
-        return ISLAM_OK;
-    };
-
-    int steps = 0, trials = 0, status = ISLAM_OK;
-    double loss = 0.0, damping = 1.0 / prm->radius, epoch = 1.0;
-    IterCfg A{nl, vl, nt, vt};            // the iteration whose verdict is awaited
-    auto run = [&]() -> int {
-    // first linearisation and the loss of the initial iterate
-    const Gate open{nullptr, 0.0};
-    if (reproj && (rc = reproj_reduce_gated(nl, nullptr, Mloc, reproj, a, rp_lin, open, s)) != ISLAM_OK) return rc;
-    if ((rc = linbuild_gated(nl, vl, lp, lr, ltr, lv, ldt, nloc, prm, lin, loss_part, Hd, Ho, rhs, rp_lin, reproj, a, open, s)) != ISLAM_OK) return rc;
-    hipLaunchKernelGGL(own_loss_kernel, dim3(1), dim3(256), 0, s, lin, Mloc, n_own, reproj ? rp_lin : (const double*)nullptr, msg);
-    if (world > 1 && (rc = red.sum(msg, 1, s)) != ISLAM_OK) return rc;
-    hipLaunchKernelGGL(begin_kernel, dim3(1), dim3(64), 0, s, msg, state, flags);
-
-    if ((rc = enqueue_iter(A, 1.0, epoch, false)) != ISLAM_OK) return rc;
-    for (;;) {
-        const double seq = (double)(trials + 1);
-        // run ahead: the next iteration under the assumption "trial accepted, loop continues"
-        const IterCfg B{A.tri_n, A.tri_v, A.cur_n, A.cur_v};
-        if (steps + 1 < prm->max_steps && (rc = enqueue_iter(B, seq + 1.0, epoch, true)) != ISLAM_OK) return rc;
-        volatile double* hs = hs_all + 16 * ((long long)seq & 1);
-        {
-            unsigned long spins = 0;
-            while (hs[15] != seq) {
-                if (++spins > 400000000ul) {
-                    ISLAM_HIP_CHECK(hipStreamSynchronize(s));
-                    if (hs[15] != seq) return fail(ISLAM_EHIP, "islam_pvgo_run_chain_sharded: no status from the device (trial %d)", trials + 1);
-                }
-            }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        }
-        ++trials;
-        const int verdict = (int)hs[12];
-        damping = hs[2];
-        loss = hs[0];
-        steps = (int)hs[13];
-        if (verdict == 0) { A = B; continue; }          // accepted, continue: B is the iteration now in flight
-        epoch += 1.0;                                   // any other verdict bumped the device epoch: B's kernels are no-ops
-        if (verdict == 1) {                             // rejected: same iterate, same (cumulatively damped) linearisation
-            if ((rc = enqueue_iter(A, seq + 1.0, epoch, false)) != ISLAM_OK) return rc;
-            continue;
-        }
-        if (verdict == 2) { A = B; break; }             // accepted, StopOnPlateau says stop
-        status = ISLAM_ENOTPD;                          // "Linear solver failed. Breaking optimization step..."
-        if (verdict == 4) break;
-        if ((rc = enqueue_iter(A, seq + 1.0, epoch, true)) != ISLAM_OK) return rc;      // same iterate, new linearisation
-    }
-    // the full solution on every rank: own rows (the left outer separator belongs to the previous rank), summed
-    ISLAM_HIP_CHECK(hipMemsetAsync(full, 0, sizeof(double) * 10 * (size_t)N, s));
-    const int r0 = sh.has_left ? 1 : 0, r1 = n_own + 1;
-    hipLaunchKernelGGL(scatter_full_kernel, dim3(((r1 - r0) * 10 + 255) / 256), dim3(256), 0, s, A.cur_n, A.cur_v, r0, r1, a, full);
-    if (world > 1 && (rc = red.sum(full, 10 * (size_t)N, s)) != ISLAM_OK) return rc;
-    hipLaunchKernelGGL(unpack_full_kernel, dim3((N * 10 + 255) / 256), dim3(256), 0, s, full, N, nodes, vels);
-    ISLAM_LAUNCH_CHECK();
-    ISLAM_HIP_CHECK(hipStreamSynchronize(s));
-    return ISLAM_OK;
-    };
-    rc = run();
-    if (rc != ISLAM_OK) {
-        // A failed enqueue / collective / status wait leaves gated kernels (and possibly collectives) of the run-ahead chain in
-        // flight: they would still write the pinned verdict block and the scratch the NEXT call reuses.  Close the gate (any
-        // epoch no enqueued kernel carries) and drain the stream before handing the error up; the message of the original
-        // failure is kept.  After a collective error the peers may be blocked in their next collective: the caller must destroy
-        // (abort) the communicator.
-        hipLaunchKernelGGL(close_gate_kernel, dim3(1), dim3(64), 0, s, state, epoch + 2.0);
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-        return rc;
-    }
-    res->steps = steps; res->trials = trials; res->status = status; res->loss = loss; res->damping = damping;
-    if (exchanged_bytes) *exchanged_bytes = xbytes;
-    return ISLAM_OK;
 }
 
 int islam_pvgo_run_chain_sharded(void* comm, int world, int rank, double* nodes, double* vels, const double* poses, const double* drots,

@@ -1,7 +1,5 @@
 // pvgo_host.inl -- part of the pvgo.hip translation unit (textually included there; not compiled on its own).
-// host side: level planner, workspace carving, kernel launchers
-// ------------------------------------------------------------------------------------------
-// host side
+// host side: level planner, workspace carving, kernel launchers, the pieces the LM-loop drivers and the entry points share
 struct LevelPlan { int n, m, P, nsep; };
 constexpr int MAXL = ISLAM_PVGO_MAX_LEVELS;
 constexpr int TOPW = 1;                        // wavefronts of the top kernel's workgroup (see plan_levels)
@@ -130,6 +128,57 @@ Workspace carve(void* base, int N) {
     return w;
 }
 
+// carve after the size check every entry point makes; msg: the caller's message, a format that may take (given, needed) bytes
+static int workspace_or_fail(const char* msg, int N, void* workspace, size_t workspace_bytes, Workspace& w) {
+    const size_t need = islam_pvgo_workspace_bytes(N);
+    if (workspace_bytes < need) return fail(ISLAM_EARG, msg, workspace_bytes, need);
+    w = carve((void*)align_up((size_t)workspace), N);
+    return ISLAM_OK;
+}
+
+// plan as the entry points report it: (nodes, segment length, segments) per level, then the first level of the top kernel
+static void write_plan(const SolvePlan& sp, int* out) {
+    for (int l = 0; l < MAXL; ++l) {
+        out[3 * l] = l < sp.nl ? sp.lv[l].n : 0;
+        out[3 * l + 1] = l < sp.nl ? sp.lv[l].m : 0;
+        out[3 * l + 2] = l < sp.nl ? sp.lv[l].P : 0;
+    }
+    out[3 * MAXL] = sp.top;
+}
+
+// Kernels that use dynamic LDS above the default limit.  The attribute lives in the device's code object, so it is set once per
+// device: `set` is the static bool[64] the caller keeps for these kernels.
+static int ensure_dynamic_lds(std::initializer_list<const void*> kernels, int bytes, bool (&set)[64]) {
+    int dev_i = 0;
+    ISLAM_HIP_CHECK(hipGetDevice(&dev_i));
+    if (dev_i < 0 || dev_i >= 64 || set[dev_i]) return ISLAM_OK;
+    for (const void* k : kernels) ISLAM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    set[dev_i] = true;
+    return ISLAM_OK;
+}
+// linbuild_kernel / trial_lin_kernel stage their node blocks in dynamic LDS
+static int ensure_linbuild_lds() {
+    static bool set[64] = {};
+    return ensure_dynamic_lds({(const void*)linbuild_kernel<false>, (const void*)trial_lin_kernel<false>, (const void*)linbuild_kernel<true>,
+                               (const void*)trial_lin_kernel<true>}, LB_DYN_BYTES, set);
+}
+static int ensure_fused_lds() {
+    static bool set[64] = {};
+    return ensure_dynamic_lds({(const void*)trial_elim_kernel}, FZ_LDS_BYTES, set);
+}
+
+static int device_cus() {
+    static int cus[64] = {};
+    int dev_i = 0;
+    if (hipGetDevice(&dev_i) != hipSuccess || dev_i < 0 || dev_i >= 64) return 0;
+    if (cus[dev_i] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_i) != hipSuccess) return 0;
+        cus[dev_i] = v;
+    }
+    return cus[dev_i];
+}
+
 static LevelDst level_dst(const LevelBufs& b, double* x) {
     LevelDst d{};
     d.fac = b.fac; d.inv = b.inv; d.Dsep = b.Dsep; d.rsep = b.rsep; d.cL = b.cL; d.cR = b.cR; d.cgL = b.cgL; d.cgR = b.cgR;
@@ -149,7 +198,7 @@ static LevelSrc level_src_from(const LevelBufs& pb, int Pprev) {
 // between lanes) made the exchange end 2-3 us after the upstream words were published (no gain); with the matrices copied through
 // LDS in contiguous 512-byte stores / loads the exchange is done ~1 us after the influence matrices are.
 static bool merge_levels() {
-    static const bool v = [] { const char* e = std::getenv("ISLAM_PVGO_NO_MERGE"); return !(e && e[0] == '1'); }();
+    static const bool v = !env_is("ISLAM_PVGO_NO_MERGE", '1');
     return v;
 }
 
@@ -164,7 +213,7 @@ static int next_serial() {
 static void launch_tw(const LevelSrc& src, const LevelDst& dst, int n, int m, int* flags, int seg0, int nseg, Gate gate, hipStream_t s) {
     // level 0 of a graph with >= 3072 segments (four rounds of resident workgroups) runs on the two-wave kernel: N = 300 007, 37 504
     // segments: 1266 -> 1205 us per LM iteration.  (ISLAM_PVGO_L0_TW2 = that threshold; 0: never)
-    static const int tw2_from = [] { const char* e = std::getenv("ISLAM_PVGO_L0_TW2"); return e ? std::atoi(e) : 3072; }();
+    static const int tw2_from = env_int("ISLAM_PVGO_L0_TW2", 3072);
     if (src.level0 && tw2_from > 0 && nseg >= tw2_from) {
         hipLaunchKernelGGL(bt_eliminate_tw2_kernel, dim3(xcd_grid(nseg)), dim3(128), 0, s, src, dst, n, m, flags, seg0, nseg, gate);
         return;
@@ -188,13 +237,10 @@ static void launch_eliminate(const LevelPlan& L, bool tw, const LevelSrc& src, c
 int enqueue_levels(const Workspace& w, const SolvePlan& sp, int lbegin, const LevelSrc& first, const LevelBufs* first_prev,
                    double* xout, int* flags, hipStream_t s, hipEvent_t* evs, int* nev, Gate gate = Gate{nullptr, 0.0},
                    bool skip_first = false) {
-    static bool lds_attr_set[64] = {};                       // per device: the attribute lives in the device's code object
-    int dev_i = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev_i));
-    if (dev_i >= 0 && dev_i < 64 && !lds_attr_set[dev_i]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)bt_top_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            TOPW * LDS_PER_WAVE * (int)sizeof(double)));
-        lds_attr_set[dev_i] = true;
+    static bool top_lds_set[64] = {};
+    {
+        const int rc_lds = ensure_dynamic_lds({(const void*)bt_top_kernel}, TOPW * LDS_PER_WAVE * (int)sizeof(double), top_lds_set);
+        if (rc_lds != ISLAM_OK) return rc_lds;
     }
     const int nl = sp.nl, top = std::max(sp.top, lbegin);
     int ne = 0;
@@ -298,7 +344,7 @@ static int enqueue_control_init(const Workspace& w, const islam_pvgo_params* prm
 
 // single-GPU solves use the twisted elimination; ISLAM_PVGO_ONESIDED=1 keeps the one-sided path (A/B measurements)
 static bool solve_twisted() {
-    static const bool tw = [] { const char* e = std::getenv("ISLAM_PVGO_ONESIDED"); return !(e && e[0] == '1'); }();
+    static const bool tw = !env_is("ISLAM_PVGO_ONESIDED", '1');
     return tw;
 }
 
@@ -313,3 +359,100 @@ int enqueue_solve(const Workspace& w, double* Hd, const double* Ho, const double
     return enqueue_levels(w, sp, 0, src, nullptr, dx, w.flags, s, evs, nev, gate);
 }
 
+// ---- what the LM-loop drivers (pvgo_lm_loop.inl, pvgo_sharded.inl) and the entry points share ------------------------------------
+static LinWeights lin_weights(const islam_pvgo_params* prm) {
+    return LinWeights{prm->w[0], prm->w[1], prm->w[2], prm->w[3], prm->vmin, prm->vmax};
+}
+
+static int reproj_dev(const islam_pvgo_reproj* r, ReprojDev& d) {
+    if (!r->points || !r->targets || r->K < 1) return fail(ISLAM_EARG, "islam_pvgo_reproj: null points/targets or K=%d < 1", r->K);
+    d.points = r->points; d.targets = r->targets; d.K = r->K;
+    d.fx = r->fx; d.fy = r->fy; d.cx = r->cx; d.cy = r->cy;
+    d.C = {{r->rgb2imu[0], r->rgb2imu[1], r->rgb2imu[2]}, {r->rgb2imu[3], r->rgb2imu[4], r->rgb2imu[5], r->rgb2imu[6]}};
+    d.weight = r->weight;
+    d.compat_first = r->compat_first_motion;
+    return ISLAM_OK;
+}
+
+// the factor as a rank of the sharded loop sees it: keypoints / targets of its local link 0 = global link `link0`; the frozen
+// first motion (pvgo.py:57) belongs to global link 0
+static int reproj_dev_local(const islam_pvgo_reproj* r, int link0, ReprojDev& d) {
+    const int rc = reproj_dev(r, d);
+    if (rc != ISLAM_OK) return rc;
+    d.points += (size_t)link0 * d.K * 3;
+    d.targets += (size_t)link0 * d.K * 2;
+    if (link0 != 0) d.compat_first = 0;
+    return ISLAM_OK;
+}
+
+// islam_pvgo_robust -> RobustDev; returns whether any group has a kernel in *active (NONE everywhere: the plain loop)
+static int robust_dev(const islam_pvgo_robust* r, RobustDev& d, bool* active = nullptr) {
+    bool any = false;
+    for (int g = 0; g < 4; ++g) {
+        const int k = r->kind[g];
+        if (k != ISLAM_ROBUST_NONE && k != ISLAM_ROBUST_HUBER && k != ISLAM_ROBUST_CAUCHY)
+            return fail(ISLAM_EARG, "islam_pvgo_robust: unknown kind %d for factor group %d", k, g);
+        if (k != ISLAM_ROBUST_NONE && !(r->delta[g] > 0.0 && std::isfinite(r->delta[g])))
+            return fail(ISLAM_EARG, "islam_pvgo_robust: delta %g of factor group %d is not a finite positive number", r->delta[g], g);
+        d.kind[g] = k;
+        d.delta[g] = k != ISLAM_ROBUST_NONE ? r->delta[g] : 1.0;
+        any = any || k != ISLAM_ROBUST_NONE;
+    }
+    if (active) *active = any;
+    return ISLAM_OK;
+}
+
+static void enqueue_reproj_reduce(const double* nodes, const double* dx, int M, const ReprojDev& rp, double* red, hipStream_t s,
+                                  Gate gate = Gate{nullptr, 0.0}) {
+    const int waves = std::min(4, std::max(1, (rp.K + 127) / 128));
+    hipLaunchKernelGGL(reproj_reduce_kernel, dim3(xcd_grid(M)), dim3(64 * waves), 64 * waves * (RP_NSUM + 1) * sizeof(double), s, nodes,
+                       dx, M, rp, red, gate);
+}
+
+// the measurements of a chain of N nodes
+struct ChainData { const double *poses, *drots, *dtrans, *dvels, *dts; int N; };
+// a linearisation: link records, block diagonal / couplings, right-hand side
+struct LinBufs { double *lin, *Hd, *Ho, *rhs; };
+
+// linearisation + normal equations at (xn, xv) in one launch; red: the reprojection reduction there (nullptr: no such factor);
+// robust: nullptr = the plain instance
+static void launch_linbuild(const double* xn, const double* xv, const ChainData& d, const LinWeights& W, const LinBufs& o, double* loss_part,
+                            const double* red, const ReprojDev& rp, Gate gate, const RobustDev* robust, hipStream_t s) {
+    const int nlb = (d.N + LB_NODES - 1) / LB_NODES;
+    const auto kernel = robust ? linbuild_kernel<true> : linbuild_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, xn, xv, d.poses, d.drots, d.dtrans, d.dvels, d.dts, d.N, W,
+                       o.lin, loss_part, o.Hd, o.Ho, o.rhs, red, rp, gate, robust ? *robust : RobustDev{});
+}
+
+// spare CUs the fused loop leaves free (ISLAM_FZ_SPARE; 8 / 16 / 47 spare CUs: 63.3 / 62.9 / 62.9 us per LM iteration)
+static int fz_spare_cus() {
+    static const int v = env_int("ISLAM_FZ_SPARE", 16);
+    return v;
+}
+// What every user of trial_elim_kernel asks of a plan: twisted levels, the root alone in the down-sweep launch, level-0 segments the
+// kernel's LDS holds, and at most FZ_S of the nseg segments on each of the nwg workgroups (one workgroup per CU: the whole level
+// must be resident at once).  Each site adds its own terms next to the call.
+static bool fused_plan_core(const SolvePlan& sp, int nseg, int nwg) {
+    return sp.twisted && sp.top == sp.nl - 1 && sp.lv[0].m <= FZ_MAXM && (nseg + nwg - 1) / nwg <= FZ_S;
+}
+
+// one pass of an LM loop: linearisation buffer pb, current iterate, trial iterate
+struct IterCfg { int pb; double *cur_n, *cur_v, *tri_n, *tri_v; };
+
+// optional trace row of a trial (trial loss, damping, accepted) -- a trial whose solve failed (verdicts 3, 4) leaves none
+static void record_trace(double* trace, int trace_cap, int trial, int verdict, const volatile double* hs) {
+    if (!trace || trial > trace_cap || verdict == 3 || verdict == 4) return;
+    trace[3 * (trial - 1)] = hs[6];
+    trace[3 * (trial - 1) + 1] = hs[2];
+    trace[3 * (trial - 1) + 2] = (verdict == 1) ? 0.0 : 1.0;
+}
+
+// Error path of a run.  A failed enqueue or status wait leaves epoch-gated kernels of the run-ahead chain queued: they would still
+// write the pinned verdict block and the workspace the NEXT call reuses.  Close the gate and drain the stream before handing the
+// error up (the message of the original failure is kept) -- the same rule as the launch-per-stage sharded loop (pvgo_dist.hip).
+static int abandon_run(double* state, hipStream_t s, int rc) {
+    hipLaunchKernelGGL(close_gate_kernel, dim3(1), dim3(64), 0, s, state);
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    return rc;
+}

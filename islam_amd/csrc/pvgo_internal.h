@@ -1,8 +1,11 @@
 // What pvgo.hip (the single-GPU LM loop and the stage kernels) shares with pvgo_dist.hip (the sharded LM loop): the run-ahead
-// gate, the LM control rules as they run on the device, and the stage entry points WITH a gate.  Internal to libislam_hip.so --
+// gate, the LM control rules as they run on the device, the host pieces every LM loop uses (verdict block and wait, result, parameter
+// blocks, environment switches), and the stage entry points WITH a gate.  Internal to libislam_hip.so --
 // the public islam_pvgo_* stage functions of include/islam_hip.h call the same code ungated.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstdlib>
 
 #include "common.h"
 
@@ -113,6 +116,66 @@ __device__ inline int lm_control(double s, double q, double* __restrict__ st, bo
         __hip_atomic_store(&report[15], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     return (int)rep[12];
+}
+
+// ---- host pieces of the LM loops (pvgo_lm_loop.inl, pvgo_sharded.inl, pvgo_dist.hip) --------------------------------------------
+// environment switches: `NAME` starts with the character c / an integer with a default.  A caller that wants the value read once per
+// process keeps it in a function-local static; the A/B switches the tests flip inside one process are read on every call.
+inline bool env_is(const char* name, char c) { const char* e = std::getenv(name); return e && e[0] == c; }
+inline int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
+
+inline TRParams tr_params(const islam_pvgo_params* prm) {
+    return TRParams{prm->high, prm->low, prm->up, prm->down, prm->factor, prm->rmin, prm->rmax, prm->reject,
+                    prm->max_steps, prm->patience, prm->decreasing};
+}
+
+// Verdict blocks in pinned, device-visible host memory: the deciding lane of a trial writes one (two slots of 16 doubles, alternating
+// with the trial number), the host polls its sequence number -- no stream synchronisation, no copy on the critical path.  One block
+// per host thread (portable: it serves calls on any device).
+struct VerdictBlock {
+    volatile double* host = nullptr;
+    double* dev = nullptr;
+    int acquire() {
+        static thread_local double* host_state = nullptr;
+        if (!host_state) ISLAM_HIP_CHECK(hipHostMalloc((void**)&host_state, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocPortable));
+        ISLAM_HIP_CHECK(hipHostGetDevicePointer((void**)&dev, host_state, 0));
+        host = host_state;
+        host[15] = 0.0;
+        host[31] = 0.0;
+        return ISLAM_OK;
+    }
+    volatile double* slot(double seq) const { return host + 16 * ((long long)seq & 1); }
+    double* dev_slot(double seq) const { return dev ? dev + 16 * ((long long)seq & 1) : nullptr; }      // (no block: nobody waits)
+};
+
+// wait until the slot carries sequence number `seq`: poll, fall back to a stream synchronisation after ~2 s.  what: the caller's
+// message, a format that may take the trial number
+inline int wait_verdict(volatile double* hs, double seq, hipStream_t s, const char* what) {
+    unsigned long spins = 0;
+    while (hs[15] != seq) {
+        if (++spins > 400000000ul) {
+            ISLAM_HIP_CHECK(hipStreamSynchronize(s));
+            if (hs[15] != seq) return fail(ISLAM_EHIP, what, (int)seq);
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return ISLAM_OK;
+}
+
+// one more verdict into the tally of a run (the loop's own islam_pvgo_result, handed to the caller when the run ends well);
+// returns the verdict (report[12])
+inline int take_verdict(islam_pvgo_result& t, const volatile double* hs) {
+    ++t.trials;
+    t.damping = hs[2]; t.loss = hs[0]; t.steps = (int)hs[13];
+    return (int)hs[12];
+}
+
+// the accepted iterate ended in the other pair of arrays: bring it home (stream-ordered)
+inline int copy_back_if_moved(double* nodes, double* vels, const double* cur_n, const double* cur_v, int N, hipStream_t s) {
+    if (cur_n == nodes) return ISLAM_OK;
+    ISLAM_HIP_CHECK(hipMemcpyAsync(nodes, cur_n, (size_t)N * 7 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    ISLAM_HIP_CHECK(hipMemcpyAsync(vels, cur_v, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return ISLAM_OK;
 }
 
 // ---- gated stage entry points (defined in pvgo.hip) --------------------------------------------------------------------------

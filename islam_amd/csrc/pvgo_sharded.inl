@@ -1,6 +1,64 @@
 // pvgo_sharded.inl -- part of the pvgo.hip translation unit (textually included there; not compiled on its own).
-// the sharded LM loop (one graph over several GPUs; driven by pvgo_dist.hip): pack / decide kernels, run_chain_sharded_fused
+// the sharded LM loop (one graph over several GPUs; driven by pvgo_dist.hip): the split of the level tree over the ranks, the gated
+// stage functions, pack / decide kernels, run_chain_sharded_fused
 namespace islam {
+
+// ---- sharded (multi-GPU) building blocks
+// The sharded entry points plan like the single-GPU solve (twisted elimination wherever every level qualifies).
+static int shard_plan(int N, const int seg_len[2], SolvePlan& sp) { return plan_levels(N, seg_len, sp, solve_twisted()); }
+
+static void products_view(double* base, int P, LevelBufs& b) {
+    b.Dsep = base; b.rsep = base + 81 * (size_t)P; b.cL = base + 90 * (size_t)P; b.cR = base + 171 * (size_t)P;
+    b.fill = base + 252 * (size_t)P; b.cgL = base + 333 * (size_t)P; b.cgR = base + 342 * (size_t)P;
+}
+
+// ---- sharding at a HIGHER level of the tree: the interface-only exchange of SURVEY section 8e.
+// A rank owns a contiguous range of the segments of the EXCHANGE level xl (the highest level below the root that still has
+// one segment per rank) and, below it, everything between the two outer separators of that range: at level l-1 the segments
+// whose separators are its level-l nodes.  Levels 0 .. xl are eliminated locally (every block a node needs comes from the
+// rank's own segments), only the products of level xl -- 351 doubles per segment, P_xl segments -- are summed over the
+// ranks, the few levels above are solved redundantly, and the back-substitution of levels xl .. 0 is local again.
+struct ShardRanges { int xl; int seg0[MAXL], nseg[MAXL]; };
+
+static int shard_ranges(const SolvePlan& sp, int world, int rank, ShardRanges& R) {
+    if (world < 1 || rank < 0 || rank >= world) return -1;
+    int xl = -1;
+    for (int l = 0; l < sp.nl - 1; ++l)
+        if (sp.lv[l].P >= world) xl = l;
+    if (xl < 0) return -1;
+    R.xl = xl;
+    const int P = sp.lv[xl].P;
+    const int s0 = (int)((long long)rank * P / world), s1 = (int)((long long)(rank + 1) * P / world);
+    for (int l = 0; l < MAXL; ++l) { R.seg0[l] = 0; R.nseg[l] = 0; }
+    R.seg0[xl] = s0;
+    R.nseg[xl] = s1 - s0;
+    for (int l = xl; l > 0; --l) {
+        const int m = sp.lv[l].m, n = sp.lv[l].n;
+        const int a = R.seg0[l] * (m + 1);                                                   // first owned node of level l
+        const int b = std::min(n - 1, (R.seg0[l] + R.nseg[l] - 1) * (m + 1) + m - 1);       // last one
+        R.seg0[l - 1] = a;                                                                    // segment a: right separator = node a
+        R.nseg[l - 1] = std::min(b + 1, sp.lv[l - 1].P - 1) - a + 1;                          // ... segment b+1: left separator = node b
+        // the last rank owns the chain to its end: when level l closes with a trailing separator (a node of the level above)
+        // the level-(l-1) segment beyond it still feeds that separator's block, which the rank's last segment composes
+        if (R.seg0[l] + R.nseg[l] == sp.lv[l].P) R.nseg[l - 1] = sp.lv[l - 1].P - a;
+    }
+    return 0;
+}
+
+// The block of an outer separator that a rank hands up (Dsep / rsep of the last segment of each of its levels) is composed
+// level by level as  own block - (Schur contribution of the segment on its left) - (that of the segment on its RIGHT); the
+// segment on the right belongs to the next rank.  The composition is additive, so the next rank subtracts its share -- the
+// left-separator contributions cL / cgL of its first segment of every level below xl -- from the same rows of the exchange
+// buffer, and the sum over the ranks is the complete block.
+struct OuterFix { const double* cL[MAXL]; const double* cgL[MAXL]; double* Dsep; double* rsep; int n; };
+// (C linkage: the symbol it has always had)
+extern "C" __global__ void outer_block_kernel(OuterFix f, Gate gate) {
+    const int t = threadIdx.x;
+    if (t >= 90 || gate_closed(gate)) return;
+    double v = 0.0;
+    for (int i = 0; i < f.n; ++i) v += t < 81 ? f.cL[i][t] : f.cgL[i][t - 81];
+    if (t < 81) f.Dsep[t] = -v; else f.rsep[t - 81] = -v;       // a row of the PREVIOUS rank's segment: nothing else is written there locally
+}
 
 // Up-sweep of levels 0 .. xl over the rank's own segments.  Hd/Ho/rhs: LOCAL level-0 arrays whose row 0 is global node
 // `node0`; exchange: 351*P_xl doubles (array-major like the level-0 products), own rows written -- and the rank's share of its
@@ -13,8 +71,9 @@ int shard_upsweep_gated(double* Hd, const double* Ho, const double* rhs, double 
     const int nl = shard_plan(N, seg_len, sp);
     ShardRanges R;
     if (nl < 2 || shard_ranges(sp, world, rank, R) != 0) return fail(ISLAM_EARG, "islam_pvgo_shard_upsweep: N=%d, world=%d, rank=%d", N, world, rank);
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N)) return fail(ISLAM_EARG, "islam_pvgo_shard_upsweep: workspace too small");
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
+    Workspace w;
+    const int rc_ws = workspace_or_fail("islam_pvgo_shard_upsweep: workspace too small", N, workspace, workspace_bytes, w);
+    if (rc_ws != ISLAM_OK) return rc_ws;
     if (zero_exchange) ISLAM_HIP_CHECK(hipMemsetAsync(exchange, 0, sizeof(double) * 351 * (size_t)sp.lv[R.xl].P, s));
     LevelBufs xb{};
     products_view(exchange, sp.lv[R.xl].P, xb);
@@ -59,8 +118,9 @@ int shard_downsweep_gated(const double* exchange, int N, const int seg_len[2], i
     const int nl = shard_plan(N, seg_len, sp);
     ShardRanges R;
     if (nl < 2 || shard_ranges(sp, world, rank, R) != 0) return fail(ISLAM_EARG, "islam_pvgo_shard_downsweep: N=%d, world=%d, rank=%d", N, world, rank);
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N)) return fail(ISLAM_EARG, "islam_pvgo_shard_downsweep: workspace too small");
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
+    Workspace w;
+    const int rc_ws = workspace_or_fail("islam_pvgo_shard_downsweep: workspace too small", N, workspace, workspace_bytes, w);
+    if (rc_ws != ISLAM_OK) return rc_ws;
     return shard_downsweep_planned(sp, R, w, exchange, world, node0, dx, flags, gate, s);
 }
 // (the plan, the ranges and the carved workspace do not change within a run: the loop in the library computes them once)
@@ -258,101 +318,73 @@ __global__ __launch_bounds__(128) void shard_pack_decide_kernel(PackArgs p, Deci
     if (t < STATE_DOUBLES) d.st[t] = st_l[t];
 }
 
-__global__ void shard_close_gate_kernel(double* __restrict__ st) {
-    if (threadIdx.x == 0) st[14] = -1.0;
-}
-
 size_t shard_fused_scratch_doubles(int N, int world) {
     const size_t n = (size_t)N + 2, ex = 351 * (n / 5 + 2) + 3 + 18 * (size_t)world;
     auto a256 = [](size_t k) { return align_up(k * sizeof(double)) / sizeof(double); };
     return 2 * a256(ex) + 2 * a256(96) + a256(32) + 64;
 }
 
-int run_chain_sharded_fused(const ShardSum& red, int world, int rank, double* nodes, double* vels, const double* poses, const double* drots,
-                            const double* dtrans, const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
-                            void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, islam_pvgo_result* res,
-                            long long* exchanged_bytes, hipStream_t s, int* taken, const double** out_nodes, const double** out_vels,
-                            int* own0, int* own1) {
-    *taken = 0;
-    static const bool off = [] { const char* e = std::getenv("ISLAM_SHARD_FUSED"); return e && e[0] == '0'; }();
-    SolvePlan sp;
-    const int nl = shard_plan(N, prm->seg_len, sp);
-    ShardRanges R;
-    if (off || nl < 2 || shard_ranges(sp, world, rank, R) != 0) return ISLAM_OK;
-    static const int fz_spare = [] { const char* e = std::getenv("ISLAM_FZ_SPARE"); return e ? std::atoi(e) : 16; }();
-    // (the same plans the single-GPU loop fuses, decided on numbers every rank shares: all ranks take the same path)
-    int max_nseg = 0;
-    for (int r = 0; r < world; ++r) {
-        ShardRanges Rr;
-        if (shard_ranges(sp, world, r, Rr) != 0) return ISLAM_OK;
-        max_nseg = std::max(max_nseg, Rr.nseg[0]);
-        if (Rr.nseg[0] < 1) return ISLAM_OK;
-    }
-    const int cus = std::max(device_cus() - fz_spare, 1);
-    if (!(N > 96 && sp.twisted && sp.top == sp.nl - 1 && sp.lv[0].m <= FZ_MAXM && prm->reject < STATE_DOUBLES - STATE_HIST - 1 &&
-          (max_nseg + std::min(max_nseg, cus) - 1) / std::min(max_nseg, cus) <= FZ_S))
-        return ISLAM_OK;
-    if (workspace_bytes < islam_pvgo_workspace_bytes(N)) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: workspace too small");
-    if (scratch_bytes < shard_fused_scratch_doubles(N, world) * sizeof(double)) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: scratch too small");
-    *taken = 1;
-    const int M = N - 1, xl = R.xl, Pxl = sp.lv[xl].P, m = sp.lv[0].m, stride = m + 1;
-    const int seg_lo = R.seg0[0], nseg = R.nseg[0], first_node = seg_lo * stride, sR = (seg_lo + nseg - 1) * stride + m;
-    const bool has_left = seg_lo > 0, has_right = sR < N - 1;
-    const int N_eff = has_right ? sR + 1 : N;
-    const int nwg = std::min(nseg, cus);
-    const int nmsg = 3 + 18 * (world - 1);
-    const size_t nex = 351 * (size_t)Pxl + nmsg;
-    Workspace w = carve((void*)align_up((size_t)workspace), N);
-    double* p = (double*)align_up((size_t)scratch);
-    auto take = [&](size_t k) { double* r = p; p += align_up(k * sizeof(double)) / sizeof(double); return r; };
-    double* ex_own = take(nex);
-    double* ex = world > 1 ? take(nex) : ex_own;
-    double* SH[2] = {take(96), take(96)};
-    double* rep_dev = take(32);
-    {
-        static bool fz_attr_set[64] = {};
-        int dev_i = 0;
-        ISLAM_HIP_CHECK(hipGetDevice(&dev_i));
-        if (dev_i >= 0 && dev_i < 64 && !fz_attr_set[dev_i]) {
-            ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)trial_elim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FZ_LDS_BYTES));
-            fz_attr_set[dev_i] = true;
-        }
-    }
-    static thread_local double* host_state = nullptr;
-    if (!host_state) ISLAM_HIP_CHECK(hipHostMalloc((void**)&host_state, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocPortable));
-    double* report = nullptr;
-    ISLAM_HIP_CHECK(hipHostGetDevicePointer((void**)&report, host_state, 0));
-    volatile double* hs_all = host_state;
-    hs_all[15] = 0.0;
-    hs_all[31] = 0.0;
-    // product rows of other ranks' segments read as zero; the own rows of the exchange buffer are rewritten by every solve
-    if (world > 1)
-        for (int l = 0; l < sp.nl; ++l) ISLAM_HIP_CHECK(hipMemsetAsync(w.lv[l].Dsep, 0, w.lv[l].prod_bytes, s));
-    if (world > 1) ISLAM_HIP_CHECK(hipMemsetAsync(ex_own, 0, sizeof(double) * nex, s));
-    {
-        const int rc_init = enqueue_control_init(w, prm, s);
-        if (rc_init != ISLAM_OK) return rc_init;
-    }
-    const TRParams tr{prm->high, prm->low, prm->up, prm->down, prm->factor, prm->rmin, prm->rmax, prm->reject,
-                      prm->max_steps, prm->patience, prm->decreasing};
-    const LinWeights W{prm->w[0], prm->w[1], prm->w[2], prm->w[3], prm->vmin, prm->vmax};
-    double* LIN[2] = {w.lin, w.lin2};
-    double* HD[2] = {w.Hd, w.Hd2};
-    double* HO[2] = {w.Ho, w.Ho2};
-    double* RH[2] = {w.rhs, w.rhs2};
-    LevelBufs xb{};
-    products_view(ex_own, Pxl, xb);
-    auto level_out = [&](int l) {                              // products of level l: the exchange buffer at the exchange level
+// One rank's run of the fused sharded loop: a ChainRun over the whole chain plus the rank's share of it (ShardRun::setup) and
+// the stages of the loop.
+struct ShardRun : ChainRun {
+    const ShardSum* red;
+    int world, rank;
+    SolvePlan sp; ShardRanges R;
+    int xl, Pxl, m, seg_lo, nseg, first_node, N_eff, nwg, nmsg;
+    bool has_left, has_right;
+    size_t nex;
+    double *ex_own, *ex, *SH[2], *rep_dev;
+    LevelBufs xb;
+    long long xbytes;
+    IterCfg A;                            // the iteration whose verdict is awaited
+    islam_pvgo_result t;                  // ... and what the verdicts have said so far
+    double epoch;
+
+    LevelBufs level_out(int l) const {                         // products of level l: the exchange buffer at the exchange level
         LevelBufs ob = w.lv[l];
         if (l == xl) { ob.Dsep = xb.Dsep; ob.rsep = xb.rsep; ob.cL = xb.cL; ob.cR = xb.cR; ob.fill = xb.fill; ob.cgL = xb.cgL; ob.cgR = xb.cgR; }
         return ob;
-    };
-    int* const eflag_none = w.flags + 6;
-    long long xbytes = 0;
+    }
+
+    // (the ChainRun part, sp and R are in place)
+    int setup(int cus, void* scratch) {
+        const int N = d.N, stride = sp.lv[0].m + 1;
+        xl = R.xl; Pxl = sp.lv[xl].P; m = sp.lv[0].m;
+        seg_lo = R.seg0[0]; nseg = R.nseg[0]; first_node = seg_lo * stride;
+        const int sR = (seg_lo + nseg - 1) * stride + m;
+        has_left = seg_lo > 0; has_right = sR < N - 1;
+        N_eff = has_right ? sR + 1 : N;
+        nwg = std::min(nseg, cus);
+        fz_m = m; fz_P = nseg; fz_nwg = nwg;
+        nmsg = 3 + 18 * (world - 1);
+        nex = 351 * (size_t)Pxl + nmsg;
+        double* p = (double*)align_up((size_t)scratch);
+        auto take = [&](size_t k) { double* q = p; p += align_up(k * sizeof(double)) / sizeof(double); return q; };
+        ex_own = take(nex);
+        ex = world > 1 ? take(nex) : ex_own;
+        SH[0] = take(96); SH[1] = take(96);
+        rep_dev = take(32);
+        int rc = ensure_fused_lds();
+        if (rc != ISLAM_OK) return rc;
+        if ((rc = vb.acquire()) != ISLAM_OK) return rc;
+        // product rows of other ranks' segments read as zero; the own rows of the exchange buffer are rewritten by every solve
+        if (world > 1)
+            for (int l = 0; l < sp.nl; ++l) ISLAM_HIP_CHECK(hipMemsetAsync(w.lv[l].Dsep, 0, w.lv[l].prod_bytes, s));
+        if (world > 1) ISLAM_HIP_CHECK(hipMemsetAsync(ex_own, 0, sizeof(double) * nex, s));
+        if ((rc = enqueue_control_init(w, prm, s)) != ISLAM_OK) return rc;
+        xb = LevelBufs{};
+        products_view(ex_own, Pxl, xb);
+        xbytes = 0;
+        A = IterCfg{0, nodes, vels, w.nodes_t, w.vels_t};
+        t = islam_pvgo_result{};
+        epoch = 1.0;
+        return ISLAM_OK;
+    }
+
     // levels 1 .. xl, the pack, the all-reduce, the decision and the down-sweep behind an eliminated level 0 of buffer pb
     // decision_only: an accepted trial would be the last optimizer step (StopOnPlateau's step limit) -- no solve follows it, only the
     // scalars of the message matter (the blocks in front of them are whatever the buffer holds, the same on every rank)
-    auto enqueue_rest = [&](int pb, int mode, int damp_mode, bool with_trial, double seq, const Gate& gate, bool decision_only = false) -> int {
+    int enqueue_rest(int pb, int mode, int damp_mode, bool with_trial, double seq, const Gate& gate, bool decision_only = false) {
         for (int l = 1; l <= xl && !decision_only; ++l)
             launch_tw(level_src_from(w.lv[l - 1], sp.lv[l - 1].P), level_dst(level_out(l), nullptr), sp.lv[l].n, sp.lv[l].m, w.flags, R.seg0[l],
                       R.nseg[l], gate, s);
@@ -364,7 +396,7 @@ int run_chain_sharded_fused(const ShardSum& red, int world, int rank, double* no
         pa.st = w.state; pa.tr = tr; pa.damp_mode = damp_mode; pa.part = with_trial ? w.part : (const double*)nullptr; pa.nwg = nwg;
         pa.msg = ex_own + 351 * (size_t)Pxl; pa.nmsg = nmsg; pa.rank = rank;
         // the verdict block: straight to the host's slot when no down-sweep follows, else to device memory -- the down-sweep forwards it
-        double* const host_slot = report + 16 * ((long long)seq & 1);
+        double* const host_slot = vb.dev_slot(seq);
         double* const dev_slot = rep_dev + 16 * ((long long)seq & 1);
         const bool forward = mode == 0 && !decision_only;
         DecideArgs da{};
@@ -373,7 +405,7 @@ int run_chain_sharded_fused(const ShardSum& red, int world, int rank, double* no
         da.plain_report = forward ? 1 : 0;
         if (world > 1) {
             hipLaunchKernelGGL(shard_pack_kernel, dim3(1), dim3(128), 0, s, pa, gate);
-            const int r = red.fn(red.self, ex_own, ex, nex, s);
+            const int r = red->fn(red->self, ex_own, ex, nex, s);
             if (r != ISLAM_OK) return r;
             xbytes += 8LL * (long long)nex;
             hipLaunchKernelGGL(shard_decide_kernel, dim3(1), dim3(64), 0, s, da, gate);
@@ -384,77 +416,59 @@ int run_chain_sharded_fused(const ShardSum& red, int world, int rank, double* no
         // (a trial that is not "accepted, continue, damping as speculated" bumps the epoch: the down-sweep turns into a no-op)
         if (decision_only) return ISLAM_OK;
         return shard_downsweep_planned(sp, R, w, ex, world, 0, w.dx, w.flags, gate, s, forward ? dev_slot : (const double*)nullptr, host_slot);
-    };
-    struct IterCfg { int pb; double *cur_n, *cur_v, *tri_n, *tri_v; };
-    auto fused_args = [&](const IterCfg& c, bool first, double seq, int* eprev, bool trial_only = false) {
-        FusedArgs fa{};
-        fa.nodes = c.cur_n; fa.vels = c.cur_v; fa.dx = first ? (const double*)nullptr : w.dx; fa.poses = poses; fa.drots = drots; fa.dtrans = dtrans;
-        fa.dvels = dvels; fa.dts = dts; fa.lin = first ? (const double*)nullptr : LIN[c.pb]; fa.N = N_eff; fa.nodes_t = c.tri_n; fa.vels_t = c.tri_v;
-        fa.part = w.part; fa.st = w.state; fa.flags = w.flags; fa.ticket = nullptr; fa.tr = tr; fa.report = nullptr; fa.seq = seq; fa.W = W;
-        const int ob = first ? c.pb : 1 - c.pb;
-        fa.lin_o = LIN[ob]; fa.Hd_o = HD[ob]; fa.Ho_o = HO[ob]; fa.rhs_o = RH[ob];
+    }
+
+    // trial_elim_kernel over the rank's own level-0 segments: the single-GPU arguments, but the rank's stretch of the chain, the
+    // exchange buffer as the products' home, and neither ticket nor report (the decision follows the all-reduce)
+    FusedArgs shard_fused_args(const IterCfg& c, FusedMode mode, double seq, int* eprev) const {
+        FusedArgs fa = fused_args(*this, c, mode, seq, eprev);
+        fa.N = N_eff; fa.ticket = nullptr; fa.report = nullptr;
         fa.dst = level_dst(level_out(0), w.dx);
-        fa.m = m; fa.P = nseg; fa.nwg = nwg;
-        fa.eflag = w.flags + 4 + (((long long)seq + 1) & 1);
-        fa.eflag_prev = eprev;
-        fa.Ms = M; fa.shard = 1; fa.seg_lo = seg_lo; fa.own_left = has_left ? 1 : 0; fa.share = SH[ob]; fa.open_right = has_right ? 1 : 0;
-        fa.trial_only = trial_only ? 1 : 0;
+        fa.eflag = w.flags + 4 + (((long long)seq + 1) & 1);        // (in every mode)
+        fa.shard = 1; fa.seg_lo = seg_lo; fa.own_left = has_left ? 1 : 0; fa.open_right = has_right ? 1 : 0;
+        fa.share = SH[mode == FUSED_FIRST ? c.pb : 1 - c.pb];
         return fa;
-    };
-    IterCfg A{0, nodes, vels, w.nodes_t, w.vels_t};
-    int steps = 0, trials = 0, status = ISLAM_OK;
-    double loss = 0.0, damping = 1.0 / prm->radius, epoch = 1.0;
-    auto run = [&]() -> int {
+    }
+
+    // trial `seq` of iteration c: trial_elim_kernel (cur + dx -> tri, linearisation at tri, level 0 of solve seq+1) and the rest of
+    // solve seq+1 around the all-reduce
+    // steps_before: optimizer steps finished when this trial is evaluated
+    int enqueue_trial(const IterCfg& c, double seq, double ep, bool prev_fused, int steps_before) {
+        const Gate gate{w.state, ep};
+        const bool last = steps_before + 1 >= prm->max_steps;      // nothing can follow an accepted trial: decision only
+        const FusedArgs fa = shard_fused_args(c, last ? FUSED_TRIAL_ONLY : FUSED_TRIAL_ELIM, seq, prev_fused ? w.flags + 4 + ((long long)seq & 1) : eflag_none());
+        hipLaunchKernelGGL(trial_elim_kernel, dim3(xcd_grid(nwg)), dim3(FZ_THREADS), FZ_LDS_BYTES, s, fa, gate);
+        return enqueue_rest(1 - c.pb, 0, 0, true, seq, gate, last);
+    }
+
+    int loop() {
         int rc;
         {   // the first solve: linearisation at the initial iterate, its loss, elimination with the initial damping
             const Gate gate{w.state, epoch};
-            const FusedArgs fa = fused_args(A, true, 0.0, eflag_none);
+            const FusedArgs fa = shard_fused_args(A, FUSED_FIRST, 0.0, eflag_none());
             hipLaunchKernelGGL(trial_elim_kernel, dim3(xcd_grid(nwg)), dim3(FZ_THREADS), FZ_LDS_BYTES, s, fa, gate);
             if ((rc = enqueue_rest(A.pb, 2, 2, true, 0.0, gate)) != ISLAM_OK) return rc;
         }
-        // trial `seq` of iteration c: trial_elim_kernel (cur + dx -> tri, linearisation at tri, level 0 of solve seq+1) and the rest of
-        // solve seq+1 around the all-reduce
-        // steps_before: optimizer steps finished when this trial is evaluated
-        auto enqueue_trial = [&](const IterCfg& c, double seq, double ep, bool prev_fused, int steps_before) -> int {
-            const Gate gate{w.state, ep};
-            const bool last = steps_before + 1 >= prm->max_steps;      // nothing can follow an accepted trial: decision only
-            const FusedArgs fa = fused_args(c, false, seq, prev_fused ? w.flags + 4 + ((long long)seq & 1) : eflag_none, last);
-            hipLaunchKernelGGL(trial_elim_kernel, dim3(xcd_grid(nwg)), dim3(FZ_THREADS), FZ_LDS_BYTES, s, fa, gate);
-            return enqueue_rest(1 - c.pb, 0, 0, true, seq, gate, last);
-        };
         if ((rc = enqueue_trial(A, 1.0, epoch, true, 0)) != ISLAM_OK) return rc;
         for (;;) {
-            const double seq = (double)(trials + 1);
+            const double seq = (double)(t.trials + 1);
             // run ahead (the verdict of a trial is written BEHIND the all-reduce, too late to launch the next trial on time): trial
             // seq+1 under the assumption "accepted, continue, damping as speculated"; any other verdict bumps the device epoch and the
             // chain -- its collective included, on unchanged buffers, the same on every rank -- runs as no-ops
             const IterCfg B{1 - A.pb, A.tri_n, A.tri_v, A.cur_n, A.cur_v};
-            if (steps + 1 < prm->max_steps && (rc = enqueue_trial(B, seq + 1.0, epoch, true, steps + 1)) != ISLAM_OK) return rc;
-            volatile double* hs = hs_all + 16 * ((long long)seq & 1);
-            {
-                unsigned long spins = 0;
-                while (hs[15] != seq) {
-                    if (++spins > 400000000ul) {
-                        ISLAM_HIP_CHECK(hipStreamSynchronize(s));
-                        if (hs[15] != seq) return fail(ISLAM_EHIP, "islam_pvgo_run_chain_sharded: no status from the device (trial %d)", trials + 1);
-                    }
-                }
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            }
-            ++trials;
-            const int verdict = (int)hs[12];
-            damping = hs[2];
-            loss = hs[0];
-            steps = (int)hs[13];
+            if (t.steps + 1 < prm->max_steps && (rc = enqueue_trial(B, seq + 1.0, epoch, true, t.steps + 1)) != ISLAM_OK) return rc;
+            volatile double* hs = vb.slot(seq);
+            if ((rc = wait_verdict(hs, seq, s, "islam_pvgo_run_chain_sharded: no status from the device (trial %d)")) != ISLAM_OK) return rc;
+            const int verdict = take_verdict(t, hs);
             if (verdict == 0) { A = B; continue; }              // B's trial is the one in flight
             epoch += 1.0;
             if (verdict == 2) { A = B; break; }
-            if (verdict == 4) { status = ISLAM_ENOTPD; break; }
+            if (verdict == 4) { t.status = ISLAM_ENOTPD; break; }
             // the speculative elimination is void: the next solve runs on the launched level-0 kernel from the linearisation in global
             // memory (undamped: the damping list of the state), with its own all-reduce of the interface blocks
             ISLAM_HIP_CHECK(hipMemsetAsync(w.flags + 4 + (((long long)seq + 1) & 1), 0, sizeof(int), s));
             if (verdict == 5) A = B;
-            if (verdict == 3) status = ISLAM_ENOTPD;
+            if (verdict == 3) t.status = ISLAM_ENOTPD;
             {
                 const Gate gate{w.state, epoch};
                 LevelSrc src{};
@@ -462,22 +476,46 @@ int run_chain_sharded_fused(const ShardSum& red, int world, int rank, double* no
                 launch_tw(src, level_dst(level_out(0), nullptr), N_eff, m, w.flags, seg_lo, nseg, gate, s);
                 if ((rc = enqueue_rest(A.pb, 1, 1, false, seq, gate)) != ISLAM_OK) return rc;
             }
-            if ((rc = enqueue_trial(A, seq + 1.0, epoch, false, steps)) != ISLAM_OK) return rc;
+            if ((rc = enqueue_trial(A, seq + 1.0, epoch, false, t.steps)) != ISLAM_OK) return rc;
         }
         return ISLAM_OK;
-    };
-    const int rc = run();
-    if (rc != ISLAM_OK) {
-        hipLaunchKernelGGL(shard_close_gate_kernel, dim3(1), dim3(64), 0, s, w.state);
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-        return rc;
     }
-    res->steps = steps; res->trials = trials; res->status = status; res->loss = loss; res->damping = damping;
-    if (exchanged_bytes) *exchanged_bytes = xbytes;
-    *out_nodes = A.cur_n; *out_vels = A.cur_v;
-    *own0 = has_left ? first_node : 0;
-    *own1 = N_eff;
+};
+
+int run_chain_sharded_fused(const ShardSum& red, int world, int rank, double* nodes, double* vels, const double* poses, const double* drots,
+                            const double* dtrans, const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                            void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, islam_pvgo_result* res,
+                            long long* exchanged_bytes, hipStream_t s, int* taken, const double** out_nodes, const double** out_vels,
+                            int* own0, int* own1) {
+    *taken = 0;
+    static const bool off = env_is("ISLAM_SHARD_FUSED", '0');
+    ShardRun r{};
+    r.red = &red; r.world = world; r.rank = rank;
+    const int nl = shard_plan(N, prm->seg_len, r.sp);
+    if (off || nl < 2 || shard_ranges(r.sp, world, rank, r.R) != 0) return ISLAM_OK;
+    // (the same plans the single-GPU loop fuses, decided on numbers every rank shares: all ranks take the same path)
+    int max_nseg = 0;
+    for (int q = 0; q < world; ++q) {
+        ShardRanges Rq;
+        if (shard_ranges(r.sp, world, q, Rq) != 0) return ISLAM_OK;
+        max_nseg = std::max(max_nseg, Rq.nseg[0]);
+        if (Rq.nseg[0] < 1) return ISLAM_OK;
+    }
+    const int cus = std::max(device_cus() - fz_spare_cus(), 1);
+    if (!(N > 96 && fused_plan_core(r.sp, max_nseg, std::min(max_nseg, cus)) && prm->reject < STATE_DOUBLES - STATE_HIST - 1)) return ISLAM_OK;
+    Workspace w;
+    int rc = workspace_or_fail("islam_pvgo_run_chain_sharded: workspace too small", N, workspace, workspace_bytes, w);
+    if (rc != ISLAM_OK) return rc;
+    if (scratch_bytes < shard_fused_scratch_doubles(N, world) * sizeof(double)) return fail(ISLAM_EARG, "islam_pvgo_run_chain_sharded: scratch too small");
+    *taken = 1;
+    static_cast<ChainRun&>(r) = chain_run(nodes, vels, ChainData{poses, drots, dtrans, dvels, dts, N}, prm, w, s);
+    if ((rc = r.setup(cus, scratch)) != ISLAM_OK) return rc;
+    if ((rc = r.loop()) != ISLAM_OK) return abandon_run(r.w.state, s, rc);
+    *res = r.t;
+    if (exchanged_bytes) *exchanged_bytes = r.xbytes;
+    *out_nodes = r.A.cur_n; *out_vels = r.A.cur_v;
+    *own0 = r.has_left ? r.first_node : 0;
+    *own1 = r.N_eff;
     return ISLAM_OK;
 }
 
@@ -518,10 +556,8 @@ int linbuild_gated(const double* nodes, const double* vels, const double* poses,
     if (rc != ISLAM_OK) return rc;
     ReprojDev rp{};
     if (reproj && (rc = reproj_dev_local(reproj, link0, rp)) != ISLAM_OK) return rc;
-    const LinWeights W{prm->w[0], prm->w[1], prm->w[2], prm->w[3], prm->vmin, prm->vmax};
-    const int nlb = (N + LB_NODES - 1) / LB_NODES;
-    hipLaunchKernelGGL(linbuild_kernel<false>, dim3(xcd_grid(nlb)), dim3(LB_THREADS), LB_DYN_BYTES, s, nodes, vels, poses, drots, dtrans, dvels,
-                       dts, N, W, lin, loss_part, Hd, Ho, rhs, reproj ? red : (const double*)nullptr, rp, gate, RobustDev{});
+    launch_linbuild(nodes, vels, ChainData{poses, drots, dtrans, dvels, dts, N}, lin_weights(prm), LinBufs{lin, Hd, Ho, rhs}, loss_part,
+                    reproj ? red : (const double*)nullptr, rp, gate, nullptr, s);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
