@@ -360,7 +360,7 @@ int islam_scale_ls_depth(const float* depth, const float* flow, const float* pos
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward
- * (integrate + predict; covariance propagation is discarded by the reference and not computed).
+ * (integrate + predict; the reference discards the covariance PyPose propagates beside them: islam_imu_preint_cov below computes it).
  * dt (S), gyro (S,3), acc (S,3): the batch slice (already bias-corrected / denoised);
  * seg (nframes+1) int64: sample offset of each frame boundary inside the slice;
  * init_pos(3), init_rot(4), init_vel(3); motion_mode as imu_integrator.py:69-80.
@@ -396,6 +396,29 @@ size_t islam_imu_preint_bwd_scratch_bytes(int nframes);
 int islam_imu_preint_bwd(const void* dt, const void* gyro, const void* acc, const int64_t* seg, int nframes, int64_t S,
                          double gravity, int motion_mode, const void* fwd_scratch, const void* g_pos, const void* g_rot,
                          const void* g_vel, void* g_gyro, void* g_acc, void* scratch, int dtype, void* stream);
+
+/* Covariance of the pre-integration: what pp.module.IMUPreintegrator(prop_cov=True) propagates beside the increments (PyPose is external:
+ * the definition below is the contract, its match to PyPose is unpinned).  Error state [dphi, dv, dp] (Forster's ordering): dphi is the
+ * right perturbation of the pre-integrated rotation DR, dv and dp are expressed in the body frame at the start of the pre-integration.
+ * For sample j with d = dt_j, w = gyro_j, a = acc_j (as handed to the integrator, gravity NOT removed), DR_j the rotation accumulated in
+ * front of it and dr = Exp(w d):
+ *   A_j = [ dr^T 0 0 ; -DR_j [a]x d  I  0 ; -DR_j [a]x d^2/2  I d  I ],  Bg_j = [ Jr(w d) d ; 0 ; 0 ],  Ba_j = [ 0 ; DR_j d ; DR_j d^2/2 ],
+ *   Sigma_{j+1} = A_j Sigma_j A_j^T + Bg_j diag(sg2) Bg_j^T + Ba_j diag(sa2) Ba_j^T.
+ * gyro_cov, acc_cov: HOST arrays of three per-sample (discrete) variances; gyro_cov_s / acc_cov_s: optional (S,3) device arrays of the I/O
+ * dtype with per-sample variances that replace them (NULL: the constants).  dt, gyro, acc, seg, max_frame_samples: as islam_imu_preint.
+ * motion_mode != 0: out_cov has nframes rows, row i = the recurrence over samples [seg[i], seg[i+1]) from Sigma = 0, DR = I (a frame
+ * without samples: zero).  motion_mode == 0: nframes + 1 rows, row 0 = init_cov (81 doubles in device memory, its symmetric part is
+ * taken; NULL: zero), row k = the recurrence over ALL samples [seg[0], seg[k]) from init_cov with DR accumulated since seg[0] -- the
+ * dead-reckoning uncertainty in the body frame of the window's start (a frame without samples repeats the row in front of it).  The
+ * result does not depend on the initial rotation, position, velocity or gravity.
+ * out_cov: rows x 9 x 9 float64, every row exactly symmetric; the arithmetic is float64 for either dtype.  nframes == 0 is legal.
+ * scratch: islam_imu_preint_cov_scratch_bytes(S, nframes) bytes (world mode; motion mode uses none).  Log-depth: the samples of a frame
+ * are reduced by one wavefront, the frames by a multi-level scan (csrc/imu_cov.hip); no workgroup waits for another. */
+size_t islam_imu_preint_cov_scratch_bytes(int64_t S, int nframes);
+int islam_imu_preint_cov(const void* dt, const void* gyro, const void* acc, const int64_t* seg, int nframes, int64_t S,
+                         int max_frame_samples, const double gyro_cov[3], const double acc_cov[3], const void* gyro_cov_s,
+                         const void* acc_cov_s, const double* init_cov, int motion_mode, double* out_cov, void* scratch, int dtype,
+                         void* stream);
 
 /* ---------------------------------------------------------------- PVGO (pose-velocity graph optimisation) */
 

@@ -4,7 +4,7 @@
 //   imu_integrator.py:116-158  the per-frame Python loop of IMUModule.integrate
 //                              (each iteration ~60 tiny kernels + 3 D2H syncs)
 //   pp.module.IMUPreintegrator.forward = integrate + predict (PyPose, external);
-//   its covariance propagation is discarded by the reference and is not computed.
+//   its covariance propagation, which the reference discards, is a kernel of its own: imu_cov.hip (islam_imu_preint_cov).
 //
 // Floating-point contract: the results are defined to be bit-identical to the plain-C restatement
 // in oracle/imu_preint.c.  Every operation is one IEEE operation in the working precision in the

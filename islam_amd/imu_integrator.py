@@ -3,6 +3,8 @@
 One ``integrate`` call = slice the stream (:94-99), static-bias / denoiser correction (:101-113, PyTorch-ROCm),
 then ONE call into libislam_hip.so for the whole frame loop (:116-158): the reference runs ~60 tiny kernels
 and 3 device->host copies per frame.  Outputs come back on the CPU like the reference's (poses, rots, covs, vels).
+``covs`` is ``[]`` like the reference's unless the module was built with ``prop_cov=True``: then it is the (rows, 9, 9)
+covariance of the pre-integration (islam_imu_preint_cov), which the reference's PyPose integrator propagates and drops.
 """
 import numpy as np
 import torch
@@ -28,7 +30,7 @@ def prase_init(init=None, motion_mode=False, device='cuda:0', dtype=None):
 class IMUModule:
     def __init__(self, accels, gyros, dts, accel_bias=torch.zeros(3), gyro_bias=torch.zeros(3), init=None, gravity=9.81007,
                  rgb2imu_sync=None, device='cuda:0', denoise_model_name=None, denoise_accel=True, denoise_gyro=True,
-                 use_est_cov=False, dtype=None):
+                 use_est_cov=False, dtype=None, prop_cov=False, gyro_cov=(1.6968e-4) ** 2, acc_cov=(2.0e-3) ** 2):
         if torch.device(device).type != 'cuda':
             raise RuntimeError('islam_amd.IMUModule runs on the MI355X only (device=%r); there is no CPU fallback' % (device,))
         self.device = device
@@ -54,6 +56,20 @@ class IMUModule:
         # fix SURVEY section 8f rank 4 asks for: the denoiser runs with grad enabled and the pre-integration is differentiable
         # (islam_imu_preint_bwd), so run_pvgo(target='imu') back-propagates into its parameters.  Default: reference behaviour.
         self.train_denoiser = False
+        # prop_cov: integrate() also returns the 9x9 covariances of the pre-integration, error state [dphi, dv, dp], from the per-sample
+        # measurement variances gyro_cov / acc_cov (a scalar or three values; believed to be PyPose's defaults -- unpinned).  The
+        # denoiser predicts no covariance (IMUCorrector_CNN_GRU_WO_COV returns None for both), so use_est_cov stays inert.
+        self.prop_cov = bool(prop_cov)
+        self.gyro_cov, self.acc_cov = gyro_cov, acc_cov
+
+    def _cov(self, dts, gyros, accels, seg, seg_host, motion_mode, init_cov):
+        """(rows, 9, 9) covariance rows in the module dtype, on the device; forward values only."""
+        if init_cov is not None:
+            init_cov = torch.as_tensor(np.asarray(init_cov, dtype=np.float64)).to(self.device)
+        with torch.no_grad():
+            cov = ops.imu_preint_cov(dts.contiguous(), gyros.detach().contiguous(), accels.detach().contiguous(), seg, seg_host,
+                                     self.gyro_cov, self.acc_cov, motion_mode, None if motion_mode else init_cov)
+        return cov.to(self.dtype)
 
     def _corrected(self, st, end):
         """The stream slice of frames [st, end] after the static-bias / denoiser correction (imu_integrator.py:94-113)."""
@@ -76,14 +92,14 @@ class IMUModule:
                 gyros = d_gyro.to(self.dtype)
         return b0, dts, gyros, accels
 
-    def integrate_both(self, st, end, init=None):
+    def integrate_both(self, st, end, init=None, init_cov=None):
         """``integrate(st, end, init, motion_mode=False)`` and ``integrate(st, end, init, motion_mode=True)`` -- the pair the
         reference's loop asks for on every batch (train.py:200-215) -- from ONE pass over the samples (islam_imu_preint_both: the
         scan, the rotation chain and the frame sums are common to the two modes) and one device->host copy.  Returns the two
         result tuples, bit-identical to the two calls.  Forward values only: with ``train_denoiser`` the two differentiable calls
-        are made instead."""
+        are made instead.  With ``prop_cov`` both tuples carry their covariances (``init_cov``: row 0 of the world rows)."""
         if self.train_denoiser and self.use_denoise_model:
-            return self.integrate(st, end, init, motion_mode=False), self.integrate(st, end, init, motion_mode=True)
+            return self.integrate(st, end, init, motion_mode=False, init_cov=init_cov), self.integrate(st, end, init, motion_mode=True)
         b0, dts, gyros, accels = self._corrected(st, end)
         np_dt = {torch.float32: np.float32, torch.float64: np.float64}[self.dtype]
         i10 = np.zeros(10, dtype=np_dt)
@@ -98,20 +114,28 @@ class IMUModule:
         with torch.no_grad():
             world, motion, packed = ops.imu_preint_both(dts.contiguous(), gyros.detach().contiguous(), accels.detach().contiguous(), seg,
                                                         seg_host, i10[0:3], i10[3:7], i10[7:10], self.gravity)
-        host = packed.cpu()
         n = len(seg_host) - 1
+        if self.prop_cov:                           # the covariances ride in the same device->host copy
+            covs = [self._cov(dts, gyros, accels, seg, seg_host, mm, init_cov) for mm in (False, True)]
+            packed = torch.cat([packed] + [c.reshape(-1) for c in covs])
+        host = packed.cpu()
         res, o = [], 0
         for rows in (n + 1, n):
             pos = host[o:o + rows * 3].view(rows, 3); o += rows * 3
             rot = host[o:o + rows * 4].view(rows, 4); o += rows * 4
             vel = host[o:o + rows * 3].view(rows, 3); o += rows * 3
-            res.append((pos.contiguous(), pp.SO3(rot.contiguous()), [], vel.contiguous()))
-        return res[0], res[1]
+            res.append([pos.contiguous(), pp.SO3(rot.contiguous()), [], vel.contiguous()])
+        if self.prop_cov:
+            for r, rows in zip(res, (n + 1, n)):
+                r[2] = host[o:o + rows * 81].view(rows, 9, 9).contiguous(); o += rows * 81
+        return tuple(res[0]), tuple(res[1])
 
-    def integrate(self, st, end, init=None, motion_mode=False):
+    def integrate(self, st, end, init=None, motion_mode=False, init_cov=None):
         """imu_integrator.py:69-164.  world mode: (end-st+1) rows incl. the initial state; motion mode: (end-st) rows.
         Host traffic per call: one H2D of the 10 initial-state values, one of the frame offsets, one D2H of the packed
-        result (the reference: 3 D2H copies per frame)."""
+        result (the reference: 3 D2H copies per frame).  ``prop_cov``: ``covs`` is the (rows, 9, 9) covariance of the rows
+        (world mode: row 0 = ``init_cov``, None = zero; accumulated over the whole range in the body frame of its start;
+        motion mode: every frame from zero), in the same copy."""
         b0, dts, gyros, accels = self._corrected(st, end)
         # prase_init (imu_integrator.py:11-28) packed into one transfer: [pos(3) | rot(4) | vel(3)]
         np_dt = {torch.float32: np.float32, torch.float64: np.float64}[self.dtype]
@@ -127,5 +151,10 @@ class IMUModule:
         seg = torch.from_numpy(seg_host).to(self.device)
         pos, rot, vel = ops.imu_preint(dts.contiguous(), gyros.contiguous(), accels.contiguous(), seg, seg_host,
                                        i10[0:3], i10[3:7], i10[7:10], self.gravity, motion_mode)
+        if self.prop_cov:
+            cov = self._cov(dts, gyros, accels, seg, seg_host, motion_mode, init_cov)
+            out = torch.cat((pos, rot, vel, cov.reshape(cov.shape[0], 81)), 1).cpu()
+            return (out[:, 0:3].contiguous(), pp.SO3(out[:, 3:7].contiguous()), out[:, 10:91].detach().reshape(-1, 9, 9).contiguous(),
+                    out[:, 7:10].contiguous())
         out = torch.cat((pos, rot, vel), 1).cpu()
         return out[:, 0:3].contiguous(), pp.SO3(out[:, 3:7].contiguous()), [], out[:, 7:10].contiguous()

@@ -798,6 +798,45 @@ def imu_preint(dt, gyro, acc, seg, seg_host, init_pos, init_rot, init_vel, gravi
     return _imu_preint_raw(dt, gyro, acc, seg, seg_host, init_pos, init_rot, init_vel, gravity, motion_mode)[:3]
 
 
+def _variance3(v, name):
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 3)
+    if a.size != 3:
+        raise ValueError('%s: one variance or three, got %d values' % (name, a.size))
+    return (ctypes.c_double * 3)(*a)
+
+
+def imu_preint_cov(dt, gyro, acc, seg, seg_host, gyro_cov, acc_cov, motion_mode, init_cov=None, gyro_cov_s=None, acc_cov_s=None):
+    """Covariance of the pre-integration over the frames of ``seg`` (islam_imu_preint_cov; definition in include/islam_hip.h):
+    (rows, 9, 9) float64 on the device, error state [dphi, dv, dp]; rows = nframes in motion mode, nframes + 1 in world mode
+    (row 0 = ``init_cov``, a 9x9 tensor or None = zero).  gyro_cov / acc_cov: a per-sample variance or three of them;
+    gyro_cov_s / acc_cov_s: optional (S, 3) device tensors of per-sample variances in dt's dtype.  Forward values only."""
+    require_cuda(dt, gyro, acc, seg, init_cov, gyro_cov_s, acc_cov_s)
+    dtype = dt.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = dt.device
+    nframes = int(seg_host.shape[0]) - 1
+    S = int(dt.shape[0])
+    maxF = int(np.max(np.diff(seg_host))) if nframes > 0 else 0
+    for v, name in ((gyro_cov_s, 'gyro_cov_s'), (acc_cov_s, 'acc_cov_s')):
+        if v is not None and (tuple(v.shape) != (S, 3) or v.dtype != dtype or not v.is_contiguous()):
+            raise ValueError('%s: a contiguous (%d, 3) tensor of %s expected' % (name, S, dtype))
+    if init_cov is not None:
+        if tuple(init_cov.shape) != (9, 9):
+            raise ValueError('init_cov: a 9x9 tensor expected, got %s' % (tuple(init_cov.shape),))
+        init_cov = init_cov.to(torch.float64).contiguous()
+    rows = nframes if motion_mode else nframes + 1
+    out = torch.empty((rows, 9, 9), dtype=torch.float64, device=dev)
+    scratch = None
+    if not motion_mode and nframes > 0:
+        scratch = torch.empty(lib().islam_imu_preint_cov_scratch_bytes(S, nframes), dtype=torch.uint8, device=dev)
+    check(lib().islam_imu_preint_cov(ptr(dt), ptr(gyro), ptr(acc), ptr(seg), nframes, S, maxF, _variance3(gyro_cov, 'gyro_cov'),
+                                     _variance3(acc_cov, 'acc_cov'), ptr(gyro_cov_s), ptr(acc_cov_s), ptr(init_cov),
+                                     1 if motion_mode else 0, ptr(out), ptr(scratch), code, stream_ptr(dev)))
+    return out
+
+
 # --------------------------------------------------------------------------- PVGO
 def pvgo_default_params(loss_weight=(1, 1, 1, 1), radius=1e4, seg_len=(0, 0)):
     p = _lib.PvgoParams()
