@@ -420,6 +420,55 @@ int islam_imu_preint_cov(const void* dt, const void* gyro, const void* acc, cons
                          const void* acc_cov_s, const double* init_cov, int motion_mode, double* out_cov, void* scratch, int dtype,
                          void* stream);
 
+/* Bias Jacobians of the pre-integration: J = d[dphi, dv, dp] / d[b_g | b_a], 9x6 by rows, of a FURTHER bias b
+ * subtracted from every sample (sample - b), evaluated at b = 0.  The samples are as handed to the integrator (already bias-corrected /
+ * denoised).  The dphi rows are the right perturbation of DR (DR(b) = DR Exp(J_phig b) to first order), the dv and dp rows are in the
+ * body frame at the start of the pre-integration.  With A_j, Bg_j, Ba_j as defined for islam_imu_preint_cov above:
+ *   J_{j+1} = A_j J_j - [ Bg_j | Ba_j ],  J_0 = 0.
+ * Gravity plays no part: islam_imu_preint subtracts gravity in a gyro-dependent body frame, and the gyro-bias sensitivity of that term
+ * is not part of J (the covariance leaves it out for the same reason).
+ * dt, gyro, acc, seg, max_frame_samples, dtype: as islam_imu_preint_cov.
+ * motion_mode != 0: nframes rows, row i = the recurrence over samples [seg[i], seg[i+1]) from J = 0, DR = I (a frame without samples:
+ * exact zeros).  motion_mode == 0: nframes + 1 rows, row 0 = init_jac (54 doubles in device memory, NULL: zero; its (dphi, b_a) block is
+ * ignored and written as zero), row k = the recurrence over ALL samples [seg[0], seg[k]) from init_jac with DR accumulated since seg[0]
+ * (a frame without samples repeats the row in front of it bit for bit).  To continue a window [0, m) over [m, n) with a second call,
+ * whose elements live in the body frame at sample m: hand it init_jac = diag(I, W^T, W^T) J_m and take diag(I, W, W) times its rows,
+ * W = the rotation DR accumulated over [0, m) (the v and p ROWS are rotated, the dphi rows are not).
+ * out_jac: rows x 9 x 6 float64, the (dphi, b_a) block exactly 0.0; float64 arithmetic from the up-cast samples for either dtype.
+ * nframes == 0 is legal; a second call gives the same bits (fixed association order, no atomics).
+ * scratch: islam_imu_preint_bias_jac_scratch_bytes(S, nframes) bytes (world mode; motion mode uses none).  The frame-reduce /
+ * multi-level-scan structure is islam_imu_preint_cov's (csrc/imu_bias_jac.hip); no workgroup waits for another. */
+size_t islam_imu_preint_bias_jac_scratch_bytes(int64_t S, int nframes);
+int islam_imu_preint_bias_jac(const void* dt, const void* gyro, const void* acc, const int64_t* seg, int nframes, int64_t S,
+                              int max_frame_samples, const double* init_jac, int motion_mode, double* out_jac, void* scratch, int dtype,
+                              void* stream);
+
+/* First-order correction of pre-integrated increments for a bias change (dbg, dba: HOST arrays of three; the samples lose a further
+ * bias): per row, with the row's J of islam_imu_preint_bias_jac,
+ *   DR' = DR Exp(J_phig dbg) (quaternion xyzw, renormalised),  dv' = dv + J_vg dbg + J_va dba,  dp' = dp + J_pg dbg + J_pa dba.
+ * jac (rows, 9, 6) float64; rot (rows, 4), vel, pos (rows, 3) and the outputs in the I/O dtype (float64 arithmetic); the outputs may
+ * alias the inputs.  The increments must be in the START-BODY frame of their row.  islam_imu_preint(motion_mode = 1) returns, for
+ * frame i, rot = DR_i as is, but vel = R0_i dv_i and pos = R0_i dp_i, where R0_i = init_rot DR_0 ... DR_{i-1} is the rotation at the
+ * start of frame i (row i of the world-mode rotations of the same stream): only frame 0 of a call with the identity init_rot is in its
+ * start-body frame already.  The caller rotates vel and pos by R0_i^T before this call and by R0_i after it (rot passes unchanged).
+ * With gravity != 0 those rows also hold the integrated gravity term, which the correction leaves as it is (see above). */
+int islam_imu_bias_correct(const double* jac, const void* rot, const void* vel, const void* pos, int rows, const double dbg[3],
+                           const double dba[3], void* out_rot, void* out_vel, void* out_pos, int dtype, void* stream);
+
+/* Closed-form gyro-bias step from rotation residuals: dbg = argmin sum_i w_i | Log(DR_i^T DRref_i) - J_phig,i dbg |^2 over the rows,
+ * H = sum_i w_i J_phig,i^T J_phig,i.  rot_imu: the pre-integrated relative rotations (rows, 4) xyzw in the I/O dtype, rot_ref: the
+ * relative rotations the caller trusts (VO, PVGO-optimised), jac (rows, 9, 6) float64 of the same rows, weight (rows) float64 device
+ * memory or NULL = all ones.  out_dbg: 3 doubles, out_H: 9 doubles or NULL (device memory).  The gyro bias to subtract from the samples
+ * becomes bias + dbg.  A row whose weight is zero takes no part, exactly as if it were not there (the rows that count are compacted in
+ * row order and summed in a fixed order, no atomics: a second call gives the same bits).  A row of non-zero weight whose residual or
+ * weight is not finite is excluded and counted.
+ * Returns the number of excluded rows (>= 0), or ISLAM_ENOTPD when H is singular (a Cholesky pivot <= 1e-13 of its diagonal entry;
+ * out_dbg is then zero, out_H is still written), or ISLAM_EARG.  The call synchronises the stream (one 8-byte read-back).
+ * scratch: islam_imu_gyro_bias_solve_scratch_bytes(rows) bytes. */
+size_t islam_imu_gyro_bias_solve_scratch_bytes(int rows);
+int islam_imu_gyro_bias_solve(const double* jac, const void* rot_imu, const void* rot_ref, const double* weight, int rows,
+                              double* out_dbg, double* out_H, void* scratch, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- PVGO (pose-velocity graph optimisation) */
 
 typedef struct {

@@ -5,6 +5,8 @@ then ONE call into libislam_hip.so for the whole frame loop (:116-158): the refe
 and 3 device->host copies per frame.  Outputs come back on the CPU like the reference's (poses, rots, covs, vels).
 ``covs`` is ``[]`` like the reference's unless the module was built with ``prop_cov=True``: then it is the (rows, 9, 9)
 covariance of the pre-integration (islam_imu_preint_cov), which the reference's PyPose integrator propagates and drops.
+``bias_jac=True`` keeps the (rows, 9, 6) bias Jacobians of the rows (islam_imu_preint_bias_jac) on the module as
+``last_bias_jac``; ``estimate_gyro_bias`` recovers a gyro bias from trusted relative rotations in closed form.
 """
 import numpy as np
 import torch
@@ -30,7 +32,8 @@ def prase_init(init=None, motion_mode=False, device='cuda:0', dtype=None):
 class IMUModule:
     def __init__(self, accels, gyros, dts, accel_bias=torch.zeros(3), gyro_bias=torch.zeros(3), init=None, gravity=9.81007,
                  rgb2imu_sync=None, device='cuda:0', denoise_model_name=None, denoise_accel=True, denoise_gyro=True,
-                 use_est_cov=False, dtype=None, prop_cov=False, gyro_cov=(1.6968e-4) ** 2, acc_cov=(2.0e-3) ** 2):
+                 use_est_cov=False, dtype=None, prop_cov=False, gyro_cov=(1.6968e-4) ** 2, acc_cov=(2.0e-3) ** 2,
+                 bias_jac=False):
         if torch.device(device).type != 'cuda':
             raise RuntimeError('islam_amd.IMUModule runs on the MI355X only (device=%r); there is no CPU fallback' % (device,))
         self.device = device
@@ -61,6 +64,15 @@ class IMUModule:
         # denoiser predicts no covariance (IMUCorrector_CNN_GRU_WO_COV returns None for both), so use_est_cov stays inert.
         self.prop_cov = bool(prop_cov)
         self.gyro_cov, self.acc_cov = gyro_cov, acc_cov
+        # bias_jac: integrate() / integrate_both() also leave the (rows, 9, 6) Jacobians of the rows w.r.t. a further gyro / accelerometer
+        # bias on the module (CPU, module dtype; integrate_both: the (world, motion) pair).  The returned tuples do not change.
+        self.bias_jac = bool(bias_jac)
+        self.last_bias_jac = None
+
+    def _jac(self, dts, gyros, accels, seg, seg_host, motion_mode):
+        """(rows, 9, 6) bias Jacobians in the module dtype, on the device; forward values only."""
+        return ops.imu_preint_bias_jac(dts.contiguous(), gyros.detach().contiguous(), accels.detach().contiguous(), seg, seg_host,
+                                       motion_mode).to(self.dtype)
 
     def _cov(self, dts, gyros, accels, seg, seg_host, motion_mode, init_cov):
         """(rows, 9, 9) covariance rows in the module dtype, on the device; forward values only."""
@@ -118,6 +130,9 @@ class IMUModule:
         if self.prop_cov:                           # the covariances ride in the same device->host copy
             covs = [self._cov(dts, gyros, accels, seg, seg_host, mm, init_cov) for mm in (False, True)]
             packed = torch.cat([packed] + [c.reshape(-1) for c in covs])
+        if self.bias_jac:
+            jacs = [self._jac(dts, gyros, accels, seg, seg_host, mm) for mm in (False, True)]
+            packed = torch.cat([packed] + [j.reshape(-1) for j in jacs])
         host = packed.cpu()
         res, o = [], 0
         for rows in (n + 1, n):
@@ -128,6 +143,11 @@ class IMUModule:
         if self.prop_cov:
             for r, rows in zip(res, (n + 1, n)):
                 r[2] = host[o:o + rows * 81].view(rows, 9, 9).contiguous(); o += rows * 81
+        if self.bias_jac:
+            pair = []
+            for rows in (n + 1, n):
+                pair.append(host[o:o + rows * 54].view(rows, 9, 6).contiguous()); o += rows * 54
+            self.last_bias_jac = tuple(pair)
         return tuple(res[0]), tuple(res[1])
 
     def integrate(self, st, end, init=None, motion_mode=False, init_cov=None):
@@ -151,10 +171,41 @@ class IMUModule:
         seg = torch.from_numpy(seg_host).to(self.device)
         pos, rot, vel = ops.imu_preint(dts.contiguous(), gyros.contiguous(), accels.contiguous(), seg, seg_host,
                                        i10[0:3], i10[3:7], i10[7:10], self.gravity, motion_mode)
+        cols = [pos, rot, vel]
         if self.prop_cov:
             cov = self._cov(dts, gyros, accels, seg, seg_host, motion_mode, init_cov)
-            out = torch.cat((pos, rot, vel, cov.reshape(cov.shape[0], 81)), 1).cpu()
-            return (out[:, 0:3].contiguous(), pp.SO3(out[:, 3:7].contiguous()), out[:, 10:91].detach().reshape(-1, 9, 9).contiguous(),
-                    out[:, 7:10].contiguous())
-        out = torch.cat((pos, rot, vel), 1).cpu()
-        return out[:, 0:3].contiguous(), pp.SO3(out[:, 3:7].contiguous()), [], out[:, 7:10].contiguous()
+            cols.append(cov.reshape(cov.shape[0], 81))
+        if self.bias_jac:                           # rides in the same device->host copy, behind the covariance columns
+            jac = self._jac(dts, gyros, accels, seg, seg_host, motion_mode)
+            cols.append(jac.reshape(jac.shape[0], 54))
+        out = torch.cat(cols, 1).cpu()
+        if self.bias_jac:
+            self.last_bias_jac = out[:, -54:].detach().reshape(-1, 9, 6).contiguous()
+        covs = out[:, 10:91].detach().reshape(-1, 9, 9).contiguous() if self.prop_cov else []
+        return out[:, 0:3].contiguous(), pp.SO3(out[:, 3:7].contiguous()), covs, out[:, 7:10].contiguous()
+
+    def estimate_gyro_bias(self, st, end, ref_rots, weight=None):
+        """Gyro bias of frames [st, end] from relative rotations the caller trusts (``ref_rots``: (end - st, 4) xyzw quaternions or an
+        SO3, frame i -> i + 1: VO or PVGO-optimised), in closed form: the motion rows are integrated with the module's current
+        ``gyro_bias`` subtracted (whatever ``optm_bias`` says; the denoiser is not run), their rotations and bias Jacobians give
+        dbg = argmin sum_i w_i |Log(DR_i^T ref_i) - J_phig,i dbg|^2 (islam_imu_gyro_bias_solve).  Returns (``gyro_bias + dbg`` (3) and
+        the 3x3 normal matrix H, both on the CPU in float64).  The module is not changed."""
+        b0 = int(self.rgb2imu_sync[st])
+        b1 = int(self.rgb2imu_sync[end]) + 1
+        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
+        seg = torch.from_numpy(seg_host).to(self.device)
+        ref = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
+        ref = ref.detach().to(self.dtype).to(self.device)
+        if weight is not None:
+            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+        with torch.no_grad():
+            dts = self.dts[b0:b1, 0].contiguous()
+            gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
+            accels = self.accels[b0:b1].contiguous()
+            init = torch.zeros(10, dtype=self.dtype, device=self.device)
+            init[6] = 1.0
+            _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
+            jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
+            dbg, H, _ = ops.imu_gyro_bias_solve(jac, rot, ref, weight)
+            res = torch.cat((self.gyro_bias.to(torch.float64) + dbg, H.reshape(9))).cpu()
+        return res[0:3].contiguous(), res[3:12].view(3, 3).contiguous()

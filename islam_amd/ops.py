@@ -837,6 +837,88 @@ def imu_preint_cov(dt, gyro, acc, seg, seg_host, gyro_cov, acc_cov, motion_mode,
     return out
 
 
+def imu_preint_bias_jac(dt, gyro, acc, seg, seg_host, motion_mode, init_jac=None):
+    """Bias Jacobians of the pre-integration over the frames of ``seg`` (islam_imu_preint_bias_jac; definition in
+    include/islam_hip.h): (rows, 9, 6) float64 on the device, rows [dphi, dv, dp], columns [b_g | b_a]; rows = nframes in motion
+    mode, nframes + 1 in world mode (row 0 = ``init_jac``, a 9x6 tensor or None = zero).  Forward values only."""
+    require_cuda(dt, gyro, acc, seg, init_jac)
+    code = {torch.float32: 0, torch.float64: 1}[dt.dtype]
+    dev = dt.device
+    nframes = int(seg_host.shape[0]) - 1
+    S = int(dt.shape[0])
+    maxF = int(np.max(np.diff(seg_host))) if nframes > 0 else 0
+    if init_jac is not None:
+        if tuple(init_jac.shape) != (9, 6):
+            raise ValueError('init_jac: a 9x6 tensor expected, got %s' % (tuple(init_jac.shape),))
+        init_jac = init_jac.to(torch.float64).contiguous()
+    rows = nframes if motion_mode else nframes + 1
+    with torch.no_grad():
+        out = torch.empty((rows, 9, 6), dtype=torch.float64, device=dev)
+        scratch = None
+        if not motion_mode and nframes > 0:
+            scratch = torch.empty(lib().islam_imu_preint_bias_jac_scratch_bytes(S, nframes), dtype=torch.uint8, device=dev)
+        check(lib().islam_imu_preint_bias_jac(ptr(dt), ptr(gyro), ptr(acc), ptr(seg), nframes, S, maxF,
+                                              None if motion_mode else ptr(init_jac), 1 if motion_mode else 0, ptr(out), ptr(scratch),
+                                              code, stream_ptr(dev)))
+    return out
+
+
+def _rows_of(jac, rot):
+    rows = int(jac.shape[0])
+    if tuple(jac.shape) != (rows, 9, 6) or jac.dtype != torch.float64 or not jac.is_contiguous():
+        raise ValueError('jac: a contiguous (rows, 9, 6) float64 tensor expected, got %s %s' % (tuple(jac.shape), jac.dtype))
+    if tuple(rot.shape) != (rows, 4):
+        raise ValueError('rotations: (%d, 4) expected, got %s' % (rows, tuple(rot.shape)))
+    return rows
+
+
+def imu_bias_correct(jac, rot, vel, pos, dbg, dba):
+    """First-order correction of pre-integrated increments in their start-body frame for a further bias (dbg, dba: three values
+    each) subtracted from the samples (islam_imu_bias_correct; include/islam_hip.h says how motion rows of a non-identity start
+    rotation must be rotated first).  jac (rows, 9, 6) float64; rot (rows, 4) xyzw, vel, pos (rows, 3) in float32 or float64.
+    Returns new (rot, vel, pos).  Forward values only."""
+    require_cuda(jac, rot, vel, pos)
+    rows = _rows_of(jac, rot)
+    dtype = rot.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    with torch.no_grad():
+        rot, vel, pos = (t.detach().to(dtype).contiguous() for t in (rot, vel, pos))
+        if tuple(vel.shape) != (rows, 3) or tuple(pos.shape) != (rows, 3):
+            raise ValueError('vel / pos: (%d, 3) expected' % rows)
+        out = [torch.empty_like(t) for t in (rot, vel, pos)]
+        g3 = (ctypes.c_double * 3)(*np.asarray(torch.as_tensor(dbg).detach().cpu(), dtype=np.float64).reshape(3))
+        a3 = (ctypes.c_double * 3)(*np.asarray(torch.as_tensor(dba).detach().cpu(), dtype=np.float64).reshape(3))
+        check(lib().islam_imu_bias_correct(ptr(jac), ptr(rot), ptr(vel), ptr(pos), rows, g3, a3, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                           code, stream_ptr(rot.device)))
+    return tuple(out)
+
+
+def imu_gyro_bias_solve(jac, rot_imu, rot_ref, weight=None):
+    """Closed-form gyro-bias step (islam_imu_gyro_bias_solve): dbg minimises sum_i w_i |Log(rot_imu_i^T rot_ref_i) - J_phig,i dbg|^2.
+    Returns (dbg (3) float64, H (3, 3) float64, number of rows excluded for a non-finite residual); the bias to subtract from the
+    gyro samples becomes bias + dbg.  Raises IslamHipError (code ISLAM_ENOTPD) when H is singular.  Synchronises the stream."""
+    require_cuda(jac, rot_imu, rot_ref, weight)
+    rows = _rows_of(jac, rot_imu)
+    dtype = rot_imu.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = jac.device
+    with torch.no_grad():
+        rot_imu, rot_ref = rot_imu.detach().contiguous(), rot_ref.detach().to(dtype).contiguous()
+        if tuple(rot_ref.shape) != (rows, 4):
+            raise ValueError('rot_ref: (%d, 4) expected, got %s' % (rows, tuple(rot_ref.shape)))
+        if weight is not None:
+            weight = weight.detach().to(torch.float64).contiguous()
+            if tuple(weight.shape) != (rows,):
+                raise ValueError('weight: (%d,) expected, got %s' % (rows, tuple(weight.shape)))
+        out = torch.empty(12, dtype=torch.float64, device=dev)
+        scratch = torch.empty(lib().islam_imu_gyro_bias_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
+        rc = lib().islam_imu_gyro_bias_solve(ptr(jac), ptr(rot_imu), ptr(rot_ref), ptr(weight), rows, ptr(out[0:3]), ptr(out[3:12]),
+                                             ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return out[0:3], out[3:12].view(3, 3), int(rc)
+
+
 # --------------------------------------------------------------------------- PVGO
 def pvgo_default_params(loss_weight=(1, 1, 1, 1), radius=1e4, seg_len=(0, 0)):
     p = _lib.PvgoParams()
