@@ -469,6 +469,47 @@ size_t islam_imu_gyro_bias_solve_scratch_bytes(int rows);
 int islam_imu_gyro_bias_solve(const double* jac, const void* rot_imu, const void* rot_ref, const double* weight, int rows,
                               double* out_dbg, double* out_H, void* scratch, int dtype, void* stream);
 
+/* Gravity, accelerometer bias and velocities from pre-integrated increments and trusted poses, in closed form (DESIGN.md section 3.13;
+ * the linear visual-inertial alignment of ORB-SLAM-VI / VINS-Mono).  n = rows intervals i = 0 .. n-1 between n + 1 poses.  Given
+ *   R_i, p_i   world rotation (xyzw) and position of the IMU BODY at pose i = 0 .. n (VO or PVGO; the caller applies rgb2imu),
+ *   d_i        the duration of interval i,
+ *   dv_i, dp_i the gravity-free pre-integrated increments of interval i in the body frame at its start (islam_imu_preint motion rows
+ *              with gravity 0, rotated by R0_i^T as described for islam_imu_bias_correct),
+ *   Jv_i = J_va,i, Jp_i = J_pa,i   the 3x3 blocks (rows 3:6 and 6:9, columns 3:6) of the row's islam_imu_preint_bias_jac Jacobian,
+ * the unknowns are the gravity g (the world acceleration: v' = R a + g), a further accelerometer bias b (sample - b) and the world
+ * velocities v_0 .. v_n:
+ *   p_{i+1} = p_i + v_i d_i + g d_i^2 / 2 + R_i (dp_i + Jp_i b)        (P_i)
+ *   v_{i+1} = v_i + g d_i + R_i (dv_i + Jv_i b)                        (V_i)
+ * (P_i) defines v_i for i < n; put into (V_i) it leaves, for every pair of consecutive intervals i = 0 .. n-2, three equations in
+ * x = [g; b] alone:
+ *   A_i x = r_i,   A_i = [ -(d_i + d_{i+1}) / 2 I  |  R_i Jp_i / d_i - R_{i+1} Jp_{i+1} / d_{i+1} - R_i Jv_i ],
+ *   r_i = (p_{i+1} - p_i) / d_i - (p_{i+2} - p_{i+1}) / d_{i+1} + R_{i+1} dp_{i+1} / d_{i+1} - R_i dp_i / d_i + R_i dv_i.
+ * x = argmin sum_i w_i | L_i^-1 (A_i x - r_i) |^2,  H = sum_i w_i A_i^T C_i^-1 A_i (6x6),  c = sum_i w_i A_i^T C_i^-1 r_i.
+ * weight: (rows - 1) float64 per pair, NULL = all ones.  cov: the (rows, 9, 9) islam_imu_preint_cov motion rows S_i (error state
+ * [phi, v, p], subscripts name its 3x3 blocks) or NULL; with them C_i = L_i L_i^T is the pair's covariance
+ *   C_i = R_{i+1} S_{i+1}^pp R_{i+1}^T / d_{i+1}^2 + R_i ( S_i^pp / d_i^2 - (S_i^pv + S_i^vp) / d_i + S_i^vv ) R_i^T,
+ * without them C_i = I.  Neighbouring pairs share interval i + 1; their correlation is neglected.  jac NULL: b is not estimated, the
+ * system is 3x3 in g and the b outputs are exact zeros.  The velocities follow by back-substitution: v_i, i < n, from (P_i), v_n from
+ * (V_{n-1}); a pose whose own interval has d <= 0 takes (P), (V) of the interval in front of it, and NaN if that has d <= 0 as well.
+ * gravity_norm = G > 0: gravity of known magnitude, on the same quadratic form x^T H x - 2 x^T c with no second pass over the data:
+ * gh = g / |g| of the free solve; four times: b1 = normalise(e - (e . gh) gh) with e the coordinate axis of the smallest |gh . e|
+ * (lowest index on a tie), b2 = gh x b1, the 5x5 (2x2 without jac) projection of (H, c) onto g = G gh + [b1 b2] u solved for (u, b),
+ * gh <- normalise(G gh + [b1 b2] u); the outputs are g = G gh and the b of the last round.  gravity_norm = 0: the free solve.
+ * A pair takes part if its weight is finite and non-zero, its A_i, r_i are finite, its d are > 0 and, with cov, C_i factorises (a
+ * Cholesky pivot <= 1e-13 of its diagonal entry fails, as in islam_imu_gyro_bias_solve).  A pair of weight zero takes no part,
+ * whatever its data holds, and is not counted; any other pair that does not take part is excluded and counted.
+ * rot_ref (rows + 1, 4), pos_ref (rows + 1, 3), dts (rows), dvel, dpos (rows, 3) in the I/O dtype; jac (rows, 9, 6), cov, weight
+ * float64; float64 arithmetic for either dtype.  out_x: 6 doubles [g, b]; out_H: 36 doubles or NULL; out_vel: (rows + 1, 3) doubles
+ * or NULL (all device memory).  Returns the number of excluded pairs (>= 0), or ISLAM_ENOTPD when H (or its 3x3 / 5x5 / 2x2 form)
+ * fails the pivot rule or no pair takes part (rows <= 1 included): out_x and out_vel are then zeros, out_H is still written; or
+ * ISLAM_EARG.  The sum runs in an order that depends on rows alone, without atomics: a second call gives the same bits, and a pair of
+ * weight zero gives the bits of the same call with other data behind that weight.  The call synchronises the stream (one 8-byte
+ * read-back).  scratch: islam_imu_gravity_bias_solve_scratch_bytes(rows) bytes. */
+size_t islam_imu_gravity_bias_solve_scratch_bytes(int rows);
+int islam_imu_gravity_bias_solve(const void* rot_ref, const void* pos_ref, const void* dts, const void* dvel, const void* dpos,
+                                 const double* jac, const double* cov, const double* weight, int rows, double gravity_norm, double* out_x,
+                                 double* out_H, double* out_vel, void* scratch, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- PVGO (pose-velocity graph optimisation) */
 
 typedef struct {

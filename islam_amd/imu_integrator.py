@@ -209,3 +209,48 @@ class IMUModule:
             dbg, H, _ = ops.imu_gyro_bias_solve(jac, rot, ref, weight)
             res = torch.cat((self.gyro_bias.to(torch.float64) + dbg, H.reshape(9))).cpu()
         return res[0:3].contiguous(), res[3:12].view(3, 3).contiguous()
+
+    def estimate_gravity_accel_bias(self, st, end, ref_rots, ref_pos, weight=None, use_cov=False, gravity_norm=None):
+        """Gravity, accelerometer bias and velocities of frames [st, end] from world poses of the IMU body the caller trusts
+        (``ref_rots``: (end - st + 1, 4) xyzw quaternions or an SO3, ``ref_pos``: (end - st + 1, 3); VO or PVGO-optimised, rgb2imu
+        applied), in closed form (islam_imu_gravity_bias_solve).  The motion rows are integrated with gravity 0 and the module's
+        current ``gyro_bias`` and ``accel_bias`` subtracted (whatever ``optm_bias`` says; the denoiser is not run) and brought into the
+        start-body frame of their frame; their bias Jacobians and, with ``use_cov``, their motion-mode covariances (the module's
+        ``gyro_cov`` / ``acc_cov``) enter the solve; the duration of a frame is the sum of its ``dt``.  ``weight``: (end - st - 1) per
+        pair of consecutive frames; ``gravity_norm``: the known magnitude of gravity, None = free.  Returns (gravity (3) in the frame
+        of the poses, ``accel_bias + b`` (3), velocities (end - st + 1, 3), the 6x6 normal matrix H), on the CPU in float64.  The
+        gravity is the world acceleration (v' = R a + g), about (0, 0, -9.81) in a z-up world.  Run ``estimate_gyro_bias`` first: the
+        gyro-bias sensitivity of the increments is not part of this solve.  The module is not changed."""
+        b0 = int(self.rgb2imu_sync[st])
+        b1 = int(self.rgb2imu_sync[end]) + 1
+        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
+        seg = torch.from_numpy(seg_host).to(self.device)
+        n = len(seg_host) - 1
+        rots = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
+        rots = rots.detach().to(self.dtype).to(self.device)
+        poss = torch.as_tensor(np.asarray(ref_pos)).detach().to(self.dtype).to(self.device)
+        if weight is not None:
+            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+        with torch.no_grad():
+            dts = self.dts[b0:b1, 0].contiguous()
+            gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
+            accels = (self.accels[b0:b1] - self.accel_bias.view(1, 3)).contiguous()
+            init = torch.zeros(10, dtype=self.dtype, device=self.device)
+            init[6] = 1.0
+            world, motion, _ = ops.imu_preint_both(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0)
+            # motion rows hold R0_i dv_i, R0_i dp_i with R0_i = row i of the world rotations from the identity (include/islam_hip.h)
+            R0t = pp._qmat(world[1][:n].to(torch.float64)).transpose(-1, -2)
+            dvel = (R0t @ motion[2].to(torch.float64).unsqueeze(-1)).squeeze(-1).to(self.dtype)
+            dpos = (R0t @ motion[0].to(torch.float64).unsqueeze(-1)).squeeze(-1).to(self.dtype)
+            # d_i = the sum of the frame's dt, in a fixed order: the frames padded to the longest one
+            maxF = int(np.max(np.diff(seg_host))) if n > 0 else 0
+            idx = seg[:-1, None] + torch.arange(max(maxF, 1), device=self.device)[None, :]
+            inside = idx < seg[1:, None]
+            dur = torch.where(inside, dts.to(torch.float64)[idx.clamp(max=max(b1 - b0 - 1, 0))], torch.zeros((), dtype=torch.float64,
+                              device=self.device)).sum(1).to(self.dtype)
+            jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
+            cov = ops.imu_preint_cov(dts, gyros, accels, seg, seg_host, self.gyro_cov, self.acc_cov, True) if use_cov else None
+            g, b, H, vel, _ = ops.imu_gravity_bias_solve(rots, poss, dur, dvel, dpos, jac, cov, weight, gravity_norm)
+            res = torch.cat((g, self.accel_bias.to(torch.float64) + b, vel.reshape(-1), H.reshape(36))).cpu()
+        o = 6 + 3 * (n + 1)
+        return res[0:3].contiguous(), res[3:6].contiguous(), res[6:o].view(n + 1, 3).contiguous(), res[o:o + 36].view(6, 6).contiguous()

@@ -919,6 +919,41 @@ def imu_gyro_bias_solve(jac, rot_imu, rot_ref, weight=None):
     return out[0:3], out[3:12].view(3, 3), int(rc)
 
 
+def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None, weight=None, gravity_norm=None):
+    """Gravity, accelerometer bias and velocities from pre-integrated increments and trusted body poses, in closed form
+    (islam_imu_gravity_bias_solve; definition in include/islam_hip.h).  rot_ref (rows + 1, 4) xyzw, pos_ref (rows + 1, 3): world
+    poses of the IMU body; dts (rows), dvel, dpos (rows, 3): duration and gravity-free increments of every interval in its
+    start-body frame, float32 or float64 (dts' dtype); jac (rows, 9, 6) float64 or None (no bias is estimated), cov (rows, 9, 9)
+    float64 motion-mode covariances or None (unit weights), weight (rows - 1) per pair or None, gravity_norm: the known magnitude
+    or None.  Returns (g (3), b (3), H (6, 6), vel (rows + 1, 3), number of excluded pairs), float64 on the device.  Raises
+    IslamHipError (code ISLAM_ENOTPD) when the normal matrix is singular.  Synchronises the stream."""
+    require_cuda(rot_ref, pos_ref, dts, dvel, dpos, jac, cov, weight)
+    rows = int(dts.shape[0])
+    dtype = dts.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = dts.device
+    with torch.no_grad():
+        io = [t.detach().to(dtype).contiguous() for t in (rot_ref, pos_ref, dts, dvel, dpos)]
+        for t, shape, name in zip(io, ((rows + 1, 4), (rows + 1, 3), (rows,), (rows, 3), (rows, 3)), ('rot_ref', 'pos_ref', 'dts', 'dvel', 'dpos')):
+            if tuple(t.shape) != shape:
+                raise ValueError('%s: %s expected, got %s' % (name, shape, tuple(t.shape)))
+        f64 = []
+        for t, shape, name in ((jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight')):
+            if t is not None:
+                t = t.detach().to(torch.float64).contiguous()
+                if tuple(t.shape) != shape:
+                    raise ValueError('%s: %s expected, got %s' % (name, shape, tuple(t.shape)))
+            f64.append(t)
+        out = torch.empty(42 + 3 * (rows + 1), dtype=torch.float64, device=dev)
+        scratch = torch.empty(lib().islam_imu_gravity_bias_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
+        rc = lib().islam_imu_gravity_bias_solve(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows,
+                                                c_double(0.0 if gravity_norm is None else float(gravity_norm)), ptr(out[0:6]),
+                                                ptr(out[6:42]), ptr(out[42:]), ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return out[0:3], out[3:6], out[6:42].view(6, 6), out[42:].view(rows + 1, 3), int(rc)
+
+
 # --------------------------------------------------------------------------- PVGO
 def pvgo_default_params(loss_weight=(1, 1, 1, 1), radius=1e4, seg_len=(0, 0)):
     p = _lib.PvgoParams()
