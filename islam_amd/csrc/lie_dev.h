@@ -6,9 +6,9 @@
 //
 // Everything is register-resident: 3x3 matrices are nine named scalars in a struct that is only
 // ever indexed with compile-time constants (runtime-indexed arrays would go to scratch memory).
-// Small-angle branches switch to Taylor series below 1e-2 rad: PyPose switches only at machine
-// eps, where its closed forms lose up to all digits to cancellation ((t^2+2cos t-2)/2t^4 ...);
-// the series agree with the closed forms to < 1e-13 at the switch point.
+// Small-angle branches switch to Taylor series below 1e-2 rad (se3_Q: below 0.1 rad, see there): PyPose
+// switches only at machine eps, where its closed forms lose up to all digits to cancellation
+// ((t^2+2cos t-2)/2t^4 ...); tests/test_lie_gpu.py holds every branch to a 50-digit reference.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -153,11 +153,14 @@ template <class T> ISLAM_DEV M3<T> so3_Jl(V3<T> phi) {
     return m3_identity<T>() + c1 * K + c2 * (K * K);
 }
 
-// Barfoot's Q(rho, phi) (PyPose calcQ)
+// Barfoot's Q(rho, phi) (PyPose calcQ).  Its closed forms cancel harder than the others: th^2 + 2cos th - 2 keeps th^4/12 of
+// terms of size th^2, so at th = 1e-2 c2 has 1e-8 left and Q (times rho) is off by ~1e-12 -- 600 rounding floors, measured
+// against a 50-digit reference (tests/golden/make_lie_golden.py).  Hence the series up to th = 0.1, two more terms each;
+// there the closed forms are good to ~4e-14 |rho|.
 template <class T> ISLAM_DEV M3<T> se3_Q(V3<T> rho, V3<T> phi) {
     T th2 = dot(phi, phi);
     T c1, c2, c3;
-    if (th2 > T(1e-4)) {
+    if (th2 > T(1e-2)) {
         T th = sqrt(th2);
         T s, co;
         sincos(th, &s, &co);
@@ -166,9 +169,13 @@ template <class T> ISLAM_DEV M3<T> se3_Q(V3<T> rho, V3<T> phi) {
         c2 = (th2 + T(2) * co - T(2)) / (T(2) * th4);
         c3 = (T(2) * th - T(3) * s + th * co) / (T(2) * th4 * th);
     } else {
-        c1 = T(1.0 / 6.0) - th2 * T(1.0 / 120.0) + th2 * th2 * T(1.0 / 5040.0);
-        c2 = T(1.0 / 24.0) - th2 * T(1.0 / 720.0) + th2 * th2 * T(1.0 / 40320.0);
-        c3 = T(1.0 / 120.0) - th2 * T(1.0 / 2520.0) + th2 * th2 * T(1.0 / 120960.0);
+        T th4 = th2 * th2;
+        c1 = T(1.0 / 6.0) - th2 * T(1.0 / 120.0) + th4 * T(1.0 / 5040.0) - th4 * th2 * T(1.0 / 362880.0) +
+             th4 * th4 * T(1.0 / 39916800.0);
+        c2 = T(1.0 / 24.0) - th2 * T(1.0 / 720.0) + th4 * T(1.0 / 40320.0) - th4 * th2 * T(1.0 / 3628800.0) +
+             th4 * th4 * T(1.0 / 479001600.0);
+        c3 = T(1.0 / 120.0) - th2 * T(1.0 / 2520.0) + th4 * T(1.0 / 120960.0) - th4 * th2 * T(1.0 / 9979200.0) +
+             th4 * th4 * T(1.0 / 1245404160.0);
     }
     M3<T> Tm = skew(rho), P = skew(phi);
     M3<T> PT = P * Tm, TP = Tm * P;

@@ -16,6 +16,61 @@ def chain_problem(n_frames, seed=11, **kw):
     return synthetic.pvgo_problem_from_deltas(tr, drot, dpos, dvel, pos, rot, vel), tr
 
 
+def tumbling_trajectory(n_frames, seed=5, frame_dt=0.1, imu_per_frame=10, gravity=9.81, gyro_sigma=1.7e-4, acc_sigma=2e-3,
+                        vo_sigma_t=0.05, vo_sigma_r=0.002):
+    """An airborne body that tumbles: body rates up to ~2 rad/s about all three axes (0.2 rad per frame about a general, moving
+    axis; the attitude covers SO(3), w < 0 included) on a closed 3-D curve.  Same keys and IMU / VO construction as
+    synthetic.car_trajectory, whose yaw rate stays below 0.1 rad/s with 0.01 rad of roll and pitch."""
+    from scipy.spatial.transform import Rotation
+    F = int(n_frames)
+    S = (F - 1) * imu_per_frame + 1
+    h = frame_dt / imu_per_frame
+    sub = 8
+    hs = h / sub
+    T = np.arange((S + 1) * sub + 1) * hs
+    rng = np.random.default_rng(seed)
+    ph = rng.uniform(0, 2 * np.pi, 6)
+    Tm = 0.5 * (T[1:] + T[:-1])
+    rate = np.stack([2.0 * np.sin(0.7 * Tm + ph[0]), 1.7 * np.sin(1.1 * Tm + ph[1]), 1.9 * np.cos(0.9 * Tm + ph[2])], 1)
+    q = np.zeros((len(T), 4))
+    q[0] = Rotation.random(random_state=seed).as_quat()
+    inc = Rotation.from_rotvec(rate * hs).as_quat()
+    x, y, z, w = inc.T
+    for i in range(len(T) - 1):                                         # R_{i+1} = R_i Exp(rate hs)
+        ax, ay, az, aw = q[i]
+        q[i + 1] = (aw * x[i] + ax * w[i] + ay * z[i] - az * y[i], aw * y[i] - ax * z[i] + ay * w[i] + az * x[i],
+                    aw * z[i] + ax * y[i] - ay * x[i] + az * w[i], aw * w[i] - ax * x[i] - ay * y[i] - az * z[i])
+    R = Rotation.from_quat(q)
+    pos_w = np.stack([8.0 * np.sin(0.5 * T + ph[3]), 8.0 * np.cos(0.3 * T + ph[4]), 3.0 * np.sin(0.7 * T + ph[5])], 1)
+    vel_w = np.stack([4.0 * np.cos(0.5 * T + ph[3]), -2.4 * np.sin(0.3 * T + ph[4]), 2.1 * np.cos(0.7 * T + ph[5])], 1)
+    idx = np.arange(S) * sub
+    Rc = R[idx]
+    gyro = (Rc.inv() * R[idx + sub]).as_rotvec() / h + rng.normal(0.0, gyro_sigma, (S, 3))
+    acc = Rc.inv().apply((vel_w[idx + sub] - vel_w[idx]) / h + np.array([0.0, 0.0, gravity])) + rng.normal(0.0, acc_sigma, (S, 3))
+    fidx = np.arange(F) * imu_per_frame
+    gt_R = R[fidx * sub]
+    gt_quat, gt_pos, gt_vel = gt_R.as_quat(), pos_w[fidx * sub], vel_w[fidx * sub]
+    rel_R = gt_R[:-1].inv() * gt_R[1:]
+    rel_t = gt_R[:-1].inv().apply(gt_pos[1:] - gt_pos[:-1])
+    vo_q = (rel_R * Rotation.from_rotvec(rng.normal(0.0, vo_sigma_r, rel_t.shape))).as_quat()
+    vo_t = rel_t + rel_R.apply(rng.normal(0.0, vo_sigma_t, rel_t.shape))
+    links = np.stack([np.arange(F - 1), np.arange(1, F)], 1).astype(np.int64)
+    return dict(gt_pos=gt_pos, gt_quat=gt_quat, gt_vel=gt_vel, accels=acc, gyros=gyro, imu_dts=np.full(S, h),
+                rgb2imu_sync=fidx.astype(np.int64), vo_motions=np.concatenate([vo_t, vo_q], 1), links=links,
+                dts=np.full(F - 1, frame_dt), gravity=gravity,
+                init=dict(pos=gt_pos[0].copy(), rot=gt_quat[0].copy(), vel=gt_vel[0].copy()))
+
+
+def tumbling_problem(n_frames, seed=5):
+    """chain_problem on tumbling_trajectory: run_pvgo inputs with IMU deltas from the oracle integrator."""
+    tr = tumbling_trajectory(n_frames, seed=seed)
+    F = n_frames
+    a = (tr['accels'], tr['gyros'], tr['imu_dts'], tr['rgb2imu_sync'], 0, F - 1, tr['init'], tr['gravity'])
+    pos, rot, vel = oimu.integrate(*a, False)
+    dpos, drot, dvel = oimu.integrate(*a, True)
+    return synthetic.pvgo_problem_from_deltas(tr, drot, dpos, dvel, pos, rot, vel), tr
+
+
 def se3_log_err(X, Xref):
     from oracle import lie
     d = lie.se3_log(lie.se3_mul(lie.se3_inv(Xref), X))
