@@ -510,6 +510,38 @@ int islam_imu_gravity_bias_solve(const void* rot_ref, const void* pos_ref, const
                                  const double* jac, const double* cov, const double* weight, int rows, double gravity_norm, double* out_x,
                                  double* out_H, double* out_vel, void* scratch, int dtype, void* stream);
 
+/* Camera-IMU extrinsic rotation from pairs of relative rotations, in closed form (the rotation calibration of
+ * VINS-Mono, CalibrationExRotation in its initial_ex_rotation.cpp).  The reference has no counterpart: it reads rgb2imu_pose (T_IL) from
+ * the dataset, and every other solve of this header assumes it.  For pair i = 0 .. rows-1
+ *   qb_i   the IMU's relative rotation over frame i (DR_i, the rotation of islam_imu_preint's motion rows), xyzw,
+ *   qc_i   the camera's relative rotation over the same frame (VO), xyzw.
+ * A rigid mount q (the rotation of T_IL: body motion = T_IL camera motion T_IL^-1) satisfies qb_i (x) q = q (x) qc_i, that is
+ * M_i q = 0 with M_i = L(qb_i) - R(qc_i), where L(a) p = a (x) p and R(a) p = p (x) a are the 4x4 matrices of the quaternion product.
+ * Before use every input quaternion is normalised and negated if its w < 0: conjugate rotations have the same angle, so the two sides
+ * of a pair then have equal w, and a sign flip of an input does not change M_i.  A quaternion of zero or non-finite norm makes its
+ * pair invalid.
+ *   A = sum_i w_i rho_i M_i^T M_i   (4x4, symmetric, positive semi-definite)
+ *   q = the unit eigenvector of the smallest eigenvalue of A, with w >= 0
+ * out_eig holds the eigenvalues of A ascending, l0 <= l1 <= l2 <= l3; they are the observability diagnosis: when all rotations share
+ * one axis the null space is two-dimensional and l1 ~ l0 (a scale-free test is (l1 - l0) / l3).  A degenerate but non-empty problem
+ * is not an error: the caller reads the eigenvalues.
+ * rho_i is a Huber weight on the angular residual: 1 in round 0; with delta > 0 and rounds = K >= 1 the solve is repeated K more
+ * times with rho_i = min(1, delta / theta_i), theta_i = angle(qb_i^-1 (x) q^ (x) qc_i (x) q^^-1) under the previous round's q^, the
+ * angle taken as 2 atan2(|vec|, |w|).  delta = 0: one round, rounds is ignored.
+ * weight: (rows) float64 or NULL = all ones.  A pair of weight exactly zero takes no part, whatever its data holds, and is not counted;
+ * a pair with a negative or non-finite weight or an invalid quaternion is excluded and counted.
+ * rot_imu, rot_cam (rows, 4) in the I/O dtype; float64 arithmetic for either dtype.  out_q: 4 doubles; out_eig: 4 doubles; out_res:
+ * rows doubles or NULL: theta_i under the final q, NaN for an invalid quaternion, computed for pairs of weight zero too (all device
+ * memory).  Returns the number of excluded pairs (>= 0); ISLAM_ENOTPD when no pair takes part (rows = 0 included): out_q, out_eig and
+ * out_res are then zeros; ISLAM_EARG, before any device work, for a NULL out_q / out_eig / scratch, NULL rot_imu / rot_cam with
+ * rows > 0, rows < 0, a bad dtype, a negative or non-finite delta, rounds < 0.  The sums run in an order that depends on rows alone,
+ * without atomics: a second call gives the same bits, and a pair of weight zero gives the bits of the same call with other data behind
+ * that weight.  Cost: (K + 1) x (2 or 3) launches plus one for out_res.  The call synchronises the stream (one 8-byte read-back).
+ * scratch: islam_imu_extrinsic_rot_solve_scratch_bytes(rows) bytes. */
+size_t islam_imu_extrinsic_rot_solve_scratch_bytes(int rows);
+int islam_imu_extrinsic_rot_solve(const void* rot_imu, const void* rot_cam, const double* weight, int rows, double delta, int rounds,
+                                  double* out_q, double* out_eig, double* out_res, void* scratch, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- PVGO (pose-velocity graph optimisation) */
 
 typedef struct {

@@ -254,3 +254,43 @@ class IMUModule:
             res = torch.cat((g, self.accel_bias.to(torch.float64) + b, vel.reshape(-1), H.reshape(36))).cpu()
         o = 6 + 3 * (n + 1)
         return res[0:3].contiguous(), res[3:6].contiguous(), res[6:o].view(n + 1, 3).contiguous(), res[o:o + 36].view(6, 6).contiguous()
+
+
+    def estimate_extrinsic_rotation(self, st, end, cam_rots, weight=None, delta=None, rounds=4, min_gap=None):
+        """Rotation of the camera-IMU mount from the relative rotations of frames [st, end], in closed form
+        (islam_imu_extrinsic_rot_solve; the rotation calibration of VINS-Mono).  ``cam_rots``: (end - st, 4) xyzw quaternions or an SO3,
+        the CAMERA's relative rotation over frame i -> i + 1 (VO, in the camera's own frame, no rgb2imu applied).  The motion rows are
+        integrated exactly as ``estimate_gyro_bias`` does (the module's current ``gyro_bias`` subtracted whatever ``optm_bias`` says;
+        the denoiser is not run) and their rotations DR_i enter with ``cam_rots``: q minimises sum_i w_i rho_i |DR_i (x) q - q (x) cam_i|^2
+        over unit quaternions.  ``weight``: (end - st) per frame; ``delta``: Huber threshold on the angular residual in rad (None = no
+        reweighting) for ``rounds`` reweighted solves.  Returns (q (4) xyzw, the eigenvalues (4) ascending, the angular residuals
+        (end - st) under q), on the CPU in float64.  q is the rotation of ``rgb2imu_pose`` (T_IL: body motion = T_IL camera motion
+        T_IL^-1).  The eigenvalues are the observability diagnosis: rotations about one axis only leave q undetermined and give
+        eig[1] ~ eig[0] without an error; with ``min_gap`` a ``ValueError`` is raised when (eig[1] - eig[0]) / eig[3] < min_gap.
+        A gyro-bias error perturbs q at first order (it rotates every DR_i), so the order of calls is: this first, then
+        ``estimate_gyro_bias`` on the camera rotations conjugated by q (q (x) cam_i (x) q^-1).  Out of scope: the joint refinement of
+        the two, the lever arm (the translation of T_IL) and the time offset between the two sensors.  The module is not changed."""
+        b0 = int(self.rgb2imu_sync[st])
+        b1 = int(self.rgb2imu_sync[end]) + 1
+        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
+        seg = torch.from_numpy(seg_host).to(self.device)
+        n = len(seg_host) - 1
+        cam = cam_rots.tensor() if hasattr(cam_rots, 'tensor') else torch.as_tensor(np.asarray(cam_rots))
+        cam = cam.detach().to(self.dtype).to(self.device)
+        if weight is not None:
+            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+        with torch.no_grad():
+            dts = self.dts[b0:b1, 0].contiguous()
+            gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
+            accels = self.accels[b0:b1].contiguous()
+            init = torch.zeros(10, dtype=self.dtype, device=self.device)
+            init[6] = 1.0
+            _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
+            q, eig, res, _ = ops.imu_extrinsic_rot_solve(rot, cam, weight, delta, rounds)
+            host = torch.cat((q, eig, res)).cpu()
+        q, eig, res = host[0:4].contiguous(), host[4:8].contiguous(), host[8:8 + n].contiguous()
+        gap = float(eig[1] - eig[0]) / float(eig[3]) if float(eig[3]) > 0.0 else 0.0
+        if min_gap is not None and not gap >= float(min_gap):
+            raise ValueError('estimate_extrinsic_rotation: the rotations of frames [%d, %d] do not span more than one axis: '
+                             '(eig1 - eig0) / eig3 = %.3g < min_gap = %.3g' % (st, end, gap, min_gap))
+        return q, eig, res

@@ -954,6 +954,37 @@ def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None
     return out[0:3], out[3:6], out[6:42].view(6, 6), out[42:].view(rows + 1, 3), int(rc)
 
 
+def imu_extrinsic_rot_solve(rot_imu, rot_cam, weight=None, delta=None, rounds=4):
+    """Camera-IMU extrinsic rotation from pairs of relative rotations, in closed form (islam_imu_extrinsic_rot_solve; definition in
+    include/islam_hip.h).  rot_imu (rows, 4) xyzw: the IMU's relative rotation over every frame (the motion rows' rotations), rot_cam
+    (rows, 4): the camera's over the same frame, float32 or float64 (rot_imu's dtype); weight (rows) or None; delta: the Huber
+    threshold on the angular residual in rad, None = no reweighting; rounds: the reweighted solves after the first one.  Returns
+    (q (4) with rot_imu_i (x) q = q (x) rot_cam_i, eig (4) the eigenvalues ascending, res (rows) the angular residuals under q, number
+    of excluded pairs), float64 on the device.  Rotations about one axis only leave q undetermined: eig[1] ~ eig[0], no error.
+    Raises IslamHipError (code ISLAM_ENOTPD) when no pair takes part.  Synchronises the stream."""
+    require_cuda(rot_imu, rot_cam, weight)
+    rows = int(rot_imu.shape[0])
+    dtype = rot_imu.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = rot_imu.device
+    with torch.no_grad():
+        rot_imu, rot_cam = rot_imu.detach().contiguous(), rot_cam.detach().to(dtype).contiguous()
+        for t, name in ((rot_imu, 'rot_imu'), (rot_cam, 'rot_cam')):
+            if tuple(t.shape) != (rows, 4):
+                raise ValueError('%s: (%d, 4) expected, got %s' % (name, rows, tuple(t.shape)))
+        if weight is not None:
+            weight = weight.detach().to(torch.float64).contiguous()
+            if tuple(weight.shape) != (rows,):
+                raise ValueError('weight: (%d,) expected, got %s' % (rows, tuple(weight.shape)))
+        out = torch.empty(8 + rows, dtype=torch.float64, device=dev)
+        scratch = torch.empty(lib().islam_imu_extrinsic_rot_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
+        rc = lib().islam_imu_extrinsic_rot_solve(ptr(rot_imu), ptr(rot_cam), ptr(weight), rows, c_double(0.0 if delta is None else float(delta)),
+                                                 int(rounds), ptr(out[0:4]), ptr(out[4:8]), ptr(out[8:]), ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return out[0:4], out[4:8], out[8:], int(rc)
+
+
 # --------------------------------------------------------------------------- PVGO
 def pvgo_default_params(loss_weight=(1, 1, 1, 1), radius=1e4, seg_len=(0, 0)):
     p = _lib.PvgoParams()
