@@ -3,14 +3,12 @@
 // the library already produces.  The definition is in include/islam_hip.h (islam_imu_gravity_bias_solve).
 //
 // For every pair of consecutive intervals i, i + 1 the velocities drop out of (P_i), (P_{i+1}), (V_i) and leave three equations
-// A_i x = r_i in x = [g; b].  Kernels (float64 arithmetic whatever the I/O type; separate launches on the stream: no workgroup waits
-// for another, no atomics, a second call gives the same bits)
+// A_i x = r_i in x = [g; b].  Kernels (float64 arithmetic whatever the I/O type; the fixed-order sum between them is imu_terms.h)
 //   ga_pair_kernel     one lane per pair: A_i, r_i, the pair's covariance C_i = L L^T, the whitened L^-1 [A | r] and the pair's terms
-//                      w A^T C^-1 A (upper triangle, 21) | w A^T C^-1 r (6) | excluded (0 or 1), stored by term (coalesced); a pair
-//                      that takes no part stores zeros, so the sum below runs over all pairs in an order that depends on their number alone
-//   ga_partial_kernel  more than REACH pairs: one workgroup sums REACH of them (lane-strided, a shuffle tree, the four waves in order)
-//   ga_solve_kernel    one workgroup sums the terms (or the partial sums) the same way; lane 0 solves by Cholesky in LDS: the free
-//                      6x6 (3x3 without Jacobians), then the four rounds of the gravity-norm constraint on the same (H, c)
+//                      w A^T C^-1 A (upper triangle, 21) | w A^T C^-1 r (6) | excluded (0 or 1)
+//   ga_partial_kernel  more than REACH pairs: the partial sums
+//   ga_solve_kernel    the sum; lane 0 solves by Cholesky in LDS: the free 6x6 (3x3 without Jacobians), then the four rounds of the
+//                      gravity-norm constraint on the same (H, c)
 //   ga_vel_kernel      one lane per pose: v_i from (P_i), the last one from (V_{n-1})
 // The small matrices of the solve live in LDS and are indexed there: no private memory.  FMA contraction stays on (results are
 // checked to a tolerance, not to the bit, against the numpy restatement of tests/test_imu_align_gpu.py).
@@ -18,16 +16,14 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "imu_terms.h"
 
 using namespace islam;
+using namespace islam::tsum;
 
 namespace {
 
 constexpr int NT = 28;                // per-pair terms: H upper triangle by rows (21) | c (6) | excluded (1)
-constexpr int BLOCK = 256;
-constexpr int REACH = 4 * BLOCK;      // pairs one workgroup sums
-constexpr int HEAD = 32;              // doubles in front of the terms (the two status words live there)
 constexpr double PIVOT_REL = 1e-13;   // islam_imu_gyro_bias_solve's rule: a pivot at or below this share of its diagonal entry fails
 
 // rotation matrix (by rows) of a unit quaternion xyzw
@@ -180,34 +176,8 @@ __global__ __launch_bounds__(BLOCK) void ga_pair_kernel(const T* __restrict__ ro
     for (int q = 0; q < NT; ++q) terms[(size_t)q * P + s] = t[q];
 }
 
-// tot[q] = sum over c in [c0, c1) of src[q ld + c], in an order that depends on c1 - c0 alone: lane-strided partial sums, a shuffle
-// tree inside every wave, the four waves in order.  Ends on a barrier: every lane may read tot afterwards.
-__device__ __forceinline__ void block_sum(const double* __restrict__ src, size_t ld, size_t c0, size_t c1, double* wsum, double* tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q) acc[q] = 0.0;
-    for (size_t c = c0 + tid; c < c1; c += BLOCK)
-#pragma unroll
-        for (int q = 0; q < NT; ++q) acc[q] += src[(size_t)q * ld + c];
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1)
-#pragma unroll
-        for (int q = 0; q < NT; ++q) acc[q] += __shfl_down(acc[q], sft, 64);
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < NT; ++q) wsum[wv * NT + q] = acc[q];
-    __syncthreads();
-    if (tid < NT) tot[tid] = ((wsum[tid] + wsum[NT + tid]) + wsum[2 * NT + tid]) + wsum[3 * NT + tid];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(BLOCK) void ga_partial_kernel(const double* __restrict__ terms, int P, int nblocks, double* __restrict__ partial) {
-    __shared__ double wsum[4 * NT], tot[NT];
-    const size_t c0 = (size_t)blockIdx.x * REACH;
-    const size_t c1 = c0 + REACH < (size_t)P ? c0 + REACH : (size_t)P;
-    block_sum(terms, (size_t)P, c0, c1, wsum, tot);
-    if (threadIdx.x < NT) partial[(size_t)threadIdx.x * nblocks + blockIdx.x] = tot[threadIdx.x];
+    partial_sum<NT>(terms, P, nblocks, partial);
 }
 
 // M (n x n, row stride 6) = L L^T under the pivot rule, then L L^T x = rhs.  Every array lives in LDS.
@@ -301,7 +271,7 @@ __global__ __launch_bounds__(BLOCK) void ga_solve_kernel(const double* __restric
                                                          int* __restrict__ status, double* __restrict__ out_x, double* __restrict__ out_H) {
     __shared__ double wsum[4 * NT], tot[NT];
     __shared__ SolveLds S;
-    block_sum(src, (size_t)ld, 0, (size_t)count, wsum, tot);
+    block_sum<NT>(src, (size_t)ld, 0, (size_t)count, wsum, tot);
     if (threadIdx.x != 0) return;
     int idx = 0;
     for (int a = 0; a < 6; ++a)
@@ -365,27 +335,20 @@ __global__ __launch_bounds__(BLOCK) void ga_vel_kernel(const T* __restrict__ rot
     for (int c = 0; c < 3; ++c) out_vel[3 * (size_t)i + c] = v[c];
 }
 
-inline int partial_blocks(int P) { return P > REACH ? (P + REACH - 1) / REACH : 0; }
-
 template <class T>
 int run(const T* rot, const T* pos, const T* dts, const T* dvel, const T* dpos, const double* jac, const double* cov, const double* weight,
         int rows, double G, double* out_x, double* out_H, double* out_vel, void* scratch, hipStream_t s) {
-    const int P = rows > 1 ? rows - 1 : 0, NB = partial_blocks(P);
-    int* status = reinterpret_cast<int*>(scratch);
-    double* terms = reinterpret_cast<double*>(scratch) + HEAD;
-    double* partial = terms + (size_t)NT * P;
+    const int P = rows > 1 ? rows - 1 : 0;
+    const Scratch sc(scratch, NT, P);
     if (P > 0)
-        hipLaunchKernelGGL(ga_pair_kernel<T>, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, cov, weight, P, terms);
-    if (NB > 0) hipLaunchKernelGGL(ga_partial_kernel, dim3(NB), dim3(BLOCK), 0, s, (const double*)terms, P, NB, partial);
-    hipLaunchKernelGGL(ga_solve_kernel, dim3(1), dim3(BLOCK), 0, s, NB > 0 ? (const double*)partial : (const double*)terms, NB > 0 ? NB : P,
-                       NB > 0 ? NB : P, jac ? 6 : 3, G, status, out_x, out_H);
+        hipLaunchKernelGGL(ga_pair_kernel<T>, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, cov, weight, P, sc.terms);
+    if (sc.blocks > 0) hipLaunchKernelGGL(ga_partial_kernel, dim3(sc.blocks), dim3(BLOCK), 0, s, (const double*)sc.terms, P, sc.blocks, sc.partial);
+    hipLaunchKernelGGL(ga_solve_kernel, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, jac ? 6 : 3, G, sc.status, out_x, out_H);
     if (out_vel)
         hipLaunchKernelGGL(ga_vel_kernel<T>, dim3(rows / BLOCK + 1), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, rows, (const double*)out_x,
-                           (const int*)status, out_vel);
-    ISLAM_LAUNCH_CHECK();
-    int host[2] = {0, 0};
-    ISLAM_HIP_CHECK(hipMemcpyAsync(host, status, sizeof(host), hipMemcpyDeviceToHost, s));
-    ISLAM_HIP_CHECK(hipStreamSynchronize(s));
+                           (const int*)sc.status, out_vel);
+    int host[2];
+    if (const int rc = read_status(sc.status, s, host)) return rc;
     if (host[0] != 0)
         return fail(ISLAM_ENOTPD, "islam_imu_gravity_bias_solve: the normal matrix of %d pairs (%d excluded) is not positive definite", P, host[1]);
     return host[1];
@@ -396,8 +359,7 @@ int run(const T* rot, const T* pos, const T* dts, const T* dvel, const T* dpos, 
 extern "C" {
 
 size_t islam_imu_gravity_bias_solve_scratch_bytes(int rows) {
-    const int P = rows > 1 ? rows - 1 : 0;
-    return sizeof(double) * (HEAD + (size_t)NT * P + (size_t)NT * partial_blocks(P));
+    return Scratch::bytes(NT, rows > 1 ? rows - 1 : 0);
 }
 
 int islam_imu_gravity_bias_solve(const void* rot_ref, const void* pos_ref, const void* dts, const void* dvel, const void* dpos,

@@ -25,7 +25,7 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "imu_terms.h"
 
 using namespace islam;
 
@@ -373,7 +373,6 @@ __global__ __launch_bounds__(256) void bias_correct_kernel(const double* __restr
 
 // ---------------------------------------------------------------------------------------------------- gyro-bias solve
 constexpr int NT = 9;                 // per-row terms: w J^T J (upper triangle by rows, 6) | w J^T r (3)
-constexpr int SOLVE_HEAD = 32;        // doubles in front of the terms (the two status words live there)
 constexpr double PIVOT_REL = 1e-13;   // a Cholesky pivot below this share of its diagonal entry: H counts as singular
 
 // One workgroup.  The rows that count (finite residual, finite non-zero weight) are compacted IN ROW ORDER into `terms`, then summed in
@@ -529,7 +528,7 @@ int islam_imu_bias_correct(const double* jac, const void* rot, const void* vel, 
     return ISLAM_OK;
 }
 
-size_t islam_imu_gyro_bias_solve_scratch_bytes(int rows) { return sizeof(double) * (SOLVE_HEAD + (size_t)NT * (rows > 0 ? rows : 0)); }
+size_t islam_imu_gyro_bias_solve_scratch_bytes(int rows) { return sizeof(double) * (tsum::HEAD + (size_t)NT * (rows > 0 ? rows : 0)); }
 
 int islam_imu_gyro_bias_solve(const double* jac, const void* rot_imu, const void* rot_ref, const double* weight, int rows, double* out_dbg,
                               double* out_H, void* scratch, int dtype, void* stream) {
@@ -539,17 +538,15 @@ int islam_imu_gyro_bias_solve(const double* jac, const void* rot_imu, const void
     if (rows > 0 && (!jac || !rot_imu || !rot_ref)) return fail(ISLAM_EARG, "islam_imu_gyro_bias_solve: jac / rot_imu / rot_ref is NULL (rows=%d)", rows);
     hipStream_t s = as_stream(stream);
     int* status = reinterpret_cast<int*>(scratch);
-    double* terms = reinterpret_cast<double*>(scratch) + SOLVE_HEAD;
+    double* terms = reinterpret_cast<double*>(scratch) + tsum::HEAD;
     if (dtype == ISLAM_F64)
         hipLaunchKernelGGL(gyro_bias_solve_kernel<double>, dim3(1), dim3(256), 0, s, jac, (const double*)rot_imu, (const double*)rot_ref, weight, rows,
                            terms, status, out_dbg, out_H);
     else
         hipLaunchKernelGGL(gyro_bias_solve_kernel<float>, dim3(1), dim3(256), 0, s, jac, (const float*)rot_imu, (const float*)rot_ref, weight, rows,
                            terms, status, out_dbg, out_H);
-    ISLAM_LAUNCH_CHECK();
-    int host[2] = {0, 0};
-    ISLAM_HIP_CHECK(hipMemcpyAsync(host, status, sizeof(host), hipMemcpyDeviceToHost, s));
-    ISLAM_HIP_CHECK(hipStreamSynchronize(s));
+    int host[2];
+    if (const int rc = tsum::read_status(status, s, host)) return rc;
     if (host[0] != 0)
         return fail(ISLAM_ENOTPD, "islam_imu_gyro_bias_solve: the 3x3 normal matrix of %d rows (%d excluded) is not positive definite", rows, host[1]);
     return host[1];

@@ -3,16 +3,14 @@
 // relative rotations.  The definition is in include/islam_hip.h (islam_imu_extrinsic_rot_solve).
 //
 // A rigid mount q satisfies qb_i (x) q = q (x) qc_i for every pair, M_i q = 0 with M_i = L(qb_i) - R(qc_i); q is the unit eigenvector of
-// the smallest eigenvalue of A = sum_i w_i rho_i M_i^T M_i.  Kernels (float64 arithmetic whatever the I/O type; separate launches on
-// the stream: no workgroup waits for another, no atomics, a second call gives the same bits)
+// the smallest eigenvalue of A = sum_i w_i rho_i M_i^T M_i.  Kernels (float64 arithmetic whatever the I/O type; the fixed-order sum
+// between them is imu_terms.h)
 //   ex_pair_kernel     one lane per pair: the two quaternions normalised with w >= 0, in rounds >= 1 the Huber weight rho_i from the
 //                      previous round's estimate (read from scratch), the pair's terms w rho M^T M (upper triangle, 10) | excluded
-//                      (0 or 1) | takes part (0 or 1), stored by term (coalesced); a pair that takes no part stores zeros, so the sum
-//                      below runs over all pairs in an order that depends on their number alone
-//   ex_partial_kernel  more than REACH pairs: one workgroup sums REACH of them (lane-strided, a shuffle tree, the four waves in order:
-//                      the scheme of ga_partial_kernel in imu_align.hip)
-//   ex_solve_kernel    one workgroup sums the terms (or the partial sums) the same way; lane 0 runs a cyclic Jacobi eigen-decomposition
-//                      of the 4x4 in LDS, sorts the eigenvalues, writes the estimate for the next round and, after the last, the outputs
+//                      (0 or 1) | takes part (0 or 1)
+//   ex_partial_kernel  more than REACH pairs: the partial sums
+//   ex_solve_kernel    the sum; lane 0 runs a cyclic Jacobi eigen-decomposition of the 4x4 in LDS, sorts the eigenvalues, writes the
+//                      estimate for the next round and, after the last, the outputs
 //   ex_res_kernel      one lane per pair: the angular residual under the final estimate (only when it is asked for)
 // The 4x4 and its eigenvectors live in LDS and are indexed there: no private memory.  FMA contraction stays on (results are checked to
 // a tolerance, not to the bit, against the numpy restatement of tests/test_imu_extrinsic_gpu.py).
@@ -20,17 +18,15 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "imu_terms.h"
 
 using namespace islam;
+using namespace islam::tsum;
 
 namespace {
 
 constexpr int NT = 12;                // per-pair terms: A upper triangle by rows (10) | excluded (1) | takes part (1)
-constexpr int BLOCK = 256;
-constexpr int REACH = 4 * BLOCK;      // pairs one workgroup sums
-constexpr int HEAD = 32;              // doubles in front of the terms: the two status words, then the estimate of the last round
-constexpr int QHAT = 4;               // the estimate's place in the head (doubles 4 .. 7)
+constexpr int QHAT = 4;               // the last round's estimate in the scratch head (doubles 4 .. 7), behind the two status words
 constexpr int MAX_SWEEPS = 16;        // cap on the Jacobi sweeps (a 4x4 is at rounding level after 4 to 6)
 constexpr double OFF_REL = 0x1p-56;   // a sweep that finds every off-diagonal entry at or below this share of the largest diagonal ends
 
@@ -117,34 +113,8 @@ __global__ __launch_bounds__(BLOCK) void ex_pair_kernel(const T* __restrict__ ro
     for (int q = 0; q < NT; ++q) terms[(size_t)q * P + s] = t[q];
 }
 
-// tot[q] = sum over c in [c0, c1) of src[q ld + c], in an order that depends on c1 - c0 alone: lane-strided partial sums, a shuffle
-// tree inside every wave, the four waves in order.  Ends on a barrier: every lane may read tot afterwards.
-__device__ __forceinline__ void block_sum(const double* __restrict__ src, size_t ld, size_t c0, size_t c1, double* wsum, double* tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q) acc[q] = 0.0;
-    for (size_t c = c0 + tid; c < c1; c += BLOCK)
-#pragma unroll
-        for (int q = 0; q < NT; ++q) acc[q] += src[(size_t)q * ld + c];
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1)
-#pragma unroll
-        for (int q = 0; q < NT; ++q) acc[q] += __shfl_down(acc[q], sft, 64);
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < NT; ++q) wsum[wv * NT + q] = acc[q];
-    __syncthreads();
-    if (tid < NT) tot[tid] = ((wsum[tid] + wsum[NT + tid]) + wsum[2 * NT + tid]) + wsum[3 * NT + tid];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(BLOCK) void ex_partial_kernel(const double* __restrict__ terms, int P, int nblocks, double* __restrict__ partial) {
-    __shared__ double wsum[4 * NT], tot[NT];
-    const size_t c0 = (size_t)blockIdx.x * REACH;
-    const size_t c1 = c0 + REACH < (size_t)P ? c0 + REACH : (size_t)P;
-    block_sum(terms, (size_t)P, c0, c1, wsum, tot);
-    if (threadIdx.x < NT) partial[(size_t)threadIdx.x * nblocks + blockIdx.x] = tot[threadIdx.x];
+    partial_sum<NT>(terms, P, nblocks, partial);
 }
 
 struct EigLds {
@@ -194,7 +164,7 @@ __global__ __launch_bounds__(BLOCK) void ex_solve_kernel(const double* __restric
                                                          double* __restrict__ qhat, double* __restrict__ out_q, double* __restrict__ out_eig) {
     __shared__ double wsum[4 * NT], tot[NT];
     __shared__ EigLds E;
-    block_sum(src, (size_t)ld, 0, (size_t)count, wsum, tot);
+    block_sum<NT>(src, (size_t)ld, 0, (size_t)count, wsum, tot);
     if (threadIdx.x != 0) return;
     const bool any = tot[NT - 1] > 0.0;
     int idx = 0;
@@ -242,31 +212,24 @@ __global__ __launch_bounds__(BLOCK) void ex_res_kernel(const T* __restrict__ rot
     out_res[s] = th;
 }
 
-inline int partial_blocks(int P) { return P > REACH ? (P + REACH - 1) / REACH : 0; }
-
 template <class T>
 int run(const T* rot_imu, const T* rot_cam, const double* weight, int P, double delta, int rounds, double* out_q, double* out_eig,
         double* out_res, void* scratch, hipStream_t s) {
-    const int NB = partial_blocks(P), K = delta > 0.0 ? rounds : 0;
-    int* status = reinterpret_cast<int*>(scratch);
-    double* qhat = reinterpret_cast<double*>(scratch) + QHAT;
-    double* terms = reinterpret_cast<double*>(scratch) + HEAD;
-    double* partial = terms + (size_t)NT * P;
+    const int K = delta > 0.0 ? rounds : 0;
+    const Scratch sc(scratch, NT, P);
+    double* qhat = sc.head + QHAT;
     for (int r = 0; r <= K; ++r) {
         if (P > 0)
             hipLaunchKernelGGL(ex_pair_kernel<T>, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot_imu, rot_cam, weight, P, delta,
-                               r > 0 ? (const double*)qhat : (const double*)nullptr, terms);
-        if (NB > 0) hipLaunchKernelGGL(ex_partial_kernel, dim3(NB), dim3(BLOCK), 0, s, (const double*)terms, P, NB, partial);
-        hipLaunchKernelGGL(ex_solve_kernel, dim3(1), dim3(BLOCK), 0, s, NB > 0 ? (const double*)partial : (const double*)terms,
-                           NB > 0 ? NB : P, NB > 0 ? NB : P, r == K ? 1 : 0, status, qhat, out_q, out_eig);
+                               r > 0 ? (const double*)qhat : (const double*)nullptr, sc.terms);
+        if (sc.blocks > 0) hipLaunchKernelGGL(ex_partial_kernel, dim3(sc.blocks), dim3(BLOCK), 0, s, (const double*)sc.terms, P, sc.blocks, sc.partial);
+        hipLaunchKernelGGL(ex_solve_kernel, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, r == K ? 1 : 0, sc.status, qhat, out_q, out_eig);
     }
     if (out_res && P > 0)
         hipLaunchKernelGGL(ex_res_kernel<T>, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot_imu, rot_cam, P, (const double*)qhat,
-                           (const int*)status, out_res);
-    ISLAM_LAUNCH_CHECK();
-    int host[2] = {0, 0};
-    ISLAM_HIP_CHECK(hipMemcpyAsync(host, status, sizeof(host), hipMemcpyDeviceToHost, s));
-    ISLAM_HIP_CHECK(hipStreamSynchronize(s));
+                           (const int*)sc.status, out_res);
+    int host[2];
+    if (const int rc = read_status(sc.status, s, host)) return rc;
     if (host[0] != 0)
         return fail(ISLAM_ENOTPD, "islam_imu_extrinsic_rot_solve: no pair of %d takes part (%d excluded)", P, host[1]);
     return host[1];
@@ -277,8 +240,7 @@ int run(const T* rot_imu, const T* rot_cam, const double* weight, int P, double 
 extern "C" {
 
 size_t islam_imu_extrinsic_rot_solve_scratch_bytes(int rows) {
-    const int P = rows > 0 ? rows : 0;
-    return sizeof(double) * (HEAD + (size_t)NT * P + (size_t)NT * partial_blocks(P));
+    return Scratch::bytes(NT, rows > 0 ? rows : 0);
 }
 
 int islam_imu_extrinsic_rot_solve(const void* rot_imu, const void* rot_cam, const double* weight, int rows, double delta, int rounds,

@@ -872,6 +872,16 @@ def _rows_of(jac, rot):
     return rows
 
 
+def _imu_arg(t, dtype, shape, name, got=True):
+    """``t`` detached, in ``dtype`` and contiguous for the IMU entry points; None passes through; ValueError unless its shape is ``shape``"""
+    if t is None:
+        return None
+    t = (t if t.dtype == dtype else t.to(dtype)).detach().contiguous()
+    if tuple(t.shape) != shape:
+        raise ValueError('%s: %s expected' % (name, shape) + (', got %s' % (tuple(t.shape),) if got else ''))
+    return t
+
+
 def imu_bias_correct(jac, rot, vel, pos, dbg, dba):
     """First-order correction of pre-integrated increments in their start-body frame for a further bias (dbg, dba: three values
     each) subtracted from the samples (islam_imu_bias_correct; include/islam_hip.h says how motion rows of a non-identity start
@@ -882,9 +892,8 @@ def imu_bias_correct(jac, rot, vel, pos, dbg, dba):
     dtype = rot.dtype
     code = {torch.float32: 0, torch.float64: 1}[dtype]
     with torch.no_grad():
-        rot, vel, pos = (t.detach().to(dtype).contiguous() for t in (rot, vel, pos))
-        if tuple(vel.shape) != (rows, 3) or tuple(pos.shape) != (rows, 3):
-            raise ValueError('vel / pos: (%d, 3) expected' % rows)
+        rot = _imu_arg(rot, dtype, (rows, 4), 'rotations')
+        vel, pos = (_imu_arg(t, dtype, (rows, 3), 'vel / pos', got=False) for t in (vel, pos))
         out = [torch.empty_like(t) for t in (rot, vel, pos)]
         g3 = (ctypes.c_double * 3)(*np.asarray(torch.as_tensor(dbg).detach().cpu(), dtype=np.float64).reshape(3))
         a3 = (ctypes.c_double * 3)(*np.asarray(torch.as_tensor(dba).detach().cpu(), dtype=np.float64).reshape(3))
@@ -903,13 +912,8 @@ def imu_gyro_bias_solve(jac, rot_imu, rot_ref, weight=None):
     code = {torch.float32: 0, torch.float64: 1}[dtype]
     dev = jac.device
     with torch.no_grad():
-        rot_imu, rot_ref = rot_imu.detach().contiguous(), rot_ref.detach().to(dtype).contiguous()
-        if tuple(rot_ref.shape) != (rows, 4):
-            raise ValueError('rot_ref: (%d, 4) expected, got %s' % (rows, tuple(rot_ref.shape)))
-        if weight is not None:
-            weight = weight.detach().to(torch.float64).contiguous()
-            if tuple(weight.shape) != (rows,):
-                raise ValueError('weight: (%d,) expected, got %s' % (rows, tuple(weight.shape)))
+        rot_imu, rot_ref = _imu_arg(rot_imu, dtype, (rows, 4), 'rotations'), _imu_arg(rot_ref, dtype, (rows, 4), 'rot_ref')
+        weight = _imu_arg(weight, torch.float64, (rows,), 'weight')
         out = torch.empty(12, dtype=torch.float64, device=dev)
         scratch = torch.empty(lib().islam_imu_gyro_bias_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
         rc = lib().islam_imu_gyro_bias_solve(ptr(jac), ptr(rot_imu), ptr(rot_ref), ptr(weight), rows, ptr(out[0:3]), ptr(out[3:12]),
@@ -933,17 +937,11 @@ def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None
     code = {torch.float32: 0, torch.float64: 1}[dtype]
     dev = dts.device
     with torch.no_grad():
-        io = [t.detach().to(dtype).contiguous() for t in (rot_ref, pos_ref, dts, dvel, dpos)]
-        for t, shape, name in zip(io, ((rows + 1, 4), (rows + 1, 3), (rows,), (rows, 3), (rows, 3)), ('rot_ref', 'pos_ref', 'dts', 'dvel', 'dpos')):
-            if tuple(t.shape) != shape:
-                raise ValueError('%s: %s expected, got %s' % (name, shape, tuple(t.shape)))
-        f64 = []
-        for t, shape, name in ((jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight')):
-            if t is not None:
-                t = t.detach().to(torch.float64).contiguous()
-                if tuple(t.shape) != shape:
-                    raise ValueError('%s: %s expected, got %s' % (name, shape, tuple(t.shape)))
-            f64.append(t)
+        io = [_imu_arg(t, dtype, shape, name) for t, shape, name in (
+            (rot_ref, (rows + 1, 4), 'rot_ref'), (pos_ref, (rows + 1, 3), 'pos_ref'), (dts, (rows,), 'dts'), (dvel, (rows, 3), 'dvel'),
+            (dpos, (rows, 3), 'dpos'))]
+        f64 = [_imu_arg(t, torch.float64, shape, name) for t, shape, name in (
+            (jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight'))]
         out = torch.empty(42 + 3 * (rows + 1), dtype=torch.float64, device=dev)
         scratch = torch.empty(lib().islam_imu_gravity_bias_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
         rc = lib().islam_imu_gravity_bias_solve(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows,
@@ -968,14 +966,8 @@ def imu_extrinsic_rot_solve(rot_imu, rot_cam, weight=None, delta=None, rounds=4)
     code = {torch.float32: 0, torch.float64: 1}[dtype]
     dev = rot_imu.device
     with torch.no_grad():
-        rot_imu, rot_cam = rot_imu.detach().contiguous(), rot_cam.detach().to(dtype).contiguous()
-        for t, name in ((rot_imu, 'rot_imu'), (rot_cam, 'rot_cam')):
-            if tuple(t.shape) != (rows, 4):
-                raise ValueError('%s: (%d, 4) expected, got %s' % (name, rows, tuple(t.shape)))
-        if weight is not None:
-            weight = weight.detach().to(torch.float64).contiguous()
-            if tuple(weight.shape) != (rows,):
-                raise ValueError('weight: (%d,) expected, got %s' % (rows, tuple(weight.shape)))
+        rot_imu, rot_cam = _imu_arg(rot_imu, dtype, (rows, 4), 'rot_imu'), _imu_arg(rot_cam, dtype, (rows, 4), 'rot_cam')
+        weight = _imu_arg(weight, torch.float64, (rows,), 'weight')
         out = torch.empty(8 + rows, dtype=torch.float64, device=dev)
         scratch = torch.empty(lib().islam_imu_extrinsic_rot_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
         rc = lib().islam_imu_extrinsic_rot_solve(ptr(rot_imu), ptr(rot_cam), ptr(weight), rows, c_double(0.0 if delta is None else float(delta)),

@@ -27,6 +27,8 @@ B_PLANTED = np.array([0.12, -0.05, 0.08])
 RAGGED12 = (3, 11, 1, 6, 140, 2, 9, 5, 10, 4, 7, 8)   # 12 frames, one long one
 SHAPES = {'4x7': ((7,) * 4, 1.0), '12xragged': (RAGGED12, 1.0), '70x10': ((10,) * 70, 1.0), '300x10': ((10,) * 300, 0.5),
           '1100x4': ((4,) * 1100, 0.5)}
+# P = 1024 and P = 1025 pairs: the last size the solve kernel sums by itself and the first with a partial-sum launch (csrc/imu_terms.h)
+REACH_SHAPES = {'1025x4': ((4,) * 1025, 0.5), '1026x4': ((4,) * 1026, 0.5)}
 
 
 def _mat_to_quat(R):
@@ -64,9 +66,9 @@ def make_stream(counts, amp=1.0, bias=B_PLANTED, seed=0, tail=0):
 
 @functools.lru_cache(maxsize=None)
 def planted_stream(name, bias=True):
-    """The solve's inputs for one of SHAPES, in float64: quaternions and positions of the poses, durations, increments in the
+    """The solve's inputs for one of SHAPES or REACH_SHAPES, in float64: quaternions and positions of the poses, durations, increments in the
     start-body frame, bias Jacobians; and the planted g, b, v."""
-    counts, amp = SHAPES[name]
+    counts, amp = SHAPES[name] if name in SHAPES else REACH_SHAPES[name]
     s = make_stream(counts, amp, B_PLANTED if bias else np.zeros(3), seed=len(counts))
     seg, n = s['seg'], len(counts)
     d, dv, dp = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3))
@@ -211,8 +213,7 @@ def _check(tag, got, ref, st, h_tol=1e-9):
 
 
 # ------------------------------------------------------------------------------------------------ 1. parity and recovery
-@pytest.mark.parametrize('dtype', [np.float64, np.float32])
-@pytest.mark.parametrize('name', list(SHAPES))
+@pytest.mark.parametrize('name,dtype', [(n, d) for n in SHAPES for d in (np.float64, np.float32)] + [(n, np.float64) for n in REACH_SHAPES])
 def test_against_the_restatement_and_the_planted_truth(cuda, name, dtype):
     st = planted_stream(name)
     got = _solve(cuda, st, dtype)

@@ -11,7 +11,7 @@ between the restatement summed forwards and summed backwards (the sensitivity to
 the planted truth and against the restatement, to 10 x the larger of the two, with a floor of 16 * 2^-52 * l3 / (l1 - l0): the
 first-order eigenvector perturbation bound for sixteen roundings of |A|.  Eigenvalues against eigh: 1e-9 l3, the float64 bound of
 tests/test_imu_cov_gpu.py for accumulated matrices.  The residuals against the restatement's: the same angle bound.  All angles are
-rotation angles, 2 atan2(|vec|, |w|) of the relative quaternion.  The partial-sum kernel's reach is 1024 pairs, hence the 1025 case."""
+rotation angles, 2 atan2(|vec|, |w|) of the relative quaternion.  The partial-sum kernel's reach is 1024 pairs, hence the 1024 and 1025 cases."""
 import functools
 
 import numpy as np
@@ -23,7 +23,7 @@ from tests.test_imu_cov_gpu import _rounded
 
 pytestmark = pytest.mark.gpu
 
-REACH = 1024                                          # pairs one workgroup of the partial-sum kernel sums (csrc/imu_extrinsic.hip)
+REACH = 1024                                          # pairs one workgroup of the partial-sum kernel sums (csrc/imu_terms.h)
 EPS = 2.0 ** -52
 
 
@@ -213,7 +213,7 @@ def _check(tag, got, ref):
 
 # ------------------------------------------------------------------------------------------------ 1. parity and recovery
 @pytest.mark.parametrize('dtype', [np.float64, np.float32])
-@pytest.mark.parametrize('n', [2, 3, 65, 257, REACH + 1, 5000, 70001])
+@pytest.mark.parametrize('n', [2, 3, 65, 257, REACH, REACH + 1, 5000, 70001])
 def test_against_the_restatement_and_the_planted_truth(cuda, n, dtype):
     ref = measured(n, np.dtype(dtype).name)
     got = _solve(cuda, ref['qb'], ref['qc'], dtype)
