@@ -649,11 +649,13 @@ __device__ __forceinline__ V3 rot3(Q<double> q, V3 p) {
 __device__ __forceinline__ Q<double> conj(Q<double> q) { return {-q.x, -q.y, -q.z, q.w}; }
 template <class T> __device__ __forceinline__ Q<double> ldqd(const T* p) { return {(double)p[0], (double)p[1], (double)p[2], (double)p[3]}; }
 template <class T> __device__ __forceinline__ V3 ld3d(const T* p) { return p ? V3{(double)p[0], (double)p[1], (double)p[2]} : V3{0, 0, 0}; }
-// Jl(w)^T u = Jl(-w) u
+// Jl(w)^T u = Jl(-w) u.  c1 is the half-angle form, as B in imu_cov.hip: (1 - cos th) / th^2 loses eps / th^2 to the cancellation
+// (1e-8 just above the switch), and c1 multiplies w x u, which is first order in th.  c2 stands in front of a second-order term: the
+// cancellation in th - sin th costs eps there.
 __device__ __forceinline__ V3 JlT(V3 w, V3 u) {
     const double th2 = w.x * w.x + w.y * w.y + w.z * w.z, th = sqrt(th2);
     double c1, c2;
-    if (th > 1e-4) { c1 = (1.0 - cos(th)) / th2; c2 = (th - sin(th)) / (th2 * th); }
+    if (th > 1e-4) { const double sh = sin(0.5 * th); c1 = 2.0 * sh * sh / th2; c2 = (th - sin(th)) / (th2 * th); }
     else { c1 = 0.5 - th2 / 24.0; c2 = 1.0 / 6.0 - th2 / 120.0; }
     const V3 wu = cross3(w, u);
     return u + (-c1) * wu + c2 * cross3(w, wu);
