@@ -510,6 +510,42 @@ int islam_imu_gravity_bias_solve(const void* rot_ref, const void* pos_ref, const
                                  const double* jac, const double* cov, const double* weight, int rows, double gravity_norm, double* out_x,
                                  double* out_H, double* out_vel, void* scratch, int dtype, void* stream);
 
+/* Lever arm and metric scale in the closed-form alignment (the visual-inertial alignment of VINS-Mono,
+ * LinearAlignment in its initial_aligment.cpp, which solves the scale and takes the lever arm as known).  The reference has no
+ * counterpart: it reads rgb2imu_pose (T_IL) from the dataset.  It is islam_imu_gravity_bias_solve for a caller who has CAMERA
+ * positions and not yet the translation of the mount, or positions up to a scale.  The mount is body <- camera, T_IL = (R_x, t); with
+ *   Rc_i, q_i  world rotation and position of the CAMERA at pose i = 0 .. n (VO; q_i possibly up to the scale s),
+ * the body poses are R_i = Rc_i R_x^T and p_i = s q_i - R_i t.  Put into (P_i), (V_i) above, with the velocities v_i of the BODY
+ * eliminated in the same way, every pair of consecutive intervals i = 0 .. n-2 leaves three equations in x = [g(3); b(3); t(3); s]:
+ *   A_i [g; b] + T_i t - s Q_i = m_i,   A_i as above,
+ *   T_i = (R_{i+1} - R_i) / d_i - (R_{i+2} - R_{i+1}) / d_{i+1},
+ *   Q_i = (q_{i+1} - q_i) / d_i - (q_{i+2} - q_{i+1}) / d_{i+1},
+ *   m_i = R_{i+1} dp_{i+1} / d_{i+1} - R_i dp_i / d_i + R_i dv_i.
+ * solve_lever, solve_scale (0 or 1 each, not both 0: that case is islam_imu_gravity_bias_solve on body positions) say which of t and
+ * s are unknowns.  t not solved: t = 0, the columns T_i are exact zeros.  s not solved: s = 1, the column -Q_i is exact zeros and Q_i
+ * joins the right-hand side.  jac NULL: b = 0 as above.  The unknowns that are solved (3 to 10, in the order g, b, t, s) minimise
+ * sum_i w_i | L_i^-1 (Y_i [x; -1]) |^2 with Y_i = [A_i | T_i | -Q_i | rhs_i]; weight, cov, C_i = L_i L_i^T, the pivot rule, the pairs
+ * that take part and their count are exactly islam_imu_gravity_bias_solve's.  The normal matrix (up to 10x10) is solved by Cholesky
+ * under the same pivot rule.  gravity_norm = G > 0: the same four rounds on the same (H, c), with b1, b2 as above and the (n-1) x (n-1)
+ * projection onto g = G gh + [b1 b2] u solved for u and every other unknown.  The velocities of the body follow by back-substitution,
+ *   v_i = ( s (q_{k+1} - q_k) - (R_{k+1} - R_k) t - g d_k^2 / 2 - R_k (dp_k + Jp_k b) ) / d_k,   k = i,
+ * and for a pose whose own interval is missing or has d <= 0: k = i - 1, plus g d_k + R_k (dv_k + Jv_k b); NaN if that has d <= 0 too.
+ * rot_body (rows + 1, 4) xyzw: the world rotation of the BODY, R_i = Rc_i R_x^T (the caller conjugates, R_x e.g. from
+ * islam_imu_extrinsic_rot_solve); pos_cam (rows + 1, 3): q_i; dts, dvel, dpos, jac, cov, weight as for islam_imu_gravity_bias_solve.
+ * Without rotation between the poses T_i = 0 and t is unobservable (ISLAM_ENOTPD); without acceleration s is.
+ * out_x: 10 doubles [g, b, t, s]; unknowns that are not solved are exactly 0.0 (b, t) and exactly 1.0 (s).  out_H: 100 doubles or NULL,
+ * the 10x10 normal matrix, symmetric, exact zeros in the rows and columns of unknowns that are not solved.  out_vel: (rows + 1, 3)
+ * doubles or NULL (all device memory).  Returns the number of excluded pairs (>= 0), or ISLAM_ENOTPD when the normal matrix (or its
+ * projection) fails the pivot rule or no pair takes part (rows <= 1 included): all ten of out_x and out_vel are then zeros, out_H is
+ * still written; or ISLAM_EARG, before any device work: the argument errors of islam_imu_gravity_bias_solve, solve_lever or
+ * solve_scale not 0 or 1, both 0.  Same bits on a second call and behind a weight of zero, as above.  The call synchronises the stream
+ * (one 8-byte read-back).  scratch: islam_imu_lever_scale_solve_scratch_bytes(rows) bytes (528 B per pair). */
+size_t islam_imu_lever_scale_solve_scratch_bytes(int rows);
+int islam_imu_lever_scale_solve(const void* rot_body, const void* pos_cam, const void* dts, const void* dvel, const void* dpos,
+                                const double* jac, const double* cov, const double* weight, int rows, int solve_lever, int solve_scale,
+                                double gravity_norm, double* out_x /*10*/, double* out_H /*100, optional*/,
+                                double* out_vel /*(rows + 1) * 3, optional*/, void* scratch, int dtype, void* stream);
+
 /* Camera-IMU extrinsic rotation from pairs of relative rotations, in closed form (the rotation calibration of
  * VINS-Mono, CalibrationExRotation in its initial_ex_rotation.cpp).  The reference has no counterpart: it reads rgb2imu_pose (T_IL) from
  * the dataset, and every other solve of this header assumes it.  For pair i = 0 .. rows-1

@@ -123,6 +123,8 @@ SIGNATURES = {
     'islam_imu_gyro_bias_solve': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p]),
     'islam_imu_gravity_bias_solve_scratch_bytes': (c_size_t, [c_int]),
     'islam_imu_gravity_bias_solve': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 4 + [c_int, c_void_p]),
+    'islam_imu_lever_scale_solve_scratch_bytes': (c_size_t, [c_int]),
+    'islam_imu_lever_scale_solve': (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_double] + [c_void_p] * 4 + [c_int, c_void_p]),
     'islam_imu_extrinsic_rot_solve_scratch_bytes': (c_size_t, [c_int]),
     'islam_imu_extrinsic_rot_solve': (c_int, [c_void_p] * 3 + [c_int, c_double, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
     'islam_pvgo_default_params': (None, [ctypes.POINTER(PvgoParams)]),

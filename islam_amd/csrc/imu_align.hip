@@ -16,55 +16,16 @@
 
 #include <cmath>
 
+#include "imu_mat.h"
 #include "imu_terms.h"
 
 using namespace islam;
+using namespace islam::imat;
 using namespace islam::tsum;
 
 namespace {
 
 constexpr int NT = 28;                // per-pair terms: H upper triangle by rows (21) | c (6) | excluded (1)
-constexpr double PIVOT_REL = 1e-13;   // islam_imu_gyro_bias_solve's rule: a pivot at or below this share of its diagonal entry fails
-
-// rotation matrix (by rows) of a unit quaternion xyzw
-template <class T>
-__device__ __forceinline__ void quat_mat(const T* q, double (&R)[9]) {
-    const double x = (double)q[0], y = (double)q[1], z = (double)q[2], w = (double)q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w); R[2] = 2.0 * (x * z + y * w);
-    R[3] = 2.0 * (x * y + z * w); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
-    R[6] = 2.0 * (x * z - y * w); R[7] = 2.0 * (y * z + x * w); R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-template <class T>
-__device__ __forceinline__ void ld_vec(const T* p, double (&v)[3]) { v[0] = (double)p[0]; v[1] = (double)p[1]; v[2] = (double)p[2]; }
-
-__device__ __forceinline__ void mat_vec(const double (&R)[9], const double (&v)[3], double (&o)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = R[3 * k] * v[0] + R[3 * k + 1] * v[1] + R[3 * k + 2] * v[2];
-}
-
-__device__ __forceinline__ void mat_mat(const double (&a)[9], const double (&b)[9], double (&o)[9]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-}
-
-// o = a b^T
-__device__ __forceinline__ void mat_matT(const double (&a)[9], const double (&b)[9], double (&o)[9]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = a[3 * i] * b[3 * j] + a[3 * i + 1] * b[3 * j + 1] + a[3 * i + 2] * b[3 * j + 2];
-}
-
-// the 3x3 block (r0.., c0..) of a row-major matrix with `ld` columns
-__device__ __forceinline__ void ld_block(const double* m, int ld, int r0, int c0, double (&o)[9]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = m[(r0 + i) * ld + c0 + j];
-}
 
 // One lane per pair of consecutive intervals i, i + 1 (P = rows - 1 pairs).
 template <class T>
@@ -180,35 +141,6 @@ __global__ __launch_bounds__(BLOCK) void ga_partial_kernel(const double* __restr
     partial_sum<NT>(terms, P, nblocks, partial);
 }
 
-// M (n x n, row stride 6) = L L^T under the pivot rule, then L L^T x = rhs.  Every array lives in LDS.
-__device__ bool chol_solve(const double* M, const double* rhs, int n, double* L, double* x) {
-    for (int j = 0; j < n; ++j) {
-        double p = M[6 * j + j];
-        for (int k = 0; k < j; ++k) p -= L[6 * j + k] * L[6 * j + k];
-        if (!(p > PIVOT_REL * M[6 * j + j]) || !isfinite(p)) return false;
-        const double l = sqrt(p);
-        L[6 * j + j] = l;
-        for (int i = j + 1; i < n; ++i) {
-            double v = M[6 * i + j];
-            for (int k = 0; k < j; ++k) v -= L[6 * i + k] * L[6 * j + k];
-            L[6 * i + j] = v / l;
-        }
-    }
-    bool fin = true;
-    for (int i = 0; i < n; ++i) {
-        double v = rhs[i];
-        for (int k = 0; k < i; ++k) v -= L[6 * i + k] * x[k];
-        x[i] = v / L[6 * i + i];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double v = x[i];
-        for (int k = i + 1; k < n; ++k) v -= L[6 * k + i] * x[k];
-        x[i] = v / L[6 * i + i];
-        fin = fin && isfinite(x[i]);
-    }
-    return fin;
-}
-
 struct SolveLds {
     double H[36], c[6], L[36], x[6], B[36], HB[36], M[36], rr[6], z[6], gh[3];
 };
@@ -254,7 +186,7 @@ __device__ bool norm_rounds(SolveLds& S, int n, double G) {
         }
         for (int i = 0; i < m; ++i)                       // the exactly symmetric part: M_ij and M_ji differ by rounding
             for (int j = 0; j < i; ++j) S.M[6 * i + j] = S.M[6 * j + i] = 0.5 * (S.M[6 * i + j] + S.M[6 * j + i]);
-        if (!chol_solve(S.M, S.rr, m, S.L, S.z)) return false;
+        if (!chol_solve<6>(S.M, S.rr, m, S.L, S.z)) return false;
         double g[3];
         for (int k = 0; k < 3; ++k) g[k] = G * S.gh[k] + b1[k] * S.z[0] + b2[k] * S.z[1];
         gn = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
@@ -277,7 +209,7 @@ __global__ __launch_bounds__(BLOCK) void ga_solve_kernel(const double* __restric
     for (int a = 0; a < 6; ++a)
         for (int b = a; b < 6; ++b) { S.H[6 * a + b] = S.H[6 * b + a] = tot[idx]; ++idx; }
     for (int a = 0; a < 6; ++a) { S.c[a] = tot[21 + a]; S.x[a] = 0.0; }
-    bool pd = chol_solve(S.H, S.c, n, S.L, S.x);
+    bool pd = chol_solve<6>(S.H, S.c, n, S.L, S.x);
     if (pd && G > 0.0) pd = norm_rounds(S, n, G);
     for (int a = 0; a < 6; ++a) out_x[a] = pd && a < n ? S.x[a] : 0.0;
     if (out_H)

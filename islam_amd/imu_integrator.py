@@ -210,6 +210,35 @@ class IMUModule:
             res = torch.cat((self.gyro_bias.to(torch.float64) + dbg, H.reshape(9))).cpu()
         return res[0:3].contiguous(), res[3:12].view(3, 3).contiguous()
 
+    def _alignment_rows(self, st, end, use_cov):
+        """The rows of the closed-form alignment solves over frames [st, end], on the device: (n, durations (n), dvel, dpos (n, 3) in the
+        start-body frame of their frame, bias Jacobians (n, 9, 6), motion-mode covariances (n, 9, 9) or None).  The motion rows are
+        integrated with gravity 0 and the module's current ``gyro_bias`` and ``accel_bias`` subtracted."""
+        b0 = int(self.rgb2imu_sync[st])
+        b1 = int(self.rgb2imu_sync[end]) + 1
+        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
+        seg = torch.from_numpy(seg_host).to(self.device)
+        n = len(seg_host) - 1
+        dts = self.dts[b0:b1, 0].contiguous()
+        gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
+        accels = (self.accels[b0:b1] - self.accel_bias.view(1, 3)).contiguous()
+        init = torch.zeros(10, dtype=self.dtype, device=self.device)
+        init[6] = 1.0
+        world, motion, _ = ops.imu_preint_both(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0)
+        # motion rows hold R0_i dv_i, R0_i dp_i with R0_i = row i of the world rotations from the identity (include/islam_hip.h)
+        R0t = pp._qmat(world[1][:n].to(torch.float64)).transpose(-1, -2)
+        dvel = (R0t @ motion[2].to(torch.float64).unsqueeze(-1)).squeeze(-1).to(self.dtype)
+        dpos = (R0t @ motion[0].to(torch.float64).unsqueeze(-1)).squeeze(-1).to(self.dtype)
+        # d_i = the sum of the frame's dt, in a fixed order: the frames padded to the longest one
+        maxF = int(np.max(np.diff(seg_host))) if n > 0 else 0
+        idx = seg[:-1, None] + torch.arange(max(maxF, 1), device=self.device)[None, :]
+        inside = idx < seg[1:, None]
+        dur = torch.where(inside, dts.to(torch.float64)[idx.clamp(max=max(b1 - b0 - 1, 0))], torch.zeros((), dtype=torch.float64,
+                          device=self.device)).sum(1).to(self.dtype)
+        jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
+        cov = ops.imu_preint_cov(dts, gyros, accels, seg, seg_host, self.gyro_cov, self.acc_cov, True) if use_cov else None
+        return n, dur, dvel, dpos, jac, cov
+
     def estimate_gravity_accel_bias(self, st, end, ref_rots, ref_pos, weight=None, use_cov=False, gravity_norm=None):
         """Gravity, accelerometer bias and velocities of frames [st, end] from world poses of the IMU body the caller trusts
         (``ref_rots``: (end - st + 1, 4) xyzw quaternions or an SO3, ``ref_pos``: (end - st + 1, 3); VO or PVGO-optimised, rgb2imu
@@ -221,40 +250,51 @@ class IMUModule:
         of the poses, ``accel_bias + b`` (3), velocities (end - st + 1, 3), the 6x6 normal matrix H), on the CPU in float64.  The
         gravity is the world acceleration (v' = R a + g), about (0, 0, -9.81) in a z-up world.  Run ``estimate_gyro_bias`` first: the
         gyro-bias sensitivity of the increments is not part of this solve.  The module is not changed."""
-        b0 = int(self.rgb2imu_sync[st])
-        b1 = int(self.rgb2imu_sync[end]) + 1
-        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
-        seg = torch.from_numpy(seg_host).to(self.device)
-        n = len(seg_host) - 1
         rots = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
         rots = rots.detach().to(self.dtype).to(self.device)
         poss = torch.as_tensor(np.asarray(ref_pos)).detach().to(self.dtype).to(self.device)
         if weight is not None:
             weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
         with torch.no_grad():
-            dts = self.dts[b0:b1, 0].contiguous()
-            gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
-            accels = (self.accels[b0:b1] - self.accel_bias.view(1, 3)).contiguous()
-            init = torch.zeros(10, dtype=self.dtype, device=self.device)
-            init[6] = 1.0
-            world, motion, _ = ops.imu_preint_both(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0)
-            # motion rows hold R0_i dv_i, R0_i dp_i with R0_i = row i of the world rotations from the identity (include/islam_hip.h)
-            R0t = pp._qmat(world[1][:n].to(torch.float64)).transpose(-1, -2)
-            dvel = (R0t @ motion[2].to(torch.float64).unsqueeze(-1)).squeeze(-1).to(self.dtype)
-            dpos = (R0t @ motion[0].to(torch.float64).unsqueeze(-1)).squeeze(-1).to(self.dtype)
-            # d_i = the sum of the frame's dt, in a fixed order: the frames padded to the longest one
-            maxF = int(np.max(np.diff(seg_host))) if n > 0 else 0
-            idx = seg[:-1, None] + torch.arange(max(maxF, 1), device=self.device)[None, :]
-            inside = idx < seg[1:, None]
-            dur = torch.where(inside, dts.to(torch.float64)[idx.clamp(max=max(b1 - b0 - 1, 0))], torch.zeros((), dtype=torch.float64,
-                              device=self.device)).sum(1).to(self.dtype)
-            jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
-            cov = ops.imu_preint_cov(dts, gyros, accels, seg, seg_host, self.gyro_cov, self.acc_cov, True) if use_cov else None
+            n, dur, dvel, dpos, jac, cov = self._alignment_rows(st, end, use_cov)
             g, b, H, vel, _ = ops.imu_gravity_bias_solve(rots, poss, dur, dvel, dpos, jac, cov, weight, gravity_norm)
             res = torch.cat((g, self.accel_bias.to(torch.float64) + b, vel.reshape(-1), H.reshape(36))).cpu()
         o = 6 + 3 * (n + 1)
         return res[0:3].contiguous(), res[3:6].contiguous(), res[6:o].view(n + 1, 3).contiguous(), res[o:o + 36].view(6, 6).contiguous()
 
+    def estimate_lever_arm(self, st, end, cam_rots, cam_pos, ext_rot, weight=None, use_cov=False, gravity_norm=None, solve_scale=False):
+        """Lever arm of the camera-IMU mount (the translation of ``rgb2imu_pose``), gravity, accelerometer bias, velocities and, with
+        ``solve_scale``, the metric scale of the positions, of frames [st, end] from world poses of the CAMERA (``cam_rots``:
+        (end - st + 1, 4) xyzw quaternions or an SO3, ``cam_pos``: (end - st + 1, 3); VO, no rgb2imu applied; monocular positions may be
+        up to a scale), in closed form (islam_imu_lever_scale_solve).  ``ext_rot``: (4) xyzw, the rotation of ``rgb2imu_pose``, e.g. the
+        q of ``estimate_extrinsic_rotation``; the body rotations ``cam_rots (x) ext_rot^-1`` are formed in float64.  The rows are
+        built exactly as ``estimate_gravity_accel_bias`` builds them, and ``weight``, ``use_cov`` and ``gravity_norm`` mean what they mean
+        there.  Returns (gravity (3) in the frame of the poses, ``accel_bias + b`` (3), the lever arm t (3) in the body frame, the scale
+        s (a 0-d tensor, exactly 1 unless ``solve_scale``), the velocities of the BODY (end - st + 1, 3), the 10x10 normal matrix H in the
+        order g, b, t, s), on the CPU in float64; the body position of pose i is ``s cam_pos_i - R_i t``.  The lever arm needs rotation
+        between the frames and the scale needs acceleration: a stream without them raises IslamHipError (ISLAM_ENOTPD).  Order of calls:
+        ``estimate_extrinsic_rotation``, then ``estimate_gyro_bias`` on the camera rotations conjugated by q, then this.  The module is
+        not changed."""
+        cam = cam_rots.tensor() if hasattr(cam_rots, 'tensor') else torch.as_tensor(np.asarray(cam_rots))
+        ext = ext_rot.tensor() if hasattr(ext_rot, 'tensor') else torch.as_tensor(np.asarray(ext_rot))
+        cam = cam.detach().to(torch.float64).to(self.device)
+        ext = ext.detach().to(torch.float64).to(self.device).reshape(4)
+        poss = torch.as_tensor(np.asarray(cam_pos)).detach().to(self.dtype).to(self.device)
+        if weight is not None:
+            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+        with torch.no_grad():
+            # R_i = Rc_i R_x^T: the quaternion product of cam_i and the conjugate of ext
+            x, y, z, w = cam.unbind(-1)
+            cx, cy, cz, cw = -ext[0], -ext[1], -ext[2], ext[3]
+            rots = torch.stack((w * cx + x * cw + y * cz - z * cy, w * cy - x * cz + y * cw + z * cx, w * cz + x * cy - y * cx + z * cw,
+                                w * cw - x * cx - y * cy - z * cz), -1).to(self.dtype)
+            n, dur, dvel, dpos, jac, cov = self._alignment_rows(st, end, use_cov)
+            g, b, t, s, H, vel, _ = ops.imu_lever_scale_solve(rots, poss, dur, dvel, dpos, jac, cov, weight, True, bool(solve_scale),
+                                                              gravity_norm)
+            res = torch.cat((g, self.accel_bias.to(torch.float64) + b, t, s.reshape(1), vel.reshape(-1), H.reshape(100))).cpu()
+        o = 10 + 3 * (n + 1)
+        return (res[0:3].contiguous(), res[3:6].contiguous(), res[6:9].contiguous(), res[9].clone(), res[10:o].view(n + 1, 3).contiguous(),
+                res[o:o + 100].view(10, 10).contiguous())
 
     def estimate_extrinsic_rotation(self, st, end, cam_rots, weight=None, delta=None, rounds=4, min_gap=None):
         """Rotation of the camera-IMU mount from the relative rotations of frames [st, end], in closed form
@@ -268,8 +308,10 @@ class IMUModule:
         T_IL^-1).  The eigenvalues are the observability diagnosis: rotations about one axis only leave q undetermined and give
         eig[1] ~ eig[0] without an error; with ``min_gap`` a ``ValueError`` is raised when (eig[1] - eig[0]) / eig[3] < min_gap.
         A gyro-bias error perturbs q at first order (it rotates every DR_i), so the order of calls is: this first, then
-        ``estimate_gyro_bias`` on the camera rotations conjugated by q (q (x) cam_i (x) q^-1).  Out of scope: the joint refinement of
-        the two, the lever arm (the translation of T_IL) and the time offset between the two sensors.  The module is not changed."""
+        ``estimate_gyro_bias`` on the camera rotations conjugated by q (q (x) cam_i (x) q^-1), then ``estimate_lever_arm``, which gives
+        the lever arm (the translation of T_IL) with gravity, accelerometer bias and velocities (``estimate_gravity_accel_bias`` is the
+        solve for a known lever arm).  Out of scope: the joint refinement of rotation and gyro bias and the time offset between the two
+        sensors.  The module is not changed."""
         b0 = int(self.rgb2imu_sync[st])
         b1 = int(self.rgb2imu_sync[end]) + 1
         seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)

@@ -952,6 +952,37 @@ def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None
     return out[0:3], out[3:6], out[6:42].view(6, 6), out[42:].view(rows + 1, 3), int(rc)
 
 
+def imu_lever_scale_solve(rot_body, pos_cam, dts, dvel, dpos, jac=None, cov=None, weight=None, solve_lever=True, solve_scale=False,
+                          gravity_norm=None):
+    """imu_gravity_bias_solve with the lever arm t of the camera-IMU mount and / or the scale s of the camera positions as further
+    unknowns, in closed form (islam_imu_lever_scale_solve; definition in include/islam_hip.h).  rot_body (rows + 1, 4) xyzw: world
+    rotations of the IMU BODY (the camera's conjugated by the mount's rotation), pos_cam (rows + 1, 3): world positions of the
+    CAMERA, body position = s pos_cam - R_body t; dts, dvel, dpos, jac, cov, weight, gravity_norm as for imu_gravity_bias_solve.
+    solve_lever / solve_scale: which of t and s are unknowns (not both False: that is imu_gravity_bias_solve).  Returns (g (3),
+    b (3), t (3), s (), H (10, 10), vel (rows + 1, 3) of the body, number of excluded pairs), float64 on the device; unknowns that are
+    not solved come back as exactly 0 (b, t) and 1 (s), with zero rows and columns in H.  Raises IslamHipError (code ISLAM_ENOTPD)
+    when the normal matrix is singular (no rotation between the poses leaves t undetermined).  Synchronises the stream."""
+    require_cuda(rot_body, pos_cam, dts, dvel, dpos, jac, cov, weight)
+    rows = int(dts.shape[0])
+    dtype = dts.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = dts.device
+    with torch.no_grad():
+        io = [_imu_arg(t, dtype, shape, name) for t, shape, name in (
+            (rot_body, (rows + 1, 4), 'rot_body'), (pos_cam, (rows + 1, 3), 'pos_cam'), (dts, (rows,), 'dts'), (dvel, (rows, 3), 'dvel'),
+            (dpos, (rows, 3), 'dpos'))]
+        f64 = [_imu_arg(t, torch.float64, shape, name) for t, shape, name in (
+            (jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight'))]
+        out = torch.empty(110 + 3 * (rows + 1), dtype=torch.float64, device=dev)
+        scratch = torch.empty(lib().islam_imu_lever_scale_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
+        rc = lib().islam_imu_lever_scale_solve(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows, int(solve_lever), int(solve_scale),
+                                               c_double(0.0 if gravity_norm is None else float(gravity_norm)), ptr(out[0:10]),
+                                               ptr(out[10:110]), ptr(out[110:]), ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return out[0:3], out[3:6], out[6:9], out[9], out[10:110].view(10, 10), out[110:].view(rows + 1, 3), int(rc)
+
+
 def imu_extrinsic_rot_solve(rot_imu, rot_cam, weight=None, delta=None, rounds=4):
     """Camera-IMU extrinsic rotation from pairs of relative rotations, in closed form (islam_imu_extrinsic_rot_solve; definition in
     include/islam_hip.h).  rot_imu (rows, 4) xyzw: the IMU's relative rotation over every frame (the motion rows' rotations), rot_cam
