@@ -275,7 +275,8 @@ int islam_pvgo_eliminate_level0(double* Hd, const double* Ho, const double* rhs,
     if (plan_levels(N, seg_len, sp, solve_twisted()) < 2) return fail(ISLAM_EARG, "islam_pvgo_eliminate_level0: single-level problem");
     LevelSrc src{};
     src.level0 = 1; src.Hd = Hd; src.Ho = Ho; src.rhs0 = rhs; src.state = nullptr; src.damping_override = damping;
-    launch_eliminate(sp.lv[0], sp.twisted != 0, src, level_dst(w.lv[0], w.lv[0].x), w.flags, as_stream(stream), Gate{nullptr, 0.0});
+    const int rc_l = launch_eliminate(sp.lv[0], sp.twisted != 0, src, level_dst(w.lv[0], w.lv[0].x), w.flags, as_stream(stream), Gate{nullptr, 0.0});
+    if (rc_l != ISLAM_OK) return rc_l;
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

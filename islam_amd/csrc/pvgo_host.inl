@@ -210,25 +210,39 @@ static int next_serial() {
     return serial;
 }
 
-static void launch_tw(const LevelSrc& src, const LevelDst& dst, int n, int m, int* flags, int seg0, int nseg, Gate gate, hipStream_t s) {
+// the flat form of a level's product arrays as sources (ProdRef); they are carved contiguously everywhere, so a failure is a logic error
+static int prod_ref_or_fail(const LevelSrc& src, ProdRef& pr) {
+    if (!prod_ref(src, pr)) return fail(ISLAM_EARG, "pvgo: the products of a level (%d segments) are not one contiguous carving", src.Pprev);
+    return ISLAM_OK;
+}
+
+static int launch_tw(const LevelSrc& src, const LevelDst& dst, int n, int m, int* flags, int seg0, int nseg, Gate gate, hipStream_t s) {
     // level 0 of a graph with >= 3072 segments (four rounds of resident workgroups) runs on the two-wave kernel: N = 300 007, 37 504
     // segments: 1266 -> 1205 us per LM iteration.  (ISLAM_PVGO_L0_TW2 = that threshold; 0: never)
     static const int tw2_from = env_int("ISLAM_PVGO_L0_TW2", 3072);
     if (src.level0 && tw2_from > 0 && nseg >= tw2_from) {
         hipLaunchKernelGGL(bt_eliminate_tw2_kernel, dim3(xcd_grid(nseg)), dim3(128), 0, s, src, dst, n, m, flags, seg0, nseg, gate);
-        return;
+        return ISLAM_OK;
     }
-    if (src.level0) hipLaunchKernelGGL(bt_eliminate_tw_kernel<1>, dim3(xcd_grid(nseg)), dim3(192), 0, s, src, dst, n, m, flags, seg0, nseg, gate);
-    else hipLaunchKernelGGL(bt_eliminate_tw_kernel<0>, dim3(xcd_grid(nseg)), dim3(192), 0, s, src, dst, n, m, flags, seg0, nseg, gate);
+    if (src.level0) {
+        hipLaunchKernelGGL(bt_eliminate_tw_kernel<1>, dim3(xcd_grid(nseg)), dim3(192), 0, s, (const double*)nullptr, 0u, 0u, 0u, 0u, 0u, 0u, n, m,
+                           seg0, nseg, 0, src, dst, flags, gate);
+        return ISLAM_OK;
+    }
+    ProdRef pr;
+    const int rc = prod_ref_or_fail(src, pr);
+    if (rc != ISLAM_OK) return rc;
+    hipLaunchKernelGGL(bt_eliminate_tw_kernel<0>, dim3(xcd_grid(nseg)), dim3(192), 0, s, pr.base, pr.rsep, pr.cL, pr.cR, pr.fill, pr.cgL, pr.cgR,
+                       n, m, seg0, nseg, src.Pprev, src, dst, flags, gate);
+    return ISLAM_OK;
 }
 
 // the up-sweep launch of one level below the root: one workgroup per segment (three wavefronts when twisted)
-static void launch_eliminate(const LevelPlan& L, bool tw, const LevelSrc& src, const LevelDst& dst, int* flags, hipStream_t s,
-                             Gate gate) {
-    if (tw)
-        launch_tw(src, dst, L.n, L.m, flags, 0, L.P, gate, s);
-    else
-        hipLaunchKernelGGL(bt_eliminate_kernel, dim3(xcd_grid(L.P)), dim3(64), 0, s, src, dst, L.n, L.m, flags, 0, L.P, gate);
+static int launch_eliminate(const LevelPlan& L, bool tw, const LevelSrc& src, const LevelDst& dst, int* flags, hipStream_t s,
+                            Gate gate) {
+    if (tw) return launch_tw(src, dst, L.n, L.m, flags, 0, L.P, gate, s);
+    hipLaunchKernelGGL(bt_eliminate_kernel, dim3(xcd_grid(L.P)), dim3(64), 0, s, src, dst, L.n, L.m, flags, 0, L.P, gate);
+    return ISLAM_OK;
 }
 
 // Enqueue levels [lbegin, nl): `first` describes the source of level lbegin (level-0 arrays, or the level-0 products when
@@ -255,7 +269,8 @@ int enqueue_levels(const Workspace& w, const SolvePlan& sp, int lbegin, const Le
     const bool tw = sp.twisted && sweep && lbegin == 0;
     for (int l = lbegin; l < top; ++l) {
         if (l == lbegin && skip_first) continue;
-        launch_eliminate(sp.lv[l], tw, src_of(l), level_dst(w.lv[l], x_of(l)), flags, s, gate);
+        const int rc_l = launch_eliminate(sp.lv[l], tw, src_of(l), level_dst(w.lv[l], x_of(l)), flags, s, gate);
+        if (rc_l != ISLAM_OK) return rc_l;
         if (evs) (void)hipEventRecord(evs[ne++], s);
     }
     if (sweep) {

@@ -88,9 +88,10 @@ int shard_upsweep_gated(double* Hd, const double* Ho, const double* rhs, double 
         }
         LevelBufs ob = w.lv[l];
         if (l == R.xl) { ob.Dsep = xb.Dsep; ob.rsep = xb.rsep; ob.cL = xb.cL; ob.cR = xb.cR; ob.fill = xb.fill; ob.cgL = xb.cgL; ob.cgR = xb.cgR; }
-        if (sp.twisted)
-            launch_tw(src, level_dst(ob, nullptr), sp.lv[l].n, sp.lv[l].m, flags, R.seg0[l], R.nseg[l], gate, s);
-        else
+        if (sp.twisted) {
+            const int rc_l = launch_tw(src, level_dst(ob, nullptr), sp.lv[l].n, sp.lv[l].m, flags, R.seg0[l], R.nseg[l], gate, s);
+            if (rc_l != ISLAM_OK) return rc_l;
+        } else
             hipLaunchKernelGGL(bt_eliminate_kernel, dim3(xcd_grid(R.nseg[l])), dim3(64), 0, s, src, level_dst(ob, nullptr), sp.lv[l].n,
                                sp.lv[l].m, flags, R.seg0[l], R.nseg[l], gate);
     }
@@ -134,8 +135,10 @@ static int shard_downsweep_planned(const SolvePlan& sp, const ShardRanges& R, co
     auto src_of = [&](int l) { return level_src_from(l == xl + 1 ? pb : w.lv[l - 1], sp.lv[l - 1].P); };
     double* x0 = dx - (ptrdiff_t)node0 * 9;                                   // level-0 solution, global indexing
     auto x_of = [&](int l) { return l == 0 ? x0 : w.lv[l].x; };
-    for (int l = xl + 1; l < top; ++l)
-        launch_eliminate(sp.lv[l], tw, src_of(l), level_dst(w.lv[l], x_of(l)), flags, s, gate);
+    for (int l = xl + 1; l < top; ++l) {
+        const int rc_l = launch_eliminate(sp.lv[l], tw, src_of(l), level_dst(w.lv[l], x_of(l)), flags, s, gate);
+        if (rc_l != ISLAM_OK) return rc_l;
+    }
     const int serial = next_serial();
     SweepArgs a{};
     a.root_src = src_of(top);
@@ -385,9 +388,11 @@ struct ShardRun : ChainRun {
     // decision_only: an accepted trial would be the last optimizer step (StopOnPlateau's step limit) -- no solve follows it, only the
     // scalars of the message matter (the blocks in front of them are whatever the buffer holds, the same on every rank)
     int enqueue_rest(int pb, int mode, int damp_mode, bool with_trial, double seq, const Gate& gate, bool decision_only = false) {
-        for (int l = 1; l <= xl && !decision_only; ++l)
-            launch_tw(level_src_from(w.lv[l - 1], sp.lv[l - 1].P), level_dst(level_out(l), nullptr), sp.lv[l].n, sp.lv[l].m, w.flags, R.seg0[l],
-                      R.nseg[l], gate, s);
+        for (int l = 1; l <= xl && !decision_only; ++l) {
+            const int rc_l = launch_tw(level_src_from(w.lv[l - 1], sp.lv[l - 1].P), level_dst(level_out(l), nullptr), sp.lv[l].n, sp.lv[l].m,
+                                       w.flags, R.seg0[l], R.nseg[l], gate, s);
+            if (rc_l != ISLAM_OK) return rc_l;
+        }
         PackArgs pa{};
         pa.f.n = xl;
         for (int l = 0; l < xl; ++l) { pa.f.cL[l] = w.lv[l].cL + (size_t)R.seg0[l] * 81; pa.f.cgL[l] = w.lv[l].cgL + (size_t)R.seg0[l] * 9; }
@@ -473,7 +478,7 @@ struct ShardRun : ChainRun {
                 const Gate gate{w.state, epoch};
                 LevelSrc src{};
                 src.level0 = 1; src.Hd = HD[A.pb]; src.Ho = HO[A.pb]; src.rhs0 = RH[A.pb]; src.state = w.state; src.hist = 1;
-                launch_tw(src, level_dst(level_out(0), nullptr), N_eff, m, w.flags, seg_lo, nseg, gate, s);
+                if ((rc = launch_tw(src, level_dst(level_out(0), nullptr), N_eff, m, w.flags, seg_lo, nseg, gate, s)) != ISLAM_OK) return rc;
                 if ((rc = enqueue_rest(A.pb, 1, 1, false, seq, gate)) != ISLAM_OK) return rc;
             }
             if ((rc = enqueue_trial(A, seq + 1.0, epoch, false, t.steps)) != ISLAM_OK) return rc;

@@ -15,6 +15,37 @@ struct LevelSrc {
     const double *Dsep, *rsep, *cL, *cR, *cgL, *cgR, *fill;
     int Pprev;                   // number of segments of the previous level
 };
+// The products of a level are carved contiguously (Dsep first: carve, products_view), so a kernel can take them as ONE base pointer
+// and six 32-bit offsets in doubles -- flat leading kernel arguments, which arrive in SGPRs with the wave (kernel-argument preload
+// takes only a leading run of scalars and pointers, never a struct), instead of seven pointers inside LevelSrc, which every wave
+// fetches with a scalar load that is cold after the kernel boundary before it can form its first address.
+// prod_ref (launcher) and prod_bind (kernel) are the two directions of the same map.
+struct ProdRef { const double* base; unsigned rsep, cL, cR, fill, cgL, cgR; };
+__host__ __device__ __forceinline__ void prod_bind(LevelSrc& s, const double* base, unsigned o_rsep, unsigned o_cL, unsigned o_cR,
+                                                   unsigned o_fill, unsigned o_cgL, unsigned o_cgR, int Pprev) {
+    s.level0 = 0;
+    s.Dsep = base; s.rsep = base + o_rsep; s.cL = base + o_cL; s.cR = base + o_cR; s.fill = base + o_fill; s.cgL = base + o_cgL;
+    s.cgR = base + o_cgR; s.Pprev = Pprev;
+}
+// false: the arrays do not lie behind Dsep within 2^32 doubles (not a carved level)
+static inline bool prod_ref(const LevelSrc& s, ProdRef& r) {
+    const double* const a[6] = {s.rsep, s.cL, s.cR, s.fill, s.cgL, s.cgR};
+    unsigned o[6];
+    if (s.Dsep == nullptr) return false;
+    for (int i = 0; i < 6; ++i) {
+        const ptrdiff_t d = a[i] - s.Dsep;
+        if (d < 0 || d > (ptrdiff_t)0xffffffffll) return false;
+        o[i] = (unsigned)d;
+    }
+    r = ProdRef{s.Dsep, o[0], o[1], o[2], o[3], o[4], o[5]};
+    LevelSrc back{};
+    prod_bind(back, r.base, r.rsep, r.cL, r.cR, r.fill, r.cgL, r.cgR, s.Pprev);
+    return back.rsep == s.rsep && back.cL == s.cL && back.cR == s.cR && back.fill == s.fill && back.cgL == s.cgL && back.cgR == s.cgR;
+}
+#define ISLAM_PROD_PARAMS const double* pbase, unsigned o_rsep, unsigned o_cL, unsigned o_cR, unsigned o_fill, unsigned o_cgL, unsigned o_cgR
+#define ISLAM_PROD_ARGS pbase, o_rsep, o_cL, o_cR, o_fill, o_cgL, o_cgR
+constexpr int PROD_DWORDS = 8;               // dwords ISLAM_PROD_PARAMS takes
+
 struct LevelDst {
     double *fac, *inv;           // n x 252, n x 9
     double *Dsep, *rsep;         // (n / stride) x 81, x 9
@@ -52,6 +83,11 @@ __device__ __forceinline__ LaneSrc lane_source(const LevelSrc& s, int lane) {
     L.sa = enA ? (L.isG ? 1 : 9) : 0;
     L.nsB = L.nsC = enBC ? (L.isG ? 9 : 81) : 0;
     L.sb = L.sc = enBC ? (L.isG ? 1 : 9) : 0;
+    // (The level must be known at compile time wherever this is inlined into a latency-bound prologue: under a branch on a level
+    // known only at run time the compiler kept B and C in a private array -- a store under a run-time index and a load back, through
+    // scratch memory, in front of the first column loads of every upper-level launch and of the down-sweep's root.  Those callers
+    // fix the level (twisted_helper, prod_bind, the root of bt_downsweep_kernel).  Selects instead of the branch remove the array as well, but cost small_lm_kernel,
+    // whose three call sites do take the level at run time, 22 more spilled registers.)
     if (s.level0) {
         L.A = !enA ? L.Z : L.isU ? s.Ho + cu : L.isG ? s.rhs0 : s.Hd + cs;
         L.B = L.C = L.A;
@@ -550,8 +586,18 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //   nbar       (HELP) barriers every wave of the workgroup executes = node steps of the forward sweep
 //   L0         1 / 0: the level is known at compile time (level-0 instantiation: no composition loads, fewer registers); -1: runtime
 //   PF / nbst  (HELP, upper levels) the next node's columns come composed from the helper: nbst[2][H_NB], buffer t & 1 for step t
+// Keeps every dword of the arguments a kernel reads late -- the struct part, fetched by scalar loads the compiler issues at entry --
+// live up to this point.  Without it the register allocator hands a dword that one path never reads (the factor pointers on a
+// sweeping wave, say) to a temporary of the prologue, and the write to it has to wait for the whole scalar load: the round trip the
+// preloaded arguments were meant to take out of the way of the first column loads.
+__device__ __forceinline__ void late_args_live(const LevelDst& d, const int* flags, const Gate& g) {
+    asm volatile("" ::"s"(d.fac), "s"(d.inv), "s"(d.Dsep), "s"(d.rsep), "s"(d.cL), "s"(d.cR), "s"(d.cgL), "s"(d.cgR), "s"(d.fill), "s"(d.x),
+                 "s"(flags), "s"(g.ctl), "s"(g.epoch));
+}
+
+// returns false when the run-ahead gate was closed (nothing written, no barrier executed)
 template <bool REV, bool HELP = false, int L0 = -1, bool PF = false>
-__device__ __forceinline__ void twisted_sweep(const LevelSrc& src_in, const LevelDst& dst, int n, int p, int first, int count,
+__device__ __forceinline__ bool twisted_sweep(const LevelSrc& src_in, const LevelDst& dst, int n, int p, int first, int count,
                                               bool has_spike, int merge_t, int last_next, bool has_right, int* flags, int lane,
                                               double* __restrict__ lds, const double* __restrict__ TnB,
                                               double* __restrict__ accB, const Gate& gate, int nbar = 0,
@@ -609,7 +655,8 @@ __device__ __forceinline__ void twisted_sweep(const LevelSrc& src_in, const Leve
     // valid memory and writes nothing), so the gate word's round trip overlaps them instead of preceding them.  The epoch
     // cannot change while this kernel runs (it is bumped by the previous iteration's trial kernel), so both wavefronts of
     // the workgroup take the same branch.
-    if (gate_closed(gate)) return;
+    if constexpr (L0 == 0 && PF) late_args_live(dst, flags, gate);      // (PF: bt_eliminate_tw_kernel<0>, whose leading arguments are preloaded)
+    if (gate_closed(gate)) return false;
 #ifdef ISLAM_PROBE
     if (prb) islam_probe_buf[pbase] = t_entry;
 #endif
@@ -778,6 +825,7 @@ __device__ __forceinline__ void twisted_sweep(const LevelSrc& src_in, const Leve
     }
     PROBE_WALL(prb, pbase + 29);
     if (bad && lane == 0) atomicOr(flags, 1);
+    return true;
 }
 
 // The helper wavefront (see H_STAGE): after barrier t it owns the stages of node t of both sweeps.  Per node:
@@ -831,7 +879,7 @@ __device__ __forceinline__ bool pf_next(const HelpSeg& g, int t, int& k) {
 
 template <int NSEG, bool PF = false>
 __device__ __forceinline__ void twisted_helper(const LevelDst& dst, const HelpSeg (&sg)[NSEG], int nbar, int lane,
-                                               const LevelSrc* src = nullptr) {
+                                               const LevelSrc* src = nullptr, const Gate& gate = Gate{nullptr, 0.0}) {
     int pa, pb;
     pair_of(lane, pa, pb);
     if (lane >= 45) { pa = lane - 45; pb = 9; }
@@ -878,9 +926,15 @@ __device__ __forceinline__ void twisted_helper(const LevelDst& dst, const HelpSe
     [[maybe_unused]] const bool hprb = PF && lane == 0 && sg[0].p == 1 && src && src->Pprev > 500;      // probe build: level 1, segment 1
     PROBE_WALL(hprb, 500);
     if constexpr (PF) {
-        LSA = lane_source(*src, lane);
-        LSB = lane_source_rev(*src, lane);
+        LevelSrc up = *src;
+        up.level0 = 0;                                       // (PF: an upper level -- see lane_source)
+        LSA = lane_source(up, lane);
+        LSB = lane_source_rev(up, lane);
         pf_issue(0);
+    }
+    // (as in twisted_sweep: the gate word's round trip overlaps the first loads; a cancelled launch has read valid memory)
+    if (gate_closed(gate)) return;
+    if constexpr (PF) {
 #pragma unroll
         for (int q = 0; q < NSEG; ++q) {                     // the column lanes without a column of their own read: 0.0
             if (sg[q].on && lane >= 28 && lane < 28 + XS) {
@@ -984,19 +1038,21 @@ __device__ __forceinline__ void eliminate_twisted(const LevelSrc& src, const Lev
 // The two sweeps of segment p with helper hand-off (HELP): role 0 = forward, 1 = reverse.  nbar = barriers every wave of the
 // workgroup executes (>= this segment's forward step count; more when a workgroup holds segments of different lengths).
 template <int L0, bool PF = false>
-__device__ __forceinline__ void sweep_with_helper(const LevelSrc& src, const LevelDst& dst, int n, int m, int p, int* flags, int role, int lane,
+__device__ __forceinline__ bool sweep_with_helper(const LevelSrc& src, const LevelDst& dst, int n, int m, int p, int* flags, int role, int lane,
                                                   double* __restrict__ lds_seg, const Gate& gate, int nbar) {
     const SegGeom g = seg_geom(n, m, p);
     double* ldsA = lds_seg;
     double* ldsB = lds_seg + H_SWEEP;
     double* accB = lds_seg + 2 * H_SWEEP;
     if (role == 0)
-        twisted_sweep<false, true, L0, PF>(src, dst, n, p, g.c0, g.nA, g.has_left, g.tw ? g.h - 1 : -1, g.has_right ? g.sR : -1, g.has_right,
+        return twisted_sweep<false, true, L0, PF>(src, dst, n, p, g.c0, g.nA, g.has_left, g.tw ? g.h - 1 : -1, g.has_right ? g.sR : -1, g.has_right,
                                            flags, lane, ldsA, ldsB + 2 * H_STAGE, accB, gate, nbar, lds_seg + LDS_TW4);
-    else if (g.tw)
-        twisted_sweep<true, true, L0, PF>(src, dst, n, p, g.c0 + g.cnt - 1, g.nB, g.has_right, -1, -1, g.has_right, flags, lane, ldsB, nullptr,
+    if (g.tw)
+        return twisted_sweep<true, true, L0, PF>(src, dst, n, p, g.c0 + g.cnt - 1, g.nB, g.has_right, -1, -1, g.has_right, flags, lane, ldsB, nullptr,
                                           accB, gate, nbar, lds_seg + LDS_TW4 + 2 * H_NB);
-    else if (!gate_closed(gate)) { for (int t = 0; t < nbar; ++t) lds_barrier(); }
+    if (gate_closed(gate)) return false;
+    for (int t = 0; t < nbar; ++t) lds_barrier();
+    return true;
 }
 
 // three wavefronts per segment: 0 = forward sweep, 1 = reverse sweep, 2 = the helper of both
@@ -1006,19 +1062,24 @@ __device__ __forceinline__ void eliminate_twisted3(const LevelSrc& src, const Le
     const SegGeom g = seg_geom(n, m, p);
     constexpr bool PF = L0 == 0;                     // upper levels: the helper fetches and composes the next node's columns
     if (wave < 2) sweep_with_helper<L0, PF>(src, dst, n, m, p, flags, wave, lane, lds_wg, gate, g.nA);
-    else if (!gate_closed(gate)) {
+    else {
         const HelpSeg sg[1] = {help_seg(g, p, lds_wg, n)};
-        twisted_helper<1, PF>(dst, sg, g.nA, lane, &src);
+        twisted_helper<1, PF>(dst, sg, g.nA, lane, &src, gate);
     }
 }
 
 // (level 0 of the N = 5001 tree has 834 segments, all of which must be resident at once: 3 waves per SIMD, i.e. <= 168 VGPRs)
+// Flat leading arguments (TW_FLAT_DWORDS of them, preloaded into SGPRs): all that the first column loads of a wave depend on.  On an
+// upper level (L0 = 0) the sources are the previous level's products, bound from pbase + offsets (prod_bind); the struct arguments
+// behind them -- src (level 0 only), dst, flags, gate -- are first read when those loads are in flight.
+constexpr int TW_FLAT_DWORDS = PROD_DWORDS + 5;
 template <int L0>
-__global__ __launch_bounds__(192, L0 ? 3 : 2) void bt_eliminate_tw_kernel(LevelSrc src, LevelDst dst, int n, int m, int* flags, int seg0,
-                                                                          int nseg, Gate gate) {
+__global__ __launch_bounds__(192, L0 ? 3 : 2) void bt_eliminate_tw_kernel(ISLAM_PROD_PARAMS, int n, int m, int seg0, int nseg, int Pprev,
+                                                                          LevelSrc src, LevelDst dst, int* flags, Gate gate) {
     __shared__ __attribute__((aligned(16))) double lds[L0 ? LDS_TW4 : LDS_TW4_PF];
     const int p = xcd_index(blockIdx.x, nseg);
     if (p < 0) return;
+    if constexpr (L0 == 0) prod_bind(src, ISLAM_PROD_ARGS, Pprev);
     eliminate_twisted3<L0>(src, dst, n, m, p + seg0, flags, threadIdx.x >> 6, threadIdx.x & 63, lds, gate);
 }
 
@@ -1385,16 +1446,18 @@ __global__ __launch_bounds__(128, 2) void bt_downsweep_kernel(SweepArgs a, int* 
     // the three LDS stages (forward sweep: nodes 0, 1 in its two stages; reverse sweep: node 2).  Root published 8.8 -> 7.x us
     // into the launch (scripts/probe_sweep.py).
     const bool root3 = a.root_twisted && a.root_n == 3;
+    LevelSrc root_src = a.root_src;
+    root_src.level0 = 0;                            // (the root always reads the products of the level below it -- see lane_source)
     if (threadIdx.x >= 64) {
-        if (b == 0 && root3) sweep_with_helper<0>(a.root_src, a.root_dst, 3, 3, 0, flags, 1, lane, lds, Gate{nullptr, 0.0}, 2);
-        else if (b == 0 && a.root_twisted) eliminate_twisted(a.root_src, a.root_dst, a.root_n, a.root_n, 0, flags, 1, lane, lds);
+        if (b == 0 && root3) sweep_with_helper<0>(root_src, a.root_dst, 3, 3, 0, flags, 1, lane, lds, Gate{nullptr, 0.0}, 2);
+        else if (b == 0 && a.root_twisted) eliminate_twisted(root_src, a.root_dst, a.root_n, a.root_n, 0, flags, 1, lane, lds);
         return;
     }
     if (b == 0) {                                   // root: eliminate + solve
         PROBE_WALL(lane == 0, 300);
-        if (root3) sweep_with_helper<0>(a.root_src, a.root_dst, 3, 3, 0, flags, 0, lane, lds, Gate{nullptr, 0.0}, 2);
-        else if (a.root_twisted) eliminate_twisted(a.root_src, a.root_dst, a.root_n, a.root_n, 0, flags, 0, lane, lds);
-        else eliminate_segment(a.root_src, a.root_dst, a.root_n, a.root_n, 0, flags, lane, lds);
+        if (root3) sweep_with_helper<0>(root_src, a.root_dst, 3, 3, 0, flags, 0, lane, lds, Gate{nullptr, 0.0}, 2);
+        else if (a.root_twisted) eliminate_twisted(root_src, a.root_dst, a.root_n, a.root_n, 0, flags, 0, lane, lds);
+        else eliminate_segment(root_src, a.root_dst, a.root_n, a.root_n, 0, flags, lane, lds);
         PROBE_WALL(lane == 0, 301);
         double xn[9], xL[9];
 #pragma unroll
