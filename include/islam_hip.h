@@ -578,6 +578,55 @@ size_t islam_imu_extrinsic_rot_solve_scratch_bytes(int rows);
 int islam_imu_extrinsic_rot_solve(const void* rot_imu, const void* rot_cam, const double* weight, int rows, double delta, int rounds,
                                   double* out_q, double* out_eig, double* out_res, void* scratch, int dtype, void* stream);
 
+/* Camera-IMU time offset and gyro bias from relative rotations, in closed form (the rotation-only temporal
+ * calibration that Kalibr uses as its initial guess, the td state of VINS-Mono restricted to rotations).  The reference has no
+ * counterpart: it trusts the dataset's synchronisation (rgb2imu_sync), and so does every other solve of this header.  Conventions are
+ * islam_imu_gyro_bias_solve's.  Row i is a frame:
+ *   DR_i     rot_imu, the pre-integrated relative rotation over the samples [seg[i], seg[i+1]), that is over IMU time [t_i, t_{i+1}],
+ *   DRref_i  rot_ref, the relative rotation of the body the caller trusts (VO or PVGO, conjugated into the body frame) between the two
+ *            images STAMPED t_i and t_{i+1}.
+ * If an image stamped t was really taken at t + td on the IMU's clock, DRref_i is the body's rotation over [t_i + td, t_{i+1} + td].
+ * Let ws_i and we_i be the body angular rates at the two boundaries of row i; under the integrator's own zero-order hold these are the
+ * samples that START there, gyro[seg[i]] and gyro[seg[i+1]] (rate_start, rate_end).  Then, for 0 <= td <= the duration of those
+ * samples, exactly
+ *   DR_i(td) = Exp(-ws_i td) DR_i Exp(we_i td) = DR_i Exp(u_i td + O(td^2)),   u_i = we_i - DR_i^T ws_i,
+ * and with DR(b) = DR Exp(J_phig b) of islam_imu_preint_bias_jac that gives three equations per row, linear in x = [dbg(3); td]:
+ *   e_i = Log(DR_i^T DRref_i) = J_phig,i dbg + u_i td,
+ *   x = argmin sum_i w_i rho_i | e_i - Y_i x |^2,   Y_i = [J_phig,i | u_i] (3x4),   H = sum_i w_i rho_i Y_i^T Y_i (4x4).
+ * td is observable only where the angular rate changes: with a constant rate about a fixed axis u_i = 0 and the pivot of td fails.
+ * solve_bias = 0: td alone is solved, dbg is exactly 0.0, the bias rows and columns of out_H are exact zeros and jac is not read (it
+ * may be NULL).  The unknowns that are solved (4 or 1) are compacted and solved by Cholesky under islam_imu_gyro_bias_solve's pivot
+ * rule (a pivot <= 1e-13 of its diagonal entry fails; for the 1x1 case a pivot <= 0 fails).
+ * rho_i is a Huber weight on the residual: 1 in round 0; with delta > 0 and rounds = K >= 1 the solve is repeated K more times with
+ * rho_i = min(1, delta / |e_i - Y_i x^|) under the previous round's x^.  delta = 0: one round, rounds is ignored.
+ * weight: (rows) float64 or NULL = all ones.  A row counts with a finite non-zero weight and finite e_i, u_i, J_phig,i.  A row of weight
+ * exactly zero takes no part, whatever its data holds, and is not counted; a row with a negative or non-finite weight, or non-finite
+ * data behind a non-zero weight, is excluded and counted.
+ * jac (rows, 9, 6) float64; rot_imu, rot_ref (rows, 4) xyzw, rate_start, rate_end (rows, 3) in the I/O dtype; float64 arithmetic for
+ * either dtype.  out_x: 4 doubles [dbg, td]; out_H: 16 doubles or NULL, symmetric; out_res: rows doubles or NULL: | e_i - Y_i x | under
+ * the final x, NaN for a row with non-finite data, computed for rows of weight zero too (all device memory).  The gyro bias to subtract
+ * from the samples becomes bias + dbg; td is added to the camera's stamps.
+ * Returns the number of excluded rows (>= 0); ISLAM_ENOTPD on a pivot failure in any round or when no row takes part (rows = 0
+ * included): out_x and out_res are then zeros, out_H is still written; ISLAM_EARG, before any device work, for a NULL rot_imu / rot_ref
+ * / rate_start / rate_end with rows > 0, a NULL out_x or scratch, a NULL jac with solve_bias = 1 (and rows > 0), rows < 0, a bad dtype,
+ * solve_bias not 0 or 1, a negative or non-finite delta, rounds < 0.  The sums run in an order that depends on rows alone, without
+ * atomics: a second call gives the same bits, and a row of weight zero gives the bits of the same call with other data behind that
+ * weight.  Cost: (K + 1) x (2 or 3) launches plus one for out_res.  The call synchronises the stream (one 8-byte read-back).
+ * scratch: islam_imu_time_offset_solve_scratch_bytes(rows) bytes (120 B per row). */
+size_t islam_imu_time_offset_solve_scratch_bytes(int rows);
+int islam_imu_time_offset_solve(const double* jac /*(rows,9,6) or NULL iff solve_bias==0*/, const void* rot_imu, const void* rot_ref,
+                                const void* rate_start, const void* rate_end /*(rows,3), I/O dtype*/, const double* weight /*rows or NULL*/,
+                                int rows, int solve_bias, double delta, int rounds, double* out_x /*4: dbg, td*/,
+                                double* out_H /*16 or NULL*/, double* out_res /*rows or NULL*/, void* scratch, int dtype, void* stream);
+
+/* The pre-integrated rotations of a window moved by tau, without re-integrating: out_rot_i = Exp(-ws_i tau) (x) rot_i (x) Exp(we_i tau),
+ * renormalised (exact under the zero-order hold for 0 <= tau <= the duration of the two boundary samples).  It is to the time offset
+ * what islam_imu_bias_correct is to the bias: a Gauss-Newton round of islam_imu_time_offset_solve starts from a sub-sample offset.
+ * rot (rows, 4) xyzw, rate_start, rate_end (rows, 3), out_rot (rows, 4) in the I/O dtype (float64 arithmetic); out_rot may alias rot;
+ * tau: a host double.  ISLAM_EARG for rows < 0, a bad dtype, a non-finite tau, a NULL pointer with rows > 0.  Does not synchronise. */
+int islam_imu_time_shift(const void* rot, const void* rate_start, const void* rate_end, int rows, double tau, void* out_rot, int dtype,
+                         void* stream);
+
 /* ---------------------------------------------------------------- PVGO (pose-velocity graph optimisation) */
 
 typedef struct {

@@ -127,6 +127,9 @@ SIGNATURES = {
     'islam_imu_lever_scale_solve': (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_double] + [c_void_p] * 4 + [c_int, c_void_p]),
     'islam_imu_extrinsic_rot_solve_scratch_bytes': (c_size_t, [c_int]),
     'islam_imu_extrinsic_rot_solve': (c_int, [c_void_p] * 3 + [c_int, c_double, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
+    'islam_imu_time_offset_solve_scratch_bytes': (c_size_t, [c_int]),
+    'islam_imu_time_offset_solve': (c_int, [c_void_p] * 6 + [c_int, c_int, c_double, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
+    'islam_imu_time_shift': (c_int, [c_void_p] * 3 + [c_int, c_double, c_void_p, c_int, c_void_p]),
     'islam_pvgo_default_params': (None, [ctypes.POINTER(PvgoParams)]),
     'islam_pvgo_workspace_bytes': (c_size_t, [c_int]),
     'islam_pvgo_run_chain': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), c_void_p, c_size_t,

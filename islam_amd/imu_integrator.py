@@ -210,6 +210,62 @@ class IMUModule:
             res = torch.cat((self.gyro_bias.to(torch.float64) + dbg, H.reshape(9))).cpu()
         return res[0:3].contiguous(), res[3:12].view(3, 3).contiguous()
 
+    def estimate_time_offset(self, st, end, ref_rots, weight=None, solve_bias=True, delta=None, rounds=4, gn_rounds=3):
+        """Time offset between the camera's and the IMU's clock, with the gyro bias, of frames [st, end] from relative rotations the
+        caller trusts (``ref_rots``: (end - st, 4) xyzw quaternions or an SO3 of the BODY, frame i -> i + 1: VO or PVGO-optimised,
+        conjugated by the mount's rotation), by Gauss-Newton rounds of a closed-form solve (islam_imu_time_offset_solve).  Sign: an image
+        stamped t was taken at t + T on the IMU's clock, so ADD T to the camera's stamps, i.e. move ``rgb2imu_sync`` by k samples (the
+        rest, 0 <= T - k dt < dt, is below the sample spacing).  The state is T = k dt + tau (k whole samples, 0 <= tau < dt), starting
+        at 0, and the module's ``gyro_bias``.  Each of the 1 + ``gn_rounds`` rounds slices the frames with their boundaries moved by k
+        samples, subtracts the current bias (whatever ``optm_bias`` says; the denoiser is not run), integrates the motion rows with
+        gravity 0 and their bias Jacobians, takes the boundary rates from the slice (the sample that starts at each boundary), moves the
+        rotations by tau (islam_imu_time_shift), solves for (dbg, td) and updates bias += dbg, T += td.  The Jacobian of the un-shifted
+        increment is used for the shifted one (the difference is first order in tau and only slows convergence).  Rows whose moved
+        window or end sample leaves the stored stream get weight zero.  ``weight``: (end - st) per frame; ``solve_bias=False`` keeps the
+        bias; ``delta`` / ``rounds``: the Huber rounds of every solve.  With ``gn_rounds > 0`` the sample spacing of the slice must be
+        uniform to 1e-6 relative (``ValueError`` otherwise); ``gn_rounds = 0`` is the single linearised solve and accepts any spacing (k
+        then counts samples of the slice's first spacing).  The first linearisation has to point the right way: roughly |T| below a
+        quarter period of the motion.  Returns (T in seconds (a 0-d tensor), ``gyro_bias`` + the sum of dbg (3), the 4x4 normal matrix H
+        of the last round in the order dbg, td, the residuals (end - st) of the last round, k), on the CPU in float64 (k: an int).  A
+        constant angular rate leaves T undetermined: IslamHipError (ISLAM_ENOTPD).  The module is not changed."""
+        sync = np.asarray(self.rgb2imu_sync[st:end + 1], dtype=np.int64)
+        n, S = len(sync) - 1, int(self.dts.shape[0])
+        ref = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
+        ref = ref.detach().to(self.dtype).to(self.device)
+        w0 = np.ones(n) if weight is None else np.asarray(weight, dtype=np.float64).reshape(n).copy()
+        slice_dts = self.dts[int(sync[0]):int(sync[-1]) + 1, 0].to(torch.float64).cpu().numpy()
+        dt = float(slice_dts[0])
+        if gn_rounds > 0 and not np.all(np.abs(slice_dts - dt) <= 1e-6 * abs(dt)):
+            raise ValueError('estimate_time_offset: the sample spacing of frames [%d, %d] is not uniform to 1e-6 (%.9g .. %.9g); only '
+                             'gn_rounds=0, the single linearised solve, accepts that' % (st, end, slice_dts.min(), slice_dts.max()))
+        T, k, tau = 0.0, 0, 0.0
+        bias = self.gyro_bias.detach().to(torch.float64).cpu().numpy().copy()
+        with torch.no_grad():
+            for _ in range(1 + int(gn_rounds)):
+                moved = sync + k
+                inside = (moved[:-1] >= 0) & (moved[1:] <= S - 1)          # the window and the sample that starts at its end are stored
+                segc = np.clip(moved, 0, S - 1)
+                b0, b1 = int(segc[0]), int(segc[-1]) + 1
+                seg_host = np.ascontiguousarray(segc - b0, dtype=np.int64)
+                seg = torch.from_numpy(seg_host).to(self.device)
+                w = torch.from_numpy(np.where(inside, w0, 0.0)).to(self.device)
+                dts = self.dts[b0:b1, 0].contiguous()
+                gyros = (self.gyros[b0:b1] - torch.from_numpy(bias).to(self.dtype).to(self.device).view(1, 3)).contiguous()
+                accels = self.accels[b0:b1].contiguous()
+                init = torch.zeros(10, dtype=self.dtype, device=self.device)
+                init[6] = 1.0
+                _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
+                jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
+                rate_start, rate_end = gyros[seg[:-1]].contiguous(), gyros[seg[1:]].contiguous()
+                rot = ops.imu_time_shift(rot, rate_start, rate_end, tau)
+                dbg, td, H, res, _ = ops.imu_time_offset_solve(jac, rot, ref, rate_start, rate_end, w, solve_bias, delta, rounds)
+                host = torch.cat((dbg, td.reshape(1), H.reshape(16), res)).cpu()
+                bias = bias + host[0:3].numpy()
+                T = T + float(host[3])
+                k = int(np.floor(T / dt))
+                tau = T - k * dt
+        return (torch.tensor(T, dtype=torch.float64), torch.from_numpy(bias), host[4:20].view(4, 4).contiguous(), host[20:20 + n].contiguous(), k)
+
     def _alignment_rows(self, st, end, use_cov):
         """The rows of the closed-form alignment solves over frames [st, end], on the device: (n, durations (n), dvel, dpos (n, 3) in the
         start-body frame of their frame, bias Jacobians (n, 9, 6), motion-mode covariances (n, 9, 9) or None).  The motion rows are
@@ -310,8 +366,8 @@ class IMUModule:
         A gyro-bias error perturbs q at first order (it rotates every DR_i), so the order of calls is: this first, then
         ``estimate_gyro_bias`` on the camera rotations conjugated by q (q (x) cam_i (x) q^-1), then ``estimate_lever_arm``, which gives
         the lever arm (the translation of T_IL) with gravity, accelerometer bias and velocities (``estimate_gravity_accel_bias`` is the
-        solve for a known lever arm).  Out of scope: the joint refinement of rotation and gyro bias and the time offset between the two
-        sensors.  The module is not changed."""
+        solve for a known lever arm).  Out of scope: the joint refinement of rotation and gyro bias; the time offset between the two
+        sensors is ``estimate_time_offset``'s.  The module is not changed."""
         b0 = int(self.rgb2imu_sync[st])
         b1 = int(self.rgb2imu_sync[end]) + 1
         seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)

@@ -1008,6 +1008,54 @@ def imu_extrinsic_rot_solve(rot_imu, rot_cam, weight=None, delta=None, rounds=4)
     return out[0:4], out[4:8], out[8:], int(rc)
 
 
+def imu_time_offset_solve(jac, rot_imu, rot_ref, rate_start, rate_end, weight=None, solve_bias=True, delta=None, rounds=4):
+    """Camera-IMU time offset td and a further gyro bias dbg from relative rotations, in closed form (islam_imu_time_offset_solve;
+    definition in include/islam_hip.h): x = [dbg; td] minimises sum_i w_i rho_i |Log(rot_imu_i^T rot_ref_i) - J_phig,i dbg - u_i td|^2
+    with u_i = rate_end_i - rot_imu_i^T rate_start_i.  jac (rows, 9, 6) float64 (None is allowed with solve_bias=False, which solves td
+    alone); rot_imu, rot_ref (rows, 4) xyzw, rate_start, rate_end (rows, 3): the gyro samples that start at the two boundaries of every
+    row, float32 or float64 (rot_imu's dtype); weight (rows) or None; delta: the Huber threshold on the residual in rad, None = no
+    reweighting; rounds: the reweighted solves after the first one.  Returns (dbg (3), td (), H (4, 4), res (rows), number of excluded
+    rows), float64 on the device; an image stamped t was taken at t + td on the IMU's clock.  Raises IslamHipError (code ISLAM_ENOTPD)
+    when H is singular (a constant angular rate leaves td undetermined).  Synchronises the stream."""
+    require_cuda(jac, rot_imu, rot_ref, rate_start, rate_end, weight)
+    rows = int(rot_imu.shape[0])
+    dtype = rot_imu.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = rot_imu.device
+    if solve_bias and jac is None:
+        raise ValueError('jac: the (rows, 9, 6) bias Jacobians are required with solve_bias=True')
+    with torch.no_grad():
+        jac = _imu_arg(jac, torch.float64, (rows, 9, 6), 'jac')
+        rot_imu, rot_ref = _imu_arg(rot_imu, dtype, (rows, 4), 'rot_imu'), _imu_arg(rot_ref, dtype, (rows, 4), 'rot_ref')
+        rate_start, rate_end = _imu_arg(rate_start, dtype, (rows, 3), 'rate_start'), _imu_arg(rate_end, dtype, (rows, 3), 'rate_end')
+        weight = _imu_arg(weight, torch.float64, (rows,), 'weight')
+        out = torch.empty(20 + rows, dtype=torch.float64, device=dev)
+        scratch = torch.empty(lib().islam_imu_time_offset_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
+        rc = lib().islam_imu_time_offset_solve(ptr(jac), ptr(rot_imu), ptr(rot_ref), ptr(rate_start), ptr(rate_end), ptr(weight), rows,
+                                               int(bool(solve_bias)), c_double(0.0 if delta is None else float(delta)), int(rounds),
+                                               ptr(out[0:4]), ptr(out[4:20]), ptr(out[20:]), ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return out[0:3], out[3], out[4:20].view(4, 4), out[20:], int(rc)
+
+
+def imu_time_shift(rot, rate_start, rate_end, tau):
+    """Pre-integrated rotations of a window moved by ``tau`` seconds without re-integrating (islam_imu_time_shift):
+    Exp(-rate_start_i tau) (x) rot_i (x) Exp(rate_end_i tau), renormalised.  rot (rows, 4) xyzw, rate_start, rate_end (rows, 3) in float32
+    or float64 (rot's dtype).  Returns the new rot.  Forward values only."""
+    require_cuda(rot, rate_start, rate_end)
+    rows = int(rot.shape[0])
+    dtype = rot.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    with torch.no_grad():
+        rot = _imu_arg(rot, dtype, (rows, 4), 'rot')
+        rate_start, rate_end = _imu_arg(rate_start, dtype, (rows, 3), 'rate_start'), _imu_arg(rate_end, dtype, (rows, 3), 'rate_end')
+        out = torch.empty_like(rot)
+        check(lib().islam_imu_time_shift(ptr(rot), ptr(rate_start), ptr(rate_end), rows, c_double(float(tau)), ptr(out), code,
+                                         stream_ptr(rot.device)))
+    return out
+
+
 # --------------------------------------------------------------------------- PVGO
 def pvgo_default_params(loss_weight=(1, 1, 1, 1), radius=1e4, seg_len=(0, 0)):
     p = _lib.PvgoParams()
