@@ -871,6 +871,28 @@ int islam_pvgo_assemble_dense(const double* Hd, const double* Ho, const double* 
 int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
                                      const double* c_vo, const int64_t* edges, const int64_t* node_ptr,
                                      const int64_t* node_adj, double w0, int N, int E, double* A, double* rhs, void* stream);
+/* Dense fp64 Cholesky A = L L^T of the general-topology normal matrix and the solve with its factor (csrc/dense_chol.hip, DESIGN.md
+ * section 3.17): the O(n^3) step of the loop-closure LM on the matrix cores (v_mfma_f64_16x16x4_f64), n = 9N, any n >= 1.
+ * Storage contract.  A: n x n row-major device doubles.  islam_dense_chol_factor READS the strict upper triangle of A and diag (n) --
+ * the diagonal of the matrix, A's own diagonal is not read -- and WRITES L into the lower triangle and the diagonal of A.  The strict
+ * upper triangle and diag are never written: factoring the same linearisation again with another diag (the LM's growing damping)
+ * needs no restoration, and no second n x n array exists at any time.  islam_dense_chol_solve reads the lower triangle and the
+ * diagonal of that array only and solves L y = b, L^T x = y for one right-hand side; x may alias b (neither may overlap the workspace).
+ * Pivot rule.  The pivot of column c is d = a_cc - sum_k l_ck^2 as computed; d <= 0 or d not finite fails.  info (one device int,
+ * rewritten by every factor call) receives c + 1 for the first failing column (LAPACK's potrf numbering), 0 when none fails.  After a
+ * failed pivot every remaining launch still runs and terminates (no loop depends on data); the lower triangle then holds unspecified
+ * values (NaN among them), and a solve on it returns unspecified values without faulting.
+ * Determinism.  No atomics, every sum in an order fixed by n: the same inputs give the same bits on every call.
+ * Both calls only enqueue on `stream`: no read-back, no synchronisation.  With nb = ceil(n / 64): the factor is 3 nb - 1 launches (per
+ * block column the MFMA update of all rows below, the diagonal block in one workgroup, the panel by substitution; the last column
+ * has no panel), the solve 2 nb launches and one device-to-device copy of b.
+ * workspace: islam_dense_chol_workspace_bytes(n) bytes (two vectors of n doubles; 0 for n < 1), shared by both calls.
+ * ISLAM_EARG before any HIP call for n < 1, a NULL pointer or a workspace that is too small. */
+size_t islam_dense_chol_workspace_bytes(int n);
+int islam_dense_chol_factor(double* A, const double* diag, int n, void* workspace, size_t workspace_bytes,
+                            int* info /* device */, void* stream);
+int islam_dense_chol_solve(const double* L, int n, const double* b, double* x /* may alias b */,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* vo_loss forward/backward (pvgo.py:67-78 with PyPose's left-tangent gradient convention).
  * fwd: e (E,6) = Log(P^-1 Xi^-1 Xj); trans_loss, rot_loss (E).  bwd: grad_poses (E,7), last column 0. */
 int islam_pvgo_vo_loss_fwd(const double* nodes, const int64_t* edges, const double* poses, int E,

@@ -1270,6 +1270,43 @@ def pvgo_retract(nodes, vels, dx, sign=1.0):
     return no, vo
 
 
+def dense_chol_workspace(n, device):
+    nbytes = lib().islam_dense_chol_workspace_bytes(n)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _dense_chol_args(A, vec, what):
+    require_cuda(A, vec)
+    n = A.shape[0]
+    if not (A.dim() == 2 and A.shape[1] == n and A.dtype == torch.float64 and A.is_contiguous()):
+        raise ValueError('dense_chol: A must be a contiguous square float64 matrix')
+    if not (vec.shape == (n,) and vec.dtype == torch.float64 and vec.is_contiguous()):
+        raise ValueError('dense_chol: %s must be a contiguous float64 vector of A.shape[0] entries' % what)
+    return n
+
+
+def dense_chol_factor(A, diag, ws=None):
+    """islam_dense_chol_factor: A = L L^T in place.  Reads the strict upper triangle of A and ``diag``; writes L into the lower triangle and
+    the diagonal of A; the strict upper triangle and ``diag`` stay as they are.  Enqueue only.  Returns info, a device int32 tensor
+    (1): 0, or the 1-based index of the first pivot that was <= 0 or not finite."""
+    n = _dense_chol_args(A, diag, 'diag')
+    if ws is None:
+        ws = dense_chol_workspace(n, A.device)
+    info = torch.empty((1,), dtype=torch.int32, device=A.device)
+    check(lib().islam_dense_chol_factor(ptr(A), ptr(diag), n, ptr(ws[0]), c_size_t(ws[1]), ptr(info), stream_ptr(A.device)))
+    return info
+
+
+def dense_chol_solve(A, b, ws=None):
+    """islam_dense_chol_solve: x with L L^T x = b, L = the lower triangle and diagonal of A as dense_chol_factor left them.  Enqueue only."""
+    n = _dense_chol_args(A, b, 'b')
+    if ws is None:
+        ws = dense_chol_workspace(n, A.device)
+    x = torch.empty_like(b)
+    check(lib().islam_dense_chol_solve(ptr(A), n, ptr(b), ptr(x), ptr(ws[0]), c_size_t(ws[1]), stream_ptr(A.device)))
+    return x
+
+
 def pvgo_align(nodes, vels, target7):
     N = nodes.shape[0]
     no, vo = torch.empty_like(nodes), torch.empty_like(vels)

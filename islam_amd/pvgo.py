@@ -96,6 +96,10 @@ def pvgo_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvel
                          anchor)
 
 
+_GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
+_GENERAL_SOLVER_ERROR = "general_solver must be 'auto', 'dense', 'dense_hip' or 'band_pcg'"
+
+
 def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels,
              device='cuda:0', radius=1e4, loss_weight=(1, 1, 1, 1), reproj=None, target='vo', seg_len=(0, 0),
              return_info=False, general_solver='auto', marginals=False, kernel=None):
@@ -112,6 +116,8 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
             raise NotImplementedError('run_pvgo: marginals under a robust kernel (kernel with marginals=True) are not implemented')
     N = len(init_nodes)
     chain = _is_canonical_chain(links, N)
+    if not chain and general_solver not in _GENERAL_SOLVERS:
+        raise ValueError(_GENERAL_SOLVER_ERROR)
     if marginals and not chain:
         raise UnsupportedGraphError('marginals=True serves canonical chains (links[k] = [k, k+1]) only; covariances of '
                                     'loop-closure graphs are not implemented')
@@ -136,14 +142,14 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
         if how == 'band_pcg':
             nodes, vels, res = run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp,
                                                kernel=robust)
-        elif how == 'dense':
+        elif how in ('dense', 'dense_hip'):      # 'dense_hip': the same LM with the project's own Cholesky (csrc/dense_chol.hip)
             if N > 12000:
                 raise UnsupportedGraphError('dense general-topology path is sized for N <= 12000 nodes, (9N)^2 doubles (got %d '
                                             'nodes, %d off-band edges; general_solver="band_pcg" has no such limit)' % (N, k_off))
             nodes, vels, res = run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp,
-                                            kernel=robust)
+                                            kernel=robust, solver='hip' if how == 'dense_hip' else 'torch')
         else:
-            raise ValueError("general_solver must be 'auto', 'dense' or 'band_pcg'")
+            raise ValueError(_GENERAL_SOLVER_ERROR)
 
     if target == 'vo':
         vo = vo_motions if isinstance(vo_motions, torch.Tensor) else torch.as_tensor(vo_motions)

@@ -8,7 +8,8 @@ normal matrix PyPose factorises, but never forms the Jacobian PyPose multiplies 
     arbitrary edges, islam_pvgo_linearize for the IMU factors, which always couple consecutive nodes);
   * A = J^T W J (9N x 9N) and b = -J^T W r assembled block by block on the device (islam_pvgo_assemble_dense):
     O(E) work instead of the 2*rows*cols^2 dense product;
-  * fp64 POTRF / POTRS from rocSOLVER (the only O(N^3) piece; its trailing updates are fp64 MFMA GEMMs);
+  * fp64 POTRF / POTRS from rocSOLVER (the only O(N^3) piece; its trailing updates are fp64 MFMA GEMMs), or with solver='hip' the
+    project's own blocked Cholesky on v_mfma_f64_16x16x4_f64 (csrc/dense_chol.hip, DESIGN.md section 3.17), in place;
   * retraction, trial residuals and the trust-region term (J D)^T (2R + J D) from the per-factor blocks.
 Sized by the dense matrix: (9N)^2 doubles (N = 5001: 16 GB of the 288 GB).
 
@@ -130,11 +131,15 @@ class _ReprojTerms:
 
 
 def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
-                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None):
+                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, solver='torch'):
     """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None.
+    solver: 'torch' (torch.linalg.cholesky_ex / cholesky_solve: a second (9N)^2 matrix per trial) or 'hip' (islam_dense_chol_factor /
+    _solve, csrc/dense_chol.hip: the damped diagonal goes in as a vector and the factor lands in A's lower triangle, no second matrix).
     Returns (nodes, vels, info dict)."""
     N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
     _check_kernel(kernel, reproj)
+    if solver not in ('torch', 'hip'):
+        raise ValueError("solver must be 'torch' or 'hip'")
     if E != M:
         raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, M))
     dev = nodes.device
@@ -147,6 +152,7 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
     b = torch.empty((9 * N,), dtype=torch.float64, device=dev)
     ctl = LMControl(radius=radius, max_steps=max_steps, patience=patience, decreasing=decreasing)
     trials = 0
+    cws = ops.dense_chol_workspace(9 * N, dev) if solver == 'hip' else None
     while ctl.continual:
         vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
         rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
@@ -168,15 +174,22 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
         d = A.diagonal().clamp(vmin, vmax).clone()                    # A.diagonal().clamp_(min, max)
         while True:
             d = d + d * ctl.damping                                   # cumulative, like A.diagonal().add_(...)
-            A.diagonal().copy_(d)
-            L, info = torch.linalg.cholesky_ex(A)
             trials += 1
-            if int(info) != 0 or not bool(torch.isfinite(L.diagonal()).all()):
+            if solver == 'hip':               # upper triangle of A + d -> L in A's lower triangle; one small read-back
+                info = ops.dense_chol_factor(A, d, cws)
+                D = ops.dense_chol_solve(A, b, cws).view(N, 9)
+                failed = torch.stack([info[0] != 0, ~torch.isfinite(D).all()]).any().item()
+            else:
+                A.diagonal().copy_(d)
+                L, info = torch.linalg.cholesky_ex(A)
+                failed = int(info) != 0 or not bool(torch.isfinite(L.diagonal()).all())
+            if failed:
                 print('Linear solver failed. Breaking optimization step...')
                 ctl.solver_failed()
                 break
-            D = torch.cholesky_solve(b[:, None], L)[:, 0].view(N, 9).contiguous()
-            del L
+            if solver != 'hip':
+                D = torch.cholesky_solve(b[:, None], L)[:, 0].view(N, 9).contiguous()
+                del L
             nt, vt = ops.pvgo_retract(nodes, vels, D, 1.0)
             vo_t, lin_t = _linearize(nt, vt, edges, poses, drots, dtrans, dvels, dts, dummy)
             st, qt = _trial_loss(vo_t, lin_t, kernel), _quality_term(vo, lin, edges, dts, D, c_vo, c_imu)
