@@ -1,5 +1,5 @@
-// The 3x3 helpers and the small Cholesky solve of the closed-form IMU alignment solves (DESIGN.md sections 3.13 and 3.15:
-// imu_align.hip, imu_lever.hip).  Device code only; every function is inlined or instantiated where it is used.
+// The 3x3 helpers and the small Cholesky solve of the closed-form IMU solves (DESIGN.md sections 3.13 and 3.15: imu_align.hip at 6 and
+// at 10 unknowns; section 3.16: imu_time_offset.hip).  Device code only; every function is inlined or instantiated where it is used.
 #pragma once
 #include <hip/hip_runtime.h>
 

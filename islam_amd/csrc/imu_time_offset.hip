@@ -22,22 +22,19 @@
 #include <cmath>
 
 #include "imu_mat.h"
+#include "imu_normal.h"
 #include "imu_terms.h"
 #include "lie_dev.h"
 
 using namespace islam;
 using namespace islam::imat;
+using namespace islam::normal;
 using namespace islam::tsum;
 
 namespace {
 
-constexpr int NX = 4;                 // the layout of the unknowns: dbg (0..2) | td (3)
-constexpr int NH = NX * (NX + 1) / 2; // the upper triangle of H by rows
-constexpr int NT = NH + NX + 1;       // per-row terms: H upper triangle (10) | c (4) | excluded (1)
+constexpr int NX = 4;                 // the layout of the unknowns: dbg (0..2) | td (3); NT<NX> terms per row (imu_normal.h): 10 | 4 | 1
 constexpr int XHAT = 4;               // the last round's x in the scratch head (doubles 4 .. 7), behind the two status words
-
-// where H_ab (a <= b) sits among the terms
-__device__ __forceinline__ int tri(int a, int b) { return a * NX - a * (a - 1) / 2 + (b - a); }
 
 // Y = [J_phig | u | e] of row s; jac NULL: the columns of J are exact zeros.  True iff every entry is finite.
 template <class T>
@@ -96,9 +93,9 @@ __global__ __launch_bounds__(BLOCK) void td_row_kernel(const double* __restrict_
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= rows) return;
     const size_t s = (size_t)i;
-    double t[NT];
+    double t[NT<NX>];
 #pragma unroll
-    for (int q = 0; q < NT; ++q) t[q] = 0.0;
+    for (int q = 0; q < NT<NX>; ++q) t[q] = 0.0;
     const double w = weight ? weight[s] : 1.0;
     if (w != 0.0) {                                       // a row of weight zero takes no part, whatever its data holds
         double Y[3][NX + 1];
@@ -106,29 +103,14 @@ __global__ __launch_bounds__(BLOCK) void td_row_kernel(const double* __restrict_
         ok = ok && isfinite(w) && w > 0.0;
         double wr = w;
         if (xhat && ok) wr = w * fmin(1.0, delta / residual_norm(Y, xhat));   // (a residual of 0: delta / 0 = inf, rho = 1)
-        int idx = 0;
-        double tf = 0.0;
-#pragma unroll
-        for (int a = 0; a < NX; ++a)
-#pragma unroll
-            for (int b = a; b < NX + 1; ++b) {
-                const double v = wr * (Y[0][a] * Y[0][b] + Y[1][a] * Y[1][b] + Y[2][a] * Y[2][b]);
-                tf += fabs(v);
-                if (b < NX) t[idx++] = v; else t[NH + a] = v;
-            }
-        ok = ok && isfinite(tf);
-        if (!ok) {                                        // excluded and counted
-#pragma unroll
-            for (int q = 0; q < NT - 1; ++q) t[q] = 0.0;
-            t[NT - 1] = 1.0;
-        }
+        normal_terms<NX>(Y, wr, ok, t);
     }
 #pragma unroll
-    for (int q = 0; q < NT; ++q) terms[(size_t)q * rows + s] = t[q];
+    for (int q = 0; q < NT<NX>; ++q) terms[(size_t)q * rows + s] = t[q];
 }
 
 __global__ __launch_bounds__(BLOCK) void td_partial_kernel(const double* __restrict__ terms, int rows, int nblocks, double* __restrict__ partial) {
-    partial_sum<NT>(terms, rows, nblocks, partial);
+    partial_sum<NT<NX>>(terms, rows, nblocks, partial);
 }
 
 // the compacted system of the n unknowns that are solved, row stride NX
@@ -142,31 +124,23 @@ struct SolveLds {
 __global__ __launch_bounds__(BLOCK) void td_solve_kernel(const double* __restrict__ src, int ld, int count, int solve_bias, int first, int last,
                                                          int* __restrict__ status, double* __restrict__ xhat, double* __restrict__ out_x,
                                                          double* __restrict__ out_H) {
-    __shared__ double wsum[4 * NT], tot[NT];
+    __shared__ double wsum[4 * NT<NX>], tot[NT<NX>];
     __shared__ SolveLds S;
-    block_sum<NT>(src, (size_t)ld, 0, (size_t)count, wsum, tot);
+    block_sum<NT<NX>>(src, (size_t)ld, 0, (size_t)count, wsum, tot);
     if (threadIdx.x != 0) return;
-    int n = 0;
-    for (int a = 0; a < NX; ++a)
-        if (a == NX - 1 || solve_bias != 0) S.at[n++] = a;
-    for (int a = 0; a < n; ++a) {
-        for (int b = a; b < n; ++b) S.H[NX * a + b] = S.H[NX * b + a] = tot[tri(S.at[a], S.at[b])];
-        S.c[a] = tot[NH + S.at[a]];
-        S.x[a] = 0.0;
-    }
+    int at[NX];
+    const int n = list_solved<NX>([=](int a) { return a == NX - 1 || solve_bias != 0; }, S.at, at);
+    gather_solved<NX>(tot, at, S.H, S.c);
     bool pd = chol_solve<NX>(S.H, S.c, n, S.L, S.x);
     if (!first && status[0] != 0) pd = false;
     for (int a = 0; a < NX; ++a) xhat[a] = 0.0;
-    if (pd)
-        for (int a = 0; a < n; ++a) xhat[S.at[a]] = S.x[a];
+    if (pd) scatter_solved<NX>(S.x, at, n, xhat);
     if (last) {
         for (int a = 0; a < NX; ++a) out_x[a] = xhat[a];
-        if (out_H)
-            for (int a = 0; a < NX; ++a)
-                for (int b = a; b < NX; ++b) out_H[NX * a + b] = out_H[NX * b + a] = tot[tri(a, b)];
+        if (out_H) write_full_H<NX>(tot, out_H);
     }
     status[0] = pd ? 0 : 1;
-    status[1] = (int)tot[NT - 1];
+    status[1] = (int)tot[NT<NX> - 1];
 }
 
 // One lane per row: |e_i - Y_i x| under the final x, NaN for a row with non-finite data; zeros when the solve failed.
@@ -206,7 +180,7 @@ template <class T>
 int run(const double* jac, const T* rot_imu, const T* rot_ref, const T* rate_start, const T* rate_end, const double* weight, int rows,
         int solve_bias, double delta, int rounds, double* out_x, double* out_H, double* out_res, void* scratch, hipStream_t s) {
     const int K = delta > 0.0 ? rounds : 0;
-    const Scratch sc(scratch, NT, rows);
+    const Scratch sc(scratch, NT<NX>, rows);
     double* xhat = sc.head + XHAT;
     const dim3 grid((rows + BLOCK - 1) / BLOCK);
     for (int r = 0; r <= K; ++r) {
@@ -233,7 +207,7 @@ int run(const double* jac, const T* rot_imu, const T* rot_ref, const T* rate_sta
 extern "C" {
 
 size_t islam_imu_time_offset_solve_scratch_bytes(int rows) {
-    return Scratch::bytes(NT, rows > 0 ? rows : 0);
+    return Scratch::bytes(NT<NX>, rows > 0 ? rows : 0);
 }
 
 int islam_imu_time_offset_solve(const double* jac, const void* rot_imu, const void* rot_ref, const void* rate_start, const void* rate_end,

@@ -923,6 +923,32 @@ def imu_gyro_bias_solve(jac, rot_imu, rot_ref, weight=None):
     return out[0:3], out[3:12].view(3, 3), int(rc)
 
 
+def _imu_alignment_solve(symbol, nx, names, rot, pos, dts, dvel, dpos, jac, cov, weight, flags, gravity_norm):
+    """What imu_gravity_bias_solve (nx = 6) and imu_lever_scale_solve (nx = 10) share: the arguments made contiguous, the outputs and the
+    scratch, the call of `symbol` (flags: the ints between rows and gravity_norm), the return code.  Returns (x (nx), H (nx, nx),
+    vel (rows + 1, 3), number of excluded pairs)."""
+    require_cuda(rot, pos, dts, dvel, dpos, jac, cov, weight)
+    rows = int(dts.shape[0])
+    dtype = dts.dtype
+    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    dev = dts.device
+    xh = nx + nx * nx
+    with torch.no_grad():
+        io = [_imu_arg(t, dtype, shape, name) for t, shape, name in (
+            (rot, (rows + 1, 4), names[0]), (pos, (rows + 1, 3), names[1]), (dts, (rows,), 'dts'), (dvel, (rows, 3), 'dvel'),
+            (dpos, (rows, 3), 'dpos'))]
+        f64 = [_imu_arg(t, torch.float64, shape, name) for t, shape, name in (
+            (jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight'))]
+        out = torch.empty(xh + 3 * (rows + 1), dtype=torch.float64, device=dev)
+        scratch = torch.empty(getattr(lib(), symbol + '_scratch_bytes')(rows), dtype=torch.uint8, device=dev)
+        rc = getattr(lib(), symbol)(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows, *flags,
+                                    c_double(0.0 if gravity_norm is None else float(gravity_norm)), ptr(out[0:nx]), ptr(out[nx:xh]),
+                                    ptr(out[xh:]), ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return out[0:nx], out[nx:xh].view(nx, nx), out[xh:].view(rows + 1, 3), int(rc)
+
+
 def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None, weight=None, gravity_norm=None):
     """Gravity, accelerometer bias and velocities from pre-integrated increments and trusted body poses, in closed form
     (islam_imu_gravity_bias_solve; definition in include/islam_hip.h).  rot_ref (rows + 1, 4) xyzw, pos_ref (rows + 1, 3): world
@@ -931,25 +957,9 @@ def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None
     float64 motion-mode covariances or None (unit weights), weight (rows - 1) per pair or None, gravity_norm: the known magnitude
     or None.  Returns (g (3), b (3), H (6, 6), vel (rows + 1, 3), number of excluded pairs), float64 on the device.  Raises
     IslamHipError (code ISLAM_ENOTPD) when the normal matrix is singular.  Synchronises the stream."""
-    require_cuda(rot_ref, pos_ref, dts, dvel, dpos, jac, cov, weight)
-    rows = int(dts.shape[0])
-    dtype = dts.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
-    dev = dts.device
-    with torch.no_grad():
-        io = [_imu_arg(t, dtype, shape, name) for t, shape, name in (
-            (rot_ref, (rows + 1, 4), 'rot_ref'), (pos_ref, (rows + 1, 3), 'pos_ref'), (dts, (rows,), 'dts'), (dvel, (rows, 3), 'dvel'),
-            (dpos, (rows, 3), 'dpos'))]
-        f64 = [_imu_arg(t, torch.float64, shape, name) for t, shape, name in (
-            (jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight'))]
-        out = torch.empty(42 + 3 * (rows + 1), dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib().islam_imu_gravity_bias_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
-        rc = lib().islam_imu_gravity_bias_solve(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows,
-                                                c_double(0.0 if gravity_norm is None else float(gravity_norm)), ptr(out[0:6]),
-                                                ptr(out[6:42]), ptr(out[42:]), ptr(scratch), code, stream_ptr(dev))
-    if rc < 0:
-        check(rc)
-    return out[0:3], out[3:6], out[6:42].view(6, 6), out[42:].view(rows + 1, 3), int(rc)
+    x, H, vel, bad = _imu_alignment_solve('islam_imu_gravity_bias_solve', 6, ('rot_ref', 'pos_ref'), rot_ref, pos_ref, dts, dvel, dpos, jac,
+                                          cov, weight, (), gravity_norm)
+    return x[0:3], x[3:6], H, vel, bad
 
 
 def imu_lever_scale_solve(rot_body, pos_cam, dts, dvel, dpos, jac=None, cov=None, weight=None, solve_lever=True, solve_scale=False,
@@ -962,25 +972,9 @@ def imu_lever_scale_solve(rot_body, pos_cam, dts, dvel, dpos, jac=None, cov=None
     b (3), t (3), s (), H (10, 10), vel (rows + 1, 3) of the body, number of excluded pairs), float64 on the device; unknowns that are
     not solved come back as exactly 0 (b, t) and 1 (s), with zero rows and columns in H.  Raises IslamHipError (code ISLAM_ENOTPD)
     when the normal matrix is singular (no rotation between the poses leaves t undetermined).  Synchronises the stream."""
-    require_cuda(rot_body, pos_cam, dts, dvel, dpos, jac, cov, weight)
-    rows = int(dts.shape[0])
-    dtype = dts.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
-    dev = dts.device
-    with torch.no_grad():
-        io = [_imu_arg(t, dtype, shape, name) for t, shape, name in (
-            (rot_body, (rows + 1, 4), 'rot_body'), (pos_cam, (rows + 1, 3), 'pos_cam'), (dts, (rows,), 'dts'), (dvel, (rows, 3), 'dvel'),
-            (dpos, (rows, 3), 'dpos'))]
-        f64 = [_imu_arg(t, torch.float64, shape, name) for t, shape, name in (
-            (jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight'))]
-        out = torch.empty(110 + 3 * (rows + 1), dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib().islam_imu_lever_scale_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
-        rc = lib().islam_imu_lever_scale_solve(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows, int(solve_lever), int(solve_scale),
-                                               c_double(0.0 if gravity_norm is None else float(gravity_norm)), ptr(out[0:10]),
-                                               ptr(out[10:110]), ptr(out[110:]), ptr(scratch), code, stream_ptr(dev))
-    if rc < 0:
-        check(rc)
-    return out[0:3], out[3:6], out[6:9], out[9], out[10:110].view(10, 10), out[110:].view(rows + 1, 3), int(rc)
+    x, H, vel, bad = _imu_alignment_solve('islam_imu_lever_scale_solve', 10, ('rot_body', 'pos_cam'), rot_body, pos_cam, dts, dvel, dpos, jac,
+                                          cov, weight, (int(solve_lever), int(solve_scale)), gravity_norm)
+    return x[0:3], x[3:6], x[6:9], x[9], H, vel, bad
 
 
 def imu_extrinsic_rot_solve(rot_imu, rot_cam, weight=None, delta=None, rounds=4):

@@ -2,7 +2,9 @@
 included) with Jacobians, with Jacobians and covariances, and with the gravity norm, at 5000 frames x 10 samples and at N = 300 007
 rows, beside islam_imu_gyro_bias_solve on the same rows IN THE SAME PROCESS and beside the numpy restatement of
 tests/test_imu_align_gpu.py on one core (one run; at N = 300 007 on the first 20 000 rows, scaled).  HIP events around every call,
-3 warm-up calls, the median of 20.  There is no earlier version to compare against; the expectation to check is "within a small
+3 warm-up calls, the median of 20.  Two builds are compared by running the script once per build, alternating, with ISLAM_HIP_LIB
+naming the other library (profiles/imu_align_bench.json: the solve as a file of its own against the NX = 6 instantiation of
+csrc/imu_align.hip's kernel family); the expectation to check is "within a small
 multiple of the gyro-bias solve at 5000 rows; the large case not serial in one workgroup".  Every case runs in a child process of its
 own under a time limit; a child that fails or runs out of time ends the script.
 

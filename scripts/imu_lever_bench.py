@@ -1,8 +1,9 @@
 """Cost of islam_imu_lever_scale_solve: us per call (float64, Jacobians, velocities asked for, its 8-byte
 read-back and synchronise included) with the lever arm, with lever arm and scale, with covariances and with the gravity norm, at 5000
 frames x 10 samples and at N = 300 007 rows, beside islam_imu_gravity_bias_solve (section 3.13, with Jacobians) on the same rows IN THE
-SAME PROCESS as the yardstick.  HIP events around every call, 3 warm-up calls, the median of 20.  There is no earlier version to compare
-against; the expectation to check is "launch-bound at 5000 rows, about what section 3.13 costs; N = 300 007 moves 2.4 times section
+SAME PROCESS as the yardstick.  HIP events around every call, 3 warm-up calls, the median of 20.  Both solves are csrc/imu_align.hip's
+kernel family, at NX = 10 and NX = 6.  Two builds are compared by running the script once per build, alternating, with ISLAM_HIP_LIB
+naming the other library (profiles/imu_lever_bench.json); the expectation to check is "launch-bound at 5000 rows, about what section 3.13 costs; N = 300 007 moves 2.4 times section
 3.13's terms".  Every case runs in a child process of its own under a time limit; a child that fails or runs out of time ends the
 script.
 

@@ -84,13 +84,19 @@ def test_python_surface_refuses_to_run_without_a_gpu(lib):
 
 
 def test_new_kernels_use_no_private_memory(lib):
-    """No scratch memory and no spilled register in any kernel of csrc/imu_align.hip; the small matrices of the solve live in LDS."""
+    """No scratch memory and no spilled register in any kernel of csrc/imu_align.hip; the small matrices of the solve live in LDS.  Four
+    kernels at two numbers of unknowns (6: this solve, 10: the lever / scale solve), two of the four also at two I/O types."""
     from tests import test_codeobj_cpu as co
-    ks = {n: b for n, b in co._kernels().items() if any(k in n for k in ('ga_pair_kernel', 'ga_partial_kernel', 'ga_solve_kernel', 'ga_vel_kernel'))}
-    assert len(ks) == 6, sorted(ks)        # two templated on the I/O type
-    for n, b in ks.items():
-        assert co._field(b, 'private_segment_fixed_size') == 0 and co._field(b, 'vgpr_spill_count') == 0 and co._field(b, 'sgpr_spill_count') == 0, n
-        assert co._field(b, 'group_segment_fixed_size') <= 4096, n
+    ks = {n: b for n, b in co._kernels().items() if 'ga_' in n}
+    assert len(ks) == 12, sorted(ks)
+    for nx, lds in (('ILi6E', 4096), ('ILi10E', 8192)):
+        for k, count in (('ga_pair_kernel', 2), ('ga_partial_kernel', 1), ('ga_solve_kernel', 1), ('ga_vel_kernel', 2)):
+            assert sum(k + nx in n for n in ks) == count, (k, nx, sorted(ks))
+        for n, b in ks.items():
+            if nx in n:
+                assert co._field(b, 'private_segment_fixed_size') == 0 and co._field(b, 'vgpr_spill_count') == 0, n
+                assert co._field(b, 'sgpr_spill_count') == 0, n
+                assert co._field(b, 'group_segment_fixed_size') <= lds, n
 
 
 # the issue's CPU figures for these streams (worst error of (g, b)): 4e-12, 6e-13, 4e-14, 3e-13 at cond(H) 1e7, 2e4, 45, 41.  The bound

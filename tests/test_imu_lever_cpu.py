@@ -94,9 +94,11 @@ def test_python_surface_refuses_to_run_without_a_gpu(lib):
 
 
 def test_new_kernels_use_no_private_memory(lib):
-    """No scratch memory and no spilled register in any kernel of csrc/imu_lever.hip; the small matrices of the solve live in LDS."""
+    """No scratch memory and no spilled register in the kernels of this solve, csrc/imu_align.hip's at ten unknowns; the small matrices of
+    the solve live in LDS."""
     from tests import test_codeobj_cpu as co
-    ks = {n: b for n, b in co._kernels().items() if any(k in n for k in ('la_pair_kernel', 'la_partial_kernel', 'la_solve_kernel', 'la_vel_kernel'))}
+    ks = {n: b for n, b in co._kernels().items()
+          if any(k + 'ILi10E' in n for k in ('ga_pair_kernel', 'ga_partial_kernel', 'ga_solve_kernel', 'ga_vel_kernel'))}
     assert len(ks) == 6, sorted(ks)        # two templated on the I/O type
     for n, b in ks.items():
         assert co._field(b, 'private_segment_fixed_size') == 0 and co._field(b, 'vgpr_spill_count') == 0 and co._field(b, 'sgpr_spill_count') == 0, n
