@@ -893,6 +893,31 @@ int islam_dense_chol_factor(double* A, const double* diag, int n, void* workspac
                             int* info /* device */, void* stream);
 int islam_dense_chol_solve(const double* L, int n, const double* b, double* x /* may alias b */,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* Inverse of that factor in place and covariance blocks from it (csrc/dense_inverse.hip): Sigma = A^-1 = W^T W
+ * with W = L^-1, for the marginal covariances of loop-closure graphs.
+ * islam_dense_chol_invert_factor.  L: the n x n array islam_dense_chol_factor left (info = 0).  READS and WRITES the lower triangle and the
+ * diagonal only: W = L^-1 replaces L.  The strict upper triangle (the matrix's own entries) is never written and never read as data:
+ * every load whose column can exceed its row is predicated and gives 0 there, so NaN above the diagonal cannot reach the result.
+ * Block columns of 64: one launch inverts every diagonal block (one wave each), then per block column, descending, T = -L_below W_jj
+ * (stored transposed in the workspace) and W_below = tril(W_trailing) T, both on v_mfma_f64_16x16x4_f64.  With nb = ceil(n / 64):
+ * 2 nb - 1 launches.  workspace: islam_dense_chol_inverse_workspace_bytes(n) bytes (one 64 x n panel of doubles; 0 for n < 1).
+ * islam_pvgo_dense_cov_blocks.  W: that inverse, n = 9 N.  node_cov (N,9,9) device: Sigma_kk = sum_{i >= 9k} W[i, 9k:9k+9]^T W[i, 9k:9k+9].
+ * pair_cov (P,9,9) device: Sigma_ab (rows node a, columns node b) for every pairs[p] = (a, b), any a, b in [0, N), a > b and a = b
+ * included; both are sums over the rows i >= 9 max(a, b) of the lower triangle only.  pairs: (P,2) int64 in HOST memory -- it is
+ * validated here and travels to the device as kernel arguments (384 pairs per launch), so nothing is copied and the array may be
+ * freed when the call returns.  P = 0 with pairs = NULL is allowed; node_cov or pair_cov may be NULL to skip it.  anchor >= 0: the six
+ * pose rows / columns of that node are written as zero in every block that touches them (the gauge was fixed there by unit rows in
+ * the matrix); -1: none.  One workgroup per block, rows strided over its threads, reduced in a fixed order; the (b, a) block is the
+ * transpose of the (a, b) block to the bit.  1 + ceil(P / 384) launches.
+ * Both calls only enqueue on `stream`.  Dependencies are launch boundaries: no atomics, no spin-waits, no cooperative launches, no loop
+ * whose trip count depends on data -- on a factor that holds NaN (a failed pivot) every launch still terminates.  Every sum runs in an
+ * order fixed by n (and the pair): a second call gives the same bits.
+ * ISLAM_EARG before any HIP call for n < 1, n not a multiple of 9 (cov_blocks), a NULL matrix, a NULL or too small workspace, an anchor
+ * outside [-1, N), P < 0, P > 0 without pairs, or a pair index outside [0, N). */
+size_t islam_dense_chol_inverse_workspace_bytes(int n);
+int islam_dense_chol_invert_factor(double* L, int n, void* workspace, size_t workspace_bytes, void* stream);
+int islam_pvgo_dense_cov_blocks(const double* W, int n, int anchor, const int64_t* pairs /* host */, int P,
+                                double* node_cov, double* pair_cov, void* stream);
 /* vo_loss forward/backward (pvgo.py:67-78 with PyPose's left-tangent gradient convention).
  * fwd: e (E,6) = Log(P^-1 Xi^-1 Xj); trans_loss, rot_loss (E).  bwd: grad_poses (E,7), last column 0. */
 int islam_pvgo_vo_loss_fwd(const double* nodes, const int64_t* edges, const double* poses, int E,

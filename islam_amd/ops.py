@@ -1274,7 +1274,7 @@ def _dense_chol_args(A, vec, what):
     n = A.shape[0]
     if not (A.dim() == 2 and A.shape[1] == n and A.dtype == torch.float64 and A.is_contiguous()):
         raise ValueError('dense_chol: A must be a contiguous square float64 matrix')
-    if not (vec.shape == (n,) and vec.dtype == torch.float64 and vec.is_contiguous()):
+    if vec is not None and not (vec.shape == (n,) and vec.dtype == torch.float64 and vec.is_contiguous()):
         raise ValueError('dense_chol: %s must be a contiguous float64 vector of A.shape[0] entries' % what)
     return n
 
@@ -1299,6 +1299,42 @@ def dense_chol_solve(A, b, ws=None):
     x = torch.empty_like(b)
     check(lib().islam_dense_chol_solve(ptr(A), n, ptr(b), ptr(x), ptr(ws[0]), c_size_t(ws[1]), stream_ptr(A.device)))
     return x
+
+
+def dense_chol_inverse_workspace(n, device):
+    nbytes = lib().islam_dense_chol_inverse_workspace_bytes(n)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def dense_chol_invert_factor(A, ws=None):
+    """islam_dense_chol_invert_factor: W = L^-1 in place, in the lower triangle and diagonal of A as dense_chol_factor left them; the strict
+    upper triangle is neither written nor read as data.  ws: dense_chol_inverse_workspace(n, device).  Enqueue only.  Returns A."""
+    n = _dense_chol_args(A, None, None)
+    if ws is None:
+        ws = dense_chol_inverse_workspace(n, A.device)
+    check(lib().islam_dense_chol_invert_factor(ptr(A), n, ptr(ws[0]), c_size_t(ws[1]), stream_ptr(A.device)))
+    return A
+
+
+def pvgo_dense_cov_blocks(A, anchor=None, pairs=None):
+    """islam_pvgo_dense_cov_blocks: blocks of Sigma = W^T W from W = the lower triangle and diagonal of A as dense_chol_invert_factor left
+    them (9N x 9N).  pairs: (P,2) integers (sequence, array or tensor; read on the host) or None.  Returns (node_cov (N,9,9), pair_cov
+    (P,9,9)) on A's device; the pose rows / columns of node ``anchor`` (None: no such node) are zero.  Enqueue only."""
+    n =_dense_chol_args(A, None, None)
+    if n % 9 != 0:
+        raise ValueError('pvgo_dense_cov_blocks: A must be 9N x 9N (got n=%d)' % n)
+    N = n // 9
+    if pairs is None:
+        ph = np.zeros((0, 2), dtype=np.int64)
+    else:
+        ph = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+        ph = np.ascontiguousarray(ph.reshape(-1, 2), dtype=np.int64)
+    P = ph.shape[0]
+    node_cov = torch.empty((N, 9, 9), dtype=torch.float64, device=A.device)
+    pair_cov = torch.empty((P, 9, 9), dtype=torch.float64, device=A.device)
+    check(lib().islam_pvgo_dense_cov_blocks(ptr(A), n, -1 if anchor is None else int(anchor), c_void_p(ph.ctypes.data if P else 0), P,
+                                            ptr(node_cov), ptr(pair_cov) if P else c_void_p(0), stream_ptr(A.device)))
+    return node_cov, pair_cov
 
 
 def pvgo_align(nodes, vels, target7):

@@ -96,6 +96,59 @@ def pvgo_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvel
                          anchor)
 
 
+class PvgoGraphMarginals:
+    """Marginal covariances of the poses and velocities of a graph of any topology (float64, on the device).
+
+    node_cov (N,9,9): Sigma_kk; pairs (P,2) int64 and pair_cov (P,9,9): Sigma_ab for every requested pair (a, b), rows node a, columns
+    node b; pose_cov (N,6,6) and vel_cov (N,3,3): the pose and velocity blocks of node_cov.  Per-node ordering, perturbation convention
+    and the meaning of ``anchor`` are those of PvgoMarginals."""
+
+    def __init__(self, node_cov, pairs, pair_cov, anchor):
+        self.node_cov, self.pairs, self.pair_cov, self.anchor = node_cov, pairs, pair_cov, anchor
+
+    @property
+    def pose_cov(self):
+        return self.node_cov[:, :6, :6]
+
+    @property
+    def vel_cov(self):
+        return self.node_cov[:, 6:, 6:]
+
+
+def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, pairs):
+    from .pvgo_dense import marginals_dense
+    N = nodes.shape[0]
+    if N > 12000:
+        raise UnsupportedGraphError('dense covariances are sized for N <= 12000 nodes, (9N)^2 doubles (got %d nodes)' % N)
+    if pairs is None:
+        pairs = edges
+    pairs = pairs.detach().cpu() if isinstance(pairs, torch.Tensor) else torch.as_tensor(np.asarray(pairs))
+    pairs = pairs.to(torch.int64).reshape(-1, 2)
+    node_cov, pair_cov = marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=rp, anchor=anchor,
+                                         pairs=pairs)
+    return PvgoGraphMarginals(node_cov, pairs.to(nodes.device), pair_cov, anchor)
+
+
+def pvgo_marginals_general(nodes, vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight=(1, 1, 1, 1), reproj=None,
+                           anchor=0, pairs=None):
+    """Marginal covariances of the poses and velocities of a graph with arbitrary ``links`` (loop closures; canonical chains too) at the
+    given state: Sigma = A^-1 with A = J^T W J the undamped Gauss-Newton matrix of run_pvgo's graph, the pose DoF of node ``anchor``
+    held fixed (None: no gauge fix).  Dense: the project's Cholesky, the inverse of its factor in place and the requested blocks
+    (islam_amd.pvgo_dense.marginals_dense), N <= 12000.  pairs (P,2): the node pairs whose cross-covariance is wanted; None: ``links``.
+    Returns a PvgoGraphMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
+    t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(torch.float64).contiguous()
+    n64 = t64(nodes)
+    dev = n64.device
+    if dev.type != 'cuda':
+        raise RuntimeError('islam_amd.pvgo_marginals_general runs on the MI355X only; there is no CPU fallback')
+    d = lambda x: t64(x).to(dev)
+    v64, poses, drots, dtrans, dvels = d(vels), d(vo_motions), d(imu_drots), d(imu_dtrans), d(imu_dvels)
+    dts64 = d(dts).reshape(-1)
+    edges = torch.as_tensor(links).to(dev, torch.int64).contiguous()
+    return _graph_marginals_at(n64, v64, edges, poses, drots, dtrans, dvels, dts64, loss_weight, _reproj_struct(reproj, loss_weight, dev),
+                               anchor, pairs)
+
+
 _GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
 _GENERAL_SOLVER_ERROR = "general_solver must be 'auto', 'dense', 'dense_hip' or 'band_pcg'"
 
@@ -118,9 +171,10 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     chain = _is_canonical_chain(links, N)
     if not chain and general_solver not in _GENERAL_SOLVERS:
         raise ValueError(_GENERAL_SOLVER_ERROR)
-    if marginals and not chain:
+    if marginals and not chain and general_solver != 'dense_hip':
         raise UnsupportedGraphError('marginals=True serves canonical chains (links[k] = [k, k+1]) only; covariances of '
-                                    'loop-closure graphs are not implemented')
+                                    "loop-closure graphs are not implemented (except with general_solver='dense_hip': the dense "
+                                    'selected inverse, pvgo_marginals_general)')
     rp = _reproj_struct(reproj, loss_weight, dev)
     out_dtype = pp._plain(init_nodes).dtype if isinstance(init_nodes, torch.Tensor) else torch.get_default_dtype()
     t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(dev, torch.float64).contiguous()
@@ -168,7 +222,9 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
 
     an, av = ops.pvgo_align(nodes, vels, target0)
     marg = None
-    if marginals:        # at the aligned fp64 state the caller receives; stream-ordered, its status rides on the host copy below
+    if marginals and not chain:     # general_solver='dense_hip': dense selected inverse at the aligned fp64 state, anchor 0, pairs = links
+        marg = _graph_marginals_at(an, av, edges, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, None)      # (the LM's matrix is gone)
+    elif marginals:      # at the aligned fp64 state the caller receives; stream-ordered, its status rides on the host copy below
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
         marg = _marginals_at(an, av, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, seg_len=seg_len, status=status)
     # ONE device -> host copy for everything the caller reads on the host: aligned poses, velocities and the two loss vectors (their
@@ -177,10 +233,11 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     E = trans_loss.shape[0]
     parts = [an.reshape(-1), av.reshape(-1), trans_loss.detach().to(torch.float64).reshape(-1),
              rot_loss.detach().to(torch.float64).reshape(-1)]
-    if marg is not None:
+    chain_status = marg is not None and chain
+    if chain_status:
         parts.append(marg.status.to(torch.float64))
     host = torch.cat(parts).cpu()
-    if marg is not None and host[-1].item() != 0:
+    if chain_status and host[-1].item() != 0:
         from ._lib import IslamHipError
         raise IslamHipError(int(host[-1].item()), 'run_pvgo(marginals=True): the Gauss-Newton matrix at the solution is not '
                                                   'positive definite')

@@ -130,6 +130,76 @@ class _ReprojTerms:
         return (d * (2 * self.g + (self.S @ d[:, :, None])[:, :, 0])).sum()
 
 
+def _assemble_normal(A, b, vo, lin, edges, nptr, nadj, dts, w, rpt=None, c_vo=None, c_imu=None):
+    """A (9N x 9N, fully written) and b (9N) of one linearisation: the undamped, unclamped Gauss-Newton matrix J^T W J and -J^T W r.
+    w: the four squared loss weights; rpt: _ReprojTerms or None; c_vo, c_imu: robust multipliers or None."""
+    N, E, dev = A.shape[0] // 9, edges.shape[0], A.device
+    Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
+    if rpt is not None:
+        rpt.add_to_chain(Hd, Ho, rhs)
+    if c_vo is not None:
+        check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), ptr(edges), ptr(nptr), ptr(nadj),
+                                                     c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
+    else:
+        check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(edges), ptr(nptr), ptr(nadj),
+                                              c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
+
+
+def gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None):
+    """A = J^T W J (9N x 9N, device, fully written) at (nodes, vels): undamped, unclamped, no gauge fixed -- what run_lm_dense assembles
+    before it damps the diagonal.  The VO factors may sit on any number of edges (the assembly needs no E = N - 1; only the LM's loss
+    does)."""
+    N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
+    if poses.shape[0] != E:
+        raise ValueError('one VO motion per edge: %d motions for %d edges' % (poses.shape[0], E))
+    dev = nodes.device
+    w = [float(x) ** 2 for x in loss_weight[:4]]
+    dummy = torch.zeros((M, 7), dtype=torch.float64, device=dev)
+    dummy[:, 6] = 1.0
+    nptr, nadj = _node_adjacency(edges.cpu().numpy(), N)
+    nptr, nadj = torch.from_numpy(nptr).to(dev), torch.from_numpy(nadj).to(dev)
+    A = torch.empty((9 * N, 9 * N), dtype=torch.float64, device=dev)
+    b = torch.empty((9 * N,), dtype=torch.float64, device=dev)
+    vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
+    rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
+    _assemble_normal(A, b, vo, lin, edges, nptr, nadj, dts, w, rpt)
+    return A
+
+
+def fix_gauge(A, anchor):
+    """Hold the pose of node ``anchor`` fixed in the matrix the dense Cholesky reads: its six pose rows and columns become zero (in the
+    strict upper triangle, which is all the factorisation reads of A) and the diagonal vector, A's own diagonal elsewhere, gets 1 in
+    their places.  Returns that vector.  anchor None: nothing is fixed."""
+    d = A.diagonal().clone()
+    if anchor is not None:
+        i = 9 * int(anchor)
+        A[i:i + 6, :] = 0.0
+        A[:, i:i + 6] = 0.0
+        d[i:i + 6] = 1.0
+    return d
+
+
+def marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None, anchor=0, pairs=None):
+    """Marginal covariances of a general-topology graph at (nodes, vels): Sigma = A^-1, A the undamped, unclamped Gauss-Newton matrix
+    run_lm_dense assembles (with the reprojection factor when ``reproj`` is given), the pose of node ``anchor`` held fixed.  The project's
+    Cholesky factors A in place, the factor is inverted in place (csrc/dense_inverse.hip) and only the
+    requested 9 x 9 blocks of W^T W are formed: one (9N)^2 array in all.
+    In: float64 contiguous device tensors; pairs (P,2) node index pairs or None (the graph's own edges).
+    Returns (node_cov (N,9,9), pair_cov (P,9,9)); raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
+    from ._lib import IslamHipError
+    N = nodes.shape[0]
+    if anchor is not None and not 0 <= int(anchor) < N:
+        raise ValueError('anchor=%r is not a node of a graph of %d nodes' % (anchor, N))
+    A = gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj)
+    d = fix_gauge(A, anchor)
+    info = ops.dense_chol_factor(A, d)
+    bad = int(info.item())                                              # the one read-back
+    if bad != 0:
+        raise IslamHipError(-3, 'marginals_dense: non-positive pivot %d (anchored matrix not positive definite)' % bad)
+    ops.dense_chol_invert_factor(A)
+    return ops.pvgo_dense_cov_blocks(A, anchor, edges if pairs is None else pairs)
+
+
 def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
                  decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, solver='torch'):
     """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None.
@@ -162,15 +232,7 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
         if not ctl.has_loss:
             ctl.set_initial_loss(float(rho) if kernel is not None else float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
         ctl.begin_step()
-        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
-        if rpt is not None:
-            rpt.add_to_chain(Hd, Ho, rhs)
-        if kernel is not None:
-            check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), ptr(edges), ptr(nptr), ptr(nadj),
-                                                         c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
-        else:
-            check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(edges), ptr(nptr), ptr(nadj),
-                                                  c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
+        _assemble_normal(A, b, vo, lin, edges, nptr, nadj, dts, w, rpt, c_vo, c_imu)
         d = A.diagonal().clamp(vmin, vmax).clone()                    # A.diagonal().clamp_(min, max)
         while True:
             d = d + d * ctl.damping                                   # cumulative, like A.diagonal().add_(...)
