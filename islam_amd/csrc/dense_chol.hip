@@ -18,13 +18,7 @@
 // FIRST such column (LAPACK's potrf numbering), 0 when there is none.  After a failure the remaining launches run on whatever the
 // square root of that pivot gave; what they leave in the lower triangle is unspecified.
 //
-// f64 MFMA fragments (16 x 16 x 4, one double per lane per operand; NOT the f32 C/D map), q = lane >> 4, m = lane & 15:
-//   A[m][k = q]   B[k = q][n = m]   C/D register i in [0, 4): row = q + 4 i, col = m
-// The update computes L_i (rows x K) times L_j^T, both row-major with K contiguous, so both operands are "row m, column k" loads.  A lane
-// loads four consecutive doubles (columns k0 + 4 q .. + 3) of its row and MFMA number kk of the chunk takes element kk from both
-// operands: it sums over k0 + 4 q + kk, q = 0..3, and the four MFMAs of a chunk cover its 16 columns (any pairing of k is a valid
-// order for a sum).  The map was checked with exact small-integer data (tests/test_dense_chol_gpu.py does it on every run: an integer
-// matrix whose factor is exact).
+// Fragment map and operand loads of the update (L_i times L_j^T): see csrc/dense_tile.h.
 //
 // Solves (one right-hand side): w = b; for each block j ascending one launch of chol_fwd_kernel: every workgroup solves L_jj y_j = w_j
 // itself (64 x 64, one wave by column substitution), workgroup 0 stores y_j, every workgroup subtracts L_ij y_j from its 64 rows below.
@@ -35,20 +29,15 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "dense_tile.h"
 
 using namespace islam;
+using namespace islam::tile;
 
 namespace {
 
-constexpr int NB = 64;           // block-column width
 constexpr int NW = 512;          // wide block column of the two-level update (a multiple of NB)
-constexpr int TM = 128;          // rows of one update workgroup: 4 waves x 32 rows, each wave all 64 columns
 constexpr int LDP = NB + 1;      // padded LDS row (doubles): lanes that walk down a column hit different banks
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ d4 ld4(const double* p) { return d4{p[0], p[1], p[2], p[3]}; }
 
 // S <- S0 - L_i L_j^T over the columns [kbeg, kend) of L, for rows [cfirst + 128 bx, + 128) x columns [c0, c0 + 64), c0 = cfirst + 64 by,
 // written to the lower triangle (col <= row only).  from_upper: S0 is A (its upper triangle transposed, diag on the diagonal), otherwise
@@ -61,13 +50,12 @@ __global__ __launch_bounds__(256, 2) void chol_update_kernel(double* __restrict_
     const int rw = cfirst + blockIdx.x * TM + wave * 32;  // first row of this wave
     if (rw >= n || rw + 31 < c0) return;                   // past the end, or wholly above the diagonal (wave-uniform; no barrier here)
     const size_t ld = (size_t)n;
-    // rows past the end are clamped: they load valid memory and their results are not stored
     const double* pa[2];
     const double* pb[4];
 #pragma unroll
-    for (int a = 0; a < 2; ++a) pa[a] = A + (size_t)min(rw + 16 * a + m, n - 1) * ld + kbeg + 4 * q;
+    for (int a = 0; a < 2; ++a) pa[a] = operand_row(A, n, rw + 16 * a + m, kbeg, q);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) pb[c] = A + (size_t)min(c0 + 16 * c + m, n - 1) * ld + kbeg + 4 * q;
+    for (int c = 0; c < 4; ++c) pb[c] = operand_row(A, n, c0 + 16 * c + m, kbeg, q);
     d4 acc[2][4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -75,14 +63,7 @@ __global__ __launch_bounds__(256, 2) void chol_update_kernel(double* __restrict_
         for (int c = 0; c < 4; ++c) acc[a][c] = d4{0.0, 0.0, 0.0, 0.0};
     // columns k < kend <= cfirst <= every row read here: the part of the lower triangle the earlier block columns wrote.  kend - kbeg is a
     // multiple of 64, so the 16-column chunks come in pairs: two register sets, each loaded while the other feeds the matrix core.
-    auto chunk = [&](const d4 (&fa)[2], const d4 (&fb)[4]) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a][kk], fb[c][kk], acc[a][c], 0, 0, 0);
-    };
+    const MfmaChunk<4> chunk{acc};
     d4 fa[2], fb[4], ga[2], gb[4];
     const int klen = kend - kbeg;
     if (klen > 0) {
@@ -129,12 +110,6 @@ __global__ __launch_bounds__(256, 2) void chol_update_kernel(double* __restrict_
             }
 }
 
-// v of lane `lane` (wave-uniform) to every lane
-__device__ __forceinline__ double lane_bcast(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
 // One wave: the diagonal block S_jj (lower triangle, jb = min(64, n - c0) rows) -> L_jj, right-looking, row r in the registers of lane r
 // (the entries right of the diagonal are carried along and never used).  info: set to 0 by the first block column, then to the 1-based
 // index of the first failing pivot.
@@ -143,8 +118,7 @@ __global__ __launch_bounds__(64) void chol_diag_kernel(double* __restrict__ A, i
     const int jb = min(NB, n - c0);
     double* p = A + (size_t)(c0 + min(r, jb - 1)) * (size_t)n + c0;
     double x[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) x[k] = (r < jb && k <= r) ? p[k] : 0.0;
+    load_diag_row(p, jb, r, x);
     int bad = 0;
 #pragma unroll
     for (int c = 0; c < NB; ++c) {
@@ -158,9 +132,7 @@ __global__ __launch_bounds__(64) void chol_diag_kernel(double* __restrict__ A, i
             for (int k = c + 1; k < NB; ++k) x[k] -= l * lane_bcast(l, k);       // l_rc l_kc
         }
     }
-#pragma unroll
-    for (int k = 0; k < NB; ++k)
-        if (r < jb && k <= r) p[k] = x[k];
+    store_diag_row(p, jb, r, x);
     if (r == 0) {
         const int prev = c0 == 0 ? 0 : info[0];
         info[0] = prev != 0 ? prev : bad;
@@ -277,11 +249,9 @@ size_t islam_dense_chol_workspace_bytes(int n) {
 }
 
 int islam_dense_chol_factor(double* A, const double* diag, int n, void* workspace, size_t workspace_bytes, int* info, void* stream) {
-    if (n < 1) return fail(ISLAM_EARG, "islam_dense_chol_factor: n=%d", n);
-    if (!A || !diag || !workspace || !info) return fail(ISLAM_EARG, "islam_dense_chol_factor: A / diag / workspace / info is NULL");
-    if (workspace_bytes < islam_dense_chol_workspace_bytes(n))
-        return fail(ISLAM_EARG, "islam_dense_chol_factor: workspace of %zu bytes, n=%d needs %zu", workspace_bytes, n,
-                    islam_dense_chol_workspace_bytes(n));
+    if (int rc = check_workspace_args(__func__, n, !A || !diag || !workspace || !info, "A / diag / workspace / info", workspace_bytes,
+                                      islam_dense_chol_workspace_bytes(n)))
+        return rc;
     hipStream_t s = as_stream(stream);
     for (int C0 = 0; C0 < n; C0 += NW) {                  // wide block column [C0, C0 + we): everything left of it in one launch
         const int we = n - C0 < NW ? n - C0 : NW;
@@ -300,11 +270,9 @@ int islam_dense_chol_factor(double* A, const double* diag, int n, void* workspac
 }
 
 int islam_dense_chol_solve(const double* L, int n, const double* b, double* x, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n < 1) return fail(ISLAM_EARG, "islam_dense_chol_solve: n=%d", n);
-    if (!L || !b || !x || !workspace) return fail(ISLAM_EARG, "islam_dense_chol_solve: L / b / x / workspace is NULL");
-    if (workspace_bytes < islam_dense_chol_workspace_bytes(n))
-        return fail(ISLAM_EARG, "islam_dense_chol_solve: workspace of %zu bytes, n=%d needs %zu", workspace_bytes, n,
-                    islam_dense_chol_workspace_bytes(n));
+    if (int rc = check_workspace_args(__func__, n, !L || !b || !x || !workspace, "L / b / x / workspace", workspace_bytes,
+                                      islam_dense_chol_workspace_bytes(n)))
+        return rc;
     hipStream_t s = as_stream(stream);
     double* w = (double*)workspace;       // the running right-hand side of the forward sweep
     double* y = w + n;                    // its result, and the running right-hand side of the backward sweep

@@ -19,7 +19,7 @@
 // The last block column has nothing below it: 2 ceil(n / 64) - 1 launches.  Dependencies are the launch boundaries: no atomic, no
 // hand-off, no loop whose trip count depends on data; a NaN in the factor propagates and every launch terminates.
 //
-// Fragment map and operand loads: see csrc/dense_chol.hip (A[m][k = q], B[k = q][n = m], C/D register i: row = q + 4 i, col = m).
+// Fragment map and operand loads: see csrc/dense_tile.h (A[m][k = q], B[k = q][n = m], C/D register i: row = q + 4 i, col = m).
 //
 // Covariance blocks: Sigma = A^-1 = W^T W, so block (a, b) is sum_{i >= 9 max(a, b)} W[i, 9a : 9a+9]^T W[i, 9b : 9b+9] over the lower
 // triangle.  One workgroup of 256 per block, rows strided over the threads, 81 sums per thread, then a butterfly over the wave and the
@@ -28,26 +28,15 @@
 
 #include <cstdint>
 
-#include "common.h"
+#include "dense_tile.h"
 
 using namespace islam;
+using namespace islam::tile;
 
 namespace {
 
-constexpr int NB = 64;           // block-column width
-constexpr int TM = 128;          // rows of one update workgroup: 4 waves x 32 rows, each wave all 64 columns
 constexpr int WIDE = 8192;       // rows below a block column above which its update takes 32 columns per workgroup instead of 16
 constexpr int CB = 384;          // pairs per launch of cov_pair_kernel (passed by value: 3 KB of kernel arguments)
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ d4 ld4(const double* p) { return d4{p[0], p[1], p[2], p[3]}; }
-
-// v of lane `lane` (wave-uniform) to every lane
-__device__ __forceinline__ double lane_bcast(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
 
 // One wave: the diagonal block L_jj (lower triangle, jb = min(64, n - c0) rows) -> W_jj = L_jj^-1 in place, row r in the registers of
 // lane r.  Column c, descending: w_cc = 1 / l_cc, w_rc = -(sum_{k = c+1..r} w_rk l_kc) / l_cc; column c of L is still in place in every
@@ -58,8 +47,7 @@ __global__ __launch_bounds__(64) void trinv_diag_kernel(double* __restrict__ A, 
     const int jb = min(NB, n - c0);
     double* p = A + (size_t)(c0 + min(r, jb - 1)) * (size_t)n + c0;
     double x[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) x[k] = (r < jb && k <= r) ? p[k] : 0.0;
+    load_diag_row(p, jb, r, x);
 #pragma unroll
     for (int c = NB - 1; c >= 0; --c) {
         if (c < jb) {                                      // (uniform)
@@ -70,9 +58,7 @@ __global__ __launch_bounds__(64) void trinv_diag_kernel(double* __restrict__ A, 
             x[c] = r == c ? 1.0 / d : r > c ? -s / d : 0.0;
         }
     }
-#pragma unroll
-    for (int k = 0; k < NB; ++k)
-        if (r < jb && k <= r) p[k] = x[k];
+    store_diag_row(p, jb, r, x);
 }
 
 // T = -L[c1:, c0:c1] W_jj for the rows r >= c1 = c0 + 64 (the block is full there), computed transposed on the matrix cores as it is stored:
@@ -87,9 +73,9 @@ __global__ __launch_bounds__(256) void trinv_panel_kernel(const double* __restri
     if (r0 >= below) return;                               // (wave-uniform; no barrier in this kernel)
     const size_t ld = (size_t)n;
     const double* pw = A + (size_t)c0 * ld + c0;           // W_jj
-    const double* pl[2];                                   // rows past the end are clamped: they load valid memory and are not stored
+    const double* pl[2];
 #pragma unroll
-    for (int b = 0; b < 2; ++b) pl[b] = A + (size_t)min(c1 + r0 + 16 * b + m, n - 1) * ld + c0 + 4 * q;
+    for (int b = 0; b < 2; ++b) pl[b] = operand_row(A, n, c1 + r0 + 16 * b + m, c0, q);
     d4 acc[4][2];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -135,15 +121,14 @@ __global__ __launch_bounds__(256, 2) void trinv_update_kernel(double* __restrict
     const int rw = c1 + blockIdx.x * TM + wave * 32;      // first row of this wave
     if (rw >= n) return;                                   // (wave-uniform; no barrier in this kernel)
     const size_t ld = (size_t)n;
-    // rows past the end are clamped: they load valid memory and their results are not stored
-    int ra[2];
+    int ra[2];                                             // (clamped like the operand rows: what the straddling chunks compare k with)
     const double* pa[2];
     const double* pb[NC];
     const int cg = blockIdx.y * NC;                        // first 16-column group of this workgroup
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
         ra[a] = min(rw + 16 * a + m, n - 1);
-        pa[a] = A + (size_t)ra[a] * ld + c1 + 4 * q;
+        pa[a] = operand_row(A, n, ra[a], c1, q);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) pb[c] = Tt + (size_t)(16 * (cg + c) + m) * ldt + 4 * q;
@@ -152,17 +137,10 @@ __global__ __launch_bounds__(256, 2) void trinv_update_kernel(double* __restrict
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int c = 0; c < NC; ++c) acc[a][c] = d4{0.0, 0.0, 0.0, 0.0};
-    auto chunk = [&](const d4 (&fa)[2], const d4 (&fb)[NC]) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int c = 0; c < NC; ++c) acc[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a][kk], fb[c][kk], acc[a][c], 0, 0, 0);
-    };
     // columns k in [c1, rw): below every row of this wave, so wholly inside the lower triangle; rw - c1 is a multiple of 32.  A ring of D
     // register sets: the loads of chunk i + D go out when chunk i has fed the matrix core, so D - 1 chunks of MFMAs cover the latency of a
     // load (a chunk is only 8 NC MFMAs here).
+    const MfmaChunk<NC> chunk{acc};
     d4 fa[D][2], fb[D][NC];
     const int nch = (rw - c1) / 16;
     auto load = [&](int d, int i) {                        // chunk min(i, nch - 1): the last sets reload the last chunk instead of reading past rw
@@ -275,11 +253,8 @@ size_t islam_dense_chol_inverse_workspace_bytes(int n) {
 }
 
 int islam_dense_chol_invert_factor(double* L, int n, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n < 1) return fail(ISLAM_EARG, "islam_dense_chol_invert_factor: n=%d", n);
-    if (!L || !workspace) return fail(ISLAM_EARG, "islam_dense_chol_invert_factor: L / workspace is NULL");
-    if (workspace_bytes < islam_dense_chol_inverse_workspace_bytes(n))
-        return fail(ISLAM_EARG, "islam_dense_chol_invert_factor: workspace of %zu bytes, n=%d needs %zu", workspace_bytes, n,
-                    islam_dense_chol_inverse_workspace_bytes(n));
+    if (int rc = check_workspace_args(__func__, n, !L || !workspace, "L / workspace", workspace_bytes, islam_dense_chol_inverse_workspace_bytes(n)))
+        return rc;
     hipStream_t s = as_stream(stream);
     double* Tt = (double*)workspace;
     const int nb = (n + NB - 1) / NB;

@@ -1320,7 +1320,7 @@ def pvgo_dense_cov_blocks(A, anchor=None, pairs=None):
     """islam_pvgo_dense_cov_blocks: blocks of Sigma = W^T W from W = the lower triangle and diagonal of A as dense_chol_invert_factor left
     them (9N x 9N).  pairs: (P,2) integers (sequence, array or tensor; read on the host) or None.  Returns (node_cov (N,9,9), pair_cov
     (P,9,9)) on A's device; the pose rows / columns of node ``anchor`` (None: no such node) are zero.  Enqueue only."""
-    n =_dense_chol_args(A, None, None)
+    n = _dense_chol_args(A, None, None)
     if n % 9 != 0:
         raise ValueError('pvgo_dense_cov_blocks: A must be 9N x 9N (got n=%d)' % n)
     N = n // 9

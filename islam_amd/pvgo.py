@@ -42,16 +42,19 @@ def _reproj_struct(reproj, loss_weight, dev):
                                   getattr(reproj, 'compat_first_motion', True))
 
 
-class PvgoMarginals:
-    """Marginal covariances of a chain's poses and velocities (float64, on the device; DESIGN.md section 3.9).
+_DENSE_MAX_NODES = 12000      # the dense general-topology path holds (9N)^2 doubles
 
-    node_cov (N,9,9): Sigma_kk in the solver's per-node ordering [rho, phi, v] -- the pose part is the left perturbation
-    X <- Exp([rho, phi]) X; cross (N-1,9,9): Sigma_k,k+1 (rows node k, columns node k+1); pose_cov (N,6,6) and vel_cov (N,3,3):
-    the pose and velocity blocks of node_cov.  The gauge is fixed at node ``anchor`` (its pose rows / columns are zero)."""
 
-    def __init__(self, node_cov, cross, anchor, status=None):
-        self.node_cov, self.cross, self.anchor = node_cov, cross, anchor
-        self.status = status             # (run_pvgo: device int32 ISLAM_OK / ISLAM_ENOTPD of the stream-ordered call)
+def _graph_inputs(dev, *xs):
+    """Every x as a contiguous float64 tensor on ``dev`` (a LieTensor as its plain tensor)."""
+    return [pp._plain(torch.as_tensor(x)).detach().to(dev, torch.float64).contiguous() for x in xs]
+
+
+class _Marginals:
+    """node_cov (N,9,9), the gauge ``anchor``, and the pose (N,6,6) / velocity (N,3,3) blocks of node_cov as views."""
+
+    def __init__(self, node_cov, anchor):
+        self.node_cov, self.anchor = node_cov, anchor
 
     @property
     def pose_cov(self):
@@ -60,6 +63,19 @@ class PvgoMarginals:
     @property
     def vel_cov(self):
         return self.node_cov[:, 6:, 6:]
+
+
+class PvgoMarginals(_Marginals):
+    """Marginal covariances of a chain's poses and velocities (float64, on the device; DESIGN.md section 3.9).
+
+    node_cov (N,9,9): Sigma_kk in the solver's per-node ordering [rho, phi, v] -- the pose part is the left perturbation
+    X <- Exp([rho, phi]) X; cross (N-1,9,9): Sigma_k,k+1 (rows node k, columns node k+1); pose_cov (N,6,6) and vel_cov (N,3,3):
+    the pose and velocity blocks of node_cov.  The gauge is fixed at node ``anchor`` (its pose rows / columns are zero)."""
+
+    def __init__(self, node_cov, cross, anchor, status=None):
+        super().__init__(node_cov, anchor)
+        self.cross = cross
+        self.status = status             # (run_pvgo: device int32 ISLAM_OK / ISLAM_ENOTPD of the stream-ordered call)
 
 
 def _marginals_at(nodes, vels, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, seg_len=(0, 0), status=None):
@@ -81,22 +97,18 @@ def pvgo_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvel
     state: Sigma = A^-1 with A = J^T W J the undamped Gauss-Newton matrix of run_pvgo's graph (the PyPose-compatible Jacobians,
     the reprojection factor when ``reproj`` is given), the pose DoF of node ``anchor`` held fixed (None: no gauge fix).
     Returns a PvgoMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
-    t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(torch.float64).contiguous()
-    n64 = t64(nodes)
-    dev = n64.device
+    dev = pp._plain(torch.as_tensor(nodes)).device
     if dev.type != 'cuda':
         raise RuntimeError('islam_amd.pvgo_marginals runs on the MI355X only; there is no CPU fallback')
-    d = lambda x: t64(x).to(dev)
-    v64, poses, drots, dtrans, dvels = d(vels), d(vo_motions), d(imu_drots), d(imu_dtrans), d(imu_dvels)
-    dts64 = d(dts).reshape(-1)
+    n64, v64, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, nodes, vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     N = n64.shape[0]
     if poses.shape[0] != N - 1:
         raise UnsupportedGraphError('pvgo_marginals serves canonical chains: %d VO motions for %d nodes' % (poses.shape[0], N))
-    return _marginals_at(n64, v64, poses, drots, dtrans, dvels, dts64, loss_weight, _reproj_struct(reproj, loss_weight, dev),
+    return _marginals_at(n64, v64, poses, drots, dtrans, dvels, dts64.reshape(-1), loss_weight, _reproj_struct(reproj, loss_weight, dev),
                          anchor)
 
 
-class PvgoGraphMarginals:
+class PvgoGraphMarginals(_Marginals):
     """Marginal covariances of the poses and velocities of a graph of any topology (float64, on the device).
 
     node_cov (N,9,9): Sigma_kk; pairs (P,2) int64 and pair_cov (P,9,9): Sigma_ab for every requested pair (a, b), rows node a, columns
@@ -104,22 +116,15 @@ class PvgoGraphMarginals:
     and the meaning of ``anchor`` are those of PvgoMarginals."""
 
     def __init__(self, node_cov, pairs, pair_cov, anchor):
-        self.node_cov, self.pairs, self.pair_cov, self.anchor = node_cov, pairs, pair_cov, anchor
-
-    @property
-    def pose_cov(self):
-        return self.node_cov[:, :6, :6]
-
-    @property
-    def vel_cov(self):
-        return self.node_cov[:, 6:, 6:]
+        super().__init__(node_cov, anchor)
+        self.pairs, self.pair_cov = pairs, pair_cov
 
 
 def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, pairs):
     from .pvgo_dense import marginals_dense
     N = nodes.shape[0]
-    if N > 12000:
-        raise UnsupportedGraphError('dense covariances are sized for N <= 12000 nodes, (9N)^2 doubles (got %d nodes)' % N)
+    if N > _DENSE_MAX_NODES:
+        raise UnsupportedGraphError('dense covariances are sized for N <= %d nodes, (9N)^2 doubles (got %d nodes)' % (_DENSE_MAX_NODES, N))
     if pairs is None:
         pairs = edges
     pairs = pairs.detach().cpu() if isinstance(pairs, torch.Tensor) else torch.as_tensor(np.asarray(pairs))
@@ -136,21 +141,16 @@ def pvgo_marginals_general(nodes, vels, vo_motions, links, dts, imu_drots, imu_d
     held fixed (None: no gauge fix).  Dense: the project's Cholesky, the inverse of its factor in place and the requested blocks
     (islam_amd.pvgo_dense.marginals_dense), N <= 12000.  pairs (P,2): the node pairs whose cross-covariance is wanted; None: ``links``.
     Returns a PvgoGraphMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
-    t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(torch.float64).contiguous()
-    n64 = t64(nodes)
-    dev = n64.device
+    dev = pp._plain(torch.as_tensor(nodes)).device
     if dev.type != 'cuda':
         raise RuntimeError('islam_amd.pvgo_marginals_general runs on the MI355X only; there is no CPU fallback')
-    d = lambda x: t64(x).to(dev)
-    v64, poses, drots, dtrans, dvels = d(vels), d(vo_motions), d(imu_drots), d(imu_dtrans), d(imu_dvels)
-    dts64 = d(dts).reshape(-1)
+    n64, v64, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, nodes, vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     edges = torch.as_tensor(links).to(dev, torch.int64).contiguous()
-    return _graph_marginals_at(n64, v64, edges, poses, drots, dtrans, dvels, dts64, loss_weight, _reproj_struct(reproj, loss_weight, dev),
+    return _graph_marginals_at(n64, v64, edges, poses, drots, dtrans, dvels, dts64.reshape(-1), loss_weight, _reproj_struct(reproj, loss_weight, dev),
                                anchor, pairs)
 
 
 _GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
-_GENERAL_SOLVER_ERROR = "general_solver must be 'auto', 'dense', 'dense_hip' or 'band_pcg'"
 
 
 def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels,
@@ -170,18 +170,16 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     N = len(init_nodes)
     chain = _is_canonical_chain(links, N)
     if not chain and general_solver not in _GENERAL_SOLVERS:
-        raise ValueError(_GENERAL_SOLVER_ERROR)
+        raise ValueError("general_solver must be 'auto', 'dense', 'dense_hip' or 'band_pcg'")
     if marginals and not chain and general_solver != 'dense_hip':
         raise UnsupportedGraphError('marginals=True serves canonical chains (links[k] = [k, k+1]) only; covariances of '
                                     "loop-closure graphs are not implemented (except with general_solver='dense_hip': the dense "
                                     'selected inverse, pvgo_marginals_general)')
     rp = _reproj_struct(reproj, loss_weight, dev)
     out_dtype = pp._plain(init_nodes).dtype if isinstance(init_nodes, torch.Tensor) else torch.get_default_dtype()
-    t64 = lambda x: pp._plain(torch.as_tensor(x)).detach().to(dev, torch.float64).contiguous()
-    nodes, vels = t64(init_nodes).clone(), t64(init_vels).clone()
-    poses, drots, dtrans, dvels = t64(vo_motions), t64(imu_drots), t64(imu_dtrans), t64(imu_dvels)
-    dts64 = t64(dts).reshape(-1)
+    nodes, vels, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, init_nodes, init_vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     edges = torch.as_tensor(links).to(dev, torch.int64).contiguous()
+    nodes, vels, dts64 = nodes.clone(), vels.clone(), dts64.reshape(-1)
     target0 = nodes[0].clone()
 
     if chain:            # the topology train.py produces: block-tridiagonal fast path, whole LM loop in one library call
@@ -193,17 +191,14 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
         how = general_solver
         if how == 'auto':        # a long chain with a few loop closures: block-tridiagonal solver + low-rank correction (PCG)
             how = 'band_pcg' if (N > 512 and k_off <= 64) else 'dense'
+        if how != 'band_pcg' and N > _DENSE_MAX_NODES:
+            raise UnsupportedGraphError('dense general-topology path is sized for N <= %d nodes, (9N)^2 doubles (got %d nodes, %d off-band '
+                                        'edges; general_solver="band_pcg" has no such limit)' % (_DENSE_MAX_NODES, N, k_off))
+        lm_args = (nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight)
         if how == 'band_pcg':
-            nodes, vels, res = run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp,
-                                               kernel=robust)
-        elif how in ('dense', 'dense_hip'):      # 'dense_hip': the same LM with the project's own Cholesky (csrc/dense_chol.hip)
-            if N > 12000:
-                raise UnsupportedGraphError('dense general-topology path is sized for N <= 12000 nodes, (9N)^2 doubles (got %d '
-                                            'nodes, %d off-band edges; general_solver="band_pcg" has no such limit)' % (N, k_off))
-            nodes, vels, res = run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight, radius=radius, reproj=rp,
-                                            kernel=robust, solver='hip' if how == 'dense_hip' else 'torch')
-        else:
-            raise ValueError(_GENERAL_SOLVER_ERROR)
+            nodes, vels, res = run_lm_band_pcg(*lm_args, radius=radius, reproj=rp, kernel=robust)
+        else:                    # 'dense_hip': the LM of 'dense' with the project's own Cholesky (csrc/dense_chol.hip)
+            nodes, vels, res = run_lm_dense(*lm_args, radius=radius, reproj=rp, kernel=robust, solver='hip' if how == 'dense_hip' else 'torch')
 
     if target == 'vo':
         vo = vo_motions if isinstance(vo_motions, torch.Tensor) else torch.as_tensor(vo_motions)

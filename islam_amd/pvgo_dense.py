@@ -1,33 +1,31 @@
 """General-topology PVGO (arbitrary ``links``: loop closures, skipped frames) on the GPU -- SURVEY.md section 8f rank 4.
 
-The chain fast path (islam_amd/csrc/pvgo.hip) needs links[k] = [k, k+1].  For any other edge set this module runs the
-same LM (pp.optim.LM + Cholesky + TrustRegion + StopOnPlateau as constructed at pvgo.py:169-172) with the same dense
-normal matrix PyPose factorises, but never forms the Jacobian PyPose multiplies (rows x 10N):
-
-  * residuals and Jacobian blocks per factor from the HIP kernels (islam_pvgo_linearize_edges for the VO factors on
-    arbitrary edges, islam_pvgo_linearize for the IMU factors, which always couple consecutive nodes);
-  * A = J^T W J (9N x 9N) and b = -J^T W r assembled block by block on the device (islam_pvgo_assemble_dense):
-    O(E) work instead of the 2*rows*cols^2 dense product;
-  * fp64 POTRF / POTRS from rocSOLVER (the only O(N^3) piece; its trailing updates are fp64 MFMA GEMMs), or with solver='hip' the
-    project's own blocked Cholesky on v_mfma_f64_16x16x4_f64 (csrc/dense_chol.hip), in place;
-  * retraction, trial residuals and the trust-region term (J D)^T (2R + J D) from the per-factor blocks.
-Sized by the dense matrix: (9N)^2 doubles (N = 5001: 16 GB of the 288 GB).
-
-Long trajectories with a few loop closures do not need the dense matrix at all (run_lm_band_pcg): the IMU factors always
-couple consecutive nodes and a VO edge (i, j) adds S = w J^T J to the diagonal blocks of i and j and -S to the block (i, j), so
-  A = B + R,  B = block-tridiagonal (all diagonal blocks, the couplings |i-j| = 1),  R = the off-band blocks of the k long edges,
-B is positive definite on its own, rank(R) <= 12 k, and conjugate gradients preconditioned with B^-1 -- the block-tridiagonal
-solver of the chain path, islam_pvgo_solve_chain, ~60 us per application at N = 5001 -- reaches the solution of the SAME
-normal equations in at most 12 k + 1 iterations.  Same LM control, same trial / trust-region evaluation; memory O(N + k).
+The chain fast path (islam_amd/csrc/pvgo.hip) needs links[k] = [k, k+1].  For any other edge set this module runs the same LM
+(pp.optim.LM + Cholesky + TrustRegion + StopOnPlateau as constructed at pvgo.py:169-172) on the normal equations PyPose factorises, but
+never forms the Jacobian PyPose multiplies (rows x 10N).  There is ONE loop, _run_lm: residuals and Jacobian blocks per factor
+from the HIP kernels (islam_pvgo_linearize_edges for the VO factors on arbitrary edges, islam_pvgo_linearize for the IMU factors, which
+always couple consecutive nodes), cumulative damping, retraction, trial residuals and the trust-region term (J D)^T (2R + J D) from the
+per-factor blocks.  It is given one of three linear systems, each with assemble(vo, lin, rpt, c_vo, c_imu) -> the clamped diagonal of
+one linearisation, solve(d) -> the step (N,9) or None (failed), and ``extra`` entries for the result:
+  * _DenseSystem: A = J^T W J (9N x 9N) and b = -J^T W r assembled block by block on the device (islam_pvgo_assemble_dense: O(E) work
+    instead of the 2*rows*cols^2 dense product); fp64 POTRF / POTRS from rocSOLVER (the only O(N^3) piece), a second matrix per trial;
+  * _DenseHipSystem: the same A and b with the project's own blocked Cholesky on v_mfma_f64_16x16x4_f64 (csrc/dense_chol.hip, DESIGN.md
+    section 3.17), in place.  Both are sized by the dense matrix: (9N)^2 doubles (N = 5001: 16 GB of the 288 GB);
+  * _BandPcgSystem, for long trajectories with a few loop closures: the IMU factors always couple consecutive nodes and a VO edge
+    (i, j) adds S = w J^T J to the diagonal blocks of i and j and -S to the block (i, j), so
+      A = B + R,  B = block-tridiagonal (all diagonal blocks, the couplings |i-j| = 1),  R = the off-band blocks of the k long edges,
+    B is positive definite on its own, rank(R) <= 12 k, and conjugate gradients preconditioned with B^-1 -- the block-tridiagonal
+    solver of the chain path, islam_pvgo_solve_chain, ~60 us per application at N = 5001 -- reaches the solution of the SAME normal
+    equations in at most 12 k + 1 iterations.  Memory O(N + k).
 
 Robust kernels (``kernel``, an islam_amd.robust.RobustSpec): islam_pvgo_robust_weights gives the multiplier
 c = rho'(s) of every VO edge and IMU-side factor and the loss sum rho(s); the scaled assembly entry points and the trust-region
-term apply c per factor.  Both solvers use the same multipliers and the same loss."""
+term apply c per factor.  Every system uses the same multipliers and the same loss."""
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import c_double, check, lib, ptr, stream_ptr
+from ._lib import IslamHipError, c_double, check, lib, ptr, stream_ptr
 from .lm_control import LMControl
 
 _NOCLAMP = 1e300
@@ -39,6 +37,18 @@ def _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy_poses
     check(lib().islam_pvgo_linearize_edges(ptr(nodes), ptr(edges), ptr(poses), E, ptr(vo), stream_ptr(nodes.device)))
     lin, _ = ops.pvgo_linearize(nodes, vels, dummy_poses, drots, dtrans, dvels, dts)     # IMU rows of `lin`; VO rows unused
     return vo, lin
+
+
+class _Graph:
+    """What _run_lm and gauss_newton_matrix both set up (float64 contiguous device tensors, N nodes): w, the four squared loss weights, and
+    linearize(nodes, vels), with unit poses where islam_pvgo_linearize takes VO motions."""
+
+    def __init__(self, nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight):
+        self.N, self.edges, self.dts, self.dev = nodes.shape[0], edges, dts, nodes.device
+        self.w = [float(x) ** 2 for x in loss_weight[:4]]
+        dummy = torch.zeros((self.N - 1, 7), dtype=torch.float64, device=self.dev)
+        dummy[:, 6] = 1.0
+        self.linearize = lambda nodes, vels: _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
 
 
 def _loss(vo, lin):
@@ -130,40 +140,65 @@ class _ReprojTerms:
         return (d * (2 * self.g + (self.S @ d[:, :, None])[:, :, 0])).sum()
 
 
-def _assemble_normal(A, b, vo, lin, edges, nptr, nadj, dts, w, rpt=None, c_vo=None, c_imu=None):
-    """A (9N x 9N, fully written) and b (9N) of one linearisation: the undamped, unclamped Gauss-Newton matrix J^T W J and -J^T W r.
-    w: the four squared loss weights; rpt: _ReprojTerms or None; c_vo, c_imu: robust multipliers or None."""
-    N, E, dev = A.shape[0] // 9, edges.shape[0], A.device
-    Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
-    if rpt is not None:
-        rpt.add_to_chain(Hd, Ho, rhs)
-    if c_vo is not None:
-        check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), ptr(edges), ptr(nptr), ptr(nadj),
-                                                     c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
-    else:
-        check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(edges), ptr(nptr), ptr(nadj),
-                                              c_double(w[0]), N, E, ptr(A), ptr(b), stream_ptr(dev)))
+class _DenseSystem:
+    """A (9N x 9N) and b (9N) of one linearisation, factored by torch / rocSOLVER."""
+
+    def __init__(self, g, vmin=None, vmax=None):
+        self.g, self.vmin, self.vmax = g, vmin, vmax
+        self.nptr, self.nadj = [torch.from_numpy(a).to(g.dev) for a in _node_adjacency(g.edges.cpu().numpy(), g.N)]
+        self.A = torch.empty((9 * g.N, 9 * g.N), dtype=torch.float64, device=g.dev)
+        self.b = torch.empty((9 * g.N,), dtype=torch.float64, device=g.dev)
+        self.extra = {}
+
+    def fill(self, vo, lin, rpt=None, c_vo=None, c_imu=None):
+        """A (fully written) = J^T W J, undamped and unclamped, and b = -J^T W r.  rpt: _ReprojTerms; c_vo, c_imu: robust multipliers."""
+        g, N, E, w = self.g, self.g.N, self.g.edges.shape[0], self.g.w
+        Hd, Ho, rhs = ops.pvgo_build_normal(lin, g.dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
+        if rpt is not None:
+            rpt.add_to_chain(Hd, Ho, rhs)
+        tail = (ptr(g.edges), ptr(self.nptr), ptr(self.nadj), c_double(w[0]), N, E, ptr(self.A), ptr(self.b), stream_ptr(g.dev))
+        if c_vo is None:
+            check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), *tail))
+        else:
+            check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), *tail))
+
+    def assemble(self, vo, lin, rpt, c_vo, c_imu):
+        self.fill(vo, lin, rpt, c_vo, c_imu)
+        return self.A.diagonal().clamp(self.vmin, self.vmax).clone()          # A.diagonal().clamp_(min, max)
+
+    def solve(self, d):
+        """A second (9N)^2 matrix, L, lives until this returns: it is gone before the retraction."""
+        self.A.diagonal().copy_(d)
+        L, info = torch.linalg.cholesky_ex(self.A)
+        if int(info) != 0 or not bool(torch.isfinite(L.diagonal()).all()):
+            return None
+        return torch.cholesky_solve(self.b[:, None], L)[:, 0].view(self.g.N, 9).contiguous()
+
+
+class _DenseHipSystem(_DenseSystem):
+    """The same A and b, factored in place: the upper triangle of A and the vector d in, L in A's lower triangle."""
+
+    def __init__(self, g, vmin, vmax):
+        super().__init__(g, vmin, vmax)
+        self.cws = ops.dense_chol_workspace(9 * g.N, g.dev)
+
+    def solve(self, d):
+        info = ops.dense_chol_factor(self.A, d, self.cws)
+        D = ops.dense_chol_solve(self.A, self.b, self.cws).view(self.g.N, 9)
+        failed = torch.stack([info[0] != 0, ~torch.isfinite(D).all()]).any().item()          # one small read-back
+        return None if failed else D
 
 
 def gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None):
     """A = J^T W J (9N x 9N, device, fully written) at (nodes, vels): undamped, unclamped, no gauge fixed -- what run_lm_dense assembles
     before it damps the diagonal.  The VO factors may sit on any number of edges (the assembly needs no E = N - 1; only the LM's loss
     does)."""
-    N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
-    if poses.shape[0] != E:
-        raise ValueError('one VO motion per edge: %d motions for %d edges' % (poses.shape[0], E))
-    dev = nodes.device
-    w = [float(x) ** 2 for x in loss_weight[:4]]
-    dummy = torch.zeros((M, 7), dtype=torch.float64, device=dev)
-    dummy[:, 6] = 1.0
-    nptr, nadj = _node_adjacency(edges.cpu().numpy(), N)
-    nptr, nadj = torch.from_numpy(nptr).to(dev), torch.from_numpy(nadj).to(dev)
-    A = torch.empty((9 * N, 9 * N), dtype=torch.float64, device=dev)
-    b = torch.empty((9 * N,), dtype=torch.float64, device=dev)
-    vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
-    rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
-    _assemble_normal(A, b, vo, lin, edges, nptr, nadj, dts, w, rpt)
-    return A
+    if poses.shape[0] != edges.shape[0]:
+        raise ValueError('one VO motion per edge: %d motions for %d edges' % (poses.shape[0], edges.shape[0]))
+    sysm = _DenseSystem(_Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight))
+    vo, lin = sysm.g.linearize(nodes, vels)
+    sysm.fill(vo, lin, _ReprojTerms(nodes, reproj) if reproj is not None else None)
+    return sysm.A
 
 
 def fix_gauge(A, anchor):
@@ -186,7 +221,6 @@ def marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_w
     requested 9 x 9 blocks of W^T W are formed: one (9N)^2 array in all.
     In: float64 contiguous device tensors; pairs (P,2) node index pairs or None (the graph's own edges).
     Returns (node_cov (N,9,9), pair_cov (P,9,9)); raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
-    from ._lib import IslamHipError
     N = nodes.shape[0]
     if anchor is not None and not 0 <= int(anchor) < N:
         raise ValueError('anchor=%r is not a node of a graph of %d nodes' % (anchor, N))
@@ -200,61 +234,30 @@ def marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_w
     return ops.pvgo_dense_cov_blocks(A, anchor, edges if pairs is None else pairs)
 
 
-def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
-                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, solver='torch'):
-    """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None.
-    solver: 'torch' (torch.linalg.cholesky_ex / cholesky_solve: a second (9N)^2 matrix per trial) or 'hip' (islam_dense_chol_factor /
-    _solve, csrc/dense_chol.hip: the damped diagonal goes in as a vector and the factor lands in A's lower triangle, no second matrix).
-    Returns (nodes, vels, info dict)."""
-    N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
-    _check_kernel(kernel, reproj)
-    if solver not in ('torch', 'hip'):
-        raise ValueError("solver must be 'torch' or 'hip'")
-    if E != M:
-        raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, M))
-    dev = nodes.device
-    w = [float(x) ** 2 for x in loss_weight[:4]]
-    dummy = torch.zeros((M, 7), dtype=torch.float64, device=dev)
-    dummy[:, 6] = 1.0
-    nptr, nadj = _node_adjacency(edges.cpu().numpy(), N)
-    nptr, nadj = torch.from_numpy(nptr).to(dev), torch.from_numpy(nadj).to(dev)
-    A = torch.empty((9 * N, 9 * N), dtype=torch.float64, device=dev)
-    b = torch.empty((9 * N,), dtype=torch.float64, device=dev)
+def _run_lm(nodes, vels, g, sysm, reproj, kernel, radius, max_steps, patience, decreasing):
+    """The LM on the linear system ``sysm`` of the graph ``g``.  Returns (nodes, vels, info dict)."""
     ctl = LMControl(radius=radius, max_steps=max_steps, patience=patience, decreasing=decreasing)
     trials = 0
-    cws = ops.dense_chol_workspace(9 * N, dev) if solver == 'hip' else None
     while ctl.continual:
-        vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
+        vo, lin = g.linearize(nodes, vels)
         rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
-        c_vo = c_imu = None
-        if kernel is not None:
-            c_vo, c_imu, rho = ops.pvgo_robust_weights(vo, lin, kernel)
+        c_vo, c_imu, rho = ops.pvgo_robust_weights(vo, lin, kernel) if kernel is not None else (None, None, None)
         if not ctl.has_loss:
             ctl.set_initial_loss(float(rho) if kernel is not None else float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
         ctl.begin_step()
-        _assemble_normal(A, b, vo, lin, edges, nptr, nadj, dts, w, rpt, c_vo, c_imu)
-        d = A.diagonal().clamp(vmin, vmax).clone()                    # A.diagonal().clamp_(min, max)
+        d = sysm.assemble(vo, lin, rpt, c_vo, c_imu)
         while True:
             d = d + d * ctl.damping                                   # cumulative, like A.diagonal().add_(...)
             trials += 1
-            if solver == 'hip':               # upper triangle of A + d -> L in A's lower triangle; one small read-back
-                info = ops.dense_chol_factor(A, d, cws)
-                D = ops.dense_chol_solve(A, b, cws).view(N, 9)
-                failed = torch.stack([info[0] != 0, ~torch.isfinite(D).all()]).any().item()
-            else:
-                A.diagonal().copy_(d)
-                L, info = torch.linalg.cholesky_ex(A)
-                failed = int(info) != 0 or not bool(torch.isfinite(L.diagonal()).all())
-            if failed:
+            D = sysm.solve(d)
+            if D is None:
                 print('Linear solver failed. Breaking optimization step...')
                 ctl.solver_failed()
                 break
-            if solver != 'hip':
-                D = torch.cholesky_solve(b[:, None], L)[:, 0].view(N, 9).contiguous()
-                del L
             nt, vt = ops.pvgo_retract(nodes, vels, D, 1.0)
-            vo_t, lin_t = _linearize(nt, vt, edges, poses, drots, dtrans, dvels, dts, dummy)
-            st, qt = _trial_loss(vo_t, lin_t, kernel), _quality_term(vo, lin, edges, dts, D, c_vo, c_imu)
+            vo_t, lin_t = g.linearize(nt, vt)
+            st = _loss(vo_t, lin_t) if kernel is None else ops.pvgo_robust_weights(vo_t, lin_t, kernel, with_weights=False)[2]
+            qt = _quality_term(vo, lin, g.edges, g.dts, D, c_vo, c_imu)
             if rpt is not None:
                 st, qt = st + _ReprojTerms(nodes, reproj, D).rr, qt + rpt.quality(D)
             s, q = torch.stack([st, qt]).tolist()
@@ -262,17 +265,30 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
                 nodes, vels = nt, vt
                 break
         ctl.end_step()
-    return nodes, vels, dict(steps=ctl.steps, trials=trials, loss=ctl.loss, trace=ctl.trace)
+    return nodes, vels, dict(steps=ctl.steps, trials=trials, loss=ctl.loss, trace=ctl.trace, **sysm.extra)
 
 
-def _check_kernel(kernel, reproj):
+def _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver='torch'):
+    """The host-side checks of the two entry points, in this order and before any device work, then the _Graph."""
+    N, E = nodes.shape[0], edges.shape[0]
     if kernel is not None and reproj is not None:
         raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
+    if solver not in ('torch', 'hip'):
+        raise ValueError("solver must be 'torch' or 'hip'")
+    if E != N - 1:
+        raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, N - 1))
+    return _Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight)
 
 
-def _trial_loss(vo, lin, kernel):
-    """The LM loss at a trial point: the plain sum of squares, or sum rho under a robust kernel (islam_pvgo_robust_weights)."""
-    return _loss(vo, lin) if kernel is None else ops.pvgo_robust_weights(vo, lin, kernel, with_weights=False)[2]
+def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
+                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, solver='torch'):
+    """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None.
+    solver: 'torch' (torch.linalg.cholesky_ex / cholesky_solve: a second (9N)^2 matrix per trial) or 'hip' (islam_dense_chol_factor /
+    _solve, csrc/dense_chol.hip: the damped diagonal goes in as a vector and the factor lands in A's lower triangle, no second matrix).
+    Returns (nodes, vels, info dict)."""
+    g = _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver)
+    sysm = (_DenseHipSystem if solver == 'hip' else _DenseSystem)(g, vmin, vmax)
+    return _run_lm(nodes, vels, g, sysm, reproj, kernel, radius, max_steps, patience, decreasing)
 
 
 # ------------------------------------------------------------------------------------------ band + low-rank (PCG)
@@ -378,66 +394,41 @@ def _pcg(sysm, ws, rtol=1e-13, check_every=6):
     return x, its, rel
 
 
+class _BandPcgSystem:
+    """A = B + R of one linearisation (_BandSystem), solved by _pcg on one chain-solver workspace."""
+
+    def __init__(self, g, vmin, vmax):
+        self.g, self.vmin, self.vmax = g, vmin, vmax
+        self.off_idx = torch.from_numpy(off_band_edges(g.edges.cpu().numpy())).to(g.dev)
+        self.ws = ops.pvgo_workspace(g.N, g.dev)
+        try:
+            ops.pvgo_solve_status(g.N, self.ws, g.dev)     # initialises the fresh workspace's status / hand-off words
+        except IslamHipError:
+            pass
+        self.extra = dict(pcg_iterations=0, pcg_worst_relative_residual=0.0, off_band_edges=int(self.off_idx.numel()))
+
+    def assemble(self, vo, lin, rpt, c_vo, c_imu):
+        self.band = _BandSystem(vo, lin, self.g.edges, self.g.dts, self.g.N, self.g.w, self.vmin, self.vmax, self.off_idx, rpt, c_vo, c_imu)
+        return self.band.diag0
+
+    def solve(self, d):
+        self.band.set_diagonal(d)
+        try:
+            D, its, rel = _pcg(self.band, self.ws)
+        except IslamHipError:
+            return None
+        self.extra['pcg_iterations'] += its
+        self.extra['pcg_worst_relative_residual'] = max(self.extra['pcg_worst_relative_residual'], rel)
+        # an unconverged step must not reach LM silently: treat it like a failed factorisation (PyPose's Cholesky would
+        # have returned the exact solution or raised)
+        if not bool(torch.isfinite(D).all()) or rel > PCG_FAIL_RTOL:
+            return None
+        return D.contiguous()
+
+
 def run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
                     decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None):
     """The LM of run_lm_dense on the band + low-rank form of the same normal equations.  In: float64 contiguous device
     tensors.  Returns (nodes, vels, info dict)."""
-    from ._lib import IslamHipError
-    N, E, M = nodes.shape[0], edges.shape[0], nodes.shape[0] - 1
-    _check_kernel(kernel, reproj)
-    if E != M:
-        raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, M))
-    dev = nodes.device
-    w = [float(x) ** 2 for x in loss_weight[:4]]
-    dummy = torch.zeros((M, 7), dtype=torch.float64, device=dev)
-    dummy[:, 6] = 1.0
-    off_idx = torch.from_numpy(off_band_edges(edges.cpu().numpy())).to(dev)
-    ws = ops.pvgo_workspace(N, dev)
-    try:
-        ops.pvgo_solve_status(N, ws, dev)                  # initialises the fresh workspace's status / hand-off words
-    except IslamHipError:
-        pass
-    ctl = LMControl(radius=radius, max_steps=max_steps, patience=patience, decreasing=decreasing)
-    trials = pcg_its = 0
-    pcg_worst = 0.0
-    while ctl.continual:
-        vo, lin = _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
-        rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
-        c_vo = c_imu = None
-        if kernel is not None:
-            c_vo, c_imu, rho = ops.pvgo_robust_weights(vo, lin, kernel)
-        if not ctl.has_loss:
-            ctl.set_initial_loss(float(rho) if kernel is not None else float(_loss(vo, lin) + (rpt.rr if rpt is not None else 0.0)))
-        ctl.begin_step()
-        sysm = _BandSystem(vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt, c_vo, c_imu)
-        d = sysm.diag0
-        while True:
-            d = d + d * ctl.damping                                   # cumulative, like A.diagonal().add_(...)
-            sysm.set_diagonal(d)
-            trials += 1
-            try:
-                D, its, rel = _pcg(sysm, ws)
-            except IslamHipError:
-                print('Linear solver failed. Breaking optimization step...')
-                ctl.solver_failed()
-                break
-            pcg_its += its
-            pcg_worst = max(pcg_worst, rel)
-            # an unconverged step must not reach LM silently: treat it like a failed factorisation (PyPose's Cholesky would
-            # have returned the exact solution or raised)
-            if not bool(torch.isfinite(D).all()) or rel > PCG_FAIL_RTOL:
-                print('Linear solver failed. Breaking optimization step...')
-                ctl.solver_failed()
-                break
-            nt, vt = ops.pvgo_retract(nodes, vels, D.contiguous(), 1.0)
-            vo_t, lin_t = _linearize(nt, vt, edges, poses, drots, dtrans, dvels, dts, dummy)
-            st, qt = _trial_loss(vo_t, lin_t, kernel), _quality_term(vo, lin, edges, dts, D, c_vo, c_imu)
-            if rpt is not None:
-                st, qt = st + _ReprojTerms(nodes, reproj, D.contiguous()).rr, qt + rpt.quality(D)
-            s, q = torch.stack([st, qt]).tolist()
-            if ctl.after_trial(s, q):
-                nodes, vels = nt, vt
-                break
-        ctl.end_step()
-    return nodes, vels, dict(steps=ctl.steps, trials=trials, loss=ctl.loss, trace=ctl.trace, pcg_iterations=pcg_its,
-                             pcg_worst_relative_residual=pcg_worst, off_band_edges=int(off_idx.numel()))
+    g = _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel)
+    return _run_lm(nodes, vels, g, _BandPcgSystem(g, vmin, vmax), reproj, kernel, radius, max_steps, patience, decreasing)

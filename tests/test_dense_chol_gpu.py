@@ -267,24 +267,29 @@ def test_lm_dense_hip_equals_dense_under_huber(cuda):
 def test_lm_dense_hip_breaks_the_step_like_dense(cuda, monkeypatch, capsys):
     """An indefinite normal matrix from a negative information scalar on the velocity factor, as in
     tests/test_pvgo_gpu.py::test_lm_solver_failure_breaks_the_step_like_pypose: every solve fails, PyPose's message is printed, the
-    plateau counter ends the loop after three steps and the iterate does not move -- with either Cholesky."""
+    plateau counter ends the loop after three steps and the iterate does not move -- with either Cholesky, and with band + PCG, whose
+    chain solver reports the non-positive pivot as an error status (its info dict has the three PCG entries more)."""
     from islam_amd import ops
     info = (1.0, -0.5, 100.0, 0.01)
     real = ops.pvgo_build_normal
     monkeypatch.setattr(ops, 'pvgo_build_normal', lambda lin, dts, N, w, *a, **kw: real(lin, dts, N, (0.0, info[1], info[2], info[3]), *a, **kw))
     p2 = _loop_closure_problem()
     out = {}
-    for how in ('dense', 'dense_hip'):
+    for how in ('dense', 'dense_hip', 'band_pcg'):
         capsys.readouterr()
         out[how] = _run(p2, general_solver=how)
         out[how + '_text'] = capsys.readouterr().out
-    d, h = out['dense'], out['dense_hip']
+    d = out['dense']
     assert d[5]['steps'] == 3 and d[5]['trials'] == 3              # StopOnPlateau(patience=3): no decrease three times, one failed solve each
-    assert h[5]['steps'] == d[5]['steps'] and h[5]['trials'] == d[5]['trials'] and len(h[5]['trace']) == len(d[5]['trace']) == 3
-    for th, td in zip(h[5]['trace'], d[5]['trace']):                # a failed solve is traced as (NaN, damping, rejected)
-        assert np.isnan(th[0]) and np.isnan(td[0]) and th[1:] == td[1:] and th[2] is False
-    assert h[5]['loss'] == d[5]['loss']
     assert out['dense_text'].count('Linear solver failed. Breaking optimization step...') == 3
-    assert out['dense_hip_text'] == out['dense_text']
-    np.testing.assert_array_equal(h[2].tensor().numpy(), d[2].tensor().numpy())
-    np.testing.assert_array_equal(h[3].numpy(), d[3].numpy())
+    for how in ('dense_hip', 'band_pcg'):
+        h = out[how]
+        assert h[5]['steps'] == d[5]['steps'] and h[5]['trials'] == d[5]['trials'] and len(h[5]['trace']) == len(d[5]['trace']) == 3
+        for th, td in zip(h[5]['trace'], d[5]['trace']):            # a failed solve is traced as (NaN, damping, rejected)
+            assert np.isnan(th[0]) and np.isnan(td[0]) and th[1:] == td[1:] and th[2] is False
+        assert h[5]['loss'] == d[5]['loss']
+        assert out[how + '_text'] == out['dense_text']
+        np.testing.assert_array_equal(h[2].tensor().numpy(), d[2].tensor().numpy())
+        np.testing.assert_array_equal(h[3].numpy(), d[3].numpy())
+    assert set(out['dense_hip'][5]) == set(d[5])
+    assert set(out['band_pcg'][5]) == set(d[5]) | {'pcg_iterations', 'pcg_worst_relative_residual', 'off_band_edges'}
