@@ -710,6 +710,22 @@ int islam_pvgo_run_chain_robust(double* nodes, double* vels, const double* poses
                                 const islam_pvgo_params* prm, const islam_pvgo_robust* robust, void* workspace,
                                 size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap,
                                 void* stream);
+/* Per-factor information matrices.  The reference hands PyPose one information matrix per factor
+ * (pvgo.py:133-162 stacks (E,6,6) and (M,3,3) tensors, :178 passes them as weight=) and only ever fills them with loss_weight^2 I;
+ * here every factor k carries its own symmetric positive SEMI-definite Omega_k:
+ *   A = sum_k J_k^T Omega_k J_k,  b = -sum_k J_k^T Omega_k r_k  (the Jacobians of islam_pvgo_run_chain, unchanged).
+ * Everything else of the LM is unchanged: the diagonal clamp [vmin, vmax], cumulative damping, the reject limit, TrustRegion,
+ * StopOnPlateau, and the accept-test loss and trust-region term, which stay UNWEIGHTED as they are under scalar weights.
+ * Omega_k = w[g] I for every factor is islam_pvgo_run_chain; Omega_k = 0 removes factor k from the step.
+ * Device layout, component-major like `lin` (entry c of factor k at [c * count + k]), M = N - 1:
+ *   info_vo (21, M): the upper triangle of the 6x6 of VO factor k, rows ordered [rho, phi], row-major order of the triangle;
+ *   info_imu (18, M): the 6-entry upper triangles [00 01 02 11 12 22] of [velocity | IMU rotation | translation-velocity].
+ * prm->w is ignored for the assembly.  info_vo == info_imu == NULL: exactly islam_pvgo_run_chain; exactly one of them NULL:
+ * ISLAM_EARG before any device work.  Runs the launch-per-stage loop with one more launch (info_build_kernel) per linearisation. */
+int islam_pvgo_run_chain_info(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                              const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                              const double* info_vo, const double* info_imu, void* workspace, size_t workspace_bytes,
+                              islam_pvgo_result* result, double* trace, int trace_cap, void* stream);
 /* General topology: the multipliers c of every VO edge from vo (24,E) (islam_pvgo_linearize_edges) -> c_vo (E), and of the three
  * IMU-side factors of every link from lin (42,M) -> c_imu (3,M) [velocity | rotation | translation-velocity]; rho_part
  * ((max(E,M)+63)/64) = partial sums of rho over both.  c_vo / c_imu may be NULL (loss only). */
@@ -734,6 +750,12 @@ int islam_pvgo_build_normal(const double* lin, const double* dts, int N, const d
  * translation-velocity] (islam_pvgo_robust_weights) scale w[1], w[2], w[3] of link k. */
 int islam_pvgo_build_normal_scaled(const double* lin, const double* dts, int N, const double w[4], const double* c_imu,
                                    double vmin, double vmax, double* Hd, double* Ho, double* rhs, void* stream);
+/* islam_pvgo_build_normal with one information matrix per factor (semantics and layout: islam_pvgo_run_chain_info; pvgo.py:133-162,178):
+ * info_vo (21, N-1) or NULL (no VO group, like w[0] = 0), info_imu (18, N-1).  Per link k with A_k = [[G, C],[0, G]]: the pose block
+ * S = A_k^T O0 A_k + O3 on rho-rho + B^T O2 B on phi-phi enters Hd of both nodes and -S the coupling; O1 + dt^2 O3 (node k) and O1
+ * (node k+1) the velocity blocks; dt O3 the rho-v block of node k; -dt O3 and -O1 the v-rho and v-v blocks of the coupling. */
+int islam_pvgo_build_normal_info(const double* lin, const double* dts, int N, const double* info_vo, const double* info_imu,
+                                 double vmin, double vmax, double* Hd, double* Ho, double* rhs, void* stream);
 /* Hd.diag += Hd.diag*damping (in place, cumulative), then solve -> dx (N,9).  status (device int[4]). */
 int islam_pvgo_solve_chain(double* Hd, const double* Ho, const double* rhs, double damping, int N,
                            const int seg_len[2], void* workspace, size_t workspace_bytes, double* dx, void* stream);
@@ -871,6 +893,13 @@ int islam_pvgo_assemble_dense(const double* Hd, const double* Ho, const double* 
 int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
                                      const double* c_vo, const int64_t* edges, const int64_t* node_ptr,
                                      const int64_t* node_adj, double w0, int N, int E, double* A, double* rhs, void* stream);
+/* islam_pvgo_assemble_dense with one information matrix per VO edge (pvgo.py:133-162,178; layout: islam_pvgo_run_chain_info):
+ * info_vo (21,E); edge e adds A_e^T O_e A_e to the diagonal blocks of its two nodes (CSR order, no atomics), -A_e^T O_e A_e to the
+ * blocks (i, j) and (j, i) (one atomic per entry), and -+A_e^T O_e e to the right-hand side.  Hd, Ho, rhs_chain: the IMU part from
+ * islam_pvgo_build_normal_info with info_vo = NULL. */
+int islam_pvgo_assemble_dense_info(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
+                                   const double* info_vo, const int64_t* edges, const int64_t* node_ptr,
+                                   const int64_t* node_adj, int N, int E, double* A, double* rhs, void* stream);
 /* Dense fp64 Cholesky A = L L^T of the general-topology normal matrix and the solve with its factor (csrc/dense_chol.hip, DESIGN.md
  * section 3.17): the O(n^3) step of the loop-closure LM on the matrix cores (v_mfma_f64_16x16x4_f64), n = 9N, any n >= 1.
  * Storage contract.  A: n x n row-major device doubles.  islam_dense_chol_factor READS the strict upper triangle of A and diag (n) --

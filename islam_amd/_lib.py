@@ -140,6 +140,8 @@ SIGNATURES = {
     'islam_pvgo_run_chain_robust': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), ctypes.POINTER(PvgoRobust),
                                                              c_void_p, c_size_t, ctypes.POINTER(PvgoResult), c_void_p, c_int,
                                                              c_void_p]),
+    'islam_pvgo_run_chain_info': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), c_void_p, c_void_p, c_void_p, c_size_t,
+                                           ctypes.POINTER(PvgoResult), c_void_p, c_int, c_void_p]),
     'islam_pvgo_robust_weights': (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(PvgoRobust)] + [c_void_p] * 4),
     'islam_pvgo_reproj_reduce': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(PvgoReproj), c_void_p, c_void_p]),
     'islam_pvgo_linearize': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 3),
@@ -147,6 +149,7 @@ SIGNATURES = {
                                 [c_void_p] * 4),
     'islam_pvgo_build_normal_scaled': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_double), c_void_p, c_double, c_double] +
                                        [c_void_p] * 4),
+    'islam_pvgo_build_normal_info': (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 4),
     'islam_pvgo_solve_chain': (c_int, [c_void_p] * 3 + [c_double, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
                                                         c_void_p, c_void_p]),
     'islam_pvgo_solve_chain_enqueue': (c_int, [c_void_p] * 3 + [c_double, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
@@ -186,6 +189,7 @@ SIGNATURES = {
     'islam_pvgo_linearize_edges': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
     'islam_pvgo_assemble_dense': (c_int, [c_void_p] * 7 + [c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'islam_pvgo_assemble_dense_scaled': (c_int, [c_void_p] * 8 + [c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'islam_pvgo_assemble_dense_info': (c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'islam_dense_chol_workspace_bytes': (c_size_t, [c_int]),
     'islam_dense_chol_factor': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'islam_dense_chol_solve': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

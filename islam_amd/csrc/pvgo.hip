@@ -120,9 +120,12 @@ namespace {
 int run_chain_entry(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
                     const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
                     const islam_pvgo_reproj* reproj, const islam_pvgo_robust* robust, void* workspace,
-                    size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
+                    size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream,
+                    const double* info_vo = nullptr, const double* info_imu = nullptr) {
     if (N < 2) return fail(ISLAM_EARG, "islam_pvgo_run_chain: N=%d < 2", N);
     if (!prm || !result) return fail(ISLAM_EARG, "islam_pvgo_run_chain: null params/result");
+    if ((info_vo == nullptr) != (info_imu == nullptr))
+        return fail(ISLAM_EARG, "islam_pvgo_run_chain_info: info_vo and info_imu must both be given or both be NULL");
     int rc;
     ReprojDev rp{};
     if (reproj && (rc = reproj_dev(reproj, rp)) != ISLAM_OK) return rc;
@@ -134,7 +137,7 @@ int run_chain_entry(double* nodes, double* vels, const double* poses, const doub
     if (rc != ISLAM_OK) return rc;
     hipStream_t s = as_stream(stream);
     rc = run_chain_impl(nodes, vels, ChainData{poses, drots, dtrans, dvels, dts, N}, prm, reproj, rp, w, s, result, trace, trace_cap,
-                        robust_on ? &rb : nullptr);
+                        robust_on ? &rb : nullptr, info_vo, info_imu);
     return rc == ISLAM_OK ? rc : abandon_run(w.state, s, rc);
 }
 }  // namespace
@@ -186,6 +189,17 @@ int islam_pvgo_build_normal_scaled(const double* lin, const double* dts, int N, 
     if (N < 2 || !c_imu) return fail(ISLAM_EARG, "islam_pvgo_build_normal_scaled: N=%d < 2 or null c_imu", N);
     hipLaunchKernelGGL(build_normal_kernel<true>, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, w[0], w[1],
                        w[2], w[3], vmin, vmax, Hd, Ho, rhs, c_imu);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// per-factor information matrices (pvgo.py:133-162,178): info_vo == NULL leaves the VO group out
+int islam_pvgo_build_normal_info(const double* lin, const double* dts, int N, const double* info_vo, const double* info_imu, double vmin,
+                                 double vmax, double* Hd, double* Ho, double* rhs, void* stream) {
+    if (N < 2 || !lin || !dts || !info_imu || !Hd || !Ho || !rhs)
+        return fail(ISLAM_EARG, "islam_pvgo_build_normal_info: N=%d < 2 or a null lin / dts / info_imu / output", N);
+    hipLaunchKernelGGL(info_build_kernel, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, info_vo, info_imu, vmin, vmax, Hd,
+                       Ho, rhs, Gate{nullptr, 0.0});
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
@@ -366,6 +380,20 @@ int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const d
     return ISLAM_OK;
 }
 
+int islam_pvgo_assemble_dense_info(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo, const double* info_vo,
+                                   const int64_t* edges, const int64_t* node_ptr, const int64_t* node_adj, int N, int E, double* A,
+                                   double* rhs, void* stream) {
+    if (N < 2 || E < 0 || (E > 0 && (!info_vo || !vo)))
+        return fail(ISLAM_EARG, "islam_pvgo_assemble_dense_info: N=%d E=%d, vo %p, info_vo %p", N, E, (const void*)vo, (const void*)info_vo);
+    hipStream_t s = as_stream(stream);
+    ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
+    hipLaunchKernelGGL(dense_info_nodes_kernel, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, info_vo, node_ptr, node_adj, N, E, A,
+                       rhs);
+    if (E > 0) hipLaunchKernelGGL(dense_info_edges_kernel, dim3((E + 63) / 64), dim3(64), 0, s, vo, info_vo, edges, N, E, A);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
 int islam_pvgo_robust_weights(const double* vo, int E, const double* lin, int M, const islam_pvgo_robust* robust, double* c_vo,
                               double* c_imu, double* rho_part, void* stream) {
     if (E < 0 || M < 0 || E + M < 1 || !robust || !rho_part || (E > 0 && !vo) || (M > 0 && !lin))
@@ -440,6 +468,15 @@ int islam_pvgo_run_chain_robust(double* nodes, double* vels, const double* poses
                                 islam_pvgo_result* result, double* trace, int trace_cap, void* stream) {
     return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, robust, workspace, workspace_bytes, result,
                            trace, trace_cap, stream);
+}
+
+// per-factor information matrices: the launch-per-stage loop with info_build_kernel behind every linearisation
+int islam_pvgo_run_chain_info(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                              const double* dvels, const double* dts, int N, const islam_pvgo_params* prm, const double* info_vo,
+                              const double* info_imu, void* workspace, size_t workspace_bytes, islam_pvgo_result* result, double* trace,
+                              int trace_cap, void* stream) {
+    return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, nullptr, workspace, workspace_bytes, result,
+                           trace, trace_cap, stream, info_vo, info_imu);
 }
 
 // Measurement hook (bench.py's roofline leg): the LM loop's dominant launch, trial_elim_kernel, exactly as islam_pvgo_run_chain

@@ -204,6 +204,91 @@ __global__ __launch_bounds__(64) void dense_edges_kernel(const double* __restric
         }
 }
 
+// ---- the same assembly with one information matrix per VO edge: info_vo (21, E), the packed upper triangles
+__device__ __forceinline__ InfoVo edge_info_normal(const double* __restrict__ vo, const double* __restrict__ info_vo, int E, int e) {
+    const double* r = vo + e;
+    const size_t ld = (size_t)E;
+    const V3<double> er{r[0], r[ld], r[2 * ld]}, ep{r[3 * ld], r[4 * ld], r[5 * ld]};
+    const M3<double> G{r[6 * ld], r[7 * ld], r[8 * ld], r[9 * ld], r[10 * ld], r[11 * ld], r[12 * ld], r[13 * ld], r[14 * ld]};
+    const M3<double> C{r[15 * ld], r[16 * ld], r[17 * ld], r[18 * ld], r[19 * ld], r[20 * ld], r[21 * ld], r[22 * ld], r[23 * ld]};
+    return info_vo_normal(info_vo + e, ld, G, C, er, ep);
+}
+
+// add a 3x3 block into a row-major matrix of leading dimension ld (fixed indices: the operands stay in registers)
+__device__ __forceinline__ void add3x3(double* p, size_t ld, M3<double> a) {
+    p[0] += a.a00; p[1] += a.a01; p[2] += a.a02;
+    p[ld] += a.a10; p[ld + 1] += a.a11; p[ld + 2] += a.a12;
+    p[2 * ld] += a.a20; p[2 * ld + 1] += a.a21; p[2 * ld + 2] += a.a22;
+}
+
+// dense_nodes_kernel with S_e = A_e^T Omega0_e A_e: diagonal blocks and right-hand side in the CSR order of the node's edge ends
+__global__ __launch_bounds__(64) void dense_info_nodes_kernel(const double* __restrict__ Hd, const double* __restrict__ Ho,
+                                                               const double* __restrict__ rhs_chain, const double* __restrict__ vo,
+                                                               const double* __restrict__ info_vo, const int64_t* __restrict__ node_ptr,
+                                                               const int64_t* __restrict__ node_adj, int N, int E,
+                                                               double* __restrict__ A, double* __restrict__ rhs) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= N) return;
+    const size_t ld = (size_t)9 * N;
+    const M3<double> Z{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    M3<double> Srr = Z, Srp = Z, Spp = Z;
+    V3<double> gr{0, 0, 0}, gp{0, 0, 0};
+    for (int64_t a = node_ptr[k]; a < node_ptr[k + 1]; ++a) {
+        const int64_t code = node_adj[a];
+        const InfoVo en = edge_info_normal(vo, info_vo, E, (int)(code >> 1));
+        Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
+        if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
+    }
+    double* d = A + (size_t)9 * k * ld + 9 * k;
+#pragma unroll
+    for (int r = 0; r < 9; ++r)
+#pragma unroll
+        for (int c = 0; c < 9; ++c) d[r * ld + c] = Hd[(size_t)k * 81 + r * 9 + c];
+    add3x3(d, ld, Srr); add3x3(d + 3, ld, Srp); add3x3(d + 3 * ld, ld, transpose(Srp)); add3x3(d + 3 * ld + 3, ld, Spp);
+    const double* rc = rhs_chain + (size_t)k * 9;
+    double* b = rhs + (size_t)k * 9;
+    b[0] = rc[0] - gr.x; b[1] = rc[1] - gr.y; b[2] = rc[2] - gr.z;
+    b[3] = rc[3] - gp.x; b[4] = rc[4] - gp.y; b[5] = rc[5] - gp.z;
+    b[6] = rc[6]; b[7] = rc[7]; b[8] = rc[8];
+    if (k < N - 1) {
+        double* up = A + (size_t)9 * k * ld + 9 * (k + 1);
+        double* lo = A + (size_t)9 * (k + 1) * ld + 9 * k;
+#pragma unroll
+        for (int r = 0; r < 9; ++r)
+#pragma unroll
+            for (int c = 0; c < 9; ++c) {
+                const double v = Ho[(size_t)k * 81 + r * 9 + c];
+                up[r * ld + c] = v;
+                lo[c * ld + r] = v;
+            }
+    }
+}
+
+// dense_edges_kernel with -A_e^T Omega0_e A_e: atomics, because two edges may share a node pair
+__device__ __forceinline__ void sub3x3_atomic(double* ij, double* ji, size_t ld, M3<double> a) {
+    atomicAdd(&ij[0], -a.a00); atomicAdd(&ij[1], -a.a01); atomicAdd(&ij[2], -a.a02);
+    atomicAdd(&ij[ld], -a.a10); atomicAdd(&ij[ld + 1], -a.a11); atomicAdd(&ij[ld + 2], -a.a12);
+    atomicAdd(&ij[2 * ld], -a.a20); atomicAdd(&ij[2 * ld + 1], -a.a21); atomicAdd(&ij[2 * ld + 2], -a.a22);
+    atomicAdd(&ji[0], -a.a00); atomicAdd(&ji[ld], -a.a01); atomicAdd(&ji[2 * ld], -a.a02);
+    atomicAdd(&ji[1], -a.a10); atomicAdd(&ji[ld + 1], -a.a11); atomicAdd(&ji[2 * ld + 1], -a.a12);
+    atomicAdd(&ji[2], -a.a20); atomicAdd(&ji[ld + 2], -a.a21); atomicAdd(&ji[2 * ld + 2], -a.a22);
+}
+__global__ __launch_bounds__(64) void dense_info_edges_kernel(const double* __restrict__ vo, const double* __restrict__ info_vo,
+                                                               const int64_t* __restrict__ edges, int N, int E, double* __restrict__ A) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= E) return;
+    const int64_t i = edges[2 * e], j = edges[2 * e + 1];
+    if (i == j) return;
+    const InfoVo en = edge_info_normal(vo, info_vo, E, e);
+    const size_t ld = (size_t)9 * N;
+    double* ij = A + (size_t)9 * i * ld + 9 * j;          // block (i, j) -= S, block (j, i) -= S^T
+    double* ji = A + (size_t)9 * j * ld + 9 * i;
+    sub3x3_atomic(ij, ji, ld, en.Srr);
+    sub3x3_atomic(ij + 3, ji + 3 * ld, ld, en.Srp);
+    sub3x3_atomic(ij + 3 * ld, ji + 3, ld, transpose(en.Srp));
+    sub3x3_atomic(ij + 3 * ld + 3, ji + 3 * ld + 3, ld, en.Spp);
+}
+
 __global__ __launch_bounds__(64) void vo_loss_fwd_kernel(const double* __restrict__ nodes, const int64_t* __restrict__ edges,
                                                           const double* __restrict__ poses, int E, double* __restrict__ err6,
                                                           double* __restrict__ tl, double* __restrict__ rl) {

@@ -141,6 +141,125 @@ __global__ __launch_bounds__(64) void build_normal_kernel(const double* __restri
 }
 
 // ------------------------------------------------------------------------------------------
+// Per-factor information matrices (pvgo.py:133-162 hands PyPose one matrix per factor).  Packed once per run:
+// info_vo (21, E) = the upper triangle of each 6x6 Omega0 in row-major order of the triangle, info_imu (18, M) = the 6-entry upper
+// triangles [00 01 02 11 12 22] of [velocity | rotation | translation-velocity]; both component-major like `lin`, so a wavefront's
+// loads coalesce.  Everything below stays in M3 / V3 values: no per-lane array, no scratch.
+__device__ __forceinline__ M3<double> sym3_ld(const double* __restrict__ p, size_t ld) {
+    const double a = p[0], b = p[ld], c = p[2 * ld], d = p[3 * ld], e = p[4 * ld], f = p[5 * ld];
+    return {a, b, c, b, d, e, c, e, f};
+}
+__device__ __forceinline__ M3<double> sym_part(M3<double> a) { return 0.5 * (a + transpose(a)); }
+
+// A^T Omega0 A and A^T Omega0 e of one VO factor, A = [[G, C],[0, G]], from the 3x3 blocks of Omega0 = [[Waa, Wab],[Wab^T, Wbb]]
+// (entry c of the packed triangle at w[c * ld]).  The two diagonal blocks are symmetrised: X^T (W X) is symmetric only up to rounding.
+struct InfoVo { M3<double> Srr, Srp, Spp; V3<double> gr, gp; };
+__device__ __forceinline__ InfoVo info_vo_normal(const double* __restrict__ w, size_t ld, M3<double> G, M3<double> C, V3<double> er,
+                                                 V3<double> ep) {
+    const M3<double> Waa{w[0], w[ld], w[2 * ld], w[ld], w[6 * ld], w[7 * ld], w[2 * ld], w[7 * ld], w[11 * ld]};
+    const M3<double> Wab{w[3 * ld], w[4 * ld], w[5 * ld], w[8 * ld], w[9 * ld], w[10 * ld], w[12 * ld], w[13 * ld], w[14 * ld]};
+    const M3<double> Wbb = sym3_ld(w + 15 * ld, ld);
+    const M3<double> Gt = transpose(G), Ct = transpose(C), Wba = transpose(Wab);
+    const M3<double> X1 = Waa * G, X2 = Waa * C + Wab * G;          // (Omega0 A) top row
+    const M3<double> X4 = Wba * C + Wbb * G;                        // (Omega0 A) bottom right
+    const V3<double> u = Waa * er + Wab * ep, v = Wba * er + Wbb * ep;
+    InfoVo o;
+    o.Srr = sym_part(Gt * X1);
+    o.Srp = Gt * X2;
+    o.Spp = sym_part(Ct * X2 + Gt * X4);
+    o.gr = Gt * u;
+    o.gp = Ct * u + Gt * v;
+    return o;
+}
+
+struct InfoLink {         // per-link normal-equation pieces under information matrices
+    M3<double> Srr, Srp, Spp;   // pose-pose block S
+    M3<double> W1, W3;          // Omega1, Omega3
+    V3<double> gr, gp;          // pose gradient
+    V3<double> g1, g3;          // Omega1 rv, Omega3 rt
+};
+
+// info_vo == nullptr: no VO group (the general-topology callers add the VO factors per edge themselves)
+__device__ __forceinline__ InfoLink info_link(const double* __restrict__ lin, int M, int k, const double* __restrict__ info_vo,
+                                              const double* __restrict__ info_imu) {
+    const double* r = lin + k;
+    const size_t ld = (size_t)M;
+    auto v3at = [&](int c) { return V3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]}; };
+    auto m3at = [&](int c) {
+        return M3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld], r[(c + 3) * ld], r[(c + 4) * ld], r[(c + 5) * ld],
+                          r[(c + 6) * ld], r[(c + 7) * ld], r[(c + 8) * ld]};
+    };
+    const M3<double> B = m3at(27);
+    const V3<double> eR = v3at(24), rv = v3at(36), rt = v3at(39);
+    const double* wi = info_imu + k;
+    const M3<double> W2 = sym3_ld(wi + 6 * ld, ld);
+    InfoLink o;
+    o.W1 = sym3_ld(wi, ld);
+    o.W3 = sym3_ld(wi + 12 * ld, ld);
+    const M3<double> W2B = W2 * B;
+    o.Srr = o.W3;
+    o.Spp = sym_part(transpose(B) * W2B);
+    o.g1 = o.W1 * rv;
+    o.g3 = o.W3 * rt;
+    o.gr = o.g3;
+    o.gp = tmul(W2B, eR);                                           // B^T Omega2 er (Omega2 symmetric)
+    if (info_vo) {
+        const InfoVo q = info_vo_normal(info_vo + k, ld, m3at(6), m3at(15), v3at(0), v3at(3));
+        o.Srr = o.Srr + q.Srr; o.Srp = q.Srp; o.Spp = o.Spp + q.Spp;
+        o.gr = o.gr + q.gr; o.gp = o.gp + q.gp;
+    } else {
+        o.Srp = M3<double>{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    return o;
+}
+
+// build_normal_kernel with one information matrix per factor: A = sum J^T Omega J, rhs = -sum J^T Omega r, the same gather (link k-1,
+// then link k), the same clamp.  A closed gate makes it a no-op (the LM loop enqueues it behind linbuild_kernel / trial_lin_kernel,
+// over the buffers that launch filled).
+__global__ __launch_bounds__(64) void info_build_kernel(const double* __restrict__ lin, const double* __restrict__ dts, int N,
+                                                         const double* __restrict__ info_vo, const double* __restrict__ info_imu,
+                                                         double vmin, double vmax, double* __restrict__ Hd, double* __restrict__ Ho,
+                                                         double* __restrict__ rhs, Gate gate) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= N || gate_closed(gate)) return;
+    const int M = N - 1;
+    const M3<double> Z{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    M3<double> Hrr = Z, Hrp = Z, Hpp = Z, Hvv = Z, Hrv = Z;
+    V3<double> gr{0, 0, 0}, gp{0, 0, 0}, gv{0, 0, 0};
+    if (k > 0) {                       // link k-1, this node is its "j" end
+        const InfoLink L = info_link(lin, M, k - 1, info_vo, info_imu);
+        Hrr = Hrr + L.Srr; Hrp = Hrp + L.Srp; Hpp = Hpp + L.Spp;
+        gr = gr + L.gr; gp = gp + L.gp;
+        gv = gv - L.g1;
+        Hvv = Hvv + L.W1;
+    }
+    if (k < M) {                       // link k, this node is its "i" end
+        const InfoLink L = info_link(lin, M, k, info_vo, info_imu);
+        const double dt = dts[k];
+        Hrr = Hrr + L.Srr; Hrp = Hrp + L.Srp; Hpp = Hpp + L.Spp;
+        gr = gr - L.gr; gp = gp - L.gp;
+        gv = gv + L.g1 - dt * L.g3;
+        Hvv = Hvv + L.W1 + (dt * dt) * L.W3;
+        Hrv = dt * L.W3;
+        double* o = Ho + (size_t)k * 81;
+        put3x3(o, 0, 0, -1.0 * L.Srr); put3x3(o, 0, 3, -1.0 * L.Srp); put3x3(o, 0, 6, Z);
+        put3x3(o, 3, 0, -1.0 * transpose(L.Srp)); put3x3(o, 3, 3, -1.0 * L.Spp); put3x3(o, 3, 6, Z);
+        put3x3(o, 6, 0, -1.0 * Hrv); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, -1.0 * L.W1);
+    }
+    const auto clamp = [&](double v) { return fmin(fmax(v, vmin), vmax); };      // A.diagonal().clamp_(min, max)
+    Hrr.a00 = clamp(Hrr.a00); Hrr.a11 = clamp(Hrr.a11); Hrr.a22 = clamp(Hrr.a22);
+    Hpp.a00 = clamp(Hpp.a00); Hpp.a11 = clamp(Hpp.a11); Hpp.a22 = clamp(Hpp.a22);
+    Hvv.a00 = clamp(Hvv.a00); Hvv.a11 = clamp(Hvv.a11); Hvv.a22 = clamp(Hvv.a22);
+    double* h = Hd + (size_t)k * 81;
+    put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, Hrv);
+    put3x3(h, 3, 0, transpose(Hrp)); put3x3(h, 3, 3, Hpp); put3x3(h, 3, 6, Z);
+    put3x3(h, 6, 0, Hrv); put3x3(h, 6, 3, Z); put3x3(h, 6, 6, Hvv);
+    double* b = rhs + (size_t)k * 9;
+    b[0] = -gr.x; b[1] = -gr.y; b[2] = -gr.z; b[3] = -gp.x; b[4] = -gp.y; b[5] = -gp.z;
+    b[6] = -gv.x; b[7] = -gv.y; b[8] = -gv.z;
+}
+
+// ------------------------------------------------------------------------------------------
 // Sparse reprojection factor (pvgo.py:53-61 + dense_ba.py:276-305).  Link k: T = C^-1 (X_k^-1 X_{k+1}) C,
 // err_j = pixel(K, T^-1 P_j) - target_j.  Under the left perturbation T <- Exp(eta) T:  d p'/d eta = R_T^T [-I, [P]x], so
 // with a = (f/z) R^T[row] - (f c/z^2) R^T[2]:  d err / d eta = [-a, a x P].  Node perturbations enter through

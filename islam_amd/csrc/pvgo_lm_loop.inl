@@ -1,5 +1,5 @@
 // pvgo_lm_loop.inl -- part of the pvgo.hip translation unit (textually included there; not compiled on its own).
-// The host loops of islam_pvgo_run_chain[_reproj|_robust] (reference pvgo.py:168-180): run_chain_impl sets a ChainRun up and picks one
+// The host loops of islam_pvgo_run_chain[_reproj|_robust|_info] (reference pvgo.py:168-180): run_chain_impl sets a ChainRun up and picks one
 // of three drivers -- run_fused (trial_elim_kernel), run_small (the whole loop in one launch), run_staged (a launch per stage).
 // All of them run ahead of the device behind the epoch gate and only poll the pinned verdicts.
 
@@ -21,6 +21,7 @@ struct ChainRun {
     int fz_m, fz_P, fz_nwg;                 // level 0 as trial_elim_kernel takes it: segment length, segments, workgroups
     VerdictBlock vb;
     const islam_pvgo_reproj* reproj; ReprojDev rp; const RobustDev* robust;      // optional factors / kernels (nullptr: none)
+    const double *info_vo, *info_imu;       // per-factor information, packed (21, N-1) / (18, N-1); both nullptr: the scalars of prm->w
     islam_pvgo_result* result; double* trace; int trace_cap;
     LinBufs lin(int b) const { return LinBufs{LIN[b], HD[b], HO[b], RH[b]}; }
     int* eflag_none() const { return w.flags + 6; }            // a word nobody sets
@@ -38,11 +39,20 @@ static ChainRun chain_run(double* nodes, double* vels, const ChainData& d, const
     return r;
 }
 
+// Per-factor information: directly behind a linbuild_kernel / trial_lin_kernel launch, under that launch's
+// gate, info_build_kernel overwrites HD[b], HO[b], RH[b] from the LIN[b] it just wrote.  The stored diagonal stays undamped.
+static void enqueue_info_build(const ChainRun& r, int b, Gate gate) {
+    if (!r.info_imu) return;
+    hipLaunchKernelGGL(info_build_kernel, dim3((r.d.N + 63) / 64), dim3(64), 0, r.s, r.LIN[b], r.d.dts, r.d.N, r.info_vo, r.info_imu, r.W.vmin,
+                       r.W.vmax, r.HD[b], r.HO[b], r.RH[b], gate);
+}
+
 // red_ready: RED[b] already holds the reduction at (xn)
 static void enqueue_linbuild(const ChainRun& r, const double* xn, const double* xv, int b, bool red_ready) {
     if (r.reproj && !red_ready) enqueue_reproj_reduce(xn, nullptr, r.d.N - 1, r.rp, r.RED[b], r.s);
     launch_linbuild(xn, xv, r.d, r.W, r.lin(b), r.w.loss_part, r.reproj ? r.RED[b] : (const double*)nullptr, r.rp, Gate{nullptr, 0.0}, r.robust,
                     r.s);
+    enqueue_info_build(r, b, Gate{nullptr, 0.0});
 }
 
 // trial `seq` of iteration c (cur + dx -> tri) and the linearisation at the trial point into buffer 1 - c.pb
@@ -67,6 +77,7 @@ static int enqueue_iter(const ChainRun& r, const IterCfg& c, double seq, double 
     // the next linearisation if the trial is accepted
     if (r.reproj) enqueue_reproj_reduce(c.cur_n, w.dx, r.d.N - 1, r.rp, r.RED[1 - c.pb], r.s, gate);
     launch_trial_lin(r, c, seq, gate);
+    enqueue_info_build(r, 1 - c.pb, gate);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
@@ -108,7 +119,7 @@ static int enqueue_upper_levels(const ChainRun& r, const SolvePlan& sp, Gate gat
 
 // ---- the fused loop (default): trial t, the linearisation at its trial point and the level-0 elimination of solve t+1 in
 // ONE launch (trial_elim_kernel), under a speculated damping the deciding workgroup validates.  Plans it does not cover
-// (one-sided levels, segments longer than FZ_MAXM, a single level), the reprojection factor, robust kernels and
+// (one-sided levels, segments longer than FZ_MAXM, a single level), the reprojection factor, robust kernels, per-factor information and
 // ISLAM_PVGO_NO_FUSE=1 take the launch-per-stage loop below.
 static int run_fused(ChainRun& r, const SolvePlan& sp, int fz_nwg) {
     const Workspace& w = r.w;
@@ -251,10 +262,12 @@ static int run_staged(ChainRun& r) {
 // setup, the choice of the driver, the call
 static int run_chain_impl(double* nodes, double* vels, const ChainData& d, const islam_pvgo_params* prm, const islam_pvgo_reproj* reproj,
                           const ReprojDev& rp, const Workspace& w, hipStream_t s, islam_pvgo_result* result, double* trace, int trace_cap,
-                          const RobustDev* robust) {
+                          const RobustDev* robust, const double* info_vo = nullptr, const double* info_imu = nullptr) {
     const int N = d.N;
     ChainRun r = chain_run(nodes, vels, d, prm, w, s);
     r.reproj = reproj; r.rp = rp; r.robust = robust; r.result = result; r.trace = trace; r.trace_cap = trace_cap;
+    r.info_vo = info_vo; r.info_imu = info_imu;
+    const bool info = info_imu != nullptr;         // information lives in the launch-per-stage loop only
     int rc = r.vb.acquire();
     if (rc != ISLAM_OK) return rc;
     // device state and flags (flags[0] solver error, flags[2] ticket) initialised by a one-wave kernel: a host->device copy of a
@@ -271,7 +284,7 @@ static int run_chain_impl(double* nodes, double* vels, const ChainData& d, const
     // (small graphs -- the reference's own per-batch problem is 9 nodes, run_kitti.sh -- stay on the launch-per-stage loop: its launches
     // are cheaper than the fused kernel's fixed cost and a rejected trial costs no mis-speculated chain.  Measured per run_pvgo, fused /
     // launch-per-stage: N = 9 (18 trials) 1059 / 723 us, N = 65 206 / 190 us, N = 129 203 / 236 us, N = 513 443 / 508 us.)
-    const bool fused = !no_fuse && !reproj && !robust && N > 96 && sp.nl >= 2 && fused_plan_core(sp, sp.lv[0].P, fz_nwg) &&
+    const bool fused = !no_fuse && !reproj && !robust && !info && N > 96 && sp.nl >= 2 && fused_plan_core(sp, sp.lv[0].P, fz_nwg) &&
                        prm->reject < STATE_DOUBLES - STATE_HIST - 1;
     if (fused) return run_fused(r, sp, fz_nwg);
     enqueue_linbuild(r, nodes, vels, 0, false);
@@ -280,6 +293,6 @@ static int run_chain_impl(double* nodes, double* vels, const ChainData& d, const
     // (one wave eliminates the window's nodes one after the other, ~2 us each: beyond a couple of dozen nodes the level tree of the
     // launch-per-stage loop is faster -- N = 65 takes 190 us per run there)
     constexpr int SMALL_MAX_N = 16;
-    if (!no_small && !reproj && !robust && N <= SMALL_MAX_N) return run_small(r);
+    if (!no_small && !reproj && !robust && !info && N <= SMALL_MAX_N) return run_small(r);
     return run_staged(r);
 }

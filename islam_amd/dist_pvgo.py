@@ -143,7 +143,9 @@ class ShardedChainPVGO:
     """run_pvgo's LM loop (pvgo.py:168-180) on one chain graph split over ``world`` ranks."""
 
     def __init__(self, init_nodes, init_vels, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, seg_len=(0, 0),
-                 group=None, backend=None, rank=None, world=None):
+                 group=None, backend=None, rank=None, world=None, info=None):
+        if info is not None:
+            raise NotImplementedError('per-factor information (info) on the sharded loop is not implemented')
         import torch.distributed as dist
         self.dist = dist
         self.group = group
@@ -294,10 +296,12 @@ class RcclComm:
 
 
 def run_chain_sharded(comm, init_nodes, init_vels, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, seg_len=(0, 0), rank=None,
-                      world=None, allreduce_cb=None, params=None, reproj=None):
+                      world=None, allreduce_cb=None, params=None, reproj=None, info=None):
     """islam_pvgo_run_chain_sharded: the sharded LM loop inside the library.  ``comm``: an RcclComm (or None with world 1);
     ``allreduce_cb``: a ctypes callback instead of RCCL (tests); ``reproj``: the sparse
     reprojection factor (ops.pvgo_reproj_struct), as in ops.pvgo_run_chain.  Returns (nodes, vels, result, bytes handed to the collectives)."""
+    if info is not None:
+        raise NotImplementedError('per-factor information (info) on the sharded loop is not implemented')
     from . import ops
     from ._lib import PvgoResult, c_size_t, check, lib, ptr, stream_ptr
     dev = init_nodes.device

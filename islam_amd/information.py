@@ -1,0 +1,150 @@
+"""Per-factor information matrices of the PVGO LM (``run_pvgo(info=PvgoInfo(...))``).
+
+The reference hands PyPose one information matrix per factor (pvgo.py:133-162 stacks (E,6,6) and (M,3,3) tensors, :178 passes them
+as ``weight=``) and only ever fills them with ``loss_weight[g]**2 * I``.  A PvgoInfo carries a real matrix per factor:
+A = sum_k J_k^T Omega_k J_k, b = -sum_k J_k^T Omega_k r_k.  Factor groups, in the order of ``loss_weight``:
+
+    g  group                  rows                        Omega
+    0  vo (pgerr)             6 per edge, [rho, phi]      (E,6,6)
+    1  vel                    3 per link                  (M,3,3)
+    2  rot (IMU rotation)     3 per link                  (M,3,3)
+    3  transvel               3 per link                  (M,3,3)
+
+Every Omega is symmetric positive SEMI-definite: Omega_k = 0 switches factor k off (the LM's diagonal clamp keeps A positive
+definite).  The accept-test loss and the trust-region term stay unweighted, as they are under scalar weights."""
+import numpy as np
+import torch
+
+_GROUPS = (('vo', 6), ('vel', 3), ('rot', 3), ('transvel', 3))
+_TRIU = {k: np.triu_indices(k) for k in (3, 6)}
+
+
+def _as_matrices(name, x, k, n=None):
+    """(n,) scalars, (n,k) diagonals or (n,k,k) matrices -> (n,k,k) float64 numpy, symmetrised."""
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 1:
+        out = a[:, None, None] * np.eye(k)
+    elif a.ndim == 2 and a.shape[1] == k:
+        out = np.zeros((a.shape[0], k, k))
+        out[:, np.arange(k), np.arange(k)] = a
+    elif a.ndim == 3 and a.shape[1:] == (k, k):
+        out = 0.5 * (a + np.swapaxes(a, 1, 2))
+    else:
+        raise ValueError('PvgoInfo.%s: expected (n,), (n,%d) or (n,%d,%d), got shape %s' % (name, k, k, k, a.shape))
+    if n is not None and out.shape[0] != n:
+        raise ValueError('PvgoInfo.%s: %d factors given, the graph has %d' % (name, out.shape[0], n))
+    return out
+
+
+def _validate(name, m):
+    bad = ~np.isfinite(m).all(axis=(1, 2))
+    if bad.any():
+        raise ValueError('PvgoInfo.%s: factor %d has a non-finite entry' % (name, int(np.argmax(bad))))
+    if m.shape[0] == 0:
+        return
+    ev = np.linalg.eigvalsh(m)
+    bad = ev[:, 0] < -1e-12 * np.maximum(ev[:, -1], 0.0)
+    bad |= ev[:, -1] < 0.0
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError('PvgoInfo.%s: factor %d is not positive semi-definite (eigenvalues %g .. %g)' % (name, i, ev[i, 0], ev[i, -1]))
+
+
+class PvgoInfo:
+    """One information matrix per factor.  Each of ``vo`` (6x6 per edge), ``vel``, ``rot``, ``transvel`` (3x3 per link) is None
+    (``loss_weight[g]**2 * I``, filled in by run_pvgo), (n,) scalars per factor, (n,k) diagonals or (n,k,k) full matrices (symmetrised
+    as (O + O^T) / 2); numpy arrays or tensors.  validate: check finiteness and, on the host, smallest eigenvalue >= -1e-12 x largest;
+    a violation raises ValueError naming the group and the first offending factor."""
+
+    def __init__(self, vo=None, vel=None, rot=None, transvel=None, validate=True):
+        given = dict(vo=vo, vel=vel, rot=rot, transvel=transvel)
+        for name, k in _GROUPS:
+            m = None if given[name] is None else _as_matrices(name, given[name], k)
+            if m is not None and validate:
+                _validate(name, m)
+            setattr(self, name, m)
+
+    def matrices(self, E, M, loss_weight):
+        """The four groups as (E,6,6), (M,3,3) x 3 float64 numpy arrays, None filled with loss_weight[g]**2 * I."""
+        out = []
+        for g, (name, k) in enumerate(_GROUPS):
+            n = E if g == 0 else M
+            m = getattr(self, name)
+            if m is None:
+                m = np.broadcast_to(float(loss_weight[g]) ** 2 * np.eye(k), (n, k, k))
+            elif m.shape[0] != n:
+                raise ValueError('PvgoInfo.%s: %d factors given, the graph has %d' % (name, m.shape[0], n))
+            out.append(np.ascontiguousarray(m))
+        return out
+
+    def packed(self, E, M, loss_weight=(1, 1, 1, 1), device='cuda'):
+        """The device layout of the library (include/islam_hip.h, islam_pvgo_run_chain_info), float64, component-major:
+        info_vo (21,E) = the upper triangle of each 6x6 in row-major order of the triangle; info_imu (18,M) = the 6-entry upper
+        triangles of [vel | rot | transvel]."""
+        vo, vel, rot, tv = self.matrices(E, M, loss_weight)
+        r6, c6 = _TRIU[6]
+        r3, c3 = _TRIU[3]
+        info_vo = np.ascontiguousarray(vo[:, r6, c6].T)
+        info_imu = np.ascontiguousarray(np.concatenate([m[:, r3, c3].T for m in (vel, rot, tv)], 0))
+        return (torch.from_numpy(info_vo).to(device), torch.from_numpy(info_imu).to(device))
+
+    def covs(self, E, M, loss_weight):
+        """run_pvgo's ``covs`` dict under information: the per-factor mean of each block's diagonal (vo_trans rows 0-2, vo_rot 3-5)."""
+        vo, vel, rot, tv = self.matrices(E, M, loss_weight)
+        d = lambda m, lo, hi: np.diagonal(m, axis1=1, axis2=2)[:, lo:hi].mean(axis=1)
+        return {'vo_rot': d(vo, 3, 6), 'imu_rot': d(rot, 0, 3), 'vo_trans': d(vo, 0, 3), 'imu_vel': d(vel, 0, 3), 'transvel': d(tv, 0, 3)}
+
+    @classmethod
+    def from_imu_cov(cls, cov, rot=None, floor=0.0, vo=None):
+        """Information of the three IMU factors from the pre-integration covariances (IMUModule(prop_cov=True) /
+        ops.imu_preint_cov in motion mode).
+
+        cov (M,9,9): one covariance per link, error state [dphi, dv, dp].  rot (M,4): xyzw rotation of the START node of each link,
+        body -> the frame of ``imu_dvels`` / ``imu_dtrans`` (None: identity).  Returns a PvgoInfo with
+
+            rot      = (S_phiphi + floor I)^-1
+            vel      = (R S_vv R^T + floor I)^-1
+            transvel = (R S_pp R^T + floor I)^-1
+
+        Why: dphi is the right perturbation of the pre-integrated rotation dR, dR_true = dR Exp(dphi), and PVGO's rotation residual
+        Log(dR^-1 R_i^-1 R_j) is exactly that perturbation to first order, so S_phiphi is its covariance as it stands.  dv and dp
+        live in the body frame of the link's start; the velocity and translation-velocity residuals are written in the frame of
+        imu_dvels / imu_dtrans, so their covariances are rotated by R.  The cross blocks (phi-v, phi-p, v-p) are dropped: PVGO's three
+        IMU factors are separate residuals (a correlated 9-row factor is out of scope).  ``vo`` is passed through.
+
+        A block that is not positive definite raises ValueError naming the frame and suggesting ``floor``; a frame without samples has
+        S = 0 and triggers this."""
+        c = cov.detach().cpu().numpy() if isinstance(cov, torch.Tensor) else np.asarray(cov)
+        c = np.asarray(c, dtype=np.float64)
+        if c.ndim != 3 or c.shape[1:] != (9, 9):
+            raise ValueError('from_imu_cov: cov must be (M,9,9), got %s' % (c.shape,))
+        Mn = c.shape[0]
+        if rot is None:
+            R = np.broadcast_to(np.eye(3), (Mn, 3, 3))
+        else:
+            from . import lietensor as pp
+            q = pp._plain(rot) if isinstance(rot, torch.Tensor) else torch.as_tensor(np.asarray(rot))
+            q = q.detach().cpu().double().numpy()
+            if q.shape != (Mn, 4):
+                raise ValueError('from_imu_cov: rot must be (%d,4) xyzw, got %s' % (Mn, q.shape))
+            x, y, z, w = (q / np.linalg.norm(q, axis=1, keepdims=True)).T
+            R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                          2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                          2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1).reshape(Mn, 3, 3)
+        I3 = float(floor) * np.eye(3)
+        out = {}
+        for name, lo, rotate in (('rot', 0, False), ('vel', 3, True), ('transvel', 6, True)):
+            S = c[:, lo:lo + 3, lo:lo + 3]
+            S = 0.5 * (S + np.swapaxes(S, 1, 2))
+            if rotate:
+                S = R @ S @ np.swapaxes(R, 1, 2)
+            S = S + I3
+            ev = np.linalg.eigvalsh(S) if Mn else np.zeros((0, 3))
+            bad = ~np.isfinite(ev).all(axis=1) | (ev[:, 0] <= 1e-14 * np.maximum(ev[:, -1], 0.0))
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise ValueError('from_imu_cov: the %s covariance of frame %d is not positive definite (smallest eigenvalue %g; a frame '
+                                 'without IMU samples has zero covariance): pass floor > 0' % (name, i, ev[i, 0]))
+            out[name] = np.linalg.inv(S)
+        return cls(vo=vo, validate=True, **out)

@@ -1091,12 +1091,26 @@ def pvgo_reproj_reduce(nodes, reproj, dx=None):
     return red
 
 
-def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, workspace=None, trace_cap=0, reproj=None, robust=None):
+def _info_pair(info, E, M):
+    """(info_vo (21,E) or None, info_imu (18,M) or None) of a packed pair, checked."""
+    info_vo, info_imu = info
+    require_cuda(info_vo, info_imu)
+    for t, shape, name in ((info_vo, (21, E), 'info_vo'), (info_imu, (18, M), 'info_imu')):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError('%s: a contiguous float64 %s tensor expected, got %s %s' % (name, shape, t.dtype, tuple(t.shape)))
+    return info_vo, info_imu
+
+
+def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, workspace=None, trace_cap=0, reproj=None, robust=None, info=None):
     """In-place LM on float64 device tensors.  Returns (PvgoResult, trace ndarray (trials,3) or None).
-    robust: islam_amd.robust.RobustSpec (or None) -- islam_pvgo_run_chain_robust; not combinable with ``reproj``."""
+    robust: islam_amd.robust.RobustSpec (or None) -- islam_pvgo_run_chain_robust; not combinable with ``reproj``.
+    info: (info_vo (21,N-1), info_imu (18,N-1)), the packed per-factor information (PvgoInfo.packed) -- islam_pvgo_run_chain_info;
+    not combinable with ``reproj`` or ``robust``."""
     require_cuda(nodes, vels, poses, drots, dtrans, dvels, dts)
     if robust is not None and reproj is not None:
         raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
+    if info is not None and (robust is not None or reproj is not None):
+        raise NotImplementedError('per-factor information with robust kernels or the reprojection factor is not implemented')
     for t in (nodes, vels, poses, drots, dtrans, dvels, dts):
         assert t.dtype == torch.float64 and t.is_contiguous()
     N = nodes.shape[0]
@@ -1108,7 +1122,12 @@ def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, worksp
     res = _lib.PvgoResult()
     trace = np.zeros((trace_cap, 3), dtype=np.float64) if trace_cap > 0 else None
     tp = trace.ctypes.data_as(c_void_p) if trace is not None else c_void_p(0)
-    if robust is not None:
+    if info is not None:
+        info_vo, info_imu = _info_pair(info, N - 1, N - 1)
+        check(lib().islam_pvgo_run_chain_info(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
+                                              ctypes.byref(params), ptr(info_vo), ptr(info_imu), ptr(ws), c_size_t(nbytes),
+                                              ctypes.byref(res), tp, trace_cap, stream_ptr(nodes.device)))
+    elif robust is not None:
         check(lib().islam_pvgo_run_chain_robust(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
                                                 ctypes.byref(params), ctypes.byref(robust.struct()), ptr(ws), c_size_t(nbytes),
                                                 ctypes.byref(res), tp, trace_cap, stream_ptr(nodes.device)))
@@ -1146,6 +1165,22 @@ def pvgo_build_normal(lin, dts, N, w4, vmin=1e-4, vmax=1e32, c_imu=None):
         return Hd, Ho, rhs
     check(lib().islam_pvgo_build_normal(ptr(lin), ptr(dts), N, w, c_double(vmin), c_double(vmax), ptr(Hd), ptr(Ho),
                                         ptr(rhs), stream_ptr(dev)))
+    return Hd, Ho, rhs
+
+
+def pvgo_build_normal_info(lin, dts, N, info_vo, info_imu, vmin=1e-4, vmax=1e32):
+    """islam_pvgo_build_normal_info: the chain normal equations under per-factor information, packed as PvgoInfo.packed gives it --
+    info_vo (21,N-1) or None (no VO group), info_imu (18,N-1).  Returns (Hd (N,9,9), Ho (N,9,9), rhs (N,9))."""
+    require_cuda(lin, dts)
+    dev = lin.device
+    if info_imu is None:
+        raise ValueError('pvgo_build_normal_info: info_imu is required')
+    info_vo, info_imu = _info_pair((info_vo, info_imu), N - 1, N - 1)
+    Hd = torch.zeros((N, 9, 9), dtype=torch.float64, device=dev)
+    Ho = torch.zeros((N, 9, 9), dtype=torch.float64, device=dev)
+    rhs = torch.zeros((N, 9), dtype=torch.float64, device=dev)
+    check(lib().islam_pvgo_build_normal_info(ptr(lin), ptr(dts), N, ptr(info_vo), ptr(info_imu), c_double(vmin), c_double(vmax), ptr(Hd),
+                                             ptr(Ho), ptr(rhs), stream_ptr(dev)))
     return Hd, Ho, rhs
 
 

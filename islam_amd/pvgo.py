@@ -11,6 +11,8 @@ The information matrices of pvgo.py:125-143 are scalar multiples of the identity
 the optional sparse reprojection factor ``reproj``, islam_amd/dense_ba.py).
 ``kernel`` (islam_amd.robust.Huber / Cauchy, one for all four factor groups or a sequence of four) puts robust kernels on the LM,
 like PyPose's ``pp.optim.LM(kernel=...)``; None keeps the plain least-squares loop.
+``info`` (islam_amd.information.PvgoInfo) gives every factor its own information matrix instead; None keeps
+the four scalars.
 """
 import numpy as np
 import torch
@@ -78,12 +80,30 @@ class PvgoMarginals(_Marginals):
         self.status = status             # (run_pvgo: device int32 ISLAM_OK / ISLAM_ENOTPD of the stream-ordered call)
 
 
-def _marginals_at(nodes, vels, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, seg_len=(0, 0), status=None):
-    """A = J^T W J at (nodes, vels) -- undamped, unclamped, + the reprojection factor's node blocks -- and its selected inverse."""
+def _packed_info(info, E, M, loss_weight, dev, reproj=None, kernel=None):
+    """The argument checks of ``info`` (before any device work) and its packed device form; None stays None."""
+    if info is None:
+        return None
+    from .information import PvgoInfo
+    if not isinstance(info, PvgoInfo):
+        raise TypeError('info must be an islam_amd.information.PvgoInfo or None, got %s' % type(info).__name__)
+    if kernel is not None:
+        raise NotImplementedError('per-factor information together with a robust kernel (info with kernel) is not implemented')
+    if reproj is not None:
+        raise NotImplementedError('per-factor information together with the reprojection factor (info with reproj) is not implemented')
+    return info.packed(E, M, loss_weight, dev)
+
+
+def _marginals_at(nodes, vels, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, seg_len=(0, 0), status=None, info=None):
+    """A = J^T W J at (nodes, vels) -- undamped, unclamped, + the reprojection factor's node blocks -- and its selected inverse.
+    info: the packed per-factor information (then A = sum J^T Omega J)."""
     N = nodes.shape[0]
     lin, _ = ops.pvgo_linearize(nodes, vels, poses, drots, dtrans, dvels, dts)
     w4 = [float(x) ** 2 for x in loss_weight[:4]]
-    Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, w4, vmin=0.0, vmax=float('inf'))
+    if info is not None:
+        Hd, Ho, rhs = ops.pvgo_build_normal_info(lin, dts, N, info[0], info[1], vmin=-1e300, vmax=float('inf'))
+    else:
+        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, w4, vmin=0.0, vmax=float('inf'))
     if rp is not None:
         from .pvgo_dense import _ReprojTerms
         _ReprojTerms(nodes, rp).add_to_chain(Hd, Ho, rhs)
@@ -96,16 +116,29 @@ def pvgo_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvel
     """Marginal covariances of the poses and velocities of a canonical chain (links[k] = [k, k+1], N-1 VO motions) at the given
     state: Sigma = A^-1 with A = J^T W J the undamped Gauss-Newton matrix of run_pvgo's graph (the PyPose-compatible Jacobians,
     the reprojection factor when ``reproj`` is given), the pose DoF of node ``anchor`` held fixed (None: no gauge fix).
+    (Under per-factor information: pvgo_marginals_info.)
     Returns a PvgoMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
+    return _chain_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight, reproj, anchor, None)
+
+
+def pvgo_marginals_info(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvels, info, loss_weight=(1, 1, 1, 1), anchor=0):
+    """pvgo_marginals under per-factor information: A = sum J^T Omega J with ``info`` a PvgoInfo, whose None
+    groups are ``loss_weight[g]**2 * I``.  With real information in every group the covariances are metric."""
+    return _chain_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight, None, anchor, info)
+
+
+def _chain_marginals(nodes, vels, vo_motions, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight, reproj, anchor, info):
     dev = pp._plain(torch.as_tensor(nodes)).device
     if dev.type != 'cuda':
         raise RuntimeError('islam_amd.pvgo_marginals runs on the MI355X only; there is no CPU fallback')
+    Nn = len(nodes)
+    packed = _packed_info(info, Nn - 1, Nn - 1, loss_weight, dev, reproj)
     n64, v64, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, nodes, vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     N = n64.shape[0]
     if poses.shape[0] != N - 1:
         raise UnsupportedGraphError('pvgo_marginals serves canonical chains: %d VO motions for %d nodes' % (poses.shape[0], N))
     return _marginals_at(n64, v64, poses, drots, dtrans, dvels, dts64.reshape(-1), loss_weight, _reproj_struct(reproj, loss_weight, dev),
-                         anchor)
+                         anchor, info=packed)
 
 
 class PvgoGraphMarginals(_Marginals):
@@ -120,7 +153,7 @@ class PvgoGraphMarginals(_Marginals):
         self.pairs, self.pair_cov = pairs, pair_cov
 
 
-def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, pairs):
+def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, pairs, info=None):
     from .pvgo_dense import marginals_dense
     N = nodes.shape[0]
     if N > _DENSE_MAX_NODES:
@@ -130,24 +163,26 @@ def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, lo
     pairs = pairs.detach().cpu() if isinstance(pairs, torch.Tensor) else torch.as_tensor(np.asarray(pairs))
     pairs = pairs.to(torch.int64).reshape(-1, 2)
     node_cov, pair_cov = marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=rp, anchor=anchor,
-                                         pairs=pairs)
+                                         pairs=pairs, info=info)
     return PvgoGraphMarginals(node_cov, pairs.to(nodes.device), pair_cov, anchor)
 
 
 def pvgo_marginals_general(nodes, vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight=(1, 1, 1, 1), reproj=None,
-                           anchor=0, pairs=None):
+                           anchor=0, pairs=None, info=None):
     """Marginal covariances of the poses and velocities of a graph with arbitrary ``links`` (loop closures; canonical chains too) at the
     given state: Sigma = A^-1 with A = J^T W J the undamped Gauss-Newton matrix of run_pvgo's graph, the pose DoF of node ``anchor``
     held fixed (None: no gauge fix).  Dense: the project's Cholesky, the inverse of its factor in place and the requested blocks
     (islam_amd.pvgo_dense.marginals_dense), N <= 12000.  pairs (P,2): the node pairs whose cross-covariance is wanted; None: ``links``.
+    info: a PvgoInfo (A = sum J^T Omega J; not with ``reproj``).
     Returns a PvgoGraphMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
     dev = pp._plain(torch.as_tensor(nodes)).device
     if dev.type != 'cuda':
         raise RuntimeError('islam_amd.pvgo_marginals_general runs on the MI355X only; there is no CPU fallback')
+    packed = _packed_info(info, len(links), len(nodes) - 1, loss_weight, dev, reproj)
     n64, v64, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, nodes, vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     edges = torch.as_tensor(links).to(dev, torch.int64).contiguous()
     return _graph_marginals_at(n64, v64, edges, poses, drots, dtrans, dvels, dts64.reshape(-1), loss_weight, _reproj_struct(reproj, loss_weight, dev),
-                               anchor, pairs)
+                               anchor, pairs, info=packed)
 
 
 _GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
@@ -155,10 +190,11 @@ _GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
 
 def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels,
              device='cuda:0', radius=1e4, loss_weight=(1, 1, 1, 1), reproj=None, target='vo', seg_len=(0, 0),
-             return_info=False, general_solver='auto', marginals=False, kernel=None):
+             return_info=False, general_solver='auto', marginals=False, kernel=None, info=None):
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError("islam_amd.run_pvgo runs on the MI355X only (device=%r); there is no CPU fallback" % (device,))
+    packed = _packed_info(info, len(links), len(init_nodes) - 1, loss_weight, dev, reproj, kernel)
     robust = None
     if kernel is not None:
         from .robust import parse_kernel
@@ -184,7 +220,7 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
 
     if chain:            # the topology train.py produces: block-tridiagonal fast path, whole LM loop in one library call
         prm = ops.pvgo_default_params(loss_weight, radius=radius, seg_len=seg_len)
-        res, _ = ops.pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts64, prm, reproj=rp, robust=robust)
+        res, _ = ops.pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts64, prm, reproj=rp, robust=robust, info=packed)
     else:                # loop closures / arbitrary links: dense formulation on the device (islam_amd/pvgo_dense.py)
         from .pvgo_dense import off_band_edges, run_lm_band_pcg, run_lm_dense
         k_off = len(off_band_edges(np.asarray(edges.cpu())))
@@ -196,9 +232,10 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
                                         'edges; general_solver="band_pcg" has no such limit)' % (_DENSE_MAX_NODES, N, k_off))
         lm_args = (nodes, vels, edges, poses, drots, dtrans, dvels, dts64, loss_weight)
         if how == 'band_pcg':
-            nodes, vels, res = run_lm_band_pcg(*lm_args, radius=radius, reproj=rp, kernel=robust)
+            nodes, vels, res = run_lm_band_pcg(*lm_args, radius=radius, reproj=rp, kernel=robust, info=packed)
         else:                    # 'dense_hip': the LM of 'dense' with the project's own Cholesky (csrc/dense_chol.hip)
-            nodes, vels, res = run_lm_dense(*lm_args, radius=radius, reproj=rp, kernel=robust, solver='hip' if how == 'dense_hip' else 'torch')
+            nodes, vels, res = run_lm_dense(*lm_args, radius=radius, reproj=rp, kernel=robust, solver='hip' if how == 'dense_hip' else 'torch',
+                                            info=packed)
 
     if target == 'vo':
         vo = vo_motions if isinstance(vo_motions, torch.Tensor) else torch.as_tensor(vo_motions)
@@ -218,10 +255,10 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     an, av = ops.pvgo_align(nodes, vels, target0)
     marg = None
     if marginals and not chain:     # general_solver='dense_hip': dense selected inverse at the aligned fp64 state, anchor 0, pairs = links
-        marg = _graph_marginals_at(an, av, edges, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, None)      # (the LM's matrix is gone)
+        marg = _graph_marginals_at(an, av, edges, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, None, info=packed)      # (the LM's matrix is gone)
     elif marginals:      # at the aligned fp64 state the caller receives; stream-ordered, its status rides on the host copy below
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        marg = _marginals_at(an, av, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, seg_len=seg_len, status=status)
+        marg = _marginals_at(an, av, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, seg_len=seg_len, status=status, info=packed)
     # ONE device -> host copy for everything the caller reads on the host: aligned poses, velocities and the two loss vectors (their
     # host values ride along as ``.host`` on the returned loss tensors, so that a caller that only wants to report the loss does not
     # pay another synchronising read: BilevelLoop.step)
@@ -243,6 +280,8 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     covs = {'vo_rot': np.ones(len(links)) * loss_weight[0] ** 2, 'imu_rot': np.ones(n1) * loss_weight[2] ** 2,
             'vo_trans': np.ones(len(links)) * loss_weight[0] ** 2, 'imu_vel': np.ones(n1) * loss_weight[1] ** 2,
             'transvel': np.ones(n1) * loss_weight[3] ** 2}
+    if info is not None:             # the keys stay; each entry is the per-factor mean of its block's diagonal
+        covs = info.covs(len(links), n1, loss_weight)
     if reproj is not None:
         covs['reproj'] = np.ones(n1) * (loss_weight[4] / reproj.N) ** 2                        # pvgo.py:202-203
     out = (trans_loss, rot_loss, nodes_out, vels_out, covs) + ((res,) if return_info else ()) + ((marg,) if marginals else ())

@@ -20,7 +20,12 @@ one linearisation, solve(d) -> the step (N,9) or None (failed), and ``extra`` en
 
 Robust kernels (``kernel``, an islam_amd.robust.RobustSpec): islam_pvgo_robust_weights gives the multiplier
 c = rho'(s) of every VO edge and IMU-side factor and the loss sum rho(s); the scaled assembly entry points and the trust-region
-term apply c per factor.  Every system uses the same multipliers and the same loss."""
+term apply c per factor.  Every system uses the same multipliers and the same loss.
+
+Per-factor information (``info``, the packed pair of islam_amd.information.PvgoInfo.packed): every system
+assembles A = sum J^T Omega J and b = -sum J^T Omega r instead -- islam_pvgo_build_normal_info for the IMU groups,
+islam_pvgo_assemble_dense_info or the per-edge blocks of _edge_blocks for the VO edges.  The loop, the loss and the trust-region term
+are the unweighted ones above."""
 import numpy as np
 import torch
 
@@ -41,11 +46,15 @@ def _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy_poses
 
 class _Graph:
     """What _run_lm and gauss_newton_matrix both set up (float64 contiguous device tensors, N nodes): w, the four squared loss weights, and
-    linearize(nodes, vels), with unit poses where islam_pvgo_linearize takes VO motions."""
+    linearize(nodes, vels), with unit poses where islam_pvgo_linearize takes VO motions.  info: None, or the packed per-factor
+    information (info_vo (21,E), info_imu (18,N-1)) of PvgoInfo.packed, which then replaces w in every assembly."""
 
-    def __init__(self, nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight):
+    def __init__(self, nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info=None):
         self.N, self.edges, self.dts, self.dev = nodes.shape[0], edges, dts, nodes.device
         self.w = [float(x) ** 2 for x in loss_weight[:4]]
+        self.info = info
+        if info is not None and tuple(info[0].shape) != (21, edges.shape[0]):
+            raise ValueError('info_vo: (21, %d) expected, got %s' % (edges.shape[0], tuple(info[0].shape)))
         dummy = torch.zeros((self.N - 1, 7), dtype=torch.float64, device=self.dev)
         dummy[:, 6] = 1.0
         self.linearize = lambda nodes, vels: _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
@@ -153,6 +162,11 @@ class _DenseSystem:
     def fill(self, vo, lin, rpt=None, c_vo=None, c_imu=None):
         """A (fully written) = J^T W J, undamped and unclamped, and b = -J^T W r.  rpt: _ReprojTerms; c_vo, c_imu: robust multipliers."""
         g, N, E, w = self.g, self.g.N, self.g.edges.shape[0], self.g.w
+        if g.info is not None:                          # per-factor information: no robust multipliers, no reprojection factor
+            Hd, Ho, rhs = ops.pvgo_build_normal_info(lin, g.dts, N, None, g.info[1], -_NOCLAMP, _NOCLAMP)                   # IMU factors
+            check(lib().islam_pvgo_assemble_dense_info(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(g.info[0]), ptr(g.edges), ptr(self.nptr),
+                                                       ptr(self.nadj), N, E, ptr(self.A), ptr(self.b), stream_ptr(g.dev)))
+            return
         Hd, Ho, rhs = ops.pvgo_build_normal(lin, g.dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
@@ -189,13 +203,15 @@ class _DenseHipSystem(_DenseSystem):
         return None if failed else D
 
 
-def gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None):
+def gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None, info=None):
     """A = J^T W J (9N x 9N, device, fully written) at (nodes, vels): undamped, unclamped, no gauge fixed -- what run_lm_dense assembles
     before it damps the diagonal.  The VO factors may sit on any number of edges (the assembly needs no E = N - 1; only the LM's loss
     does)."""
     if poses.shape[0] != edges.shape[0]:
         raise ValueError('one VO motion per edge: %d motions for %d edges' % (poses.shape[0], edges.shape[0]))
-    sysm = _DenseSystem(_Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight))
+    if info is not None and reproj is not None:
+        raise NotImplementedError('per-factor information with the reprojection factor is not implemented')
+    sysm = _DenseSystem(_Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info))
     vo, lin = sysm.g.linearize(nodes, vels)
     sysm.fill(vo, lin, _ReprojTerms(nodes, reproj) if reproj is not None else None)
     return sysm.A
@@ -214,7 +230,7 @@ def fix_gauge(A, anchor):
     return d
 
 
-def marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None, anchor=0, pairs=None):
+def marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None, anchor=0, pairs=None, info=None):
     """Marginal covariances of a general-topology graph at (nodes, vels): Sigma = A^-1, A the undamped, unclamped Gauss-Newton matrix
     run_lm_dense assembles (with the reprojection factor when ``reproj`` is given), the pose of node ``anchor`` held fixed.  The project's
     Cholesky factors A in place, the factor is inverted in place (csrc/dense_inverse.hip) and only the
@@ -224,7 +240,7 @@ def marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_w
     N = nodes.shape[0]
     if anchor is not None and not 0 <= int(anchor) < N:
         raise ValueError('anchor=%r is not a node of a graph of %d nodes' % (anchor, N))
-    A = gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj)
+    A = gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, info)
     d = fix_gauge(A, anchor)
     info = ops.dense_chol_factor(A, d)
     bad = int(info.item())                                              # the one read-back
@@ -268,33 +284,45 @@ def _run_lm(nodes, vels, g, sysm, reproj, kernel, radius, max_steps, patience, d
     return nodes, vels, dict(steps=ctl.steps, trials=trials, loss=ctl.loss, trace=ctl.trace, **sysm.extra)
 
 
-def _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver='torch'):
+def _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver='torch', info=None):
     """The host-side checks of the two entry points, in this order and before any device work, then the _Graph."""
     N, E = nodes.shape[0], edges.shape[0]
+    if info is not None and (kernel is not None or reproj is not None):
+        raise NotImplementedError('per-factor information with robust kernels or the reprojection factor is not implemented')
     if kernel is not None and reproj is not None:
         raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
     if solver not in ('torch', 'hip'):
         raise ValueError("solver must be 'torch' or 'hip'")
     if E != N - 1:
         raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, N - 1))
-    return _Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight)
+    return _Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info)
 
 
 def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
-                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, solver='torch'):
-    """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None.
+                 decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, solver='torch', info=None):
+    """In: float64 contiguous device tensors; reproj: ops.pvgo_reproj_struct or None; kernel: robust.RobustSpec or None; info: the
+    packed per-factor information (PvgoInfo.packed) or None.
     solver: 'torch' (torch.linalg.cholesky_ex / cholesky_solve: a second (9N)^2 matrix per trial) or 'hip' (islam_dense_chol_factor /
     _solve, csrc/dense_chol.hip: the damped diagonal goes in as a vector and the factor lands in A's lower triangle, no second matrix).
     Returns (nodes, vels, info dict)."""
-    g = _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver)
+    g = _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver, info)
     sysm = (_DenseHipSystem if solver == 'hip' else _DenseSystem)(g, vmin, vmax)
     return _run_lm(nodes, vels, g, sysm, reproj, kernel, radius, max_steps, patience, decreasing)
 
 
 # ------------------------------------------------------------------------------------------ band + low-rank (PCG)
-def _edge_blocks(vo, w0, c_vo=None):
+def _unpack_info_vo(info_vo):
+    """info_vo (21,E), the packed upper triangles -> (E,6,6) symmetric matrices on the device."""
+    E = info_vo.shape[1]
+    iu = torch.triu_indices(6, 6, device=info_vo.device)
+    W = torch.zeros((E, 6, 6), dtype=info_vo.dtype, device=info_vo.device)
+    W[:, iu[0], iu[1]] = info_vo.t()
+    return W + W.transpose(1, 2) - torch.diag_embed(W.diagonal(dim1=1, dim2=2))
+
+
+def _edge_blocks(vo, w0, c_vo=None, info_vo=None):
     """Per VO edge: S = w0 J^T J (E,6,6) and g = w0 J^T r (E,6), J = [[G, C], [0, G]] (edge_normal in csrc/pvgo.hip); with robust
-    multipliers c_vo (E,) the weight of edge e is w0 c_vo[e]."""
+    multipliers c_vo (E,) the weight of edge e is w0 c_vo[e]; with info_vo (21,E), S = J^T Omega J and g = J^T Omega r."""
     E = vo.shape[1]
     G = vo[6:15].t().reshape(E, 3, 3)
     C = vo[15:24].t().reshape(E, 3, 3)
@@ -302,6 +330,10 @@ def _edge_blocks(vo, w0, c_vo=None):
     J[:, :3, :3], J[:, :3, 3:], J[:, 3:, 3:] = G, C, G
     r = vo[0:6].t()
     Jt = J.transpose(1, 2)
+    if info_vo is not None:
+        JtW = Jt @ _unpack_info_vo(info_vo)
+        S = JtW @ J
+        return 0.5 * (S + S.transpose(1, 2)), (JtW @ r[:, :, None])[:, :, 0]
     if c_vo is not None:
         we = w0 * c_vo
         return we[:, None, None] * (Jt @ J), we[:, None] * (Jt @ r[:, :, None])[:, :, 0]
@@ -317,12 +349,15 @@ def off_band_edges(edges_host):
 class _BandSystem:
     """A = B + R of one linearisation: B as (Hd, Ho) of the chain solver, R as the list of off-band 6x6 blocks."""
 
-    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt=None, c_vo=None, c_imu=None):
+    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt=None, c_vo=None, c_imu=None, info=None):
         dev = vo.device
-        Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
+        if info is not None:
+            Hd, Ho, rhs = ops.pvgo_build_normal_info(lin, dts, N, None, info[1], -_NOCLAMP, _NOCLAMP)                     # IMU factors
+        else:
+            Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
-        S, g = _edge_blocks(vo, w[0], c_vo)
+        S, g = _edge_blocks(vo, w[0], c_vo, info[0] if info is not None else None)
         E = S.shape[0]
         i, j = edges[:, 0], edges[:, 1]
         Sp = torch.zeros((E, 9, 9), dtype=S.dtype, device=dev)
@@ -408,7 +443,8 @@ class _BandPcgSystem:
         self.extra = dict(pcg_iterations=0, pcg_worst_relative_residual=0.0, off_band_edges=int(self.off_idx.numel()))
 
     def assemble(self, vo, lin, rpt, c_vo, c_imu):
-        self.band = _BandSystem(vo, lin, self.g.edges, self.g.dts, self.g.N, self.g.w, self.vmin, self.vmax, self.off_idx, rpt, c_vo, c_imu)
+        self.band = _BandSystem(vo, lin, self.g.edges, self.g.dts, self.g.N, self.g.w, self.vmin, self.vmax, self.off_idx, rpt, c_vo, c_imu,
+                                self.g.info)
         return self.band.diag0
 
     def solve(self, d):
@@ -427,8 +463,8 @@ class _BandPcgSystem:
 
 
 def run_lm_band_pcg(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, radius=1e4, max_steps=10, patience=3,
-                    decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None):
+                    decreasing=1e-3, vmin=1e-4, vmax=1e32, reproj=None, kernel=None, info=None):
     """The LM of run_lm_dense on the band + low-rank form of the same normal equations.  In: float64 contiguous device
     tensors.  Returns (nodes, vels, info dict)."""
-    g = _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel)
+    g = _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, info=info)
     return _run_lm(nodes, vels, g, _BandPcgSystem(g, vmin, vmax), reproj, kernel, radius, max_steps, patience, decreasing)
