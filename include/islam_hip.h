@@ -900,6 +900,26 @@ int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const d
 int islam_pvgo_assemble_dense_info(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
                                    const double* info_vo, const int64_t* edges, const int64_t* node_ptr,
                                    const int64_t* node_adj, int N, int E, double* A, double* rhs, void* stream);
+/* The same normal equations in band + off-band form, A = B + R (islam_amd/pvgo_dense.py): B block-tridiagonal
+ * in the chain solver's arrays, R the 6x6 blocks of the K edges that couple nodes more than one apart.
+ * islam_pvgo_band_assemble works IN PLACE on Hd, Ho (N,9,9) and rhs (N,9), which hold the IMU part (islam_pvgo_build_normal with
+ * w[0] = 0, _scaled or _info with info_vo = NULL; no clamp).  Edge e = (i, j), i != j, of `vo` (24,E) adds S_e to the pose blocks of
+ * Hd[i] and Hd[j] in the CSR order of node_ptr / node_adj (as islam_pvgo_assemble_dense), -+ its gradient to rhs[i] / rhs[j], and,
+ * where |i - j| = 1, -S_e to Ho[min(i, j)] whichever way the edge points; every block is written by one lane, several edges on one
+ * node pair accumulate in CSR order, and there are no atomics: the same inputs give the same bits.  S_e = w0 J^T J; with c_vo (E)
+ * w0 c_vo[e] J^T J; with info_vo (21,E) J^T Omega_e J (w0 unused); c_vo and info_vo may not both be given.  The edges must be valid
+ * (indices in [0, N), no self-loop): the caller checks them on the host.
+ * off_idx (K): the indices of the off-band edges, ascending; out: io, jo (K) their ends and So (K,6,6) their S_e.  K = 0: all four NULL.
+ * islam_pvgo_band_matvec: y (N,9) = A p in one launch, y = Hd p + Ho p+ + Ho^T p- and, on the pose rows, y_i -= So p_j and
+ * y_j -= So p_i for every off-band edge, summed per node over off_ptr (N+1) / off_adj (2K), the CSR of the off-band edge ends per node
+ * (entry = 2 * t + end, t the position in io / jo / So): fixed order, no atomics.  Reads the full Hd blocks (both triangles) and
+ * Ho[0 .. N-2]; y may not alias p.  Both calls only enqueue on `stream`.  ISLAM_EARG before any HIP call for N < 2, E < 1, K outside
+ * [0, E] or a missing array. */
+int islam_pvgo_band_assemble(double* Hd, double* Ho, double* rhs, const double* vo, const double* c_vo, const double* info_vo,
+                             const int64_t* edges, const int64_t* node_ptr, const int64_t* node_adj, double w0, int N, int E,
+                             const int64_t* off_idx, int K, int64_t* io, int64_t* jo, double* So, void* stream);
+int islam_pvgo_band_matvec(const double* Hd, const double* Ho, const double* p, const int64_t* off_ptr, const int64_t* off_adj,
+                           const int64_t* io, const int64_t* jo, const double* So, int N, int K, double* y, void* stream);
 /* Dense fp64 Cholesky A = L L^T of the general-topology normal matrix and the solve with its factor (csrc/dense_chol.hip, DESIGN.md
  * section 3.17): the O(n^3) step of the loop-closure LM on the matrix cores (v_mfma_f64_16x16x4_f64), n = 9N, any n >= 1.
  * Storage contract.  A: n x n row-major device doubles.  islam_dense_chol_factor READS the strict upper triangle of A and diag (n) --

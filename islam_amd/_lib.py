@@ -190,6 +190,8 @@ SIGNATURES = {
     'islam_pvgo_assemble_dense': (c_int, [c_void_p] * 7 + [c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'islam_pvgo_assemble_dense_scaled': (c_int, [c_void_p] * 8 + [c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'islam_pvgo_assemble_dense_info': (c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'islam_pvgo_band_assemble': (c_int, [c_void_p] * 9 + [c_double, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4),
+    'islam_pvgo_band_matvec': (c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, c_void_p]),
     'islam_dense_chol_workspace_bytes': (c_size_t, [c_int]),
     'islam_dense_chol_factor': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'islam_dense_chol_solve': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

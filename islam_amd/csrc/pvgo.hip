@@ -394,6 +394,37 @@ int islam_pvgo_assemble_dense_info(const double* Hd, const double* Ho, const dou
     return ISLAM_OK;
 }
 
+int islam_pvgo_band_assemble(double* Hd, double* Ho, double* rhs, const double* vo, const double* c_vo, const double* info_vo,
+                             const int64_t* edges, const int64_t* node_ptr, const int64_t* node_adj, double w0, int N, int E,
+                             const int64_t* off_idx, int K, int64_t* io, int64_t* jo, double* So, void* stream) {
+    if (N < 2 || E < 1 || K < 0 || K > E || !Hd || !Ho || !rhs || !vo || !edges || !node_ptr || !node_adj || (c_vo && info_vo) ||
+        (K > 0 && (!off_idx || !io || !jo || !So)))
+        return fail(ISLAM_EARG, "islam_pvgo_band_assemble: N=%d E=%d K=%d, a null array, or both c_vo and info_vo", N, E, K);
+    const dim3 grid((std::max(N, K) + 63) / 64), block(64);
+    hipStream_t s = as_stream(stream);
+    if (info_vo)
+        hipLaunchKernelGGL(band_assemble_kernel<2>, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E,
+                           off_idx, K, io, jo, So);
+    else if (c_vo)
+        hipLaunchKernelGGL(band_assemble_kernel<1>, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E,
+                           off_idx, K, io, jo, So);
+    else
+        hipLaunchKernelGGL(band_assemble_kernel<0>, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E,
+                           off_idx, K, io, jo, So);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+int islam_pvgo_band_matvec(const double* Hd, const double* Ho, const double* p, const int64_t* off_ptr, const int64_t* off_adj,
+                           const int64_t* io, const int64_t* jo, const double* So, int N, int K, double* y, void* stream) {
+    if (N < 2 || N > 200000000 /* 9 N + 255 fits an int */ || K < 0 || !Hd || !Ho || !p || !y || p == y || (K > 0 && (!off_ptr || !off_adj || !io || !jo || !So)))
+        return fail(ISLAM_EARG, "islam_pvgo_band_matvec: N=%d K=%d, a null array, or y aliasing p", N, K);
+    hipLaunchKernelGGL(band_matvec_kernel, dim3((9 * N + 255) / 256), dim3(256), 0, as_stream(stream), Hd, Ho, p, off_ptr, off_adj, io, jo,
+                       So, N, K, y);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
 int islam_pvgo_robust_weights(const double* vo, int E, const double* lin, int M, const islam_pvgo_robust* robust, double* c_vo,
                               double* c_imu, double* rho_part, void* stream) {
     if (E < 0 || M < 0 || E + M < 1 || !robust || !rho_part || (E > 0 && !vo) || (M > 0 && !lin))

@@ -289,6 +289,115 @@ __global__ __launch_bounds__(64) void dense_info_edges_kernel(const double* __re
     sub3x3_atomic(ij + 3 * ld + 3, ji + 3 * ld + 3, ld, en.Spp);
 }
 
+// ---- band + off-band form of the same normal equations (islam_pvgo_band_assemble / _matvec) ----
+// the weighted normal pieces of edge e.  MODE 0: w0 S; 1: w0 c_vo[e] S (robust multiplier); 2: A_e^T Omega_e A_e (info_vo (21,E))
+template <int MODE>
+__device__ __forceinline__ EdgeNormal band_edge_normal(const double* __restrict__ vo, const double* __restrict__ c_vo,
+                                                       const double* __restrict__ info_vo, double w0, int E, int e) {
+    EdgeNormal o;
+    if constexpr (MODE == 2) {
+        const InfoVo en = edge_info_normal(vo, info_vo, E, e);
+        o.Srr = en.Srr; o.Srp = en.Srp; o.Spp = en.Spp; o.gr = en.gr; o.gp = en.gp;
+    } else {
+        const EdgeNormal en = edge_normal(vo, E, e);
+        double we = w0;
+        if constexpr (MODE == 1) we = w0 * c_vo[e];
+        o.Srr = we * en.Srr; o.Srp = we * en.Srp; o.Spp = we * en.Spp; o.gr = we * en.gr; o.gp = we * en.gp;
+    }
+    return o;
+}
+
+// p (row-major, leading dimension ld) -= [[Srr, Srp], [Srp^T, Spp]] (sign = -1) or += (sign = +1)
+__device__ __forceinline__ void add6x6(double* p, size_t ld, double sign, M3<double> Srr, M3<double> Srp, M3<double> Spp) {
+    add3x3(p, ld, sign * Srr); add3x3(p + 3, ld, sign * Srp); add3x3(p + 3 * ld, ld, sign * transpose(Srp)); add3x3(p + 3 * ld + 3, ld, sign * Spp);
+}
+// a 3x3 block of a row-major 6x6 matrix
+__device__ __forceinline__ void store3x3_ld6(M3<double> a, double* p) {
+    p[0] = a.a00; p[1] = a.a01; p[2] = a.a02; p[6] = a.a10; p[7] = a.a11; p[8] = a.a12; p[12] = a.a20; p[13] = a.a21; p[14] = a.a22;
+}
+
+// Lane t < N, node t: walks the node's edge ends in CSR order (the order of dense_nodes_kernel) and adds, in place, every edge's S
+// to the pose block of Hd[t], its gradient to rhs[t] (-g at the edge's first node, +g at its second; rhs = -J^T W r) and -S to Ho[t]
+// for every edge whose other end is node t + 1, whichever way it points (S is symmetric): all of Ho[t] comes from this one lane, so
+// parallel edges accumulate in a fixed order and no atomic is needed.  Lane t < K, off-band edge off_idx[t]: its ends and its S.
+template <int MODE>
+__global__ __launch_bounds__(64) void band_assemble_kernel(double* __restrict__ Hd, double* __restrict__ Ho, double* __restrict__ rhs,
+                                                            const double* __restrict__ vo, const double* __restrict__ c_vo,
+                                                            const double* __restrict__ info_vo, const int64_t* __restrict__ edges,
+                                                            const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ node_adj,
+                                                            double w0, int N, int E, const int64_t* __restrict__ off_idx, int K,
+                                                            int64_t* __restrict__ io, int64_t* __restrict__ jo, double* __restrict__ So) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    const M3<double> Z{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (t < N) {
+        M3<double> Srr = Z, Srp = Z, Spp = Z, Orr = Z, Orp = Z, Opp = Z;
+        V3<double> gr{0, 0, 0}, gp{0, 0, 0};
+        for (int64_t a = node_ptr[t]; a < node_ptr[t + 1]; ++a) {
+            const int64_t code = node_adj[a];
+            const int e = (int)(code >> 1);
+            const EdgeNormal en = band_edge_normal<MODE>(vo, c_vo, info_vo, w0, E, e);
+            Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
+            if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
+            if (edges[2 * e + 1 - (int)(code & 1)] == (int64_t)t + 1) { Orr = Orr + en.Srr; Orp = Orp + en.Srp; Opp = Opp + en.Spp; }
+        }
+        add6x6(Hd + (size_t)t * 81, 9, 1.0, Srr, Srp, Spp);
+        if (t < N - 1) add6x6(Ho + (size_t)t * 81, 9, -1.0, Orr, Orp, Opp);
+        double* b = rhs + (size_t)t * 9;
+        b[0] -= gr.x; b[1] -= gr.y; b[2] -= gr.z; b[3] -= gp.x; b[4] -= gp.y; b[5] -= gp.z;
+    }
+    if (t < K) {
+        const int e = (int)off_idx[t];
+        io[t] = edges[2 * e];
+        jo[t] = edges[2 * e + 1];
+        const EdgeNormal en = band_edge_normal<MODE>(vo, c_vo, info_vo, w0, E, e);
+        double* s = So + (size_t)t * 36;
+        store3x3_ld6(en.Srr, s); store3x3_ld6(en.Srp, s + 3); store3x3_ld6(transpose(en.Srp), s + 18); store3x3_ld6(en.Spp, s + 21);
+    }
+}
+
+// y = A p of the band + off-band form, one launch, nine lanes per node: lane (k, r) forms row r of node k,
+//   y[k][r] = Hd[k][r][:] . p[k] + Ho[k][r][:] . p[k+1] + Ho[k-1][:][r] . p[k-1] - sum over the node's off-band edge ends So[t][r][:] . p[other end]
+// (r < 6 for the last term).  The nine lanes of a node read the 81 doubles of a block between them, so a wavefront's loads cover one
+// contiguous stretch of Hd and of Ho; Ho[k] is read by nodes k and k + 1, neighbours in the same wavefront but for one node in seven.
+// off_ptr (N+1), off_adj: CSR of the off-band edge ends per node, entry = 2 * t + end: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void band_matvec_kernel(const double* __restrict__ Hd, const double* __restrict__ Ho,
+                                                           const double* __restrict__ p, const int64_t* __restrict__ off_ptr,
+                                                           const int64_t* __restrict__ off_adj, const int64_t* __restrict__ io,
+                                                           const int64_t* __restrict__ jo, const double* __restrict__ So, int N, int K,
+                                                           double* __restrict__ y) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int k = t / 9, r = t - 9 * k;
+    if (k >= N) return;
+    const double* pk = p + (size_t)k * 9;
+    const double* hd = Hd + (size_t)k * 81 + r * 9;
+    double acc = 0.0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) acc += hd[c] * pk[c];
+    if (k < N - 1) {
+        const double* ho = Ho + (size_t)k * 81 + r * 9;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) acc += ho[c] * pk[9 + c];
+    }
+    if (k > 0) {
+        const double* ho = Ho + (size_t)(k - 1) * 81 + r;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) acc += ho[c * 9] * pk[c - 9];
+    }
+    if (K > 0 && r < 6) {
+        double off = 0.0;
+        for (int64_t a = off_ptr[k]; a < off_ptr[k + 1]; ++a) {
+            const int64_t code = off_adj[a];
+            const int64_t te = code >> 1;
+            const double* po = p + (size_t)((code & 1) ? io[te] : jo[te]) * 9;
+            const double* s = So + (size_t)te * 36 + r * 6;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) off += s[c] * po[c];
+        }
+        acc -= off;
+    }
+    y[t] = acc;
+}
+
 __global__ __launch_bounds__(64) void vo_loss_fwd_kernel(const double* __restrict__ nodes, const int64_t* __restrict__ edges,
                                                           const double* __restrict__ poses, int E, double* __restrict__ err6,
                                                           double* __restrict__ tl, double* __restrict__ rl) {

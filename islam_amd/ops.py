@@ -1198,6 +1198,51 @@ def pvgo_robust_weights(vo, lin, robust, with_weights=True):
     return c_vo, c_imu, part.sum()
 
 
+def pvgo_band_assemble(Hd, Ho, rhs, vo, edges, node_ptr, node_adj, w0, off_idx, c_vo=None, info_vo=None):
+    """islam_pvgo_band_assemble: the VO factors of ``vo`` (24,E) on the validated ``edges`` (E,2) added IN PLACE to the IMU-only chain
+    arrays Hd, Ho (N,9,9), rhs (N,9); node_ptr / node_adj the CSR of the edge ends per node, off_idx (K,) the off-band edges.
+    c_vo (E,): robust multipliers; info_vo (21,E): per-edge information (not both).  Returns the off-band list (io (K,), jo (K,),
+    So (K,6,6))."""
+    require_cuda(Hd, Ho, rhs, vo, edges, node_ptr, node_adj, off_idx, c_vo, info_vo)
+    N, E, K, dev = Hd.shape[0], vo.shape[1], int(off_idx.numel()), Hd.device
+    if tuple(Hd.shape) != (N, 9, 9) or tuple(Ho.shape) != (N, 9, 9) or tuple(rhs.shape) != (N, 9) or tuple(vo.shape) != (24, E) or \
+            tuple(edges.shape) != (E, 2) or node_ptr.numel() != N + 1 or node_adj.numel() != 2 * E:
+        raise ValueError('pvgo_band_assemble: Hd, Ho (N,9,9), rhs (N,9), vo (24,E), edges (E,2), node_ptr (N+1,), node_adj (2E,) expected')
+    if (c_vo is not None and tuple(c_vo.shape) != (E,)) or (info_vo is not None and tuple(info_vo.shape) != (21, E)):
+        raise ValueError('pvgo_band_assemble: c_vo (E,) / info_vo (21,E) expected')
+    for x in (Hd, Ho, rhs, vo, c_vo, info_vo):
+        if x is not None and (x.dtype != torch.float64 or not x.is_contiguous()):
+            raise ValueError('pvgo_band_assemble: contiguous float64 arrays expected')
+    for x in (edges, node_ptr, node_adj, off_idx):
+        if x.dtype != torch.int64 or not x.is_contiguous():
+            raise ValueError('pvgo_band_assemble: contiguous int64 index arrays expected')
+    io = torch.empty((K,), dtype=torch.int64, device=dev)
+    jo = torch.empty((K,), dtype=torch.int64, device=dev)
+    So = torch.empty((K, 6, 6), dtype=torch.float64, device=dev)
+    none_if_empty = lambda x: x if K else None
+    check(lib().islam_pvgo_band_assemble(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), ptr(info_vo), ptr(edges), ptr(node_ptr),
+                                         ptr(node_adj), c_double(w0), N, E, ptr(none_if_empty(off_idx)), K, ptr(none_if_empty(io)),
+                                         ptr(none_if_empty(jo)), ptr(none_if_empty(So)), stream_ptr(dev)))
+    return io, jo, So
+
+
+def pvgo_band_matvec(Hd, Ho, p, off_ptr, off_adj, io, jo, So):
+    """islam_pvgo_band_matvec: y (N,9) = (B + R) p with B = (Hd, Ho) and R the off-band list (io, jo, So) of pvgo_band_assemble;
+    off_ptr (N+1,), off_adj (2K,): the CSR of the off-band edge ends per node (entry = 2 * position in the list + end)."""
+    require_cuda(Hd, Ho, p, off_ptr, off_adj, io, jo, So)
+    N, K = Hd.shape[0], int(io.numel())
+    if tuple(Ho.shape) != (N, 9, 9) or tuple(p.shape) != (N, 9) or not p.is_contiguous() or p.dtype != torch.float64 or \
+            off_ptr.numel() != N + 1 or off_adj.numel() != 2 * K or jo.numel() != K or tuple(So.shape) != (K, 6, 6):
+        raise ValueError('pvgo_band_matvec: Hd, Ho (N,9,9), p (N,9) contiguous float64, off_ptr (N+1,), off_adj (2K,), io, jo (K,), So (K,6,6) expected')
+    y = torch.empty_like(p)
+    if K:
+        check(lib().islam_pvgo_band_matvec(ptr(Hd), ptr(Ho), ptr(p), ptr(off_ptr), ptr(off_adj), ptr(io), ptr(jo), ptr(So), N, K, ptr(y),
+                                           stream_ptr(Hd.device)))
+    else:
+        check(lib().islam_pvgo_band_matvec(ptr(Hd), ptr(Ho), ptr(p), None, None, None, None, None, N, 0, ptr(y), stream_ptr(Hd.device)))
+    return y
+
+
 def pvgo_solve_chain(Hd, Ho, rhs, damping, seg_len=(0, 0), workspace=None):
     N = Hd.shape[0]
     if workspace is None:

@@ -178,6 +178,7 @@ def pvgo_marginals_general(nodes, vels, vo_motions, links, dts, imu_drots, imu_d
     dev = pp._plain(torch.as_tensor(nodes)).device
     if dev.type != 'cuda':
         raise RuntimeError('islam_amd.pvgo_marginals_general runs on the MI355X only; there is no CPU fallback')
+    _validate_links(len(nodes), links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     packed = _packed_info(info, len(links), len(nodes) - 1, loss_weight, dev, reproj)
     n64, v64, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, nodes, vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     edges = torch.as_tensor(links).to(dev, torch.int64).contiguous()
@@ -186,6 +187,14 @@ def pvgo_marginals_general(nodes, vels, vo_motions, links, dts, imu_drots, imu_d
 
 
 _GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
+
+
+def _validate_links(N, links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts):
+    """pvgo_dense.validate_graph on the caller's own arrays, before any of them is copied to the device."""
+    from .pvgo_dense import validate_graph
+    numel = lambda x: int(pp._plain(torch.as_tensor(x)).numel())
+    return validate_graph(N, links, len(vo_motions), dict(imu_drots=len(imu_drots), imu_dtrans=len(imu_dtrans), imu_dvels=len(imu_dvels),
+                                                          dts=numel(dts)))
 
 
 def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels,
@@ -211,6 +220,8 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
         raise UnsupportedGraphError('marginals=True serves canonical chains (links[k] = [k, k+1]) only; covariances of '
                                     "loop-closure graphs are not implemented (except with general_solver='dense_hip': the dense "
                                     'selected inverse, pvgo_marginals_general)')
+    if not chain:        # any number of VO edges on the N nodes; refused before anything reaches the device
+        _validate_links(N, links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     rp = _reproj_struct(reproj, loss_weight, dev)
     out_dtype = pp._plain(init_nodes).dtype if isinstance(init_nodes, torch.Tensor) else torch.get_default_dtype()
     nodes, vels, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, init_nodes, init_vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)

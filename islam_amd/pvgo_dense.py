@@ -1,6 +1,8 @@
-"""General-topology PVGO (arbitrary ``links``: loop closures, skipped frames) on the GPU -- SURVEY.md section 8f rank 4.
+"""General-topology PVGO (arbitrary ``links``: loop closures as added or replaced edges, skipped frames) on the GPU -- SURVEY.md
+section 8f rank 4; the contract on ``links`` is DESIGN.md section 3.20 (validate_graph below).
 
-The chain fast path (islam_amd/csrc/pvgo.hip) needs links[k] = [k, k+1].  For any other edge set this module runs the same LM
+The chain fast path (islam_amd/csrc/pvgo.hip) needs links[k] = [k, k+1].  For any other edge set -- any number E >= 1 of VO edges on
+the N nodes, more or fewer than the N - 1 IMU intervals, parallel and reversed edges among them -- this module runs the same LM
 (pp.optim.LM + Cholesky + TrustRegion + StopOnPlateau as constructed at pvgo.py:169-172) on the normal equations PyPose factorises, but
 never forms the Jacobian PyPose multiplies (rows x 10N).  There is ONE loop, _run_lm: residuals and Jacobian blocks per factor
 from the HIP kernels (islam_pvgo_linearize_edges for the VO factors on arbitrary edges, islam_pvgo_linearize for the IMU factors, which
@@ -11,12 +13,13 @@ one linearisation, solve(d) -> the step (N,9) or None (failed), and ``extra`` en
     instead of the 2*rows*cols^2 dense product); fp64 POTRF / POTRS from rocSOLVER (the only O(N^3) piece), a second matrix per trial;
   * _DenseHipSystem: the same A and b with the project's own blocked Cholesky on v_mfma_f64_16x16x4_f64 (csrc/dense_chol.hip, DESIGN.md
     section 3.17), in place.  Both are sized by the dense matrix: (9N)^2 doubles (N = 5001: 16 GB of the 288 GB);
-  * _BandPcgSystem, for long trajectories with a few loop closures: the IMU factors always couple consecutive nodes and a VO edge
-    (i, j) adds S = w J^T J to the diagonal blocks of i and j and -S to the block (i, j), so
+  * _BandPcgSystem, for long trajectories with a few loop closures (added or replaced edges): the IMU factors always couple
+    consecutive nodes and a VO edge (i, j) adds S = w J^T J to the diagonal blocks of i and j and -S to the block (i, j), so
       A = B + R,  B = block-tridiagonal (all diagonal blocks, the couplings |i-j| = 1),  R = the off-band blocks of the k long edges,
     B is positive definite on its own, rank(R) <= 12 k, and conjugate gradients preconditioned with B^-1 -- the block-tridiagonal
     solver of the chain path, islam_pvgo_solve_chain, ~60 us per application at N = 5001 -- reaches the solution of the SAME normal
-    equations in at most 12 k + 1 iterations.  Memory O(N + k).
+    equations in at most 12 k + 1 iterations.  Memory O(N + k).  B and R are assembled in place by one kernel
+    (islam_pvgo_band_assemble) and A p is one launch (islam_pvgo_band_matvec); DESIGN.md section 3.20.
 
 Robust kernels (``kernel``, an islam_amd.robust.RobustSpec): islam_pvgo_robust_weights gives the multiplier
 c = rho'(s) of every VO edge and IMU-side factor and the loss sum rho(s); the scaled assembly entry points and the trust-region
@@ -24,7 +27,7 @@ term apply c per factor.  Every system uses the same multipliers and the same lo
 
 Per-factor information (``info``, the packed pair of islam_amd.information.PvgoInfo.packed): every system
 assembles A = sum J^T Omega J and b = -sum J^T Omega r instead -- islam_pvgo_build_normal_info for the IMU groups,
-islam_pvgo_assemble_dense_info or the per-edge blocks of _edge_blocks for the VO edges.  The loop, the loss and the trust-region term
+islam_pvgo_assemble_dense_info or islam_pvgo_band_assemble for the VO edges.  The loop, the loss and the trust-region term
 are the unweighted ones above."""
 import numpy as np
 import torch
@@ -58,6 +61,42 @@ class _Graph:
         dummy = torch.zeros((self.N - 1, 7), dtype=torch.float64, device=self.dev)
         dummy[:, 6] = 1.0
         self.linearize = lambda nodes, vels: _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
+
+
+def validate_graph(N, links, n_motions, imu_rows=None):
+    """The contract on a general-topology graph, checked on the host: ``links`` of shape (E, 2), E >= 1, node
+    indices in [0, N), no self-loop (a factor between a node and itself has a zero Jacobian, and the node assembly would add its S
+    twice to the diagonal); one VO motion per edge; imu_rows {name: rows}: N - 1 rows each (the IMU factors couple consecutive nodes).
+    More or fewer edges than N - 1, parallel edges and edges (j, i) with j > i are all fine.  Raises ValueError naming the first
+    offending edge; returns links as an (E, 2) int64 numpy array."""
+    l = np.asarray(links.detach().cpu() if isinstance(links, torch.Tensor) else links)
+    if l.ndim != 2 or l.shape[1] != 2:
+        raise ValueError('links: shape (E, 2) expected, got %s' % (tuple(l.shape),))
+    if l.shape[0] < 1:
+        raise ValueError('links: at least one VO edge is needed (E = 0)')
+    if l.dtype.kind not in 'iu':
+        raise ValueError('links: integer node indices expected, got %s' % l.dtype)
+    if N < 2:
+        raise ValueError('a graph needs at least 2 nodes, got N = %d' % N)
+    l = l.astype(np.int64)
+    bad = np.nonzero(((l < 0) | (l >= N)).any(axis=1) | (l[:, 0] == l[:, 1]))[0]
+    if bad.size:
+        e = int(bad[0])
+        i, j = int(l[e, 0]), int(l[e, 1])
+        if i == j and 0 <= i < N:
+            raise ValueError('links[%d] = (%d, %d) is a self-loop: a VO edge joins two different nodes' % (e, i, j))
+        raise ValueError('links[%d] = (%d, %d): node index outside [0, %d)' % (e, i, j, N))
+    if int(n_motions) != l.shape[0]:
+        raise ValueError('one VO motion per edge: %d motions for %d edges' % (n_motions, l.shape[0]))
+    for name, rows in (imu_rows or {}).items():
+        if int(rows) != N - 1:
+            raise ValueError('%s: %d rows, one per IMU interval expected (N - 1 = %d)' % (name, rows, N - 1))
+    return l
+
+
+def _validate_device_graph(nodes, edges, poses, drots, dtrans, dvels, dts):
+    return validate_graph(nodes.shape[0], edges, poses.shape[0], dict(imu_drots=drots.shape[0], imu_dtrans=dtrans.shape[0],
+                                                                         imu_dvels=dvels.shape[0], dts=dts.numel()))
 
 
 def _loss(vo, lin):
@@ -205,10 +244,8 @@ class _DenseHipSystem(_DenseSystem):
 
 def gauss_newton_matrix(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None, info=None):
     """A = J^T W J (9N x 9N, device, fully written) at (nodes, vels): undamped, unclamped, no gauge fixed -- what run_lm_dense assembles
-    before it damps the diagonal.  The VO factors may sit on any number of edges (the assembly needs no E = N - 1; only the LM's loss
-    does)."""
-    if poses.shape[0] != edges.shape[0]:
-        raise ValueError('one VO motion per edge: %d motions for %d edges' % (poses.shape[0], edges.shape[0]))
+    before it damps the diagonal.  The VO factors may sit on any number of edges (validate_graph)."""
+    _validate_device_graph(nodes, edges, poses, drots, dtrans, dvels, dts)
     if info is not None and reproj is not None:
         raise NotImplementedError('per-factor information with the reprojection factor is not implemented')
     sysm = _DenseSystem(_Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info))
@@ -285,16 +322,15 @@ def _run_lm(nodes, vels, g, sysm, reproj, kernel, radius, max_steps, patience, d
 
 
 def _lm_graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj, kernel, solver='torch', info=None):
-    """The host-side checks of the two entry points, in this order and before any device work, then the _Graph."""
-    N, E = nodes.shape[0], edges.shape[0]
+    """The host-side checks of the two entry points, in this order and before any device work (the refused combinations, then
+    validate_graph: any number E >= 1 of VO edges), then the _Graph."""
     if info is not None and (kernel is not None or reproj is not None):
         raise NotImplementedError('per-factor information with robust kernels or the reprojection factor is not implemented')
     if kernel is not None and reproj is not None:
         raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
     if solver not in ('torch', 'hip'):
         raise ValueError("solver must be 'torch' or 'hip'")
-    if E != N - 1:
-        raise ValueError('PoseVelGraph needs as many VO edges as IMU intervals (dts broadcasts over both, pvgo.py:51): E=%d, N-1=%d' % (E, N - 1))
+    _validate_device_graph(nodes, edges, poses, drots, dtrans, dvels, dts)
     return _Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info)
 
 
@@ -311,82 +347,45 @@ def run_lm_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weig
 
 
 # ------------------------------------------------------------------------------------------ band + low-rank (PCG)
-def _unpack_info_vo(info_vo):
-    """info_vo (21,E), the packed upper triangles -> (E,6,6) symmetric matrices on the device."""
-    E = info_vo.shape[1]
-    iu = torch.triu_indices(6, 6, device=info_vo.device)
-    W = torch.zeros((E, 6, 6), dtype=info_vo.dtype, device=info_vo.device)
-    W[:, iu[0], iu[1]] = info_vo.t()
-    return W + W.transpose(1, 2) - torch.diag_embed(W.diagonal(dim1=1, dim2=2))
-
-
-def _edge_blocks(vo, w0, c_vo=None, info_vo=None):
-    """Per VO edge: S = w0 J^T J (E,6,6) and g = w0 J^T r (E,6), J = [[G, C], [0, G]] (edge_normal in csrc/pvgo.hip); with robust
-    multipliers c_vo (E,) the weight of edge e is w0 c_vo[e]; with info_vo (21,E), S = J^T Omega J and g = J^T Omega r."""
-    E = vo.shape[1]
-    G = vo[6:15].t().reshape(E, 3, 3)
-    C = vo[15:24].t().reshape(E, 3, 3)
-    J = torch.zeros((E, 6, 6), dtype=vo.dtype, device=vo.device)
-    J[:, :3, :3], J[:, :3, 3:], J[:, 3:, 3:] = G, C, G
-    r = vo[0:6].t()
-    Jt = J.transpose(1, 2)
-    if info_vo is not None:
-        JtW = Jt @ _unpack_info_vo(info_vo)
-        S = JtW @ J
-        return 0.5 * (S + S.transpose(1, 2)), (JtW @ r[:, :, None])[:, :, 0]
-    if c_vo is not None:
-        we = w0 * c_vo
-        return we[:, None, None] * (Jt @ J), we[:, None] * (Jt @ r[:, :, None])[:, :, 0]
-    return w0 * (Jt @ J), w0 * (Jt @ r[:, :, None])[:, :, 0]
-
-
 def off_band_edges(edges_host):
     """Indices of the edges that couple nodes more than one apart (the part of A outside the block-tridiagonal band)."""
     d = np.abs(edges_host[:, 1] - edges_host[:, 0])
     return np.nonzero(d > 1)[0]
 
 
-class _BandSystem:
-    """A = B + R of one linearisation: B as (Hd, Ho) of the chain solver, R as the list of off-band 6x6 blocks."""
+class _BandTopology:
+    """What the band form needs of a validated edge list, built once per graph: the CSR of the edge ends per node (_node_adjacency), the
+    off-band edges, and the CSR of THEIR ends per node with entry = 2 * (position in the off-band list) + end."""
 
-    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, off_idx, rpt=None, c_vo=None, c_imu=None, info=None):
-        dev = vo.device
+    def __init__(self, edges_host, N, dev):
+        off = off_band_edges(edges_host)
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+        self.K = int(off.size)
+        self.off_idx = to(off)
+        self.nptr, self.nadj = [to(a) for a in _node_adjacency(edges_host, N)]
+        self.optr, self.oadj = [to(a) for a in _node_adjacency(edges_host[off], N)]
+
+
+class _BandSystem:
+    """A = B + R of one linearisation: B as (Hd, Ho) of the chain solver, R as the list of off-band 6x6 blocks (io, jo, So)."""
+
+    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, topo, rpt=None, c_vo=None, c_imu=None, info=None):
         if info is not None:
             Hd, Ho, rhs = ops.pvgo_build_normal_info(lin, dts, N, None, info[1], -_NOCLAMP, _NOCLAMP)                     # IMU factors
         else:
             Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
-        S, g = _edge_blocks(vo, w[0], c_vo, info[0] if info is not None else None)
-        E = S.shape[0]
-        i, j = edges[:, 0], edges[:, 1]
-        Sp = torch.zeros((E, 9, 9), dtype=S.dtype, device=dev)
-        Sp[:, :6, :6] = S
-        gp = torch.zeros((E, 9), dtype=S.dtype, device=dev)
-        gp[:, :6] = g
-        Hd.index_add_(0, i, Sp)
-        Hd.index_add_(0, j, Sp)
-        rhs.index_add_(0, i, gp)                     # b = -J^T W r: +g at the edge's first node, -g at its second
-        rhs.index_add_(0, j, -gp)
-        adj = (j - i).abs() == 1
-        Ho.index_add_(0, torch.minimum(i, j)[adj], -Sp[adj])
-        self.Hd, self.Ho, self.b = Hd, Ho, rhs
-        self.io, self.jo, self.So = i[off_idx], j[off_idx], S[off_idx]
+        self.io, self.jo, self.So = ops.pvgo_band_assemble(Hd, Ho, rhs, vo, edges, topo.nptr, topo.nadj, w[0], topo.off_idx, c_vo,
+                                                           info[0] if info is not None else None)          # the VO factors, in place
+        self.Hd, self.Ho, self.b, self.topo = Hd, Ho, rhs, topo
         self.diag0 = Hd.diagonal(dim1=1, dim2=2).clamp(vmin, vmax).clone()                  # A.diagonal().clamp_(min, max)
 
     def set_diagonal(self, d):
         self.Hd.diagonal(dim1=1, dim2=2).copy_(d)
 
     def matvec(self, p):
-        y = (self.Hd @ p[:, :, None])[:, :, 0]
-        y[:-1] += (self.Ho[:-1] @ p[1:, :, None])[:, :, 0]
-        y[1:] += (self.Ho[:-1].transpose(1, 2) @ p[:-1, :, None])[:, :, 0]
-        if self.io.numel():
-            y6 = torch.zeros((p.shape[0], 6), dtype=p.dtype, device=p.device)
-            y6.index_add_(0, self.io, (self.So @ p[self.jo, :6, None])[:, :, 0])
-            y6.index_add_(0, self.jo, (self.So @ p[self.io, :6, None])[:, :, 0])
-            y[:, :6] -= y6
-        return y
+        return ops.pvgo_band_matvec(self.Hd, self.Ho, p.contiguous(), self.topo.optr, self.topo.oadj, self.io, self.jo, self.So)
 
 
 PCG_FAIL_RTOL = 1e-8      # true relative residual above which a PCG solve counts as failed
@@ -434,16 +433,16 @@ class _BandPcgSystem:
 
     def __init__(self, g, vmin, vmax):
         self.g, self.vmin, self.vmax = g, vmin, vmax
-        self.off_idx = torch.from_numpy(off_band_edges(g.edges.cpu().numpy())).to(g.dev)
+        self.topo = _BandTopology(g.edges.cpu().numpy(), g.N, g.dev)
         self.ws = ops.pvgo_workspace(g.N, g.dev)
         try:
             ops.pvgo_solve_status(g.N, self.ws, g.dev)     # initialises the fresh workspace's status / hand-off words
         except IslamHipError:
             pass
-        self.extra = dict(pcg_iterations=0, pcg_worst_relative_residual=0.0, off_band_edges=int(self.off_idx.numel()))
+        self.extra = dict(pcg_iterations=0, pcg_worst_relative_residual=0.0, off_band_edges=self.topo.K)
 
     def assemble(self, vo, lin, rpt, c_vo, c_imu):
-        self.band = _BandSystem(vo, lin, self.g.edges, self.g.dts, self.g.N, self.g.w, self.vmin, self.vmax, self.off_idx, rpt, c_vo, c_imu,
+        self.band = _BandSystem(vo, lin, self.g.edges, self.g.dts, self.g.N, self.g.w, self.vmin, self.vmax, self.topo, rpt, c_vo, c_imu,
                                 self.g.info)
         return self.band.diag0
 
