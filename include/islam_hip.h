@@ -967,6 +967,40 @@ size_t islam_dense_chol_inverse_workspace_bytes(int n);
 int islam_dense_chol_invert_factor(double* L, int n, void* workspace, size_t workspace_bytes, void* stream);
 int islam_pvgo_dense_cov_blocks(const double* W, int n, int anchor, const int64_t* pairs /* host */, int P,
                                 double* node_cov, double* pair_cov, void* stream);
+/* Marginal covariances of a loop-closure graph from its band form A = B + R (csrc/pvgo_band_cov.inl), without
+ * any (9N)^2 array: Sigma = B_a^-1 - Y_c G Y_c^T.  B = (Hd, Ho) as islam_pvgo_band_assemble leaves it, B_a = B with the six pose rows and
+ * columns of node `anchor` replaced by the identity (-1: none); cols (R) int64 in HOST memory: DoF indices 9 node + c in [0, 9N), none of
+ * them a pose DoF of the anchor, the first Rc of them the pose DoF of the closure ends (islam_amd.pvgo_dense.band_columns);
+ * Y_c = B_a^-1[:, cols[:Rc]]; G (Rc x Rc, symmetric) = (I + M Y_S)^-1 M with M = R and Y_S = Y_c on those DoF, formed by the caller.
+ * islam_pvgo_band_inverse_columns.  Y (9N x ldy row-major, ldy >= R): Y[:, r] = B_a^-1 e_cols[r], the anchor's pose rows exactly zero.  One
+ * launch writes the anchored copy of (Hd, Ho) into the workspace (Hd, Ho are not written); every column is one unit right-hand side
+ * through the chain solver (what islam_pvgo_solve_chain_enqueue runs, damping 0), enqueued from a loop here; one launch transposes the
+ * solutions into Y.  status (one device int, or NULL): ISLAM_ENOTPD if any solve met a non-positive pivot, ISLAM_OK otherwise.
+ * islam_pvgo_band_cov_blocks.  Sd (N,9,9), So (N-1,9,9): islam_pvgo_marginals of the same (Hd, Ho) and anchor.  G: 16 ceil(Rc / 16) rows of
+ * ldg >= 16 ceil(Rc / 16) doubles, zero outside its leading Rc x Rc (the matrix-core kernel reads whole 16-column chunks of it).
+ * V = Y[:, :Rc] G on v_mfma_f64_16x16x4_f64 (kept in the workspace), then node_cov (N,9,9): Sd[k] - V_k Y_k^T over the first Rc columns,
+ * entries (p, q) and (q, p) averaged, and pair_cov (P,9,9): base(a, b) - V_a Y_b^T for every pairs[p] = (a, b) ((P,2) int64 in HOST memory,
+ * any a, b in [0, N)), base = Sd[a] for a = b (averaged likewise: equal to node_cov[a] to the bit), So[a] for b = a + 1, So[b]^T for
+ * a = b + 1, otherwise the rows of node a of Y at the columns where cols holds the DoF of node b -- ISLAM_EARG if cols lacks one of them
+ * other than the anchor's pose DoF.  A far pair (a, b) with a > b whose node a has its DoF in cols too is formed as block (b, a) and stored
+ * transposed, so that the two orders of one pair give transposes of each other to the bit (the columns of B_a^-1 come from separate
+ * solves and are symmetric only up to rounding times the condition number).  The pose rows / columns of the anchor are exactly zero in
+ * every block.  node_cov or pair_cov may be
+ * NULL to skip it; Rc = 0 (no closure): the blocks of the chain inverse are copied through, G and the workspace may be NULL.  status (one
+ * device int, or NULL): ISLAM_ENOTPD if a diagonal entry of node_cov outside the anchor's pose DoF is not finite or not positive.
+ * Launches: the projection, one for node_cov, and one per 160 pairs (or 48 distinct far second nodes).
+ * workspace: islam_pvgo_band_inverse_workspace_bytes(N, R) bytes serve both calls (the chain solver's workspace, the anchored band, and
+ * 9N x 16 ceil(R / 16) doubles; 0 for N < 2 or R < 0).  Both calls only enqueue on `stream`; no atomics, every sum in an order fixed by the
+ * shapes: the same inputs give the same bits.  ISLAM_EARG before any HIP call for N < 2, R < 0, Rc outside [0, R], ldy < R, ldg too
+ * small, an anchor outside [-1, N), a missing array, a workspace that is too small, or an index of cols / pairs out of range. */
+size_t islam_pvgo_band_inverse_workspace_bytes(int N, int R);
+int islam_pvgo_band_inverse_columns(const double* Hd, const double* Ho, int N, int anchor, const int64_t* cols /* host */, int R,
+                                    const int seg_len[2], void* workspace, size_t workspace_bytes, double* Y, int ldy,
+                                    int* status /* device */, void* stream);
+int islam_pvgo_band_cov_blocks(const double* Sd, const double* So, const double* Y, int ldy, int N, int anchor,
+                               const int64_t* cols /* host */, int R, int Rc, const double* G, int ldg, const int64_t* pairs /* host */,
+                               int P, void* workspace, size_t workspace_bytes, double* node_cov, double* pair_cov,
+                               int* status /* device */, void* stream);
 /* vo_loss forward/backward (pvgo.py:67-78 with PyPose's left-tangent gradient convention).
  * fwd: e (E,6) = Log(P^-1 Xi^-1 Xj); trans_loss, rot_loss (E).  bwd: grad_poses (E,7), last column 0. */
 int islam_pvgo_vo_loss_fwd(const double* nodes, const int64_t* edges, const double* poses, int E,

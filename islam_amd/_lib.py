@@ -198,6 +198,11 @@ SIGNATURES = {
     'islam_dense_chol_inverse_workspace_bytes': (c_size_t, [c_int]),
     'islam_dense_chol_invert_factor': (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'islam_pvgo_dense_cov_blocks': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'islam_pvgo_band_inverse_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'islam_pvgo_band_inverse_columns': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
+                                                c_void_p, c_int, c_void_p, c_void_p]),
+    'islam_pvgo_band_cov_blocks': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                           c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     'islam_pvgo_vo_loss_fwd': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
     'islam_pvgo_vo_loss_bwd': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 2),
     'islam_pvgo_align': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),

@@ -33,7 +33,7 @@
 // stage-level versions behind the islam_pvgo_* entry points the sharded driver and the tests call.
 //
 // Layout of this translation unit: device parts, host helpers and planner, the loop drivers (single GPU, then sharded), ONE
-// extern "C" block with every entry point, the marginal covariances.
+// extern "C" block with every entry point, the marginal covariances (chains, then loop-closure graphs in band form).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -568,3 +568,4 @@ int islam_pvgo_trial_elim_burst(const double* nodes, const double* vels, const d
 }  // extern "C"
 
 #include "pvgo_marginals.inl"   // marginal covariances: partitioned selected inversion
+#include "pvgo_band_cov.inl"   // marginal covariances of loop-closure graphs: Woodbury correction on the band form

@@ -1417,6 +1417,77 @@ def pvgo_dense_cov_blocks(A, anchor=None, pairs=None):
     return node_cov, pair_cov
 
 
+def pvgo_band_inverse_workspace(N, R, device):
+    nbytes = lib().islam_pvgo_band_inverse_workspace_bytes(N, R)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _host_int64(x, shape):
+    x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return np.ascontiguousarray(x.reshape(shape), dtype=np.int64)
+
+
+def pvgo_band_inverse_columns(Hd, Ho, cols, anchor=0, seg_len=(0, 0), workspace=None, status=None):
+    """islam_pvgo_band_inverse_columns: Y (9N, R) with Y[:, r] = B_a^-1 e_cols[r], B_a the block-tridiagonal (Hd, Ho) (N,9,9) with the pose
+    DoF of node ``anchor`` held fixed (None: no gauge fix); cols: R DoF indices 9 * node + c (sequence, array or tensor; read on the host).
+    Hd, Ho are not modified.  workspace: pvgo_band_inverse_workspace(N, R, device); status: a device int32 tensor of one element that
+    receives ISLAM_OK / ISLAM_ENOTPD.  Enqueue only.  Returns Y."""
+    require_cuda(Hd, Ho, status)
+    N = Hd.shape[0]
+    if tuple(Hd.shape) != (N, 9, 9) or tuple(Ho.shape[1:]) != (9, 9) or Ho.shape[0] < N - 1 or Ho.shape[0] > N:
+        raise ValueError('pvgo_band_inverse_columns: Hd (N,9,9), Ho (N-1,9,9) or (N,9,9) expected')
+    for x in (Hd, Ho):
+        if x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError('pvgo_band_inverse_columns: contiguous float64 arrays expected')
+    ch = _host_int64(cols, (-1,))
+    R = ch.shape[0]
+    if workspace is None:
+        workspace = pvgo_band_inverse_workspace(N, R, Hd.device)
+    ws, nbytes = workspace
+    Y = torch.empty((9 * N, R), dtype=torch.float64, device=Hd.device)
+    sl = (c_int * 2)(int(seg_len[0]), int(seg_len[1]))
+    check(lib().islam_pvgo_band_inverse_columns(ptr(Hd), ptr(Ho), N, -1 if anchor is None else int(anchor), c_void_p(ch.ctypes.data if R else 0),
+                                                R, sl, ptr(ws), c_size_t(nbytes), ptr(Y) if R else c_void_p(0), R, ptr(status),
+                                                stream_ptr(Hd.device)))
+    return Y
+
+
+def pvgo_band_cov_blocks(Sd, So, Y, cols, Rc, G, anchor=0, pairs=None, workspace=None, status=None):
+    """islam_pvgo_band_cov_blocks: node_cov (N,9,9) = Sd[k] - V_k Y_k^T and pair_cov (P,9,9) = base(a, b) - V_a Y_b^T with V = Y[:, :Rc] G
+    on the fp64 matrix cores.  Sd (N,9,9), So (N-1,9,9): pvgo_marginals of the band; Y (9N, R): pvgo_band_inverse_columns for ``cols``
+    (read on the host), whose first Rc entries are the closure ends' pose DoF; G (Rc, Rc) symmetric, or None when Rc = 0 (it is padded
+    with zeros to a multiple of 16 here); pairs: (P,2) integers read on the host, or None.  workspace: pvgo_band_inverse_workspace(N, R,
+    device); status: a device int32 tensor of one element that receives ISLAM_OK / ISLAM_ENOTPD.  Enqueue only."""
+    require_cuda(Sd, So, Y, G, status)
+    N, dev = Sd.shape[0], Sd.device
+    ch = _host_int64(cols, (-1,))
+    R, Rc = ch.shape[0], int(Rc)
+    if tuple(Sd.shape) != (N, 9, 9) or tuple(So.shape) != (max(N - 1, 0), 9, 9) or Y.dim() != 2 or Y.shape[0] != 9 * N or Y.shape[1] < R:
+        raise ValueError('pvgo_band_cov_blocks: Sd (N,9,9), So (N-1,9,9), Y (9N, >= R) expected')
+    if not 0 <= Rc <= R or (Rc > 0 and (G is None or tuple(G.shape) != (Rc, Rc))):
+        raise ValueError('pvgo_band_cov_blocks: 0 <= Rc <= R and G (Rc, Rc) expected')
+    for x in (Sd, So, Y, G):
+        if x is not None and (x.dtype != torch.float64 or not x.is_contiguous()):
+            raise ValueError('pvgo_band_cov_blocks: contiguous float64 arrays expected')
+    ph = _host_int64(pairs, (-1, 2)) if pairs is not None else np.zeros((0, 2), dtype=np.int64)
+    P = ph.shape[0]
+    Gp, ldg = None, 0
+    if Rc > 0:
+        ldg = (Rc + 15) // 16 * 16
+        Gp = torch.zeros((ldg, ldg), dtype=torch.float64, device=dev)
+        Gp[:Rc, :Rc] = G
+    if workspace is None:
+        workspace = pvgo_band_inverse_workspace(N, R, dev)
+    ws, nbytes = workspace
+    node_cov = torch.empty((N, 9, 9), dtype=torch.float64, device=dev)
+    pair_cov = torch.empty((P, 9, 9), dtype=torch.float64, device=dev)
+    check(lib().islam_pvgo_band_cov_blocks(ptr(Sd), ptr(So), ptr(Y) if R else c_void_p(0), int(Y.shape[1]), N, -1 if anchor is None else int(anchor),
+                                           c_void_p(ch.ctypes.data if R else 0), R, Rc, ptr(Gp), ldg, c_void_p(ph.ctypes.data if P else 0), P,
+                                           ptr(ws), c_size_t(nbytes), ptr(node_cov), ptr(pair_cov) if P else c_void_p(0), ptr(status),
+                                           stream_ptr(dev)))
+    return node_cov, pair_cov
+
+
 def pvgo_align(nodes, vels, target7):
     N = nodes.shape[0]
     no, vo = torch.empty_like(nodes), torch.empty_like(vels)

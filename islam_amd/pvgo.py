@@ -13,6 +13,8 @@ the optional sparse reprojection factor ``reproj``, islam_amd/dense_ba.py).
 like PyPose's ``pp.optim.LM(kernel=...)``; None keeps the plain least-squares loop.
 ``info`` (islam_amd.information.PvgoInfo) gives every factor its own information matrix instead; None keeps
 the four scalars.
+``marginals``: True appends the marginal covariances at the returned state (chains: section 3.9; loop-closure graphs with
+general_solver='dense_hip': section 3.18); 'band' serves loop-closure graphs with every solver from the band form (section 3.21).
 """
 import numpy as np
 import torch
@@ -45,6 +47,8 @@ def _reproj_struct(reproj, loss_weight, dev):
 
 
 _DENSE_MAX_NODES = 12000      # the dense general-topology path holds (9N)^2 doubles
+_BAND_MAX_COLUMN_BYTES = 4 << 30      # the band covariances hold 9N x R doubles, the R columns of B_a^-1 (pvgo_dense.band_columns)
+_GRAPH_MARGINAL_METHODS = ('dense', 'band')
 
 
 def _graph_inputs(dev, *xs):
@@ -146,44 +150,63 @@ class PvgoGraphMarginals(_Marginals):
 
     node_cov (N,9,9): Sigma_kk; pairs (P,2) int64 and pair_cov (P,9,9): Sigma_ab for every requested pair (a, b), rows node a, columns
     node b; pose_cov (N,6,6) and vel_cov (N,3,3): the pose and velocity blocks of node_cov.  Per-node ordering, perturbation convention
-    and the meaning of ``anchor`` are those of PvgoMarginals."""
+    and the meaning of ``anchor`` are those of PvgoMarginals.  method: 'dense' (section 3.18) or 'band' (section 3.21), how it was computed."""
 
-    def __init__(self, node_cov, pairs, pair_cov, anchor):
+    def __init__(self, node_cov, pairs, pair_cov, anchor, method='dense'):
         super().__init__(node_cov, anchor)
-        self.pairs, self.pair_cov = pairs, pair_cov
+        self.pairs, self.pair_cov, self.method = pairs, pair_cov, method
 
 
-def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, pairs, info=None):
-    from .pvgo_dense import marginals_dense
+def _check_band_columns(N, links_host, anchor, pairs):
+    """The one size limit of method='band', checked on the host before any device work: the R columns of B_a^-1 (9N doubles each) must fit."""
+    from .pvgo_dense import band_columns
+    if pairs is not None:
+        pairs = np.asarray(pairs.detach().cpu() if isinstance(pairs, torch.Tensor) else pairs).reshape(-1, 2)
+    R = band_columns(N, links_host, anchor, links_host if pairs is None else pairs)[0].size
+    if 9 * N * R * 8 > _BAND_MAX_COLUMN_BYTES:
+        raise UnsupportedGraphError('band covariances hold 9N x R doubles: N = %d nodes and R = %d columns (closure ends and far pairs) '
+                                    'exceed %d bytes' % (N, R, _BAND_MAX_COLUMN_BYTES))
+
+
+def _graph_marginals_at(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, rp, anchor, pairs, info=None, method='dense'):
+    from .pvgo_dense import marginals_band, marginals_dense
     N = nodes.shape[0]
-    if N > _DENSE_MAX_NODES:
+    if method == 'dense' and N > _DENSE_MAX_NODES:
         raise UnsupportedGraphError('dense covariances are sized for N <= %d nodes, (9N)^2 doubles (got %d nodes)' % (_DENSE_MAX_NODES, N))
     if pairs is None:
         pairs = edges
     pairs = pairs.detach().cpu() if isinstance(pairs, torch.Tensor) else torch.as_tensor(np.asarray(pairs))
     pairs = pairs.to(torch.int64).reshape(-1, 2)
-    node_cov, pair_cov = marginals_dense(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=rp, anchor=anchor,
-                                         pairs=pairs, info=info)
-    return PvgoGraphMarginals(node_cov, pairs.to(nodes.device), pair_cov, anchor)
+    fn = marginals_band if method == 'band' else marginals_dense
+    node_cov, pair_cov = fn(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=rp, anchor=anchor, pairs=pairs, info=info)
+    return PvgoGraphMarginals(node_cov, pairs.to(nodes.device), pair_cov, anchor, method)
 
 
 def pvgo_marginals_general(nodes, vels, vo_motions, links, dts, imu_drots, imu_dtrans, imu_dvels, loss_weight=(1, 1, 1, 1), reproj=None,
-                           anchor=0, pairs=None, info=None):
+                           anchor=0, pairs=None, info=None, method='dense'):
     """Marginal covariances of the poses and velocities of a graph with arbitrary ``links`` (loop closures; canonical chains too) at the
     given state: Sigma = A^-1 with A = J^T W J the undamped Gauss-Newton matrix of run_pvgo's graph, the pose DoF of node ``anchor``
-    held fixed (None: no gauge fix).  Dense: the project's Cholesky, the inverse of its factor in place and the requested blocks
-    (islam_amd.pvgo_dense.marginals_dense), N <= 12000.  pairs (P,2): the node pairs whose cross-covariance is wanted; None: ``links``.
-    info: a PvgoInfo (A = sum J^T Omega J; not with ``reproj``).
+    held fixed (None: no gauge fix).  method='dense': the project's Cholesky, the inverse of its factor in place and the requested blocks
+    (islam_amd.pvgo_dense.marginals_dense), N <= 12000.  method='band': the chain's selected inverse of the block-tridiagonal part and a
+    Woodbury correction for the off-band edges (islam_amd.pvgo_dense.marginals_band): memory O(N R) with R the
+    pose DoF of the closure ends and no limit on N, but digits are lost with the length of the graph (it agrees with 'dense' to 1e-10
+    at 65 nodes, 1e-6 at 200, 1e-2 at 3000, and is refused with ISLAM_ENOTPD where a variance comes out non-positive).
+    pairs (P,2): the node pairs whose cross-covariance is wanted; None: ``links``.  info: a PvgoInfo (A = sum J^T Omega J; not with
+    ``reproj``).
     Returns a PvgoGraphMarginals; raises IslamHipError (ISLAM_ENOTPD) when the anchored matrix is not positive definite."""
     dev = pp._plain(torch.as_tensor(nodes)).device
     if dev.type != 'cuda':
         raise RuntimeError('islam_amd.pvgo_marginals_general runs on the MI355X only; there is no CPU fallback')
-    _validate_links(len(nodes), links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
+    if method not in _GRAPH_MARGINAL_METHODS:
+        raise ValueError("method must be 'dense' or 'band'")
+    links_host = _validate_links(len(nodes), links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
+    if method == 'band':
+        _check_band_columns(len(nodes), links_host, anchor, pairs)
     packed = _packed_info(info, len(links), len(nodes) - 1, loss_weight, dev, reproj)
     n64, v64, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, nodes, vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
     edges = torch.as_tensor(links).to(dev, torch.int64).contiguous()
     return _graph_marginals_at(n64, v64, edges, poses, drots, dtrans, dvels, dts64.reshape(-1), loss_weight, _reproj_struct(reproj, loss_weight, dev),
-                               anchor, pairs, info=packed)
+                               anchor, pairs, info=packed, method=method)
 
 
 _GENERAL_SOLVERS = ('auto', 'dense', 'dense_hip', 'band_pcg')
@@ -203,6 +226,9 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError("islam_amd.run_pvgo runs on the MI355X only (device=%r); there is no CPU fallback" % (device,))
+    if not (isinstance(marginals, (bool, int)) or marginals == 'band'):
+        raise ValueError("marginals must be False, True or 'band' (got %r)" % (marginals,))
+    band_marginals = isinstance(marginals, str)           # 'band': covariances of a loop-closure graph from its band form (section 3.21)
     packed = _packed_info(info, len(links), len(init_nodes) - 1, loss_weight, dev, reproj, kernel)
     robust = None
     if kernel is not None:
@@ -216,12 +242,14 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
     chain = _is_canonical_chain(links, N)
     if not chain and general_solver not in _GENERAL_SOLVERS:
         raise ValueError("general_solver must be 'auto', 'dense', 'dense_hip' or 'band_pcg'")
-    if marginals and not chain and general_solver != 'dense_hip':
+    if marginals and not band_marginals and not chain and general_solver != 'dense_hip':
         raise UnsupportedGraphError('marginals=True serves canonical chains (links[k] = [k, k+1]) only; covariances of '
                                     "loop-closure graphs are not implemented (except with general_solver='dense_hip': the dense "
                                     'selected inverse, pvgo_marginals_general)')
     if not chain:        # any number of VO edges on the N nodes; refused before anything reaches the device
-        _validate_links(N, links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
+        links_host = _validate_links(N, links, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
+        if band_marginals:
+            _check_band_columns(N, links_host, 0, None)
     rp = _reproj_struct(reproj, loss_weight, dev)
     out_dtype = pp._plain(init_nodes).dtype if isinstance(init_nodes, torch.Tensor) else torch.get_default_dtype()
     nodes, vels, poses, drots, dtrans, dvels, dts64 = _graph_inputs(dev, init_nodes, init_vels, vo_motions, imu_drots, imu_dtrans, imu_dvels, dts)
@@ -265,8 +293,9 @@ def run_pvgo(init_nodes, init_vels, vo_motions, links, dts, imu_drots, imu_dtran
 
     an, av = ops.pvgo_align(nodes, vels, target0)
     marg = None
-    if marginals and not chain:     # general_solver='dense_hip': dense selected inverse at the aligned fp64 state, anchor 0, pairs = links
-        marg = _graph_marginals_at(an, av, edges, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, None, info=packed)      # (the LM's matrix is gone)
+    if marginals and not chain:     # at the aligned fp64 state, anchor 0, pairs = links (the LM's matrix is gone): the dense selected inverse
+        marg = _graph_marginals_at(an, av, edges, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, None, info=packed,      # (True, with
+                                   method='band' if band_marginals else 'dense')      # general_solver='dense_hip') or the band form ('band')
     elif marginals:      # at the aligned fp64 state the caller receives; stream-ordered, its status rides on the host copy below
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
         marg = _marginals_at(an, av, poses, drots, dtrans, dvels, dts64, loss_weight, rp, 0, seg_len=seg_len, status=status, info=packed)

@@ -388,7 +388,78 @@ class _BandSystem:
         return ops.pvgo_band_matvec(self.Hd, self.Ho, p.contiguous(), self.topo.optr, self.topo.oadj, self.io, self.jo, self.So)
 
 
-PCG_FAIL_RTOL = 1e-8      # true relative residual above which a PCG solve counts as failed
+def band_columns(N, edges_host, anchor, pairs_host):
+    """The columns of B_a^-1 that the band covariances need, as global DoF indices 9 * node + c: int64, in two
+    parts, each ascending and without repeats.  Closure part (Rc entries): c = 0..5 of every node that is an end of an off-band edge.
+    Extra part: c = 0..8 of the second node b of every requested pair (a, b) with |a - b| > 1, minus what the closure part holds.
+    The pose indices of node ``anchor`` (None: no such node) are left out of both.  Returns (cols, Rc)."""
+    eh = np.asarray(edges_host, dtype=np.int64).reshape(-1, 2)
+    ph = np.zeros((0, 2), dtype=np.int64) if pairs_host is None else np.asarray(pairs_host, dtype=np.int64).reshape(-1, 2)
+    for name, a in (('edges', eh), ('pairs', ph)):
+        if a.size and (a.min() < 0 or a.max() >= N):
+            raise ValueError('band_columns: %s hold a node index outside [0, %d)' % (name, N))
+    dof = lambda nodes, k: (9 * nodes[:, None] + np.arange(k, dtype=np.int64)[None, :]).reshape(-1)
+    free = lambda c: c if anchor is None else c[~((c // 9 == int(anchor)) & (c % 9 < 6))]
+    closure = free(dof(np.unique(eh[off_band_edges(eh)].reshape(-1)), 6))
+    far = np.unique(ph[np.abs(ph[:, 0] - ph[:, 1]) > 1, 1])
+    extra = np.setdiff1d(free(dof(far, 9)), closure)
+    return np.concatenate([closure, extra]).astype(np.int64), int(closure.size)
+
+
+def _capacitance(band, off_ends, Y, cols, Rc, anchor):
+    """G = (I + M Y_S)^-1 M (Rc x Rc, symmetrised) of the Woodbury form: M = R on the closure ends' pose DoF cols[:Rc] -- the block -So[t] at
+    (io[t], jo[t]) and at (jo[t], io[t]), So[t] symmetric; an edge that ends at the anchor has no block -- and Y_S = Y[cols[:Rc], :Rc].
+    Edge after edge in list order, so that parallel closures accumulate in a fixed order."""
+    dev = Y.device
+    where = {int(c): r for r, c in enumerate(cols[:Rc]) if c % 9 == 0}                   # first pose DoF of a node -> its position
+    M = torch.zeros((Rc, Rc), dtype=torch.float64, device=dev)
+    for t, (i, j) in enumerate(off_ends.tolist()):                        # (io[t], jo[t]) of the band, known on the host
+        if i == anchor or j == anchor:
+            continue
+        pi, pj = where[9 * i], where[9 * j]
+        M[pi:pi + 6, pj:pj + 6] -= band.So[t]
+        M[pj:pj + 6, pi:pi + 6] -= band.So[t]
+    YS = Y[torch.from_numpy(cols[:Rc]).to(dev), :Rc]
+    # (solve_ex: no error check, so no synchronisation; a singular capacitance comes with a band that failed its own status)
+    G = torch.linalg.solve_ex(torch.eye(Rc, dtype=torch.float64, device=dev) + M @ YS, M)[0]
+    return (0.5 * (G + G.t())).contiguous()
+
+
+def marginals_band(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_weight, reproj=None, anchor=0, pairs=None, info=None):
+    """marginals_dense without any (9N)^2 array: the same Sigma = A^-1 from the band form A = B + R of
+    _BandSystem (no clamp, the diagonal untouched), Sigma = B_a^-1 - Y_c G Y_c^T: the chain's selected inverse of B (ops.pvgo_marginals),
+    the columns of B_a^-1 at the closure ends (band_columns, ops.pvgo_band_inverse_columns), the capacitance solve in torch, and the
+    correction on the fp64 matrix cores (ops.pvgo_band_cov_blocks).  Memory O(N R), R <= 12 K + 9 (far pairs).  B_a is the open chain,
+    far worse conditioned than A: the difference above loses digits with the length of the graph (section 3.21 has the figures).
+    Arguments and return value as marginals_dense; raises IslamHipError (ISLAM_ENOTPD) when B_a is not positive definite or a variance
+    comes out non-positive."""
+    N, dev = nodes.shape[0], nodes.device
+    if anchor is not None and not 0 <= int(anchor) < N:
+        raise ValueError('anchor=%r is not a node of a graph of %d nodes' % (anchor, N))
+    if info is not None and reproj is not None:
+        raise NotImplementedError('per-factor information with the reprojection factor is not implemented')
+    anchor = None if anchor is None else int(anchor)
+    eh = _validate_device_graph(nodes, edges, poses, drots, dtrans, dvels, dts)
+    ph = eh if pairs is None else np.asarray(pairs.detach().cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    cols, Rc = band_columns(N, eh, anchor, ph)
+    g = _Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info)
+    vo, lin = g.linearize(nodes, vels)
+    rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
+    band = _BandSystem(vo, lin, edges, dts, N, g.w, -_NOCLAMP, _NOCLAMP, _BandTopology(eh, N, dev), rpt, info=info)
+    status = torch.zeros((3,), dtype=torch.int32, device=dev)
+    Sd, So = ops.pvgo_marginals(band.Hd, band.Ho, anchor=anchor, status=status[0:1])
+    ws = ops.pvgo_band_inverse_workspace(N, cols.size, dev)
+    Y = ops.pvgo_band_inverse_columns(band.Hd, band.Ho, cols, anchor, workspace=ws, status=status[1:2])
+    G = _capacitance(band, eh[off_band_edges(eh)], Y, cols, Rc, anchor) if Rc else None
+    node_cov, pair_cov = ops.pvgo_band_cov_blocks(Sd, So, Y, cols, Rc, G, anchor, ph, workspace=ws, status=status[2:3])
+    bad = status.tolist()                                               # the one read-back
+    if any(bad):
+        what = 'the band B is not positive definite' if bad[0] or bad[1] else 'a variance is not positive'
+        raise IslamHipError(-3, 'marginals_band: %s (anchored matrix not positive definite)' % what)
+    return node_cov, pair_cov
+
+
+PCG_FAIL_RTOL = 1e-8     # true relative residual above which a PCG solve counts as failed
 
 
 def _pcg(sysm, ws, rtol=1e-13, check_every=6):
