@@ -48,13 +48,10 @@ __global__ __launch_bounds__(64) void vo_edge_linearize_kernel(const double* __r
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= E) return;
     SE3<double> Xi = se3_load(nodes + 7 * edges[2 * e]), Xj = se3_load(nodes + 7 * edges[2 * e + 1]);
-    SE3<double> pre = se3_mul(se3_inv(se3_load(poses + 7 * e)), se3_inv(Xi));
+    SE3<double> pre;
     V3<double> rho, phi;
-    se3_log(se3_mul(pre, Xj), rho, phi);
-    M3<double> Ji = so3_Jl_inv(phi);
-    M3<double> R = qmat(pre.q);
-    M3<double> G = Ji * R;
-    M3<double> C = Ji * (skew(pre.t) * R - se3_Q(rho, phi) * G);
+    M3<double> G, C;
+    vo_link(Xi, Xj, se3_load(poses + 7 * e), pre, rho, phi, G, C);
     double rec[24];
     rec[0] = rho.x; rec[1] = rho.y; rec[2] = rho.z; rec[3] = phi.x; rec[4] = phi.y; rec[5] = phi.z;
     m3_store(G, rec + 6);

@@ -6,14 +6,38 @@ struct LinkRes {
     V3<double> erho, ephi, er, rv, rt;
     SE3<double> pre;      // P^-1 * Xi^-1
     Q4<double> rpre;      // dR^-1 * Ri^-1
+    M3<double> Ji;        // Jl^-1(ephi), as se3_log formed it
 };
+
+// The pose-graph (VO) factor of one link or edge, stated ONCE for every kernel that linearises it (linearize_kernel, linbuild_kernel,
+// trial_lin_kernel, small_lm_kernel, phase B of trial_elim_kernel, vo_edge_linearize_kernel): the same statements in the same order
+// are what keeps their linearisations bit-identical.
+// residual e = [erho, ephi] = Log(P^-1 Xi^-1 Xj), with pre = P^-1 Xi^-1 and Ji = Jl^-1(ephi)
+__device__ __forceinline__ void vo_residual(SE3<double> Xi, SE3<double> Xj, SE3<double> P, SE3<double>& pre, V3<double>& erho,
+                                            V3<double>& ephi, M3<double>& Ji) {
+    pre = se3_mul(se3_inv(P), se3_inv(Xi));
+    se3_log(se3_mul(pre, Xj), erho, ephi, Ji);
+}
+// d e / d delta_j = Jl^-1(e) Ad(pre) = [[G, C],[0, G]]:  G = Ji R,  C = Ji ([t]x R - Q G)   (d e / d delta_i = -that)
+__device__ __forceinline__ void vo_jacobians(const SE3<double>& pre, V3<double> erho, V3<double> ephi, const M3<double>& Ji,
+                                             M3<double>& G, M3<double>& C) {
+    const M3<double> R = qmat(pre.q);
+    G = Ji * R;
+    C = Ji * (skew(pre.t) * R - se3_Q(erho, ephi) * G);
+}
+// both at once: (erho, ephi, G, C) of the link; pre is handed back for the callers that go on from it
+__device__ __forceinline__ void vo_link(SE3<double> Xi, SE3<double> Xj, SE3<double> P, SE3<double>& pre, V3<double>& erho,
+                                        V3<double>& ephi, M3<double>& G, M3<double>& C) {
+    M3<double> Ji;
+    vo_residual(Xi, Xj, P, pre, erho, ephi, Ji);
+    vo_jacobians(pre, erho, ephi, Ji, G, C);
+}
 
 __device__ __forceinline__ LinkRes link_residuals(SE3<double> Xi, SE3<double> Xj, V3<double> vi, V3<double> vj,
                                                   SE3<double> P, Q4<double> dR, V3<double> dp, V3<double> dv,
                                                   double dt) {
     LinkRes o;
-    o.pre = se3_mul(se3_inv(P), se3_inv(Xi));
-    se3_log(se3_mul(o.pre, Xj), o.erho, o.ephi);
+    vo_residual(Xi, Xj, P, o.pre, o.erho, o.ephi, o.Ji);
     o.rv = dv - (vj - vi);
     o.rpre = qmul(qinv(dR), qinv(Xi.q));
     o.er = so3_log(qmul(o.rpre, Xj.q));
@@ -37,10 +61,8 @@ __global__ __launch_bounds__(64) void linearize_kernel(const double* __restrict_
         LinkRes r = link_residuals(Xi, Xj, ld3(vels + 3 * k), ld3(vels + 3 * (k + 1)), se3_load(poses + 7 * k),
                                    ld4(drots + 4 * k), ld3(dtrans + 3 * k), ld3(dvels + 3 * k), dts[k]);
         // d pgerr / d delta_j = Jl^-1(e) Ad(pre) = [[Ji R, Ji([t]x R - Q Ji R)],[0, Ji R]]
-        M3<double> Ji = so3_Jl_inv(r.ephi);
-        M3<double> R = qmat(r.pre.q);
-        M3<double> G = Ji * R;
-        M3<double> C = Ji * (skew(r.pre.t) * R - se3_Q(r.erho, r.ephi) * G);
+        M3<double> G, C;
+        vo_jacobians(r.pre, r.erho, r.ephi, r.Ji, G, C);
         M3<double> B = so3_Jl_inv(r.er) * qmat(r.rpre);
         double rec[LIN_C];
         rec[0] = r.erho.x; rec[1] = r.erho.y; rec[2] = r.erho.z;
@@ -420,10 +442,7 @@ __device__ __forceinline__ double robust_link(const RobustDev& rb, V3<double> er
 
 // Jacobian blocks of one link at its residuals: d pgerr / d delta_j = [[G, C],[0, G]], d imuroterr / d phi_j = B
 __device__ __forceinline__ void link_jacobians(const LinkRes& r, M3<double>& G, M3<double>& C, M3<double>& B) {
-    const M3<double> Ji = so3_Jl_inv(r.ephi);
-    const M3<double> R = qmat(r.pre.q);
-    G = Ji * R;
-    C = Ji * (skew(r.pre.t) * R - se3_Q(r.erho, r.ephi) * G);
+    vo_jacobians(r.pre, r.erho, r.ephi, r.Ji, G, C);
     B = so3_Jl_inv(r.er) * qmat(r.rpre);
 }
 

@@ -514,7 +514,8 @@ __global__ __launch_bounds__(LB_THREADS) void small_lm_kernel(SmallArgs a) {
 //   C  all waves: node blocks Hd / Ho / rhs of the stretch in LDS, one 3x3 sub-block per thread (type-major: a wave builds one or
 //      two kinds of block, no divergence); the same blocks go to global memory, lane-contiguous (fallback solves read them)
 //   D  waves 2s, 2s+1: twisted elimination of segment s, columns read from the LDS blocks (eliminate_twisted)
-// The sums of products are formed in the order of link_emit / nodes_build_copy, so the linearisation is bit-identical to
+// The pose-graph link of B is vo_link (pvgo_linearize.inl), the one function link_residuals / link_jacobians are made of, and the
+// sums of products are formed in the order of link_emit / nodes_build_copy, so the linearisation is bit-identical to
 // linbuild_kernel's.  Saves per LM iteration: one launch, the 13.7 MB round trip of Hd / Ho / rhs through HBM on the critical
 // path, and the level-0 kernel's first dependent loads.
 constexpr int FZ_S = 4;                                    // segments per workgroup
@@ -687,13 +688,10 @@ __global__ __launch_bounds__(FZ_THREADS, 3) void trial_elim_kernel(FusedArgs a, 
         const double* xj = xi + FZ_XT;
         if (wave == 0 && valid) {
             const SE3<double> Xi = se3_load(xi), Xj = se3_load(xj);
-            const SE3<double> pre = se3_mul(se3_inv(se3_load(a.poses + 7 * L)), se3_inv(Xi));
+            SE3<double> pre;
             V3<double> erho, ephi;
-            se3_log(se3_mul(pre, Xj), erho, ephi);
-            const M3<double> Ji = so3_Jl_inv(ephi);
-            const M3<double> R = qmat(pre.q);
-            const M3<double> Gm = Ji * R;
-            const M3<double> C = Ji * (skew(pre.t) * R - se3_Q(erho, ephi) * Gm);
+            M3<double> Gm, C;
+            vo_link(Xi, Xj, se3_load(a.poses + 7 * L), pre, erho, ephi, Gm, C);          // linbuild_kernel's statements (pvgo_linearize.inl)
             if (owns) {
                 double* lo = a.lin_o + L;
                 lo[0] = erho.x; lo[Ms] = erho.y; lo[2 * Ms] = erho.z;
