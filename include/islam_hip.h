@@ -756,6 +756,18 @@ int islam_pvgo_build_normal_scaled(const double* lin, const double* dts, int N, 
  * (node k+1) the velocity blocks; dt O3 the rho-v block of node k; -dt O3 and -O1 the v-rho and v-v blocks of the coupling. */
 int islam_pvgo_build_normal_info(const double* lin, const double* dts, int N, const double* info_vo, const double* info_imu,
                                  double vmin, double vmax, double* Hd, double* Ho, double* rhs, void* stream);
+/* The IMU factors of a link as ONE correlated factor: a symmetric positive semi-definite 9x9 Omega_k on the
+ * stacked residual r9 = [rv; er; rt] (velocity, IMU rotation, translation-velocity: the order of w[1..3]).  Device layout
+ * info_imu9 (45, N-1): the upper triangle of each 9x9 in row-major order of the triangle, component-major like `lin`.  With the
+ * unchanged Jacobians J_i, J_j of link k = (i, j): Hd[i] += J_i^T O J_i, Hd[j] += J_j^T O J_j, Ho[k] += J_i^T O J_j, rhs = -J^T O r9;
+ * the VO group (info_vo (21, N-1) or NULL), the clamp and every other rule are those of islam_pvgo_build_normal_info /
+ * islam_pvgo_run_chain_info, whose arguments these two take.  Omega_k = blockdiag(O1, O2, O3) is exactly the (18, N-1) form. */
+int islam_pvgo_build_normal_info9(const double* lin, const double* dts, int N, const double* info_vo, const double* info_imu9,
+                                  double vmin, double vmax, double* Hd, double* Ho, double* rhs, void* stream);
+int islam_pvgo_run_chain_info9(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                               const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
+                               const double* info_vo, const double* info_imu9, void* workspace, size_t workspace_bytes,
+                               islam_pvgo_result* result, double* trace, int trace_cap, void* stream);
 /* Hd.diag += Hd.diag*damping (in place, cumulative), then solve -> dx (N,9).  status (device int[4]). */
 int islam_pvgo_solve_chain(double* Hd, const double* Ho, const double* rhs, double damping, int N,
                            const int seg_len[2], void* workspace, size_t workspace_bytes, double* dx, void* stream);

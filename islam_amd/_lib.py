@@ -142,6 +142,8 @@ SIGNATURES = {
                                                              c_void_p]),
     'islam_pvgo_run_chain_info': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), c_void_p, c_void_p, c_void_p, c_size_t,
                                            ctypes.POINTER(PvgoResult), c_void_p, c_int, c_void_p]),
+    'islam_pvgo_run_chain_info9': (c_int, [c_void_p] * 7 + [c_int, ctypes.POINTER(PvgoParams), c_void_p, c_void_p, c_void_p, c_size_t,
+                                            ctypes.POINTER(PvgoResult), c_void_p, c_int, c_void_p]),
     'islam_pvgo_robust_weights': (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(PvgoRobust)] + [c_void_p] * 4),
     'islam_pvgo_reproj_reduce': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(PvgoReproj), c_void_p, c_void_p]),
     'islam_pvgo_linearize': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 3),
@@ -150,6 +152,7 @@ SIGNATURES = {
     'islam_pvgo_build_normal_scaled': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_double), c_void_p, c_double, c_double] +
                                        [c_void_p] * 4),
     'islam_pvgo_build_normal_info': (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 4),
+    'islam_pvgo_build_normal_info9': (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 4),
     'islam_pvgo_solve_chain': (c_int, [c_void_p] * 3 + [c_double, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,
                                                         c_void_p, c_void_p]),
     'islam_pvgo_solve_chain_enqueue': (c_int, [c_void_p] * 3 + [c_double, c_int, ctypes.POINTER(c_int), c_void_p, c_size_t,

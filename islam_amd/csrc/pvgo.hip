@@ -121,11 +121,11 @@ int run_chain_entry(double* nodes, double* vels, const double* poses, const doub
                     const double* dvels, const double* dts, int N, const islam_pvgo_params* prm,
                     const islam_pvgo_reproj* reproj, const islam_pvgo_robust* robust, void* workspace,
                     size_t workspace_bytes, islam_pvgo_result* result, double* trace, int trace_cap, void* stream,
-                    const double* info_vo = nullptr, const double* info_imu = nullptr) {
+                    const double* info_vo = nullptr, const double* info_imu = nullptr, bool info_imu9 = false) {
     if (N < 2) return fail(ISLAM_EARG, "islam_pvgo_run_chain: N=%d < 2", N);
     if (!prm || !result) return fail(ISLAM_EARG, "islam_pvgo_run_chain: null params/result");
     if ((info_vo == nullptr) != (info_imu == nullptr))
-        return fail(ISLAM_EARG, "islam_pvgo_run_chain_info: info_vo and info_imu must both be given or both be NULL");
+        return fail(ISLAM_EARG, "islam_pvgo_run_chain_info%s: info_vo and info_imu must both be given or both be NULL", info_imu9 ? "9" : "");
     int rc;
     ReprojDev rp{};
     if (reproj && (rc = reproj_dev(reproj, rp)) != ISLAM_OK) return rc;
@@ -137,7 +137,7 @@ int run_chain_entry(double* nodes, double* vels, const double* poses, const doub
     if (rc != ISLAM_OK) return rc;
     hipStream_t s = as_stream(stream);
     rc = run_chain_impl(nodes, vels, ChainData{poses, drots, dtrans, dvels, dts, N}, prm, reproj, rp, w, s, result, trace, trace_cap,
-                        robust_on ? &rb : nullptr, info_vo, info_imu);
+                        robust_on ? &rb : nullptr, info_vo, info_imu, info_imu9);
     return rc == ISLAM_OK ? rc : abandon_run(w.state, s, rc);
 }
 }  // namespace
@@ -200,6 +200,17 @@ int islam_pvgo_build_normal_info(const double* lin, const double* dts, int N, co
         return fail(ISLAM_EARG, "islam_pvgo_build_normal_info: N=%d < 2 or a null lin / dts / info_imu / output", N);
     hipLaunchKernelGGL(info_build_kernel, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, info_vo, info_imu, vmin, vmax, Hd,
                        Ho, rhs, Gate{nullptr, 0.0});
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// one correlated 9x9 per link: info_imu9 (45, N-1)
+int islam_pvgo_build_normal_info9(const double* lin, const double* dts, int N, const double* info_vo, const double* info_imu9, double vmin,
+                                  double vmax, double* Hd, double* Ho, double* rhs, void* stream) {
+    if (N < 2 || !lin || !dts || !info_imu9 || !Hd || !Ho || !rhs)
+        return fail(ISLAM_EARG, "islam_pvgo_build_normal_info9: N=%d < 2 or a null lin / dts / info_imu9 / output", N);
+    hipLaunchKernelGGL(info9_build_kernel, dim3((N + 63) / 64), dim3(64), 0, as_stream(stream), lin, dts, N, info_vo, info_imu9, vmin, vmax,
+                       Hd, Ho, rhs, Gate{nullptr, 0.0});
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
@@ -508,6 +519,15 @@ int islam_pvgo_run_chain_info(double* nodes, double* vels, const double* poses, 
                               int trace_cap, void* stream) {
     return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, nullptr, workspace, workspace_bytes, result,
                            trace, trace_cap, stream, info_vo, info_imu);
+}
+
+// the same loop with one correlated 9x9 per link: info9_build_kernel behind every linearisation
+int islam_pvgo_run_chain_info9(double* nodes, double* vels, const double* poses, const double* drots, const double* dtrans,
+                               const double* dvels, const double* dts, int N, const islam_pvgo_params* prm, const double* info_vo,
+                               const double* info_imu9, void* workspace, size_t workspace_bytes, islam_pvgo_result* result, double* trace,
+                               int trace_cap, void* stream) {
+    return run_chain_entry(nodes, vels, poses, drots, dtrans, dvels, dts, N, prm, nullptr, nullptr, workspace, workspace_bytes, result,
+                           trace, trace_cap, stream, info_vo, info_imu9, true);
 }
 
 // Measurement hook (bench.py's roofline leg): the LM loop's dominant launch, trial_elim_kernel, exactly as islam_pvgo_run_chain

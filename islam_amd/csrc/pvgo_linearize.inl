@@ -282,6 +282,132 @@ __global__ __launch_bounds__(64) void info_build_kernel(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
+// Correlated IMU information: ONE 9x9 Omega per link on the stacked residual r9 = [rv; er; rt], packed as
+// info_imu9 (45, M) = its upper triangle in row-major order of the triangle, component-major.  With J_j = [[0,0,-I],[0,B,0],[I,0,0]]
+// (rows v, r, t; columns rho, phi, v) and J_i = -J_j - dt E, E = I at (t rows, v columns), everything a link adds follows from
+// P = J_j^T Omega J_j and its rho row [P_rr, P_rp, P_rv] = Omega_t. J_j:
+//   Hd[j] += P;   Hd[i] += P + dt (column v += [P_rr; P_rp^T; P_rv^T], row v += its transpose) + dt^2 P_rr on v-v;
+//   Ho[k] = -P, row v -= dt [P_rr, P_rp, P_rv];   g_j = J_j^T y,  g_i = -g_j - dt [0; 0; y_t],  y = Omega r9.
+constexpr int tri9(int r, int c) { return r * 9 - r * (r - 1) / 2 + (c - r); }       // r <= c
+
+struct InfoLink9 {        // the IMU part of one link: the upper blocks of P in node order [rho, phi, v], and J_j^T Omega r9
+    M3<double> Prr, Prp, Prv, Ppp, Ppv, Pvv;
+    V3<double> gr, gp, gv;
+};
+
+__device__ __forceinline__ InfoLink9 info_link9(const double* __restrict__ lin, int M, int k, const double* __restrict__ info_imu9) {
+    const double* r = lin + k;
+    const double* w = info_imu9 + k;
+    const size_t ld = (size_t)M;
+    auto v3at = [&](int c) { return V3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]}; };
+    auto W = [&](int a, int b) { return w[tri9(a, b) * ld]; };
+    auto symblk = [&](int o) {
+        const double a = W(o, o), b = W(o, o + 1), c = W(o, o + 2), d = W(o + 1, o + 1), e = W(o + 1, o + 2), f = W(o + 2, o + 2);
+        return M3<double>{a, b, c, b, d, e, c, e, f};
+    };
+    auto offblk = [&](int a, int b) {
+        return M3<double>{W(a, b), W(a, b + 1), W(a, b + 2), W(a + 1, b), W(a + 1, b + 1), W(a + 1, b + 2),
+                          W(a + 2, b), W(a + 2, b + 1), W(a + 2, b + 2)};
+    };
+    const M3<double> B{r[27 * ld], r[28 * ld], r[29 * ld], r[30 * ld], r[31 * ld], r[32 * ld], r[33 * ld], r[34 * ld], r[35 * ld]};
+    const V3<double> eR = v3at(24), rv = v3at(36), rt = v3at(39);
+    const M3<double> Wvv = symblk(0), Wrr = symblk(3), Wtt = symblk(6);
+    const M3<double> Wvr = offblk(0, 3), Wvt = offblk(0, 6), Wrt = offblk(3, 6);
+    const M3<double> Bt = transpose(B);
+    InfoLink9 o;
+    o.Prr = Wtt;
+    o.Prp = transpose(Wrt) * B;                                     // Omega_tr B
+    o.Prv = -1.0 * transpose(Wvt);                                  // -Omega_tv
+    o.Ppp = sym_part(Bt * (Wrr * B));
+    o.Ppv = -1.0 * (Bt * transpose(Wvr));                           // -B^T Omega_rv
+    o.Pvv = Wvv;
+    const V3<double> yv = Wvv * rv + Wvr * eR + Wvt * rt;
+    const V3<double> yr = tmul(Wvr, rv) + Wrr * eR + Wrt * rt;
+    o.gr = tmul(Wvt, rv) + tmul(Wrt, eR) + Wtt * rt;                // y_t
+    o.gp = tmul(B, yr);
+    o.gv = -yv;
+    return o;
+}
+
+// the VO group of link k (6x6 Omega0), as info_link adds it
+__device__ __forceinline__ InfoVo info_link_vo(const double* __restrict__ lin, int M, int k, const double* __restrict__ info_vo) {
+    const double* r = lin + k;
+    const size_t ld = (size_t)M;
+    auto v3at = [&](int c) { return V3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]}; };
+    auto m3at = [&](int c) {
+        return M3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld], r[(c + 3) * ld], r[(c + 4) * ld], r[(c + 5) * ld],
+                          r[(c + 6) * ld], r[(c + 7) * ld], r[(c + 8) * ld]};
+    };
+    return info_vo_normal(info_vo + k, ld, m3at(6), m3at(15), v3at(0), v3at(3));
+}
+
+// info_build_kernel for the correlated form: the same gather (link k-1 as its j end, then link k as its i end), the same outputs, gate
+// and clamp.  One lane per node; Ho[k] is stored as soon as link k is formed.  No atomics, no waits: a second call gives the same bits.
+__global__ __launch_bounds__(64) void info9_build_kernel(const double* __restrict__ lin, const double* __restrict__ dts, int N,
+                                                          const double* __restrict__ info_vo, const double* __restrict__ info_imu9,
+                                                          double vmin, double vmax, double* __restrict__ Hd, double* __restrict__ Ho,
+                                                          double* __restrict__ rhs, Gate gate) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= N || gate_closed(gate)) return;
+    const int M = N - 1;
+    const M3<double> Z{0, 0, 0, 0, 0, 0, 0, 0, 0};
+    M3<double> Hrr = Z, Hrp = Z, Hrv = Z, Hpp = Z, Hpv = Z, Hvv = Z;
+    V3<double> gr{0, 0, 0}, gp{0, 0, 0}, gv{0, 0, 0};
+    // (sched_barrier between the IMU and the VO part of a link: left to itself the scheduler issues every load of both up front and
+    // runs out of registers; in this order the peak is one part's operands plus the accumulators)
+    if (k > 0) {                       // link k-1, this node is its "j" end
+        const InfoLink9 L = info_link9(lin, M, k - 1, info_imu9);
+        Hrr = L.Prr; Hrp = L.Prp; Hrv = L.Prv; Hpp = L.Ppp; Hpv = L.Ppv; Hvv = L.Pvv;
+        gr = L.gr; gp = L.gp; gv = L.gv;
+        __builtin_amdgcn_sched_barrier(0);
+        if (info_vo) {
+            const InfoVo q = info_link_vo(lin, M, k - 1, info_vo);
+            Hrr = Hrr + q.Srr; Hrp = Hrp + q.Srp; Hpp = Hpp + q.Spp;
+            gr = gr + q.gr; gp = gp + q.gp;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (k < M) {                       // link k, this node is its "i" end
+        const double dt = dts[k];
+        double* o = Ho + (size_t)k * 81;
+        M3<double> Srr, Srp, Spp;                                   // the pose block: IMU part, then the VO group
+        V3<double> lr, lp;
+        {
+            const InfoLink9 L = info_link9(lin, M, k, info_imu9);
+            put3x3(o, 0, 6, -1.0 * L.Prv); put3x3(o, 3, 6, -1.0 * L.Ppv);                     // the v row and column are IMU only
+            put3x3(o, 6, 0, -1.0 * (transpose(L.Prv) + dt * L.Prr)); put3x3(o, 6, 3, -1.0 * (transpose(L.Ppv) + dt * L.Prp));
+            put3x3(o, 6, 6, -1.0 * (L.Pvv + dt * L.Prv));
+            Hrv = Hrv + (L.Prv + dt * L.Prr);
+            Hpv = Hpv + (L.Ppv + dt * transpose(L.Prp));
+            Hvv = Hvv + (L.Pvv + dt * (L.Prv + transpose(L.Prv)) + (dt * dt) * L.Prr);
+            gv = gv - L.gv - dt * L.gr;
+            Srr = L.Prr; Srp = L.Prp; Spp = L.Ppp; lr = L.gr; lp = L.gp;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (info_vo) {
+            const InfoVo q = info_link_vo(lin, M, k, info_vo);
+            Srr = Srr + q.Srr; Srp = Srp + q.Srp; Spp = Spp + q.Spp;
+            lr = lr + q.gr; lp = lp + q.gp;
+        }
+        put3x3(o, 0, 0, -1.0 * Srr); put3x3(o, 0, 3, -1.0 * Srp);
+        put3x3(o, 3, 0, -1.0 * transpose(Srp)); put3x3(o, 3, 3, -1.0 * Spp);
+        Hrr = Hrr + Srr; Hrp = Hrp + Srp; Hpp = Hpp + Spp;
+        gr = gr - lr; gp = gp - lp;
+    }
+    const auto clamp = [&](double v) { return fmin(fmax(v, vmin), vmax); };      // A.diagonal().clamp_(min, max)
+    Hrr.a00 = clamp(Hrr.a00); Hrr.a11 = clamp(Hrr.a11); Hrr.a22 = clamp(Hrr.a22);
+    Hpp.a00 = clamp(Hpp.a00); Hpp.a11 = clamp(Hpp.a11); Hpp.a22 = clamp(Hpp.a22);
+    Hvv.a00 = clamp(Hvv.a00); Hvv.a11 = clamp(Hvv.a11); Hvv.a22 = clamp(Hvv.a22);
+    double* h = Hd + (size_t)k * 81;
+    put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, Hrv);
+    put3x3(h, 3, 0, transpose(Hrp)); put3x3(h, 3, 3, Hpp); put3x3(h, 3, 6, Hpv);
+    put3x3(h, 6, 0, transpose(Hrv)); put3x3(h, 6, 3, transpose(Hpv)); put3x3(h, 6, 6, Hvv);
+    double* b = rhs + (size_t)k * 9;
+    b[0] = -gr.x; b[1] = -gr.y; b[2] = -gr.z; b[3] = -gp.x; b[4] = -gp.y; b[5] = -gp.z;
+    b[6] = -gv.x; b[7] = -gv.y; b[8] = -gv.z;
+}
+
+// ------------------------------------------------------------------------------------------
 // Sparse reprojection factor (pvgo.py:53-61 + dense_ba.py:276-305).  Link k: T = C^-1 (X_k^-1 X_{k+1}) C,
 // err_j = pixel(K, T^-1 P_j) - target_j.  Under the left perturbation T <- Exp(eta) T:  d p'/d eta = R_T^T [-I, [P]x], so
 // with a = (f/z) R^T[row] - (f c/z^2) R^T[2]:  d err / d eta = [-a, a x P].  Node perturbations enter through

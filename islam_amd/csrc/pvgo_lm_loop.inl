@@ -22,6 +22,7 @@ struct ChainRun {
     VerdictBlock vb;
     const islam_pvgo_reproj* reproj; ReprojDev rp; const RobustDev* robust;      // optional factors / kernels (nullptr: none)
     const double *info_vo, *info_imu;       // per-factor information, packed (21, N-1) / (18, N-1); both nullptr: the scalars of prm->w
+    bool info_imu9;                         // info_imu is (45, N-1): one correlated 9x9 per link
     islam_pvgo_result* result; double* trace; int trace_cap;
     LinBufs lin(int b) const { return LinBufs{LIN[b], HD[b], HO[b], RH[b]}; }
     int* eflag_none() const { return w.flags + 6; }            // a word nobody sets
@@ -40,11 +41,13 @@ static ChainRun chain_run(double* nodes, double* vels, const ChainData& d, const
 }
 
 // Per-factor information: directly behind a linbuild_kernel / trial_lin_kernel launch, under that launch's
-// gate, info_build_kernel overwrites HD[b], HO[b], RH[b] from the LIN[b] it just wrote.  The stored diagonal stays undamped.
+// gate, info_build_kernel (info9_build_kernel for the correlated layout) overwrites HD[b], HO[b], RH[b] from the LIN[b] it just wrote.
+// The stored diagonal stays undamped.
 static void enqueue_info_build(const ChainRun& r, int b, Gate gate) {
     if (!r.info_imu) return;
-    hipLaunchKernelGGL(info_build_kernel, dim3((r.d.N + 63) / 64), dim3(64), 0, r.s, r.LIN[b], r.d.dts, r.d.N, r.info_vo, r.info_imu, r.W.vmin,
-                       r.W.vmax, r.HD[b], r.HO[b], r.RH[b], gate);
+    const auto kernel = r.info_imu9 ? info9_build_kernel : info_build_kernel;
+    hipLaunchKernelGGL(kernel, dim3((r.d.N + 63) / 64), dim3(64), 0, r.s, r.LIN[b], r.d.dts, r.d.N, r.info_vo, r.info_imu, r.W.vmin, r.W.vmax,
+                       r.HD[b], r.HO[b], r.RH[b], gate);
 }
 
 // red_ready: RED[b] already holds the reduction at (xn)
@@ -262,11 +265,12 @@ static int run_staged(ChainRun& r) {
 // setup, the choice of the driver, the call
 static int run_chain_impl(double* nodes, double* vels, const ChainData& d, const islam_pvgo_params* prm, const islam_pvgo_reproj* reproj,
                           const ReprojDev& rp, const Workspace& w, hipStream_t s, islam_pvgo_result* result, double* trace, int trace_cap,
-                          const RobustDev* robust, const double* info_vo = nullptr, const double* info_imu = nullptr) {
+                          const RobustDev* robust, const double* info_vo = nullptr, const double* info_imu = nullptr,
+                          bool info_imu9 = false) {
     const int N = d.N;
     ChainRun r = chain_run(nodes, vels, d, prm, w, s);
     r.reproj = reproj; r.rp = rp; r.robust = robust; r.result = result; r.trace = trace; r.trace_cap = trace_cap;
-    r.info_vo = info_vo; r.info_imu = info_imu;
+    r.info_vo = info_vo; r.info_imu = info_imu; r.info_imu9 = info_imu9;
     const bool info = info_imu != nullptr;         // information lives in the launch-per-stage loop only
     int rc = r.vb.acquire();
     if (rc != ISLAM_OK) return rc;

@@ -11,12 +11,16 @@ A = sum_k J_k^T Omega_k J_k, b = -sum_k J_k^T Omega_k r_k.  Factor groups, in th
     3  transvel               3 per link                  (M,3,3)
 
 Every Omega is symmetric positive SEMI-definite: Omega_k = 0 switches factor k off (the LM's diagonal clamp keeps A positive
-definite).  The accept-test loss and the trust-region term stay unweighted, as they are under scalar weights."""
+definite).  The accept-test loss and the trust-region term stay unweighted, as they are under scalar weights.
+
+Groups 1-3 of a link come from the same gyro and accelerometer samples.  ``imu`` (M,9,9) replaces them by ONE factor per link on the
+stacked residual [rv; er; rt] (rows in the order vel | rot | transvel), cross blocks included."""
 import numpy as np
 import torch
 
 _GROUPS = (('vo', 6), ('vel', 3), ('rot', 3), ('transvel', 3))
-_TRIU = {k: np.triu_indices(k) for k in (3, 6)}
+_TRIU = {k: np.triu_indices(k) for k in (3, 6, 9)}
+_IMU_BLOCKS = (('vel', 0), ('rot', 3), ('transvel', 6))       # where the three groups sit in the 9x9 of ``imu``
 
 
 def _as_matrices(name, x, k, n=None):
@@ -51,14 +55,48 @@ def _validate(name, m):
         raise ValueError('PvgoInfo.%s: factor %d is not positive semi-definite (eigenvalues %g .. %g)' % (name, i, ev[i, 0], ev[i, -1]))
 
 
+def _imu_cov_args(cov, rot):
+    """cov (M,9,9) as float64 numpy and the rotation matrices (M,3,3) of ``rot`` (M,4) xyzw (None: identity), checked."""
+    c = cov.detach().cpu().numpy() if isinstance(cov, torch.Tensor) else np.asarray(cov)
+    c = np.asarray(c, dtype=np.float64)
+    if c.ndim != 3 or c.shape[1:] != (9, 9):
+        raise ValueError('from_imu_cov: cov must be (M,9,9), got %s' % (c.shape,))
+    Mn = c.shape[0]
+    if rot is None:
+        return c, np.broadcast_to(np.eye(3), (Mn, 3, 3))
+    from . import lietensor as pp
+    q = pp._plain(rot) if isinstance(rot, torch.Tensor) else torch.as_tensor(np.asarray(rot))
+    q = q.detach().cpu().double().numpy()
+    if q.shape != (Mn, 4):
+        raise ValueError('from_imu_cov: rot must be (%d,4) xyzw, got %s' % (Mn, q.shape))
+    x, y, z, w = (q / np.linalg.norm(q, axis=1, keepdims=True)).T
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                  2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                  2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1).reshape(Mn, 3, 3)
+    return c, R
+
+
 class PvgoInfo:
     """One information matrix per factor.  Each of ``vo`` (6x6 per edge), ``vel``, ``rot``, ``transvel`` (3x3 per link) is None
     (``loss_weight[g]**2 * I``, filled in by run_pvgo), (n,) scalars per factor, (n,k) diagonals or (n,k,k) full matrices (symmetrised
-    as (O + O^T) / 2); numpy arrays or tensors.  validate: check finiteness and, on the host, smallest eigenvalue >= -1e-12 x largest;
-    a violation raises ValueError naming the group and the first offending factor."""
+    as (O + O^T) / 2); numpy arrays or tensors.  ``imu`` (M,9,9): one correlated information matrix per link on [rv; er; rt], in place
+    of ``vel``, ``rot`` and ``transvel`` (giving it together with one of them raises ValueError).  validate: check finiteness and, on
+    the host, smallest eigenvalue >= -1e-12 x largest; a violation raises ValueError naming the group and the first offending factor."""
 
-    def __init__(self, vo=None, vel=None, rot=None, transvel=None, validate=True):
+    def __init__(self, vo=None, vel=None, rot=None, transvel=None, validate=True, imu=None):
         given = dict(vo=vo, vel=vel, rot=rot, transvel=transvel)
+        self.imu = None
+        if imu is not None:
+            both = [name for name in ('vel', 'rot', 'transvel') if given[name] is not None]
+            if both:
+                raise ValueError('PvgoInfo: imu (the correlated 9x9 per link) replaces vel, rot and transvel; got imu together with %s'
+                                 % ', '.join(both))
+            a = imu.detach().cpu().numpy() if isinstance(imu, torch.Tensor) else np.asarray(imu)
+            if a.ndim != 3 or a.shape[1:] != (9, 9):
+                raise ValueError('PvgoInfo.imu: expected (n,9,9), got shape %s' % (a.shape,))
+            self.imu = _as_matrices('imu', a, 9)
+            if validate:
+                _validate('imu', self.imu)
         for name, k in _GROUPS:
             m = None if given[name] is None else _as_matrices(name, given[name], k)
             if m is not None and validate:
@@ -66,26 +104,44 @@ class PvgoInfo:
             setattr(self, name, m)
 
     def matrices(self, E, M, loss_weight):
-        """The four groups as (E,6,6), (M,3,3) x 3 float64 numpy arrays, None filled with loss_weight[g]**2 * I."""
+        """The four groups as (E,6,6), (M,3,3) x 3 float64 numpy arrays, None filled with loss_weight[g]**2 * I.  Under ``imu`` the
+        three IMU groups are the diagonal 3x3 blocks of the 9x9 (the cross blocks: ``imu_matrices``)."""
         out = []
+        imu = None if self.imu is None else self.imu_matrices(M)
         for g, (name, k) in enumerate(_GROUPS):
             n = E if g == 0 else M
             m = getattr(self, name)
-            if m is None:
+            if g > 0 and imu is not None:
+                lo = _IMU_BLOCKS[g - 1][1]
+                m = imu[:, lo:lo + 3, lo:lo + 3]
+            elif m is None:
                 m = np.broadcast_to(float(loss_weight[g]) ** 2 * np.eye(k), (n, k, k))
             elif m.shape[0] != n:
                 raise ValueError('PvgoInfo.%s: %d factors given, the graph has %d' % (name, m.shape[0], n))
             out.append(np.ascontiguousarray(m))
         return out
 
+    def imu_matrices(self, M):
+        """``imu`` as (M,9,9), checked against the graph's link count."""
+        if self.imu is None:
+            raise ValueError('PvgoInfo.imu is not set')
+        if self.imu.shape[0] != M:
+            raise ValueError('PvgoInfo.imu: %d factors given, the graph has %d' % (self.imu.shape[0], M))
+        return self.imu
+
     def packed(self, E, M, loss_weight=(1, 1, 1, 1), device='cuda'):
         """The device layout of the library (include/islam_hip.h, islam_pvgo_run_chain_info), float64, component-major:
         info_vo (21,E) = the upper triangle of each 6x6 in row-major order of the triangle; info_imu (18,M) = the 6-entry upper
-        triangles of [vel | rot | transvel]."""
+        triangles of [vel | rot | transvel].  With ``imu``: (info_vo, info_imu9 (45,M)), the upper triangle of each 9x9 in row-major
+        order of the triangle (islam_pvgo_run_chain_info9)."""
         vo, vel, rot, tv = self.matrices(E, M, loss_weight)
         r6, c6 = _TRIU[6]
         r3, c3 = _TRIU[3]
         info_vo = np.ascontiguousarray(vo[:, r6, c6].T)
+        if self.imu is not None:
+            r9, c9 = _TRIU[9]
+            info_imu9 = np.ascontiguousarray(self.imu_matrices(M)[:, r9, c9].T)
+            return (torch.from_numpy(info_vo).to(device), torch.from_numpy(info_imu9).to(device))
         info_imu = np.ascontiguousarray(np.concatenate([m[:, r3, c3].T for m in (vel, rot, tv)], 0))
         return (torch.from_numpy(info_vo).to(device), torch.from_numpy(info_imu).to(device))
 
@@ -95,43 +151,60 @@ class PvgoInfo:
         d = lambda m, lo, hi: np.diagonal(m, axis1=1, axis2=2)[:, lo:hi].mean(axis=1)
         return {'vo_rot': d(vo, 3, 6), 'imu_rot': d(rot, 0, 3), 'vo_trans': d(vo, 0, 3), 'imu_vel': d(vel, 0, 3), 'transvel': d(tv, 0, 3)}
 
+    @staticmethod
+    def residual_cov_from_imu_cov(cov, rot=None):
+        """C (M,9,9) = S T cov T^T S^T: the covariance of the stacked IMU residual [rv; er; rt] of each link that the pre-integration
+        covariance ``cov`` (M,9,9; error state [dphi, dv, dp]) implies; ``rot`` as in from_imu_cov.
+        from_imu_cov(correlated=True) inverts C + floor I."""
+        c, R = _imu_cov_args(cov, rot)
+        c = 0.5 * (c + np.swapaxes(c, 1, 2))
+        ST = np.zeros((c.shape[0], 9, 9))          # rows [rv, er, rt], columns [dphi, dv, dp]
+        ST[:, 0:3, 3:6] = R                        # rv = +R dv
+        ST[:, 3:6, 0:3] = -np.eye(3)               # er = -dphi
+        ST[:, 6:9, 6:9] = -R                       # rt = -R dp
+        C = ST @ c @ np.swapaxes(ST, 1, 2)
+        return 0.5 * (C + np.swapaxes(C, 1, 2))
+
     @classmethod
-    def from_imu_cov(cls, cov, rot=None, floor=0.0, vo=None):
-        """Information of the three IMU factors from the pre-integration covariances (IMUModule(prop_cov=True) /
-        ops.imu_preint_cov in motion mode).
+    def from_imu_cov(cls, cov, rot=None, floor=0.0, vo=None, correlated=False):
+        """Information of the IMU factors from the pre-integration covariances (IMUModule(prop_cov=True) / ops.imu_preint_cov in
+        motion mode).  With such covariances at hand call it with ``correlated=True``: that is the
+        pre-integration factor, one 9x9 per link.
 
         cov (M,9,9): one covariance per link, error state [dphi, dv, dp].  rot (M,4): xyzw rotation of the START node of each link,
-        body -> the frame of ``imu_dvels`` / ``imu_dtrans`` (None: identity).  Returns a PvgoInfo with
+        body -> the frame of ``imu_dvels`` / ``imu_dtrans`` (None: identity).
+
+        correlated=True returns a PvgoInfo with ``imu = (C + floor I)^-1``, C = S T cov T^T S^T the covariance of the stacked residual
+        [rv; er; rt] (``residual_cov_from_imu_cov``): T = blockdiag(I, R, R) turns dv and dp into the frame of the increments, and S
+        maps [dphi, dv, dp] onto the residual rows with their signs, rv = +R dv, er = -dphi, rt = -R dp to first order (the v-r and
+        v-t cross blocks change sign, r-t does not).
+
+        correlated=False (the default) keeps the three diagonal blocks only and returns three separate factors,
 
             rot      = (S_phiphi + floor I)^-1
             vel      = (R S_vv R^T + floor I)^-1
             transvel = (R S_pp R^T + floor I)^-1
 
-        Why: dphi is the right perturbation of the pre-integrated rotation dR, dR_true = dR Exp(dphi), and PVGO's rotation residual
-        Log(dR^-1 R_i^-1 R_j) is exactly that perturbation to first order, so S_phiphi is its covariance as it stands.  dv and dp
-        live in the body frame of the link's start; the velocity and translation-velocity residuals are written in the frame of
-        imu_dvels / imu_dtrans, so their covariances are rotated by R.  The cross blocks (phi-v, phi-p, v-p) are dropped: PVGO's three
-        IMU factors are separate residuals (a correlated 9-row factor is out of scope).  ``vo`` is passed through.
+        which weights the three residuals of a link as if they were independent although they come from the same samples.
 
-        A block that is not positive definite raises ValueError naming the frame and suggesting ``floor``; a frame without samples has
-        S = 0 and triggers this."""
-        c = cov.detach().cpu().numpy() if isinstance(cov, torch.Tensor) else np.asarray(cov)
-        c = np.asarray(c, dtype=np.float64)
-        if c.ndim != 3 or c.shape[1:] != (9, 9):
-            raise ValueError('from_imu_cov: cov must be (M,9,9), got %s' % (c.shape,))
+        Why: dphi is the right perturbation of the pre-integrated rotation dR, dR_true = dR Exp(dphi), and PVGO's rotation residual
+        Log(dR^-1 R_i^-1 R_j) is exactly that perturbation to first order (with a minus sign), so S_phiphi is its covariance as it
+        stands.  dv and dp live in the body frame of the link's start; the velocity and translation-velocity residuals are written in
+        the frame of imu_dvels / imu_dtrans, so their covariances are rotated by R.  ``vo`` is passed through.
+
+        A covariance (block) that is not positive definite raises ValueError naming the frame and suggesting ``floor``; a frame
+        without samples has S = 0 and triggers this."""
+        c, R = _imu_cov_args(cov, rot)
         Mn = c.shape[0]
-        if rot is None:
-            R = np.broadcast_to(np.eye(3), (Mn, 3, 3))
-        else:
-            from . import lietensor as pp
-            q = pp._plain(rot) if isinstance(rot, torch.Tensor) else torch.as_tensor(np.asarray(rot))
-            q = q.detach().cpu().double().numpy()
-            if q.shape != (Mn, 4):
-                raise ValueError('from_imu_cov: rot must be (%d,4) xyzw, got %s' % (Mn, q.shape))
-            x, y, z, w = (q / np.linalg.norm(q, axis=1, keepdims=True)).T
-            R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                          2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                          2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1).reshape(Mn, 3, 3)
+        if correlated:
+            C = cls.residual_cov_from_imu_cov(c, rot) + float(floor) * np.eye(9)
+            ev = np.linalg.eigvalsh(C) if Mn else np.zeros((0, 9))
+            bad = ~np.isfinite(ev).all(axis=1) | (ev[:, 0] <= 1e-14 * np.maximum(ev[:, -1], 0.0))
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise ValueError('from_imu_cov: the 9x9 covariance of frame %d is not positive definite (smallest eigenvalue %g; a frame '
+                                 'without IMU samples has zero covariance): pass floor > 0' % (i, ev[i, 0]))
+            return cls(vo=vo, validate=True, imu=np.linalg.inv(C))
         I3 = float(floor) * np.eye(3)
         out = {}
         for name, lo, rotate in (('rot', 0, False), ('vel', 3, True), ('transvel', 6, True)):

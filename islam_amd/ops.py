@@ -1092,20 +1092,29 @@ def pvgo_reproj_reduce(nodes, reproj, dx=None):
 
 
 def _info_pair(info, E, M):
-    """(info_vo (21,E) or None, info_imu (18,M) or None) of a packed pair, checked."""
+    """(info_vo (21,E) or None, info_imu (18,M) / info_imu9 (45,M) or None) of a packed pair, checked.  The row count of the second
+    array says which layout it is: 18, three 3x3 per link, or 45, one correlated 9x9 per link (``_info_imu9``)."""
     info_vo, info_imu = info
     require_cuda(info_vo, info_imu)
-    for t, shape, name in ((info_vo, (21, E), 'info_vo'), (info_imu, (18, M), 'info_imu')):
+    rows = 45 if info_imu is not None and info_imu.dim() == 2 and info_imu.shape[0] == 45 else 18
+    for t, shape, name in ((info_vo, (21, E), 'info_vo'), (info_imu, (rows, M), 'info_imu')):
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise ValueError('%s: a contiguous float64 %s tensor expected, got %s %s' % (name, shape, t.dtype, tuple(t.shape)))
+            raise ValueError('%s: a contiguous float64 %s tensor expected%s, got %s %s'
+                             % (name, shape, ' (or (45, %d), one 9x9 per link)' % M if name == 'info_imu' else '', t.dtype, tuple(t.shape)))
     return info_vo, info_imu
+
+
+def _info_imu9(info_imu):
+    """True when a checked info_imu array is the correlated layout (45,M)."""
+    return info_imu is not None and info_imu.shape[0] == 45
 
 
 def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, workspace=None, trace_cap=0, reproj=None, robust=None, info=None):
     """In-place LM on float64 device tensors.  Returns (PvgoResult, trace ndarray (trials,3) or None).
     robust: islam_amd.robust.RobustSpec (or None) -- islam_pvgo_run_chain_robust; not combinable with ``reproj``.
     info: (info_vo (21,N-1), info_imu (18,N-1)), the packed per-factor information (PvgoInfo.packed) -- islam_pvgo_run_chain_info;
-    not combinable with ``reproj`` or ``robust``."""
+    or (info_vo, info_imu9 (45,N-1)), one correlated 9x9 per link -- islam_pvgo_run_chain_info9.  Not combinable with ``reproj`` or
+    ``robust``."""
     require_cuda(nodes, vels, poses, drots, dtrans, dvels, dts)
     if robust is not None and reproj is not None:
         raise NotImplementedError('robust kernels on the reprojection factor are not implemented')
@@ -1124,9 +1133,9 @@ def pvgo_run_chain(nodes, vels, poses, drots, dtrans, dvels, dts, params, worksp
     tp = trace.ctypes.data_as(c_void_p) if trace is not None else c_void_p(0)
     if info is not None:
         info_vo, info_imu = _info_pair(info, N - 1, N - 1)
-        check(lib().islam_pvgo_run_chain_info(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
-                                              ctypes.byref(params), ptr(info_vo), ptr(info_imu), ptr(ws), c_size_t(nbytes),
-                                              ctypes.byref(res), tp, trace_cap, stream_ptr(nodes.device)))
+        run = lib().islam_pvgo_run_chain_info9 if _info_imu9(info_imu) else lib().islam_pvgo_run_chain_info
+        check(run(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N, ctypes.byref(params), ptr(info_vo),
+                  ptr(info_imu), ptr(ws), c_size_t(nbytes), ctypes.byref(res), tp, trace_cap, stream_ptr(nodes.device)))
     elif robust is not None:
         check(lib().islam_pvgo_run_chain_robust(ptr(nodes), ptr(vels), ptr(poses), ptr(drots), ptr(dtrans), ptr(dvels), ptr(dts), N,
                                                 ctypes.byref(params), ctypes.byref(robust.struct()), ptr(ws), c_size_t(nbytes),
@@ -1170,7 +1179,8 @@ def pvgo_build_normal(lin, dts, N, w4, vmin=1e-4, vmax=1e32, c_imu=None):
 
 def pvgo_build_normal_info(lin, dts, N, info_vo, info_imu, vmin=1e-4, vmax=1e32):
     """islam_pvgo_build_normal_info: the chain normal equations under per-factor information, packed as PvgoInfo.packed gives it --
-    info_vo (21,N-1) or None (no VO group), info_imu (18,N-1).  Returns (Hd (N,9,9), Ho (N,9,9), rhs (N,9))."""
+    info_vo (21,N-1) or None (no VO group), info_imu (18,N-1); or info_imu (45,N-1), one correlated 9x9 per link
+    (islam_pvgo_build_normal_info9).  Returns (Hd (N,9,9), Ho (N,9,9), rhs (N,9))."""
     require_cuda(lin, dts)
     dev = lin.device
     if info_imu is None:
@@ -1179,8 +1189,8 @@ def pvgo_build_normal_info(lin, dts, N, info_vo, info_imu, vmin=1e-4, vmax=1e32)
     Hd = torch.zeros((N, 9, 9), dtype=torch.float64, device=dev)
     Ho = torch.zeros((N, 9, 9), dtype=torch.float64, device=dev)
     rhs = torch.zeros((N, 9), dtype=torch.float64, device=dev)
-    check(lib().islam_pvgo_build_normal_info(ptr(lin), ptr(dts), N, ptr(info_vo), ptr(info_imu), c_double(vmin), c_double(vmax), ptr(Hd),
-                                             ptr(Ho), ptr(rhs), stream_ptr(dev)))
+    build = lib().islam_pvgo_build_normal_info9 if _info_imu9(info_imu) else lib().islam_pvgo_build_normal_info
+    check(build(ptr(lin), ptr(dts), N, ptr(info_vo), ptr(info_imu), c_double(vmin), c_double(vmax), ptr(Hd), ptr(Ho), ptr(rhs), stream_ptr(dev)))
     return Hd, Ho, rhs
 
 

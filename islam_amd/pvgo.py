@@ -12,7 +12,8 @@ the optional sparse reprojection factor ``reproj``, islam_amd/dense_ba.py).
 ``kernel`` (islam_amd.robust.Huber / Cauchy, one for all four factor groups or a sequence of four) puts robust kernels on the LM,
 like PyPose's ``pp.optim.LM(kernel=...)``; None keeps the plain least-squares loop.
 ``info`` (islam_amd.information.PvgoInfo) gives every factor its own information matrix instead; None keeps
-the four scalars.
+the four scalars.  ``PvgoInfo(imu=...)`` / ``PvgoInfo.from_imu_cov(..., correlated=True)`` weights the three IMU residuals of a link as
+one factor with its full 9x9 information (section 3.22); nothing else about the call changes.
 ``marginals``: True appends the marginal covariances at the returned state (chains: section 3.9; loop-closure graphs with
 general_solver='dense_hip': section 3.18); 'band' serves loop-closure graphs with every solver from the band form (section 3.21).
 """

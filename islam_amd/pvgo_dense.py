@@ -26,7 +26,8 @@ c = rho'(s) of every VO edge and IMU-side factor and the loss sum rho(s); the sc
 term apply c per factor.  Every system uses the same multipliers and the same loss.
 
 Per-factor information (``info``, the packed pair of islam_amd.information.PvgoInfo.packed): every system
-assembles A = sum J^T Omega J and b = -sum J^T Omega r instead -- islam_pvgo_build_normal_info for the IMU groups,
+assembles A = sum J^T Omega J and b = -sum J^T Omega r instead -- islam_pvgo_build_normal_info for the IMU groups
+(islam_pvgo_build_normal_info9 when the pair carries one correlated 9x9 per link, section 3.22),
 islam_pvgo_assemble_dense_info or islam_pvgo_band_assemble for the VO edges.  The loop, the loss and the trust-region term
 are the unweighted ones above."""
 import numpy as np
@@ -50,7 +51,8 @@ def _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy_poses
 class _Graph:
     """What _run_lm and gauss_newton_matrix both set up (float64 contiguous device tensors, N nodes): w, the four squared loss weights, and
     linearize(nodes, vels), with unit poses where islam_pvgo_linearize takes VO motions.  info: None, or the packed per-factor
-    information (info_vo (21,E), info_imu (18,N-1)) of PvgoInfo.packed, which then replaces w in every assembly."""
+    information (info_vo (21,E), info_imu (18,N-1) or info_imu9 (45,N-1)) of PvgoInfo.packed, which then replaces w in every assembly
+    (ops.pvgo_build_normal_info tells the two IMU layouts apart by their row count)."""
 
     def __init__(self, nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info=None):
         self.N, self.edges, self.dts, self.dev = nodes.shape[0], edges, dts, nodes.device
@@ -58,6 +60,8 @@ class _Graph:
         self.info = info
         if info is not None and tuple(info[0].shape) != (21, edges.shape[0]):
             raise ValueError('info_vo: (21, %d) expected, got %s' % (edges.shape[0], tuple(info[0].shape)))
+        if info is not None and tuple(info[1].shape) not in ((18, self.N - 1), (45, self.N - 1)):       # three 3x3 or one 9x9 per link
+            raise ValueError('info_imu: (18, %d) or (45, %d) expected, got %s' % (self.N - 1, self.N - 1, tuple(info[1].shape)))
         dummy = torch.zeros((self.N - 1, 7), dtype=torch.float64, device=self.dev)
         dummy[:, 6] = 1.0
         self.linearize = lambda nodes, vels: _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)

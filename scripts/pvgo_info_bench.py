@@ -4,8 +4,10 @@ islam_pvgo_run_chain[_info] calls / their trials) on bench.py's graph from its d
   staged         ISLAM_PVGO_NO_FUSE=1 ISLAM_PVGO_NO_SMALL=1: the launch-per-stage loop at every size, scalar weights,
   info           information = loss_weight^2 I on every factor: the launch-per-stage loop with info_build_kernel behind every
                  linearisation.  The LM takes staged's trajectory (same trials, same rejects): the difference is the extra launch,
-and the assembly kernels alone, islam_pvgo_build_normal against islam_pvgo_build_normal_info on the same `lin` record: HIP events,
-warm-up, median of 20 launches.  One JSON line per size.
+  info9          the same information as ONE 9x9 per link, blockdiag(lw1^2 I, lw2^2 I, lw3^2 I): the same loop
+                 with info9_build_kernel, which reads 45 doubles per link where info_build_kernel reads 18, and the same trajectory,
+and the assembly kernels alone, islam_pvgo_build_normal against islam_pvgo_build_normal_info and islam_pvgo_build_normal_info9 on the
+same `lin` record: HIP events, warm-up, median of 20 launches.  One JSON line per size.
     python scripts/pvgo_info_bench.py [--runs 12] [N ...]   (default N = 9 5001 300007)"""
 import argparse
 import json
@@ -15,6 +17,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import torch
 
 import bench
@@ -22,7 +25,7 @@ from islam_amd import ops
 from islam_amd.information import PvgoInfo
 
 STAGED = {'ISLAM_PVGO_NO_FUSE': '1', 'ISLAM_PVGO_NO_SMALL': '1'}
-MODES = {'default': ({}, False), 'staged': (STAGED, False), 'info': ({}, True)}
+MODES = {'default': ({}, None), 'staged': (STAGED, None), 'info': ({}, 'info'), 'info9': ({}, 'info9')}
 
 
 def us_per_trial(prob, prm, info, runs, device):
@@ -59,8 +62,8 @@ def kernel_us(fn, reps=20, warmup=5):
     return statistics.median(out)
 
 
-def assembly_us(prob, packed):
-    """The two assembly launches alone, on preallocated outputs (the ops wrappers allocate theirs: not part of the kernel)."""
+def assembly_us(prob, packed, packed9):
+    """The three assembly launches alone, on preallocated outputs (the ops wrappers allocate theirs: not part of the kernel)."""
     from islam_amd._lib import c_double, check, lib, ptr, stream_ptr
     dev = prob['init_nodes'].device
     N = prob['init_nodes'].shape[0]
@@ -71,7 +74,8 @@ def assembly_us(prob, packed):
     tail = (c_double(1e-4), c_double(1e32), ptr(Hd), ptr(Ho), ptr(rhs), stream_ptr(dev))
     scalar = lambda: check(lib().islam_pvgo_build_normal(ptr(lin), ptr(prob['dts']), N, w, *tail))
     info = lambda: check(lib().islam_pvgo_build_normal_info(ptr(lin), ptr(prob['dts']), N, ptr(packed[0]), ptr(packed[1]), *tail))
-    return kernel_us(scalar), kernel_us(info)
+    info9 = lambda: check(lib().islam_pvgo_build_normal_info9(ptr(lin), ptr(prob['dts']), N, ptr(packed9[0]), ptr(packed9[1]), *tail))
+    return kernel_us(scalar), kernel_us(info), kernel_us(info9)
 
 
 def main():
@@ -85,12 +89,16 @@ def main():
         N = int(prob['init_nodes'].shape[0])
         prm = ops.pvgo_default_params(bench.LOSS_WEIGHT)
         packed = PvgoInfo().packed(N - 1, N - 1, bench.LOSS_WEIGHT, dev)
+        w9 = np.diag(np.repeat(np.asarray(bench.LOSS_WEIGHT[1:4], dtype=np.float64) ** 2, 3))
+        packed9 = PvgoInfo(imu=np.broadcast_to(w9, (N - 1, 9, 9)), validate=False).packed(N - 1, N - 1, bench.LOSS_WEIGHT, dev)
+        assert tuple(packed9[1].shape) == (45, N - 1)
+        given = {None: None, 'info': packed, 'info9': packed9}
         out = {'N': N}
-        for name, (env, with_info) in MODES.items():
+        for name, (env, which) in MODES.items():
             saved = {k: os.environ.get(k) for k in env}
             os.environ.update(env)
             try:
-                us, it = us_per_trial(prob, prm, packed if with_info else None, a.runs, dev)
+                us, it = us_per_trial(prob, prm, given[which], a.runs, dev)
             finally:
                 for k, v in saved.items():
                     if v is None:
@@ -101,8 +109,10 @@ def main():
         out['info_minus_staged_us'] = round(out['info']['us_per_trial'] - out['staged']['us_per_trial'], 2)
         out['info_over_staged'] = round(out['info']['us_per_trial'] / out['staged']['us_per_trial'], 3)
         out['info_over_default'] = round(out['info']['us_per_trial'] / out['default']['us_per_trial'], 3)
-        s_us, i_us = assembly_us(prob, packed)
-        out['build_normal_us'], out['build_normal_info_us'] = round(s_us, 2), round(i_us, 2)
+        out['info9_minus_info_us'] = round(out['info9']['us_per_trial'] - out['info']['us_per_trial'], 2)
+        out['info9_over_info'] = round(out['info9']['us_per_trial'] / out['info']['us_per_trial'], 3)
+        s_us, i_us, i9_us = assembly_us(prob, packed, packed9)
+        out['build_normal_us'], out['build_normal_info_us'], out['build_normal_info9_us'] = round(s_us, 2), round(i_us, 2), round(i9_us, 2)
         out['runs'] = a.runs
         print(json.dumps(out), flush=True)
 
