@@ -7,7 +7,8 @@ device synchronise inside the window), and apart from it, between HIP events wit
 (islam_pvgo_solve_chain_enqueue) of the same band -- the unit of the prediction "R x one chain solve".  Medians of `--reps` rounds.  Where
 N <= 12 000, method='dense' is timed in the same process, the two ALTERNATING; there is no earlier version of the band call to compare with.
 Agreement: worst |band - dense| / (largest entry of the dense block's column) over the node and pair blocks at N = 65, 200, 513, 1025,
-3000 (nothing is asserted: above N = 65 neither side has a reference).
+3000 (nothing is asserted here; at N = 200 and 513 tests/test_real_matrix_accuracy_gpu.py measures both sides against a double-double
+reference: the error is the band formula's, the dense path is at LAPACK's floor).
 
     python scripts/band_marginals_bench.py [--out profiles/band_marginals_bench.json] [--graphs 3000:6,5001:24,50001:12] [--agree 65:3,...]
 """

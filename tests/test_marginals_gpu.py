@@ -146,6 +146,24 @@ def _solution(prob, cuda, lw):
     return nodes.cpu().numpy(), vels.cpu().numpy()
 
 
+def _check_against_dd_ref(Sd, So, A, anchor, rtol):
+    """|error| <= rtol * (largest entry of the column of Sigma) for every computed block entry in the checked columns (DoF 0, 4, 8 of
+    the start, the quarter, the middle, the end, the anchor's neighbours and the level-0 segment boundaries), Sigma's columns from the
+    double-double refinement of tests/dd_ref.py: np.linalg.inv of these matrices is itself in error by up to 4e-10 at F = 65 and 1e-8
+    at F = 200, the tolerance asserted here."""
+    from islam_amd import ops
+    from tests import dd_ref
+    from tests.test_dd_ref_cpu import checked_columns, checked_nodes
+    from tests.test_real_matrix_accuracy_gpu import _errors, _tridiagonal_pieces
+    N = Sd.shape[0]
+    m0 = ops.pvgo_marginals_plan(N)[0][1]
+    cols = checked_columns(checked_nodes(N, anchor, boundaries=(m0 - 1, m0, m0 + 1)), anchor)
+    xh, xl, x0 = dd_ref.refine_dense(A, dd_ref.unit_columns(9 * N, cols), anchor=anchor)
+    err, floor = _errors(_tridiagonal_pieces(Sd, So, cols), xh, xl, x0)
+    print('N=%d anchor=%d: %d columns, worst error / column scale %.3e (LAPACK Cholesky solve: %.3e)' % (N, anchor, cols.size, err.max(), floor.max()))
+    assert err.max() <= rtol
+
+
 @pytest.mark.parametrize('F', [2, 9, 65, 300])
 @pytest.mark.parametrize('state', ['initial', 'solution'])
 def test_pvgo_matrix_against_oracle(cuda, F, state):
@@ -161,7 +179,10 @@ def test_pvgo_matrix_against_oracle(cuda, F, state):
     for anchor in sorted({0, N // 2, N - 1}):
         mg = pvgo.pvgo_marginals(t(nodes), t(vels), loss_weight=LW, anchor=anchor, **_device_inputs(prob, cuda))
         Sd, So = mg.node_cov.cpu().numpy(), mg.cross.cpu().numpy()
-        _check_against_dense(Sd, So, _anchored_inverse(A, N, anchor), 1e-8)
+        if F <= 9:
+            _check_against_dense(Sd, So, _anchored_inverse(A, N, anchor), 1e-8)
+        else:
+            _check_against_dd_ref(Sd, So, A, anchor, 1e-8)
         assert np.all(Sd[anchor][:6, :] == 0) and np.all(Sd[anchor][:, :6] == 0)
         if anchor > 0:
             assert np.all(So[anchor - 1][:, :6] == 0)
