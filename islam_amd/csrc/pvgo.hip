@@ -140,6 +140,22 @@ int run_chain_entry(double* nodes, double* vels, const double* poses, const doub
                         robust_on ? &rb : nullptr, info_vo, info_imu, info_imu9);
     return rc == ISLAM_OK ? rc : abandon_run(w.state, s, rc);
 }
+
+// validation, the memset and the two launches shared by islam_pvgo_assemble_dense / _scaled / _info (c_vo with EW_SCALED, info_vo with EW_INFO)
+int assemble_dense_entry(const char* name, EdgeWeight mode, const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
+                         const double* c_vo, const double* info_vo, const int64_t* edges, const int64_t* node_ptr,
+                         const int64_t* node_adj, double w0, int N, int E, double* A, double* rhs, void* stream) {
+    if (N < 2 || E < 0 || (E > 0 && ((mode == EW_SCALED && !c_vo) || (mode == EW_INFO && (!info_vo || !vo)))))
+        return fail(ISLAM_EARG, "%s: N=%d E=%d, vo %p, c_vo %p, info_vo %p", name, N, E, (const void*)vo, (const void*)c_vo, (const void*)info_vo);
+    const auto nodes_k = mode == EW_INFO ? dense_nodes_kernel<EW_INFO> : mode == EW_SCALED ? dense_nodes_kernel<EW_SCALED> : dense_nodes_kernel<EW_PLAIN>;
+    const auto edges_k = mode == EW_INFO ? dense_edges_kernel<EW_INFO> : mode == EW_SCALED ? dense_edges_kernel<EW_SCALED> : dense_edges_kernel<EW_PLAIN>;
+    hipStream_t s = as_stream(stream);
+    ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
+    hipLaunchKernelGGL(nodes_k, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, c_vo, info_vo, node_ptr, node_adj, w0, N, E, A, rhs);
+    if (E > 0) hipLaunchKernelGGL(edges_k, dim3((E + 63) / 64), dim3(64), 0, s, vo, c_vo, info_vo, edges, w0, N, E, A);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
 }  // namespace
 
 #include "pvgo_sharded.inl"   // the sharded LM loop: ranges of a rank, gated stages, run_chain_sharded_fused
@@ -368,41 +384,19 @@ int islam_pvgo_linearize_edges(const double* nodes, const int64_t* edges, const 
 int islam_pvgo_assemble_dense(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
                               const int64_t* edges, const int64_t* node_ptr, const int64_t* node_adj, double w0, int N, int E,
                               double* A, double* rhs, void* stream) {
-    if (N < 2 || E < 0) return fail(ISLAM_EARG, "islam_pvgo_assemble_dense: N=%d E=%d", N, E);
-    hipStream_t s = as_stream(stream);
-    ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
-    hipLaunchKernelGGL(dense_nodes_kernel<false>, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, node_ptr, node_adj, w0, N, E, A,
-                       rhs, (const double*)nullptr);
-    if (E > 0) hipLaunchKernelGGL(dense_edges_kernel<false>, dim3((E + 63) / 64), dim3(64), 0, s, vo, edges, w0, N, E, A, (const double*)nullptr);
-    ISLAM_LAUNCH_CHECK();
-    return ISLAM_OK;
+    return assemble_dense_entry("islam_pvgo_assemble_dense", EW_PLAIN, Hd, Ho, rhs_chain, vo, nullptr, nullptr, edges, node_ptr, node_adj, w0, N, E, A, rhs, stream);
 }
 
 int islam_pvgo_assemble_dense_scaled(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo,
                                      const double* c_vo, const int64_t* edges, const int64_t* node_ptr,
                                      const int64_t* node_adj, double w0, int N, int E, double* A, double* rhs, void* stream) {
-    if (N < 2 || E < 0 || (E > 0 && !c_vo)) return fail(ISLAM_EARG, "islam_pvgo_assemble_dense_scaled: N=%d E=%d, c_vo %p", N, E, (const void*)c_vo);
-    hipStream_t s = as_stream(stream);
-    ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
-    hipLaunchKernelGGL(dense_nodes_kernel<true>, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, node_ptr, node_adj, w0, N, E, A,
-                       rhs, c_vo);
-    if (E > 0) hipLaunchKernelGGL(dense_edges_kernel<true>, dim3((E + 63) / 64), dim3(64), 0, s, vo, edges, w0, N, E, A, c_vo);
-    ISLAM_LAUNCH_CHECK();
-    return ISLAM_OK;
+    return assemble_dense_entry("islam_pvgo_assemble_dense_scaled", EW_SCALED, Hd, Ho, rhs_chain, vo, c_vo, nullptr, edges, node_ptr, node_adj, w0, N, E, A, rhs, stream);
 }
 
 int islam_pvgo_assemble_dense_info(const double* Hd, const double* Ho, const double* rhs_chain, const double* vo, const double* info_vo,
                                    const int64_t* edges, const int64_t* node_ptr, const int64_t* node_adj, int N, int E, double* A,
                                    double* rhs, void* stream) {
-    if (N < 2 || E < 0 || (E > 0 && (!info_vo || !vo)))
-        return fail(ISLAM_EARG, "islam_pvgo_assemble_dense_info: N=%d E=%d, vo %p, info_vo %p", N, E, (const void*)vo, (const void*)info_vo);
-    hipStream_t s = as_stream(stream);
-    ISLAM_HIP_CHECK(hipMemsetAsync(A, 0, (size_t)81 * N * N * sizeof(double), s));
-    hipLaunchKernelGGL(dense_info_nodes_kernel, dim3((N + 63) / 64), dim3(64), 0, s, Hd, Ho, rhs_chain, vo, info_vo, node_ptr, node_adj, N, E, A,
-                       rhs);
-    if (E > 0) hipLaunchKernelGGL(dense_info_edges_kernel, dim3((E + 63) / 64), dim3(64), 0, s, vo, info_vo, edges, N, E, A);
-    ISLAM_LAUNCH_CHECK();
-    return ISLAM_OK;
+    return assemble_dense_entry("islam_pvgo_assemble_dense_info", EW_INFO, Hd, Ho, rhs_chain, vo, nullptr, info_vo, edges, node_ptr, node_adj, 0.0, N, E, A, rhs, stream);
 }
 
 int islam_pvgo_band_assemble(double* Hd, double* Ho, double* rhs, const double* vo, const double* c_vo, const double* info_vo,
@@ -413,15 +407,8 @@ int islam_pvgo_band_assemble(double* Hd, double* Ho, double* rhs, const double* 
         return fail(ISLAM_EARG, "islam_pvgo_band_assemble: N=%d E=%d K=%d, a null array, or both c_vo and info_vo", N, E, K);
     const dim3 grid((std::max(N, K) + 63) / 64), block(64);
     hipStream_t s = as_stream(stream);
-    if (info_vo)
-        hipLaunchKernelGGL(band_assemble_kernel<2>, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E,
-                           off_idx, K, io, jo, So);
-    else if (c_vo)
-        hipLaunchKernelGGL(band_assemble_kernel<1>, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E,
-                           off_idx, K, io, jo, So);
-    else
-        hipLaunchKernelGGL(band_assemble_kernel<0>, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E,
-                           off_idx, K, io, jo, So);
+    const auto kernel = info_vo ? band_assemble_kernel<EW_INFO> : c_vo ? band_assemble_kernel<EW_SCALED> : band_assemble_kernel<EW_PLAIN>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, Hd, Ho, rhs, vo, c_vo, info_vo, edges, node_ptr, node_adj, w0, N, E, off_idx, K, io, jo, So);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

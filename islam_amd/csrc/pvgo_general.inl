@@ -60,23 +60,41 @@ __global__ __launch_bounds__(64) void vo_edge_linearize_kernel(const double* __r
     for (int c = 0; c < 24; ++c) out[(size_t)c * E + e] = rec[c];
 }
 
-// ---- general topology: dense A from block pieces (no dense J) ----
-struct EdgeNormal { M3<double> Srr, Srp, Spp; V3<double> gr, gp; };
+// ---- general topology: the normal pieces S = A_e^T W A_e, g = A_e^T W e of one VO edge, the ONE place that weights an edge; the
+// dense and the band assembly below both sum what edge_pieces returns ----
+enum EdgeWeight { EW_PLAIN, EW_SCALED, EW_INFO };   // w0 | w0 c_vo[e] (robust multiplier) | Omega0_e of info_vo (21,E)
 
-__device__ __forceinline__ EdgeNormal edge_normal(const double* __restrict__ vo, int E, int e) {
+__device__ __forceinline__ PoseNormal edge_normal(const double* __restrict__ vo, int E, int e) {      // unweighted
     double rec[24];
 #pragma unroll
     for (int c = 0; c < 24; ++c) rec[c] = vo[(size_t)c * E + e];
     const V3<double> er{rec[0], rec[1], rec[2]}, ep{rec[3], rec[4], rec[5]};
     const M3<double> G = m3_load(rec + 6), C = m3_load(rec + 15);
     const M3<double> Gt = transpose(G), Ct = transpose(C);
-    EdgeNormal o;
+    PoseNormal o;
     o.Srr = Gt * G;
     o.Srp = Gt * C;
     o.Spp = Ct * C + o.Srr;
     o.gr = Gt * er;
     o.gp = Ct * er + Gt * ep;
     return o;
+}
+
+template <EdgeWeight MODE>
+__device__ __forceinline__ PoseNormal edge_pieces(const double* __restrict__ vo, const double* __restrict__ c_vo,
+                                                  const double* __restrict__ info_vo, double w0, int E, int e) {
+    if constexpr (MODE == EW_INFO) {
+        const double* r = vo + e;
+        const size_t ld = (size_t)E;
+        return info_vo_normal(info_vo + e, ld, lin_m3(r, ld, 6), lin_m3(r, ld, 15), lin_v3(r, ld, 0), lin_v3(r, ld, 3));
+    } else {
+        const PoseNormal en = edge_normal(vo, E, e);
+        double we = w0;
+        if constexpr (MODE == EW_SCALED) we = w0 * c_vo[e];
+        PoseNormal o;
+        o.Srr = we * en.Srr; o.Srp = we * en.Srp; o.Spp = we * en.Spp; o.gr = we * en.gr; o.gp = we * en.gp;
+        return o;
+    }
 }
 
 // Robust multipliers of a general-topology linearisation (islam_pvgo_robust_weights): lane k takes VO edge k (rows 0-5 of vo)
@@ -87,8 +105,7 @@ __global__ __launch_bounds__(64) void robust_weights_kernel(const double* __rest
     const int k = blockIdx.x * 64 + threadIdx.x;
     double l = 0.0, c;
     if (k < E) {
-        const V3<double> er{vo[k], vo[(size_t)E + k], vo[2 * (size_t)E + k]};
-        const V3<double> ep{vo[3 * (size_t)E + k], vo[4 * (size_t)E + k], vo[5 * (size_t)E + k]};
+        const V3<double> er = lin_v3(vo + k, E, 0), ep = lin_v3(vo + k, E, 3);
         l += robust_rho(rb.kind[0], rb.delta[0], dot(er, er) + dot(ep, ep), c);
         if (c_vo) c_vo[k] = c;
     }
@@ -96,8 +113,7 @@ __global__ __launch_bounds__(64) void robust_weights_kernel(const double* __rest
         const int rows[3] = {36, 24, 39};
 #pragma unroll
         for (int g = 0; g < 3; ++g) {
-            const double* p = lin + (size_t)rows[g] * M + k;
-            const V3<double> r{p[0], p[M], p[2 * (size_t)M]};
+            const V3<double> r = lin_v3(lin + k, M, rows[g]);
             l += robust_rho(rb.kind[g + 1], rb.delta[g + 1], dot(r, r), c);
             if (c_imu) c_imu[(size_t)g * M + k] = c;
         }
@@ -106,124 +122,35 @@ __global__ __launch_bounds__(64) void robust_weights_kernel(const double* __rest
     if (threadIdx.x == 0) rho_part[blockIdx.x] = l;
 }
 
-// one lane per node: diagonal block + right-hand side (fixed summation order over the node's edge ends), chain coupling
-// SCALED: edge e enters with weight w0 * c_vo[e] (islam_pvgo_assemble_dense_scaled)
-template <bool SCALED>
-__global__ __launch_bounds__(64) void dense_nodes_kernel(const double* __restrict__ Hd, const double* __restrict__ Ho,
-                                                          const double* __restrict__ rhs_chain, const double* __restrict__ vo,
-                                                          const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ node_adj,
-                                                          double w0, int N, int E, double* __restrict__ A, double* __restrict__ rhs,
-                                                          const double* __restrict__ c_vo) {
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= N) return;
-    const size_t ld = (size_t)9 * N;
-    const M3<double> Z{0, 0, 0, 0, 0, 0, 0, 0, 0};
-    M3<double> Srr = Z, Srp = Z, Spp = Z;
-    V3<double> gr{0, 0, 0}, gp{0, 0, 0};
-    for (int64_t a = node_ptr[k]; a < node_ptr[k + 1]; ++a) {
-        const int64_t code = node_adj[a];
-        const EdgeNormal en = edge_normal(vo, E, (int)(code >> 1));
-        if constexpr (SCALED) {
-            const double ce = c_vo[code >> 1];
-            Srr = Srr + ce * en.Srr; Srp = Srp + ce * en.Srp; Spp = Spp + ce * en.Spp;
-            if (code & 1) { gr = gr + ce * en.gr; gp = gp + ce * en.gp; } else { gr = gr - ce * en.gr; gp = gp - ce * en.gp; }
-        } else {
-            Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
-            if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
-        }
-    }
-    double blk[81];
-#pragma unroll
-    for (int i = 0; i < 81; ++i) blk[i] = Hd[(size_t)k * 81 + i];
-    double add[36];
-    m3_store(w0 * Srr, add); m3_store(w0 * Srp, add + 9); m3_store(w0 * Spp, add + 18); m3_store(w0 * transpose(Srp), add + 27);
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            blk[r * 9 + c] += add[r * 3 + c];
-            blk[r * 9 + 3 + c] += add[9 + r * 3 + c];
-            blk[(3 + r) * 9 + c] += add[27 + r * 3 + c];
-            blk[(3 + r) * 9 + 3 + c] += add[18 + r * 3 + c];
-        }
-    double* d = A + (size_t)9 * k * ld + 9 * k;
-#pragma unroll
-    for (int r = 0; r < 9; ++r)
-#pragma unroll
-        for (int c = 0; c < 9; ++c) d[r * ld + c] = blk[r * 9 + c];
-    const double* rc = rhs_chain + (size_t)k * 9;
-    double* b = rhs + (size_t)k * 9;
-    b[0] = rc[0] - w0 * gr.x; b[1] = rc[1] - w0 * gr.y; b[2] = rc[2] - w0 * gr.z;
-    b[3] = rc[3] - w0 * gp.x; b[4] = rc[4] - w0 * gp.y; b[5] = rc[5] - w0 * gp.z;
-    b[6] = rc[6]; b[7] = rc[7]; b[8] = rc[8];
-    if (k < N - 1) {
-        double* up = A + (size_t)9 * k * ld + 9 * (k + 1);
-        double* lo = A + (size_t)9 * (k + 1) * ld + 9 * k;
-#pragma unroll
-        for (int r = 0; r < 9; ++r)
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                const double v = Ho[(size_t)k * 81 + r * 9 + c];
-                up[r * ld + c] = v;
-                lo[c * ld + r] = v;
-            }
-    }
-}
-
-// one lane per edge: the two off-diagonal blocks -w0 S (and its transpose) of an arbitrary edge (i, j) (SCALED: -w0 c_vo[e] S)
-template <bool SCALED>
-__global__ __launch_bounds__(64) void dense_edges_kernel(const double* __restrict__ vo, const int64_t* __restrict__ edges, double w0,
-                                                          int N, int E, double* __restrict__ A, const double* __restrict__ c_vo) {
-    const int e = blockIdx.x * 64 + threadIdx.x;
-    if (e >= E) return;
-    const int64_t i = edges[2 * e], j = edges[2 * e + 1];
-    if (i == j) return;
-    if constexpr (SCALED) w0 *= c_vo[e];
-    const EdgeNormal en = edge_normal(vo, E, e);
-    double S[36];       // row-major 6x6 [[Srr, Srp],[Srp^T, Spp]]
-    const M3<double> Spr = transpose(en.Srp);
-    double t[9];
-    m3_store(en.Srr, t);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S[r * 6 + c] = t[r * 3 + c];
-    m3_store(en.Srp, t);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S[r * 6 + 3 + c] = t[r * 3 + c];
-    m3_store(Spr, t);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S[(3 + r) * 6 + c] = t[r * 3 + c];
-    m3_store(en.Spp, t);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S[(3 + r) * 6 + 3 + c] = t[r * 3 + c];
-    const size_t ld = (size_t)9 * N;
-    double* ij = A + (size_t)9 * i * ld + 9 * j;
-    double* ji = A + (size_t)9 * j * ld + 9 * i;
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-            atomicAdd(&ij[r * ld + c], -w0 * S[r * 6 + c]);
-            atomicAdd(&ji[c * ld + r], -w0 * S[r * 6 + c]);
-        }
-}
-
-// ---- the same assembly with one information matrix per VO edge: info_vo (21, E), the packed upper triangles
-__device__ __forceinline__ InfoVo edge_info_normal(const double* __restrict__ vo, const double* __restrict__ info_vo, int E, int e) {
-    const double* r = vo + e;
-    const size_t ld = (size_t)E;
-    const V3<double> er{r[0], r[ld], r[2 * ld]}, ep{r[3 * ld], r[4 * ld], r[5 * ld]};
-    const M3<double> G{r[6 * ld], r[7 * ld], r[8 * ld], r[9 * ld], r[10 * ld], r[11 * ld], r[12 * ld], r[13 * ld], r[14 * ld]};
-    const M3<double> C{r[15 * ld], r[16 * ld], r[17 * ld], r[18 * ld], r[19 * ld], r[20 * ld], r[21 * ld], r[22 * ld], r[23 * ld]};
-    return info_vo_normal(info_vo + e, ld, G, C, er, ep);
-}
-
 // add a 3x3 block into a row-major matrix of leading dimension ld (fixed indices: the operands stay in registers)
 __device__ __forceinline__ void add3x3(double* p, size_t ld, M3<double> a) {
     p[0] += a.a00; p[1] += a.a01; p[2] += a.a02;
     p[ld] += a.a10; p[ld + 1] += a.a11; p[ld + 2] += a.a12;
     p[2 * ld] += a.a20; p[2 * ld + 1] += a.a21; p[2 * ld + 2] += a.a22;
 }
+// p (row-major, leading dimension ld) -= [[Srr, Srp], [Srp^T, Spp]] (sign = -1) or += (sign = +1)
+__device__ __forceinline__ void add6x6(double* p, size_t ld, double sign, M3<double> Srr, M3<double> Srp, M3<double> Spp) {
+    add3x3(p, ld, sign * Srr); add3x3(p + 3, ld, sign * Srp); add3x3(p + 3 * ld, ld, sign * transpose(Srp)); add3x3(p + 3 * ld + 3, ld, sign * Spp);
+}
+// block (i, j) -= a, block (j, i) -= a^T, atomically
+__device__ __forceinline__ void sub3x3_atomic(double* ij, double* ji, size_t ld, M3<double> a) {
+    atomicAdd(&ij[0], -a.a00); atomicAdd(&ij[1], -a.a01); atomicAdd(&ij[2], -a.a02);
+    atomicAdd(&ij[ld], -a.a10); atomicAdd(&ij[ld + 1], -a.a11); atomicAdd(&ij[ld + 2], -a.a12);
+    atomicAdd(&ij[2 * ld], -a.a20); atomicAdd(&ij[2 * ld + 1], -a.a21); atomicAdd(&ij[2 * ld + 2], -a.a22);
+    atomicAdd(&ji[0], -a.a00); atomicAdd(&ji[ld], -a.a01); atomicAdd(&ji[2 * ld], -a.a02);
+    atomicAdd(&ji[1], -a.a10); atomicAdd(&ji[ld + 1], -a.a11); atomicAdd(&ji[2 * ld + 1], -a.a12);
+    atomicAdd(&ji[2], -a.a20); atomicAdd(&ji[ld + 2], -a.a21); atomicAdd(&ji[2 * ld + 2], -a.a22);
+}
 
-// dense_nodes_kernel with S_e = A_e^T Omega0_e A_e: diagonal blocks and right-hand side in the CSR order of the node's edge ends
-__global__ __launch_bounds__(64) void dense_info_nodes_kernel(const double* __restrict__ Hd, const double* __restrict__ Ho,
-                                                               const double* __restrict__ rhs_chain, const double* __restrict__ vo,
-                                                               const double* __restrict__ info_vo, const int64_t* __restrict__ node_ptr,
-                                                               const int64_t* __restrict__ node_adj, int N, int E,
-                                                               double* __restrict__ A, double* __restrict__ rhs) {
+// ---- dense A (9N x 9N, zeroed by the caller) from block pieces, no dense J (islam_pvgo_assemble_dense / _scaled / _info) ----
+// one lane per node: diagonal block + right-hand side (fixed summation order: the node's edge ends in CSR order), both triangles of
+// the chain coupling
+template <EdgeWeight MODE>
+__global__ __launch_bounds__(64) void dense_nodes_kernel(const double* __restrict__ Hd, const double* __restrict__ Ho,
+                                                          const double* __restrict__ rhs_chain, const double* __restrict__ vo,
+                                                          const double* __restrict__ c_vo, const double* __restrict__ info_vo,
+                                                          const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ node_adj,
+                                                          double w0, int N, int E, double* __restrict__ A, double* __restrict__ rhs) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= N) return;
     const size_t ld = (size_t)9 * N;
@@ -232,7 +159,7 @@ __global__ __launch_bounds__(64) void dense_info_nodes_kernel(const double* __re
     V3<double> gr{0, 0, 0}, gp{0, 0, 0};
     for (int64_t a = node_ptr[k]; a < node_ptr[k + 1]; ++a) {
         const int64_t code = node_adj[a];
-        const InfoVo en = edge_info_normal(vo, info_vo, E, (int)(code >> 1));
+        const PoseNormal en = edge_pieces<MODE>(vo, c_vo, info_vo, w0, E, (int)(code >> 1));
         Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
         if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
     }
@@ -241,7 +168,7 @@ __global__ __launch_bounds__(64) void dense_info_nodes_kernel(const double* __re
     for (int r = 0; r < 9; ++r)
 #pragma unroll
         for (int c = 0; c < 9; ++c) d[r * ld + c] = Hd[(size_t)k * 81 + r * 9 + c];
-    add3x3(d, ld, Srr); add3x3(d + 3, ld, Srp); add3x3(d + 3 * ld, ld, transpose(Srp)); add3x3(d + 3 * ld + 3, ld, Spp);
+    add6x6(d, ld, 1.0, Srr, Srp, Spp);
     const double* rc = rhs_chain + (size_t)k * 9;
     double* b = rhs + (size_t)k * 9;
     b[0] = rc[0] - gr.x; b[1] = rc[1] - gr.y; b[2] = rc[2] - gr.z;
@@ -261,24 +188,18 @@ __global__ __launch_bounds__(64) void dense_info_nodes_kernel(const double* __re
     }
 }
 
-// dense_edges_kernel with -A_e^T Omega0_e A_e: atomics, because two edges may share a node pair
-__device__ __forceinline__ void sub3x3_atomic(double* ij, double* ji, size_t ld, M3<double> a) {
-    atomicAdd(&ij[0], -a.a00); atomicAdd(&ij[1], -a.a01); atomicAdd(&ij[2], -a.a02);
-    atomicAdd(&ij[ld], -a.a10); atomicAdd(&ij[ld + 1], -a.a11); atomicAdd(&ij[ld + 2], -a.a12);
-    atomicAdd(&ij[2 * ld], -a.a20); atomicAdd(&ij[2 * ld + 1], -a.a21); atomicAdd(&ij[2 * ld + 2], -a.a22);
-    atomicAdd(&ji[0], -a.a00); atomicAdd(&ji[ld], -a.a01); atomicAdd(&ji[2 * ld], -a.a02);
-    atomicAdd(&ji[1], -a.a10); atomicAdd(&ji[ld + 1], -a.a11); atomicAdd(&ji[2 * ld + 1], -a.a12);
-    atomicAdd(&ji[2], -a.a20); atomicAdd(&ji[ld + 2], -a.a21); atomicAdd(&ji[2 * ld + 2], -a.a22);
-}
-__global__ __launch_bounds__(64) void dense_info_edges_kernel(const double* __restrict__ vo, const double* __restrict__ info_vo,
-                                                               const int64_t* __restrict__ edges, int N, int E, double* __restrict__ A) {
+// one lane per edge: block (i, j) -= S, block (j, i) -= S^T of an arbitrary edge (i, j); atomics, because parallel edges share a node pair
+template <EdgeWeight MODE>
+__global__ __launch_bounds__(64) void dense_edges_kernel(const double* __restrict__ vo, const double* __restrict__ c_vo,
+                                                          const double* __restrict__ info_vo, const int64_t* __restrict__ edges,
+                                                          double w0, int N, int E, double* __restrict__ A) {
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= E) return;
     const int64_t i = edges[2 * e], j = edges[2 * e + 1];
     if (i == j) return;
-    const InfoVo en = edge_info_normal(vo, info_vo, E, e);
+    const PoseNormal en = edge_pieces<MODE>(vo, c_vo, info_vo, w0, E, e);
     const size_t ld = (size_t)9 * N;
-    double* ij = A + (size_t)9 * i * ld + 9 * j;          // block (i, j) -= S, block (j, i) -= S^T
+    double* ij = A + (size_t)9 * i * ld + 9 * j;
     double* ji = A + (size_t)9 * j * ld + 9 * i;
     sub3x3_atomic(ij, ji, ld, en.Srr);
     sub3x3_atomic(ij + 3, ji + 3 * ld, ld, en.Srp);
@@ -287,27 +208,6 @@ __global__ __launch_bounds__(64) void dense_info_edges_kernel(const double* __re
 }
 
 // ---- band + off-band form of the same normal equations (islam_pvgo_band_assemble / _matvec) ----
-// the weighted normal pieces of edge e.  MODE 0: w0 S; 1: w0 c_vo[e] S (robust multiplier); 2: A_e^T Omega_e A_e (info_vo (21,E))
-template <int MODE>
-__device__ __forceinline__ EdgeNormal band_edge_normal(const double* __restrict__ vo, const double* __restrict__ c_vo,
-                                                       const double* __restrict__ info_vo, double w0, int E, int e) {
-    EdgeNormal o;
-    if constexpr (MODE == 2) {
-        const InfoVo en = edge_info_normal(vo, info_vo, E, e);
-        o.Srr = en.Srr; o.Srp = en.Srp; o.Spp = en.Spp; o.gr = en.gr; o.gp = en.gp;
-    } else {
-        const EdgeNormal en = edge_normal(vo, E, e);
-        double we = w0;
-        if constexpr (MODE == 1) we = w0 * c_vo[e];
-        o.Srr = we * en.Srr; o.Srp = we * en.Srp; o.Spp = we * en.Spp; o.gr = we * en.gr; o.gp = we * en.gp;
-    }
-    return o;
-}
-
-// p (row-major, leading dimension ld) -= [[Srr, Srp], [Srp^T, Spp]] (sign = -1) or += (sign = +1)
-__device__ __forceinline__ void add6x6(double* p, size_t ld, double sign, M3<double> Srr, M3<double> Srp, M3<double> Spp) {
-    add3x3(p, ld, sign * Srr); add3x3(p + 3, ld, sign * Srp); add3x3(p + 3 * ld, ld, sign * transpose(Srp)); add3x3(p + 3 * ld + 3, ld, sign * Spp);
-}
 // a 3x3 block of a row-major 6x6 matrix
 __device__ __forceinline__ void store3x3_ld6(M3<double> a, double* p) {
     p[0] = a.a00; p[1] = a.a01; p[2] = a.a02; p[6] = a.a10; p[7] = a.a11; p[8] = a.a12; p[12] = a.a20; p[13] = a.a21; p[14] = a.a22;
@@ -317,7 +217,7 @@ __device__ __forceinline__ void store3x3_ld6(M3<double> a, double* p) {
 // to the pose block of Hd[t], its gradient to rhs[t] (-g at the edge's first node, +g at its second; rhs = -J^T W r) and -S to Ho[t]
 // for every edge whose other end is node t + 1, whichever way it points (S is symmetric): all of Ho[t] comes from this one lane, so
 // parallel edges accumulate in a fixed order and no atomic is needed.  Lane t < K, off-band edge off_idx[t]: its ends and its S.
-template <int MODE>
+template <EdgeWeight MODE>
 __global__ __launch_bounds__(64) void band_assemble_kernel(double* __restrict__ Hd, double* __restrict__ Ho, double* __restrict__ rhs,
                                                             const double* __restrict__ vo, const double* __restrict__ c_vo,
                                                             const double* __restrict__ info_vo, const int64_t* __restrict__ edges,
@@ -332,7 +232,7 @@ __global__ __launch_bounds__(64) void band_assemble_kernel(double* __restrict__ 
         for (int64_t a = node_ptr[t]; a < node_ptr[t + 1]; ++a) {
             const int64_t code = node_adj[a];
             const int e = (int)(code >> 1);
-            const EdgeNormal en = band_edge_normal<MODE>(vo, c_vo, info_vo, w0, E, e);
+            const PoseNormal en = edge_pieces<MODE>(vo, c_vo, info_vo, w0, E, e);
             Srr = Srr + en.Srr; Srp = Srp + en.Srp; Spp = Spp + en.Spp;
             if (code & 1) { gr = gr + en.gr; gp = gp + en.gp; } else { gr = gr - en.gr; gp = gp - en.gp; }
             if (edges[2 * e + 1 - (int)(code & 1)] == (int64_t)t + 1) { Orr = Orr + en.Srr; Orp = Orp + en.Srp; Opp = Opp + en.Spp; }
@@ -346,7 +246,7 @@ __global__ __launch_bounds__(64) void band_assemble_kernel(double* __restrict__ 
         const int e = (int)off_idx[t];
         io[t] = edges[2 * e];
         jo[t] = edges[2 * e + 1];
-        const EdgeNormal en = band_edge_normal<MODE>(vo, c_vo, info_vo, w0, E, e);
+        const PoseNormal en = edge_pieces<MODE>(vo, c_vo, info_vo, w0, E, e);
         double* s = So + (size_t)t * 36;
         store3x3_ld6(en.Srr, s); store3x3_ld6(en.Srp, s + 3); store3x3_ld6(transpose(en.Srp), s + 18); store3x3_ld6(en.Spp, s + 21);
     }

@@ -47,6 +47,14 @@ __device__ __forceinline__ LinkRes link_residuals(SE3<double> Xi, SE3<double> Xj
 
 __device__ __forceinline__ V3<double> ld3(const double* p) { return {p[0], p[1], p[2]}; }
 __device__ __forceinline__ Q4<double> ld4(const double* p) { return {p[0], p[1], p[2], p[3]}; }
+// components c.. of one record of a component-major array (`lin` (42,M), `vo` (24,E)): r = array + record index, ld = record count
+__device__ __forceinline__ V3<double> lin_v3(const double* r, size_t ld, int c) {
+    return {r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]};
+}
+__device__ __forceinline__ M3<double> lin_m3(const double* r, size_t ld, int c) {
+    return {r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld], r[(c + 3) * ld], r[(c + 4) * ld], r[(c + 5) * ld],
+            r[(c + 6) * ld], r[(c + 7) * ld], r[(c + 8) * ld]};
+}
 
 // one lane per link: residuals + Jacobian blocks G, C (A = [[G, C],[0, G]]) and B
 __global__ __launch_bounds__(64) void linearize_kernel(const double* __restrict__ nodes, const double* __restrict__ vels,
@@ -113,6 +121,26 @@ __device__ __forceinline__ void put3x3(double* H, int r0, int c0, M3<double> a) 
     H[(r0 + 2) * 9 + c0 + 0] = a.a20; H[(r0 + 2) * 9 + c0 + 1] = a.a21; H[(r0 + 2) * 9 + c0 + 2] = a.a22;
 }
 
+// the tail of every chain build: node block Hd[k] (row-major 9x9, order [rho, phi, v]) from its six upper blocks with the nine diagonal
+// entries clamped (A.diagonal().clamp_(min, max)), and rhs[k] = -g.  (The three clamped blocks by value, the rest by reference, the
+// addresses formed where they are used: in this form info9_build_kernel keeps its 434 VGPRs without a spill.)
+__device__ __forceinline__ void store_node(M3<double> Hrr, const M3<double>& Hrp, const M3<double>& Hrv, M3<double> Hpp,
+                                           const M3<double>& Hpv, M3<double> Hvv, const V3<double>& gr, const V3<double>& gp,
+                                           const V3<double>& gv, double vmin, double vmax, double* __restrict__ Hd,
+                                           double* __restrict__ rhs, int k) {
+    const auto clamp = [&](double v) { return fmin(fmax(v, vmin), vmax); };
+    Hrr.a00 = clamp(Hrr.a00); Hrr.a11 = clamp(Hrr.a11); Hrr.a22 = clamp(Hrr.a22);
+    Hpp.a00 = clamp(Hpp.a00); Hpp.a11 = clamp(Hpp.a11); Hpp.a22 = clamp(Hpp.a22);
+    Hvv.a00 = clamp(Hvv.a00); Hvv.a11 = clamp(Hvv.a11); Hvv.a22 = clamp(Hvv.a22);
+    double* h = Hd + (size_t)k * 81;
+    put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, Hrv);
+    put3x3(h, 3, 0, transpose(Hrp)); put3x3(h, 3, 3, Hpp); put3x3(h, 3, 6, Hpv);
+    put3x3(h, 6, 0, transpose(Hrv)); put3x3(h, 6, 3, transpose(Hpv)); put3x3(h, 6, 6, Hvv);
+    double* b = rhs + (size_t)k * 9;
+    b[0] = -gr.x; b[1] = -gr.y; b[2] = -gr.z; b[3] = -gp.x; b[4] = -gp.y; b[5] = -gp.z;
+    b[6] = -gv.x; b[7] = -gv.y; b[8] = -gv.z;
+}
+
 // one lane per node: gather the two adjacent links into Hd[k], Ho[k] (coupling k -> k+1), rhs[k] = -J^T W r
 // SCALED: w1, w2, w3 of link k are multiplied by its robust multipliers c_imu[0..2][k] (islam_pvgo_build_normal_scaled)
 template <bool SCALED>
@@ -151,15 +179,7 @@ __global__ __launch_bounds__(64) void build_normal_kernel(const double* __restri
         put3x3(o, 3, 0, -1.0 * transpose(L.Srp)); put3x3(o, 3, 3, -1.0 * L.Spp); put3x3(o, 3, 6, Z);
         put3x3(o, 6, 0, (-w3l * dt) * I); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, (-w1l) * I);
     }
-    double* h = Hd + (size_t)k * 81;
-    put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, hrv * I);
-    put3x3(h, 3, 0, transpose(Hrp)); put3x3(h, 3, 3, Hpp); put3x3(h, 3, 6, Z);
-    put3x3(h, 6, 0, hrv * I); put3x3(h, 6, 3, Z); put3x3(h, 6, 6, hvv * I);
-#pragma unroll
-    for (int d = 0; d < 9; ++d) h[d * 10] = fmin(fmax(h[d * 10], vmin), vmax);   // A.diagonal().clamp_(min, max)
-    double* b = rhs + (size_t)k * 9;
-    b[0] = -gr.x; b[1] = -gr.y; b[2] = -gr.z; b[3] = -gp.x; b[4] = -gp.y; b[5] = -gp.z;
-    b[6] = -gv.x; b[7] = -gv.y; b[8] = -gv.z;
+    store_node(Hrr, Hrp, hrv * I, Hpp, Z, hvv * I, gr, gp, gv, vmin, vmax, Hd, rhs, k);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -175,8 +195,8 @@ __device__ __forceinline__ M3<double> sym_part(M3<double> a) { return 0.5 * (a +
 
 // A^T Omega0 A and A^T Omega0 e of one VO factor, A = [[G, C],[0, G]], from the 3x3 blocks of Omega0 = [[Waa, Wab],[Wab^T, Wbb]]
 // (entry c of the packed triangle at w[c * ld]).  The two diagonal blocks are symmetrised: X^T (W X) is symmetric only up to rounding.
-struct InfoVo { M3<double> Srr, Srp, Spp; V3<double> gr, gp; };
-__device__ __forceinline__ InfoVo info_vo_normal(const double* __restrict__ w, size_t ld, M3<double> G, M3<double> C, V3<double> er,
+struct PoseNormal { M3<double> Srr, Srp, Spp; V3<double> gr, gp; };      // the pose-block pieces of one factor: S and J_j^T W r
+__device__ __forceinline__ PoseNormal info_vo_normal(const double* __restrict__ w, size_t ld, M3<double> G, M3<double> C, V3<double> er,
                                                  V3<double> ep) {
     const M3<double> Waa{w[0], w[ld], w[2 * ld], w[ld], w[6 * ld], w[7 * ld], w[2 * ld], w[7 * ld], w[11 * ld]};
     const M3<double> Wab{w[3 * ld], w[4 * ld], w[5 * ld], w[8 * ld], w[9 * ld], w[10 * ld], w[12 * ld], w[13 * ld], w[14 * ld]};
@@ -185,13 +205,19 @@ __device__ __forceinline__ InfoVo info_vo_normal(const double* __restrict__ w, s
     const M3<double> X1 = Waa * G, X2 = Waa * C + Wab * G;          // (Omega0 A) top row
     const M3<double> X4 = Wba * C + Wbb * G;                        // (Omega0 A) bottom right
     const V3<double> u = Waa * er + Wab * ep, v = Wba * er + Wbb * ep;
-    InfoVo o;
+    PoseNormal o;
     o.Srr = sym_part(Gt * X1);
     o.Srp = Gt * X2;
     o.Spp = sym_part(Ct * X2 + Gt * X4);
     o.gr = Gt * u;
     o.gp = Ct * u + Gt * v;
     return o;
+}
+// the VO group of link k (6x6 Omega0) from the chain's `lin`
+__device__ __forceinline__ PoseNormal info_link_vo(const double* __restrict__ lin, int M, int k, const double* __restrict__ info_vo) {
+    const double* r = lin + k;
+    const size_t ld = (size_t)M;
+    return info_vo_normal(info_vo + k, ld, lin_m3(r, ld, 6), lin_m3(r, ld, 15), lin_v3(r, ld, 0), lin_v3(r, ld, 3));
 }
 
 struct InfoLink {         // per-link normal-equation pieces under information matrices
@@ -206,13 +232,8 @@ __device__ __forceinline__ InfoLink info_link(const double* __restrict__ lin, in
                                               const double* __restrict__ info_imu) {
     const double* r = lin + k;
     const size_t ld = (size_t)M;
-    auto v3at = [&](int c) { return V3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]}; };
-    auto m3at = [&](int c) {
-        return M3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld], r[(c + 3) * ld], r[(c + 4) * ld], r[(c + 5) * ld],
-                          r[(c + 6) * ld], r[(c + 7) * ld], r[(c + 8) * ld]};
-    };
-    const M3<double> B = m3at(27);
-    const V3<double> eR = v3at(24), rv = v3at(36), rt = v3at(39);
+    const M3<double> B = lin_m3(r, ld, 27);
+    const V3<double> eR = lin_v3(r, ld, 24), rv = lin_v3(r, ld, 36), rt = lin_v3(r, ld, 39);
     const double* wi = info_imu + k;
     const M3<double> W2 = sym3_ld(wi + 6 * ld, ld);
     InfoLink o;
@@ -226,7 +247,7 @@ __device__ __forceinline__ InfoLink info_link(const double* __restrict__ lin, in
     o.gr = o.g3;
     o.gp = tmul(W2B, eR);                                           // B^T Omega2 er (Omega2 symmetric)
     if (info_vo) {
-        const InfoVo q = info_vo_normal(info_vo + k, ld, m3at(6), m3at(15), v3at(0), v3at(3));
+        const PoseNormal q = info_link_vo(lin, M, k, info_vo);
         o.Srr = o.Srr + q.Srr; o.Srp = q.Srp; o.Spp = o.Spp + q.Spp;
         o.gr = o.gr + q.gr; o.gp = o.gp + q.gp;
     } else {
@@ -268,17 +289,7 @@ __global__ __launch_bounds__(64) void info_build_kernel(const double* __restrict
         put3x3(o, 3, 0, -1.0 * transpose(L.Srp)); put3x3(o, 3, 3, -1.0 * L.Spp); put3x3(o, 3, 6, Z);
         put3x3(o, 6, 0, -1.0 * Hrv); put3x3(o, 6, 3, Z); put3x3(o, 6, 6, -1.0 * L.W1);
     }
-    const auto clamp = [&](double v) { return fmin(fmax(v, vmin), vmax); };      // A.diagonal().clamp_(min, max)
-    Hrr.a00 = clamp(Hrr.a00); Hrr.a11 = clamp(Hrr.a11); Hrr.a22 = clamp(Hrr.a22);
-    Hpp.a00 = clamp(Hpp.a00); Hpp.a11 = clamp(Hpp.a11); Hpp.a22 = clamp(Hpp.a22);
-    Hvv.a00 = clamp(Hvv.a00); Hvv.a11 = clamp(Hvv.a11); Hvv.a22 = clamp(Hvv.a22);
-    double* h = Hd + (size_t)k * 81;
-    put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, Hrv);
-    put3x3(h, 3, 0, transpose(Hrp)); put3x3(h, 3, 3, Hpp); put3x3(h, 3, 6, Z);
-    put3x3(h, 6, 0, Hrv); put3x3(h, 6, 3, Z); put3x3(h, 6, 6, Hvv);
-    double* b = rhs + (size_t)k * 9;
-    b[0] = -gr.x; b[1] = -gr.y; b[2] = -gr.z; b[3] = -gp.x; b[4] = -gp.y; b[5] = -gp.z;
-    b[6] = -gv.x; b[7] = -gv.y; b[8] = -gv.z;
+    store_node(Hrr, Hrp, Hrv, Hpp, Z, Hvv, gr, gp, gv, vmin, vmax, Hd, rhs, k);   // (Hrv = dt Omega3 is symmetric)
 }
 
 // ------------------------------------------------------------------------------------------
@@ -299,7 +310,6 @@ __device__ __forceinline__ InfoLink9 info_link9(const double* __restrict__ lin, 
     const double* r = lin + k;
     const double* w = info_imu9 + k;
     const size_t ld = (size_t)M;
-    auto v3at = [&](int c) { return V3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]}; };
     auto W = [&](int a, int b) { return w[tri9(a, b) * ld]; };
     auto symblk = [&](int o) {
         const double a = W(o, o), b = W(o, o + 1), c = W(o, o + 2), d = W(o + 1, o + 1), e = W(o + 1, o + 2), f = W(o + 2, o + 2);
@@ -309,8 +319,8 @@ __device__ __forceinline__ InfoLink9 info_link9(const double* __restrict__ lin, 
         return M3<double>{W(a, b), W(a, b + 1), W(a, b + 2), W(a + 1, b), W(a + 1, b + 1), W(a + 1, b + 2),
                           W(a + 2, b), W(a + 2, b + 1), W(a + 2, b + 2)};
     };
-    const M3<double> B{r[27 * ld], r[28 * ld], r[29 * ld], r[30 * ld], r[31 * ld], r[32 * ld], r[33 * ld], r[34 * ld], r[35 * ld]};
-    const V3<double> eR = v3at(24), rv = v3at(36), rt = v3at(39);
+    const M3<double> B = lin_m3(r, ld, 27);
+    const V3<double> eR = lin_v3(r, ld, 24), rv = lin_v3(r, ld, 36), rt = lin_v3(r, ld, 39);
     const M3<double> Wvv = symblk(0), Wrr = symblk(3), Wtt = symblk(6);
     const M3<double> Wvr = offblk(0, 3), Wvt = offblk(0, 6), Wrt = offblk(3, 6);
     const M3<double> Bt = transpose(B);
@@ -327,18 +337,6 @@ __device__ __forceinline__ InfoLink9 info_link9(const double* __restrict__ lin, 
     o.gp = tmul(B, yr);
     o.gv = -yv;
     return o;
-}
-
-// the VO group of link k (6x6 Omega0), as info_link adds it
-__device__ __forceinline__ InfoVo info_link_vo(const double* __restrict__ lin, int M, int k, const double* __restrict__ info_vo) {
-    const double* r = lin + k;
-    const size_t ld = (size_t)M;
-    auto v3at = [&](int c) { return V3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld]}; };
-    auto m3at = [&](int c) {
-        return M3<double>{r[c * ld], r[(c + 1) * ld], r[(c + 2) * ld], r[(c + 3) * ld], r[(c + 4) * ld], r[(c + 5) * ld],
-                          r[(c + 6) * ld], r[(c + 7) * ld], r[(c + 8) * ld]};
-    };
-    return info_vo_normal(info_vo + k, ld, m3at(6), m3at(15), v3at(0), v3at(3));
 }
 
 // info_build_kernel for the correlated form: the same gather (link k-1 as its j end, then link k as its i end), the same outputs, gate
@@ -361,7 +359,7 @@ __global__ __launch_bounds__(64) void info9_build_kernel(const double* __restric
         gr = L.gr; gp = L.gp; gv = L.gv;
         __builtin_amdgcn_sched_barrier(0);
         if (info_vo) {
-            const InfoVo q = info_link_vo(lin, M, k - 1, info_vo);
+            const PoseNormal q = info_link_vo(lin, M, k - 1, info_vo);
             Hrr = Hrr + q.Srr; Hrp = Hrp + q.Srp; Hpp = Hpp + q.Spp;
             gr = gr + q.gr; gp = gp + q.gp;
         }
@@ -385,7 +383,7 @@ __global__ __launch_bounds__(64) void info9_build_kernel(const double* __restric
         }
         __builtin_amdgcn_sched_barrier(0);
         if (info_vo) {
-            const InfoVo q = info_link_vo(lin, M, k, info_vo);
+            const PoseNormal q = info_link_vo(lin, M, k, info_vo);
             Srr = Srr + q.Srr; Srp = Srp + q.Srp; Spp = Spp + q.Spp;
             lr = lr + q.gr; lp = lp + q.gp;
         }
@@ -394,17 +392,7 @@ __global__ __launch_bounds__(64) void info9_build_kernel(const double* __restric
         Hrr = Hrr + Srr; Hrp = Hrp + Srp; Hpp = Hpp + Spp;
         gr = gr - lr; gp = gp - lp;
     }
-    const auto clamp = [&](double v) { return fmin(fmax(v, vmin), vmax); };      // A.diagonal().clamp_(min, max)
-    Hrr.a00 = clamp(Hrr.a00); Hrr.a11 = clamp(Hrr.a11); Hrr.a22 = clamp(Hrr.a22);
-    Hpp.a00 = clamp(Hpp.a00); Hpp.a11 = clamp(Hpp.a11); Hpp.a22 = clamp(Hpp.a22);
-    Hvv.a00 = clamp(Hvv.a00); Hvv.a11 = clamp(Hvv.a11); Hvv.a22 = clamp(Hvv.a22);
-    double* h = Hd + (size_t)k * 81;
-    put3x3(h, 0, 0, Hrr); put3x3(h, 0, 3, Hrp); put3x3(h, 0, 6, Hrv);
-    put3x3(h, 3, 0, transpose(Hrp)); put3x3(h, 3, 3, Hpp); put3x3(h, 3, 6, Hpv);
-    put3x3(h, 6, 0, transpose(Hrv)); put3x3(h, 6, 3, transpose(Hpv)); put3x3(h, 6, 6, Hvv);
-    double* b = rhs + (size_t)k * 9;
-    b[0] = -gr.x; b[1] = -gr.y; b[2] = -gr.z; b[3] = -gp.x; b[4] = -gp.y; b[5] = -gp.z;
-    b[6] = -gv.x; b[7] = -gv.y; b[8] = -gv.z;
+    store_node(Hrr, Hrp, Hrv, Hpp, Hpv, Hvv, gr, gp, gv, vmin, vmax, Hd, rhs, k);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1208,24 +1208,66 @@ def pvgo_robust_weights(vo, lin, robust, with_weights=True):
     return c_vo, c_imu, part.sum()
 
 
+def pvgo_linearize_edges(nodes, edges, poses):
+    """islam_pvgo_linearize_edges: residual and Jacobian blocks of the VO factor on every edge of ``edges`` (E,2) -> vo (24,E)."""
+    require_cuda(nodes, edges, poses)
+    E = edges.shape[0]
+    vo = torch.empty((24, E), dtype=torch.float64, device=nodes.device)
+    check(lib().islam_pvgo_linearize_edges(ptr(nodes), ptr(edges), ptr(poses), E, ptr(vo), stream_ptr(nodes.device)))
+    return vo
+
+
+def _check_vo_assembly(who, Hd, Ho, rhs, vo, edges, node_ptr, node_adj, c_vo, info_vo, more_index=()):
+    """The argument checks pvgo_assemble_dense and pvgo_band_assemble share.  Returns (N, E)."""
+    N, E = Hd.shape[0], vo.shape[1]
+    if tuple(Hd.shape) != (N, 9, 9) or tuple(Ho.shape) != (N, 9, 9) or tuple(rhs.shape) != (N, 9) or tuple(vo.shape) != (24, E) or \
+            tuple(edges.shape) != (E, 2) or node_ptr.numel() != N + 1 or node_adj.numel() != 2 * E:
+        raise ValueError('%s: Hd, Ho (N,9,9), rhs (N,9), vo (24,E), edges (E,2), node_ptr (N+1,), node_adj (2E,) expected' % who)
+    if (c_vo is not None and tuple(c_vo.shape) != (E,)) or (info_vo is not None and tuple(info_vo.shape) != (21, E)):
+        raise ValueError('%s: c_vo (E,) / info_vo (21,E) expected' % who)
+    for x in (Hd, Ho, rhs, vo, c_vo, info_vo):
+        if x is not None and (x.dtype != torch.float64 or not x.is_contiguous()):
+            raise ValueError('%s: contiguous float64 arrays expected' % who)
+    for x in (edges, node_ptr, node_adj) + tuple(more_index):
+        if x.dtype != torch.int64 or not x.is_contiguous():
+            raise ValueError('%s: contiguous int64 index arrays expected' % who)
+    return N, E
+
+
+def pvgo_assemble_dense(Hd, Ho, rhs, vo, edges, node_ptr, node_adj, w0, c_vo=None, info_vo=None, out=None):
+    """islam_pvgo_assemble_dense / _scaled / _info: the dense A (9N,9N), both triangles, and b (9N,) from the IMU-only chain arrays
+    Hd, Ho (N,9,9), rhs (N,9) plus the VO factors of ``vo`` (24,E) on ``edges`` (E,2); node_ptr / node_adj the CSR of the edge ends per
+    node.  The edges enter with weight w0, w0 * c_vo[e] (c_vo (E,): robust multipliers) or their own information info_vo (21,E), which
+    replaces w0; not both.  out: (A, b) to write into.  Returns (A, b)."""
+    require_cuda(Hd, Ho, rhs, vo, edges, node_ptr, node_adj, c_vo, info_vo)
+    if c_vo is not None and info_vo is not None:
+        raise ValueError('pvgo_assemble_dense: c_vo and info_vo cannot both be given')
+    N, E = _check_vo_assembly('pvgo_assemble_dense', Hd, Ho, rhs, vo, edges, node_ptr, node_adj, c_vo, info_vo)
+    if out is None:
+        out = (torch.empty((9 * N, 9 * N), dtype=torch.float64, device=Hd.device), torch.empty((9 * N,), dtype=torch.float64, device=Hd.device))
+    A, b = out
+    if tuple(A.shape) != (9 * N, 9 * N) or tuple(b.shape) != (9 * N,) or any(x.dtype != torch.float64 or not x.is_contiguous() for x in out):
+        raise ValueError('pvgo_assemble_dense: out = (A (9N,9N), b (9N,)), contiguous float64, expected')
+    head = (ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo))
+    graph = (ptr(edges), ptr(node_ptr), ptr(node_adj))
+    tail = (N, E, ptr(A), ptr(b), stream_ptr(Hd.device))
+    if info_vo is not None:
+        check(lib().islam_pvgo_assemble_dense_info(*head, ptr(info_vo), *graph, *tail))
+    elif c_vo is not None:
+        check(lib().islam_pvgo_assemble_dense_scaled(*head, ptr(c_vo), *graph, c_double(w0), *tail))
+    else:
+        check(lib().islam_pvgo_assemble_dense(*head, *graph, c_double(w0), *tail))
+    return A, b
+
+
 def pvgo_band_assemble(Hd, Ho, rhs, vo, edges, node_ptr, node_adj, w0, off_idx, c_vo=None, info_vo=None):
     """islam_pvgo_band_assemble: the VO factors of ``vo`` (24,E) on the validated ``edges`` (E,2) added IN PLACE to the IMU-only chain
     arrays Hd, Ho (N,9,9), rhs (N,9); node_ptr / node_adj the CSR of the edge ends per node, off_idx (K,) the off-band edges.
     c_vo (E,): robust multipliers; info_vo (21,E): per-edge information (not both).  Returns the off-band list (io (K,), jo (K,),
     So (K,6,6))."""
     require_cuda(Hd, Ho, rhs, vo, edges, node_ptr, node_adj, off_idx, c_vo, info_vo)
-    N, E, K, dev = Hd.shape[0], vo.shape[1], int(off_idx.numel()), Hd.device
-    if tuple(Hd.shape) != (N, 9, 9) or tuple(Ho.shape) != (N, 9, 9) or tuple(rhs.shape) != (N, 9) or tuple(vo.shape) != (24, E) or \
-            tuple(edges.shape) != (E, 2) or node_ptr.numel() != N + 1 or node_adj.numel() != 2 * E:
-        raise ValueError('pvgo_band_assemble: Hd, Ho (N,9,9), rhs (N,9), vo (24,E), edges (E,2), node_ptr (N+1,), node_adj (2E,) expected')
-    if (c_vo is not None and tuple(c_vo.shape) != (E,)) or (info_vo is not None and tuple(info_vo.shape) != (21, E)):
-        raise ValueError('pvgo_band_assemble: c_vo (E,) / info_vo (21,E) expected')
-    for x in (Hd, Ho, rhs, vo, c_vo, info_vo):
-        if x is not None and (x.dtype != torch.float64 or not x.is_contiguous()):
-            raise ValueError('pvgo_band_assemble: contiguous float64 arrays expected')
-    for x in (edges, node_ptr, node_adj, off_idx):
-        if x.dtype != torch.int64 or not x.is_contiguous():
-            raise ValueError('pvgo_band_assemble: contiguous int64 index arrays expected')
+    N, E = _check_vo_assembly('pvgo_band_assemble', Hd, Ho, rhs, vo, edges, node_ptr, node_adj, c_vo, info_vo, (off_idx,))
+    K, dev = int(off_idx.numel()), Hd.device
     io = torch.empty((K,), dtype=torch.int64, device=dev)
     jo = torch.empty((K,), dtype=torch.int64, device=dev)
     So = torch.empty((K, 6, 6), dtype=torch.float64, device=dev)

@@ -34,16 +34,14 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import IslamHipError, c_double, check, lib, ptr, stream_ptr
+from ._lib import IslamHipError
 from .lm_control import LMControl
 
 _NOCLAMP = 1e300
 
 
 def _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy_poses):
-    E = edges.shape[0]
-    vo = torch.empty((24, E), dtype=torch.float64, device=nodes.device)
-    check(lib().islam_pvgo_linearize_edges(ptr(nodes), ptr(edges), ptr(poses), E, ptr(vo), stream_ptr(nodes.device)))
+    vo = ops.pvgo_linearize_edges(nodes, edges, poses)
     lin, _ = ops.pvgo_linearize(nodes, vels, dummy_poses, drots, dtrans, dvels, dts)     # IMU rows of `lin`; VO rows unused
     return vo, lin
 
@@ -65,6 +63,17 @@ class _Graph:
         dummy = torch.zeros((self.N - 1, 7), dtype=torch.float64, device=self.dev)
         dummy[:, 6] = 1.0
         self.linearize = lambda nodes, vels: _linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
+
+    def imu_part(self, lin, c_imu=None):
+        """(Hd, Ho, rhs) of the IMU factors alone (no VO group, no clamp): the chain arrays the dense and the band assembly add the VO
+        edges to, under the graph's weighting -- per-factor information, or w with the robust multipliers c_imu (3,N-1)."""
+        if self.info is not None:
+            return ops.pvgo_build_normal_info(lin, self.dts, self.N, None, self.info[1], -_NOCLAMP, _NOCLAMP)
+        return ops.pvgo_build_normal(lin, self.dts, self.N, (0.0, self.w[1], self.w[2], self.w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)
+
+    @property
+    def info_vo(self):
+        return self.info[0] if self.info is not None else None
 
 
 def validate_graph(N, links, n_motions, imu_rows=None):
@@ -204,20 +213,11 @@ class _DenseSystem:
 
     def fill(self, vo, lin, rpt=None, c_vo=None, c_imu=None):
         """A (fully written) = J^T W J, undamped and unclamped, and b = -J^T W r.  rpt: _ReprojTerms; c_vo, c_imu: robust multipliers."""
-        g, N, E, w = self.g, self.g.N, self.g.edges.shape[0], self.g.w
-        if g.info is not None:                          # per-factor information: no robust multipliers, no reprojection factor
-            Hd, Ho, rhs = ops.pvgo_build_normal_info(lin, g.dts, N, None, g.info[1], -_NOCLAMP, _NOCLAMP)                   # IMU factors
-            check(lib().islam_pvgo_assemble_dense_info(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(g.info[0]), ptr(g.edges), ptr(self.nptr),
-                                                       ptr(self.nadj), N, E, ptr(self.A), ptr(self.b), stream_ptr(g.dev)))
-            return
-        Hd, Ho, rhs = ops.pvgo_build_normal(lin, g.dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
+        g = self.g
+        Hd, Ho, rhs = g.imu_part(lin, c_imu)
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
-        tail = (ptr(g.edges), ptr(self.nptr), ptr(self.nadj), c_double(w[0]), N, E, ptr(self.A), ptr(self.b), stream_ptr(g.dev))
-        if c_vo is None:
-            check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), *tail))
-        else:
-            check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), *tail))
+        ops.pvgo_assemble_dense(Hd, Ho, rhs, vo, g.edges, self.nptr, self.nadj, g.w[0], c_vo, g.info_vo, out=(self.A, self.b))      # the VO factors
 
     def assemble(self, vo, lin, rpt, c_vo, c_imu):
         self.fill(vo, lin, rpt, c_vo, c_imu)
@@ -373,15 +373,12 @@ class _BandTopology:
 class _BandSystem:
     """A = B + R of one linearisation: B as (Hd, Ho) of the chain solver, R as the list of off-band 6x6 blocks (io, jo, So)."""
 
-    def __init__(self, vo, lin, edges, dts, N, w, vmin, vmax, topo, rpt=None, c_vo=None, c_imu=None, info=None):
-        if info is not None:
-            Hd, Ho, rhs = ops.pvgo_build_normal_info(lin, dts, N, None, info[1], -_NOCLAMP, _NOCLAMP)                     # IMU factors
-        else:
-            Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w[1], w[2], w[3]), -_NOCLAMP, _NOCLAMP, c_imu=c_imu)     # IMU factors
+    def __init__(self, g, vo, lin, vmin, vmax, topo, rpt=None, c_vo=None, c_imu=None):
+        Hd, Ho, rhs = g.imu_part(lin, c_imu)
         if rpt is not None:
             rpt.add_to_chain(Hd, Ho, rhs)
-        self.io, self.jo, self.So = ops.pvgo_band_assemble(Hd, Ho, rhs, vo, edges, topo.nptr, topo.nadj, w[0], topo.off_idx, c_vo,
-                                                           info[0] if info is not None else None)          # the VO factors, in place
+        self.io, self.jo, self.So = ops.pvgo_band_assemble(Hd, Ho, rhs, vo, g.edges, topo.nptr, topo.nadj, g.w[0], topo.off_idx, c_vo,
+                                                           g.info_vo)                                      # the VO factors, in place
         self.Hd, self.Ho, self.b, self.topo = Hd, Ho, rhs, topo
         self.diag0 = Hd.diagonal(dim1=1, dim2=2).clamp(vmin, vmax).clone()                  # A.diagonal().clamp_(min, max)
 
@@ -449,7 +446,7 @@ def marginals_band(nodes, vels, edges, poses, drots, dtrans, dvels, dts, loss_we
     g = _Graph(nodes, edges, poses, drots, dtrans, dvels, dts, loss_weight, info)
     vo, lin = g.linearize(nodes, vels)
     rpt = _ReprojTerms(nodes, reproj) if reproj is not None else None
-    band = _BandSystem(vo, lin, edges, dts, N, g.w, -_NOCLAMP, _NOCLAMP, _BandTopology(eh, N, dev), rpt, info=info)
+    band = _BandSystem(g, vo, lin, -_NOCLAMP, _NOCLAMP, _BandTopology(eh, N, dev), rpt)
     status = torch.zeros((3,), dtype=torch.int32, device=dev)
     Sd, So = ops.pvgo_marginals(band.Hd, band.Ho, anchor=anchor, status=status[0:1])
     ws = ops.pvgo_band_inverse_workspace(N, cols.size, dev)
@@ -517,8 +514,7 @@ class _BandPcgSystem:
         self.extra = dict(pcg_iterations=0, pcg_worst_relative_residual=0.0, off_band_edges=self.topo.K)
 
     def assemble(self, vo, lin, rpt, c_vo, c_imu):
-        self.band = _BandSystem(vo, lin, self.g.edges, self.g.dts, self.g.N, self.g.w, self.vmin, self.vmax, self.topo, rpt, c_vo, c_imu,
-                                self.g.info)
+        self.band = _BandSystem(self.g, vo, lin, self.vmin, self.vmax, self.topo, rpt, c_vo, c_imu)
         return self.band.diag0
 
     def solve(self, d):

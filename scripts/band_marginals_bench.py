@@ -83,7 +83,7 @@ def band_parts(d):
     eh = d['links'].cpu().numpy()
     g = pd._Graph(d['nodes'], d['links'], d['vo_motions'], d['imu_drots'], d['imu_dtrans'], d['imu_dvels'], d['dts'], LW)
     vo, lin = g.linearize(d['nodes'], d['vels'])
-    band = pd._BandSystem(vo, lin, d['links'], d['dts'], N, g.w, -pd._NOCLAMP, pd._NOCLAMP, pd._BandTopology(eh, N, dev))
+    band = pd._BandSystem(g, vo, lin, -pd._NOCLAMP, pd._NOCLAMP, pd._BandTopology(eh, N, dev))
     cols, Rc = pd.band_columns(N, eh, 0, eh)
     ws = ops.pvgo_band_inverse_workspace(N, cols.size, dev)
     sws = ops.pvgo_workspace(N, dev)

@@ -221,14 +221,15 @@ def test_band_bookkeeping_against_numpy(name):
 
 # ------------------------------------------------------------------ the code objects
 def test_band_kernels_use_no_scratch():
-    """No private memory and no spilled register in band_assemble_kernel (three instances) and band_matvec_kernel."""
+    """No private memory and no spilled register in band_assemble_kernel (three instances), band_matvec_kernel and the dense assembly
+    over the same weighting function, dense_nodes_kernel and dense_edges_kernel (three instances each)."""
     import __graft_entry__ as g
     g.build()
     from tests.test_codeobj_cpu import READELF, _field, _kernels
     if not os.path.exists(READELF):
         pytest.skip('llvm-readelf missing')
-    ks = {k: v for k, v in _kernels().items() if re.search(r'band_(assemble|matvec)_kernel', k)}
-    assert len(ks) == 4, sorted(ks)
+    ks = {k: v for k, v in _kernels().items() if re.search(r'band_(assemble|matvec)_kernel|dense_(nodes|edges)_kernel', k)}
+    assert len(ks) == 10, sorted(ks)
     for name, blk in ks.items():
         print(name, 'vgpr', _field(blk, 'vgpr_count'), 'sgpr', _field(blk, 'sgpr_count'), 'lds', _field(blk, 'group_segment_fixed_size'))
         assert _field(blk, 'private_segment_fixed_size') == 0 and _field(blk, 'vgpr_spill_count') == 0, name

@@ -89,48 +89,33 @@ def _reference_normal(prob, w_rows):
 
 
 def _device_pieces(prob):
+    """(vo, lin) at the initial state, graph(lw, info) -> the pvgo_dense._Graph under those weights, and the band topology."""
     from islam_amd import pvgo_dense
-    N, M = prob['init_nodes'].shape[0], prob['init_nodes'].shape[0] - 1
+    N = prob['init_nodes'].shape[0]
     nodes, vels, poses = _d(prob['init_nodes']), _d(prob['init_vels']), _d(prob['vo_motions'])
     drots, dtrans, dvels, dts = _d(prob['imu_drots']), _d(prob['imu_dtrans']), _d(prob['imu_dvels']), _d(prob['dts'])
     edges = torch.tensor(prob['links'], device='cuda')
-    dummy = torch.zeros((M, 7), dtype=torch.float64, device='cuda')
-    dummy[:, 6] = 1.0
-    vo, lin = pvgo_dense._linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
-    return vo, lin, edges, dts, pvgo_dense._BandTopology(prob['links'], N, torch.device('cuda'))
+    graph = lambda lw, info=None: pvgo_dense._Graph(nodes, edges, poses, drots, dtrans, dvels, dts, lw, info)
+    vo, lin = graph(LW).linearize(nodes, vels)
+    return vo, lin, graph, pvgo_dense._BandTopology(prob['links'], N, torch.device('cuda'))
 
 
-def _chain_part(lin, dts, N, lw, c_imu=None, info_imu=None):
+def _dense_assembly(vo, lin, graph, topo, N, lw, c_vo=None, c_imu=None, info=None):
     from islam_amd import ops
-    if info_imu is not None:
-        return ops.pvgo_build_normal_info(lin, dts, N, None, info_imu, -1e300, 1e300)
-    w2 = W2(lw)
-    return ops.pvgo_build_normal(lin, dts, N, (0.0, w2[1], w2[2], w2[3]), -1e300, 1e300, c_imu=c_imu)
-
-
-def _dense_assembly(vo, lin, edges, dts, topo, N, lw, c_vo=None, c_imu=None, info=None):
-    from islam_amd._lib import c_double, check, lib, ptr, stream_ptr
-    E = edges.shape[0]
-    Hd, Ho, rhs = _chain_part(lin, dts, N, lw, c_imu, info[1] if info is not None else None)
+    g = graph(lw, info)
+    Hd, Ho, rhs = g.imu_part(lin, c_imu)
     A = torch.full((9 * N, 9 * N), float('nan'), dtype=torch.float64, device='cuda')
     b = torch.full((9 * N,), float('nan'), dtype=torch.float64, device='cuda')
-    tail = (ptr(edges), ptr(topo.nptr), ptr(topo.nadj))
-    out = (N, E, ptr(A), ptr(b), stream_ptr('cuda'))
-    if info is not None:
-        check(lib().islam_pvgo_assemble_dense_info(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(info[0]), *tail, *out))
-    elif c_vo is not None:
-        check(lib().islam_pvgo_assemble_dense_scaled(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(c_vo), *tail, c_double(W2(lw)[0]), *out))
-    else:
-        check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), *tail, c_double(W2(lw)[0]), *out))
+    ops.pvgo_assemble_dense(Hd, Ho, rhs, vo, g.edges, topo.nptr, topo.nadj, g.w[0], c_vo, g.info_vo, out=(A, b))
     return A.cpu().numpy(), b.cpu().numpy()
 
 
-def _band_assembly(vo, lin, edges, dts, topo, N, lw, c_vo=None, c_imu=None, info=None):
+def _band_assembly(vo, lin, graph, topo, N, lw, c_vo=None, c_imu=None, info=None):
     """The band arrays and the off-band list of islam_pvgo_band_assemble, as they are and expanded to the dense matrix they stand for."""
     from islam_amd import ops
-    Hd, Ho, rhs = _chain_part(lin, dts, N, lw, c_imu, info[1] if info is not None else None)
-    io, jo, So = ops.pvgo_band_assemble(Hd, Ho, rhs, vo, edges, topo.nptr, topo.nadj, W2(lw)[0], topo.off_idx, c_vo,
-                                        info[0] if info is not None else None)
+    g = graph(lw, info)
+    Hd, Ho, rhs = g.imu_part(lin, c_imu)
+    io, jo, So = ops.pvgo_band_assemble(Hd, Ho, rhs, vo, g.edges, topo.nptr, topo.nadj, g.w[0], topo.off_idx, c_vo, g.info_vo)
     raw = [x.cpu().numpy() for x in (Hd, Ho, rhs, io, jo, So)]
     hd, ho, b, i_, j_, so = raw
     A = np.zeros((9 * N, 9 * N))
@@ -207,6 +192,59 @@ def test_assemblies_match_the_dense_jacobian_product(cuda, name, mode):
     assert np.array_equal(b2.view(np.int64), b_d.view(np.int64))
 
 
+def test_dense_modes_share_one_weighting(cuda):
+    """The three modes of ops.pvgo_assemble_dense run the same kernels over one weighting function, on the
+    smallest graphs that hold each hazard: n2e3 (all edges parallel, one reversed), n3e1 (an empty CSR row), fewer17 (frames without a
+    VO edge), more17 (a parallel pair, an adjacent duplicate, a reversed edge).  Scaled mode with c_vo = 1 gives the bits of plain mode
+    -- w0 * 1.0 is exact and the two instances run the same statements -- for b everywhere and for all of A where no two edges share
+    a node pair (n3e1, fewer17: the atomics cannot reorder).  Info mode with Omega0_e = w0 c_e I6 agrees with scaled mode at the
+    tolerances of test_assemblies_match_the_dense_jacobian_product.  Then the refused arguments of the wrapper and of the C symbols."""
+    from islam_amd import ops
+    from islam_amd._lib import c_double, lib
+    w = W2(LW)
+    for name in ('n2e3', 'n3e1', 'fewer17', 'more17'):
+        N, E, M = sizes(name)
+        pieces = _device_pieces(case(name))
+        A_p, b_p = _dense_assembly(*pieces, N, LW)
+        A_1, b_1 = _dense_assembly(*pieces, N, LW, c_vo=torch.ones(E, dtype=torch.float64, device='cuda'))
+        assert np.array_equal(b_1.view(np.int64), b_p.view(np.int64)), name
+        if name in ('n3e1', 'fewer17'):
+            assert np.array_equal(A_1.view(np.int64), A_p.view(np.int64)), name
+        c = np.random.default_rng(11 + E).uniform(0.2, 1.0, E)
+        info_vo, info_imu = np.zeros((21, E)), np.zeros((18, M))
+        info_vo[[0, 6, 11, 15, 18, 20]] = w[0] * c                         # the diagonal of the packed upper triangle of a 6x6
+        for grp in range(3):                                                # [velocity | rotation | translation-velocity], [00 01 02 11 12 22]
+            info_imu[[6 * grp, 6 * grp + 3, 6 * grp + 5]] = w[1 + grp]
+        A_s, b_s = _dense_assembly(*pieces, N, LW, c_vo=_d(c))
+        A_i, b_i = _dense_assembly(*pieces, N, LW, info=(_d(info_vo), _d(info_imu)))
+        scale, bscale = np.abs(A_s).max(), np.abs(b_s).max()
+        print('%s: info vs scaled, A %.2e, b %.2e (of the largest entry)' % (name, np.abs(A_i - A_s).max() / scale, np.abs(b_i - b_s).max() / bscale))
+        np.testing.assert_allclose(A_i, A_s, atol=1e-12 * scale)
+        np.testing.assert_allclose(b_i, b_s, atol=1e-11 * bscale)
+
+    vo, lin, graph, topo = pieces                                           # more17
+    g = graph(LW)
+    Hd, Ho, rhs = g.imu_part(lin)
+    args = lambda **kw: [kw.get(k, v) for k, v in (('Hd', Hd), ('Ho', Ho), ('rhs', rhs), ('vo', vo), ('edges', g.edges), ('nptr', topo.nptr),
+                                                   ('nadj', topo.nadj), ('w0', w[0]))]
+    ones = lambda *shape, dtype=torch.float64: torch.ones(shape, dtype=dtype, device='cuda')
+    for bad in (dict(c_vo=ones(E), info_vo=ones(21, E)), dict(c_vo=ones(E + 1)), dict(c_vo=ones(E, 1)), dict(info_vo=ones(20, E)),
+                dict(c_vo=ones(2 * E)[::2]), dict(c_vo=ones(E, dtype=torch.float32)), dict(info_vo=ones(E, 21).t()),
+                dict(info_vo=ones(21, E, dtype=torch.float32))):
+        with pytest.raises(ValueError, match='pvgo_assemble_dense'):
+            ops.pvgo_assemble_dense(*args(), **bad)
+    for bad in (dict(vo=vo.t().contiguous().t()), dict(Hd=Hd.float()), dict(edges=g.edges.int())):
+        with pytest.raises(ValueError, match='pvgo_assemble_dense'):
+            ops.pvgo_assemble_dense(*args(**bad))
+    L = lib()
+    assert L.islam_pvgo_assemble_dense(*[None] * 7, c_double(1.0), 1, 0, None, None, None) == -1
+    assert b'islam_pvgo_assemble_dense:' in L.islam_last_error()
+    assert L.islam_pvgo_assemble_dense_scaled(*[None] * 8, c_double(1.0), 1, 0, None, None, None) == -1
+    assert b'islam_pvgo_assemble_dense_scaled:' in L.islam_last_error()
+    assert L.islam_pvgo_assemble_dense_info(*[None] * 8, 1, 0, None, None, None) == -1
+    assert b'islam_pvgo_assemble_dense_info:' in L.islam_last_error()
+
+
 # ------------------------------------------------------------------ 3. matvec
 def _fewer17_without_closure():
     F, extra, drop = CASES['fewer17']
@@ -220,7 +258,7 @@ def test_band_matvec_matches_the_dense_product(cuda, name):
     prob = _fewer17_without_closure() if name == 'no_off_band' else case(name)
     N = prob['init_nodes'].shape[0]
     pieces = _device_pieces(prob)
-    topo = pieces[4]
+    topo = pieces[3]
     A, _, _, (Hd, Ho, io, jo, So) = _band_assembly(*pieces, N, LW)
     assert (topo.K == 0) == (name in ('no_off_band', 'n2e3')) and io.numel() == topo.K
     p = np.random.default_rng(3).normal(size=(N, 9))

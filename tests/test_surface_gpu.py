@@ -192,7 +192,6 @@ def test_run_pvgo_general_topology_matches_oracle(cuda):
 def test_dense_assembly_matches_dense_jacobian_product(cuda):
     """islam_pvgo_assemble_dense (block assembly, no J) == J^T W J / -J^T W r of the oracle's dense Jacobian, node-major."""
     from islam_amd import ops, pvgo_dense
-    from islam_amd._lib import c_double, check, lib, ptr, stream_ptr
     F = 17
     prob, tr = chain_problem(F)
     links = prob['links'].copy()
@@ -213,16 +212,13 @@ def test_dense_assembly_matches_dense_jacobian_product(cuda):
     nodes, vels, poses = t(prob['init_nodes']), t(prob['init_vels']), t(prob['vo_motions'])
     drots, dtrans, dvels, dts = t(prob['imu_drots']), t(prob['imu_dtrans']), t(prob['imu_dvels']), t(prob['dts'])
     edges = torch.tensor(links, device=cuda)
-    dummy = torch.zeros((M, 7), dtype=torch.float64, device=cuda)
-    dummy[:, 6] = 1.0
-    vo, lin = pvgo_dense._linearize(nodes, vels, edges, poses, drots, dtrans, dvels, dts, dummy)
-    w2 = [x ** 2 for x in LW]
-    Hd, Ho, rhs = ops.pvgo_build_normal(lin, dts, N, (0.0, w2[1], w2[2], w2[3]), -1e300, 1e300)
+    g = pvgo_dense._Graph(nodes, edges, poses, drots, dtrans, dvels, dts, LW)
+    vo, lin = g.linearize(nodes, vels)
+    Hd, Ho, rhs = g.imu_part(lin)
     nptr, nadj = [torch.from_numpy(a).to(cuda) for a in pvgo_dense._node_adjacency(links, N)]
     A = torch.full((9 * N, 9 * N), float('nan'), dtype=torch.float64, device=cuda)
     b = torch.empty(9 * N, dtype=torch.float64, device=cuda)
-    check(lib().islam_pvgo_assemble_dense(ptr(Hd), ptr(Ho), ptr(rhs), ptr(vo), ptr(edges), ptr(nptr), ptr(nadj), c_double(w2[0]), N, E, ptr(A), ptr(b),
-                                          stream_ptr(cuda)))
+    ops.pvgo_assemble_dense(Hd, Ho, rhs, vo, edges, nptr, nadj, g.w[0], out=(A, b))
     scale = np.abs(A_ref).max()
     np.testing.assert_allclose(A.cpu().numpy(), A_ref, atol=1e-12 * scale)
     np.testing.assert_allclose(b.cpu().numpy(), b_ref, atol=1e-11 * np.abs(b_ref).max())
