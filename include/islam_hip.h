@@ -357,6 +357,69 @@ int islam_scale_ls_depth(const float* depth, const float* flow, const float* pos
                          const float* baseline, const uint8_t* edge, float* scale, float* z, uint8_t* mask,
                          uint8_t* dmask, double* sums, double* partial, int B, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------- dense reprojection: normal equations and pose refinement */
+
+/* The dense reprojection residual of dense_ba.DenseReprojectionLoss (reference dense_ba.py:179-273), differentiated.
+ * Inputs per link b = 0..B-1: depth (B,H,W) float32; flow (B,2,H,W) float32; mask (B,H,W) uint8 or NULL (all ones);
+ * motion (B,7) float64 = [t, q xyzw], the body-frame motion (run_pvgo's vo_motions); rgb2imu (7) float64 = C, NULL: identity;
+ * intr4 (B,4) float64 = fx, fy, cx, cy.
+ *
+ * Per link and pixel (u, v), all in float64:
+ *   T = C^-1 motion_b C,   P = z ((u - cx)/fx, (v - cy)/fy, 1),   Q = T^-1 P
+ *   valid = mask and Q_z > 0.1 and |Q_x/Q_z| <= 1 and |Q_y/Q_z| <= 1     (proj(..., return_mask=True), bounds inclusive)
+ *   r = (fx Q_x/Q_z + cx - (flow_u + u),  fy Q_y/Q_z + cy - (flow_v + v)),   s = |r|^2
+ * The perturbation is on the right of the body-frame motion, motion Exp(xi), xi = [rho, phi] (PyPose's order):
+ *   T(xi) = T Exp(A xi), A = Ad(C^-1);   dQ/dxi_cam = [-I3, [Q]x];
+ *   dr/dQ = [[fx/Q_z, 0, -fx Q_x/Q_z^2], [0, fy/Q_z, -fy Q_y/Q_z^2]];   J = dr/dQ dQ/dxi_cam A.
+ * With a robust kernel rho(s), c = rho'(s) (robust_kind = ISLAM_ROBUST_NONE / _HUBER / _CAUCHY and robust_delta = d as defined at
+ * islam_pvgo_robust below), summed over the valid pixels:
+ *   H = sum c J^T J (6x6, symmetric to the bit),  g = sum c J^T r (6),  cost = sum rho(s),  l1 = sum |r_u| + |r_v|,  count = n.
+ * l1 / n is DenseReprojectionLoss.__call__'s value; cost(xi) = cost + 2 g^T xi + xi^T H xi to second order; H / sigma_px^2 is
+ * the information of that edge's VO residual Log(P^-1 X_i^-1 X_j) in the frame and row order of islam_pvgo_run_chain_info's
+ * info_vo.  An empty mask gives H = 0, g = 0, count = 0.
+ *
+ * Outputs: out_H (B,6,6), out_g (B,6), out_cost, out_l1, out_count (B) (the count as a double), out_sums (B,30): the camera-frame
+ * sums before A is applied, [0..20] the upper triangle of sum c Jc^T Jc in row-major order of the triangle, [21..26] sum c Jc^T r,
+ * [27] cost, [28] l1, [29] count.  One workgroup row of ISLAM_DENSE_REPROJ_NBLK partial sums per link is reduced in fixed order
+ * without atomics: the same inputs give the same bits.  scratch: islam_dense_reproj_scratch_bytes(B, 0) bytes; calls that may run
+ * concurrently must not share it.  Only enqueues on `stream`.  ISLAM_EARG before any device work for B, H, W < 1 (or H*W > 2^30),
+ * an unknown robust kind, robust_delta <= 0, a NULL pointer other than mask and rgb2imu. */
+#define ISLAM_DENSE_REPROJ_NBLK 64
+#define ISLAM_DENSE_REPROJ_NSUM 30
+size_t islam_dense_reproj_scratch_bytes(int B, int iters_or_0);
+int islam_dense_reproj_normal(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                              const double* rgb2imu, const double* intr4, int robust_kind, double robust_delta,
+                              double* out_H, double* out_g, double* out_cost, double* out_l1, double* out_count,
+                              double* out_sums, void* scratch, int B, int H, int W, void* stream);
+
+/* Levenberg-Marquardt on these normal equations, `iters` evaluations, all on the device (two launches per evaluation, no host
+ * wait in between).  Evaluation 0 reduces at `motion`; evaluation k >= 1 reduces at the link's trial pose.  After it, per link:
+ *   1. the trial is accepted iff count_trial >= min_count, every sum is finite and cost_trial/count_trial < cost/count (the mean:
+ *      the pixel set moves with the pose, and losing pixels must not count as progress);
+ *   2. accepted: the trial's pose and sums become the link's state, lambda <- max(lambda/10, ISLAM_DENSE_REPROJ_LAMBDA_MIN);
+ *      otherwise lambda <- min(10 lambda, ISLAM_DENSE_REPROJ_LAMBDA_MAX);  (lambda starts at `damping`)
+ *   3. (H + lambda diag(H)) delta = -g by a 6x6 Cholesky;
+ *   4. the next trial is state Exp(delta), its quaternion normalised.  (Not after the last evaluation.)
+ * out_status (B): ISLAM_DENSE_REPROJ_FEW when, at `motion`, count < min_count or a sum is not finite; ISLAM_DENSE_REPROJ_NOTPD
+ * when step 3 meets a non-positive pivot.  Such a link stops where it stands (FEW, and NOTPD at evaluation 0: the pose as
+ * given; NOTPD later: the last accepted pose); the other links carry on.
+ * Outputs: out_motion (B,7) and out_H .. out_sums AT it, as islam_dense_reproj_normal writes them there (the same bits);
+ * out_lambda (B); out_accepted, out_rejected (B) int; trace (trace_cap,B) or NULL with trace_cap = 0: cost/count of evaluation
+ * k < trace_cap (evaluation 0: the start).  scratch: islam_dense_reproj_scratch_bytes(B, iters).  ISLAM_EARG before any device
+ * work for the cases of islam_dense_reproj_normal, iters < 1, damping < 0, min_count < 0, a NULL output, trace_cap > 0 with
+ * a NULL trace. */
+#define ISLAM_DENSE_REPROJ_OK 0
+#define ISLAM_DENSE_REPROJ_FEW 1
+#define ISLAM_DENSE_REPROJ_NOTPD 2
+#define ISLAM_DENSE_REPROJ_LAMBDA_MIN 1e-12
+#define ISLAM_DENSE_REPROJ_LAMBDA_MAX 1e12
+int islam_dense_reproj_refine(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                              const double* rgb2imu, const double* intr4, int robust_kind, double robust_delta, int iters,
+                              double damping, double min_count, double* out_motion, double* out_H, double* out_g,
+                              double* out_cost, double* out_l1, double* out_count, double* out_sums, double* out_lambda,
+                              int* out_accepted, int* out_rejected, int* out_status, double* trace, int trace_cap,
+                              void* scratch, int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

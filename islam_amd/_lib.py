@@ -17,6 +17,8 @@ c_void_p, c_int, c_int64, c_double, c_float, c_size_t = (ctypes.c_void_p, ctypes
                                                          ctypes.c_double, ctypes.c_float, ctypes.c_size_t)
 
 SCALE_NBLK, SCALE_NSUM = 16, 18
+DENSE_REPROJ_NBLK, DENSE_REPROJ_NSUM = 64, 30          # ISLAM_DENSE_REPROJ_NBLK / _NSUM
+DENSE_REPROJ_OK, DENSE_REPROJ_FEW, DENSE_REPROJ_NOTPD = 0, 1, 2  # ISLAM_DENSE_REPROJ_* status of a link under refinement
 MAX_LEVELS = 6          # ISLAM_PVGO_MAX_LEVELS
 
 
@@ -107,6 +109,10 @@ SIGNATURES = {
     'islam_edge_mask': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     'islam_scale_ls': (c_int, [c_void_p] * 13 + [c_int] * 3 + [c_void_p]),
     'islam_scale_ls_depth': (c_int, [c_void_p] * 12 + [c_int] * 3 + [c_void_p]),
+    'islam_dense_reproj_scratch_bytes': (c_size_t, [c_int, c_int]),
+    'islam_dense_reproj_normal': (c_int, [c_void_p] * 6 + [c_int, c_double] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    'islam_dense_reproj_refine': (c_int, [c_void_p] * 6 + [c_int, c_double, c_int, c_double, c_double] + [c_void_p] * 12 +
+                                  [c_int, c_void_p] + [c_int] * 3 + [c_void_p]),
     'islam_imu_scratch_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'islam_imu_preint': (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int] + [c_void_p] * 3 + [c_double, c_int] +
                          [c_void_p] * 4 + [c_int, c_void_p]),

@@ -1,0 +1,333 @@
+// Dense reprojection residual on gfx950: Gauss-Newton normal equations per link from one pass over the image, and a device-side
+// Levenberg-Marquardt on them (definitions: include/islam_hip.h, "dense reprojection").
+//
+// Per pixel (u, v) of link b, all in fp64:  P = z ((u-cx)/fx, (v-cy)/fy, 1),  Q = T^-1 P with T = C^-1 motion C,
+//   valid = mask & Q_z > 0.1 & |Q_x/Q_z| <= 1 & |Q_y/Q_z| <= 1,   r = (fx Q_x/Q_z + cx - (flow_u + u), fy Q_y/Q_z + cy - (flow_v + v)),
+//   J_cam = dr/dQ [-I, [Q]x]  (right perturbation T Exp(xi_cam)),  s = |r|^2,  c = rho'(s).
+// The partial kernel accumulates, in the CAMERA frame, sums[0..20] = the upper triangle of sum c J^T J in row-major order of the
+// triangle, sums[21..26] = sum c J^T r, sums[27] = sum rho(s), sums[28] = sum |r_u| + |r_v|, sums[29] = number of valid pixels.
+// HBM-bound: 13 bytes per pixel (depth, two flow floats, one mask byte) for ~150 flops.  The final kernel sums the NBLK rows of a
+// link in fixed order and applies A = Ad(C^-1) once: H = A^T H_cam A, g = A^T g_cam.  No atomics anywhere: a second call gives
+// the same bits.  Under refinement the final kernel's lane 0 also runs the LM bookkeeping of its link (accept test, damping,
+// 6x6 Cholesky in LDS, next trial pose), so an evaluation is two launches and the host never waits between them.
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+#include "lie_dev.h"
+
+using namespace islam;
+
+namespace {
+
+constexpr int NS = ISLAM_DENSE_REPROJ_NSUM;
+constexpr int NBLK = ISLAM_DENSE_REPROJ_NBLK;
+constexpr int S_G = 21, S_COST = 27, S_L1 = 28, S_COUNT = 29;
+
+// T^-1 = (C^-1 motion C)^-1; rgb2imu == nullptr: C = identity
+ISLAM_DEV SE3<double> camera_inverse(const double* pose7, const double* rgb2imu) {
+    SE3<double> T = se3_load(pose7);
+    if (rgb2imu) {
+        const SE3<double> C = se3_load(rgb2imu);
+        T = se3_mul(se3_mul(se3_inv(C), T), C);
+    }
+    return se3_inv(T);
+}
+
+__global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                                    const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                                    const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                                    double* __restrict__ partial, int H, int W, int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const double fx = intr4[4 * b], fy = intr4[4 * b + 1], cx = intr4[4 * b + 2], cy = intr4[4 * b + 3];
+    const SE3<double> Ti = camera_inverse(pose7 + 7 * b, rgb2imu);
+    const M3<double> R = qmat(Ti.q);
+    const V3<double> t = Ti.t;
+    const double d2 = delta * delta;
+
+    double acc[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) acc[i] = 0.0;
+
+    const float* zp = depth + (size_t)b * HW;
+    const float* fup = flow + (size_t)b * 2 * HW;
+    const float* fvp = fup + HW;
+    const uint8_t* mp = mask ? mask + (size_t)b * HW : nullptr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        const int v = i / W, u = i - v * W;
+        const double ud = (double)u, vd = (double)v;
+        const double z = (double)zp[i], flu = (double)fup[i], flv = (double)fvp[i];
+        const bool m = mp ? mp[i] != 0 : true;
+        const V3<double> P{z * ((ud - cx) / fx), z * ((vd - cy) / fy), z};
+        const V3<double> Q = R * P + t;
+        if (!(m && Q.z > 0.1)) continue;
+        const double px = Q.x / Q.z, py = Q.y / Q.z;
+        if (!(fabs(px) <= 1.0 && fabs(py) <= 1.0)) continue;
+        const double ru = fx * px + cx - (flu + ud), rv = fy * py + cy - (flv + vd);
+        const double s = ru * ru + rv * rv;
+        double rho = s, c = 1.0;
+        if (kind == ISLAM_ROBUST_HUBER) {
+            if (s > d2) {
+                const double rs = sqrt(s);
+                rho = 2.0 * delta * rs - d2;
+                c = delta / rs;
+            }
+        } else if (kind == ISLAM_ROBUST_CAUCHY) {
+            rho = d2 * log1p(s / d2);
+            c = 1.0 / (1.0 + s / d2);
+        }
+        // dr/dQ = [[a, 0, bq], [0, cq, dq]];  rows of dr/dQ [-I, [Q]x]
+        const double a = fx / Q.z, bq = -fx * Q.x / (Q.z * Q.z), cq = fy / Q.z, dq = -fy * Q.y / (Q.z * Q.z);
+        const double ju[6] = {-a, 0.0, -bq, -bq * Q.y, bq * Q.x - a * Q.z, a * Q.y};
+        const double jv[6] = {0.0, -cq, -dq, cq * Q.z - dq * Q.y, dq * Q.x, -cq * Q.x};
+        int k = 0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            const double wu = c * ju[p], wv = c * jv[p];
+#pragma unroll
+            for (int q = p; q < 6; ++q) acc[k++] += wu * ju[q] + wv * jv[q];
+            acc[S_G + p] += wu * ru + wv * rv;
+        }
+        acc[S_COST] += rho;
+        acc[S_L1] += fabs(ru) + fabs(rv);
+        acc[S_COUNT] += 1.0;
+    }
+    __shared__ double red[4][NS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        double x = acc[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+        if (lane == 0) red[wv][i] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS)
+        partial[((size_t)b * NBLK + blockIdx.x) * NS + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// what the final kernel writes per link; under refinement these arrays ARE the link's current state
+struct Outputs {
+    double *H, *g, *cost, *l1, *count, *sums;
+};
+
+// the LM bookkeeping of refinement (motion == nullptr: normal equations only)
+struct Refine {
+    double* motion;        // (B,7) current pose
+    double* trial;         // (B,7) next pose to evaluate
+    double* lambda;        // (B)
+    int *accepted, *rejected, *status;
+    double* trace;         // (trace_cap,B) mean cost of each evaluation, or nullptr
+    int trace_cap;
+    int eval;              // index of this evaluation
+    int last;              // no further evaluation follows
+    double min_count, lambda0;
+};
+
+// index of (i, j), i <= j, in the row-major upper triangle of a 6x6
+ISLAM_DEV int tri(int i, int j) { return i * (11 - i) / 2 + j; }
+
+// (H + lambda diag H) x = -g by Cholesky, everything in LDS (runtime-indexed: private arrays would go to scratch memory);
+// false on a non-positive (or NaN) pivot
+ISLAM_DEV bool lm_step(const double* Hn, const double* gn, double lambda, double (*L)[6], double* x) {
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j <= i; ++j) L[i][j] = Hn[i * 6 + j] + (i == j ? lambda * Hn[i * 6 + i] : 0.0);
+    for (int j = 0; j < 6; ++j) {
+        double d = L[j][j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(d > 0.0)) return false;
+        d = sqrt(d);
+        L[j][j] = d;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = L[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / d;
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        double v = -gn[i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * x[k];
+        x[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double v = x[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(64) void dense_reproj_final_kernel(const double* __restrict__ partial, const double* __restrict__ rgb2imu,
+                                                                 const double* __restrict__ pose_eval, Outputs out, Refine rf, int B) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    __shared__ double s[NS], Rm[9], Sm[9], A[36], Hn[36], gn[6], L[6][6], x[6], cur[7];
+    __shared__ int take;
+    if (i < NS) {
+        double v = 0.0;
+        for (int k = 0; k < NBLK; ++k) v += partial[((size_t)b * NBLK + k) * NS + i];
+        s[i] = v;
+    }
+    if (i == 0) {      // C^-1 = (R, t)
+        M3<double> Rc = m3_identity<double>(), Sc{0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (rgb2imu) {
+            const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
+            Rc = qmat(Ci.q);
+            Sc = skew(Ci.t) * Rc;
+        }
+        m3_store(Rc, Rm);
+        m3_store(Sc, Sm);
+    }
+    __syncthreads();
+    if (i < 36) {      // A = Ad(C^-1) = [[R, [t]x R], [0, R]]
+        const int r = i / 6, c = i - 6 * r;
+        A[i] = r < 3 ? (c < 3 ? Rm[3 * r + c] : Sm[3 * r + c - 3]) : (c < 3 ? 0.0 : Rm[3 * (r - 3) + c - 3]);
+    }
+    __syncthreads();
+    if (i < 36) {      // H = A^T H_cam A; (r, c) and (c, r) run the same operations, so H is symmetric to the bit
+        const int r0 = i / 6, c0 = i - 6 * r0;
+        const int r = min(r0, c0), c = max(r0, c0);
+        double v = 0.0;
+        for (int k = 0; k < 6; ++k) {
+            double w = 0.0;
+            for (int l = 0; l < 6; ++l) w += s[tri(min(k, l), max(k, l))] * A[l * 6 + c];
+            v += A[k * 6 + r] * w;
+        }
+        Hn[i] = v;
+    } else if (i < 42) {
+        const int r = i - 36;
+        double v = 0.0;
+        for (int k = 0; k < 6; ++k) v += A[k * 6 + r] * s[S_G + k];
+        gn[r] = v;
+    }
+    __syncthreads();
+
+    const bool refine = rf.motion != nullptr;
+    if (refine && i == 0) {
+        bool finite = true;
+        for (int k = 0; k < NS; ++k) finite = finite && isfinite(s[k]);
+        const double n = s[S_COUNT];
+        int acc = 0;
+        if (rf.eval == 0) {        // the state at the pose as given
+            acc = 1;
+            rf.lambda[b] = rf.lambda0;
+            rf.accepted[b] = 0;
+            rf.rejected[b] = 0;
+            rf.status[b] = (finite && n >= rf.min_count) ? ISLAM_DENSE_REPROJ_OK : ISLAM_DENSE_REPROJ_FEW;
+        } else if (rf.status[b] == ISLAM_DENSE_REPROJ_OK) {
+            // the MEAN is compared: the pixel set moves with the pose, and losing pixels must not count as progress
+            acc = finite && n >= rf.min_count && s[S_COST] / n < out.cost[b] / out.count[b];
+            if (acc) {
+                rf.lambda[b] = fmax(rf.lambda[b] / 10.0, ISLAM_DENSE_REPROJ_LAMBDA_MIN);
+                rf.accepted[b] += 1;
+            } else {
+                rf.lambda[b] = fmin(rf.lambda[b] * 10.0, ISLAM_DENSE_REPROJ_LAMBDA_MAX);
+                rf.rejected[b] += 1;
+            }
+        }
+        if (rf.trace && rf.eval < rf.trace_cap) rf.trace[(size_t)rf.eval * B + b] = s[S_COST] / n;
+        take = acc;
+    }
+    if (!refine && i == 0) take = 1;
+    __syncthreads();
+    if (take) {
+        if (i < 36) out.H[(size_t)b * 36 + i] = Hn[i];
+        if (i < 6) out.g[(size_t)b * 6 + i] = gn[i];
+        if (i < NS) out.sums[(size_t)b * NS + i] = s[i];
+        if (i == 0) {
+            out.cost[b] = s[S_COST];
+            out.l1[b] = s[S_L1];
+            out.count[b] = s[S_COUNT];
+        }
+        if (refine && i < 7) {
+            cur[i] = pose_eval[(size_t)b * 7 + i];
+            rf.motion[(size_t)b * 7 + i] = cur[i];
+        }
+    } else {           // (refinement only) the step below starts from the state an earlier evaluation left
+        if (i < 36) Hn[i] = out.H[(size_t)b * 36 + i];
+        if (i < 6) gn[i] = out.g[(size_t)b * 6 + i];
+        if (i < 7) cur[i] = rf.motion[(size_t)b * 7 + i];
+    }
+    if (!refine || rf.last) return;
+    __syncthreads();
+    if (i == 0) {
+        SE3<double> X = se3_load(cur);
+        if (rf.status[b] == ISLAM_DENSE_REPROJ_OK) {
+            if (lm_step(Hn, gn, rf.lambda[b], L, x)) {
+                X = se3_mul(X, se3_exp(v3(x[0], x[1], x[2]), v3(x[3], x[4], x[5])));
+                const double qn = 1.0 / sqrt(X.q.x * X.q.x + X.q.y * X.q.y + X.q.z * X.q.z + X.q.w * X.q.w);
+                X.q = {qn * X.q.x, qn * X.q.y, qn * X.q.z, qn * X.q.w};
+            } else {
+                rf.status[b] = ISLAM_DENSE_REPROJ_NOTPD;
+            }
+        }
+        se3_store(X, rf.trial + (size_t)b * 7);      // a link whose status is set keeps being evaluated where it stands
+    }
+}
+
+int check_common(const char* who, const float* depth, const float* flow, const double* motion, const double* intr4, int kind, double delta,
+                 const Outputs& o, const void* scratch, int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(ISLAM_EARG, "%s: bad shape (%d,%d,%d)", who, B, H, W);
+    if (kind != ISLAM_ROBUST_NONE && kind != ISLAM_ROBUST_HUBER && kind != ISLAM_ROBUST_CAUCHY)
+        return fail(ISLAM_EARG, "%s: unknown robust kind %d", who, kind);
+    if (!(delta > 0.0)) return fail(ISLAM_EARG, "%s: robust delta must be positive (got %g)", who, delta);
+    if (!depth || !flow || !motion || !intr4 || !o.H || !o.g || !o.cost || !o.l1 || !o.count || !o.sums || !scratch)
+        return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / output / scratch pointer", who);
+    return ISLAM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t islam_dense_reproj_scratch_bytes(int B, int iters_or_0) {
+    if (B < 1) return 0;
+    size_t n = align_up((size_t)B * NBLK * NS * sizeof(double));
+    if (iters_or_0 > 0) n += align_up((size_t)B * 7 * sizeof(double));
+    return n;
+}
+
+extern "C" int islam_dense_reproj_normal(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                         const double* rgb2imu, const double* intr4, int robust_kind, double robust_delta,
+                                         double* out_H, double* out_g, double* out_cost, double* out_l1, double* out_count,
+                                         double* out_sums, void* scratch, int B, int H, int W, void* stream) {
+    const Outputs o{out_H, out_g, out_cost, out_l1, out_count, out_sums};
+    if (int rc = check_common("islam_dense_reproj_normal", depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W))
+        return rc;
+    hipStream_t s = as_stream(stream);
+    double* partial = static_cast<double*>(scratch);
+    hipLaunchKernelGGL(dense_reproj_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4, partial,
+                       H, W, robust_kind, robust_delta);
+    hipLaunchKernelGGL(dense_reproj_final_kernel, dim3(B), dim3(64), 0, s, partial, rgb2imu, motion, o, Refine{}, B);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+extern "C" int islam_dense_reproj_refine(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                         const double* rgb2imu, const double* intr4, int robust_kind, double robust_delta, int iters,
+                                         double damping, double min_count, double* out_motion, double* out_H, double* out_g,
+                                         double* out_cost, double* out_l1, double* out_count, double* out_sums, double* out_lambda,
+                                         int* out_accepted, int* out_rejected, int* out_status, double* trace, int trace_cap,
+                                         void* scratch, int B, int H, int W, void* stream) {
+    const char* who = "islam_dense_reproj_refine";
+    const Outputs o{out_H, out_g, out_cost, out_l1, out_count, out_sums};
+    if (int rc = check_common(who, depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W)) return rc;
+    if (iters < 1) return fail(ISLAM_EARG, "%s: iters must be at least 1 (got %d)", who, iters);
+    if (!(damping >= 0.0) || !(min_count >= 0.0)) return fail(ISLAM_EARG, "%s: damping and min_count must be non-negative", who);
+    if (!out_motion || !out_lambda || !out_accepted || !out_rejected || !out_status)
+        return fail(ISLAM_EARG, "%s: NULL out_motion / out_lambda / out_accepted / out_rejected / out_status", who);
+    if (trace_cap < 0 || (trace_cap > 0 && !trace)) return fail(ISLAM_EARG, "%s: trace_cap %d without a trace buffer", who, trace_cap);
+    hipStream_t s = as_stream(stream);
+    double* partial = static_cast<double*>(scratch);
+    double* trial = reinterpret_cast<double*>(static_cast<char*>(scratch) + align_up((size_t)B * NBLK * NS * sizeof(double)));
+    Refine rf{out_motion, trial, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
+              min_count, damping};
+    for (int k = 0; k < iters; ++k) {
+        const double* pose = k == 0 ? motion : trial;
+        rf.eval = k;
+        rf.last = k == iters - 1;
+        hipLaunchKernelGGL(dense_reproj_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, pose, rgb2imu, intr4, partial,
+                           H, W, robust_kind, robust_delta);
+        hipLaunchKernelGGL(dense_reproj_final_kernel, dim3(B), dim3(64), 0, s, partial, rgb2imu, pose, o, rf, B);
+    }
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}

@@ -5,7 +5,9 @@
     the HIP LM loop as the 5th residual (islam_pvgo_run_chain_reproj); ``__call__`` evaluates the residual with LieTensor
     ops on whatever device its tensors live on (used for inspection and by the tests);
   * DenseReprojectionLoss (dense_ba.py:179-273): the per-frame mean L1 reprojection error over the masked pixels.  The
-    reference cannot feed it to run_pvgo (it has no ``.N``, pvgo.py:131), so it is evaluation-only here as well;
+    reference cannot feed it to run_pvgo (it has no ``.N``, pvgo.py:131), so ``__call__`` is evaluation-only here as well;
+    ``normal_equations`` / ``refine`` / ``information`` differentiate the same residual on the GPU (csrc/dense_reproj.hip,
+    DESIGN.md section 3.23) and give run_pvgo its VO information (PvgoInfo.from_dense_reproj);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -149,3 +151,48 @@ class DenseReprojectionLoss:
         rv = fy * p[..., 1] + cy * p[..., 2] - (self.flow[:, 1].to(dt) + v)
         l1 = ru.abs() + rv.abs()
         return torch.stack([l1[i][mask[i]].mean() for i in range(B)])
+
+    def _motion7(self, motion):
+        """``motion`` (LieTensor or tensor, SE3 (B,7) or se3 (B,6)) as a plain (B,7) tensor, one row per stored frame pair."""
+        if isinstance(motion, pp.LieTensor):
+            T = motion if motion.shape[-1] == 7 else motion.Exp()
+        else:
+            motion = torch.as_tensor(motion)
+            T = pp.SE3(motion) if motion.shape[-1] == 7 else pp.se3(motion).Exp()
+        m = pp._plain(T).detach().reshape(-1, 7)
+        if m.shape[0] != self.z.shape[0]:
+            raise ValueError('DenseReprojectionLoss: %d motions for %d frame pairs' % (m.shape[0], self.z.shape[0]))
+        return m
+
+    def normal_equations(self, motion, kernel=None):
+        """The residual of ``__call__`` differentiated: ops.dense_reproj_normal on the stored depth, flow, mask, intrinsics and
+        mount.  Returns H (B,6,6), g (B,6), cost, l1, count (B) and the camera-frame sums (B,30), float64 on the device; the
+        perturbation is motion Exp(xi), and l1 / count is ``__call__``'s value."""
+        from . import ops
+        return ops.dense_reproj_normal(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64),
+                                       rgb2imu=self.rgb2imu_pose, kernel=kernel)
+
+    def refine(self, motion, iters=10, kernel=None, damping=1e-4, min_count=16, trace_cap=0):
+        """``iters`` device-side Levenberg-Marquardt evaluations per link from ``motion`` (ops.dense_reproj_refine); the result's
+        ``motion`` is the refined (B,7) and ``status`` marks the links that could not be refined."""
+        from . import ops
+        return ops.dense_reproj_refine(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64),
+                                       rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
+                                       trace_cap=trace_cap)
+
+    def information(self, motion, sigma_px=1.0, kernel=None):
+        """H / sigma_px^2 (B,6,6) float64: the information of each link's VO residual in the frame and row order of PvgoInfo.vo, for
+        flow errors of ``sigma_px`` pixels per component (PvgoInfo.from_dense_reproj).  sigma_px='residual' estimates the variance per
+        link from the fit itself, sigma^2 = cost / (2 count - 6); a link with 2 count <= 6 gives the zero matrix."""
+        ne = self.normal_equations(motion, kernel=kernel)
+        if isinstance(sigma_px, str):
+            if sigma_px != 'residual':
+                raise ValueError("information: sigma_px must be a positive number or 'residual' (got %r)" % (sigma_px,))
+            dof = 2.0 * ne.count - 6.0
+            ok = dof > 0
+            var = torch.where(ok, ne.cost / torch.where(ok, dof, torch.ones_like(dof)), torch.ones_like(dof))
+            return torch.where(ok.view(-1, 1, 1), ne.H / var.view(-1, 1, 1), torch.zeros_like(ne.H))
+        sigma_px = float(sigma_px)
+        if not (sigma_px > 0.0 and sigma_px < float('inf')):
+            raise ValueError('information: sigma_px must be a finite positive number (got %r)' % (sigma_px,))
+        return ne.H / sigma_px ** 2

@@ -166,6 +166,28 @@ class PvgoInfo:
         return 0.5 * (C + np.swapaxes(C, 1, 2))
 
     @classmethod
+    def from_dense_reproj(cls, H, sigma_px=1.0, floor=0.0, imu=None, vel=None, rot=None, transvel=None):
+        """Information of the VO factors from the dense reprojection Hessians (DenseReprojectionLoss.normal_equations /
+        ops.dense_reproj_normal): vo = H / sigma_px^2 + floor I, symmetrised and validated like every other
+        group.  H (E,6,6): sum c J^T J of each edge's residual under the right perturbation motion Exp(xi); the VO residual
+        Log(P^-1 X_i^-1 X_j) is -xi to first order, so H / sigma_px^2 is its information as it stands, rows [rho, phi].  sigma_px:
+        standard deviation of one flow component in pixels.  ``imu`` or ``vel`` / ``rot`` / ``transvel`` are passed through.
+
+        Flow errors of neighbouring pixels are correlated, while the sum treats every pixel as an independent measurement: the matrix
+        is optimistic by about the correlation area in pixels.  ``sigma_px`` is where a user accounts for that (sigma_px^2 times the
+        correlation area).  An edge with H = 0 (no valid pixel) is a factor switched off."""
+        h = H.detach().cpu().numpy() if isinstance(H, torch.Tensor) else np.asarray(H)
+        h = np.asarray(h, dtype=np.float64)
+        if h.ndim != 3 or h.shape[1:] != (6, 6):
+            raise ValueError('from_dense_reproj: H must be (E,6,6), got %s' % (h.shape,))
+        sigma_px, floor = float(sigma_px), float(floor)
+        if not (np.isfinite(sigma_px) and sigma_px > 0.0):
+            raise ValueError('from_dense_reproj: sigma_px must be a finite positive number (got %r)' % (sigma_px,))
+        if not (np.isfinite(floor) and floor >= 0.0):
+            raise ValueError('from_dense_reproj: floor must be a finite non-negative number (got %r)' % (floor,))
+        return cls(vo=h / sigma_px ** 2 + floor * np.eye(6), vel=vel, rot=rot, transvel=transvel, validate=True, imu=imu)
+
+    @classmethod
     def from_imu_cov(cls, cov, rot=None, floor=0.0, vo=None, correlated=False):
         """Information of the IMU factors from the pre-integration covariances (IMUModule(prop_cov=True) / ops.imu_preint_cov in
         motion mode).  With such covariances at hand call it with ``correlated=True``: that is the

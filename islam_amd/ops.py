@@ -3,6 +3,7 @@
 PyTorch is used for device memory and the current HIP stream only.  All functions raise when given
 CPU tensors: the product path has no CPU fallback.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -151,6 +152,84 @@ def scale_ls(disp, flow, pose7, intr4, baseline, edge, disp_th, depth_input=Fals
                                    ptr(scale), ptr(z), ptr(mask), ptr(dmask), ptr(sums), ptr(partial), B, H, W,
                                    stream_ptr(dev)))
     return scale, z, mask.bool(), dmask.bool(), sums
+
+
+# --------------------------------------------------------------------------- dense reprojection
+DenseReprojNormal = collections.namedtuple('DenseReprojNormal', 'H g cost l1 count sums')
+DenseReprojRefined = collections.namedtuple('DenseReprojRefined', 'motion H g cost l1 count sums damping accepted rejected status trace')
+
+
+def _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel):
+    """The device tensors and scalars both entry points take (include/islam_hip.h, "dense reprojection")."""
+    from . import lietensor as pp
+    from .robust import NONE, _Kernel
+    require_cuda(depth, flow)
+    dev = depth.device
+    if flow.dim() != 4 or flow.shape[1] != 2 or depth.dim() != 3 or (depth.shape[0],) + tuple(depth.shape[1:]) != (flow.shape[0],) + tuple(flow.shape[2:]):
+        raise ValueError('dense_reproj: depth must be (B,H,W) and flow (B,2,H,W), got %s and %s' % (tuple(depth.shape), tuple(flow.shape)))
+    B, H, W = depth.shape
+    depth, flow = _f32c(depth), _f32c(flow)
+    if mask is not None:
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError('dense_reproj: mask must be (%d,%d,%d), got %s' % (B, H, W, tuple(mask.shape)))
+        mask = (mask.to(dev) != 0).to(torch.uint8).contiguous()
+    f64 = lambda t: pp._plain(torch.as_tensor(t)).detach().to(dev, torch.float64).contiguous()
+    motion = f64(motion)
+    if tuple(motion.shape) != (B, 7):
+        raise ValueError('dense_reproj: motion must be (%d,7) [t, q xyzw], got %s' % (B, tuple(motion.shape)))
+    intr = f64(intr)
+    if intr.numel() == 4:
+        intr = intr.reshape(1, 4).expand(B, 4).contiguous()
+    if tuple(intr.shape) != (B, 4):
+        raise ValueError('dense_reproj: intr must be (4) or (%d,4) = fx, fy, cx, cy, got %s' % (B, tuple(intr.shape)))
+    if rgb2imu is not None:
+        rgb2imu = f64(rgb2imu).reshape(-1)
+        if rgb2imu.numel() != 7:
+            raise ValueError('dense_reproj: rgb2imu must be one SE3 (7), got %d values' % rgb2imu.numel())
+    if kernel is not None and not isinstance(kernel, _Kernel):
+        raise ValueError('dense_reproj: kernel must be None, Huber(delta) or Cauchy(delta) (got %r)' % (kernel,))
+    kind, delta = (NONE, 1.0) if kernel is None else (kernel.kind, kernel.delta)
+    return dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta
+
+
+def _dense_reproj_outputs(B, dev):
+    e = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    return DenseReprojNormal(e(B, 6, 6), e(B, 6), e(B), e(B), e(B), e(B, _lib.DENSE_REPROJ_NSUM))
+
+
+def dense_reproj_normal(depth, flow, mask, motion, intr, rgb2imu=None, kernel=None):
+    """Gauss-Newton normal equations of the dense reprojection residual per link (include/islam_hip.h, "dense reprojection";
+    DESIGN.md section 3.23).  depth (B,H,W), flow (B,2,H,W), mask (B,H,W) or None, motion (B,7) SE3 [t, q], intr (4) or (B,4) =
+    fx, fy, cx, cy, rgb2imu (7) or None, kernel None / robust.Huber / robust.Cauchy.  Returns DenseReprojNormal(H (B,6,6), g (B,6),
+    cost, l1, count (B), sums (B,30)), float64 on the device; nothing is read back."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    out = _dense_reproj_outputs(B, dev)
+    scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(B, 0), dtype=torch.uint8, device=dev)
+    check(lib().islam_dense_reproj_normal(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), kind, delta,
+                                          ptr(out.H), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums),
+                                          ptr(scratch), B, H, W, stream_ptr(dev)))
+    return out
+
+
+def dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=None, kernel=None, iters=10, damping=1e-4, min_count=16, trace_cap=0):
+    """``iters`` Levenberg-Marquardt evaluations on the dense reprojection cost of each link, all on the device (accept rule and
+    schedule: include/islam_hip.h, islam_dense_reproj_refine).  Arguments as dense_reproj_normal; damping: the initial lambda;
+    min_count: fewest valid pixels a pose may have.  Returns DenseReprojRefined: motion (B,7) and H, g, cost, l1, count, sums at it,
+    damping (B), accepted, rejected, status (B) int32 (0, or _lib.DENSE_REPROJ_FEW / _NOTPD: that link's pose came back as it
+    stood) and trace (trace_cap,B) = the mean cost of each evaluation (None for trace_cap = 0)."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    iters, trace_cap = int(iters), int(trace_cap)
+    out = _dense_reproj_outputs(B, dev)
+    pose = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    lam = torch.empty(B, dtype=torch.float64, device=dev)
+    acc, rej, status = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    trace = torch.full((trace_cap, B), float('nan'), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(B, max(iters, 1)), dtype=torch.uint8, device=dev)
+    check(lib().islam_dense_reproj_refine(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), kind, delta, iters,
+                                          float(damping), float(min_count), ptr(pose), ptr(out.H), ptr(out.g), ptr(out.cost),
+                                          ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc), ptr(rej), ptr(status),
+                                          ptr(trace), trace_cap, ptr(scratch), B, H, W, stream_ptr(dev)))
+    return DenseReprojRefined(pose, *out, lam, acc, rej, status, trace)
 
 
 # --------------------------------------------------------------------------- 3x3 convolution on the matrix cores
