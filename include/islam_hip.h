@@ -420,6 +420,35 @@ int islam_dense_reproj_refine(const float* depth, const float* flow, const uint8
                               int* out_accepted, int* out_rejected, int* out_status, double* trace, int trace_cap,
                               void* scratch, int B, int H, int W, void* stream);
 
+/* The gradient of the refined pose with respect to depth and flow.
+ *
+ * islam_dense_reproj_vjp: for w (B,6) float64 in the body frame, [rho, phi], the derivative of Phi = w^T g (g as
+ * islam_dense_reproj_normal returns it at `motion`) in every depth and flow value, with the pose and the valid set held fixed.
+ * With w_cam = A w, per valid pixel (a, bq, cq, dq: the entries of dr/dQ above; c' = dc/ds):
+ *   m = -w_cam,rho + Q x w_cam,phi,   q = dr/dQ m,   e = c q + 2 c' (q.r) r,   dQ = R ((u - cx)/fx, (v - cy)/fy, 1)  (R of T^-1)
+ *   dPhi/dflow = -e,   dPhi/dz = e.(dr/dQ dQ) + c r.[ (d(dr/dQ)/dQ [dQ]) m + dr/dQ (dQ x w_cam,phi) ]
+ *   c' = 0 without a kernel; Huber: -d / (2 s^(3/2)) for s > d^2, else 0; Cauchy: -1 / (d^2 (1 + s/d^2)^2).
+ * grad_depth (B,H,W) and grad_flow (B,2,H,W), float32, are written in full: exactly 0 at every invalid pixel and over a whole link
+ * whose status_or_null (B, int; NULL: all 0) is not 0.  All arithmetic is float64, rounded once at the store; no reduction and no
+ * atomics: the same inputs give the same bits.
+ *
+ * islam_dense_reproj_ift_weights: the w for which that derivative is the gradient of a loss L on the pose a refinement ended at
+ * (implicit function theorem: at the optimum xi*(theta) = -H^-1 g(theta) to first order, so dL = w^T dg with w = -H^-1 v).
+ * grad_motion (B,7) = dL/d[t, q xyzw] at `motion` (B,7); v = dL/dxi on motion Exp(xi):  v_rho = R_motion^T dL/dt,
+ * v_phi = 1/2 E^T dL/dq, E (4x3) = d(q (x, 1))/dx at 0;  H (B,6,6): the undamped matrix islam_dense_reproj_refine returns.
+ * Using H for dg/dxi is the Gauss-Newton approximation: exact where the residual vanishes, off by terms proportional to the
+ * residual elsewhere.  status_out (B): status_in_or_null's value where that is not 0, ISLAM_DENSE_REPROJ_NOTPD where the Cholesky
+ * of H meets a non-positive pivot, else 0; w (B,6) is 0 for a link whose status_out is not 0.  One launch; the host never waits.
+ *
+ * Both return ISLAM_EARG before any device work for B (H, W) < 1 (or H*W > 2^30), an unknown robust kind, robust_delta <= 0, a NULL
+ * pointer other than mask, rgb2imu and the incoming status. */
+int islam_dense_reproj_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                           const double* rgb2imu, const double* intr4, int B, int H, int W, int robust_kind,
+                           double robust_delta, const double* w, const int* status_or_null, float* grad_depth,
+                           float* grad_flow, void* stream);
+int islam_dense_reproj_ift_weights(const double* H, const double* motion, const double* grad_motion,
+                                   const int* status_in_or_null, int B, double* w, int* status_out, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

@@ -10,6 +10,7 @@
 // link in fixed order and applies A = Ad(C^-1) once: H = A^T H_cam A, g = A^T g_cam.  No atomics anywhere: a second call gives
 // the same bits.  Under refinement the final kernel's lane 0 also runs the LM bookkeeping of its link (accept test, damping,
 // 6x6 Cholesky in LDS, next trial pose), so an evaluation is two launches and the host never waits between them.
+// Further down: the gradient of the refined pose in depth and flow (reproj_vjp_kernel, reproj_ift_kernel).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -276,6 +277,126 @@ int check_common(const char* who, const float* depth, const float* flow, const d
     return ISLAM_OK;
 }
 
+// ------------------------------------------------------------------ the gradient of the refined pose in depth and flow
+//   Phi = w^T g = sum_valid c(s) q.r with q = dr/dQ m, m = [-I, [Q]x] A w, at a fixed pose and a fixed
+// valid set.  reproj_vjp_kernel writes dPhi/dz and dPhi/dflow of every pixel: the partial kernel's pass without its reduction, 13
+// bytes read and 12 written per pixel, no LDS, no atomics.  reproj_ift_kernel makes the w for which that is the gradient of a loss
+// on the refined pose: w = -H^-1 v, v the loss's gradient in the right tangent of the pose.
+// (The two names leave "dense_reproj" to the two kernels above: tests/test_dense_reproj_cpu.py counts the kernels that carry it.)
+__global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                          const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                          const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                          const double* __restrict__ w6, const int* __restrict__ status,
+                                                          float* __restrict__ grad_depth, float* __restrict__ grad_flow, int H, int W,
+                                                          int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    float* gzp = grad_depth + (size_t)b * HW;
+    float* gup = grad_flow + (size_t)b * 2 * HW;
+    float* gvp = gup + HW;
+    if (status && status[b] != ISLAM_DENSE_REPROJ_OK) {      // a link without a gradient: zeros, whatever its pixels hold
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) gzp[i] = gup[i] = gvp[i] = 0.0f;
+        return;
+    }
+    const double fx = intr4[4 * b], fy = intr4[4 * b + 1], cx = intr4[4 * b + 2], cy = intr4[4 * b + 3];
+    const SE3<double> Ti = camera_inverse(pose7 + 7 * b, rgb2imu);
+    const M3<double> R = qmat(Ti.q);
+    const V3<double> t = Ti.t;
+    const double d2 = delta * delta;
+    // w_cam = Ad(C^-1) w = [R_c w_rho + t_c x (R_c w_phi), R_c w_phi]
+    V3<double> wr{w6[6 * b], w6[6 * b + 1], w6[6 * b + 2]}, wf{w6[6 * b + 3], w6[6 * b + 4], w6[6 * b + 5]};
+    if (rgb2imu) {
+        const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
+        const M3<double> Rc = qmat(Ci.q);
+        wf = Rc * wf;
+        wr = Rc * wr + cross(Ci.t, wf);
+    }
+
+    const float* zp = depth + (size_t)b * HW;
+    const float* fup = flow + (size_t)b * 2 * HW;
+    const float* fvp = fup + HW;
+    const uint8_t* mp = mask ? mask + (size_t)b * HW : nullptr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        const int v = i / W, u = i - v * W;
+        const double ud = (double)u, vd = (double)v;
+        const double z = (double)zp[i], flu = (double)fup[i], flv = (double)fvp[i];
+        const bool m = mp ? mp[i] != 0 : true;
+        const double xh = (ud - cx) / fx, yh = (vd - cy) / fy;
+        const V3<double> P{z * xh, z * yh, z};
+        const V3<double> Q = R * P + t;
+        double gz = 0.0, gu = 0.0, gv = 0.0;
+        bool valid = m && Q.z > 0.1;
+        double px = 0.0, py = 0.0;
+        if (valid) {
+            px = Q.x / Q.z;
+            py = Q.y / Q.z;
+            valid = fabs(px) <= 1.0 && fabs(py) <= 1.0;
+        }
+        if (valid) {
+            const double ru = fx * px + cx - (flu + ud), rv = fy * py + cy - (flv + vd);
+            const double s = ru * ru + rv * rv;
+            double c = 1.0, cp = 0.0;          // c = rho'(s), cp = dc/ds
+            if (kind == ISLAM_ROBUST_HUBER) {
+                if (s > d2) {
+                    const double rs = sqrt(s);
+                    c = delta / rs;
+                    cp = -delta / (2.0 * s * rs);
+                }
+            } else if (kind == ISLAM_ROBUST_CAUCHY) {
+                const double k = 1.0 + s / d2;
+                c = 1.0 / k;
+                cp = -1.0 / (d2 * k * k);
+            }
+            const double a = fx / Q.z, bq = -fx * Q.x / (Q.z * Q.z), cq = fy / Q.z, dq = -fy * Q.y / (Q.z * Q.z);
+            const V3<double> mm = cross(Q, wf) - wr;                            // [-I, [Q]x] w_cam
+            const double qu = a * mm.x + bq * mm.z, qv = cq * mm.y + dq * mm.z;  // q = dr/dQ m
+            const double k2 = 2.0 * cp * (qu * ru + qv * rv);
+            const double eu = c * qu + k2 * ru, ev = c * qv + k2 * rv;           // e = d(c q.r)/dr
+            const V3<double> dQ = R * V3<double>{xh, yh, 1.0};                   // dQ/dz
+            const double iz = 1.0 / Q.z;
+            const double da = -a * iz * dQ.z, dbq = -a * iz * dQ.x - 2.0 * bq * iz * dQ.z;      // d(dr/dQ) along dQ
+            const double dcq = -cq * iz * dQ.z, ddq = -cq * iz * dQ.y - 2.0 * dq * iz * dQ.z;
+            const V3<double> n = cross(dQ, wf);                                 // dm along dQ
+            const double tu = da * mm.x + dbq * mm.z + a * n.x + bq * n.z, tv = dcq * mm.y + ddq * mm.z + cq * n.y + dq * n.z;
+            gz = eu * (a * dQ.x + bq * dQ.z) + ev * (cq * dQ.y + dq * dQ.z) + c * (ru * tu + rv * tv);
+            gu = -eu;
+            gv = -ev;
+        }
+        gzp[i] = (float)gz;
+        gup[i] = (float)gu;
+        gvp[i] = (float)gv;
+    }
+}
+
+// w = -H^-1 v per link, v = dL/dxi on motion Exp(xi) from the gradient on [t, q xyzw]: v_rho = R^T dL/dt, v_phi = 1/2 E^T dL/dq with
+// E = d(q (x, 1))/dx at 0 = [[q_w I + [q_v]x], [-q_v^T]].  A link that comes with a status, or whose H has a non-positive pivot,
+// gets w = 0.
+__global__ __launch_bounds__(64) void reproj_ift_kernel(const double* __restrict__ Hm, const double* __restrict__ motion,
+                                                         const double* __restrict__ grad_motion, const int* __restrict__ status_in,
+                                                         double* __restrict__ w, int* __restrict__ status_out) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    __shared__ double Hn[36], vn[6], L[6][6], x[6];
+    __shared__ int st;
+    if (i < 36) Hn[i] = Hm[(size_t)b * 36 + i];
+    if (i == 0) {
+        const SE3<double> X = se3_load(motion + (size_t)b * 7);
+        const double* gm = grad_motion + (size_t)b * 7;
+        const V3<double> vr = tmul(qmat(X.q), v3(gm[0], gm[1], gm[2]));
+        const V3<double> qv{X.q.x, X.q.y, X.q.z}, gq{gm[3], gm[4], gm[5]};
+        const V3<double> vf = 0.5 * (X.q.w * gq - cross(qv, gq) - gm[6] * qv);
+        vn[0] = vr.x; vn[1] = vr.y; vn[2] = vr.z; vn[3] = vf.x; vn[4] = vf.y; vn[5] = vf.z;
+    }
+    __syncthreads();
+    if (i == 0) {
+        int s = status_in ? status_in[b] : ISLAM_DENSE_REPROJ_OK;
+        if (s == ISLAM_DENSE_REPROJ_OK && !lm_step(Hn, vn, 0.0, L, x)) s = ISLAM_DENSE_REPROJ_NOTPD;
+        st = s;
+        status_out[b] = s;
+    }
+    __syncthreads();
+    if (i < 6) w[(size_t)b * 6 + i] = st == ISLAM_DENSE_REPROJ_OK ? x[i] : 0.0;
+}
+
 }  // namespace
 
 extern "C" size_t islam_dense_reproj_scratch_bytes(int B, int iters_or_0) {
@@ -328,6 +449,34 @@ extern "C" int islam_dense_reproj_refine(const float* depth, const float* flow, 
                            H, W, robust_kind, robust_delta);
         hipLaunchKernelGGL(dense_reproj_final_kernel, dim3(B), dim3(64), 0, s, partial, rgb2imu, pose, o, rf, B);
     }
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+extern "C" int islam_dense_reproj_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                      const double* rgb2imu, const double* intr4, int B, int H, int W, int robust_kind,
+                                      double robust_delta, const double* w, const int* status_or_null, float* grad_depth,
+                                      float* grad_flow, void* stream) {
+    const char* who = "islam_dense_reproj_vjp";
+    if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(ISLAM_EARG, "%s: bad shape (%d,%d,%d)", who, B, H, W);
+    if (robust_kind != ISLAM_ROBUST_NONE && robust_kind != ISLAM_ROBUST_HUBER && robust_kind != ISLAM_ROBUST_CAUCHY)
+        return fail(ISLAM_EARG, "%s: unknown robust kind %d", who, robust_kind);
+    if (!(robust_delta > 0.0)) return fail(ISLAM_EARG, "%s: robust delta must be positive (got %g)", who, robust_delta);
+    if (!depth || !flow || !motion || !intr4 || !w || !grad_depth || !grad_flow)
+        return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / w / grad_depth / grad_flow pointer", who);
+    hipLaunchKernelGGL(reproj_vjp_kernel, dim3(NBLK, B), dim3(256), 0, as_stream(stream), depth, flow, mask, motion, rgb2imu, intr4, w,
+                       status_or_null, grad_depth, grad_flow, H, W, robust_kind, robust_delta);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+extern "C" int islam_dense_reproj_ift_weights(const double* H, const double* motion, const double* grad_motion,
+                                              const int* status_in_or_null, int B, double* w, int* status_out, void* stream) {
+    const char* who = "islam_dense_reproj_ift_weights";
+    if (B < 1) return fail(ISLAM_EARG, "%s: bad shape (%d)", who, B);
+    if (!H || !motion || !grad_motion || !w || !status_out)
+        return fail(ISLAM_EARG, "%s: NULL H / motion / grad_motion / w / status_out pointer", who);
+    hipLaunchKernelGGL(reproj_ift_kernel, dim3(B), dim3(64), 0, as_stream(stream), H, motion, grad_motion, status_in_or_null, w, status_out);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

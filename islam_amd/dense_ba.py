@@ -7,7 +7,8 @@
   * DenseReprojectionLoss (dense_ba.py:179-273): the per-frame mean L1 reprojection error over the masked pixels.  The
     reference cannot feed it to run_pvgo (it has no ``.N``, pvgo.py:131), so ``__call__`` is evaluation-only here as well;
     ``normal_equations`` / ``refine`` / ``information`` differentiate the same residual on the GPU (csrc/dense_reproj.hip,
-    DESIGN.md section 3.23) and give run_pvgo its VO information (PvgoInfo.from_dense_reproj);
+    DESIGN.md section 3.23) and give run_pvgo its VO information (PvgoInfo.from_dense_reproj); ``refine(differentiable=True)``
+    lets a loss on the refined pose reach the stored depth and flow (section 3.24);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -172,10 +173,24 @@ class DenseReprojectionLoss:
         return ops.dense_reproj_normal(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64),
                                        rgb2imu=self.rgb2imu_pose, kernel=kernel)
 
-    def refine(self, motion, iters=10, kernel=None, damping=1e-4, min_count=16, trace_cap=0):
+    def refine(self, motion, iters=10, kernel=None, damping=1e-4, min_count=16, trace_cap=0, differentiable=False):
         """``iters`` device-side Levenberg-Marquardt evaluations per link from ``motion`` (ops.dense_reproj_refine); the result's
-        ``motion`` is the refined (B,7) and ``status`` marks the links that could not be refined."""
+        ``motion`` is the refined (B,7) and ``status`` marks the links that could not be refined.
+
+        differentiable=True: the returned ``motion`` carries a grad_fn over the stored depth and flow (the tensors given to the
+        constructor keep their graph), so a loss on the refined pose reaches the networks that made them.  The gradient is the
+        implicit-function one at the optimum, not an unrolled LM: with v the loss's gradient in the right tangent of the refined pose
+        and H the undamped matrix returned here, it is d(w^T g)/d(depth, flow) at w = -H^-1 v (ops.dense_reproj_ift_weights and
+        ops.dense_reproj_vjp, two launches, nothing read back).  Taking H for dg/dxi is the Gauss-Newton
+        approximation: exact where the residual vanishes, off by terms proportional to the residual elsewhere; it also assumes the
+        refinement has converged (g = 0).  The start ``motion`` gets no gradient (the optimum does not depend on it); a link whose
+        status is set, or whose H is not positive definite, gets a zero gradient."""
         from . import ops
+        if differentiable:
+            mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
+            return ops.DenseReprojRefined(*ops._DenseReprojRefine.apply(
+                self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), mount, kernel, iters,
+                damping, min_count, trace_cap))
         return ops.dense_reproj_refine(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64),
                                        rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
                                        trace_cap=trace_cap)

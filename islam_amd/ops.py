@@ -232,6 +232,88 @@ def dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=None, kernel=No
     return DenseReprojRefined(pose, *out, lam, acc, rej, status, trace)
 
 
+def _dense_reproj_status(status, B, dev):
+    if status is None:
+        return None
+    status = torch.as_tensor(status).to(dev, torch.int32).contiguous()
+    if tuple(status.shape) != (B,):
+        raise ValueError('dense_reproj: status must be (%d), got %s' % (B, tuple(status.shape)))
+    return status
+
+
+def dense_reproj_vjp(depth, flow, mask, motion, intr, w, rgb2imu=None, kernel=None, status=None):
+    """The derivative of w^T g in depth and flow, g as dense_reproj_normal returns it at ``motion``, with the pose and the valid set
+    held fixed (include/islam_hip.h, islam_dense_reproj_vjp).  Arguments as dense_reproj_normal; w (B,6)
+    body frame [rho, phi]; status (B) int or None: a link whose status is not 0 gets zeros.  Returns (grad_depth (B,H,W),
+    grad_flow (B,2,H,W)), float32 on the device, exactly 0 at every invalid pixel; one launch, nothing is read back."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = torch.as_tensor(w).detach().to(dev, torch.float64).contiguous()
+    if tuple(w.shape) != (B, 6):
+        raise ValueError('dense_reproj_vjp: w must be (%d,6) [rho, phi], got %s' % (B, tuple(w.shape)))
+    return _dense_reproj_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, kind, delta, w, _dense_reproj_status(status, B, dev))
+
+
+def _dense_reproj_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, kind, delta, w, status):
+    """islam_dense_reproj_vjp on tensors _dense_reproj_args has prepared."""
+    B, H, W = depth.shape
+    grad_depth = torch.empty((B, H, W), dtype=torch.float32, device=depth.device)
+    grad_flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=depth.device)
+    check(lib().islam_dense_reproj_vjp(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), B, H, W, kind, delta,
+                                       ptr(w), ptr(status), ptr(grad_depth), ptr(grad_flow), stream_ptr(depth.device)))
+    return grad_depth, grad_flow
+
+
+def dense_reproj_ift_weights(H, motion, grad_motion, status=None):
+    """w = -H^-1 v per link (include/islam_hip.h, islam_dense_reproj_ift_weights): H (B,6,6) the undamped matrix of a refinement,
+    motion (B,7) the pose it ended at, grad_motion (B,7) a loss's gradient on [t, q xyzw] there (v: the same gradient in the right
+    tangent of the pose), status (B) int or None the refinement's status.  Returns (w (B,6) float64, status (B) int32): a link with
+    an incoming status, or whose H is not positive definite (_lib.DENSE_REPROJ_NOTPD), has w = 0.  One launch, nothing is read back."""
+    require_cuda(H)
+    dev = H.device
+    f64 = lambda t: torch.as_tensor(t).detach().to(dev, torch.float64).contiguous()
+    H, motion, grad_motion = f64(H), f64(motion), f64(grad_motion)
+    if H.dim() != 3 or tuple(H.shape[1:]) != (6, 6):
+        raise ValueError('dense_reproj_ift_weights: H must be (B,6,6), got %s' % (tuple(H.shape),))
+    B = H.shape[0]
+    if tuple(motion.shape) != (B, 7) or tuple(grad_motion.shape) != (B, 7):
+        raise ValueError('dense_reproj_ift_weights: motion and grad_motion must be (%d,7), got %s and %s' % (
+            B, tuple(motion.shape), tuple(grad_motion.shape)))
+    return _dense_reproj_ift_launch(H, motion, grad_motion, _dense_reproj_status(status, B, dev))
+
+
+def _dense_reproj_ift_launch(H, motion, grad_motion, status):
+    """islam_dense_reproj_ift_weights on contiguous float64 device tensors."""
+    B, dev = H.shape[0], H.device
+    w = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    out = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().islam_dense_reproj_ift_weights(ptr(H), ptr(motion), ptr(grad_motion), ptr(status), B, ptr(w), ptr(out), stream_ptr(dev)))
+    return w, out
+
+
+class _DenseReprojRefine(torch.autograd.Function):
+    """dense_reproj_refine whose refined motion carries the implicit-function gradient in depth and flow:
+    backward is islam_dense_reproj_ift_weights and islam_dense_reproj_vjp at the refined pose on the tensors forward prepared, two
+    launches and nothing else.  The start pose gets no gradient: the optimum does not depend on it."""
+
+    @staticmethod
+    def forward(ctx, depth, flow, mask, motion, intr, rgb2imu, kernel, iters, damping, min_count, trace_cap):
+        dev, B, H, W, depth32, flow32, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+        out = dense_reproj_refine(depth32, flow32, mask, motion, intr, rgb2imu=rgb2imu, kernel=kernel, iters=iters, damping=damping,
+                                  min_count=min_count, trace_cap=trace_cap)
+        ctx.save_for_backward(depth32, flow32, mask, out.motion, out.H, out.status, intr, rgb2imu)
+        ctx.kind, ctx.delta, ctx.dtypes = kind, delta, (depth.dtype, flow.dtype)
+        ctx.mark_non_differentiable(*(t for t in out[1:] if t is not None))
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_motion, *unused):
+        depth, flow, mask, motion, H, status, intr, rgb2imu = ctx.saved_tensors
+        w, status = _dense_reproj_ift_launch(H, motion, grad_motion.to(torch.float64).contiguous(), status)
+        grad_depth, grad_flow = _dense_reproj_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, ctx.kind, ctx.delta, w, status)
+        return (grad_depth.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None, grad_flow.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None, None, None, None)
+
+
 # --------------------------------------------------------------------------- 3x3 convolution on the matrix cores
 def deconv_to2(x, weight, bias, out=None, coff=0):
     """nn.ConvTranspose2d(C, 2, 4, 2, 1)(x) for fp32 NCHW tensors on islam_deconv4x4s2_to2_f32 (PWC-Net's deconv / upfeat layers), written

@@ -6,6 +6,12 @@ ops.dense_reproj_normal holds both of its launches and its allocations; a refine
 events around every call, 5 warm-up calls, the median of 30.  There is no earlier version to compare against and no target.
 
     python scripts/dense_reproj_bench.py [--out profiles/dense_reproj_bench.json]
+
+--grad times the gradient of the refined pose in depth and flow instead: ops.dense_reproj_vjp alone, the
+backward (ops.dense_reproj_ift_weights and ops.dense_reproj_vjp), a 10-evaluation refinement with its backward through autograd, and
+what the gradient costs without the kernel: eager float64 torch autograd of w^T g on the same tensors.
+
+    python scripts/dense_reproj_bench.py --grad [--case 448x640] [--out profiles/dense_reproj_grad_bench.json]
 """
 import json
 import os
@@ -69,8 +75,133 @@ def run_case(H, W):
     return out
 
 
+GRAD_PIXEL_BYTES = 25          # the 13 of the forward pass and three float32 stores
+
+
+def torch_wtg(depth, flow, mask, R, t, A, intr, w):
+    """w^T g of every link in eager torch (float64, differentiable in depth and flow; the valid set is held fixed): what the gradient
+    costs without the kernel.  R (B,3,3), t (B,3): T^-1 per link; A (6,6) = Ad(C^-1)."""
+    import torch
+    B, H, W = depth.shape
+    fx, fy, cx, cy = (intr[:, k].view(B, 1, 1) for k in range(4))
+    u = torch.arange(W, dtype=torch.float64, device=depth.device).view(1, 1, W)
+    v = torch.arange(H, dtype=torch.float64, device=depth.device).view(1, H, 1)
+    P = torch.stack([depth * ((u - cx) / fx), depth * ((v - cy) / fy), depth], -1)
+    Q = (P.view(B, H * W, 3) @ R.mT + t.view(B, 1, 3)).view(B, H, W, 3)
+    Qx, Qy, Qz = Q.unbind(-1)
+    with torch.no_grad():
+        valid = mask & (Qz > 0.1)
+        valid = valid & ((Qx / Qz).abs() <= 1.0) & ((Qy / Qz).abs() <= 1.0)
+    Qz = torch.where(valid, Qz, torch.ones_like(Qz))
+    ru = fx * Qx / Qz + cx - (flow[:, 0] + u)
+    rv = fy * Qy / Qz + cy - (flow[:, 1] + v)
+    wc = w @ A.T
+    wr, wf = wc[:, :3].view(B, 1, 1, 3), wc[:, 3:].view(B, 1, 1, 3).expand(B, H, W, 3)
+    m = torch.cross(Q, wf, dim=-1) - wr
+    qu = fx / Qz * m[..., 0] - fx * Qx / Qz ** 2 * m[..., 2]
+    qv = fy / Qz * m[..., 1] - fy * Qy / Qz ** 2 * m[..., 2]
+    return torch.where(valid, qu * ru + qv * rv, torch.zeros_like(ru)).sum()
+
+
+def run_grad_case(H, W):
+    """--grad: the backward of the refined pose alone and behind a 10-evaluation refinement, beside the
+    forward pass it is expected to cost about as much as, and beside eager float64 torch autograd of w^T g on the same tensors."""
+    import numpy as np
+    import torch
+    from islam_amd import lietensor as pp
+    from islam_amd import ops, robust
+    from islam_amd.dense_ba import DenseReprojectionLoss
+    from oracle import lie
+    from tests.test_dense_reproj_cpu import MOUNT, make_scene, right_perturb
+    dev = torch.device('cuda:0')
+    sc = make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    coeff = d(np.random.default_rng(0).standard_normal((B, 7)))
+    fx, fy, cx, cy = sc['intr'][0]
+    ref = ops.dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=mount, iters=10)
+    w, status = ops.dense_reproj_ift_weights(ref.H, ref.motion, coeff, ref.status)
+    zl, fl = depth.clone().requires_grad_(), flow.clone().requires_grad_()
+    loss = DenseReprojectionLoss(zl, fl, fx, fy, cx, cy, mask, pp.SE3(mount), device=dev)
+
+    def refine_backward():
+        zl.grad = fl.grad = None
+        (loss.refine(pp.SE3(motion), iters=10, differentiable=True).motion * coeff).sum().backward()
+
+    def backward():
+        wk, st = ops.dense_reproj_ift_weights(ref.H, ref.motion, coeff, ref.status)
+        return ops.dense_reproj_vjp(depth, flow, mask, ref.motion, intr, wk, rgb2imu=mount, status=st)
+
+    # eager torch on the same tensors, float64, at the refined pose
+    pose = ref.motion.cpu().numpy()
+    Ti = np.stack([lie.se3_inv(lie.se3_mul(lie.se3_mul(lie.se3_inv(MOUNT), p), MOUNT)) for p in pose])
+    R, t = d(np.stack([lie.quat_matrix(x[3:]) for x in Ti])), d(Ti[:, :3])
+    A = d(lie.se3_adj(lie.se3_inv(MOUNT)))
+    z64, f64 = depth.double().requires_grad_(), flow.double().requires_grad_()
+
+    def torch_autograd():
+        return torch.autograd.grad(torch_wtg(z64, f64, mask, R, t, A, intr, w), (z64, f64))
+
+    fns = {'normal': lambda: ops.dense_reproj_normal(depth, flow, mask, motion, intr, rgb2imu=mount),
+           'vjp': lambda: ops.dense_reproj_vjp(depth, flow, mask, ref.motion, intr, w, rgb2imu=mount, status=status),
+           'vjp_huber': lambda: ops.dense_reproj_vjp(depth, flow, mask, ref.motion, intr, w, rgb2imu=mount, kernel=robust.Huber(1.0), status=status),
+           'backward': backward, 'refine10': lambda: ops.dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=mount, iters=10),
+           'refine10_backward': refine_backward, 'torch_autograd_f64': torch_autograd}
+
+    def median(fn, n=30):
+        us = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        us.sort()
+        return 0.5 * (us[n // 2 - 1] + us[n // 2])
+
+    out = {}
+    for name, fn in fns.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = median(fn)
+    gd, gf = backward()
+    td, tf = torch_autograd()
+    out['grad_depth_vs_torch_f64'] = float((gd.double() - td).abs().max() / td.abs().max())
+    out['grad_flow_vs_torch_f64'] = float((gf.double() - tf).abs().max() / tf.abs().max())
+    out['MB_moved'] = GRAD_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_vjp'] = GRAD_PIXEL_BYTES * B * H * W / (out['vjp'] * 1e-6) / 1e9 / HBM_GBS
+    out['hbm_frac_normal'] = PIXEL_BYTES * B * H * W / (out['normal'] * 1e-6) / 1e9 / HBM_GBS
+    out['vjp_over_normal'] = out['vjp'] / out['normal']
+    out['torch_over_backward'] = out['torch_autograd_f64'] / out['backward']
+    return out
+
+
+def main_grad(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_grad_case(*hw) for case, hw in cases.items()}
+    cols = ('normal', 'vjp', 'vjp_huber', 'backward', 'refine10', 'refine10_backward', 'torch_autograd_f64', 'MB_moved', 'hbm_frac_vjp',
+            'hbm_frac_normal', 'vjp_over_normal', 'torch_over_backward', 'grad_depth_vs_torch_f64', 'grad_flow_vs_torch_f64')
+    print('us per call at B = %d: the median of 30; hbm_frac_vjp: %d bytes per pixel over the time, of %.0f GB/s' % (B, GRAD_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'dense_reproj_grad_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--grad' in sys.argv[1:]:
+        return main_grad(sys.argv[1:])
     assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
     rows = {case: run_case(*hw) for case, hw in CASES.items()}
     cols = ('normal', 'normal_huber', 'refine10', 'torch_call_f32', 'torch_call_f64', 'MB_read', 'hbm_frac_normal', 'hbm_frac_refine_eval',
