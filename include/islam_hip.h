@@ -449,6 +449,53 @@ int islam_dense_reproj_vjp(const float* depth, const float* flow, const uint8_t*
 int islam_dense_reproj_ift_weights(const double* H, const double* motion, const double* grad_motion,
                                    const int* status_in_or_null, int B, double* w, int* status_out, void* stream);
 
+/* Joint two-view dense bundle adjustment: the pose of a link AND one inverse depth per pixel, the stereo depth as a Gaussian prior,
+ * the depths eliminated pixel by pixel.  Per link b and pixel i, with the symbols above: the unknown
+ * inverse depth rho_i; the prior rho0_i = 1/depth_i, computed in float64 from the float32 map; the prior weight w_b > 0
+ * (prior_weight (B) float64), w = sigma_px^2 / sigma_rho^2, so that the sums stay in px^2.
+ *   P = (1/rho) ray,  ray = ((u - cx)/fx, (v - cy)/fy, 1),   Q = T^-1 P;   r, valid, s, c, rho_rob(s), Jq = dr/dQ, J_cam: as above
+ *   jd = Jq R ray (-1/rho^2)                                  (2-vector dr/drho; R the rotation of T^-1)
+ *   h_pd = c J_cam^T jd (6),   h_dd = c jd^T jd + w,   g_d = c jd^T r + w (rho - rho0)
+ *   S_cam = sum_valid ( c J_cam^T J_cam - h_pd h_pd^T / h_dd ),   gs_cam = sum_valid ( c J_cam^T r - h_pd g_d / h_dd )
+ *   cost  = sum_valid ( rho_rob(s) + w (rho - rho0)^2 );   l1, count: as above
+ * A pixel whose input depth is not finite or is <= 0 has no usable prior: it is outside the valid set at every state and carries
+ * rho = 0 in the state (so does, in islam_dense_ba_normal, a pixel whose given rho is not finite or is <= 0).  For a pixel that is
+ * invalid for any other reason the same formulas hold with c = 0: h_pd = 0, h_dd = w, g_d = w (rho - rho0).  The 30 camera-frame
+ * sums keep the layout above ([0..20] upper triangle of S_cam, [21..26] gs_cam, [27] cost, [28] l1, [29] count) and the final step
+ * is unchanged: S = A^T S_cam A, g = A^T gs_cam.  S / sigma_px^2 is the depth-marginalised information of the edge in the frame and
+ * row order of islam_pvgo_run_chain_info's info_vo; H - S is positive semi-definite and S -> H as w -> infinity.
+ *
+ * islam_dense_ba_normal: the sums at a given state (motion, inv_depth_or_null (B,H,W) float64; NULL: rho = rho0).  Outputs and
+ * scratch (islam_dense_ba_scratch_bytes(B, H, W, 0)) as islam_dense_reproj_normal.  A link whose prior_weight is not > 0 gets NaN in
+ * every output.
+ *
+ * islam_dense_ba_refine: the Levenberg-Marquardt of islam_dense_reproj_refine (schedule, accept rule on the mean cost, min_count,
+ * finiteness, lambda bounds, status words) on the joint problem.  Only the pose block is damped, (S + lambda diag S) delta = -gs;
+ * the depth block is not (w > 0 keeps h_dd positive, and S stays independent of lambda).  After the pose step every pixel gets
+ *   drho = -(g_d + h_pd^T delta_cam) / h_dd,  delta_cam = A delta,  evaluated at the current state;
+ * a trial rho that is not finite or is <= 0 leaves that pixel at its current rho; a pixel that is invalid at the current state goes
+ * back to rho0.  Pose and inverse depths are accepted or rejected together.  The inverse depths live in two (B,H,W) buffers of the
+ * scratch with one selector word per link; evaluation k >= 1 forms the trial rho and evaluates at it in one launch (two sweeps over
+ * a workgroup's pixels), the final kernel flips the selector on acceptance; two launches per evaluation plus one copy of the result
+ * into out_inv_depth at the end, no host wait.  out_status additionally: ISLAM_DENSE_REPROJ_BADPRIOR for a link whose prior_weight
+ * is not > 0 (a device value: no read-back); that link's pose comes back as given, its inverse depths as the prior, its sums NaN.
+ * Outputs: out_motion (B,7), out_inv_depth (B,H,W) float64 and out_S .. out_sums AT them: the same bits islam_dense_ba_normal
+ * gives at (out_motion, out_inv_depth).  scratch: islam_dense_ba_scratch_bytes(B, H, W, iters).  ISLAM_EARG before any device work
+ * for the cases of islam_dense_reproj_normal / _refine, a NULL prior_weight and a NULL out_inv_depth. */
+#define ISLAM_DENSE_REPROJ_BADPRIOR 3
+size_t islam_dense_ba_scratch_bytes(int B, int H, int W, int iters_or_0);
+int islam_dense_ba_normal(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                          const double* rgb2imu, const double* intr4, const double* prior_weight,
+                          const double* inv_depth_or_null, int robust_kind, double robust_delta, double* out_S, double* out_g,
+                          double* out_cost, double* out_l1, double* out_count, double* out_sums, void* scratch, int B, int H,
+                          int W, void* stream);
+int islam_dense_ba_refine(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                          const double* rgb2imu, const double* intr4, const double* prior_weight, int robust_kind,
+                          double robust_delta, int iters, double damping, double min_count, double* out_motion,
+                          double* out_inv_depth, double* out_S, double* out_g, double* out_cost, double* out_l1,
+                          double* out_count, double* out_sums, double* out_lambda, int* out_accepted, int* out_rejected,
+                          int* out_status, double* trace, int trace_cap, void* scratch, int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

@@ -19,6 +19,7 @@ c_void_p, c_int, c_int64, c_double, c_float, c_size_t = (ctypes.c_void_p, ctypes
 SCALE_NBLK, SCALE_NSUM = 16, 18
 DENSE_REPROJ_NBLK, DENSE_REPROJ_NSUM = 64, 30          # ISLAM_DENSE_REPROJ_NBLK / _NSUM
 DENSE_REPROJ_OK, DENSE_REPROJ_FEW, DENSE_REPROJ_NOTPD = 0, 1, 2  # ISLAM_DENSE_REPROJ_* status of a link under refinement
+DENSE_REPROJ_BADPRIOR = 3       # ... and, under the joint refinement only, a prior weight that is not > 0
 MAX_LEVELS = 6          # ISLAM_PVGO_MAX_LEVELS
 
 
@@ -115,6 +116,10 @@ SIGNATURES = {
                                   [c_int, c_void_p] + [c_int] * 3 + [c_void_p]),
     'islam_dense_reproj_vjp': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_double] + [c_void_p] * 5),
     'islam_dense_reproj_ift_weights': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
+    'islam_dense_ba_scratch_bytes': (c_size_t, [c_int] * 4),
+    'islam_dense_ba_normal': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_refine': (c_int, [c_void_p] * 7 + [c_int, c_double, c_int, c_double, c_double] + [c_void_p] * 13 +
+                              [c_int, c_void_p] + [c_int] * 3 + [c_void_p]),
     'islam_imu_scratch_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'islam_imu_preint': (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int] + [c_void_p] * 3 + [c_double, c_int] +
                          [c_void_p] * 4 + [c_int, c_void_p]),

@@ -10,29 +10,17 @@
 // link in fixed order and applies A = Ad(C^-1) once: H = A^T H_cam A, g = A^T g_cam.  No atomics anywhere: a second call gives
 // the same bits.  Under refinement the final kernel's lane 0 also runs the LM bookkeeping of its link (accept test, damping,
 // 6x6 Cholesky in LDS, next trial pose), so an evaluation is two launches and the host never waits between them.
+// The final kernel's body, the Cholesky step and the pose decode are shared with dense_ba.hip through dense_reproj_dev.h.
 // Further down: the gradient of the refined pose in depth and flow (reproj_vjp_kernel, reproj_ift_kernel).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "dense_reproj_dev.h"
 #include "lie_dev.h"
 
 using namespace islam;
 
 namespace {
-
-constexpr int NS = ISLAM_DENSE_REPROJ_NSUM;
-constexpr int NBLK = ISLAM_DENSE_REPROJ_NBLK;
-constexpr int S_G = 21, S_COST = 27, S_L1 = 28, S_COUNT = 29;
-
-// T^-1 = (C^-1 motion C)^-1; rgb2imu == nullptr: C = identity
-ISLAM_DEV SE3<double> camera_inverse(const double* pose7, const double* rgb2imu) {
-    SE3<double> T = se3_load(pose7);
-    if (rgb2imu) {
-        const SE3<double> C = se3_load(rgb2imu);
-        T = se3_mul(se3_mul(se3_inv(C), T), C);
-    }
-    return se3_inv(T);
-}
 
 __global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
                                                                     const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
@@ -108,162 +96,9 @@ __global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* 
             red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// what the final kernel writes per link; under refinement these arrays ARE the link's current state
-struct Outputs {
-    double *H, *g, *cost, *l1, *count, *sums;
-};
-
-// the LM bookkeeping of refinement (motion == nullptr: normal equations only)
-struct Refine {
-    double* motion;        // (B,7) current pose
-    double* trial;         // (B,7) next pose to evaluate
-    double* lambda;        // (B)
-    int *accepted, *rejected, *status;
-    double* trace;         // (trace_cap,B) mean cost of each evaluation, or nullptr
-    int trace_cap;
-    int eval;              // index of this evaluation
-    int last;              // no further evaluation follows
-    double min_count, lambda0;
-};
-
-// index of (i, j), i <= j, in the row-major upper triangle of a 6x6
-ISLAM_DEV int tri(int i, int j) { return i * (11 - i) / 2 + j; }
-
-// (H + lambda diag H) x = -g by Cholesky, everything in LDS (runtime-indexed: private arrays would go to scratch memory);
-// false on a non-positive (or NaN) pivot
-ISLAM_DEV bool lm_step(const double* Hn, const double* gn, double lambda, double (*L)[6], double* x) {
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j <= i; ++j) L[i][j] = Hn[i * 6 + j] + (i == j ? lambda * Hn[i * 6 + i] : 0.0);
-    for (int j = 0; j < 6; ++j) {
-        double d = L[j][j];
-        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-        if (!(d > 0.0)) return false;
-        d = sqrt(d);
-        L[j][j] = d;
-        for (int i = j + 1; i < 6; ++i) {
-            double v = L[i][j];
-            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-            L[i][j] = v / d;
-        }
-    }
-    for (int i = 0; i < 6; ++i) {
-        double v = -gn[i];
-        for (int k = 0; k < i; ++k) v -= L[i][k] * x[k];
-        x[i] = v / L[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double v = x[i];
-        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
-        x[i] = v / L[i][i];
-    }
-    return true;
-}
-
 __global__ __launch_bounds__(64) void dense_reproj_final_kernel(const double* __restrict__ partial, const double* __restrict__ rgb2imu,
                                                                  const double* __restrict__ pose_eval, Outputs out, Refine rf, int B) {
-    const int b = blockIdx.x, i = threadIdx.x;
-    __shared__ double s[NS], Rm[9], Sm[9], A[36], Hn[36], gn[6], L[6][6], x[6], cur[7];
-    __shared__ int take;
-    if (i < NS) {
-        double v = 0.0;
-        for (int k = 0; k < NBLK; ++k) v += partial[((size_t)b * NBLK + k) * NS + i];
-        s[i] = v;
-    }
-    if (i == 0) {      // C^-1 = (R, t)
-        M3<double> Rc = m3_identity<double>(), Sc{0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (rgb2imu) {
-            const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
-            Rc = qmat(Ci.q);
-            Sc = skew(Ci.t) * Rc;
-        }
-        m3_store(Rc, Rm);
-        m3_store(Sc, Sm);
-    }
-    __syncthreads();
-    if (i < 36) {      // A = Ad(C^-1) = [[R, [t]x R], [0, R]]
-        const int r = i / 6, c = i - 6 * r;
-        A[i] = r < 3 ? (c < 3 ? Rm[3 * r + c] : Sm[3 * r + c - 3]) : (c < 3 ? 0.0 : Rm[3 * (r - 3) + c - 3]);
-    }
-    __syncthreads();
-    if (i < 36) {      // H = A^T H_cam A; (r, c) and (c, r) run the same operations, so H is symmetric to the bit
-        const int r0 = i / 6, c0 = i - 6 * r0;
-        const int r = min(r0, c0), c = max(r0, c0);
-        double v = 0.0;
-        for (int k = 0; k < 6; ++k) {
-            double w = 0.0;
-            for (int l = 0; l < 6; ++l) w += s[tri(min(k, l), max(k, l))] * A[l * 6 + c];
-            v += A[k * 6 + r] * w;
-        }
-        Hn[i] = v;
-    } else if (i < 42) {
-        const int r = i - 36;
-        double v = 0.0;
-        for (int k = 0; k < 6; ++k) v += A[k * 6 + r] * s[S_G + k];
-        gn[r] = v;
-    }
-    __syncthreads();
-
-    const bool refine = rf.motion != nullptr;
-    if (refine && i == 0) {
-        bool finite = true;
-        for (int k = 0; k < NS; ++k) finite = finite && isfinite(s[k]);
-        const double n = s[S_COUNT];
-        int acc = 0;
-        if (rf.eval == 0) {        // the state at the pose as given
-            acc = 1;
-            rf.lambda[b] = rf.lambda0;
-            rf.accepted[b] = 0;
-            rf.rejected[b] = 0;
-            rf.status[b] = (finite && n >= rf.min_count) ? ISLAM_DENSE_REPROJ_OK : ISLAM_DENSE_REPROJ_FEW;
-        } else if (rf.status[b] == ISLAM_DENSE_REPROJ_OK) {
-            // the MEAN is compared: the pixel set moves with the pose, and losing pixels must not count as progress
-            acc = finite && n >= rf.min_count && s[S_COST] / n < out.cost[b] / out.count[b];
-            if (acc) {
-                rf.lambda[b] = fmax(rf.lambda[b] / 10.0, ISLAM_DENSE_REPROJ_LAMBDA_MIN);
-                rf.accepted[b] += 1;
-            } else {
-                rf.lambda[b] = fmin(rf.lambda[b] * 10.0, ISLAM_DENSE_REPROJ_LAMBDA_MAX);
-                rf.rejected[b] += 1;
-            }
-        }
-        if (rf.trace && rf.eval < rf.trace_cap) rf.trace[(size_t)rf.eval * B + b] = s[S_COST] / n;
-        take = acc;
-    }
-    if (!refine && i == 0) take = 1;
-    __syncthreads();
-    if (take) {
-        if (i < 36) out.H[(size_t)b * 36 + i] = Hn[i];
-        if (i < 6) out.g[(size_t)b * 6 + i] = gn[i];
-        if (i < NS) out.sums[(size_t)b * NS + i] = s[i];
-        if (i == 0) {
-            out.cost[b] = s[S_COST];
-            out.l1[b] = s[S_L1];
-            out.count[b] = s[S_COUNT];
-        }
-        if (refine && i < 7) {
-            cur[i] = pose_eval[(size_t)b * 7 + i];
-            rf.motion[(size_t)b * 7 + i] = cur[i];
-        }
-    } else {           // (refinement only) the step below starts from the state an earlier evaluation left
-        if (i < 36) Hn[i] = out.H[(size_t)b * 36 + i];
-        if (i < 6) gn[i] = out.g[(size_t)b * 6 + i];
-        if (i < 7) cur[i] = rf.motion[(size_t)b * 7 + i];
-    }
-    if (!refine || rf.last) return;
-    __syncthreads();
-    if (i == 0) {
-        SE3<double> X = se3_load(cur);
-        if (rf.status[b] == ISLAM_DENSE_REPROJ_OK) {
-            if (lm_step(Hn, gn, rf.lambda[b], L, x)) {
-                X = se3_mul(X, se3_exp(v3(x[0], x[1], x[2]), v3(x[3], x[4], x[5])));
-                const double qn = 1.0 / sqrt(X.q.x * X.q.x + X.q.y * X.q.y + X.q.z * X.q.z + X.q.w * X.q.w);
-                X.q = {qn * X.q.x, qn * X.q.y, qn * X.q.z, qn * X.q.w};
-            } else {
-                rf.status[b] = ISLAM_DENSE_REPROJ_NOTPD;
-            }
-        }
-        se3_store(X, rf.trial + (size_t)b * 7);      // a link whose status is set keeps being evaluated where it stands
-    }
+    final_body<false>(partial, rgb2imu, pose_eval, out, rf, Joint{}, B);
 }
 
 int check_common(const char* who, const float* depth, const float* flow, const double* motion, const double* intr4, int kind, double delta,

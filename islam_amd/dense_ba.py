@@ -8,14 +8,20 @@
     reference cannot feed it to run_pvgo (it has no ``.N``, pvgo.py:131), so ``__call__`` is evaluation-only here as well;
     ``normal_equations`` / ``refine`` / ``information`` differentiate the same residual on the GPU (csrc/dense_reproj.hip,
     DESIGN.md section 3.23) and give run_pvgo its VO information (PvgoInfo.from_dense_reproj); ``refine(differentiable=True)``
-    lets a loss on the refined pose reach the stored depth and flow (section 3.24);
+    lets a loss on the refined pose reach the stored depth and flow (section 3.24); ``refine_joint`` and
+    ``information(sigma_inv_depth=...)`` treat the stored depth as a Gaussian prior on one inverse depth per pixel and refine or
+    marginalise it with the pose (csrc/dense_ba.hip, section 3.25);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
 """
+import collections
+
 import torch
 
 from . import lietensor as pp
+
+DenseBAJoint = collections.namedtuple('DenseBAJoint', 'motion inv_depth S g cost l1 count sums damping accepted rejected status trace depth')
 
 
 def pixel2point(pixels, depth, intrinsics):
@@ -195,19 +201,78 @@ class DenseReprojectionLoss:
                                        rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
                                        trace_cap=trace_cap)
 
-    def information(self, motion, sigma_px=1.0, kernel=None):
+    @staticmethod
+    def sigma_inv_depth_from_disparity(sigma_disp, fx, baseline):
+        """The inverse-depth standard deviation of a stereo depth map whose disparity is off by ``sigma_disp`` pixels:
+        depth = fx baseline / disparity, so sigma_rho = sigma_disp / (fx baseline), uniform over the image."""
+        sigma_disp, fx, baseline = float(sigma_disp), float(fx), float(baseline)
+        if not (sigma_disp > 0.0 and fx > 0.0 and baseline > 0.0):
+            raise ValueError('sigma_inv_depth_from_disparity: sigma_disp, fx and baseline must be positive (got %r, %r, %r)' % (sigma_disp, fx, baseline))
+        return sigma_disp / (fx * baseline)
+
+    def _prior_weight(self, sigma_inv_depth, sigma_px, who):
+        """w = sigma_px^2 / sigma_inv_depth^2 per link: a number, or a (B,) tensor that is not read back when it lives on the device."""
+        sigma_px = float(sigma_px)
+        if not (sigma_px > 0.0 and sigma_px < float('inf')):
+            raise ValueError('%s: sigma_px must be a finite positive number (got %r)' % (who, sigma_px))
+        B = self.z.shape[0]
+        if torch.is_tensor(sigma_inv_depth):
+            sig = sigma_inv_depth.detach().to(torch.float64)
+            if sig.numel() != 1 and tuple(sig.shape) != (B,):
+                raise ValueError('%s: sigma_inv_depth must be a positive number or a (%d,) tensor, got shape %s' % (who, B, tuple(sig.shape)))
+            if not sig.is_cuda and not bool(((sig > 0) & torch.isfinite(sig)).all()):
+                raise ValueError('%s: sigma_inv_depth must be finite and positive (got %s)' % (who, sig.tolist()))
+            return (sigma_px / sig.reshape(-1)) ** 2
+        sig = float(sigma_inv_depth)
+        if not (sig > 0.0 and sig < float('inf')):
+            raise ValueError('%s: sigma_inv_depth must be a finite positive number (got %r)' % (who, sigma_inv_depth))
+        return (sigma_px / sig) ** 2
+
+    def refine_joint(self, motion, sigma_inv_depth, sigma_px=1.0, iters=20, kernel=None, damping=1e-4, min_count=16, trace_cap=0):
+        """Joint two-view bundle adjustment of each link: ``iters`` device-side Levenberg-Marquardt evaluations on the pose AND one
+        inverse depth per pixel, the stored depth as a Gaussian prior of standard deviation ``sigma_inv_depth`` (1/m; a positive number
+        or a (B,) tensor; sigma_inv_depth_from_disparity gives the usual stereo value) beside flow errors of ``sigma_px`` pixels
+        (ops.dense_ba_refine).  Returns DenseBAJoint: the fields of ops.DenseBARefined (motion, inv_depth, S,
+        g, cost, l1, count, sums, damping, accepted, rejected, status, trace) and ``depth``: 1 / inv_depth where that is positive,
+        the stored depth elsewhere.  No gradient is attached (refine(differentiable=True) is pose-only)."""
+        from . import ops
+        w = self._prior_weight(sigma_inv_depth, sigma_px, 'refine_joint')
+        out = ops.dense_ba_refine(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w,
+                                  rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
+                                  trace_cap=trace_cap)
+        ok = out.inv_depth > 0
+        depth = torch.where(ok, (1.0 / torch.where(ok, out.inv_depth, torch.ones_like(out.inv_depth))).to(self.z.dtype), self.z.detach())
+        return DenseBAJoint(*out, depth)
+
+    def information(self, motion, sigma_px=1.0, kernel=None, sigma_inv_depth=None):
         """H / sigma_px^2 (B,6,6) float64: the information of each link's VO residual in the frame and row order of PvgoInfo.vo, for
         flow errors of ``sigma_px`` pixels per component (PvgoInfo.from_dense_reproj).  sigma_px='residual' estimates the variance per
-        link from the fit itself, sigma^2 = cost / (2 count - 6); a link with 2 count <= 6 gives the zero matrix."""
-        ne = self.normal_equations(motion, kernel=kernel)
+        link from the fit itself, sigma^2 = cost / (2 count - 6); a link with 2 count <= 6 gives the zero matrix.
+
+        sigma_inv_depth (a positive number or a (B,) tensor; None: the depth is taken as exact, the path above): the stored depth is
+        a Gaussian prior of that standard deviation in inverse depth, and the result is S / sigma_px^2 with S the Schur complement of
+        the joint (pose, inverse depth) problem onto the pose, at the prior depths (ops.dense_ba_normal): the
+        depth-marginalised information, never larger than H / sigma_px^2.  With sigma_px='residual' the prior weight is formed with
+        sigma_px = 1 and the variance comes from the joint cost, again over 2 count - 6 degrees of freedom (the n depth unknowns are
+        matched by their n prior rows)."""
+        if sigma_inv_depth is None:
+            ne = self.normal_equations(motion, kernel=kernel)
+            Hm = ne.H
+        else:
+            from . import ops
+            residual = isinstance(sigma_px, str)
+            w = self._prior_weight(sigma_inv_depth, 1.0 if residual else sigma_px, 'information')
+            ne = ops.dense_ba_normal(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w,
+                                     rgb2imu=self.rgb2imu_pose, kernel=kernel)
+            Hm = ne.S
         if isinstance(sigma_px, str):
             if sigma_px != 'residual':
                 raise ValueError("information: sigma_px must be a positive number or 'residual' (got %r)" % (sigma_px,))
             dof = 2.0 * ne.count - 6.0
             ok = dof > 0
             var = torch.where(ok, ne.cost / torch.where(ok, dof, torch.ones_like(dof)), torch.ones_like(dof))
-            return torch.where(ok.view(-1, 1, 1), ne.H / var.view(-1, 1, 1), torch.zeros_like(ne.H))
+            return torch.where(ok.view(-1, 1, 1), Hm / var.view(-1, 1, 1), torch.zeros_like(Hm))
         sigma_px = float(sigma_px)
         if not (sigma_px > 0.0 and sigma_px < float('inf')):
             raise ValueError('information: sigma_px must be a finite positive number (got %r)' % (sigma_px,))
-        return ne.H / sigma_px ** 2
+        return Hm / sigma_px ** 2

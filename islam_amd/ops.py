@@ -232,6 +232,69 @@ def dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=None, kernel=No
     return DenseReprojRefined(pose, *out, lam, acc, rej, status, trace)
 
 
+DenseBANormal = collections.namedtuple('DenseBANormal', 'S g cost l1 count sums')
+DenseBARefined = collections.namedtuple('DenseBARefined', 'motion inv_depth S g cost l1 count sums damping accepted rejected status trace')
+
+
+def _dense_ba_prior_weight(prior_weight, B, dev):
+    """prior_weight as a (B,) float64 device tensor.  A host-side number is validated here; a device tensor is not read back (a
+    non-positive entry marks its link with _lib.DENSE_REPROJ_BADPRIOR on the device)."""
+    if not torch.is_tensor(prior_weight):
+        prior_weight = torch.as_tensor(prior_weight, dtype=torch.float64)
+    if not prior_weight.is_cuda and not bool(((prior_weight > 0) & torch.isfinite(prior_weight)).all()):
+        raise ValueError('dense_ba: prior_weight must be finite and positive (got %s)' % (prior_weight.tolist(),))
+    w = prior_weight.detach().to(dev, torch.float64)
+    if w.numel() == 1:
+        w = w.reshape(1).expand(B)
+    if tuple(w.shape) != (B,):
+        raise ValueError('dense_ba: prior_weight must be a number or (%d,), got %s' % (B, tuple(w.shape)))
+    return w.contiguous()
+
+
+def dense_ba_normal(depth, flow, mask, motion, intr, prior_weight, inv_depth=None, rgb2imu=None, kernel=None):
+    """The depth-marginalised normal equations of the joint (pose, inverse depth) dense reprojection problem per link
+    (include/islam_hip.h, islam_dense_ba_normal).  Arguments as dense_reproj_normal, plus prior_weight (a
+    positive number or (B,)) = sigma_px^2 / sigma_inv_depth^2 and inv_depth (B,H,W) float64, the state's inverse depths (None: the
+    prior 1/depth).  Returns DenseBANormal(S (B,6,6), g (B,6), cost, l1, count (B), sums (B,30)), float64 on the device; nothing is
+    read back."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, B, dev)
+    if inv_depth is not None:
+        require_cuda(inv_depth)
+        if tuple(inv_depth.shape) != (B, H, W):
+            raise ValueError('dense_ba: inv_depth must be (%d,%d,%d), got %s' % (B, H, W, tuple(inv_depth.shape)))
+        inv_depth = inv_depth.detach().to(torch.float64).contiguous()
+    out = DenseBANormal(*_dense_reproj_outputs(B, dev))
+    scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(B, H, W, 0), dtype=torch.uint8, device=dev)
+    check(lib().islam_dense_ba_normal(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), ptr(inv_depth),
+                                      kind, delta, ptr(out.S), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums),
+                                      ptr(scratch), B, H, W, stream_ptr(dev)))
+    return out
+
+
+def dense_ba_refine(depth, flow, mask, motion, intr, prior_weight, rgb2imu=None, kernel=None, iters=20, damping=1e-4, min_count=16,
+                    trace_cap=0):
+    """``iters`` Levenberg-Marquardt evaluations on the joint (pose, inverse depth) problem of each link, all on the device
+    (include/islam_hip.h, islam_dense_ba_refine).  Arguments as dense_reproj_refine plus prior_weight (see dense_ba_normal).  Returns
+    DenseBARefined: motion (B,7), inv_depth (B,H,W) float64 (0 where the depth gives no prior) and S, g, cost, l1, count, sums at
+    them, damping, accepted, rejected, status (B) int32 (0, or _lib.DENSE_REPROJ_FEW / _NOTPD / _BADPRIOR) and trace."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, B, dev)
+    iters, trace_cap = int(iters), int(trace_cap)
+    out = _dense_reproj_outputs(B, dev)
+    pose = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    rho = torch.empty((B, H, W), dtype=torch.float64, device=dev)
+    lam = torch.empty(B, dtype=torch.float64, device=dev)
+    acc, rej, status = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    trace = torch.full((trace_cap, B), float('nan'), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(B, H, W, max(iters, 1)), dtype=torch.uint8, device=dev)
+    check(lib().islam_dense_ba_refine(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), kind, delta, iters,
+                                      float(damping), float(min_count), ptr(pose), ptr(rho), ptr(out.H), ptr(out.g), ptr(out.cost),
+                                      ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc), ptr(rej), ptr(status),
+                                      ptr(trace), trace_cap, ptr(scratch), B, H, W, stream_ptr(dev)))
+    return DenseBARefined(pose, rho, *out, lam, acc, rej, status, trace)
+
+
 def _dense_reproj_status(status, B, dev):
     if status is None:
         return None

@@ -12,6 +12,11 @@ backward (ops.dense_reproj_ift_weights and ops.dense_reproj_vjp), a 10-evaluatio
 what the gradient costs without the kernel: eager float64 torch autograd of w^T g on the same tensors.
 
     python scripts/dense_reproj_bench.py --grad [--case 448x640] [--out profiles/dense_reproj_grad_bench.json]
+
+--joint times the joint (pose, inverse depth) problem instead: ops.dense_ba_normal, a 20- and a 10-evaluation
+ops.dense_ba_refine, beside the pose-only ops.dense_reproj_normal / ops.dense_reproj_refine on the same tensors.
+
+    python scripts/dense_reproj_bench.py --joint [--case 448x640] [--out profiles/dense_ba_bench.json]
 """
 import json
 import os
@@ -198,10 +203,84 @@ def main_grad(argv):
         f.write(line + '\n')
 
 
+JOINT_PIXEL_BYTES = 29          # an evaluation of the joint refinement: the 13 of the pose-only pass, 8 of rho read, 8 of trial rho written
+
+
+def run_joint_case(H, W):
+    """--joint: the depth-marginalised normal equations and the joint refinement beside the pose-only calls on
+    the same tensors (the depth map carries sigma_rho = 0.02 /m of inverse-depth noise)."""
+    import numpy as np
+    import torch
+    from islam_amd import ops
+    from tests.test_dense_ba_joint_cpu import PRIOR_W, noisy_prior
+    from tests.test_dense_reproj_cpu import MOUNT, make_scene, right_perturb
+    dev = torch.device('cuda:0')
+    sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    w = torch.full((B,), PRIOR_W, dtype=torch.float64, device=dev)
+    fns = {'normal': lambda: ops.dense_reproj_normal(depth, flow, mask, motion, intr, rgb2imu=mount),
+           'ba_normal': lambda: ops.dense_ba_normal(depth, flow, mask, motion, intr, w, rgb2imu=mount),
+           'refine10': lambda: ops.dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=mount, iters=10),
+           'refine20': lambda: ops.dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=mount, iters=20),
+           'ba_refine10': lambda: ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=10),
+           'ba_refine20': lambda: ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20)}
+
+    def median(fn, n=30):
+        us = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        us.sort()
+        return 0.5 * (us[n // 2 - 1] + us[n // 2])
+
+    out = {}
+    for name, fn in fns.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = median(fn)
+    out['ba_eval'] = (out['ba_refine20'] - out['ba_refine10']) / 10          # the slope: one evaluation without the call's fixed cost
+    out['eval'] = (out['refine20'] - out['refine10']) / 10
+    out['ba_eval_over_eval'] = out['ba_eval'] / out['eval']
+    out['MB_moved_per_eval'] = JOINT_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_ba_eval'] = JOINT_PIXEL_BYTES * B * H * W / (out['ba_eval'] * 1e-6) / 1e9 / HBM_GBS
+    r = fns['ba_refine20']()
+    out['status_ok'] = int((r.status == 0).sum())
+    out['accepted_mean'] = float(r.accepted.double().mean())
+    return out
+
+
+def main_joint(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_joint_case(*hw) for case, hw in cases.items()}
+    cols = ('normal', 'ba_normal', 'refine10', 'refine20', 'ba_refine10', 'ba_refine20', 'eval', 'ba_eval', 'ba_eval_over_eval', 'MB_moved_per_eval',
+            'hbm_frac_ba_eval', 'status_ok', 'accepted_mean')
+    print('us per call at B = %d: the median of 30; hbm_frac_ba_eval: %d bytes per pixel over the time, of %.0f GB/s' % (B, JOINT_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'dense_ba_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
     if '--grad' in sys.argv[1:]:
         return main_grad(sys.argv[1:])
+    if '--joint' in sys.argv[1:]:
+        return main_joint(sys.argv[1:])
     assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
     rows = {case: run_case(*hw) for case, hw in CASES.items()}
     cols = ('normal', 'normal_huber', 'refine10', 'torch_call_f32', 'torch_call_f64', 'MB_read', 'hbm_frac_normal', 'hbm_frac_refine_eval',
