@@ -1,6 +1,7 @@
 // Joint two-view dense bundle adjustment on gfx950: the pose of a link and one inverse depth per pixel, the stereo depth as a
 // Gaussian prior, the depths eliminated pixel by pixel (definitions: include/islam_hip.h, "dense reprojection"; DESIGN.md section
-// 3.25).  It stands beside dense_reproj.hip and shares its final-kernel body, Cholesky step and sum layout (dense_reproj_dev.h).
+// 3.25).  It stands beside dense_reproj.hip and shares its per-pixel front (reproj_pixel), reduction epilogue, final-kernel body,
+// Cholesky step, sum layout and host-side argument checks (dense_reproj_dev.h).
 //
 // Per pixel of link b at inverse depth rho, all in fp64:  P = (1/rho) ray,  Q = T^-1 P,  r, valid, s, c, J_cam as in section 3.23,
 //   jd = dr/drho = dr/dQ R ray (-1/rho^2),   h_pd = c J_cam^T jd,   h_dd = c jd.jd + w,   g_d = c jd.r + w (rho - rho0),
@@ -35,46 +36,23 @@ struct RhoState {
     int eval;
 };
 
-// everything of one pixel at (T^-1 = (R, t), rho) that the sums and the back-substitution need
-struct Pixel {
-    bool valid;
-    double ru, rv, c, rob, ju[6], jv[6], jdu, jdv;
+// everything of one pixel at (T^-1 = (R, t), rho) that the sums and the back-substitution need: the shared front at z = 1 / rho and
+// jd = dr/drho = dr/dQ R ray (-1/rho^2)
+struct BaPixel {
+    Pixel p;
+    double jdu, jdv;
 };
 
-ISLAM_DEV Pixel ba_pixel(const M3<double>& R, const V3<double>& t, double rho, double xh, double yh, double tu, double tv, bool m,
-                         double fx, double fy, double cx, double cy, int kind, double delta, double d2) {
-    Pixel p;
+ISLAM_DEV BaPixel ba_pixel(const M3<double>& R, const V3<double>& t, double rho, double xh, double yh, double tu, double tv, bool m,
+                           const Intr& in, int kind, double delta, double d2) {
+    BaPixel b;
     const double zi = 1.0 / rho;
-    const V3<double> P{zi * xh, zi * yh, zi};
-    const V3<double> Q = R * P + t;
-    p.valid = m && Q.z > 0.1;
-    const double px = Q.x / Q.z, py = Q.y / Q.z;
-    p.valid = p.valid && fabs(px) <= 1.0 && fabs(py) <= 1.0;
-    p.ru = fx * px + cx - tu;
-    p.rv = fy * py + cy - tv;
-    const double s = p.ru * p.ru + p.rv * p.rv;
-    p.rob = s;
-    p.c = 1.0;
-    if (kind == ISLAM_ROBUST_HUBER) {
-        if (s > d2) {
-            const double rs = sqrt(s);
-            p.rob = 2.0 * delta * rs - d2;
-            p.c = delta / rs;
-        }
-    } else if (kind == ISLAM_ROBUST_CAUCHY) {
-        p.rob = d2 * log1p(s / d2);
-        p.c = 1.0 / (1.0 + s / d2);
-    }
-    // dr/dQ = [[a, 0, bq], [0, cq, dq]];  rows of dr/dQ [-I, [Q]x]
-    const double iz = 1.0 / Q.z;
-    const double a = fx * iz, bq = -(a * px), cq = fy * iz, dq = -(cq * py);
-    p.ju[0] = -a; p.ju[1] = 0.0; p.ju[2] = -bq; p.ju[3] = -bq * Q.y; p.ju[4] = bq * Q.x - a * Q.z; p.ju[5] = a * Q.y;
-    p.jv[0] = 0.0; p.jv[1] = -cq; p.jv[2] = -dq; p.jv[3] = cq * Q.z - dq * Q.y; p.jv[4] = dq * Q.x; p.jv[5] = -cq * Q.x;
+    b.p = reproj_pixel(R, t, zi, xh, yh, tu, tv, m, in, kind, delta, d2);
     const V3<double> dR = R * V3<double>{xh, yh, 1.0};      // dQ/d(1/rho)
     const double k = -(zi * zi);
-    p.jdu = (a * dR.x + bq * dR.z) * k;
-    p.jdv = (cq * dR.y + dq * dR.z) * k;
-    return p;
+    b.jdu = (b.p.a * dR.x + b.p.bq * dR.z) * k;
+    b.jdv = (b.p.cq * dR.y + b.p.dq * dR.z) * k;
+    return b;
 }
 
 ISLAM_DEV void pose_to_lds(const SE3<double>& Ti, double* dst) {
@@ -91,7 +69,7 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
                                                                 int H, int W, int kind, double delta, RhoState rs) {
     const int b = blockIdx.y;
     const int HW = H * W;
-    const double fx = intr4[4 * b], fy = intr4[4 * b + 1], cx = intr4[4 * b + 2], cy = intr4[4 * b + 3];
+    const Intr in = intr_load(intr4 + 4 * b);
     const double w = prior_weight[b];
     const bool wok = w > 0.0;
     const double d2 = delta * delta;
@@ -102,15 +80,9 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
         pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp[1]);
         if (backsub) {
             pose_to_lds(camera_inverse(rs.cur_pose + 7 * b, rgb2imu), Tp[0]);
-            // delta_cam = Ad(C^-1) delta = [R_c d_rho + t_c x (R_c d_phi), R_c d_phi]
             const double* dl = rs.delta + 6 * b;
             V3<double> dr{dl[0], dl[1], dl[2]}, df{dl[3], dl[4], dl[5]};
-            if (rgb2imu) {
-                const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
-                const M3<double> Rc = qmat(Ci.q);
-                df = Rc * df;
-                dr = Rc * dr + cross(Ci.t, df);
-            }
+            adjoint_apply(rgb2imu, dr, df);      // delta_cam = Ad(C^-1) delta
             dcam[0] = dr.x; dcam[1] = dr.y; dcam[2] = dr.z; dcam[3] = df.x; dcam[4] = df.y; dcam[5] = df.z;
         }
     }
@@ -147,17 +119,17 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
             const double rho = rcur[i];
             double trial = rho0;
             if (prior && rho > 0.0) {
-                const Pixel p = ba_pixel(R, t, rho, (ud - cx) / fx, (vd - cy) / fy, (double)fup[i] + ud, (double)fvp[i] + vd,
-                                         mp ? mp[i] != 0 : true, fx, fy, cx, cy, kind, delta, d2);
-                if (p.valid) {
-                    const double eu = p.c * p.jdu, ev = p.c * p.jdv;
+                const BaPixel p = ba_pixel(R, t, rho, (ud - in.cx) / in.fx, (vd - in.cy) / in.fy, (double)fup[i] + ud, (double)fvp[i] + vd,
+                                           mp ? mp[i] != 0 : true, in, kind, delta, d2);
+                if (p.p.valid) {
+                    const double eu = p.p.c * p.jdu, ev = p.p.c * p.jdv;
                     const double hdd = eu * p.jdu + ev * p.jdv + w;
-                    const double gd = eu * p.ru + ev * p.rv + w * (rho - rho0);
+                    const double gd = eu * p.p.ru + ev * p.p.rv + w * (rho - rho0);
                     double du = 0.0, dv = 0.0;      // J_cam delta_cam
 #pragma unroll
                     for (int q = 0; q < 6; ++q) {
-                        du += p.ju[q] * dcam[q];
-                        dv += p.jv[q] * dcam[q];
+                        du += p.p.ju[q] * dcam[q];
+                        dv += p.p.jv[q] * dcam[q];
                     }
                     trial = rho - (gd + (eu * du + ev * dv)) / hdd;
                     if (!(isfinite(trial) && trial > 0.0)) trial = rho;
@@ -184,45 +156,35 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
         const double rho = rsrc ? rsrc[i] : rho0;
         if (rs.eval == 0) rnext[i] = rho0;
         if (!(prior && wok && isfinite(rho) && rho > 0.0)) continue;      // outside the valid set at every state
-        const Pixel p = ba_pixel(R, t, rho, (ud - cx) / fx, (vd - cy) / fy, (double)fup[i] + ud, (double)fvp[i] + vd,
-                                 mp ? mp[i] != 0 : true, fx, fy, cx, cy, kind, delta, d2);
-        if (!p.valid) continue;
+        const BaPixel p = ba_pixel(R, t, rho, (ud - in.cx) / in.fx, (vd - in.cy) / in.fy, (double)fup[i] + ud, (double)fvp[i] + vd,
+                                   mp ? mp[i] != 0 : true, in, kind, delta, d2);
+        if (!p.p.valid) continue;
+        const double c = p.p.c, ru = p.p.ru, rv = p.p.rv;
         // with e = c jd:  h_pd = J_cam^T e,  h_dd = e.jd + w,  g_d = e.r + w (rho - rho0).  The pixel's Schur term takes the shape of
         // section 3.23's: c J^T J - h_pd h_pd^T / h_dd = J^T M J with the 2x2 M = c I - e e^T / h_dd, and
         // c J^T r - h_pd g_d / h_dd = J^T (c r - e g_d / h_dd)
-        const double eu = p.c * p.jdu, ev = p.c * p.jdv;
+        const double eu = c * p.jdu, ev = c * p.jdv;
         const double dprior = rho - rho0;
         const double hdd = eu * p.jdu + ev * p.jdv + w;
-        const double gd = eu * p.ru + ev * p.rv + w * dprior;
+        const double gd = eu * ru + ev * rv + w * dprior;
         const double ih = 1.0 / hdd;
         const double fu = eu * ih, fv = ev * ih;
-        const double m00 = p.c - fu * eu, m01 = -(fu * ev), m11 = p.c - fv * ev;
-        const double su = p.c * p.ru - fu * gd, sv = p.c * p.rv - fv * gd;
+        const double m00 = c - fu * eu, m01 = -(fu * ev), m11 = c - fv * ev;
+        const double su = c * ru - fu * gd, sv = c * rv - fv * gd;
         int k = 0;
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            const double wu = m00 * p.ju[q] + m01 * p.jv[q], wv = m01 * p.ju[q] + m11 * p.jv[q];
+            const double wu = m00 * p.p.ju[q] + m01 * p.p.jv[q], wv = m01 * p.p.ju[q] + m11 * p.p.jv[q];
 #pragma unroll
-            for (int l = q; l < 6; ++l) acc[k++] += wu * p.ju[l] + wv * p.jv[l];
-            acc[S_G + q] += p.ju[q] * su + p.jv[q] * sv;
+            for (int l = q; l < 6; ++l) acc[k++] += wu * p.p.ju[l] + wv * p.p.jv[l];
+            acc[S_G + q] += p.p.ju[q] * su + p.p.jv[q] * sv;
         }
-        acc[S_COST] += p.rob + w * dprior * dprior;
-        acc[S_L1] += fabs(p.ru) + fabs(p.rv);
+        acc[S_COST] += p.p.rob + w * dprior * dprior;
+        acc[S_L1] += fabs(ru) + fabs(rv);
         acc[S_COUNT] += 1.0;
     }
-    __shared__ double red[4][NS];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        double x = acc[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) red[wv][i] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < NS)      // a link without a usable prior weight has no sums: NaN, which the final kernel reports
-        partial[((size_t)b * NBLK + blockIdx.x) * NS + threadIdx.x] =
-            wok ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : NAN;
+    // a link without a usable prior weight has no sums: NaN, which the final kernel reports
+    reduce_and_store_row(acc, partial + ((size_t)b * NBLK + blockIdx.x) * NS, wok);
 }
 
 __global__ __launch_bounds__(64) void dense_ba_final_kernel(const double* __restrict__ partial, const double* __restrict__ rgb2imu,
@@ -238,20 +200,6 @@ __global__ __launch_bounds__(256) void dense_ba_gather_kernel(const double* __re
     double* dst = out + (size_t)b * HW;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) dst[i] = src[i];
 }
-
-int check_common(const char* who, const float* depth, const float* flow, const double* motion, const double* intr4, const double* prior_weight,
-                 int kind, double delta, const Outputs& o, const void* scratch, int B, int H, int W) {
-    if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(ISLAM_EARG, "%s: bad shape (%d,%d,%d)", who, B, H, W);
-    if (kind != ISLAM_ROBUST_NONE && kind != ISLAM_ROBUST_HUBER && kind != ISLAM_ROBUST_CAUCHY)
-        return fail(ISLAM_EARG, "%s: unknown robust kind %d", who, kind);
-    if (!(delta > 0.0)) return fail(ISLAM_EARG, "%s: robust delta must be positive (got %g)", who, delta);
-    if (!depth || !flow || !motion || !intr4 || !o.H || !o.g || !o.cost || !o.l1 || !o.count || !o.sums || !scratch)
-        return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / output / scratch pointer", who);
-    if (!prior_weight) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
-    return ISLAM_OK;
-}
-
-size_t partial_bytes(int B) { return align_up((size_t)B * NBLK * NS * sizeof(double)); }
 
 }  // namespace
 
@@ -270,7 +218,8 @@ extern "C" int islam_dense_ba_normal(const float* depth, const float* flow, cons
                                      double* out_cost, double* out_l1, double* out_count, double* out_sums, void* scratch, int B, int H,
                                      int W, void* stream) {
     const Outputs o{out_S, out_g, out_cost, out_l1, out_count, out_sums};
-    if (int rc = check_common("islam_dense_ba_normal", depth, flow, motion, intr4, prior_weight, robust_kind, robust_delta, o, scratch, B, H, W))
+    if (int rc = check_common("islam_dense_ba_normal", depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W,
+                              prior_weight != nullptr))
         return rc;
     hipStream_t s = as_stream(stream);
     double* partial = static_cast<double*>(scratch);
@@ -292,13 +241,12 @@ extern "C" int islam_dense_ba_refine(const float* depth, const float* flow, cons
                                      int* out_status, double* trace, int trace_cap, void* scratch, int B, int H, int W, void* stream) {
     const char* who = "islam_dense_ba_refine";
     const Outputs o{out_S, out_g, out_cost, out_l1, out_count, out_sums};
-    if (int rc = check_common(who, depth, flow, motion, intr4, prior_weight, robust_kind, robust_delta, o, scratch, B, H, W)) return rc;
-    if (iters < 1) return fail(ISLAM_EARG, "%s: iters must be at least 1 (got %d)", who, iters);
-    if (!(damping >= 0.0) || !(min_count >= 0.0)) return fail(ISLAM_EARG, "%s: damping and min_count must be non-negative", who);
-    if (!out_motion || !out_lambda || !out_accepted || !out_rejected || !out_status)
-        return fail(ISLAM_EARG, "%s: NULL out_motion / out_lambda / out_accepted / out_rejected / out_status", who);
+    if (int rc = check_common(who, depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W, prior_weight != nullptr))
+        return rc;
+    Refine rf{out_motion, nullptr, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
+              min_count, damping};
+    if (int rc = check_refine(who, iters, rf, trace)) return rc;
     if (!out_inv_depth) return fail(ISLAM_EARG, "%s: NULL out_inv_depth", who);
-    if (trace_cap < 0 || (trace_cap > 0 && !trace)) return fail(ISLAM_EARG, "%s: trace_cap %d without a trace buffer", who, trace_cap);
     hipStream_t s = as_stream(stream);
     char* base = static_cast<char*>(scratch);
     double* partial = reinterpret_cast<double*>(base);
@@ -312,8 +260,7 @@ extern "C" int islam_dense_ba_refine(const float* depth, const float* flow, cons
     const size_t HW = (size_t)H * W;
     double* buf0 = reinterpret_cast<double*>(base);
     double* buf1 = reinterpret_cast<double*>(base + align_up((size_t)B * HW * sizeof(double)));
-    Refine rf{out_motion, trial, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
-              min_count, damping};
+    rf.trial = trial;
     const Joint jt{prior_weight, step, select};
     RhoState rs{nullptr, buf0, buf1, select, out_status, out_motion, step, 0};
     for (int k = 0; k < iters; ++k) {

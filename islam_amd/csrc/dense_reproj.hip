@@ -10,7 +10,8 @@
 // link in fixed order and applies A = Ad(C^-1) once: H = A^T H_cam A, g = A^T g_cam.  No atomics anywhere: a second call gives
 // the same bits.  Under refinement the final kernel's lane 0 also runs the LM bookkeeping of its link (accept test, damping,
 // 6x6 Cholesky in LDS, next trial pose), so an evaluation is two launches and the host never waits between them.
-// The final kernel's body, the Cholesky step and the pose decode are shared with dense_ba.hip through dense_reproj_dev.h.
+// Everything of a pixel ahead of the accumulators (reproj_pixel), the reduction epilogue, the final kernel's body, the Cholesky step,
+// the pose decode and the host-side argument checks are shared with dense_ba.hip through dense_reproj_dev.h.
 // Further down: the gradient of the refined pose in depth and flow (reproj_vjp_kernel, reproj_ift_kernel).
 #include <hip/hip_runtime.h>
 
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* 
                                                                     double* __restrict__ partial, int H, int W, int kind, double delta) {
     const int b = blockIdx.y;
     const int HW = H * W;
-    const double fx = intr4[4 * b], fy = intr4[4 * b + 1], cx = intr4[4 * b + 2], cy = intr4[4 * b + 3];
+    const Intr in = intr_load(intr4 + 4 * b);
     const SE3<double> Ti = camera_inverse(pose7 + 7 * b, rgb2imu);
     const M3<double> R = qmat(Ti.q);
     const V3<double> t = Ti.t;
@@ -45,55 +46,23 @@ __global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* 
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
         const int v = i / W, u = i - v * W;
         const double ud = (double)u, vd = (double)v;
-        const double z = (double)zp[i], flu = (double)fup[i], flv = (double)fvp[i];
-        const bool m = mp ? mp[i] != 0 : true;
-        const V3<double> P{z * ((ud - cx) / fx), z * ((vd - cy) / fy), z};
-        const V3<double> Q = R * P + t;
-        if (!(m && Q.z > 0.1)) continue;
-        const double px = Q.x / Q.z, py = Q.y / Q.z;
-        if (!(fabs(px) <= 1.0 && fabs(py) <= 1.0)) continue;
-        const double ru = fx * px + cx - (flu + ud), rv = fy * py + cy - (flv + vd);
-        const double s = ru * ru + rv * rv;
-        double rho = s, c = 1.0;
-        if (kind == ISLAM_ROBUST_HUBER) {
-            if (s > d2) {
-                const double rs = sqrt(s);
-                rho = 2.0 * delta * rs - d2;
-                c = delta / rs;
-            }
-        } else if (kind == ISLAM_ROBUST_CAUCHY) {
-            rho = d2 * log1p(s / d2);
-            c = 1.0 / (1.0 + s / d2);
-        }
-        // dr/dQ = [[a, 0, bq], [0, cq, dq]];  rows of dr/dQ [-I, [Q]x]
-        const double a = fx / Q.z, bq = -fx * Q.x / (Q.z * Q.z), cq = fy / Q.z, dq = -fy * Q.y / (Q.z * Q.z);
-        const double ju[6] = {-a, 0.0, -bq, -bq * Q.y, bq * Q.x - a * Q.z, a * Q.y};
-        const double jv[6] = {0.0, -cq, -dq, cq * Q.z - dq * Q.y, dq * Q.x, -cq * Q.x};
+        const Pixel px = reproj_pixel(R, t, (double)zp[i], (ud - in.cx) / in.fx, (vd - in.cy) / in.fy, (double)fup[i] + ud, (double)fvp[i] + vd,
+                                      mp ? mp[i] != 0 : true, in, kind, delta, d2);
+        if (!px.valid) continue;
+        const double *ju = px.ju, *jv = px.jv;
         int k = 0;
 #pragma unroll
         for (int p = 0; p < 6; ++p) {
-            const double wu = c * ju[p], wv = c * jv[p];
+            const double wu = px.c * ju[p], wv = px.c * jv[p];
 #pragma unroll
             for (int q = p; q < 6; ++q) acc[k++] += wu * ju[q] + wv * jv[q];
-            acc[S_G + p] += wu * ru + wv * rv;
+            acc[S_G + p] += wu * px.ru + wv * px.rv;
         }
-        acc[S_COST] += rho;
-        acc[S_L1] += fabs(ru) + fabs(rv);
+        acc[S_COST] += px.rob;
+        acc[S_L1] += fabs(px.ru) + fabs(px.rv);
         acc[S_COUNT] += 1.0;
     }
-    __shared__ double red[4][NS];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        double x = acc[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) red[wv][i] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < NS)
-        partial[((size_t)b * NBLK + blockIdx.x) * NS + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    reduce_and_store_row(acc, partial + ((size_t)b * NBLK + blockIdx.x) * NS, true);
 }
 
 __global__ __launch_bounds__(64) void dense_reproj_final_kernel(const double* __restrict__ partial, const double* __restrict__ rgb2imu,
@@ -101,23 +70,12 @@ __global__ __launch_bounds__(64) void dense_reproj_final_kernel(const double* __
     final_body<false>(partial, rgb2imu, pose_eval, out, rf, Joint{}, B);
 }
 
-int check_common(const char* who, const float* depth, const float* flow, const double* motion, const double* intr4, int kind, double delta,
-                 const Outputs& o, const void* scratch, int B, int H, int W) {
-    if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(ISLAM_EARG, "%s: bad shape (%d,%d,%d)", who, B, H, W);
-    if (kind != ISLAM_ROBUST_NONE && kind != ISLAM_ROBUST_HUBER && kind != ISLAM_ROBUST_CAUCHY)
-        return fail(ISLAM_EARG, "%s: unknown robust kind %d", who, kind);
-    if (!(delta > 0.0)) return fail(ISLAM_EARG, "%s: robust delta must be positive (got %g)", who, delta);
-    if (!depth || !flow || !motion || !intr4 || !o.H || !o.g || !o.cost || !o.l1 || !o.count || !o.sums || !scratch)
-        return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / output / scratch pointer", who);
-    return ISLAM_OK;
-}
-
 // ------------------------------------------------------------------ the gradient of the refined pose in depth and flow
 //   Phi = w^T g = sum_valid c(s) q.r with q = dr/dQ m, m = [-I, [Q]x] A w, at a fixed pose and a fixed
 // valid set.  reproj_vjp_kernel writes dPhi/dz and dPhi/dflow of every pixel: the partial kernel's pass without its reduction, 13
 // bytes read and 12 written per pixel, no LDS, no atomics.  reproj_ift_kernel makes the w for which that is the gradient of a loss
 // on the refined pose: w = -H^-1 v, v the loss's gradient in the right tangent of the pose.
-// (The two names leave "dense_reproj" to the two kernels above: tests/test_dense_reproj_cpu.py counts the kernels that carry it.)
+// (The two names leave "dense_reproj" to the two kernels above: tests/test_dense_reproj_cpu.py pins the family's kernel names.)
 __global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
                                                           const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
                                                           const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
@@ -133,19 +91,13 @@ __global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict
         for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) gzp[i] = gup[i] = gvp[i] = 0.0f;
         return;
     }
-    const double fx = intr4[4 * b], fy = intr4[4 * b + 1], cx = intr4[4 * b + 2], cy = intr4[4 * b + 3];
+    const Intr in = intr_load(intr4 + 4 * b);
     const SE3<double> Ti = camera_inverse(pose7 + 7 * b, rgb2imu);
     const M3<double> R = qmat(Ti.q);
     const V3<double> t = Ti.t;
     const double d2 = delta * delta;
-    // w_cam = Ad(C^-1) w = [R_c w_rho + t_c x (R_c w_phi), R_c w_phi]
     V3<double> wr{w6[6 * b], w6[6 * b + 1], w6[6 * b + 2]}, wf{w6[6 * b + 3], w6[6 * b + 4], w6[6 * b + 5]};
-    if (rgb2imu) {
-        const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
-        const M3<double> Rc = qmat(Ci.q);
-        wf = Rc * wf;
-        wr = Rc * wr + cross(Ci.t, wf);
-    }
+    adjoint_apply(rgb2imu, wr, wf);      // w_cam = Ad(C^-1) w
 
     const float* zp = depth + (size_t)b * HW;
     const float* fup = flow + (size_t)b * 2 * HW;
@@ -154,41 +106,18 @@ __global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
         const int v = i / W, u = i - v * W;
         const double ud = (double)u, vd = (double)v;
-        const double z = (double)zp[i], flu = (double)fup[i], flv = (double)fvp[i];
-        const bool m = mp ? mp[i] != 0 : true;
-        const double xh = (ud - cx) / fx, yh = (vd - cy) / fy;
-        const V3<double> P{z * xh, z * yh, z};
-        const V3<double> Q = R * P + t;
+        const double xh = (ud - in.cx) / in.fx, yh = (vd - in.cy) / in.fy;
+        const Pixel p = reproj_pixel(R, t, (double)zp[i], xh, yh, (double)fup[i] + ud, (double)fvp[i] + vd, mp ? mp[i] != 0 : true, in, kind,
+                                     delta, d2);
         double gz = 0.0, gu = 0.0, gv = 0.0;
-        bool valid = m && Q.z > 0.1;
-        double px = 0.0, py = 0.0;
-        if (valid) {
-            px = Q.x / Q.z;
-            py = Q.y / Q.z;
-            valid = fabs(px) <= 1.0 && fabs(py) <= 1.0;
-        }
-        if (valid) {
-            const double ru = fx * px + cx - (flu + ud), rv = fy * py + cy - (flv + vd);
-            const double s = ru * ru + rv * rv;
-            double c = 1.0, cp = 0.0;          // c = rho'(s), cp = dc/ds
-            if (kind == ISLAM_ROBUST_HUBER) {
-                if (s > d2) {
-                    const double rs = sqrt(s);
-                    c = delta / rs;
-                    cp = -delta / (2.0 * s * rs);
-                }
-            } else if (kind == ISLAM_ROBUST_CAUCHY) {
-                const double k = 1.0 + s / d2;
-                c = 1.0 / k;
-                cp = -1.0 / (d2 * k * k);
-            }
-            const double a = fx / Q.z, bq = -fx * Q.x / (Q.z * Q.z), cq = fy / Q.z, dq = -fy * Q.y / (Q.z * Q.z);
+        if (p.valid) {
+            const V3<double>& Q = p.Q;
+            const double ru = p.ru, rv = p.rv, c = p.c, cp = p.cp, a = p.a, bq = p.bq, cq = p.cq, dq = p.dq, iz = p.iz;
             const V3<double> mm = cross(Q, wf) - wr;                            // [-I, [Q]x] w_cam
             const double qu = a * mm.x + bq * mm.z, qv = cq * mm.y + dq * mm.z;  // q = dr/dQ m
             const double k2 = 2.0 * cp * (qu * ru + qv * rv);
             const double eu = c * qu + k2 * ru, ev = c * qv + k2 * rv;           // e = d(c q.r)/dr
             const V3<double> dQ = R * V3<double>{xh, yh, 1.0};                   // dQ/dz
-            const double iz = 1.0 / Q.z;
             const double da = -a * iz * dQ.z, dbq = -a * iz * dQ.x - 2.0 * bq * iz * dQ.z;      // d(dr/dQ) along dQ
             const double dcq = -cq * iz * dQ.z, ddq = -cq * iz * dQ.y - 2.0 * dq * iz * dQ.z;
             const V3<double> n = cross(dQ, wf);                                 // dm along dQ
@@ -236,7 +165,7 @@ __global__ __launch_bounds__(64) void reproj_ift_kernel(const double* __restrict
 
 extern "C" size_t islam_dense_reproj_scratch_bytes(int B, int iters_or_0) {
     if (B < 1) return 0;
-    size_t n = align_up((size_t)B * NBLK * NS * sizeof(double));
+    size_t n = partial_bytes(B);
     if (iters_or_0 > 0) n += align_up((size_t)B * 7 * sizeof(double));
     return n;
 }
@@ -266,16 +195,12 @@ extern "C" int islam_dense_reproj_refine(const float* depth, const float* flow, 
     const char* who = "islam_dense_reproj_refine";
     const Outputs o{out_H, out_g, out_cost, out_l1, out_count, out_sums};
     if (int rc = check_common(who, depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W)) return rc;
-    if (iters < 1) return fail(ISLAM_EARG, "%s: iters must be at least 1 (got %d)", who, iters);
-    if (!(damping >= 0.0) || !(min_count >= 0.0)) return fail(ISLAM_EARG, "%s: damping and min_count must be non-negative", who);
-    if (!out_motion || !out_lambda || !out_accepted || !out_rejected || !out_status)
-        return fail(ISLAM_EARG, "%s: NULL out_motion / out_lambda / out_accepted / out_rejected / out_status", who);
-    if (trace_cap < 0 || (trace_cap > 0 && !trace)) return fail(ISLAM_EARG, "%s: trace_cap %d without a trace buffer", who, trace_cap);
-    hipStream_t s = as_stream(stream);
     double* partial = static_cast<double*>(scratch);
-    double* trial = reinterpret_cast<double*>(static_cast<char*>(scratch) + align_up((size_t)B * NBLK * NS * sizeof(double)));
+    double* trial = reinterpret_cast<double*>(static_cast<char*>(scratch) + partial_bytes(B));
     Refine rf{out_motion, trial, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
               min_count, damping};
+    if (int rc = check_refine(who, iters, rf, trace)) return rc;
+    hipStream_t s = as_stream(stream);
     for (int k = 0; k < iters; ++k) {
         const double* pose = k == 0 ? motion : trial;
         rf.eval = k;
@@ -293,10 +218,7 @@ extern "C" int islam_dense_reproj_vjp(const float* depth, const float* flow, con
                                       double robust_delta, const double* w, const int* status_or_null, float* grad_depth,
                                       float* grad_flow, void* stream) {
     const char* who = "islam_dense_reproj_vjp";
-    if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(ISLAM_EARG, "%s: bad shape (%d,%d,%d)", who, B, H, W);
-    if (robust_kind != ISLAM_ROBUST_NONE && robust_kind != ISLAM_ROBUST_HUBER && robust_kind != ISLAM_ROBUST_CAUCHY)
-        return fail(ISLAM_EARG, "%s: unknown robust kind %d", who, robust_kind);
-    if (!(robust_delta > 0.0)) return fail(ISLAM_EARG, "%s: robust delta must be positive (got %g)", who, robust_delta);
+    if (int rc = check_shape_kind(who, B, H, W, robust_kind, robust_delta)) return rc;
     if (!depth || !flow || !motion || !intr4 || !w || !grad_depth || !grad_flow)
         return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / w / grad_depth / grad_flow pointer", who);
     hipLaunchKernelGGL(reproj_vjp_kernel, dim3(NBLK, B), dim3(256), 0, as_stream(stream), depth, flow, mask, motion, rgb2imu, intr4, w,

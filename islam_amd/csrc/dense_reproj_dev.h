@@ -1,8 +1,13 @@
-// What the two dense reprojection files share on the device (dense_reproj.hip: DESIGN.md sections 3.23 / 3.24; dense_ba.hip: section
-// 3.25): the camera-frame pose of a link, the 6x6 damped Cholesky step, and the body of the per-link final kernel -- the fixed-order
-// sum of the NBLK workgroup rows, A = Ad(C^-1) applied once, and under refinement the LM bookkeeping of the link on lane 0.
+// What the two dense reprojection files share (dense_reproj.hip: DESIGN.md sections 3.23 / 3.24; dense_ba.hip: section 3.25).  On the
+// device: the camera-frame pose of a link, the per-pixel front of the three pixel kernels (reproj_pixel: back-projection, T^-1, the
+// validity clauses, the residual, the robust kernel, dr/dQ and the rows of J_cam; robust_terms), Ad(C^-1) on a 6-vector, the reduction
+// epilogue of the two partial kernels, the 6x6 damped Cholesky step, and the body of the per-link final kernel -- the fixed-order
+// sum of the NBLK workgroup rows, A = Ad(C^-1) applied once, and under refinement the LM bookkeeping of the link on lane 0.  On the
+// host: the argument checks of the entry points and the size of the partial-sum scratch.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cmath>
 
 #include "common.h"
 #include "lie_dev.h"
@@ -22,6 +27,93 @@ ISLAM_DEV SE3<double> camera_inverse(const double* pose7, const double* rgb2imu)
         T = se3_mul(se3_mul(se3_inv(C), T), C);
     }
     return se3_inv(T);
+}
+
+// C^-1 applied to a body-frame 6-vector, in place: Ad(C^-1) [rho; phi] = [R_c rho + t_c x (R_c phi); R_c phi]
+ISLAM_DEV void adjoint_apply(const double* rgb2imu, V3<double>& rho3, V3<double>& phi3) {
+    if (!rgb2imu) return;
+    const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
+    const M3<double> Rc = qmat(Ci.q);
+    phi3 = Rc * phi3;
+    rho3 = Rc * rho3 + cross(Ci.t, phi3);
+}
+
+// The robust kernel at s = |r|^2: rho(s), c = rho'(s), cp = dc/ds.  The one place the Huber / Cauchy branches live; what a caller
+// does not use falls away once this is inlined.
+ISLAM_DEV void robust_terms(int kind, double delta, double d2, double s, double& rho, double& c, double& cp) {
+    rho = s;
+    c = 1.0;
+    cp = 0.0;
+    if (kind == ISLAM_ROBUST_HUBER) {
+        if (s > d2) {
+            const double rs = sqrt(s);
+            rho = 2.0 * delta * rs - d2;
+            c = delta / rs;
+            cp = -delta / (2.0 * s * rs);
+        }
+    } else if (kind == ISLAM_ROBUST_CAUCHY) {
+        const double k = 1.0 + s / d2;
+        rho = d2 * log1p(s / d2);
+        c = 1.0 / k;
+        cp = -1.0 / (d2 * k * k);
+    }
+}
+
+struct Intr {
+    double fx, fy, cx, cy;
+};
+
+ISLAM_DEV Intr intr_load(const double* intr4) { return {intr4[0], intr4[1], intr4[2], intr4[3]}; }
+
+// one pixel at T^-1 = (R, t): everything ahead of the accumulators.  dr/dQ = [[a, 0, bq], [0, cq, dq]], iz = 1 / Q_z, and ju, jv: the
+// two rows of J_cam = dr/dQ [-I, [Q]x]
+struct Pixel {
+    bool valid;
+    double ru, rv, s, rob, c, cp;
+    V3<double> Q;
+    double iz, a, bq, cq, dq, ju[6], jv[6];
+};
+
+// The per-pixel front.  z: the depth along the ray (xh, yh, 1); (tu, tv): where the flow says the pixel went; m: the user mask.
+// Straight-line: an invalid pixel carries numbers nobody may use; what a caller does not read (the rows in the gradient kernel)
+// falls away once this is inlined.
+ISLAM_DEV Pixel reproj_pixel(const M3<double>& R, const V3<double>& t, double z, double xh, double yh, double tu, double tv, bool m,
+                             const Intr& in, int kind, double delta, double d2) {
+    Pixel p;
+    const V3<double> P{z * xh, z * yh, z};
+    p.Q = R * P + t;
+    p.valid = m && p.Q.z > 0.1;
+    const double px = p.Q.x / p.Q.z, py = p.Q.y / p.Q.z;
+    p.valid = p.valid && fabs(px) <= 1.0 && fabs(py) <= 1.0;
+    p.ru = in.fx * px + in.cx - tu;
+    p.rv = in.fy * py + in.cy - tv;
+    p.s = p.ru * p.ru + p.rv * p.rv;
+    robust_terms(kind, delta, d2, p.s, p.rob, p.c, p.cp);
+    // dr/dQ in locals and the rows right here, not in a function of their own: with either the compiler contracts the sums over
+    // column 2 of J_cam (-bq, -dq) into other FMAs, and the joint kernel's last bits move
+    const V3<double>& Q = p.Q;
+    const double iz = 1.0 / Q.z;
+    const double a = in.fx * iz, bq = -(a * px), cq = in.fy * iz, dq = -(cq * py);
+    p.ju[0] = -a; p.ju[1] = 0.0; p.ju[2] = -bq; p.ju[3] = -bq * Q.y; p.ju[4] = bq * Q.x - a * Q.z; p.ju[5] = a * Q.y;
+    p.jv[0] = 0.0; p.jv[1] = -cq; p.jv[2] = -dq; p.jv[3] = cq * Q.z - dq * Q.y; p.jv[4] = dq * Q.x; p.jv[5] = -cq * Q.x;
+    p.iz = iz; p.a = a; p.bq = bq; p.cq = cq; p.dq = dq;
+    return p;
+}
+
+// The epilogue of a partial kernel (256 threads): the workgroup's sum of every accumulator, one row of NS by plain stores.
+// ok = false stores NaN, which the final kernel reports.
+ISLAM_DEV void reduce_and_store_row(const double* acc, double* __restrict__ row, bool ok) {
+    __shared__ double red[4][NS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        double x = acc[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+        if (lane == 0) red[wv][i] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) row[threadIdx.x] = ok ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : NAN;
 }
 
 // what the final kernel writes per link; under refinement these arrays ARE the link's current state
@@ -200,6 +292,37 @@ ISLAM_DEV void final_body(const double* __restrict__ partial, const double* __re
         }
         se3_store(X, rf.trial + (size_t)b * 7);      // a link whose status is set keeps being evaluated where it stands
     }
+}
+
+// ------------------------------------------------------------------ host side: the argument checks of the entry points
+inline size_t partial_bytes(int B) { return align_up((size_t)B * NBLK * NS * sizeof(double)); }
+
+inline int check_shape_kind(const char* who, int B, int H, int W, int kind, double delta) {
+    if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(ISLAM_EARG, "%s: bad shape (%d,%d,%d)", who, B, H, W);
+    if (kind != ISLAM_ROBUST_NONE && kind != ISLAM_ROBUST_HUBER && kind != ISLAM_ROBUST_CAUCHY)
+        return fail(ISLAM_EARG, "%s: unknown robust kind %d", who, kind);
+    if (!(delta > 0.0)) return fail(ISLAM_EARG, "%s: robust delta must be positive (got %g)", who, delta);
+    return ISLAM_OK;
+}
+
+// prior_ok: the joint entry points pass prior_weight != nullptr
+inline int check_common(const char* who, const float* depth, const float* flow, const double* motion, const double* intr4, int kind,
+                        double delta, const Outputs& o, const void* scratch, int B, int H, int W, bool prior_ok = true) {
+    if (int rc = check_shape_kind(who, B, H, W, kind, delta)) return rc;
+    if (!depth || !flow || !motion || !intr4 || !o.H || !o.g || !o.cost || !o.l1 || !o.count || !o.sums || !scratch)
+        return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / output / scratch pointer", who);
+    if (!prior_ok) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    return ISLAM_OK;
+}
+
+// the LM arguments of a _refine entry point, from rf as the entry point filled it; trace: the pointer as the caller gave it
+inline int check_refine(const char* who, int iters, const Refine& rf, const double* trace) {
+    if (iters < 1) return fail(ISLAM_EARG, "%s: iters must be at least 1 (got %d)", who, iters);
+    if (!(rf.lambda0 >= 0.0) || !(rf.min_count >= 0.0)) return fail(ISLAM_EARG, "%s: damping and min_count must be non-negative", who);
+    if (!rf.motion || !rf.lambda || !rf.accepted || !rf.rejected || !rf.status)
+        return fail(ISLAM_EARG, "%s: NULL out_motion / out_lambda / out_accepted / out_rejected / out_status", who);
+    if (rf.trace_cap < 0 || (rf.trace_cap > 0 && !trace)) return fail(ISLAM_EARG, "%s: trace_cap %d without a trace buffer", who, rf.trace_cap);
+    return ISLAM_OK;
 }
 
 }  // namespace

@@ -197,6 +197,16 @@ def _dense_reproj_outputs(B, dev):
     return DenseReprojNormal(e(B, 6, 6), e(B, 6), e(B), e(B), e(B), e(B, _lib.DENSE_REPROJ_NSUM))
 
 
+def _dense_lm_outputs(B, dev, trace_cap):
+    """What a refinement returns beside the normal equations: pose (B,7), lambda (B), accepted, rejected, status (B) int32 and the
+    NaN-filled trace (trace_cap,B) (None for trace_cap = 0)."""
+    pose = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    lam = torch.empty(B, dtype=torch.float64, device=dev)
+    acc, rej, status = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    trace = torch.full((trace_cap, B), float('nan'), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    return pose, lam, acc, rej, status, trace
+
+
 def dense_reproj_normal(depth, flow, mask, motion, intr, rgb2imu=None, kernel=None):
     """Gauss-Newton normal equations of the dense reprojection residual per link (include/islam_hip.h, "dense reprojection";
     DESIGN.md section 3.23).  depth (B,H,W), flow (B,2,H,W), mask (B,H,W) or None, motion (B,7) SE3 [t, q], intr (4) or (B,4) =
@@ -220,10 +230,7 @@ def dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=None, kernel=No
     dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
     iters, trace_cap = int(iters), int(trace_cap)
     out = _dense_reproj_outputs(B, dev)
-    pose = torch.empty((B, 7), dtype=torch.float64, device=dev)
-    lam = torch.empty(B, dtype=torch.float64, device=dev)
-    acc, rej, status = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
-    trace = torch.full((trace_cap, B), float('nan'), dtype=torch.float64, device=dev) if trace_cap > 0 else None
+    pose, lam, acc, rej, status, trace = _dense_lm_outputs(B, dev, trace_cap)
     scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(B, max(iters, 1)), dtype=torch.uint8, device=dev)
     check(lib().islam_dense_reproj_refine(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), kind, delta, iters,
                                           float(damping), float(min_count), ptr(pose), ptr(out.H), ptr(out.g), ptr(out.cost),
@@ -282,11 +289,8 @@ def dense_ba_refine(depth, flow, mask, motion, intr, prior_weight, rgb2imu=None,
     w = _dense_ba_prior_weight(prior_weight, B, dev)
     iters, trace_cap = int(iters), int(trace_cap)
     out = _dense_reproj_outputs(B, dev)
-    pose = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    pose, lam, acc, rej, status, trace = _dense_lm_outputs(B, dev, trace_cap)
     rho = torch.empty((B, H, W), dtype=torch.float64, device=dev)
-    lam = torch.empty(B, dtype=torch.float64, device=dev)
-    acc, rej, status = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
-    trace = torch.full((trace_cap, B), float('nan'), dtype=torch.float64, device=dev) if trace_cap > 0 else None
     scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(B, H, W, max(iters, 1)), dtype=torch.uint8, device=dev)
     check(lib().islam_dense_ba_refine(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), kind, delta, iters,
                                       float(damping), float(min_count), ptr(pose), ptr(rho), ptr(out.H), ptr(out.g), ptr(out.cost),

@@ -37,7 +37,7 @@ def run_case(H, W):
     from islam_amd import lietensor as pp
     from islam_amd import ops, robust
     from islam_amd.dense_ba import DenseReprojectionLoss
-    from tests.test_dense_reproj_cpu import MOUNT, make_scene, right_perturb
+    from tests.dense_reproj_f64 import MOUNT, make_scene, right_perturb
     dev = torch.device('cuda:0')
     # the scene of the tests at this size (a quarter-resolution pinhole camera: fx = W / 2)
     sc = make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False)
@@ -117,7 +117,7 @@ def run_grad_case(H, W):
     from islam_amd import ops, robust
     from islam_amd.dense_ba import DenseReprojectionLoss
     from oracle import lie
-    from tests.test_dense_reproj_cpu import MOUNT, make_scene, right_perturb
+    from tests.dense_reproj_f64 import MOUNT, make_scene, right_perturb
     dev = torch.device('cuda:0')
     sc = make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False)
     start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
@@ -212,8 +212,7 @@ def run_joint_case(H, W):
     import numpy as np
     import torch
     from islam_amd import ops
-    from tests.test_dense_ba_joint_cpu import PRIOR_W, noisy_prior
-    from tests.test_dense_reproj_cpu import MOUNT, make_scene, right_perturb
+    from tests.dense_reproj_f64 import MOUNT, PRIOR_W, make_scene, noisy_prior, right_perturb
     dev = torch.device('cuda:0')
     sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
     start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])

@@ -1,11 +1,9 @@
 """Joint (pose, inverse depth) dense bundle adjustment (include/islam_hip.h, islam_dense_ba_normal / _refine):
-the float64 numpy restatement of the per-pixel Schur sums and of the joint Levenberg-Marquardt, the planted scenes the GPU tests
-share, and everything that can be checked without a GPU -- the Schur complement against the explicitly assembled dense system, the
-full gradient against central differences, the two limits (H - S >= 0, S -> H), the planted refinement, the host-side argument
-errors and the new kernels' register metadata."""
-import functools
+everything about the float64 numpy restatement of the per-pixel Schur sums and of the joint Levenberg-Marquardt (ba_reference_link and
+ba_refine_reference_link in tests/dense_reproj_f64.py) that can be checked without a GPU -- the Schur complement against the explicitly
+assembled dense system, the full gradient against central differences, the two limits (H - S >= 0, S -> H), the planted refinement --
+and the host-side argument errors.  (The kernels' register metadata: tests/test_dense_reproj_cpu.py.)"""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -13,227 +11,8 @@ import torch
 
 from islam_amd import robust
 from oracle import lie
-from tests.test_dense_reproj_cpu import (FEW, LAMBDA_MAX, LAMBDA_MIN, MOUNT, NOTPD, NSUM, OK, S_COST, S_COUNT, S_G, S_L1, TRIU, _fsum_cols,
-                                         _seq_cols, body_from_sums, make_scene, reproj_reference_link, right_perturb)
-
-BADPRIOR = 3                  # ISLAM_DENSE_REPROJ_BADPRIOR
-U = 2.0 ** -52
-# Roundings in one term of a camera-frame sum, counted from dense_ba_partial_kernel's arithmetic.  The kernel
-# forms a pixel's term as J^T M J with the 2x2 M = c I - e e^T / h_dd, e = c jd (J^T (c r - e g_d / h_dd) on the right-hand side), so
-# it has section 3.23's 64 for everything up to c, r and J_cam and the product with J, and on top 1/rho (1), R ray (10), -1/rho^2 (2),
-# jd (8), e (2), h_dd (4), g_d with rho0 and rho - rho0 (7), 1/h_dd (1), e / h_dd (2), the entries of M or of c r - e g_d / h_dd (4
-# each), and M J in place of c J (3 more per entry): 48 more, 112, rounded up.
-K_ROUND = 128
-
-
-# ------------------------------------------------------------------------------------------------ the restatement
-def ba_reference_link(depth, flow, mask, motion, rgb2imu, intr, w, rho=None, kernel=None):
-    """One link of the joint problem at (motion, rho), pixel by pixel from the header's definitions, float64.  depth (H,W), flow
-    (2,H,W), mask (H,W) or None, motion (7), rgb2imu (7) or None, intr (4), w > 0, rho (H,W) or None (the prior 1/depth).  Returns a
-    dict: sums (30, camera frame, each the correctly rounded sum of its terms), abs (30: per sum, the sum over the pixels of the
-    magnitudes of the term's two parts, |c J^T J| + |h_pd h_pd^T / h_dd|), fwd / bwd (the terms added in pixel order and in
-    reverse), S, g (body frame), Sabs, gabs (abs pushed through |A|), cost, l1, count, A; per pixel of the whole image (c = 0 at an
-    invalid one) hpd (H,W,6, camera frame), hdd, gd, and valid, prior (the depth gives a prior), rho0, rho; Hpp / gp: the body-frame
-    pose block sum c J^T J and sum c J^T r before the depths are eliminated; margin / rejects as reproj_reference_link."""
-    Hh, Ww = depth.shape
-    fx, fy, cx, cy = (float(x) for x in intr)
-    M = np.asarray(motion, np.float64)
-    if rgb2imu is None:
-        T, A = M, np.eye(6)
-    else:
-        C = np.asarray(rgb2imu, np.float64)
-        T = lie.se3_mul(lie.se3_mul(lie.se3_inv(C), M), C)
-        A = lie.se3_adj(lie.se3_inv(C))
-    Ti = lie.se3_inv(T)
-    R, t = lie.quat_matrix(Ti[3:]), Ti[:3]
-    v, u = np.meshgrid(np.arange(Hh, dtype=np.float64), np.arange(Ww, dtype=np.float64), indexing='ij')
-    z = np.asarray(depth, np.float64)
-    prior = np.isfinite(z) & (z > 0)
-    rho0 = np.where(prior, 1.0 / np.where(prior, z, 1.0), 0.0)
-    rho = rho0.copy() if rho is None else np.asarray(rho, np.float64)
-    usable = prior & np.isfinite(rho) & (rho > 0)
-    rs = np.where(usable, rho, 1.0)
-    zi = 1.0 / rs
-    xh, yh = (u - cx) / fx, (v - cy) / fy
-    ray = np.stack([xh, yh, np.ones_like(xh)], -1)
-    P = np.stack([zi * xh, zi * yh, zi], -1)
-    Q = P @ R.T + t
-    dR = ray @ R.T
-    user = np.ones((Hh, Ww), bool) if mask is None else np.asarray(mask) != 0
-    with np.errstate(divide='ignore', invalid='ignore'):
-        px, py = Q[..., 0] / Q[..., 2], Q[..., 1] / Q[..., 2]
-    c1 = Q[..., 2] > 0.1
-    c2 = np.abs(px) <= 1.0
-    c3 = np.abs(py) <= 1.0
-    keep = user & usable
-    valid = keep & c1 & c2 & c3
-    margin = np.stack([np.abs(Q[..., 2] - 0.1) / 0.1, np.where(c1, np.abs(1.0 - np.abs(px)), np.nan),
-                       np.where(c1, np.abs(1.0 - np.abs(py)), np.nan)], -1)[keep]
-    rejects = np.array([(keep & ~c1).sum(), (keep & c1 & ~c2).sum(), (keep & c1 & ~c3).sum()])
-    fl = np.asarray(flow, np.float64)
-    Qx, Qy = Q[..., 0], Q[..., 1]
-    Qz = np.where(valid, Q[..., 2], 1.0)
-    ru = fx * (Qx / Qz) + cx - (fl[0] + u)
-    rv = fy * (Qy / Qz) + cy - (fl[1] + v)
-    s = ru * ru + rv * rv
-    if kernel is None:
-        rob, c = s, np.ones_like(s)
-    else:
-        rob, c = kernel.rho(s), kernel.weight(s)
-    c = np.where(valid, c, 0.0)
-    a, bq, cq, dq = fx / Qz, -fx * Qx / Qz ** 2, fy / Qz, -fy * Qy / Qz ** 2
-    zero = np.zeros_like(a)
-    ju = np.stack([-a, zero, -bq, -bq * Qy, bq * Qx - a * Qz, a * Qy], -1)
-    jv = np.stack([zero, -cq, -dq, cq * Qz - dq * Qy, dq * Qx, -cq * Qx], -1)
-    k = -1.0 / (rs * rs)
-    jdu = (a * dR[..., 0] + bq * dR[..., 2]) * k
-    jdv = (cq * dR[..., 1] + dq * dR[..., 2]) * k
-    hpd = c[..., None] * (ju * jdu[..., None] + jv * jdv[..., None])
-    dprior = rho - rho0
-    hdd = c * (jdu * jdu + jdv * jdv) + w
-    gd = c * (jdu * ru + jdv * rv) + w * dprior
-
-    sel = valid
-    cs, jus, jvs, hs, hds, gds = c[sel], ju[sel], jv[sel], hpd[sel], hdd[sel], gd[sel]
-    n = int(sel.sum())
-    first = np.zeros((n, NSUM))
-    second = np.zeros((n, NSUM))
-    first[:, :21] = (cs[:, None, None] * (jus[:, :, None] * jus[:, None, :] + jvs[:, :, None] * jvs[:, None, :]))[:, TRIU[0], TRIU[1]]
-    second[:, :21] = (hs[:, :, None] * hs[:, None, :] / hds[:, None, None])[:, TRIU[0], TRIU[1]]
-    first[:, S_G:S_G + 6] = cs[:, None] * (jus * ru[sel][:, None] + jvs * rv[sel][:, None])
-    second[:, S_G:S_G + 6] = hs * (gds / hds)[:, None]
-    first[:, S_COST] = rob[sel]
-    second[:, S_COST] = -w * dprior[sel] ** 2
-    first[:, S_L1] = np.abs(ru[sel]) + np.abs(rv[sel])
-    first[:, S_COUNT] = 1.0
-    terms = first - second
-    sums, ab = _fsum_cols(terms), _fsum_cols(np.abs(first) + np.abs(second))
-    S, g = body_from_sums(sums, A)
-    Sabs, gabs = body_from_sums(ab, np.abs(A))
-    Hpp, gp = body_from_sums(_fsum_cols(first), A)
-    return dict(sums=sums, abs=ab, fwd=_seq_cols(terms), bwd=_seq_cols(terms[::-1]), S=S, g=g, Sabs=Sabs, gabs=gabs, cost=sums[S_COST],
-                l1=sums[S_L1], count=n, A=A, valid=valid, prior=prior, rho0=rho0, rho=rho, hpd=hpd, hdd=hdd, gd=gd, Hpp=Hpp, gp=gp,
-                margin=margin, rejects=rejects, c=c, ju=ju, jv=jv, jdu=jdu, jdv=jdv, ru=ru, rv=rv)
-
-
-def ba_reference(depth, flow, mask, motion, rgb2imu, intr, w, rho=None, kernel=None):
-    """ba_reference_link for every link of a batch: a list of dicts.  w: a number or (B,)."""
-    B = depth.shape[0]
-    intr = np.broadcast_to(np.asarray(intr, np.float64).reshape(-1, 4), (B, 4))
-    w = np.broadcast_to(np.asarray(w, np.float64).reshape(-1), (B,))
-    return [ba_reference_link(depth[b], flow[b], None if mask is None else mask[b], motion[b], rgb2imu, intr[b], float(w[b]),
-                              None if rho is None else rho[b], kernel) for b in range(B)]
-
-
-def ba_refine_reference_link(depth, flow, mask, motion, rgb2imu, intr, w, kernel=None, iters=20, damping=1e-4, min_count=16, order='sums'):
-    """The joint LM of islam_dense_ba_refine for one link: section 3.23's schedule and accept rule, the damping on the pose block
-    only, the device's inverse-depth update (a trial that is not finite or is <= 0 keeps the pixel's rho; a pixel invalid at the
-    current state returns to its prior; a pixel without a prior stays at 0).  ``order`` picks which of the restatement's sums drives
-    it.  Returns dict(motion, rho, status, accepted, rejected, damping, last_step (the larger of |delta| and max |delta rho| of the
-    last trial), trace, valid)."""
-    def evaluate(X, rho):
-        r = ba_reference_link(depth, flow, mask, X, rgb2imu, intr, w, rho, kernel)
-        r['Sd'], r['gsd'] = body_from_sums(r[order], r['A'])
-        r['cost_o'] = r[order][S_COST]
-        r['finite'] = bool(np.isfinite(r[order]).all())
-        return r
-
-    cur = np.asarray(motion, np.float64).copy()
-    st = evaluate(cur, None)
-    rho = st['rho0'].copy()
-    out = dict(motion=cur, rho=rho, status=OK, accepted=0, rejected=0, damping=float(damping), last_step=float('nan'),
-               trace=[st['cost_o'] / st['count'] if st['count'] else float('nan')], valid=st['valid'])
-    if not w > 0:
-        out['status'] = BADPRIOR
-        return out
-    if not (st['finite'] and st['count'] >= min_count):
-        out['status'] = FEW
-        return out
-    for _ in range(1, iters):
-        Sd = st['Sd'] + out['damping'] * np.diag(np.diag(st['Sd']))
-        try:
-            L = np.linalg.cholesky(Sd)
-        except np.linalg.LinAlgError:
-            out['status'] = NOTPD
-            break
-        delta = np.linalg.solve(L.T, np.linalg.solve(L, -st['gsd']))
-        dcam = st['A'] @ delta
-        trial_pose = right_perturb(cur, delta)
-        with np.errstate(all='ignore'):
-            stepped = rho - (st['gd'] + st['hpd'] @ dcam) / st['hdd']
-        stepped = np.where(np.isfinite(stepped) & (stepped > 0), stepped, rho)
-        trial_rho = np.where(st['valid'], stepped, st['rho0'])
-        out['last_step'] = float(max(np.linalg.norm(delta), np.abs(trial_rho - rho)[st['valid']].max()))
-        tr = evaluate(trial_pose, trial_rho)
-        out['trace'].append(tr['cost_o'] / tr['count'] if tr['count'] else float('nan'))
-        if tr['finite'] and tr['count'] >= min_count and tr['cost_o'] / tr['count'] < st['cost_o'] / st['count']:
-            cur, rho, st = trial_pose, trial_rho, tr
-            out['damping'] = max(out['damping'] / 10.0, LAMBDA_MIN)
-            out['accepted'] += 1
-        else:
-            out['damping'] = min(out['damping'] * 10.0, LAMBDA_MAX)
-            out['rejected'] += 1
-    out['motion'], out['rho'], out['valid'] = cur, rho, st['valid']
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ seeded scenes
-SIGMA_RHO = 0.02          # 1/m: the inverse-depth noise of the planted scenes
-PRIOR_W = (0.3 / SIGMA_RHO) ** 2          # w = sigma_px^2 / sigma_rho^2 at their 0.3 px of flow noise
-XI0 = np.array([0.03, -0.04, 0.03, 0.03, -0.02, 0.03]) * (0.08 / np.linalg.norm([0.03, -0.04, 0.03, 0.03, -0.02, 0.03]))
-
-
-def noisy_prior(sc, seed, sigma_rho=SIGMA_RHO):
-    """The scene of make_scene with its depth map replaced by a noisy prior: 1 / (1/depth + sigma_rho N(0,1)), float32.  The flow
-    stays the one of the true depth; ``rho_true`` keeps 1/depth of the true map."""
-    rng = np.random.default_rng(seed)
-    true = sc['depth'].astype(np.float64)
-    rho = 1.0 / true + sigma_rho * rng.standard_normal(true.shape)
-    assert (rho > 0).all()
-    return dict(sc, depth=(1.0 / rho).astype(np.float32), rho_true=1.0 / true)
-
-
-def planted_scene(H, W, seed, sigma_rho=SIGMA_RHO, noise=0.3):
-    """The planted two-view scene of DESIGN.md section 3.25: one link, identity mount, fx = fy = 0.6 W, principal point at the centre,
-    true depth uniform in [3, 8] m, a true motion of up to 0.3 m / 0.04 rad per axis, the exact flow of the true depth plus
-    ``noise`` px, and as the depth map the true inverse depth plus ``sigma_rho`` N(0,1), stored as float32 depth.  No mask."""
-    rng = np.random.default_rng(seed)
-    intr = np.array([[0.6 * W, 0.6 * W, (W - 1) / 2.0, (H - 1) / 2.0]])
-    motion = lie.se3_exp(np.concatenate([rng.uniform(-0.3, 0.3, (1, 3)), rng.uniform(-0.04, 0.04, (1, 3))], 1))
-    true = rng.uniform(3.0, 8.0, (1, H, W))
-    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
-    Ti = lie.se3_inv(motion[0])
-    P = np.stack([true[0] * ((u - intr[0, 2]) / intr[0, 0]), true[0] * ((v - intr[0, 3]) / intr[0, 1]), true[0]], -1)
-    Q = P @ lie.quat_matrix(Ti[3:]).T + Ti[:3]
-    flow = np.stack([intr[0, 0] * Q[..., 0] / Q[..., 2] + intr[0, 2] - u, intr[0, 1] * Q[..., 1] / Q[..., 2] + intr[0, 3] - v])[None]
-    flow = flow + noise * rng.standard_normal(flow.shape)
-    rho = 1.0 / true + sigma_rho * rng.standard_normal(true.shape)
-    assert (rho > 0).all()
-    return dict(depth=(1.0 / rho).astype(np.float32), flow=flow.astype(np.float32), mask=np.ones((1, H, W), bool), motion=motion, intr=intr,
-                rgb2imu=None, rho_true=1.0 / true, start=right_perturb(motion, XI0))
-
-
-PLANTED_SEED = 0
-
-
-def pose_only_reference_link(sc, iters):
-    from tests.test_dense_reproj_cpu import refine_reference_link
-    return refine_reference_link(sc['depth'][0], sc['flow'][0], sc['mask'][0], sc['start'][0], sc['rgb2imu'], sc['intr'][0], iters=iters)
-
-
-@functools.lru_cache(maxsize=None)
-def planted_case(H, W):
-    """The planted scene of a size, the restatement's joint refinement of it in the three summation orders (20 evaluations) and its
-    pose-only refinement (computed once, shared with the GPU tests)."""
-    sc = planted_scene(H, W, PLANTED_SEED)
-    w = PRIOR_W
-    run = lambda order: ba_refine_reference_link(sc['depth'][0], sc['flow'][0], sc['mask'][0], sc['start'][0], None, sc['intr'][0], w, iters=20,
-                                                 order=order)
-    return sc, w, {o: run(o) for o in ('sums', 'fwd', 'bwd')}, pose_only_reference_link(sc, 20)
-
-
-def pose_dist(a, b):
-    return float(np.linalg.norm(lie.se3_log(lie.se3_mul(lie.se3_inv(a), b))))
+from tests.dense_reproj_f64 import (BADPRIOR, K_ROUND, MOUNT, OK, PRIOR_W, U, ba_reference_link, make_scene, noisy_prior, planted_case, pose_dist,
+                                    reproj_reference_link, right_perturb)
 
 
 # ------------------------------------------------------------------------------------------------ 1. Schur against the dense system
@@ -395,7 +174,7 @@ def lib():
 def test_host_side_argument_errors(lib):
     """Arguments are refused on the host, before any device work, with a message naming the entry point."""
     from islam_amd import _lib
-    assert _lib.DENSE_REPROJ_BADPRIOR == BADPRIOR
+    assert _lib.DENSE_REPROJ_BADPRIOR == BADPRIOR == 3
     one = 1        # any non-NULL address: a refused call never reads it
     assert lib.islam_dense_ba_scratch_bytes(0, 4, 4, 0) == 0
     b0, b1 = lib.islam_dense_ba_scratch_bytes(3, 5, 7, 0), lib.islam_dense_ba_scratch_bytes(3, 5, 7, 20)
@@ -499,14 +278,3 @@ def test_information_takes_the_old_path_without_a_depth_sigma(monkeypatch):
     assert torch.equal(got, 2 * Hm / (3 * cost / (2 * count - 6)).view(-1, 1, 1))
     assert calls[0][0] == 'new' and torch.equal(calls[0][1], (1.0 / torch.tensor([0.02, 0.04], dtype=torch.float64)) ** 2)
 
-
-def test_dense_ba_kernels_do_not_spill(lib):
-    """Thirty fp64 accumulators, two poses and the per-pixel Schur terms: none of the new kernels may have a private segment or a
-    spilled VGPR."""
-    from tests.test_codeobj_cpu import LIB, READELF, _field, _kernels
-    if not (os.path.exists(LIB) and os.path.exists(READELF)):
-        pytest.skip('library or llvm-readelf missing')
-    ks = {n: blk for n, blk in _kernels().items() if 'dense_ba' in n}
-    assert len(ks) == 3 and all(any(want in n for n in ks) for want in ('dense_ba_partial_kernel', 'dense_ba_final_kernel', 'dense_ba_gather_kernel'))
-    for n, blk in ks.items():
-        assert _field(blk, 'private_segment_fixed_size') == 0 and _field(blk, 'vgpr_spill_count') == 0, n

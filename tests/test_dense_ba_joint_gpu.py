@@ -1,12 +1,12 @@
 """Joint (pose, inverse depth) dense bundle adjustment on the MI355X (csrc/dense_ba.hip) against the float64
-restatement of tests/test_dense_ba_joint_cpu.py.
+restatement of tests/dense_reproj_f64.py.
 
 Shapes, seeds and scene conditions are section 3.23's (tests/test_dense_reproj_gpu.py), asserted again on the joint restatement; the
 depth map is that scene's with sigma_rho = 0.02 /m of inverse-depth noise, and three of its pixels carry no prior (0, NaN, -1).
 
 Tolerances.  All per-pixel arithmetic is float64 on both sides.  A term of a sum is the difference of two parts, c J^T J and
 h_pd h_pd^T / h_dd, which cancel, so the yardstick is the sum of the two parts' magnitudes: |dev - ref| <= 2^-52 (K + n) sum|parts| with
-K = 128 roundings per term (counted in tests/test_dense_ba_joint_cpu.py and section 3.25) and n for any order of summation."""
+K = 128 roundings per term (counted in tests/dense_reproj_f64.py and section 3.25) and n for any order of summation."""
 import functools
 
 import numpy as np
@@ -17,12 +17,10 @@ from islam_amd import _lib, ops, robust
 from islam_amd import lietensor as pp
 from islam_amd.dense_ba import DenseReprojectionLoss
 from islam_amd.information import PvgoInfo
-from tests.test_dense_ba_joint_cpu import (BADPRIOR, K_ROUND, PRIOR_W, SIGMA_RHO, ba_reference, noisy_prior, planted_case, pose_dist)
-from tests.test_dense_reproj_cpu import FEW, MOUNT, NOTPD, OK, S_COST, S_COUNT, S_L1, make_scene, right_perturb
-from tests.test_dense_reproj_gpu import KERNELS, SEEDS, SHAPES, _dev, _dev_args
+from tests.dense_reproj_f64 import (BADPRIOR, FEW, K_ROUND, KERNELS, MOUNT, NOTPD, OK, PRIOR_W, S_COST, S_COUNT, S_L1, SEEDS, SHAPES, SIGMA_RHO, U,
+                                    _dev, _dev_args, ba_reference, make_scene, noisy_prior, planted_case, pose_dist, right_perturb)
 
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -52
 WEIGHTS = np.array([PRIOR_W, 400.0, 100.0])          # per-link prior weights
 NO_PRIOR = {(2, 5): 0.0, (3, 1): np.nan, (1, 7): -1.0}          # pixels whose depth gives no prior
 

@@ -1,8 +1,7 @@
-"""Dense reprojection normal equations (include/islam_hip.h, "dense reprojection"): the float64 numpy
-restatement of the definitions, its Levenberg-Marquardt, the seeded scenes the GPU tests share, and everything that can be checked
-without a GPU -- the convention (gradient against central differences, the quadratic form, the mount conjugation),
-PvgoInfo.from_dense_reproj, the host-side argument errors and the kernels' register metadata."""
-import math
+"""Dense reprojection normal equations (include/islam_hip.h, "dense reprojection"): everything about the
+float64 numpy restatement (tests/dense_reproj_f64.py) and the library that can be checked without a GPU -- the convention (gradient
+against central differences, the quadratic form, the mount conjugation), PvgoInfo.from_dense_reproj, the host-side argument errors
+and the register metadata of the whole dense reprojection kernel family."""
 import os
 
 import numpy as np
@@ -12,193 +11,8 @@ import torch
 from islam_amd import robust
 from islam_amd.information import PvgoInfo
 from oracle import lie
-
-NSUM, S_G, S_COST, S_L1, S_COUNT = 30, 21, 27, 28, 29
-TRIU = np.triu_indices(6)
-LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12          # ISLAM_DENSE_REPROJ_LAMBDA_MIN / _MAX
-OK, FEW, NOTPD = 0, 1, 2                      # ISLAM_DENSE_REPROJ_OK / _FEW / _NOTPD
-MOUNT = np.concatenate([[0.1, -0.05, 0.2], lie.so3_exp(np.array([0.3, -0.2, 0.4]))])
-
-
-# ------------------------------------------------------------------------------------------------ the restatement
-def _fsum_cols(t):
-    return np.array([math.fsum(t[:, k]) for k in range(t.shape[1])]) if t.shape[0] else np.zeros(t.shape[1])
-
-
-def _seq_cols(t):
-    return np.cumsum(t, axis=0)[-1] if t.shape[0] else np.zeros(t.shape[1])        # cumsum adds in index order
-
-
-def body_from_sums(sums, A):
-    """(H, g) in the body frame from the 30 camera-frame sums: H = A^T H_cam A, g = A^T g_cam."""
-    Hc = np.zeros((6, 6))
-    Hc[TRIU] = sums[:21]
-    Hc = Hc + np.triu(Hc, 1).T
-    return A.T @ Hc @ A, A.T @ sums[S_G:S_G + 6]
-
-
-def reproj_reference_link(depth, flow, mask, motion, rgb2imu, intr, kernel=None):
-    """One link, pixel by pixel from the header's definitions, float64.  depth (H,W), flow (2,H,W), mask (H,W) or None, motion (7),
-    rgb2imu (7) or None, intr (4).  Returns a dict: sums (30, camera frame, each the correctly rounded sum of its terms), abs
-    (30, sum |term|), fwd / bwd (30, the terms added in pixel order and in reverse), H, g (body frame, from sums), Habs, gabs (abs
-    pushed through |A|), cost, l1, count, A, valid (H,W) and, for every pixel the user mask keeps, the margin of each clause
-    relative to its threshold (margin, (n,3); NaN where an earlier clause already dropped the pixel) and rejects (3): how many
-    pixels each clause drops."""
-    Hh, Ww = depth.shape
-    fx, fy, cx, cy = (float(x) for x in intr)
-    M = np.asarray(motion, np.float64)
-    if rgb2imu is None:
-        T, A = M, np.eye(6)
-    else:
-        C = np.asarray(rgb2imu, np.float64)
-        T = lie.se3_mul(lie.se3_mul(lie.se3_inv(C), M), C)
-        A = lie.se3_adj(lie.se3_inv(C))
-    Ti = lie.se3_inv(T)
-    R, t = lie.quat_matrix(Ti[3:]), Ti[:3]
-    v, u = np.meshgrid(np.arange(Hh, dtype=np.float64), np.arange(Ww, dtype=np.float64), indexing='ij')
-    z = np.asarray(depth, np.float64)
-    P = np.stack([z * ((u - cx) / fx), z * ((v - cy) / fy), z], -1)
-    Q = P @ R.T + t
-    user = np.ones((Hh, Ww), bool) if mask is None else np.asarray(mask) != 0
-    with np.errstate(divide='ignore', invalid='ignore'):
-        px, py = Q[..., 0] / Q[..., 2], Q[..., 1] / Q[..., 2]
-    c1 = Q[..., 2] > 0.1
-    c2 = np.abs(px) <= 1.0
-    c3 = np.abs(py) <= 1.0
-    valid = user & c1 & c2 & c3
-    margin = np.stack([np.abs(Q[..., 2] - 0.1) / 0.1, np.where(c1, np.abs(1.0 - np.abs(px)), np.nan),
-                       np.where(c1, np.abs(1.0 - np.abs(py)), np.nan)], -1)[user]
-    rejects = np.array([(user & ~c1).sum(), (user & c1 & ~c2).sum(), (user & c1 & ~c3).sum()])
-    Qx, Qy, Qz = (Q[..., k][valid] for k in range(3))
-    uu, vv = u[valid], v[valid]
-    fl = np.asarray(flow, np.float64)
-    ru = fx * (Qx / Qz) + cx - (fl[0][valid] + uu)
-    rv = fy * (Qy / Qz) + cy - (fl[1][valid] + vv)
-    s = ru * ru + rv * rv
-    if kernel is None:
-        rho, c = s, np.ones_like(s)
-    else:
-        rho, c = kernel.rho(s), kernel.weight(s)
-    a, bq, cq, dq = fx / Qz, -fx * Qx / Qz ** 2, fy / Qz, -fy * Qy / Qz ** 2
-    zero = np.zeros_like(a)
-    ju = np.stack([-a, zero, -bq, -bq * Qy, bq * Qx - a * Qz, a * Qy], -1)          # rows of dr/dQ [-I, [Q]x]
-    jv = np.stack([zero, -cq, -dq, cq * Qz - dq * Qy, dq * Qx, -cq * Qx], -1)
-    terms = np.zeros((s.shape[0], NSUM))
-    terms[:, :21] = (c[:, None, None] * (ju[:, :, None] * ju[:, None, :] + jv[:, :, None] * jv[:, None, :]))[:, TRIU[0], TRIU[1]]
-    terms[:, S_G:S_G + 6] = c[:, None] * (ju * ru[:, None] + jv * rv[:, None])
-    terms[:, S_COST] = rho
-    terms[:, S_L1] = np.abs(ru) + np.abs(rv)
-    terms[:, S_COUNT] = 1.0
-    # sum |term|: for H and g the two products of a term are taken separately (the kernel adds them one after the other)
-    absterms = terms.copy()
-    absterms[:, :21] = (c[:, None, None] * (np.abs(ju[:, :, None] * ju[:, None, :]) + np.abs(jv[:, :, None] * jv[:, None, :])))[:, TRIU[0], TRIU[1]]
-    absterms[:, S_G:S_G + 6] = c[:, None] * (np.abs(ju * ru[:, None]) + np.abs(jv * rv[:, None]))
-    sums, ab = _fsum_cols(terms), _fsum_cols(np.abs(absterms))
-    H, g = body_from_sums(sums, A)
-    Habs, gabs = body_from_sums(ab, np.abs(A))
-    return dict(sums=sums, abs=ab, fwd=_seq_cols(terms), bwd=_seq_cols(terms[::-1]), H=H, g=g, Habs=Habs, gabs=gabs, cost=sums[S_COST],
-                l1=sums[S_L1], count=int(s.shape[0]), A=A, valid=valid, margin=margin, rejects=rejects)
-
-
-def reproj_reference(depth, flow, mask, motion, rgb2imu, intr, kernel=None):
-    """reproj_reference_link for every link of a batch: a list of dicts."""
-    B = depth.shape[0]
-    intr = np.broadcast_to(np.asarray(intr, np.float64).reshape(-1, 4), (B, 4))
-    return [reproj_reference_link(depth[b], flow[b], None if mask is None else mask[b], motion[b], rgb2imu, intr[b], kernel) for b in range(B)]
-
-
-def right_perturb(motion, xi):
-    """motion Exp(xi), quaternion normalised."""
-    X = lie.se3_mul(np.asarray(motion, np.float64), lie.se3_exp(np.asarray(xi, np.float64)))
-    X[..., 3:] /= np.linalg.norm(X[..., 3:], axis=-1, keepdims=True)
-    return X
-
-
-def refine_reference_link(depth, flow, mask, motion, rgb2imu, intr, kernel=None, iters=10, damping=1e-4, min_count=16, order='sums'):
-    """The LM of islam_dense_reproj_refine for one link, same accept rule and schedule; ``order`` picks which of the restatement's
-    sums drives it ('sums', 'fwd' or 'bwd').  Returns dict(motion, status, accepted, rejected, damping, last_step, trace)."""
-    def evaluate(X):
-        r = reproj_reference_link(depth, flow, mask, X, rgb2imu, intr, kernel)
-        H, g = body_from_sums(r[order], r['A'])
-        return dict(H=H, g=g, cost=r[order][S_COST], count=r['count'], finite=bool(np.isfinite(r[order]).all()))
-
-    cur = np.asarray(motion, np.float64).copy()
-    st = evaluate(cur)
-    out = dict(motion=cur, status=OK, accepted=0, rejected=0, damping=float(damping), last_step=float('nan'),
-               trace=[st['cost'] / st['count'] if st['count'] else float('nan')])
-    if not (st['finite'] and st['count'] >= min_count):
-        out['status'] = FEW
-        return out
-    for _ in range(1, iters):
-        Hd = st['H'] + out['damping'] * np.diag(np.diag(st['H']))
-        try:
-            L = np.linalg.cholesky(Hd)
-        except np.linalg.LinAlgError:
-            out['status'], out['motion'] = NOTPD, cur
-            return out
-        delta = np.linalg.solve(L.T, np.linalg.solve(L, -st['g']))
-        out['last_step'] = float(np.linalg.norm(delta))
-        trial = right_perturb(cur, delta)
-        tr = evaluate(trial)
-        out['trace'].append(tr['cost'] / tr['count'] if tr['count'] else float('nan'))
-        if tr['finite'] and tr['count'] >= min_count and tr['cost'] / tr['count'] < st['cost'] / st['count']:
-            cur, st = trial, tr
-            out['damping'] = max(out['damping'] / 10.0, LAMBDA_MIN)
-            out['accepted'] += 1
-        else:
-            out['damping'] = min(out['damping'] * 10.0, LAMBDA_MAX)
-            out['rejected'] += 1
-    out['motion'] = cur
-    return out
-
-
-# ------------------------------------------------------------------------------------------------ seeded scenes
-# (H, W): fx, fy, cx, cy of link 0.  fx is below half the width (the |Q_x/Q_z| <= 1 clause drops border columns), fy just below
-# cy (it drops the border rows).
-INTRINSICS = {(7, 9): (4.3, 3.2, 3.6, 2.7), (24, 40): (15.0, 11.0, 19.5, 11.5), (72, 96): (40.0, 34.0, 47.5, 35.5),
-              (136, 168): (70.0, 65.0, 83.5, 67.5)}
-
-
-def make_scene(B, H, W, seed, noise=0.0, outliers=0.0, intr0=None, low_depth=True, user_mask=True, flow_dtype=np.float32, motion=None,
-               vary=True):
-    """B links of H x W: depth in [2, 10] (float32; every 17th pixel at 0.05 when low_depth), a planted body-frame motion per link
-    (a few tenths of a metre, a few hundredths of a radian), the mount MOUNT, per-link intrinsics, a user mask with about 10 %
-    zeros, and the flow that makes the residual zero at the planted motion, plus Gaussian ``noise`` (pixels) and a fraction
-    ``outliers`` of pixels moved by up to +-20 px.  motion (B,7): planted motions to use instead of the drawn ones; vary=False:
-    one set of intrinsics for all links.  Returns a dict of numpy arrays."""
-    rng = np.random.default_rng(seed)
-    fx, fy, cx, cy = INTRINSICS[(H, W)] if intr0 is None else intr0
-    k = 1.0 if vary else 0.0          # vary: every link has its own intrinsics
-    intr = np.stack([[fx * (1 + 0.02 * k * b), fy * (1 - 0.015 * k * b), cx + 0.3 * k * b, cy - 0.2 * k * b] for b in range(B)])
-    planted = lie.se3_exp(np.concatenate([rng.uniform(-0.3, 0.3, (B, 3)), rng.uniform(-0.04, 0.04, (B, 3))], 1))
-    motion = planted if motion is None else np.asarray(motion, np.float64)
-    depth = rng.uniform(2.0, 10.0, (B, H, W)).astype(np.float32)
-    if low_depth:
-        depth.reshape(B, -1)[:, 3::17] = 0.05
-    mask = (rng.random((B, H, W)) > 0.1) if user_mask else np.ones((B, H, W), bool)
-    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
-    flow = np.zeros((B, 2, H, W))
-    for b in range(B):
-        T = lie.se3_mul(lie.se3_mul(lie.se3_inv(MOUNT), motion[b]), MOUNT)
-        Ti = lie.se3_inv(T)
-        z = depth[b].astype(np.float64)
-        P = np.stack([z * ((u - intr[b, 2]) / intr[b, 0]), z * ((v - intr[b, 3]) / intr[b, 1]), z], -1)
-        Q = P @ lie.quat_matrix(Ti[3:]).T + Ti[:3]
-        ok = Q[..., 2] > 0.05
-        Qz = np.where(ok, Q[..., 2], 1.0)
-        flow[b, 0] = np.where(ok, intr[b, 0] * Q[..., 0] / Qz + intr[b, 2] - u, 0.0)
-        flow[b, 1] = np.where(ok, intr[b, 1] * Q[..., 1] / Qz + intr[b, 3] - v, 0.0)
-    flow = np.clip(flow, -4.0 * W, 4.0 * W)
-    if noise:
-        flow += noise * rng.standard_normal(flow.shape)
-    if outliers:
-        hit = rng.random((B, 1, H, W)) < outliers
-        flow += np.where(hit, rng.uniform(-20.0, 20.0, flow.shape), 0.0)
-    return dict(depth=depth, flow=flow.astype(flow_dtype), mask=mask, motion=motion, intr=intr, rgb2imu=MOUNT.copy())
-
-
-def scene_args(sc, motion=None):
-    return (sc['depth'], sc['flow'], sc['mask'], sc['motion'] if motion is None else motion, sc['rgb2imu'], sc['intr'])
+from tests.dense_reproj_f64 import (MOUNT, OK, S_L1, make_scene, refine_reference_link, reproj_reference, reproj_reference_link, right_perturb,
+                                    scene_args)
 
 
 # ------------------------------------------------------------------------------------------------ the convention
@@ -400,12 +214,18 @@ def test_ops_refuse_cpu_tensors():
         ops.dense_reproj_refine(*args, iters=3)
 
 
-def test_dense_reproj_kernels_do_not_spill(lib):
-    """Thirty fp64 accumulators plus the pose are tight: neither kernel may have a private segment or a spilled VGPR."""
+# every kernel of the family (dense_reproj.hip, dense_ba.hip)
+FAMILY_KERNELS = ('dense_reproj_partial_kernel', 'dense_reproj_final_kernel', 'reproj_vjp_kernel', 'reproj_ift_kernel', 'dense_ba_partial_kernel',
+                  'dense_ba_final_kernel', 'dense_ba_gather_kernel')
+
+
+def test_dense_family_kernels_do_not_spill(lib):
+    """Thirty fp64 accumulators plus the pose (two poses and the per-pixel Schur terms in the joint kernel) are tight: the library holds
+    exactly the seven kernels of the family, and none of them may have a private segment or a spilled VGPR."""
     from tests.test_codeobj_cpu import LIB, READELF, _field, _kernels
     if not (os.path.exists(LIB) and os.path.exists(READELF)):
         pytest.skip('library or llvm-readelf missing')
-    ks = {n: blk for n, blk in _kernels().items() if 'dense_reproj' in n}
-    assert any('dense_reproj_partial_kernel' in n for n in ks) and any('dense_reproj_final_kernel' in n for n in ks) and len(ks) == 2
+    ks = {n: blk for n, blk in _kernels().items() if any(part in n for part in ('dense_reproj', 'dense_ba', 'reproj_vjp', 'reproj_ift'))}
+    assert len(ks) == len(FAMILY_KERNELS) and all(sum(want in n for n in ks) == 1 for want in FAMILY_KERNELS), sorted(ks)
     for n, blk in ks.items():
         assert _field(blk, 'private_segment_fixed_size') == 0 and _field(blk, 'vgpr_spill_count') == 0, n

@@ -1,5 +1,5 @@
 """Dense reprojection normal equations and pose refinement on the MI355X (csrc/dense_reproj.hip) against the
-float64 restatement of tests/test_dense_reproj_cpu.py.
+float64 restatement of tests/dense_reproj_f64.py.
 
 Shapes are chosen against the kernel's constants (256 threads, ISLAM_DENSE_REPROJ_NBLK = 64 workgroups per link): 7 x 9 is below one
 wavefront, 24 x 40 = 960 leaves most workgroups idle and is no multiple of 256, 136 x 168 = 22848 is above 64 * 256 = 16384 with a
@@ -18,25 +18,11 @@ from islam_amd import ops, robust
 from islam_amd import lietensor as pp
 from islam_amd.dense_ba import DenseReprojectionLoss
 from islam_amd.information import PvgoInfo
-from oracle import lie
-from tests.test_dense_reproj_cpu import (FEW, MOUNT, OK, S_COST, S_COUNT, S_L1, make_scene, refine_reference_link, reproj_reference,
-                                         right_perturb, scene_args)
+from tests.dense_reproj_f64 import (FEW, KERNELS, MOUNT, OK, S_COST, S_COUNT, S_L1, SEEDS, SHAPES, XI0, U, _dev, _dev_args, make_scene,
+                                    refine_reference_link, reproj_reference, right_perturb, scene_args)
+from tests.dense_reproj_f64 import pose_dist as _dist
 
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -52
-KERNELS = {'none': None, 'huber': robust.Huber(1.0), 'cauchy': robust.Cauchy(1.0)}
-SHAPES = [(1, 7, 9), (3, 24, 40), (1, 24, 40), (3, 136, 168)]
-SEEDS = {7: 107, 24: 124, 136: 201}          # seeds at which test_scene_conditions holds on every link (the 0.05 depths of a link pass or fail
-                                             # the Q_z clause together, depending on the planted translation)
-
-
-def _dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to('cuda')
-    return t if dtype is None else t.to(dtype)
-
-
-def _dev_args(sc, motion=None):
-    return (_dev(sc['depth']), _dev(sc['flow']), _dev(sc['mask']), _dev(sc['motion'] if motion is None else motion), _dev(sc['intr']))
 
 
 @functools.lru_cache(maxsize=None)
@@ -147,13 +133,6 @@ def test_cost_is_the_quadratic_form_of_the_device_H(cuda):
             quad, got, abs(got - quad), defect, defect / quad_ref))
         assert 0 < defect <= 0.05 * quad_ref
         assert abs(got - quad) <= 10 * defect
-
-
-XI0 = np.array([0.03, -0.04, 0.03, 0.03, -0.02, 0.03]) * (0.08 / np.linalg.norm([0.03, -0.04, 0.03, 0.03, -0.02, 0.03]))
-
-
-def _dist(a, b):
-    return float(np.linalg.norm(lie.se3_log(lie.se3_mul(lie.se3_inv(a), b))))
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,8 +1,8 @@
 """The gradient of the refined dense-reprojection pose in depth and flow (include/islam_hip.h, islam_dense_reproj_vjp and
-islam_dense_reproj_ift_weights): the float64 numpy restatement the GPU tests compare against, and
-everything about it that can be checked without a GPU -- the vector-Jacobian product against central differences of w^T g, the
-implicit gradient against re-refining on perturbed data, the conversion of a gradient on [t, q] to the right tangent, the
-host-side argument errors and the kernels' register metadata."""
+islam_dense_reproj_ift_weights): everything about the float64 numpy restatement the GPU tests compare against
+(vjp_reference_link in tests/dense_reproj_f64.py) that can be checked without a GPU -- the vector-Jacobian product against central
+differences of w^T g, the implicit gradient against re-refining on perturbed data, the conversion of a gradient on [t, q] to the
+right tangent -- and the host-side argument errors.  (The kernels' register metadata: tests/test_dense_reproj_cpu.py.)"""
 import os
 
 import numpy as np
@@ -11,105 +11,9 @@ import torch
 
 from islam_amd import robust
 from oracle import lie
-from tests.test_dense_reproj_cpu import make_scene, refine_reference_link, reproj_reference_link, right_perturb
+from tests.dense_reproj_f64 import make_scene, refine_reference_link, reproj_reference_link, right_perturb, tangent_from_pose_grad, vjp_reference_link
 
 EPS = np.finfo(np.float64).eps
-
-
-# ------------------------------------------------------------------------------------------------ the restatement
-def _terms(a, bq, cq, dq, Qx, Qy, Qz, iz, dQx, dQy, dQz, wr, wf, c, cp, ru, rv, neg):
-    """The header's formulas from their leaves.  neg = -1: the values.  neg = +1 on the magnitudes of the leaves: every product the
-    values are summed from, taken positive (sum |term|).  Returns (e.(Jq dQ), c r.[dJq m + Jq (dQ x w_phi)], dPhi/dflow_u, _v)."""
-    m0 = neg * wr[0] + Qy * wf[2] + neg * Qz * wf[1]          # m = -w_rho + Q x w_phi
-    m1 = neg * wr[1] + Qz * wf[0] + neg * Qx * wf[2]
-    m2 = neg * wr[2] + Qx * wf[1] + neg * Qy * wf[0]
-    qu, qv = a * m0 + bq * m2, cq * m1 + dq * m2              # q = Jq m
-    k2 = 2.0 * cp * (qu * ru + qv * rv)
-    eu, ev = c * qu + k2 * ru, c * qv + k2 * rv               # e = c q + 2 c' (q.r) r
-    da, dcq = neg * (a * iz) * dQz, neg * (cq * iz) * dQz     # the differential of a, bq, cq, dq along dQ
-    dbq = neg * (a * iz) * dQx + neg * 2.0 * (bq * iz) * dQz
-    ddq = neg * (cq * iz) * dQy + neg * 2.0 * (dq * iz) * dQz
-    n0 = dQy * wf[2] + neg * dQz * wf[1]                      # dQ x w_phi
-    n1 = dQz * wf[0] + neg * dQx * wf[2]
-    n2 = dQx * wf[1] + neg * dQy * wf[0]
-    tu = da * m0 + dbq * m2 + a * n0 + bq * n2
-    tv = dcq * m1 + ddq * m2 + cq * n1 + dq * n2
-    return eu * (a * dQx + bq * dQz) + ev * (cq * dQy + dq * dQz), c * (ru * tu + rv * tv), neg * eu, neg * ev
-
-
-def vjp_reference_link(depth, flow, mask, motion, rgb2imu, intr, w, kernel=None):
-    """d(w^T g)/d(depth, flow) of one link at a fixed pose and valid set, pixel by pixel from the header's formulas, float64; the
-    arguments of reproj_reference_link and w (6, body frame).  Returns a dict: grad_depth (H,W), grad_flow (2,H,W) (0 where
-    invalid), depth_dJ (H,W): the part of grad_depth that comes from dq/dz (the "dJ/dz term"), abs_depth, abs_flow: per element the
-    sum of |term| over the products the value is summed from (a, bq, cq, dq, Q, dQ, w_cam, c and c' are leaves; r, a difference
-    of numbers of the size of the image, enters with |fx p| + |cx| + |flow| + |u|), valid (H,W) and s (H,W; NaN where invalid)."""
-    Hh, Ww = depth.shape
-    fx, fy, cx, cy = (float(x) for x in intr)
-    M = np.asarray(motion, np.float64)
-    if rgb2imu is None:
-        T, A = M, np.eye(6)
-    else:
-        C = np.asarray(rgb2imu, np.float64)
-        T = lie.se3_mul(lie.se3_mul(lie.se3_inv(C), M), C)
-        A = lie.se3_adj(lie.se3_inv(C))
-    wc = A @ np.asarray(w, np.float64)
-    Ti = lie.se3_inv(T)
-    R, t = lie.quat_matrix(Ti[3:]), Ti[:3]
-    v, u = np.meshgrid(np.arange(Hh, dtype=np.float64), np.arange(Ww, dtype=np.float64), indexing='ij')
-    z = np.asarray(depth, np.float64)
-    ray = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1)
-    Q = (z[..., None] * ray) @ R.T + t
-    dQ = ray @ R.T
-    user = np.ones((Hh, Ww), bool) if mask is None else np.asarray(mask) != 0
-    with np.errstate(divide='ignore', invalid='ignore'):
-        px, py = Q[..., 0] / Q[..., 2], Q[..., 1] / Q[..., 2]
-    valid = user & (Q[..., 2] > 0.1) & (np.abs(px) <= 1.0) & (np.abs(py) <= 1.0)
-    Qx, Qy, Qz = (Q[..., k][valid] for k in range(3))
-    dQx, dQy, dQz = (dQ[..., k][valid] for k in range(3))
-    fl = np.asarray(flow, np.float64)
-    ru = fx * (Qx / Qz) + cx - (fl[0][valid] + u[valid])
-    rv = fy * (Qy / Qz) + cy - (fl[1][valid] + v[valid])
-    rua = np.abs(fx * (Qx / Qz)) + abs(cx) + np.abs(fl[0][valid]) + u[valid]
-    rva = np.abs(fy * (Qy / Qz)) + abs(cy) + np.abs(fl[1][valid]) + v[valid]
-    s = ru * ru + rv * rv
-    c, cp = np.ones_like(s), np.zeros_like(s)
-    if isinstance(kernel, robust.Huber):
-        d = kernel.delta
-        out = s > d * d
-        c[out] = d / np.sqrt(s[out])
-        cp[out] = -d / (2.0 * s[out] ** 1.5)
-    elif isinstance(kernel, robust.Cauchy):
-        d2 = kernel.delta ** 2
-        c = 1.0 / (1.0 + s / d2)
-        cp = -1.0 / (d2 * (1.0 + s / d2) ** 2)
-    elif kernel is not None:
-        raise ValueError(kernel)
-    a, bq, cq, dq = fx / Qz, -fx * Qx / Qz ** 2, fy / Qz, -fy * Qy / Qz ** 2
-    val = _terms(a, bq, cq, dq, Qx, Qy, Qz, 1.0 / Qz, dQx, dQy, dQz, wc[:3], wc[3:], c, cp, ru, rv, -1.0)
-    mag = _terms(*(np.abs(x) for x in (a, bq, cq, dq, Qx, Qy, Qz, 1.0 / Qz, dQx, dQy, dQz, wc[:3], wc[3:], c, cp)), rua, rva, 1.0)
-
-    def image(x):
-        full = np.zeros((Hh, Ww))
-        full[valid] = x
-        return full
-
-    smap = np.full((Hh, Ww), np.nan)
-    smap[valid] = s
-    return dict(grad_depth=image(val[0] + val[1]), grad_flow=np.stack([image(val[2]), image(val[3])]), depth_dJ=image(val[1]),
-                abs_depth=image(mag[0] + mag[1]), abs_flow=np.stack([image(mag[2]), image(mag[3])]), valid=valid, s=smap)
-
-
-def tangent_from_pose_grad(motion, grad7):
-    """v = dL/dxi on motion Exp(xi) from grad7 = dL/d[t, q xyzw]: v_rho = R^T dL/dt, v_phi = 1/2 E^T dL/dq with E = d(q (x, 1))/dx at
-    0 = [[q_w I + [q_v]x], [-q_v^T]]."""
-    motion, grad7 = np.asarray(motion, np.float64), np.asarray(grad7, np.float64)
-    qv, qw = motion[3:6], motion[6]
-    return np.concatenate([lie.quat_matrix(motion[3:]).T @ grad7[:3], 0.5 * (qw * grad7[3:6] - np.cross(qv, grad7[3:6]) - grad7[6] * qv)])
-
-
-def ift_weights_reference(H, motion, grad7):
-    """w = -H^-1 v."""
-    return -np.linalg.solve(np.asarray(H, np.float64), tangent_from_pose_grad(motion, grad7))
 
 
 # ------------------------------------------------------------------------------------------------ the VJP against central differences
@@ -330,14 +234,3 @@ def test_ops_refuse_cpu_tensors():
     with pytest.raises(RuntimeError):
         loss.refine(pp.SE3(t(sc['motion'])), iters=3, differentiable=True)
 
-
-def test_gradient_kernels_do_not_spill(lib):
-    """The two kernels of this file's subject have no private segment and no spilled VGPR (read from the library's metadata, as
-    test_dense_reproj_kernels_do_not_spill does)."""
-    from tests.test_codeobj_cpu import LIB, READELF, _field, _kernels
-    if not (os.path.exists(LIB) and os.path.exists(READELF)):
-        pytest.skip('library or llvm-readelf missing')
-    ks = {n: blk for n, blk in _kernels().items() if 'reproj_vjp_kernel' in n or 'reproj_ift_kernel' in n}
-    assert len(ks) == 2, list(ks)
-    for n, blk in ks.items():
-        assert _field(blk, 'private_segment_fixed_size') == 0 and _field(blk, 'vgpr_spill_count') == 0, n

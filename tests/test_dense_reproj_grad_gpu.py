@@ -1,5 +1,5 @@
 """The gradient of the refined dense-reprojection pose in depth and flow on the MI355X (csrc/dense_reproj.hip, reproj_vjp_kernel and
-reproj_ift_kernel) against the float64 restatement of tests/test_dense_reproj_grad_cpu.py.
+reproj_ift_kernel) against the float64 restatement of tests/dense_reproj_f64.py.
 
 Shapes as in tests/test_dense_reproj_gpu.py (the kernel is laid out like the partial kernel: 256 threads, 64 workgroups per link):
 7 x 9 is below one wavefront, 24 x 40 leaves most workgroups idle, 136 x 168 = 22848 is above one grid stride of 16384 with a ragged
@@ -17,9 +17,8 @@ import torch
 from islam_amd import lietensor as pp
 from islam_amd import ops, robust
 from islam_amd.dense_ba import DenseReprojectionLoss
-from tests.test_dense_reproj_cpu import FEW, MOUNT, NOTPD, OK, make_scene, reproj_reference, right_perturb, scene_args
-from tests.test_dense_reproj_gpu import KERNELS, SEEDS, SHAPES, _dev, _dev_args
-from tests.test_dense_reproj_grad_cpu import ift_weights_reference, vjp_reference_link
+from tests.dense_reproj_f64 import (FEW, KERNELS, MOUNT, NOTPD, OK, SEEDS, SHAPES, _dev, _dev_args, ift_weights_reference, make_scene,
+                                    reproj_reference, right_perturb, scene_args, vjp_reference_link)
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -52
