@@ -496,6 +496,49 @@ int islam_dense_ba_refine(const float* depth, const float* flow, const uint8_t* 
                           double* out_count, double* out_sums, double* out_lambda, int* out_accepted, int* out_rejected,
                           int* out_status, double* trace, int trace_cap, void* scratch, int B, int H, int W, void* stream);
 
+/* The gradient of the joint refinement with respect to depth and flow.  At the state islam_dense_ba_refine
+ * returned -- motion T* (B,7), inv_depth rho* (B,H,W) -- the joint gradient G = [g_p; g_d] vanishes (g_p = A^T sum c J_cam^T r,
+ * g_d,i as above).  For a loss L on the outputs, with v_p = dL/dxi on T* Exp(xi) (from grad_motion (B,7) = dL/d[t, q xyzw] by the
+ * conversion of islam_dense_reproj_ift_weights) and v_d,i = dL/drho*_i (grad_inv_depth_or_null (B,H,W) float64; NULL: 0), the implicit
+ * function theorem gives dL = lambda^T dG with H_full lambda = -v, H_full the Gauss-Newton matrix of the joint problem.  The depths
+ * are eliminated pixel by pixel, as in the forward pass:
+ *   u_cam = sum_valid h_pd,i v_d,i / h_dd,i                       (6 sums per link; 0 when no gradient arrives on inv_depth)
+ *   S lambda_p = -(v_p - A^T u_cam)                               (S (B,6,6): the undamped matrix islam_dense_ba_refine returns)
+ *   lambda_cam = A lambda_p
+ *   valid pixel:                 lambda_d,i = -(v_d,i + h_pd,i^T lambda_cam) / h_dd,i
+ *   invalid pixel with a prior:  lambda_d,i = -v_d,i / w          (the same formula at c = 0)
+ *   pixel without a prior (depth not finite or <= 0): no gradient
+ * and with Phi = lambda_p^T g_p + sum lambda_d,i g_d,i, the state, lambda and the valid set held fixed:
+ *   q_i = J_cam,i lambda_cam + jd_i lambda_d,i,   e_i = c q_i + 2 c' (q_i.r_i) r_i        (c' as for islam_dense_reproj_vjp)
+ *   dL/dflow_i = -e_i  (valid pixels; 0 elsewhere),   dL/ddepth_i = w lambda_d,i / depth_i^2  (every pixel with a prior)
+ * The input depth enters only through the prior rho0 = 1/depth (dg_d/drho0 = -w, drho0/dz = -1/z^2), so both derivatives of Phi are
+ * exact; a masked-out pixel gets dL/ddepth = -v_d / depth^2, the derivative of rho* = 1/depth.  H_full is the Gauss-Newton matrix:
+ * exact where r = 0 and rho = rho0, off by terms proportional to the residuals elsewhere, and the formula assumes the refinement has
+ * converged in pose and depths.  The start pose and prior_weight get no gradient.
+ *
+ * islam_dense_ba_ift_weights: lambda_p (B,6) float64.  u_cam is reduced like the sums above (NBLK rows of 6 per link by plain stores,
+ * added in fixed order: the same inputs give the same bits), a launch that is skipped when grad_inv_depth_or_null is NULL; the
+ * solve is one more.  scratch: islam_dense_ba_adjoint_scratch_bytes(B).  status_out (B): status_in_or_null's value where that is not
+ * 0, ISLAM_DENSE_REPROJ_BADPRIOR where prior_weight is not > 0, ISLAM_DENSE_REPROJ_NOTPD where the Cholesky of S meets a
+ * non-positive pivot, else 0; lambda_p is 0 for a link whose status_out is not 0.
+ *
+ * islam_dense_ba_vjp: grad_depth (B,H,W) and grad_flow (B,2,H,W), float32, written in full from lambda_p and grad_inv_depth_or_null:
+ * exactly 0 where the formulas give 0 and over a whole link whose status_or_null (B; NULL: all 0) is not 0 or whose prior_weight is
+ * not > 0.  All arithmetic is float64, rounded once at the store; one launch, no reduction, no atomics.
+ *
+ * Both return ISLAM_EARG before any device work for B, H, W < 1 (or H*W > 2^30), an unknown robust kind, robust_delta <= 0, and a
+ * NULL pointer other than mask, rgb2imu, grad_inv_depth_or_null and the incoming status.  The host never waits. */
+size_t islam_dense_ba_adjoint_scratch_bytes(int B);
+int islam_dense_ba_ift_weights(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                               const double* rgb2imu, const double* intr4, const double* prior_weight, const double* inv_depth,
+                               int robust_kind, double robust_delta, const double* S, const double* grad_motion,
+                               const double* grad_inv_depth_or_null, const int* status_in_or_null, void* scratch, int B, int H,
+                               int W, double* lambda_p, int* status_out, void* stream);
+int islam_dense_ba_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion, const double* rgb2imu,
+                       const double* intr4, const double* prior_weight, const double* inv_depth, int robust_kind,
+                       double robust_delta, const double* lambda_p, const double* grad_inv_depth_or_null,
+                       const int* status_or_null, float* grad_depth, float* grad_flow, int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

@@ -120,6 +120,9 @@ SIGNATURES = {
     'islam_dense_ba_normal': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
     'islam_dense_ba_refine': (c_int, [c_void_p] * 7 + [c_int, c_double, c_int, c_double, c_double] + [c_void_p] * 13 +
                               [c_int, c_void_p] + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_adjoint_scratch_bytes': (c_size_t, [c_int]),
+    'islam_dense_ba_ift_weights': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 3),
+    'islam_dense_ba_vjp': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'islam_imu_scratch_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'islam_imu_preint': (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int] + [c_void_p] * 3 + [c_double, c_int] +
                          [c_void_p] * 4 + [c_int, c_void_p]),

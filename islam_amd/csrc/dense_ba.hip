@@ -13,6 +13,8 @@
 // (One sweep with both halves per pixel needs 446 VGPRs, one wave per SIMD, and spills at 256; two sweeps need no more than the
 // pose-only kernel)  Both sweeps call ba_pixel for the per-pixel terms, and the second sweep is the only
 // code that forms sums, so islam_dense_ba_normal at the returned state runs the same instructions on the same bits.
+// Further down: the gradient of the joint refinement in depth and flow (joint_adj_partial_kernel, joint_adj_solve_kernel,
+// joint_adj_vjp_kernel).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -272,6 +274,231 @@ extern "C" int islam_dense_ba_refine(const float* depth, const float* flow, cons
         hipLaunchKernelGGL(dense_ba_final_kernel, dim3(B), dim3(64), 0, s, partial, rgb2imu, pose, o, rf, jt, B);
     }
     hipLaunchKernelGGL(dense_ba_gather_kernel, dim3(NBLK, B), dim3(256), 0, s, buf0, buf1, select, out_inv_depth, (int)HW);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// ------------------------------------------------------------------ the gradient of the joint refinement in depth and flow
+//   At the state (T*, rho*) a refinement returned the joint gradient G = [g_p; g_d] vanishes, so a loss L on
+// the outputs has dL = lambda^T dG with H_full lambda = -v, v = [v_p; v_d] the loss's gradient in the pose tangent and in every rho*.
+// The depths are eliminated pixel by pixel as in the forward pass:
+//   u_cam = sum_valid h_pd v_d / h_dd,   S lambda_p = -(v_p - A^T u_cam),   lambda_cam = A lambda_p,
+//   lambda_d = -(v_d + h_pd^T lambda_cam) / h_dd   (an invalid pixel with a prior: c = 0, lambda_d = -v_d / w),
+// and with Phi = lambda_p^T g_p + sum lambda_d g_d at fixed state, lambda and valid set, q = J_cam lambda_cam + jd lambda_d:
+//   dPhi/dflow = -(c q + 2 c' (q.r) r),   dPhi/ddepth = w lambda_d / depth^2.
+// joint_adj_partial_kernel reduces u_cam (one row of 6 per workgroup, plain stores), joint_adj_solve_kernel makes lambda_p,
+// joint_adj_vjp_kernel streams the two gradients out.  (The three names keep clear of the four substrings by which
+// tests/test_dense_reproj_cpu.py counts the family's seven older kernels.)
+namespace {
+
+__global__ __launch_bounds__(256) void joint_adj_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                                 const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                                 const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                                 const double* __restrict__ prior_weight, const double* __restrict__ inv_depth,
+                                                                 const double* __restrict__ grad_rho, const int* __restrict__ status,
+                                                                 double* __restrict__ partial6, int H, int W, int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const double w = prior_weight[b];
+    // a marked link (or one without a usable prior weight) stores rows of zeros without reading its pixels
+    const bool live = w > 0.0 && !(status && status[b] != ISLAM_DENSE_REPROJ_OK);
+    double acc[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[i] = 0.0;
+    if (live) {
+        const Intr in = intr_load(intr4 + 4 * b);
+        const double d2 = delta * delta;
+        __shared__ double Tp[12];
+        if (threadIdx.x == 0) pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+        __syncthreads();
+        const M3<double> R = m3_load(Tp);
+        const V3<double> t{Tp[9], Tp[10], Tp[11]};
+        const size_t off = (size_t)b * HW;
+        const float* zp = depth + off;
+        const float* fup = flow + 2 * off;
+        const float* fvp = fup + HW;
+        const uint8_t* mp = mask ? mask + off : nullptr;
+        const double* rp = inv_depth + off;
+        const double* vp = grad_rho + off;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+            const int v = i / W, u = i - v * W;
+            const double ud = (double)u, vd = (double)v;
+            const double z = (double)zp[i];
+            const double rho = rp[i];
+            if (!(isfinite(z) && z > 0.0 && isfinite(rho) && rho > 0.0)) continue;
+            const BaPixel p = ba_pixel(R, t, rho, (ud - in.cx) / in.fx, (vd - in.cy) / in.fy, (double)fup[i] + ud, (double)fvp[i] + vd,
+                                       mp ? mp[i] != 0 : true, in, kind, delta, d2);
+            if (!p.p.valid) continue;
+            const double eu = p.p.c * p.jdu, ev = p.p.c * p.jdv;
+            const double k = vp[i] / (eu * p.jdu + ev * p.jdv + w);      // v_d / h_dd
+#pragma unroll
+            for (int q = 0; q < 6; ++q) acc[q] += (eu * p.p.ju[q] + ev * p.p.jv[q]) * k;
+        }
+    }
+    reduce_and_store_row6(acc, partial6 + ((size_t)b * NBLK + blockIdx.x) * 6, live);
+}
+
+// lambda_p per link.  v_p from the gradient on [t, q xyzw] as reproj_ift_kernel forms it; u_cam = the NBLK rows in fixed order (0 when
+// the reduction did not run); A^T u = [R^T u_rho; R^T (u_phi - t x u_rho)] with C^-1 = (R, t).  A link that comes with a status, whose
+// prior weight is not > 0, or whose S has a non-positive pivot gets lambda_p = 0.
+__global__ __launch_bounds__(64) void joint_adj_solve_kernel(const double* __restrict__ Sm, const double* __restrict__ motion,
+                                                              const double* __restrict__ grad_motion, const double* __restrict__ rgb2imu,
+                                                              const double* __restrict__ prior_weight, const int* __restrict__ status_in,
+                                                              const double* __restrict__ partial6, double* __restrict__ lambda_p,
+                                                              int* __restrict__ status_out) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    __shared__ double Hn[36], un[6], vn[6], L[6][6], x[6];
+    __shared__ int st;
+    if (i < 36) Hn[i] = Sm[(size_t)b * 36 + i];
+    if (i >= 36 && i < 42) {
+        double v = 0.0;
+        if (partial6)
+            for (int k = 0; k < NBLK; ++k) v += partial6[((size_t)b * NBLK + k) * 6 + (i - 36)];
+        un[i - 36] = v;
+    }
+    __syncthreads();
+    if (i == 0) {
+        const SE3<double> X = se3_load(motion + (size_t)b * 7);
+        const double* gm = grad_motion + (size_t)b * 7;
+        V3<double> vr = tmul(qmat(X.q), v3(gm[0], gm[1], gm[2]));
+        const V3<double> qv{X.q.x, X.q.y, X.q.z}, gq{gm[3], gm[4], gm[5]};
+        V3<double> vf = 0.5 * (X.q.w * gq - cross(qv, gq) - gm[6] * qv);
+        V3<double> ur{un[0], un[1], un[2]}, uf{un[3], un[4], un[5]};
+        if (rgb2imu) {
+            const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
+            const M3<double> Rc = qmat(Ci.q);
+            uf = tmul(Rc, uf - cross(Ci.t, ur));
+            ur = tmul(Rc, ur);
+        }
+        vr = vr - ur;
+        vf = vf - uf;
+        vn[0] = vr.x; vn[1] = vr.y; vn[2] = vr.z; vn[3] = vf.x; vn[4] = vf.y; vn[5] = vf.z;
+        int s = status_in ? status_in[b] : ISLAM_DENSE_REPROJ_OK;
+        if (s == ISLAM_DENSE_REPROJ_OK && !(prior_weight[b] > 0.0)) s = ISLAM_DENSE_REPROJ_BADPRIOR;
+        if (s == ISLAM_DENSE_REPROJ_OK && !lm_step(Hn, vn, 0.0, L, x)) s = ISLAM_DENSE_REPROJ_NOTPD;
+        st = s;
+        status_out[b] = s;
+    }
+    __syncthreads();
+    if (i < 6) lambda_p[(size_t)b * 6 + i] = st == ISLAM_DENSE_REPROJ_OK ? x[i] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void joint_adj_vjp_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                             const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                             const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                             const double* __restrict__ prior_weight, const double* __restrict__ inv_depth,
+                                                             const double* __restrict__ lambda_p, const double* __restrict__ grad_rho,
+                                                             const int* __restrict__ status, float* __restrict__ grad_depth,
+                                                             float* __restrict__ grad_flow, int H, int W, int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const size_t off = (size_t)b * HW;
+    float* gzp = grad_depth + off;
+    float* gup = grad_flow + 2 * off;
+    float* gvp = gup + HW;
+    const double w = prior_weight[b];
+    if (!(w > 0.0) || (status && status[b] != ISLAM_DENSE_REPROJ_OK)) {      // a link without a gradient: zeros, whatever its pixels hold
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) gzp[i] = gup[i] = gvp[i] = 0.0f;
+        return;
+    }
+    const Intr in = intr_load(intr4 + 4 * b);
+    const double d2 = delta * delta;
+    __shared__ double Tp[12], lcam[6];
+    if (threadIdx.x == 0) {
+        pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+        const double* lp = lambda_p + 6 * b;
+        V3<double> lr{lp[0], lp[1], lp[2]}, lf{lp[3], lp[4], lp[5]};
+        adjoint_apply(rgb2imu, lr, lf);      // lambda_cam = Ad(C^-1) lambda_p
+        lcam[0] = lr.x; lcam[1] = lr.y; lcam[2] = lr.z; lcam[3] = lf.x; lcam[4] = lf.y; lcam[5] = lf.z;
+    }
+    __syncthreads();
+    const M3<double> R = m3_load(Tp);
+    const V3<double> t{Tp[9], Tp[10], Tp[11]};
+    const float* zp = depth + off;
+    const float* fup = flow + 2 * off;
+    const float* fvp = fup + HW;
+    const uint8_t* mp = mask ? mask + off : nullptr;
+    const double* rp = inv_depth + off;
+    const double* vp = grad_rho ? grad_rho + off : nullptr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        const int v = i / W, u = i - v * W;
+        const double ud = (double)u, vd = (double)v;
+        const double z = (double)zp[i];
+        double gz = 0.0, gu = 0.0, gv = 0.0;
+        if (isfinite(z) && z > 0.0) {      // the pixel has a prior
+            const double rho = rp[i];
+            const double vdi = vp ? vp[i] : 0.0;
+            double ld = -vdi / w;          // c = 0: an invalid pixel follows its prior
+            if (isfinite(rho) && rho > 0.0) {
+                const BaPixel p = ba_pixel(R, t, rho, (ud - in.cx) / in.fx, (vd - in.cy) / in.fy, (double)fup[i] + ud, (double)fvp[i] + vd,
+                                           mp ? mp[i] != 0 : true, in, kind, delta, d2);
+                if (p.p.valid) {
+                    const double c = p.p.c, ru = p.p.ru, rv = p.p.rv;
+                    const double eu = c * p.jdu, ev = c * p.jdv;
+                    double du = 0.0, dv = 0.0;      // J_cam lambda_cam
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) {
+                        du += p.p.ju[q] * lcam[q];
+                        dv += p.p.jv[q] * lcam[q];
+                    }
+                    ld = -(vdi + (eu * du + ev * dv)) / (eu * p.jdu + ev * p.jdv + w);
+                    const double qu = du + p.jdu * ld, qv = dv + p.jdv * ld;
+                    const double k2 = 2.0 * p.p.cp * (qu * ru + qv * rv);
+                    gu = -(c * qu + k2 * ru);
+                    gv = -(c * qv + k2 * rv);
+                }
+            }
+            gz = w * ld / (z * z);
+        }
+        gzp[i] = (float)gz;
+        gup[i] = (float)gu;
+        gvp[i] = (float)gv;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t islam_dense_ba_adjoint_scratch_bytes(int B) {
+    if (B < 1) return 0;
+    return align_up((size_t)B * NBLK * 6 * sizeof(double));
+}
+
+extern "C" int islam_dense_ba_ift_weights(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                          const double* rgb2imu, const double* intr4, const double* prior_weight, const double* inv_depth,
+                                          int robust_kind, double robust_delta, const double* S, const double* grad_motion,
+                                          const double* grad_inv_depth_or_null, const int* status_in_or_null, void* scratch, int B, int H,
+                                          int W, double* lambda_p, int* status_out, void* stream) {
+    const char* who = "islam_dense_ba_ift_weights";
+    if (int rc = check_shape_kind(who, B, H, W, robust_kind, robust_delta)) return rc;
+    if (!depth || !flow || !motion || !intr4 || !scratch)
+        return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / scratch pointer", who);
+    if (!prior_weight) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    if (!inv_depth || !S || !grad_motion || !lambda_p || !status_out)
+        return fail(ISLAM_EARG, "%s: NULL inv_depth / S / grad_motion / lambda_p / status_out pointer", who);
+    hipStream_t s = as_stream(stream);
+    double* partial6 = static_cast<double*>(scratch);
+    if (grad_inv_depth_or_null)
+        hipLaunchKernelGGL(joint_adj_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4, prior_weight,
+                           inv_depth, grad_inv_depth_or_null, status_in_or_null, partial6, H, W, robust_kind, robust_delta);
+    hipLaunchKernelGGL(joint_adj_solve_kernel, dim3(B), dim3(64), 0, s, S, motion, grad_motion, rgb2imu, prior_weight, status_in_or_null,
+                       grad_inv_depth_or_null ? partial6 : nullptr, lambda_p, status_out);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+extern "C" int islam_dense_ba_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion, const double* rgb2imu,
+                                  const double* intr4, const double* prior_weight, const double* inv_depth, int robust_kind,
+                                  double robust_delta, const double* lambda_p, const double* grad_inv_depth_or_null,
+                                  const int* status_or_null, float* grad_depth, float* grad_flow, int B, int H, int W, void* stream) {
+    const char* who = "islam_dense_ba_vjp";
+    if (int rc = check_shape_kind(who, B, H, W, robust_kind, robust_delta)) return rc;
+    if (!depth || !flow || !motion || !intr4) return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 pointer", who);
+    if (!prior_weight) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    if (!inv_depth || !lambda_p || !grad_depth || !grad_flow)
+        return fail(ISLAM_EARG, "%s: NULL inv_depth / lambda_p / grad_depth / grad_flow pointer", who);
+    hipLaunchKernelGGL(joint_adj_vjp_kernel, dim3(NBLK, B), dim3(256), 0, as_stream(stream), depth, flow, mask, motion, rgb2imu, intr4,
+                       prior_weight, inv_depth, lambda_p, grad_inv_depth_or_null, status_or_null, grad_depth, grad_flow, H, W, robust_kind,
+                       robust_delta);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

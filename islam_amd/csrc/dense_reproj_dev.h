@@ -116,6 +116,22 @@ ISLAM_DEV void reduce_and_store_row(const double* acc, double* __restrict__ row,
     if (threadIdx.x < NS) row[threadIdx.x] = ok ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : NAN;
 }
 
+// The same epilogue for a row of six (joint_adj_partial_kernel, section 3.26).  A sibling and not a row-length argument of the function
+// above: that one's instructions stay as they are.  ok = false stores zeros.
+ISLAM_DEV void reduce_and_store_row6(const double* acc, double* __restrict__ row, bool ok) {
+    __shared__ double red6[4][6];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double x = acc[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+        if (lane == 0) red6[wv][i] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) row[threadIdx.x] = ok ? red6[0][threadIdx.x] + red6[1][threadIdx.x] + red6[2][threadIdx.x] + red6[3][threadIdx.x] : 0.0;
+}
+
 // what the final kernel writes per link; under refinement these arrays ARE the link's current state
 struct Outputs {
     double *H, *g, *cost, *l1, *count, *sums;

@@ -10,7 +10,8 @@
     DESIGN.md section 3.23) and give run_pvgo its VO information (PvgoInfo.from_dense_reproj); ``refine(differentiable=True)``
     lets a loss on the refined pose reach the stored depth and flow (section 3.24); ``refine_joint`` and
     ``information(sigma_inv_depth=...)`` treat the stored depth as a Gaussian prior on one inverse depth per pixel and refine or
-    marginalise it with the pose (csrc/dense_ba.hip, section 3.25);
+    marginalise it with the pose (csrc/dense_ba.hip, section 3.25); ``refine_joint(differentiable=True)`` lets a loss on the jointly
+    refined pose, inverse depths or depth map reach the stored depth and flow (section 3.26);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -228,18 +229,38 @@ class DenseReprojectionLoss:
             raise ValueError('%s: sigma_inv_depth must be a finite positive number (got %r)' % (who, sigma_inv_depth))
         return (sigma_px / sig) ** 2
 
-    def refine_joint(self, motion, sigma_inv_depth, sigma_px=1.0, iters=20, kernel=None, damping=1e-4, min_count=16, trace_cap=0):
+    def refine_joint(self, motion, sigma_inv_depth, sigma_px=1.0, iters=20, kernel=None, damping=1e-4, min_count=16, trace_cap=0,
+                     differentiable=False):
         """Joint two-view bundle adjustment of each link: ``iters`` device-side Levenberg-Marquardt evaluations on the pose AND one
         inverse depth per pixel, the stored depth as a Gaussian prior of standard deviation ``sigma_inv_depth`` (1/m; a positive number
         or a (B,) tensor; sigma_inv_depth_from_disparity gives the usual stereo value) beside flow errors of ``sigma_px`` pixels
         (ops.dense_ba_refine).  Returns DenseBAJoint: the fields of ops.DenseBARefined (motion, inv_depth, S,
         g, cost, l1, count, sums, damping, accepted, rejected, status, trace) and ``depth``: 1 / inv_depth where that is positive,
-        the stored depth elsewhere.  No gradient is attached (refine(differentiable=True) is pose-only)."""
+        the stored depth elsewhere.
+
+        differentiable=False (the default): no gradient is attached.  differentiable=True: ``motion`` and ``inv_depth`` carry a grad_fn
+        over the stored depth and flow (the tensors given to the constructor keep their graph), and ``depth``, formed from
+        ``inv_depth`` in torch, follows by the chain rule, so a loss on the refined pose, inverse depths or depth map reaches the
+        networks.  The gradient is the implicit-function one of the joint problem at the returned state, not an unrolled LM: the
+        adjoint system H_full lambda = -v is solved by the forward pass's per-pixel elimination against the undamped S returned
+        here, and the gradient is d(lambda^T G)/d(depth, flow) (ops.dense_ba_ift_weights and ops.dense_ba_vjp, two or three launches,
+        nothing read back).  The input depth enters only through the prior, so that derivative is exact; H_full
+        is the Gauss-Newton matrix: exact where the residual vanishes and rho = rho0, off by terms proportional to the residuals
+        elsewhere (with a noisy prior the residuals at the optimum are not zero: section 3.26 measures the error), and the formula
+        assumes convergence in pose and depths.  The start ``motion`` gets no gradient (the optimum does not depend on it), nor does
+        the prior weight (``sigma_inv_depth``, ``sigma_px``: out of scope); a link whose status is set, or whose S is not positive
+        definite, gets a zero gradient."""
         from . import ops
         w = self._prior_weight(sigma_inv_depth, sigma_px, 'refine_joint')
-        out = ops.dense_ba_refine(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w,
-                                  rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
-                                  trace_cap=trace_cap)
+        if differentiable:
+            mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
+            out = ops.DenseBARefined(*ops._DenseBARefine.apply(
+                self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w, mount, kernel, iters,
+                damping, min_count, trace_cap))
+        else:
+            out = ops.dense_ba_refine(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w,
+                                      rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
+                                      trace_cap=trace_cap)
         ok = out.inv_depth > 0
         depth = torch.where(ok, (1.0 / torch.where(ok, out.inv_depth, torch.ones_like(out.inv_depth))).to(self.z.dtype), self.z.detach())
         return DenseBAJoint(*out, depth)

@@ -381,6 +381,111 @@ class _DenseReprojRefine(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None)
 
 
+def _dense_ba_state(inv_depth, B, H, W, dev, who, name='inv_depth'):
+    if tuple(inv_depth.shape) != (B, H, W):
+        raise ValueError('%s: %s must be (%d,%d,%d), got %s' % (who, name, B, H, W, tuple(inv_depth.shape)))
+    return inv_depth.detach().to(dev, torch.float64).contiguous()
+
+
+def dense_ba_ift_weights(depth, flow, mask, motion, intr, prior_weight, inv_depth, S, grad_motion, grad_inv_depth=None, rgb2imu=None,
+                         kernel=None, status=None):
+    """lambda_p (B,6) of the joint refinement's implicit gradient (include/islam_hip.h, islam_dense_ba_ift_weights; DESIGN.md section
+    3.26): S lambda_p = -(v_p - A^T u_cam) at the state (motion (B,7), inv_depth (B,H,W)) a dense_ba_refine returned with the undamped
+    S (B,6,6), for a loss with gradient grad_motion (B,7) on [t, q xyzw] and grad_inv_depth (B,H,W) or None on inv_depth (None skips
+    the reduction of u_cam).  Other arguments as dense_ba_normal; status (B) int or None: the refinement's status.  Returns
+    (lambda_p float64, status (B) int32): a link with an incoming status, a prior weight that is not > 0 (_lib.DENSE_REPROJ_BADPRIOR)
+    or an S that is not positive definite (_NOTPD) has lambda_p = 0.  One or two launches, nothing is read back."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, B, dev)
+    rho = _dense_ba_state(inv_depth, B, H, W, dev, 'dense_ba_ift_weights')
+    f64 = lambda t: torch.as_tensor(t).detach().to(dev, torch.float64).contiguous()
+    S, grad_motion = f64(S), f64(grad_motion)
+    if tuple(S.shape) != (B, 6, 6) or tuple(grad_motion.shape) != (B, 7):
+        raise ValueError('dense_ba_ift_weights: S must be (%d,6,6) and grad_motion (%d,7), got %s and %s' % (
+            B, B, tuple(S.shape), tuple(grad_motion.shape)))
+    if grad_inv_depth is not None:
+        grad_inv_depth = _dense_ba_state(grad_inv_depth, B, H, W, dev, 'dense_ba_ift_weights', 'grad_inv_depth')
+    return _dense_ba_ift_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, S, grad_motion, grad_inv_depth,
+                                _dense_reproj_status(status, B, dev))
+
+
+def _dense_ba_ift_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, S, grad_motion, grad_rho, status):
+    """islam_dense_ba_ift_weights on tensors _dense_reproj_args has prepared."""
+    B, H, W = depth.shape
+    dev = depth.device
+    lam = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    out = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(lib().islam_dense_ba_adjoint_scratch_bytes(B), dtype=torch.uint8, device=dev)
+    check(lib().islam_dense_ba_ift_weights(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), ptr(rho), kind,
+                                           delta, ptr(S), ptr(grad_motion), ptr(grad_rho), ptr(status), ptr(scratch), B, H, W, ptr(lam),
+                                           ptr(out), stream_ptr(dev)))
+    return lam, out
+
+
+def dense_ba_vjp(depth, flow, mask, motion, intr, prior_weight, inv_depth, lambda_p, grad_inv_depth=None, rgb2imu=None, kernel=None,
+                 status=None):
+    """The gradient of a loss on a joint refinement's outputs in depth and flow, from lambda_p (B,6) (dense_ba_ift_weights) and the
+    loss's gradient grad_inv_depth (B,H,W) or None on inv_depth (include/islam_hip.h, islam_dense_ba_vjp):
+    per pixel lambda_d, then dL/dflow = -(c q + 2 c' (q.r) r) and dL/ddepth = w lambda_d / depth^2.  Other arguments as
+    dense_ba_normal; status (B) int or None: a link whose status is not 0 gets zeros.  Returns (grad_depth (B,H,W), grad_flow
+    (B,2,H,W)), float32 on the device; one launch, nothing is read back."""
+    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, B, dev)
+    rho = _dense_ba_state(inv_depth, B, H, W, dev, 'dense_ba_vjp')
+    lambda_p = torch.as_tensor(lambda_p).detach().to(dev, torch.float64).contiguous()
+    if tuple(lambda_p.shape) != (B, 6):
+        raise ValueError('dense_ba_vjp: lambda_p must be (%d,6) [rho, phi], got %s' % (B, tuple(lambda_p.shape)))
+    if grad_inv_depth is not None:
+        grad_inv_depth = _dense_ba_state(grad_inv_depth, B, H, W, dev, 'dense_ba_vjp', 'grad_inv_depth')
+    return _dense_ba_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, lambda_p, grad_inv_depth,
+                                _dense_reproj_status(status, B, dev))
+
+
+def _dense_ba_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, lambda_p, grad_rho, status):
+    """islam_dense_ba_vjp on tensors _dense_reproj_args has prepared."""
+    B, H, W = depth.shape
+    grad_depth = torch.empty((B, H, W), dtype=torch.float32, device=depth.device)
+    grad_flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=depth.device)
+    check(lib().islam_dense_ba_vjp(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), ptr(rho), kind, delta,
+                                   ptr(lambda_p), ptr(grad_rho), ptr(status), ptr(grad_depth), ptr(grad_flow), B, H, W,
+                                   stream_ptr(depth.device)))
+    return grad_depth, grad_flow
+
+
+class _DenseBARefine(torch.autograd.Function):
+    """dense_ba_refine whose refined motion and inv_depth carry the implicit-function gradient in depth and flow (DESIGN.md section
+    3.26): backward is islam_dense_ba_ift_weights (two launches, one when no gradient arrives on inv_depth) and islam_dense_ba_vjp at
+    the refined state on the tensors forward prepared, and nothing else.  The start pose and the prior weight get no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth, flow, mask, motion, intr, prior_weight, rgb2imu, kernel, iters, damping, min_count, trace_cap):
+        dev, B, H, W, depth32, flow32, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+        w = _dense_ba_prior_weight(prior_weight, B, dev)
+        out = dense_ba_refine(depth32, flow32, mask, motion, intr, w, rgb2imu=rgb2imu, kernel=kernel, iters=iters, damping=damping,
+                              min_count=min_count, trace_cap=trace_cap)
+        ctx.save_for_backward(depth32, flow32, mask, out.motion, out.inv_depth, out.S, out.status, intr, rgb2imu, w)
+        ctx.kind, ctx.delta, ctx.dtypes = kind, delta, (depth.dtype, flow.dtype)
+        ctx.mark_non_differentiable(*(t for t in out[2:] if t is not None))
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None: no reduction for it
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_motion, grad_inv_depth, *unused):
+        none = (None,) * 12
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return none
+        depth, flow, mask, motion, rho, S, status, intr, rgb2imu, w = ctx.saved_tensors
+        grad_motion = torch.zeros_like(motion) if grad_motion is None else grad_motion.to(torch.float64).contiguous()
+        if grad_inv_depth is not None:
+            grad_inv_depth = grad_inv_depth.to(torch.float64).contiguous()
+        lam, status = _dense_ba_ift_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, ctx.kind, ctx.delta, S, grad_motion,
+                                           grad_inv_depth, status)
+        grad_depth, grad_flow = _dense_ba_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, ctx.kind, ctx.delta, lam,
+                                                     grad_inv_depth, status)
+        return (grad_depth.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
+                grad_flow.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None) + none[2:]
+
+
 # --------------------------------------------------------------------------- 3x3 convolution on the matrix cores
 def deconv_to2(x, weight, bias, out=None, coff=0):
     """nn.ConvTranspose2d(C, 2, 4, 2, 1)(x) for fp32 NCHW tensors on islam_deconv4x4s2_to2_f32 (PWC-Net's deconv / upfeat layers), written

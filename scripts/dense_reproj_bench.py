@@ -17,6 +17,13 @@ what the gradient costs without the kernel: eager float64 torch autograd of w^T 
 ops.dense_ba_refine, beside the pose-only ops.dense_reproj_normal / ops.dense_reproj_refine on the same tensors.
 
     python scripts/dense_reproj_bench.py --joint [--case 448x640] [--out profiles/dense_ba_bench.json]
+
+--joint-grad times the gradient of the joint refinement in depth and flow instead, by the method of --grad:
+ops.dense_ba_vjp alone (beside ops.dense_reproj_vjp on the same tensors), the whole backward (ops.dense_ba_ift_weights and
+ops.dense_ba_vjp) with and without a gradient on inv_depth, a 20-evaluation refine_joint(differentiable=True) with its backward through
+autograd, and what the gradient costs without the kernels: eager float64 torch autograd of the same Phi.
+
+    python scripts/dense_reproj_bench.py --joint-grad [--case 448x640] [--out profiles/dense_ba_grad_bench.json]
 """
 import json
 import os
@@ -274,8 +281,153 @@ def main_joint(argv):
         f.write(line + '\n')
 
 
+JOINT_GRAD_PIXEL_BYTES = 41          # the joint VJP: the 13 of the pose-only pass, rho and the gradient on it (8 each), three float32 stores
+
+
+def torch_phi(depth, flow, mask, rho, R, t, A, intr, lam, v_d, w):
+    """Phi = lambda_p^T g_p + sum lambda_d g_d of every link in eager torch (float64, no robust kernel, differentiable in depth and flow;
+    the state, lambda and the valid set are held fixed; lambda_d is formed here from lam and v_d as the kernel forms it): what the
+    gradient of the joint refinement costs without the kernels.  R (B,3,3), t (B,3): T^-1 per link; A (6,6) = Ad(C^-1); w (B)."""
+    import torch
+    B, H, W = depth.shape
+    fx, fy, cx, cy = (intr[:, k].view(B, 1, 1) for k in range(4))
+    u = torch.arange(W, dtype=torch.float64, device=depth.device).view(1, 1, W)
+    v = torch.arange(H, dtype=torch.float64, device=depth.device).view(1, H, 1)
+    wb = w.view(B, 1, 1)
+    with torch.no_grad():
+        prior = torch.isfinite(depth) & (depth > 0)
+        usable = prior & (rho > 0)
+    zi = 1.0 / torch.where(usable, rho, torch.ones_like(rho))
+    ray = torch.stack([((u - cx) / fx).expand(B, H, W), ((v - cy) / fy).expand(B, H, W), torch.ones_like(rho)], -1)
+    Q = ((zi.unsqueeze(-1) * ray).view(B, H * W, 3) @ R.mT + t.view(B, 1, 3)).view(B, H, W, 3)
+    dR = (ray.view(B, H * W, 3) @ R.mT).view(B, H, W, 3)
+    Qx, Qy, Qz = Q.unbind(-1)
+    with torch.no_grad():
+        valid = mask & usable & (Qz > 0.1)
+        valid = valid & ((Qx / Qz).abs() <= 1.0) & ((Qy / Qz).abs() <= 1.0)
+    Qz = torch.where(valid, Qz, torch.ones_like(Qz))
+    ru = fx * Qx / Qz + cx - (flow[:, 0] + u)
+    rv = fy * Qy / Qz + cy - (flow[:, 1] + v)
+    lc = lam @ A.T
+    lr, lf = lc[:, :3].view(B, 1, 1, 3), lc[:, 3:].view(B, 1, 1, 3).expand(B, H, W, 3)
+    m = torch.cross(Q, lf, dim=-1) - lr
+    a, bq, cq, dq = fx / Qz, -fx * Qx / Qz ** 2, fy / Qz, -fy * Qy / Qz ** 2
+    du, dv = a * m[..., 0] + bq * m[..., 2], cq * m[..., 1] + dq * m[..., 2]
+    k = -(zi * zi)
+    jdu, jdv = (a * dR[..., 0] + bq * dR[..., 2]) * k, (cq * dR[..., 1] + dq * dR[..., 2]) * k
+    zero = torch.zeros_like(ru)
+    ld = -(v_d + torch.where(valid, jdu * du + jdv * dv, zero)) / (torch.where(valid, jdu * jdu + jdv * jdv, zero) + wb)
+    ld = torch.where(prior, ld, zero)
+    rho0 = 1.0 / torch.where(prior, depth, torch.ones_like(depth))
+    return torch.where(valid, (du + jdu * ld) * ru + (dv + jdv * ld) * rv, zero).sum() + torch.where(prior, wb * ld * (rho - rho0), zero).sum()
+
+
+def run_joint_grad_case(H, W):
+    """--joint-grad: the backward of the joint refinement -- the VJP alone, the whole backward with and without a
+    gradient on inv_depth, and a 20-evaluation refine_joint(differentiable=True) with its backward through autograd -- beside the
+    pose-only VJP of section 3.24 on the same tensors and beside eager float64 torch autograd of the same Phi."""
+    import numpy as np
+    import torch
+    from islam_amd import lietensor as pp
+    from islam_amd import ops
+    from islam_amd.dense_ba import DenseReprojectionLoss
+    from oracle import lie
+    from tests.dense_reproj_f64 import MOUNT, PRIOR_W, SIGMA_RHO, make_scene, noisy_prior, right_perturb
+    dev = torch.device('cuda:0')
+    sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    w = torch.full((B,), PRIOR_W, dtype=torch.float64, device=dev)
+    rng = np.random.default_rng(0)
+    coeff, coeff_depth = d(rng.standard_normal((B, 7))), d(rng.standard_normal((B, H, W)).astype(np.float32))
+    v_d = d(rng.standard_normal((B, H, W)))
+    fx, fy, cx, cy = sc['intr'][0]
+    ref = ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20)
+    state = (depth, flow, mask, ref.motion, intr, w, ref.inv_depth)
+    lam, status = ops.dense_ba_ift_weights(*state, ref.S, coeff, grad_inv_depth=v_d, rgb2imu=mount, status=ref.status)
+    zl, fl = depth.clone().requires_grad_(), flow.clone().requires_grad_()
+    loss = DenseReprojectionLoss(zl, fl, fx, fy, cx, cy, mask, pp.SE3(mount), device=dev)
+
+    def refine_backward():
+        zl.grad = fl.grad = None
+        out = loss.refine_joint(pp.SE3(motion), SIGMA_RHO, sigma_px=0.3, iters=20, differentiable=True)
+        ((out.motion * coeff).sum() + (out.depth * coeff_depth).sum()).backward()
+
+    def backward(g=v_d):
+        lk, st = ops.dense_ba_ift_weights(*state, ref.S, coeff, grad_inv_depth=g, rgb2imu=mount, status=ref.status)
+        return ops.dense_ba_vjp(*state, lk, grad_inv_depth=g, rgb2imu=mount, status=st)
+
+    pose = ref.motion.cpu().numpy()
+    Ti = np.stack([lie.se3_inv(lie.se3_mul(lie.se3_mul(lie.se3_inv(MOUNT), p), MOUNT)) for p in pose])
+    R, t = d(np.stack([lie.quat_matrix(x[3:]) for x in Ti])), d(Ti[:, :3])
+    A = d(lie.se3_adj(lie.se3_inv(MOUNT)))
+    z64, f64 = depth.double().requires_grad_(), flow.double().requires_grad_()
+
+    def torch_autograd():
+        return torch.autograd.grad(torch_phi(z64, f64, mask, ref.inv_depth, R, t, A, intr, lam, v_d, w), (z64, f64))
+
+    pw, _ = ops.dense_reproj_ift_weights(ref.S, ref.motion, coeff, ref.status)
+    fns = {'reproj_vjp': lambda: ops.dense_reproj_vjp(depth, flow, mask, ref.motion, intr, pw, rgb2imu=mount, status=ref.status),
+           'ba_vjp': lambda: ops.dense_ba_vjp(*state, lam, grad_inv_depth=v_d, rgb2imu=mount, status=status),
+           'ba_vjp_pose_loss': lambda: ops.dense_ba_vjp(*state, lam, rgb2imu=mount, status=status),
+           'backward': backward, 'backward_pose_loss': lambda: backward(None),
+           'ba_refine20': lambda: ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20),
+           'refine_joint20_backward': refine_backward, 'torch_autograd_f64': torch_autograd}
+
+    def median(fn, n=30):
+        us = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        us.sort()
+        return 0.5 * (us[n // 2 - 1] + us[n // 2])
+
+    out = {}
+    for name, fn in fns.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = median(fn)
+    gd, gf = fns['ba_vjp']()
+    td, tf = torch_autograd()
+    out['grad_depth_vs_torch_f64'] = float((gd.double() - td).abs().max() / td.abs().max())
+    out['grad_flow_vs_torch_f64'] = float((gf.double() - tf).abs().max() / tf.abs().max())
+    out['status_ok'] = int((status == 0).sum())
+    out['MB_moved'] = JOINT_GRAD_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_ba_vjp'] = JOINT_GRAD_PIXEL_BYTES * B * H * W / (out['ba_vjp'] * 1e-6) / 1e9 / HBM_GBS
+    out['ba_vjp_over_reproj_vjp'] = out['ba_vjp'] / out['reproj_vjp']
+    out['torch_over_backward'] = out['torch_autograd_f64'] / out['backward']
+    return out
+
+
+def main_joint_grad(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_joint_grad_case(*hw) for case, hw in cases.items()}
+    cols = ('reproj_vjp', 'ba_vjp', 'ba_vjp_pose_loss', 'backward', 'backward_pose_loss', 'ba_refine20', 'refine_joint20_backward', 'torch_autograd_f64',
+            'MB_moved', 'hbm_frac_ba_vjp', 'ba_vjp_over_reproj_vjp', 'torch_over_backward', 'grad_depth_vs_torch_f64', 'grad_flow_vs_torch_f64', 'status_ok')
+    print('us per call at B = %d: the median of 30; hbm_frac_ba_vjp: %d bytes per pixel over the time, of %.0f GB/s' % (B, JOINT_GRAD_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'dense_ba_grad_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--joint-grad' in sys.argv[1:]:
+        return main_joint_grad(sys.argv[1:])
     if '--grad' in sys.argv[1:]:
         return main_grad(sys.argv[1:])
     if '--joint' in sys.argv[1:]:
