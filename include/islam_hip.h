@@ -191,14 +191,18 @@ int islam_bias_act_bwd_f32_nhwc(const float* gy, const float* y, float* gx, floa
  * stride 2 and a 1x1 stride-2 convolution on its shortcut) and the two Linear heads (:84-92), and its backward (what
  * train.py:280-283's loss.backward() runs through this module) -- each ONE call that enqueues hand-written fp32 kernels (exact-fp32
  * matrix-core implicit GEMMs, csrc/pose_head.hip) on `stream`: no MIOpen / CK / ATen launch, deterministic summation orders.
- *   x        (B,H,W,4) fp32 channels-last: [flow(2), intrinsic layer(2)] (Network/VONet.py:36); B <= 16; the input's 1/64-size feature map must
- *            have 6 pixels (448x640 images: H = 112, W = 160)
+ *   x        (B,H,W,4) fp32 channels-last: [flow(2), intrinsic layer(2)] (Network/VONet.py:36); B <= 16; the input's 1/64-size feature map
+ *            (six times v -> (v - 1) / 2 + 1) must have 6 pixels: 2x3 for H = 65..128, W = 129..192 (448x640 images: H = 112, W = 160);
+ *            3x2 and 1x6 are served as well, 6x1 (a level one pixel wide) is not
  *   params   the module's 120 parameters in state_dict order (feat_net.0.0.weight, feat_net.0.0.bias, ..., voflow_rot.2.bias), device pointers;
  *            convolution weights in channels_last memory ([Cout][ky][kx][Cin]), everything else contiguous
  *   out6     (B,6) = cat(trans, rot)
- *   workspace  islam_pose_head_workspace_bytes(B,H,W) bytes (0: unsupported shape); holds every activation of the forward -- the backward
- *            reads what the LAST forward on this workspace left there -- plus gradient ping-pong buffers and split-K scratch.  Must be
- *            zero-filled once before its first use (ticket words; every launch leaves them zero).
+ *   workspace  islam_pose_head_workspace_bytes(B,H,W) bytes (0: unsupported shape), or more; holds every activation of the forward plus
+ *            gradient buffers and split-K scratch.  Must be zero-filled ONCE before its first use (the split-K ticket words and a
+ *            region of zeros: both sit at the same offsets for every shape, in front of everything a call writes, and every launch
+ *            leaves them zero).  One workspace may then serve any sequence of shapes it is large enough for (the largest
+ *            islam_pose_head_workspace_bytes of the sequence; the size grows with B, H and W) without being cleared in between.  The
+ *            backward reads what the LAST forward on this workspace left there: that forward must have had the SAME (B,H,W) and x.
  * backward: grads[i] receives (accumulate = 0) or is incremented by (accumulate = 1) the gradient of parameter i, same layouts as params;
  * grad_out6 (B,6).  No gradient w.r.t. x is produced (the reference detaches the flow in front of the head's consumers only when the flow
  * net is frozen, TartanVO.py:109; a trainable flow net takes the eager autograd path in islam_amd/nets.py). */

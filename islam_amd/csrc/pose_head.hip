@@ -65,7 +65,7 @@ struct ConvArgs {
     int rows;              // GEMM rows: FWD B*Hout*Wout, DGRAD B*Hin*Win, WGRAD Cout
     int nchunk_main, nchunk;     // FWD / DGRAD: K chunks of the 3x3 part / in total.  WGRAD: pixel chunks
     int ntile_main;        // WGRAD: tiles of the 3x3 weights (the rest belong to w2)
-    unsigned mg_hw, mg_w, mg_n8;        // ceil(2^32 / d) for d = (rows' H*W, W) and the padded tile count: n / d = umulhi(n, magic) for n, d < 2^16
+    unsigned mg_hw, mg_w, mg_n8;        // ceil(2^32 / d) for d = (rows' H*W, W) and the padded tile count: n / d = umulhi(n, magic) for n, d < 2^16, d > 1
     int zin, zin2, zg, zg2;             // offset (floats) of the workspace's 4 KB zero region from in / in2 / g / g2: where invalid pieces are read from
     float* partial; unsigned* ticket;   // cross-workgroup split (gridDim.y > 1)
     int stamp_slot;                     // ISLAM_POSE_STAMPS builds (scripts/debug/pose_head_stamps.py): which row of the phase-clock table this launch writes
@@ -81,7 +81,8 @@ namespace {
 #endif
 
 // n / d for n * d < 2^32 with mg = ceil(2^32 / d): one multiply instead of the ~40-instruction integer division sequence (the row decode
-// of a workgroup's set-up and of every weight-gradient chunk was 4-6 of them per thread)
+// of a workgroup's set-up and of every weight-gradient chunk was 4-6 of them per thread).  d = 1 has no such multiplier (2^32 does not
+// fit in 32 bits): make_plan refuses inputs with a level one pixel wide.
 __device__ __forceinline__ int fdiv(int n, unsigned mg) { return (int)__umulhi((unsigned)n, mg); }
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -715,6 +716,11 @@ bool make_plan(int B, int H, int W, Plan& p) {
     size_t off = 0;
     auto take = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
     p.a_zero = take(1024);                                   // nobody writes it: the workspace is zero-filled once, kernels read invalid pieces from here
+    // The split-K ticket words: zero before the first call, left at zero by every launch.  Like a_zero they sit at the SAME offsets for
+    // every (B,H,W), in front of everything a call writes -- one workspace, zero-filled once, serves any sequence of shapes.  (Behind the
+    // activations, whose sizes follow the shape, the tickets of a smaller plan would lie in what a larger one wrote: a ticket that
+    // starts off zero has no last arriver, and the tile's epilogue never runs.)
+    for (int i = 0; i < 2; ++i) p.a_ticket[i] = take(N_TICKETS);
     p.g_stem_geo = Geo{half_up(H), half_up(W), 32};
     const size_t stem_n = (size_t)B * p.g_stem_geo.H * p.g_stem_geo.W * 32;
     for (int i = 0; i < 3; ++i) p.a_stem[i] = take(stem_n);
@@ -735,6 +741,7 @@ bool make_plan(int B, int H, int W, Plan& p) {
             k.g_h = take(n);
             k.g_out = take(n);
             p.blocks.push_back(k);
+            if (k.gout.W < 2) return false;                  // a 6 x 1 feature map: the kernels' row decode (fdiv) cannot divide by a width of 1
             g = k.gout;
         }
     }
@@ -746,10 +753,7 @@ bool make_plan(int B, int H, int W, Plan& p) {
     p.a_gh1 = take((size_t)2 * B * FC_H1);
     for (int i = 0; i < 3; ++i) p.g_stem[i] = take(stem_n);
     p.partial_floats = PARTIAL_FLOATS;
-    for (int i = 0; i < 2; ++i) {
-        p.a_partial[i] = take(p.partial_floats);
-        p.a_ticket[i] = take(N_TICKETS);
-    }
+    for (int i = 0; i < 2; ++i) p.a_partial[i] = take(p.partial_floats);
     p.floats = off;
     return true;
 }
@@ -819,6 +823,7 @@ int prepare(ConvArgs a, int kdim, int kdim2, float* partial, size_t partial_floa
         auto magic = [](int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };
         const int H = MODE == MODE_DGRAD ? a.Hin : a.Hout, W = MODE == MODE_DGRAD ? a.Win : a.Wout, n8 = (ntiles + 7) & ~7;
         // (n / d == umulhi(n, ceil(2^32 / d)) for n * d < 2^32)
+        if (W < 2) return fail(ISLAM_EARG, "pose head: a %d x %d level (one pixel wide) has no row decode", H, W);      // (magic(1) = 2^32)
         if ((long long)a.B * H * W * H * W >= (1ll << 32) || (long long)n8 * KS * n8 >= (1ll << 32)) return fail(ISLAM_EARG, "pose head: %d x %d x %d pixels exceed the row decode", a.B, H, W);
         a.mg_hw = magic(H * W); a.mg_w = magic(W); a.mg_n8 = magic(n8);
     }
@@ -940,7 +945,7 @@ struct Fork {
 
 int check_common(const char* fn, const void* x, const void* const* params, const void* ws, size_t ws_bytes, int B, int H, int W, Plan& p) {
     if (!x || !params || !ws) return fail(ISLAM_EARG, "%s: null pointer", fn);
-    if (!make_plan(B, H, W, p)) return fail(ISLAM_EARG, "%s: B=%d (1..%d) and a %dx%d input whose 256-channel feature map is not 6 pixels", fn, B, FC_MAXB, H, W);
+    if (!make_plan(B, H, W, p)) return fail(ISLAM_EARG, "%s: B=%d (1..%d) and a %dx%d input whose 256-channel feature map is not 6 pixels, or is one pixel wide", fn, B, FC_MAXB, H, W);
     if (ws_bytes < p.floats * sizeof(float)) return fail(ISLAM_EARG, "%s: workspace of %zu bytes, %zu needed", fn, ws_bytes, p.floats * sizeof(float));
     for (int i = 0; i < N_PARAMS; ++i)
         if (!params[i]) return fail(ISLAM_EARG, "%s: parameter %d is null", fn, i);

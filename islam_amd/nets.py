@@ -1061,9 +1061,9 @@ class VOFlowRes(nn.Module):
 
     def forward(self, x, extrinsic=None):
         if getattr(self, 'use_hip_head', False) and not (torch.is_grad_enabled() and x.requires_grad):
-            from . import pose_head
-            if pose_head.supported_input(x):
-                return self.hip_head()(x)
+            y = self.hip_head().run(x)          # None: an input or parameters the kernels do not serve (pose_head.supported) -> the modules below
+            if y is not None:
+                return y
         if getattr(self, 'fused_tail', False) and _fused_tail_ok(x):
             for i, m in enumerate(self.feat_net):
                 x = _conv_relu_fused(m, x) if i < 3 else m(x)
@@ -1275,10 +1275,12 @@ class VONet(nn.Module):
                     pg.key = key
                     self._pose_graphed = tuple(x.shape)
                 pose = _PoseGraphFn.apply(x, pg.leaf, pg) if tuple(x.shape) == self._pose_graphed else self.flowPoseNet(x)
-        elif self.graph_pose and self.graph_pose != 'accumulate' and self.flowPoseNet.training and torch.is_grad_enabled():
+        elif self.graph_pose is True and self.flowPoseNet.training and torch.is_grad_enabled():
             # forward AND backward of the trainable pose head replay from two captured HIP graphs
             # (torch.cuda.make_graphed_callables patches the module's forward; eval mode keeps the eager path, and so does a
-            # batch of another shape, e.g. the last one of an epoch)
+            # batch of another shape, e.g. the last one of an epoch).  Only graph_pose=True: 'hip' and 'accumulate' with an input that
+            # carries a gradient (a trainable flow net) belong in the eager branch below -- graphed callables captured on a detached
+            # sample would return no gradient for it.
             with self._pose_autocast():
                 if self._pose_graphed is None:
                     self._pose_eager = self.flowPoseNet.forward

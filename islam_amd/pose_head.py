@@ -9,7 +9,9 @@ Autograd: ``head(x)`` returns a (B,6) tensor whose backward node ACCUMULATES the
 ``nets._PoseGraphFn``: handing 120 tensors back to the engine costs 1-2 ms of host time per step).  The node hangs on ``head.leaf``, a
 zero-dimensional tensor that requires grad: ``loss.backward()`` reaches it by itself; a caller of ``torch.autograd.grad(loss, inputs)``
 lists it among ``inputs`` (``VONet.pose_graph_leaf()``; ``BilevelLoop._accumulate_gradients`` does).  No gradient flows to ``x``: a pose
-head fed by a TRAINABLE flow net takes the eager modules (``VONet.forward``).
+head fed by a TRAINABLE flow net takes the eager modules (``VONet.forward``), and so does one whose parameters the kernels cannot read
+in place (``PoseHeadHip.run`` returns None; ``VOFlowRes.forward``).  One head serves any sequence of batch and spatial sizes on one
+workspace (zero-filled once, grown when a shape needs more).
 """
 import ctypes
 
@@ -20,21 +22,16 @@ from ._lib import c_size_t, c_void_p, check, lib, stream_ptr
 N_PARAMS = 120
 
 
-def supported_input(x):
-    """True if the kernels serve this input: an fp32 (B,4,H,W) channels-last device tensor whose 1/64-size feature map has 6 pixels, B <= 16."""
+def _input_ok(x):
+    """What supported_input asks of x apart from its size: fp32, (B,4,H,W), channels-last, on a device, no autocast."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 4 and x.shape[0] <= 16):
         return False
-    if not x.is_contiguous(memory_format=torch.channels_last) or torch.is_autocast_enabled():
-        return False
-    return lib().islam_pose_head_workspace_bytes(int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) != 0
+    return x.is_contiguous(memory_format=torch.channels_last) and not torch.is_autocast_enabled()
 
 
-def supported(module, x):
-    """supported_input(x) and parameters the kernels can read in place: fp32 on x's device, convolution weights channels_last."""
-    if not supported_input(x):
-        return False
-    for p in module.parameters():
-        if p.dtype != torch.float32 or p.device != x.device:
+def _params_ok(params, device):
+    for p in params:
+        if p.dtype != torch.float32 or p.device != device:
             return False
         if p.dim() == 4 and not p.is_contiguous(memory_format=torch.channels_last):
             return False
@@ -43,12 +40,23 @@ def supported(module, x):
     return True
 
 
+def supported_input(x):
+    """True if the kernels serve this input: an fp32 (B,4,H,W) channels-last device tensor whose 1/64-size feature map has 6 pixels, B <= 16."""
+    return _input_ok(x) and lib().islam_pose_head_workspace_bytes(int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) != 0
+
+
+def supported(module, x):
+    """supported_input(x) and parameters the kernels can read in place: fp32 on x's device, convolution weights channels_last."""
+    return supported_input(x) and _params_ok(module.parameters(), x.device)
+
+
 class PoseHeadHip:
     def __init__(self, module, graphs=False):
         self.module = module
         self.graphs = bool(graphs)
         self.gen = 0                    # serial number of the latest forward (the backward reads ITS activations from the workspace)
         self._key = None
+        self._refused = None            # the latest key (shape, parameter addresses) the kernels do not serve (run() -> None)
         self._ws = None
         self._graph = {}
         self.leaf = None
@@ -56,22 +64,29 @@ class PoseHeadHip:
 
     # ---- tables -------------------------------------------------------------------------------------------------------------------
     def _prepare(self, x):
+        """Tables, workspace and gradient buffers for x's shape and the parameters where they are now; False if the kernels do not serve
+        them (supported(module, x)).  Per call: x's type and layout and one walk over the parameters (the key); whether the shape and
+        the parameters are served is decided once per key."""
+        if not _input_ok(x):
+            return False
         params = list(self.module.parameters())
         if len(params) != N_PARAMS:
             raise RuntimeError('PoseHeadHip: the module has %d parameters, VOFlowRes of config 1 has %d' % (len(params), N_PARAMS))
         B, _, H, W = x.shape
         key = (x.device, int(B), int(H), int(W), tuple(p.data_ptr() for p in params))
         if key == self._key:
-            return
+            return True
+        if key == self._refused:
+            return False
         dev = x.device
-        if not supported(self.module, x):
-            raise RuntimeError('PoseHeadHip: fp32 parameters on %s with channels_last convolution weights and an fp32 channels-last (B<=16,4,H,W) '
-                               'input are needed (VONet.set_pose_channels_last(True))' % (dev,))
-        nbytes = int(lib().islam_pose_head_workspace_bytes(int(B), int(H), int(W)))
+        nbytes = int(lib().islam_pose_head_workspace_bytes(int(B), int(H), int(W))) if _params_ok(params, dev) else 0
         if nbytes == 0:
-            raise RuntimeError('PoseHeadHip: unsupported input shape %s' % (tuple(x.shape),))
+            self._refused = key
+            return False
         if self._ws is None or self._ws.numel() * 4 < nbytes or self._ws.device != dev:
-            self._ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev)       # (ticket words must start at zero)
+            # zero-filled once: the ticket words and the zero region sit at the same offsets for every shape, and every launch leaves
+            # them zero -- a workspace that is large enough is kept as it is
+            self._ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         self.params = params
         self._ptab = (c_void_p * N_PARAMS)(*[p.data_ptr() for p in params])
         # this batch's gradients: one flat buffer, one view per parameter in the parameter's own memory layout
@@ -90,6 +105,13 @@ class PoseHeadHip:
             self.zero = torch.zeros((), device=dev)
         self._graph = {}
         self._key = key
+        return True
+
+    def _need(self, x):
+        if not self._prepare(x):
+            raise RuntimeError('PoseHeadHip: fp32 parameters on %s with channels_last convolution weights and an fp32 channels-last (B<=16,4,H,W) '
+                               'input whose 1/64-size feature map has 6 pixels (2 x 3; 3 x 2 and 1 x 6 too) are needed (VONet.set_pose_channels_last(True)); got an input of shape %s'
+                               % (x.device, tuple(x.shape)))
 
     def _views(self, flat):
         out = []
@@ -141,8 +163,9 @@ class PoseHeadHip:
                 self._c_backward(g['x'], g['gy'])
         return g
 
-    def forward_raw(self, x):
-        self._prepare(x)
+    def forward_raw(self, x, prepared=False):
+        if not prepared:
+            self._need(x)
         self.gen += 1
         if self.graphs:
             g = self._graphed(x)
@@ -193,18 +216,27 @@ class PoseHeadHip:
 
     # ---- autograd -----------------------------------------------------------------------------------------------------------------
     def __call__(self, x):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.module.parameters()):
+        y = self.run(x)
+        if y is None:
+            self._need(x)
+        return y
+
+    def run(self, x):
+        """head(x) -- or None, with nothing done, where the kernels do not serve x with the module's parameters as they are (the caller
+        takes the eager modules).  Decided once per (shape, parameter addresses)."""
+        if not self._prepare(x):
+            return None
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.params):
             if x.requires_grad:
                 raise RuntimeError('PoseHeadHip produces no gradient w.r.t. its input; use the eager modules for a trainable flow net')
-            self._prepare(x)
             return _PoseHeadFn.apply(x, self.leaf, self)
-        return self.forward_raw(x)
+        return self.forward_raw(x, prepared=True)
 
 
 class _PoseHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, leaf, head):
-        y = head.forward_raw(x)
+        y = head.forward_raw(x, prepared=True)                 # (PoseHeadHip.run has prepared the head for x)
         ctx.head, ctx.gen = head, head.gen
         return y
 
@@ -212,8 +244,8 @@ class _PoseHeadFn(torch.autograd.Function):
     def backward(ctx, gy):
         head = ctx.head
         if ctx.gen != head.gen:
-            raise RuntimeError('PoseHeadHip: backward of a forward whose activations a later forward has overwritten (forward #%d, latest #%d); '
-                               'run forwards that need no gradient under torch.no_grad(), or back-propagate before the next forward'
-                               % (ctx.gen, head.gen))
+            raise RuntimeError('PoseHeadHip: backward of a forward whose activations a later forward has overwritten (forward #%d, latest #%d). '
+                               'EVERY forward of this head writes them, one under torch.no_grad() too: back-propagate before the next forward, '
+                               'or give the forwards in between a PoseHeadHip of their own (or the eager modules)' % (ctx.gen, head.gen))
         head.backward_raw(gy)
         return None, head.zero, None

@@ -69,6 +69,41 @@ def test_host_only_entry_points(lib):
     assert lib.islam_pvgo_run_chain_sharded(None, 2, 0, None, None, None, None, None, None, None, 100, None, None, None, 0, None, 0, None, None, None) == -1
 
 
+def test_pose_head_workspace_size_and_argument_checks(lib):
+    """islam_pose_head_workspace_bytes serves B = 1..16 and inputs whose 1/64-size feature map is 2 x 3 (H 65..128, W 129..192); the
+    entry points refuse null pointers and a workspace that is too small before any device call (there is no device here)."""
+    wb = lib.islam_pose_head_workspace_bytes
+    assert wb(1, 65, 129) > 0 and wb(16, 128, 192) > 0
+    for B, H, W in [(0, 112, 160), (0, 65, 129), (17, 112, 160), (17, 128, 192), (2, 64, 160), (2, 129, 193), (2, 112, 193),
+                    (2, 330, 40)]:               # (a 6 x 1 feature map: a level one pixel wide)
+        assert wb(B, H, W) == 0, (B, H, W)
+    for H, W in [(65, 129), (112, 160), (128, 192)]:
+        sizes = [wb(B, H, W) for B in range(1, 17)]
+        assert all(a < b for a, b in zip(sizes, sizes[1:])), (H, W, sizes)
+        assert all(s % 4 == 0 for s in sizes)
+    assert wb(2, 65, 129) < wb(2, 112, 160) < wb(2, 128, 192)
+    assert wb(2, 136, 72) > 0 and wb(2, 40, 330) > 0                 # 3 x 2 and 1 x 6 maps are served
+    EARG = -1
+    B, H, W = 2, 112, 160
+    need = wb(B, H, W)
+    host = (ctypes.c_float * 64)()                                    # stands in for every pointer: the checks below fire before any is followed
+    p = ctypes.cast(host, ctypes.c_void_p)
+    tab = (ctypes.c_void_p * 120)(*[p.value] * 120)
+    ptab = ctypes.cast(tab, ctypes.c_void_p)
+    assert lib.islam_pose_head_forward(p, ptab, p, p, need - 1, B, H, W, None) == EARG
+    msg = lib.islam_last_error()
+    assert b'islam_pose_head_forward' in msg and b'workspace' in msg and str(need).encode() in msg
+    assert lib.islam_pose_head_backward(p, ptab, ptab, p, p, need - 1, B, H, W, 0, None) == EARG
+    assert b'islam_pose_head_backward' in lib.islam_last_error() and b'workspace' in lib.islam_last_error()
+    for args in [(None, ptab, p, p), (p, None, p, p), (p, ptab, p, None)]:
+        assert lib.islam_pose_head_forward(*args, need, B, H, W, None) == EARG
+        assert b'null pointer' in lib.islam_last_error()
+    assert lib.islam_pose_head_backward(None, ptab, ptab, p, p, need, B, H, W, 0, None) == EARG and b'null pointer' in lib.islam_last_error()
+    assert lib.islam_pose_head_backward(p, ptab, ptab, p, None, need, B, H, W, 1, None) == EARG and b'null pointer' in lib.islam_last_error()
+    assert lib.islam_pose_head_forward(p, ptab, p, p, need, 17, H, W, None) == EARG and b'B=17' in lib.islam_last_error()
+    assert lib.islam_pose_head_forward(p, ptab, p, p, need, B, 64, W, None) == EARG and b'64x160' in lib.islam_last_error()
+
+
 def test_level_plan_matches_python_mirror(lib):
     from tests.np_shard_backend import plan_levels
     for N in (1, 2, 9, 40, 41, 64, 100, 257, 1000, 5001, 20000):

@@ -366,6 +366,137 @@ def test_pose_graph_forward_without_backward_is_harmless(cuda):
     torch.cuda.synchronize()
 
 
+def _hip_twins(cuda, seed):
+    """An eager VONet and a twin with the same parameters on graph_pose='hip' (channels-last pose head), both in train mode."""
+    from islam_amd import nets
+    torch.manual_seed(seed)
+    va, vb = nets.VONet(fix_parts=('flow', 'stereo')), nets.VONet(fix_parts=('flow', 'stereo'))
+    vb.load_state_dict(va.state_dict())
+    for v in (va, vb):
+        v.flowPoseNet.to(cuda).train()
+    vb.set_pose_channels_last(True)
+    vb.graph_pose = 'hip'
+    return va, vb
+
+
+def _assert_pose_and_grads_close(pose_b, pose_a, grads_b, grads_a):
+    torch.testing.assert_close(pose_b, pose_a, rtol=1e-3, atol=1e-5)
+    for a, b in zip(grads_b, grads_a):
+        assert a is not None
+        torch.testing.assert_close(a, b, rtol=5e-3, atol=2e-3 * float(b.abs().max()) + 1e-8)
+
+
+def test_pose_head_on_the_hip_kernels_trains_like_eager(cuda):
+    """VONet.graph_pose='hip' (csrc/pose_head.hip, each way one HIP graph replay) against an eager twin: three SGD steps with a second
+    backward onto existing gradients in the middle one, a batch of another size and back, and a step whose gradients are asked for
+    with torch.autograd.grad(loss, [...parameters, pose_graph_leaf()]) as BilevelLoop does."""
+    va, vb = _hip_twins(cuda, 17)
+    opt = [torch.optim.SGD(v.flowPoseNet.parameters(), lr=1e-3) for v in (va, vb)]
+    wts = torch.arange(1, 7, device=cuda, dtype=torch.float32)
+    assert vb.pose_graph_leaf() is None
+    for it, B in enumerate([2, 2, 2, 1, 2, 2]):
+        flow = torch.randn(B, 2, 112, 160, device=cuda)
+        intr = torch.rand(B, 2, 112, 160, device=cuda)
+        frozen = (flow, torch.zeros(B, 1, 112, 160, device=cuda))
+        torch.cuda.synchronize()                                 # a new batch size drops the head's captured graphs: with the device idle
+        poses, grads = [], []
+        for v, o in zip((va, vb), opt):
+            o.zero_grad(set_to_none=(it != 2))
+            _, _, pose = v(None, None, None, None, intr, frozen=frozen)
+            loss = (pose * wts).sum()
+            if it == 5 and v is vb:
+                params = list(v.flowPoseNet.parameters())
+                got = torch.autograd.grad(loss, params + [v.pose_graph_leaf()], allow_unused=True)
+                assert all(g is None for g in got[:-1])         # the node has added them to .grad itself
+            else:
+                loss.backward()
+            if it == 1:                                          # accumulation onto existing gradients
+                _, _, pose2 = v(None, None, None, None, intr, frozen=frozen)
+                (pose2 * wts).sum().backward()
+            poses.append(pose.detach().clone())
+            grads.append([None if p.grad is None else p.grad.detach().clone() for p in v.flowPoseNet.parameters()])
+            o.step()
+        assert vb.pose_graph_leaf() is not None
+        _assert_pose_and_grads_close(poses[1], poses[0], grads[1], grads[0])
+    hh = vb.flowPoseNet.hip_head()
+    assert hh.graphs and hh._key[1:4] == (2, 112, 160) and hh.gen == 7        # every forward of the twin ran on the kernels
+    assert vb._pose_graphed is None
+    assert list(va.state_dict().keys()) == list(vb.state_dict().keys())
+    torch.cuda.synchronize()
+    del va, vb, opt, hh, poses, grads, pose, pose2, loss
+    import gc
+    gc.collect()
+    torch.cuda.synchronize()
+
+
+def test_pose_head_on_the_hip_kernels_with_a_trainable_flow(cuda):
+    """graph_pose='hip' produces no gradient w.r.t. the head's input, so a flow that requires grad takes the eager modules: the flow gets
+    the eager twin's gradient, the head's parameters get theirs, and nothing is captured behind the caller's back."""
+    va, vb = _hip_twins(cuda, 19)
+    wts = torch.arange(1, 7, device=cuda, dtype=torch.float32)
+    B = 2
+    intr = torch.rand(B, 2, 112, 160, device=cuda)
+    z = torch.zeros(B, 1, 112, 160, device=cuda)
+    flow = torch.randn(B, 2, 112, 160, device=cuda)
+    out = []
+    for v in (va, vb):
+        f = flow.clone().requires_grad_(True)
+        _, _, pose = v(None, None, None, None, intr, frozen=(f, z))
+        (pose * wts).sum().backward()
+        out.append((pose.detach().clone(), f.grad, [p.grad for p in v.flowPoseNet.parameters()]))
+    assert out[1][1] is not None, 'the pose loss does not reach the flow'
+    _assert_pose_and_grads_close(out[1][0], out[0][0], [out[1][1]] + out[1][2], [out[0][1]] + out[0][2])
+    assert vb._pose_graphed is None
+    # the next batch with a frozen flow is back on the kernels
+    for v in (va, vb):
+        for p in v.flowPoseNet.parameters():
+            p.grad = None
+    out = []
+    for v in (va, vb):
+        _, _, pose = v(None, None, None, None, intr, frozen=(flow, z))
+        (pose * wts).sum().backward()
+        out.append((pose.detach().clone(), [p.grad for p in v.flowPoseNet.parameters()]))
+    assert vb.pose_graph_leaf() is not None and vb.flowPoseNet.hip_head().gen == 1
+    _assert_pose_and_grads_close(out[1][0], out[0][0], out[1][1], out[0][1])
+    torch.cuda.synchronize()
+    del va, vb, out, pose
+    import gc
+    gc.collect()
+    torch.cuda.synchronize()
+
+
+def test_hip_pose_head_falls_back_to_eager_for_weights_it_cannot_read(cuda):
+    """VOFlowRes.set_hip_head(True) with contiguous (not channels_last) convolution weights and an input the kernels would serve: the
+    module's eager result, differentiable -- not an exception."""
+    from islam_amd import nets
+    torch.manual_seed(23)
+    net = nets.VOFlowRes().to(cuda).train()
+    x = torch.randn(2, 4, 112, 160, device=cuda).contiguous(memory_format=torch.channels_last)
+    gy = torch.randn(2, 6, device=cuda)
+    y0 = net(x)
+    y0.backward(gy)
+    g0 = [p.grad.detach().clone() for p in net.parameters()]
+    for p in net.parameters():
+        p.grad = None
+    net.set_hip_head(True)
+    for rep in range(2):                                         # (the second call meets the remembered refusal)
+        y1 = net(x)
+        assert y1.requires_grad and net.hip_head().gen == 0
+    y1.backward(gy)
+    _assert_pose_and_grads_close(y1.detach(), y0.detach(), [p.grad for p in net.parameters()], g0)
+    with torch.no_grad():
+        torch.testing.assert_close(net(x), y0.detach(), rtol=1e-3, atol=1e-5)
+    # channels_last weights: the same module now runs on the kernels
+    net.to(memory_format=torch.channels_last)
+    for p in net.parameters():
+        p.grad = None
+    y2 = net(x)
+    assert net.hip_head().gen == 1
+    y2.backward(gy)
+    _assert_pose_and_grads_close(y2.detach(), y0.detach(), [p.grad for p in net.parameters()], g0)
+    torch.cuda.synchronize()
+
+
 def test_pose_head_fused_elementwise_tail(cuda):
     """VOFlowRes.set_fused_tail (islam_bias_act_f32_nhwc / _bwd): bias + ReLU (+ shortcut) behind every encoder convolution in one
     launch each way.  Same convolutions on the same inputs: the forward is the same sequence of fp32 additions (bit-equal pose), the
