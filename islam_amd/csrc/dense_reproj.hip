@@ -10,8 +10,9 @@
 // link in fixed order and applies A = Ad(C^-1) once: H = A^T H_cam A, g = A^T g_cam.  No atomics anywhere: a second call gives
 // the same bits.  Under refinement the final kernel's lane 0 also runs the LM bookkeeping of its link (accept test, damping,
 // 6x6 Cholesky in LDS, next trial pose), so an evaluation is two launches and the host never waits between them.
-// Everything of a pixel ahead of the accumulators (reproj_pixel), the reduction epilogue, the final kernel's body, the Cholesky step,
-// the pose decode and the host-side argument checks are shared with dense_ba.hip through dense_reproj_dev.h.
+// The head of the pixel loop (pixel_in), everything of a pixel ahead of the accumulators (reproj_pixel), the reduction epilogue, the
+// final kernel's body, the Cholesky step, the pose decode, the stores of the VJP kernel, the head and tail of the solve kernel and
+// the host-side argument checks are shared with dense_ba.hip through dense_reproj_dev.h.
 // Further down: the gradient of the refined pose in depth and flow (reproj_vjp_kernel, reproj_ift_kernel).
 #include <hip/hip_runtime.h>
 
@@ -29,25 +30,15 @@ __global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* 
                                                                     double* __restrict__ partial, int H, int W, int kind, double delta) {
     const int b = blockIdx.y;
     const int HW = H * W;
-    const Intr in = intr_load(intr4 + 4 * b);
     const SE3<double> Ti = camera_inverse(pose7 + 7 * b, rgb2imu);
     const M3<double> R = qmat(Ti.q);
     const V3<double> t = Ti.t;
-    const double d2 = delta * delta;
 
-    double acc[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) acc[i] = 0.0;
-
-    const float* zp = depth + (size_t)b * HW;
-    const float* fup = flow + (size_t)b * 2 * HW;
-    const float* fvp = fup + HW;
-    const uint8_t* mp = mask ? mask + (size_t)b * HW : nullptr;
+    double acc[NS] = {};
+    const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
-        const int v = i / W, u = i - v * W;
-        const double ud = (double)u, vd = (double)v;
-        const Pixel px = reproj_pixel(R, t, (double)zp[i], (ud - in.cx) / in.fx, (vd - in.cy) / in.fy, (double)fup[i] + ud, (double)fvp[i] + vd,
-                                      mp ? mp[i] != 0 : true, in, kind, delta, d2);
+        const PixelIn pin = pixel_in(lp, i);
+        const Pixel px = reproj_pixel(R, t, pin.z, pin, lp);
         if (!px.valid) continue;
         const double *ju = px.ju, *jv = px.jv;
         int k = 0;
@@ -62,7 +53,7 @@ __global__ __launch_bounds__(256) void dense_reproj_partial_kernel(const float* 
         acc[S_L1] += fabs(px.ru) + fabs(px.rv);
         acc[S_COUNT] += 1.0;
     }
-    reduce_and_store_row(acc, partial + ((size_t)b * NBLK + blockIdx.x) * NS, true);
+    reduce_and_store_row<NS>(acc, partial + ((size_t)b * NBLK + blockIdx.x) * NS, true, NAN);
 }
 
 __global__ __launch_bounds__(64) void dense_reproj_final_kernel(const double* __restrict__ partial, const double* __restrict__ rgb2imu,
@@ -84,31 +75,18 @@ __global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict
                                                           int kind, double delta) {
     const int b = blockIdx.y;
     const int HW = H * W;
-    float* gzp = grad_depth + (size_t)b * HW;
-    float* gup = grad_flow + (size_t)b * 2 * HW;
-    float* gvp = gup + HW;
-    if (status && status[b] != ISLAM_DENSE_REPROJ_OK) {      // a link without a gradient: zeros, whatever its pixels hold
-        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) gzp[i] = gup[i] = gvp[i] = 0.0f;
-        return;
-    }
-    const Intr in = intr_load(intr4 + 4 * b);
+    const LinkGrads out = link_grads(grad_depth, grad_flow, b, HW);
+    if (status && status[b] != ISLAM_DENSE_REPROJ_OK) return grad_zero_link(out, HW);      // a link without a gradient
     const SE3<double> Ti = camera_inverse(pose7 + 7 * b, rgb2imu);
     const M3<double> R = qmat(Ti.q);
     const V3<double> t = Ti.t;
-    const double d2 = delta * delta;
     V3<double> wr{w6[6 * b], w6[6 * b + 1], w6[6 * b + 2]}, wf{w6[6 * b + 3], w6[6 * b + 4], w6[6 * b + 5]};
     adjoint_apply(rgb2imu, wr, wf);      // w_cam = Ad(C^-1) w
 
-    const float* zp = depth + (size_t)b * HW;
-    const float* fup = flow + (size_t)b * 2 * HW;
-    const float* fvp = fup + HW;
-    const uint8_t* mp = mask ? mask + (size_t)b * HW : nullptr;
+    const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
-        const int v = i / W, u = i - v * W;
-        const double ud = (double)u, vd = (double)v;
-        const double xh = (ud - in.cx) / in.fx, yh = (vd - in.cy) / in.fy;
-        const Pixel p = reproj_pixel(R, t, (double)zp[i], xh, yh, (double)fup[i] + ud, (double)fvp[i] + vd, mp ? mp[i] != 0 : true, in, kind,
-                                     delta, d2);
+        const PixelIn pin = pixel_in(lp, i);
+        const Pixel p = reproj_pixel(R, t, pin.z, pin, lp);
         double gz = 0.0, gu = 0.0, gv = 0.0;
         if (p.valid) {
             const V3<double>& Q = p.Q;
@@ -117,7 +95,7 @@ __global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict
             const double qu = a * mm.x + bq * mm.z, qv = cq * mm.y + dq * mm.z;  // q = dr/dQ m
             const double k2 = 2.0 * cp * (qu * ru + qv * rv);
             const double eu = c * qu + k2 * ru, ev = c * qv + k2 * rv;           // e = d(c q.r)/dr
-            const V3<double> dQ = R * V3<double>{xh, yh, 1.0};                   // dQ/dz
+            const V3<double> dQ = R * V3<double>{pin.xh, pin.yh, 1.0};           // dQ/dz
             const double da = -a * iz * dQ.z, dbq = -a * iz * dQ.x - 2.0 * bq * iz * dQ.z;      // d(dr/dQ) along dQ
             const double dcq = -cq * iz * dQ.z, ddq = -cq * iz * dQ.y - 2.0 * dq * iz * dQ.z;
             const V3<double> n = cross(dQ, wf);                                 // dm along dQ
@@ -126,39 +104,25 @@ __global__ __launch_bounds__(256) void reproj_vjp_kernel(const float* __restrict
             gu = -eu;
             gv = -ev;
         }
-        gzp[i] = (float)gz;
-        gup[i] = (float)gu;
-        gvp[i] = (float)gv;
+        grad_store(out, i, gz, gu, gv);
     }
 }
 
-// w = -H^-1 v per link, v = dL/dxi on motion Exp(xi) from the gradient on [t, q xyzw]: v_rho = R^T dL/dt, v_phi = 1/2 E^T dL/dq with
-// E = d(q (x, 1))/dx at 0 = [[q_w I + [q_v]x], [-q_v^T]].  A link that comes with a status, or whose H has a non-positive pivot,
-// gets w = 0.
+// w = -H^-1 v per link, v = dL/dxi on motion Exp(xi) from the gradient on [t, q xyzw] (tangent_gradient).  A link that comes with a
+// status, or whose H has a non-positive pivot, gets w = 0.
 __global__ __launch_bounds__(64) void reproj_ift_kernel(const double* __restrict__ Hm, const double* __restrict__ motion,
                                                          const double* __restrict__ grad_motion, const int* __restrict__ status_in,
                                                          double* __restrict__ w, int* __restrict__ status_out) {
     const int b = blockIdx.x, i = threadIdx.x;
     __shared__ double Hn[36], vn[6], L[6][6], x[6];
-    __shared__ int st;
     if (i < 36) Hn[i] = Hm[(size_t)b * 36 + i];
     if (i == 0) {
-        const SE3<double> X = se3_load(motion + (size_t)b * 7);
-        const double* gm = grad_motion + (size_t)b * 7;
-        const V3<double> vr = tmul(qmat(X.q), v3(gm[0], gm[1], gm[2]));
-        const V3<double> qv{X.q.x, X.q.y, X.q.z}, gq{gm[3], gm[4], gm[5]};
-        const V3<double> vf = 0.5 * (X.q.w * gq - cross(qv, gq) - gm[6] * qv);
+        V3<double> vr, vf;
+        tangent_gradient(motion + (size_t)b * 7, grad_motion + (size_t)b * 7, vr, vf);
         vn[0] = vr.x; vn[1] = vr.y; vn[2] = vr.z; vn[3] = vf.x; vn[4] = vf.y; vn[5] = vf.z;
     }
     __syncthreads();
-    if (i == 0) {
-        int s = status_in ? status_in[b] : ISLAM_DENSE_REPROJ_OK;
-        if (s == ISLAM_DENSE_REPROJ_OK && !lm_step(Hn, vn, 0.0, L, x)) s = ISLAM_DENSE_REPROJ_NOTPD;
-        st = s;
-        status_out[b] = s;
-    }
-    __syncthreads();
-    if (i < 6) w[(size_t)b * 6 + i] = st == ISLAM_DENSE_REPROJ_OK ? x[i] : 0.0;
+    adjoint_solve_tail(status_in ? status_in[b] : ISLAM_DENSE_REPROJ_OK, Hn, vn, L, x, status_out + b, w + (size_t)b * 6);
 }
 
 }  // namespace

@@ -1,9 +1,11 @@
-// What the two dense reprojection files share (dense_reproj.hip: DESIGN.md sections 3.23 / 3.24; dense_ba.hip: section 3.25).  On the
-// device: the camera-frame pose of a link, the per-pixel front of the three pixel kernels (reproj_pixel: back-projection, T^-1, the
-// validity clauses, the residual, the robust kernel, dr/dQ and the rows of J_cam; robust_terms), Ad(C^-1) on a 6-vector, the reduction
-// epilogue of the two partial kernels, the 6x6 damped Cholesky step, and the body of the per-link final kernel -- the fixed-order
-// sum of the NBLK workgroup rows, A = Ad(C^-1) applied once, and under refinement the LM bookkeeping of the link on lane 0.  On the
-// host: the argument checks of the entry points and the size of the partial-sum scratch.
+// What the two dense reprojection files share (dense_reproj.hip: DESIGN.md sections 3.23 / 3.24; dense_ba.hip: sections 3.25 / 3.26).
+// On the device: the camera-frame pose of a link, Ad(C^-1) and its transpose on a 6-vector, the head of the pixel loop (LinkPixels,
+// pixel_in: the link's base pointers, u / v, the ray, the flow target, the mask byte), the per-pixel front of the five pixel kernels
+// (reproj_pixel: back-projection, T^-1, the validity clauses, the residual, the robust kernel, dr/dQ and the rows of J_cam;
+// robust_terms), the stores of the two VJP kernels (LinkGrads), the reduction epilogue of the three partial kernels, the 6x6 damped
+// Cholesky step, the head and the tail of the two adjoint solve kernels (tangent_gradient, adjoint_solve_tail), and the body of the
+// per-link final kernel -- the fixed-order sum of the NBLK workgroup rows, A = Ad(C^-1) applied once, and under refinement the LM
+// bookkeeping of the link on lane 0.  On the host: the argument checks of the entry points and the size of the partial-sum scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,13 +31,27 @@ ISLAM_DEV SE3<double> camera_inverse(const double* pose7, const double* rgb2imu)
     return se3_inv(T);
 }
 
-// C^-1 applied to a body-frame 6-vector, in place: Ad(C^-1) [rho; phi] = [R_c rho + t_c x (R_c phi); R_c phi]
+// C^-1 applied to a body-frame 6-vector, in place: Ad(C^-1) [rho; phi] = [R_c rho + t_c x (R_c phi); R_c phi].  TRANSPOSE: its
+// transpose on a camera-frame 6-vector, Ad(C^-1)^T [rho; phi] = [R_c^T rho; R_c^T (phi - t_c x rho)]
+template <bool TRANSPOSE = false>
 ISLAM_DEV void adjoint_apply(const double* rgb2imu, V3<double>& rho3, V3<double>& phi3) {
     if (!rgb2imu) return;
     const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
     const M3<double> Rc = qmat(Ci.q);
-    phi3 = Rc * phi3;
-    rho3 = Rc * rho3 + cross(Ci.t, phi3);
+    if constexpr (TRANSPOSE) {
+        phi3 = tmul(Rc, phi3 - cross(Ci.t, rho3));
+        rho3 = tmul(Rc, rho3);
+    } else {
+        phi3 = Rc * phi3;
+        rho3 = Rc * rho3 + cross(Ci.t, phi3);
+    }
+}
+
+// a body-frame 6-vector into the camera frame: dst6 = Ad(C^-1) src6 (one thread; dst6 is LDS in the joint kernels)
+ISLAM_DEV void adjoint_to_camera(const double* rgb2imu, const double* src6, double* dst6) {
+    V3<double> r{src6[0], src6[1], src6[2]}, f{src6[3], src6[4], src6[5]};
+    adjoint_apply(rgb2imu, r, f);
+    dst6[0] = r.x; dst6[1] = r.y; dst6[2] = r.z; dst6[3] = f.x; dst6[4] = f.y; dst6[5] = f.z;
 }
 
 // The robust kernel at s = |r|^2: rho(s), c = rho'(s), cp = dc/ds.  The one place the Huber / Cauchy branches live; what a caller
@@ -65,6 +81,36 @@ struct Intr {
 
 ISLAM_DEV Intr intr_load(const double* intr4) { return {intr4[0], intr4[1], intr4[2], intr4[3]}; }
 
+// The head of the pixel loop.  LinkPixels: link b as the pixel kernels see it -- where its depth, flow and mask lie, its intrinsics and
+// the robust kernel; PixelIn: pixel i as the front takes it -- the stored depth z, the ray (xh, yh, 1), (tu, tv) = where the flow says
+// the pixel went, and m = the user mask.
+struct LinkPixels {
+    const float *z, *fu, *fv;
+    const uint8_t* m;      // nullptr: no mask
+    Intr in;
+    int W, kind;
+    double delta, d2;
+};
+
+ISLAM_DEV LinkPixels link_pixels(const float* depth, const float* flow, const uint8_t* mask, const double* intr4, int b, int HW, int W,
+                                 int kind, double delta) {
+    const size_t off = (size_t)b * HW;
+    const float* fu = flow + 2 * off;
+    return {depth + off, fu, fu + HW, mask ? mask + off : nullptr, intr_load(intr4 + 4 * b), W, kind, delta, delta * delta};
+}
+
+struct PixelIn {
+    double z, xh, yh, tu, tv;
+    bool m;
+};
+
+ISLAM_DEV PixelIn pixel_in(const LinkPixels& lp, int i) {
+    const int v = i / lp.W, u = i - v * lp.W;
+    const double ud = (double)u, vd = (double)v;
+    return {(double)lp.z[i], (ud - lp.in.cx) / lp.in.fx, (vd - lp.in.cy) / lp.in.fy, (double)lp.fu[i] + ud, (double)lp.fv[i] + vd,
+            lp.m ? lp.m[i] != 0 : true};
+}
+
 // one pixel at T^-1 = (R, t): everything ahead of the accumulators.  dr/dQ = [[a, 0, bq], [0, cq, dq]], iz = 1 / Q_z, and ju, jv: the
 // two rows of J_cam = dr/dQ [-I, [Q]x]
 struct Pixel {
@@ -74,21 +120,20 @@ struct Pixel {
     double iz, a, bq, cq, dq, ju[6], jv[6];
 };
 
-// The per-pixel front.  z: the depth along the ray (xh, yh, 1); (tu, tv): where the flow says the pixel went; m: the user mask.
-// Straight-line: an invalid pixel carries numbers nobody may use; what a caller does not read (the rows in the gradient kernel)
-// falls away once this is inlined.
-ISLAM_DEV Pixel reproj_pixel(const M3<double>& R, const V3<double>& t, double z, double xh, double yh, double tu, double tv, bool m,
-                             const Intr& in, int kind, double delta, double d2) {
+// The per-pixel front.  z: the depth along the ray of q (q.z, or 1 / rho in the joint kernels).  Straight-line: an invalid pixel carries
+// numbers nobody may use; what a caller does not read (the rows in the gradient kernel) falls away once this is inlined.
+ISLAM_DEV Pixel reproj_pixel(const M3<double>& R, const V3<double>& t, double z, const PixelIn& q, const LinkPixels& lp) {
     Pixel p;
-    const V3<double> P{z * xh, z * yh, z};
+    const Intr& in = lp.in;
+    const V3<double> P{z * q.xh, z * q.yh, z};
     p.Q = R * P + t;
-    p.valid = m && p.Q.z > 0.1;
+    p.valid = q.m && p.Q.z > 0.1;
     const double px = p.Q.x / p.Q.z, py = p.Q.y / p.Q.z;
     p.valid = p.valid && fabs(px) <= 1.0 && fabs(py) <= 1.0;
-    p.ru = in.fx * px + in.cx - tu;
-    p.rv = in.fy * py + in.cy - tv;
+    p.ru = in.fx * px + in.cx - q.tu;
+    p.rv = in.fy * py + in.cy - q.tv;
     p.s = p.ru * p.ru + p.rv * p.rv;
-    robust_terms(kind, delta, d2, p.s, p.rob, p.c, p.cp);
+    robust_terms(lp.kind, lp.delta, lp.d2, p.s, p.rob, p.c, p.cp);
     // dr/dQ in locals and the rows right here, not in a function of their own: with either the compiler contracts the sums over
     // column 2 of J_cam (-bq, -dq) into other FMAs, and the joint kernel's last bits move
     const V3<double>& Q = p.Q;
@@ -100,36 +145,41 @@ ISLAM_DEV Pixel reproj_pixel(const M3<double>& R, const V3<double>& t, double z,
     return p;
 }
 
-// The epilogue of a partial kernel (256 threads): the workgroup's sum of every accumulator, one row of NS by plain stores.
-// ok = false stores NaN, which the final kernel reports.
-ISLAM_DEV void reduce_and_store_row(const double* acc, double* __restrict__ row, bool ok) {
-    __shared__ double red[4][NS];
+// Where a VJP kernel writes the gradients of link b: three float stores per pixel, and zeros over the whole link for one without a
+// gradient, whatever its pixels hold.
+struct LinkGrads {
+    float *z, *u, *v;
+};
+
+ISLAM_DEV LinkGrads link_grads(float* grad_depth, float* grad_flow, int b, int HW) {
+    const size_t off = (size_t)b * HW;
+    float* gu = grad_flow + 2 * off;
+    return {grad_depth + off, gu, gu + HW};
+}
+
+ISLAM_DEV void grad_store(const LinkGrads& g, int i, double gz, double gu, double gv) {
+    g.z[i] = (float)gz; g.u[i] = (float)gu; g.v[i] = (float)gv;
+}
+
+ISLAM_DEV void grad_zero_link(const LinkGrads& g, int HW) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) g.z[i] = g.u[i] = g.v[i] = 0.0f;
+}
+
+// The epilogue of a partial kernel (256 threads): the workgroup's sum of every accumulator, one row of N by plain stores.
+// ok = false stores bad: NaN, which the final kernel reports (the sums), or 0 (the adjoint's row of six, section 3.26).
+template <int N>
+ISLAM_DEV void reduce_and_store_row(const double* acc, double* __restrict__ row, bool ok, double bad) {
+    __shared__ double red[4][N];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int i = 0; i < NS; ++i) {
+    for (int i = 0; i < N; ++i) {
         double x = acc[i];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
         if (lane == 0) red[wv][i] = x;
     }
     __syncthreads();
-    if (threadIdx.x < NS) row[threadIdx.x] = ok ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : NAN;
-}
-
-// The same epilogue for a row of six (joint_adj_partial_kernel, section 3.26).  A sibling and not a row-length argument of the function
-// above: that one's instructions stay as they are.  ok = false stores zeros.
-ISLAM_DEV void reduce_and_store_row6(const double* acc, double* __restrict__ row, bool ok) {
-    __shared__ double red6[4][6];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double x = acc[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) red6[wv][i] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) row[threadIdx.x] = ok ? red6[0][threadIdx.x] + red6[1][threadIdx.x] + red6[2][threadIdx.x] + red6[3][threadIdx.x] : 0.0;
+    if (threadIdx.x < N) row[threadIdx.x] = ok ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : bad;
 }
 
 // what the final kernel writes per link; under refinement these arrays ARE the link's current state
@@ -188,6 +238,28 @@ ISLAM_DEV bool lm_step(const double* Hn, const double* gn, double lambda, double
         x[i] = v / L[i][i];
     }
     return true;
+}
+
+// A loss's gradient on [t, q xyzw] in the right tangent of the pose, v = dL/dxi on motion Exp(xi): v_rho = R^T dL/dt, v_phi = 1/2 E^T dL/dq
+// with E = d(q (x, 1))/dx at 0 = [[q_w I + [q_v]x], [-q_v^T]]
+ISLAM_DEV void tangent_gradient(const double* motion7, const double* gm, V3<double>& vr, V3<double>& vf) {
+    const SE3<double> X = se3_load(motion7);
+    vr = tmul(qmat(X.q), v3(gm[0], gm[1], gm[2]));
+    const V3<double> qv{X.q.x, X.q.y, X.q.z}, gq{gm[3], gm[4], gm[5]};
+    vf = 0.5 * (X.q.w * gq - cross(qv, gq) - gm[6] * qv);
+}
+
+// The tail of an adjoint solve kernel (64 threads; Hn, vn, L, x in LDS, vn written by lane 0 or ahead of a barrier): x = -Hn^-1 vn for
+// a link that comes with s = OK, the link's status out, and its row of six -- zeros for a link with a status or a non-positive pivot.
+ISLAM_DEV void adjoint_solve_tail(int s, const double* Hn, const double* vn, double (*L)[6], double* x, int* status_out, double* row) {
+    __shared__ int st;
+    if (threadIdx.x == 0) {
+        if (s == ISLAM_DENSE_REPROJ_OK && !lm_step(Hn, vn, 0.0, L, x)) s = ISLAM_DENSE_REPROJ_NOTPD;
+        st = s;
+        *status_out = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) row[threadIdx.x] = st == ISLAM_DENSE_REPROJ_OK ? x[threadIdx.x] : 0.0;
 }
 
 // The final kernel of a link: one 64-lane workgroup.  JOINT = false is dense_reproj_final_kernel as section 3.23 describes it;
@@ -328,6 +400,17 @@ inline int check_common(const char* who, const float* depth, const float* flow, 
     if (!depth || !flow || !motion || !intr4 || !o.H || !o.g || !o.cost || !o.l1 || !o.count || !o.sums || !scratch)
         return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 / output / scratch pointer", who);
     if (!prior_ok) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    return ISLAM_OK;
+}
+
+// what the two entry points of the joint adjoint (section 3.26) share; lambda_p is an output of one and an input of the other
+inline int check_joint_adjoint(const char* who, const float* depth, const float* flow, const double* motion, const double* intr4,
+                               const double* prior_weight, const double* inv_depth, const double* lambda_p, int kind, double delta, int B,
+                               int H, int W) {
+    if (int rc = check_shape_kind(who, B, H, W, kind, delta)) return rc;
+    if (!depth || !flow || !motion || !intr4) return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 pointer", who);
+    if (!prior_weight) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    if (!inv_depth || !lambda_p) return fail(ISLAM_EARG, "%s: NULL inv_depth / lambda_p pointer", who);
     return ISLAM_OK;
 }
 

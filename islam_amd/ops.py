@@ -159,8 +159,16 @@ DenseReprojNormal = collections.namedtuple('DenseReprojNormal', 'H g cost l1 cou
 DenseReprojRefined = collections.namedtuple('DenseReprojRefined', 'motion H g cost l1 count sums damping accepted rejected status trace')
 
 
+class _DenseArgs(collections.namedtuple('_DenseArgs', 'dev B H W depth flow mask motion intr rgb2imu kind delta')):
+    """What _dense_reproj_args prepared: the device tensors and scalars every entry point of the family takes."""
+
+    def head(self):
+        """The six pointers every entry point starts with."""
+        return ptr(self.depth), ptr(self.flow), ptr(self.mask), ptr(self.motion), ptr(self.rgb2imu), ptr(self.intr)
+
+
 def _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel):
-    """The device tensors and scalars both entry points take (include/islam_hip.h, "dense reprojection")."""
+    """The device tensors and scalars every entry point takes (include/islam_hip.h, "dense reprojection"), as one _DenseArgs."""
     from . import lietensor as pp
     from .robust import NONE, _Kernel
     require_cuda(depth, flow)
@@ -189,7 +197,7 @@ def _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel):
     if kernel is not None and not isinstance(kernel, _Kernel):
         raise ValueError('dense_reproj: kernel must be None, Huber(delta) or Cauchy(delta) (got %r)' % (kernel,))
     kind, delta = (NONE, 1.0) if kernel is None else (kernel.kind, kernel.delta)
-    return dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta
+    return _DenseArgs(dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta)
 
 
 def _dense_reproj_outputs(B, dev):
@@ -207,17 +215,26 @@ def _dense_lm_outputs(B, dev, trace_cap):
     return pose, lam, acc, rej, status, trace
 
 
+def _dense_grad_outputs(a):
+    """What a VJP entry point fills: (grad_depth (B,H,W), grad_flow (B,2,H,W)), float32."""
+    return (torch.empty((a.B, a.H, a.W), dtype=torch.float32, device=a.dev), torch.empty((a.B, 2, a.H, a.W), dtype=torch.float32, device=a.dev))
+
+
+def _dense_ift_outputs(B, dev):
+    """What an ift_weights entry point fills: (the link's row of six (B,6) float64, status (B) int32)."""
+    return torch.empty((B, 6), dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+
+
 def dense_reproj_normal(depth, flow, mask, motion, intr, rgb2imu=None, kernel=None):
     """Gauss-Newton normal equations of the dense reprojection residual per link (include/islam_hip.h, "dense reprojection";
     DESIGN.md section 3.23).  depth (B,H,W), flow (B,2,H,W), mask (B,H,W) or None, motion (B,7) SE3 [t, q], intr (4) or (B,4) =
     fx, fy, cx, cy, rgb2imu (7) or None, kernel None / robust.Huber / robust.Cauchy.  Returns DenseReprojNormal(H (B,6,6), g (B,6),
     cost, l1, count (B), sums (B,30)), float64 on the device; nothing is read back."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    out = _dense_reproj_outputs(B, dev)
-    scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(B, 0), dtype=torch.uint8, device=dev)
-    check(lib().islam_dense_reproj_normal(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), kind, delta,
-                                          ptr(out.H), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums),
-                                          ptr(scratch), B, H, W, stream_ptr(dev)))
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    out = _dense_reproj_outputs(a.B, a.dev)
+    scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(a.B, 0), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_reproj_normal(*a.head(), a.kind, a.delta, ptr(out.H), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count),
+                                          ptr(out.sums), ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
     return out
 
 
@@ -227,15 +244,18 @@ def dense_reproj_refine(depth, flow, mask, motion, intr, rgb2imu=None, kernel=No
     min_count: fewest valid pixels a pose may have.  Returns DenseReprojRefined: motion (B,7) and H, g, cost, l1, count, sums at it,
     damping (B), accepted, rejected, status (B) int32 (0, or _lib.DENSE_REPROJ_FEW / _NOTPD: that link's pose came back as it
     stood) and trace (trace_cap,B) = the mean cost of each evaluation (None for trace_cap = 0)."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    return _dense_reproj_refine_launch(_dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel), iters, damping, min_count, trace_cap)
+
+
+def _dense_reproj_refine_launch(a, iters, damping, min_count, trace_cap):
+    """islam_dense_reproj_refine on what _dense_reproj_args prepared."""
     iters, trace_cap = int(iters), int(trace_cap)
-    out = _dense_reproj_outputs(B, dev)
-    pose, lam, acc, rej, status, trace = _dense_lm_outputs(B, dev, trace_cap)
-    scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(B, max(iters, 1)), dtype=torch.uint8, device=dev)
-    check(lib().islam_dense_reproj_refine(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), kind, delta, iters,
-                                          float(damping), float(min_count), ptr(pose), ptr(out.H), ptr(out.g), ptr(out.cost),
-                                          ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc), ptr(rej), ptr(status),
-                                          ptr(trace), trace_cap, ptr(scratch), B, H, W, stream_ptr(dev)))
+    out = _dense_reproj_outputs(a.B, a.dev)
+    pose, lam, acc, rej, status, trace = _dense_lm_outputs(a.B, a.dev, trace_cap)
+    scratch = torch.empty(lib().islam_dense_reproj_scratch_bytes(a.B, max(iters, 1)), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_reproj_refine(*a.head(), a.kind, a.delta, iters, float(damping), float(min_count), ptr(pose), ptr(out.H),
+                                          ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc), ptr(rej),
+                                          ptr(status), ptr(trace), trace_cap, ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
     return DenseReprojRefined(pose, *out, lam, acc, rej, status, trace)
 
 
@@ -264,18 +284,15 @@ def dense_ba_normal(depth, flow, mask, motion, intr, prior_weight, inv_depth=Non
     positive number or (B,)) = sigma_px^2 / sigma_inv_depth^2 and inv_depth (B,H,W) float64, the state's inverse depths (None: the
     prior 1/depth).  Returns DenseBANormal(S (B,6,6), g (B,6), cost, l1, count (B), sums (B,30)), float64 on the device; nothing is
     read back."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    w = _dense_ba_prior_weight(prior_weight, B, dev)
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
     if inv_depth is not None:
         require_cuda(inv_depth)
-        if tuple(inv_depth.shape) != (B, H, W):
-            raise ValueError('dense_ba: inv_depth must be (%d,%d,%d), got %s' % (B, H, W, tuple(inv_depth.shape)))
-        inv_depth = inv_depth.detach().to(torch.float64).contiguous()
-    out = DenseBANormal(*_dense_reproj_outputs(B, dev))
-    scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(B, H, W, 0), dtype=torch.uint8, device=dev)
-    check(lib().islam_dense_ba_normal(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), ptr(inv_depth),
-                                      kind, delta, ptr(out.S), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums),
-                                      ptr(scratch), B, H, W, stream_ptr(dev)))
+        inv_depth = _dense_ba_state(inv_depth, a, 'dense_ba')
+    out = DenseBANormal(*_dense_reproj_outputs(a.B, a.dev))
+    scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(a.B, a.H, a.W, 0), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_ba_normal(*a.head(), ptr(w), ptr(inv_depth), a.kind, a.delta, ptr(out.S), ptr(out.g), ptr(out.cost), ptr(out.l1),
+                                      ptr(out.count), ptr(out.sums), ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
     return out
 
 
@@ -285,17 +302,20 @@ def dense_ba_refine(depth, flow, mask, motion, intr, prior_weight, rgb2imu=None,
     (include/islam_hip.h, islam_dense_ba_refine).  Arguments as dense_reproj_refine plus prior_weight (see dense_ba_normal).  Returns
     DenseBARefined: motion (B,7), inv_depth (B,H,W) float64 (0 where the depth gives no prior) and S, g, cost, l1, count, sums at
     them, damping, accepted, rejected, status (B) int32 (0, or _lib.DENSE_REPROJ_FEW / _NOTPD / _BADPRIOR) and trace."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    w = _dense_ba_prior_weight(prior_weight, B, dev)
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    return _dense_ba_refine_launch(a, _dense_ba_prior_weight(prior_weight, a.B, a.dev), iters, damping, min_count, trace_cap)
+
+
+def _dense_ba_refine_launch(a, w, iters, damping, min_count, trace_cap):
+    """islam_dense_ba_refine on what _dense_reproj_args and _dense_ba_prior_weight prepared."""
     iters, trace_cap = int(iters), int(trace_cap)
-    out = _dense_reproj_outputs(B, dev)
-    pose, lam, acc, rej, status, trace = _dense_lm_outputs(B, dev, trace_cap)
-    rho = torch.empty((B, H, W), dtype=torch.float64, device=dev)
-    scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(B, H, W, max(iters, 1)), dtype=torch.uint8, device=dev)
-    check(lib().islam_dense_ba_refine(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), kind, delta, iters,
-                                      float(damping), float(min_count), ptr(pose), ptr(rho), ptr(out.H), ptr(out.g), ptr(out.cost),
-                                      ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc), ptr(rej), ptr(status),
-                                      ptr(trace), trace_cap, ptr(scratch), B, H, W, stream_ptr(dev)))
+    out = _dense_reproj_outputs(a.B, a.dev)
+    pose, lam, acc, rej, status, trace = _dense_lm_outputs(a.B, a.dev, trace_cap)
+    rho = torch.empty((a.B, a.H, a.W), dtype=torch.float64, device=a.dev)
+    scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(a.B, a.H, a.W, max(iters, 1)), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_ba_refine(*a.head(), ptr(w), a.kind, a.delta, iters, float(damping), float(min_count), ptr(pose), ptr(rho),
+                                      ptr(out.H), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc),
+                                      ptr(rej), ptr(status), ptr(trace), trace_cap, ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
     return DenseBARefined(pose, rho, *out, lam, acc, rej, status, trace)
 
 
@@ -313,20 +333,18 @@ def dense_reproj_vjp(depth, flow, mask, motion, intr, w, rgb2imu=None, kernel=No
     held fixed (include/islam_hip.h, islam_dense_reproj_vjp).  Arguments as dense_reproj_normal; w (B,6)
     body frame [rho, phi]; status (B) int or None: a link whose status is not 0 gets zeros.  Returns (grad_depth (B,H,W),
     grad_flow (B,2,H,W)), float32 on the device, exactly 0 at every invalid pixel; one launch, nothing is read back."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    w = torch.as_tensor(w).detach().to(dev, torch.float64).contiguous()
-    if tuple(w.shape) != (B, 6):
-        raise ValueError('dense_reproj_vjp: w must be (%d,6) [rho, phi], got %s' % (B, tuple(w.shape)))
-    return _dense_reproj_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, kind, delta, w, _dense_reproj_status(status, B, dev))
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = torch.as_tensor(w).detach().to(a.dev, torch.float64).contiguous()
+    if tuple(w.shape) != (a.B, 6):
+        raise ValueError('dense_reproj_vjp: w must be (%d,6) [rho, phi], got %s' % (a.B, tuple(w.shape)))
+    return _dense_reproj_vjp_launch(a, w, _dense_reproj_status(status, a.B, a.dev))
 
 
-def _dense_reproj_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, kind, delta, w, status):
-    """islam_dense_reproj_vjp on tensors _dense_reproj_args has prepared."""
-    B, H, W = depth.shape
-    grad_depth = torch.empty((B, H, W), dtype=torch.float32, device=depth.device)
-    grad_flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=depth.device)
-    check(lib().islam_dense_reproj_vjp(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), B, H, W, kind, delta,
-                                       ptr(w), ptr(status), ptr(grad_depth), ptr(grad_flow), stream_ptr(depth.device)))
+def _dense_reproj_vjp_launch(a, w, status):
+    """islam_dense_reproj_vjp on what _dense_reproj_args prepared."""
+    grad_depth, grad_flow = _dense_grad_outputs(a)
+    check(lib().islam_dense_reproj_vjp(*a.head(), a.B, a.H, a.W, a.kind, a.delta, ptr(w), ptr(status), ptr(grad_depth), ptr(grad_flow),
+                                       stream_ptr(a.dev)))
     return grad_depth, grad_flow
 
 
@@ -351,8 +369,7 @@ def dense_reproj_ift_weights(H, motion, grad_motion, status=None):
 def _dense_reproj_ift_launch(H, motion, grad_motion, status):
     """islam_dense_reproj_ift_weights on contiguous float64 device tensors."""
     B, dev = H.shape[0], H.device
-    w = torch.empty((B, 6), dtype=torch.float64, device=dev)
-    out = torch.empty(B, dtype=torch.int32, device=dev)
+    w, out = _dense_ift_outputs(B, dev)
     check(lib().islam_dense_reproj_ift_weights(ptr(H), ptr(motion), ptr(grad_motion), ptr(status), B, ptr(w), ptr(out), stream_ptr(dev)))
     return w, out
 
@@ -364,27 +381,27 @@ class _DenseReprojRefine(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, depth, flow, mask, motion, intr, rgb2imu, kernel, iters, damping, min_count, trace_cap):
-        dev, B, H, W, depth32, flow32, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-        out = dense_reproj_refine(depth32, flow32, mask, motion, intr, rgb2imu=rgb2imu, kernel=kernel, iters=iters, damping=damping,
-                                  min_count=min_count, trace_cap=trace_cap)
-        ctx.save_for_backward(depth32, flow32, mask, out.motion, out.H, out.status, intr, rgb2imu)
-        ctx.kind, ctx.delta, ctx.dtypes = kind, delta, (depth.dtype, flow.dtype)
+        a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+        out = _dense_reproj_refine_launch(a, iters, damping, min_count, trace_cap)
+        ctx.save_for_backward(a.depth, a.flow, a.mask, out.motion, out.H, out.status, a.intr, a.rgb2imu)
+        ctx.kind, ctx.delta, ctx.dtypes = a.kind, a.delta, (depth.dtype, flow.dtype)
         ctx.mark_non_differentiable(*(t for t in out[1:] if t is not None))
         return tuple(out)
 
     @staticmethod
     def backward(ctx, grad_motion, *unused):
         depth, flow, mask, motion, H, status, intr, rgb2imu = ctx.saved_tensors
+        a = _DenseArgs(depth.device, *depth.shape, depth, flow, mask, motion, intr, rgb2imu, ctx.kind, ctx.delta)      # at the refined pose
         w, status = _dense_reproj_ift_launch(H, motion, grad_motion.to(torch.float64).contiguous(), status)
-        grad_depth, grad_flow = _dense_reproj_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, ctx.kind, ctx.delta, w, status)
+        grad_depth, grad_flow = _dense_reproj_vjp_launch(a, w, status)
         return (grad_depth.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None, grad_flow.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None,
                 None, None, None, None, None, None, None, None, None)
 
 
-def _dense_ba_state(inv_depth, B, H, W, dev, who, name='inv_depth'):
-    if tuple(inv_depth.shape) != (B, H, W):
-        raise ValueError('%s: %s must be (%d,%d,%d), got %s' % (who, name, B, H, W, tuple(inv_depth.shape)))
-    return inv_depth.detach().to(dev, torch.float64).contiguous()
+def _dense_ba_state(inv_depth, a, who, name='inv_depth'):
+    if tuple(inv_depth.shape) != (a.B, a.H, a.W):
+        raise ValueError('%s: %s must be (%d,%d,%d), got %s' % (who, name, a.B, a.H, a.W, tuple(inv_depth.shape)))
+    return inv_depth.detach().to(a.dev, torch.float64).contiguous()
 
 
 def dense_ba_ift_weights(depth, flow, mask, motion, intr, prior_weight, inv_depth, S, grad_motion, grad_inv_depth=None, rgb2imu=None,
@@ -395,30 +412,25 @@ def dense_ba_ift_weights(depth, flow, mask, motion, intr, prior_weight, inv_dept
     the reduction of u_cam).  Other arguments as dense_ba_normal; status (B) int or None: the refinement's status.  Returns
     (lambda_p float64, status (B) int32): a link with an incoming status, a prior weight that is not > 0 (_lib.DENSE_REPROJ_BADPRIOR)
     or an S that is not positive definite (_NOTPD) has lambda_p = 0.  One or two launches, nothing is read back."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    w = _dense_ba_prior_weight(prior_weight, B, dev)
-    rho = _dense_ba_state(inv_depth, B, H, W, dev, 'dense_ba_ift_weights')
-    f64 = lambda t: torch.as_tensor(t).detach().to(dev, torch.float64).contiguous()
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+    rho = _dense_ba_state(inv_depth, a, 'dense_ba_ift_weights')
+    f64 = lambda t: torch.as_tensor(t).detach().to(a.dev, torch.float64).contiguous()
     S, grad_motion = f64(S), f64(grad_motion)
-    if tuple(S.shape) != (B, 6, 6) or tuple(grad_motion.shape) != (B, 7):
+    if tuple(S.shape) != (a.B, 6, 6) or tuple(grad_motion.shape) != (a.B, 7):
         raise ValueError('dense_ba_ift_weights: S must be (%d,6,6) and grad_motion (%d,7), got %s and %s' % (
-            B, B, tuple(S.shape), tuple(grad_motion.shape)))
+            a.B, a.B, tuple(S.shape), tuple(grad_motion.shape)))
     if grad_inv_depth is not None:
-        grad_inv_depth = _dense_ba_state(grad_inv_depth, B, H, W, dev, 'dense_ba_ift_weights', 'grad_inv_depth')
-    return _dense_ba_ift_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, S, grad_motion, grad_inv_depth,
-                                _dense_reproj_status(status, B, dev))
+        grad_inv_depth = _dense_ba_state(grad_inv_depth, a, 'dense_ba_ift_weights', 'grad_inv_depth')
+    return _dense_ba_ift_launch(a, w, rho, S, grad_motion, grad_inv_depth, _dense_reproj_status(status, a.B, a.dev))
 
 
-def _dense_ba_ift_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, S, grad_motion, grad_rho, status):
-    """islam_dense_ba_ift_weights on tensors _dense_reproj_args has prepared."""
-    B, H, W = depth.shape
-    dev = depth.device
-    lam = torch.empty((B, 6), dtype=torch.float64, device=dev)
-    out = torch.empty(B, dtype=torch.int32, device=dev)
-    scratch = torch.empty(lib().islam_dense_ba_adjoint_scratch_bytes(B), dtype=torch.uint8, device=dev)
-    check(lib().islam_dense_ba_ift_weights(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), ptr(rho), kind,
-                                           delta, ptr(S), ptr(grad_motion), ptr(grad_rho), ptr(status), ptr(scratch), B, H, W, ptr(lam),
-                                           ptr(out), stream_ptr(dev)))
+def _dense_ba_ift_launch(a, w, rho, S, grad_motion, grad_rho, status):
+    """islam_dense_ba_ift_weights on what _dense_reproj_args prepared."""
+    lam, out = _dense_ift_outputs(a.B, a.dev)
+    scratch = torch.empty(lib().islam_dense_ba_adjoint_scratch_bytes(a.B), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_ba_ift_weights(*a.head(), ptr(w), ptr(rho), a.kind, a.delta, ptr(S), ptr(grad_motion), ptr(grad_rho),
+                                           ptr(status), ptr(scratch), a.B, a.H, a.W, ptr(lam), ptr(out), stream_ptr(a.dev)))
     return lam, out
 
 
@@ -429,26 +441,22 @@ def dense_ba_vjp(depth, flow, mask, motion, intr, prior_weight, inv_depth, lambd
     per pixel lambda_d, then dL/dflow = -(c q + 2 c' (q.r) r) and dL/ddepth = w lambda_d / depth^2.  Other arguments as
     dense_ba_normal; status (B) int or None: a link whose status is not 0 gets zeros.  Returns (grad_depth (B,H,W), grad_flow
     (B,2,H,W)), float32 on the device; one launch, nothing is read back."""
-    dev, B, H, W, depth, flow, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    w = _dense_ba_prior_weight(prior_weight, B, dev)
-    rho = _dense_ba_state(inv_depth, B, H, W, dev, 'dense_ba_vjp')
-    lambda_p = torch.as_tensor(lambda_p).detach().to(dev, torch.float64).contiguous()
-    if tuple(lambda_p.shape) != (B, 6):
-        raise ValueError('dense_ba_vjp: lambda_p must be (%d,6) [rho, phi], got %s' % (B, tuple(lambda_p.shape)))
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+    rho = _dense_ba_state(inv_depth, a, 'dense_ba_vjp')
+    lambda_p = torch.as_tensor(lambda_p).detach().to(a.dev, torch.float64).contiguous()
+    if tuple(lambda_p.shape) != (a.B, 6):
+        raise ValueError('dense_ba_vjp: lambda_p must be (%d,6) [rho, phi], got %s' % (a.B, tuple(lambda_p.shape)))
     if grad_inv_depth is not None:
-        grad_inv_depth = _dense_ba_state(grad_inv_depth, B, H, W, dev, 'dense_ba_vjp', 'grad_inv_depth')
-    return _dense_ba_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, lambda_p, grad_inv_depth,
-                                _dense_reproj_status(status, B, dev))
+        grad_inv_depth = _dense_ba_state(grad_inv_depth, a, 'dense_ba_vjp', 'grad_inv_depth')
+    return _dense_ba_vjp_launch(a, w, rho, lambda_p, grad_inv_depth, _dense_reproj_status(status, a.B, a.dev))
 
 
-def _dense_ba_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, kind, delta, lambda_p, grad_rho, status):
-    """islam_dense_ba_vjp on tensors _dense_reproj_args has prepared."""
-    B, H, W = depth.shape
-    grad_depth = torch.empty((B, H, W), dtype=torch.float32, device=depth.device)
-    grad_flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=depth.device)
-    check(lib().islam_dense_ba_vjp(ptr(depth), ptr(flow), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(w), ptr(rho), kind, delta,
-                                   ptr(lambda_p), ptr(grad_rho), ptr(status), ptr(grad_depth), ptr(grad_flow), B, H, W,
-                                   stream_ptr(depth.device)))
+def _dense_ba_vjp_launch(a, w, rho, lambda_p, grad_rho, status):
+    """islam_dense_ba_vjp on what _dense_reproj_args prepared."""
+    grad_depth, grad_flow = _dense_grad_outputs(a)
+    check(lib().islam_dense_ba_vjp(*a.head(), ptr(w), ptr(rho), a.kind, a.delta, ptr(lambda_p), ptr(grad_rho), ptr(status),
+                                   ptr(grad_depth), ptr(grad_flow), a.B, a.H, a.W, stream_ptr(a.dev)))
     return grad_depth, grad_flow
 
 
@@ -459,12 +467,11 @@ class _DenseBARefine(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, depth, flow, mask, motion, intr, prior_weight, rgb2imu, kernel, iters, damping, min_count, trace_cap):
-        dev, B, H, W, depth32, flow32, mask, motion, intr, rgb2imu, kind, delta = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-        w = _dense_ba_prior_weight(prior_weight, B, dev)
-        out = dense_ba_refine(depth32, flow32, mask, motion, intr, w, rgb2imu=rgb2imu, kernel=kernel, iters=iters, damping=damping,
-                              min_count=min_count, trace_cap=trace_cap)
-        ctx.save_for_backward(depth32, flow32, mask, out.motion, out.inv_depth, out.S, out.status, intr, rgb2imu, w)
-        ctx.kind, ctx.delta, ctx.dtypes = kind, delta, (depth.dtype, flow.dtype)
+        a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+        w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+        out = _dense_ba_refine_launch(a, w, iters, damping, min_count, trace_cap)
+        ctx.save_for_backward(a.depth, a.flow, a.mask, out.motion, out.inv_depth, out.S, out.status, a.intr, a.rgb2imu, w)
+        ctx.kind, ctx.delta, ctx.dtypes = a.kind, a.delta, (depth.dtype, flow.dtype)
         ctx.mark_non_differentiable(*(t for t in out[2:] if t is not None))
         ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None: no reduction for it
         return tuple(out)
@@ -475,13 +482,12 @@ class _DenseBARefine(torch.autograd.Function):
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return none
         depth, flow, mask, motion, rho, S, status, intr, rgb2imu, w = ctx.saved_tensors
+        a = _DenseArgs(depth.device, *depth.shape, depth, flow, mask, motion, intr, rgb2imu, ctx.kind, ctx.delta)      # at the refined state
         grad_motion = torch.zeros_like(motion) if grad_motion is None else grad_motion.to(torch.float64).contiguous()
         if grad_inv_depth is not None:
             grad_inv_depth = grad_inv_depth.to(torch.float64).contiguous()
-        lam, status = _dense_ba_ift_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, ctx.kind, ctx.delta, S, grad_motion,
-                                           grad_inv_depth, status)
-        grad_depth, grad_flow = _dense_ba_vjp_launch(depth, flow, mask, motion, rgb2imu, intr, w, rho, ctx.kind, ctx.delta, lam,
-                                                     grad_inv_depth, status)
+        lam, status = _dense_ba_ift_launch(a, w, rho, S, grad_motion, grad_inv_depth, status)
+        grad_depth, grad_flow = _dense_ba_vjp_launch(a, w, rho, lam, grad_inv_depth, status)
         return (grad_depth.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
                 grad_flow.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None) + none[2:]
 

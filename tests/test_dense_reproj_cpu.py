@@ -216,16 +216,16 @@ def test_ops_refuse_cpu_tensors():
 
 # every kernel of the family (dense_reproj.hip, dense_ba.hip)
 FAMILY_KERNELS = ('dense_reproj_partial_kernel', 'dense_reproj_final_kernel', 'reproj_vjp_kernel', 'reproj_ift_kernel', 'dense_ba_partial_kernel',
-                  'dense_ba_final_kernel', 'dense_ba_gather_kernel')
+                  'dense_ba_final_kernel', 'dense_ba_gather_kernel', 'joint_adj_partial_kernel', 'joint_adj_solve_kernel', 'joint_adj_vjp_kernel')
 
 
 def test_dense_family_kernels_do_not_spill(lib):
     """Thirty fp64 accumulators plus the pose (two poses and the per-pixel Schur terms in the joint kernel) are tight: the library holds
-    exactly the seven kernels of the family, and none of them may have a private segment or a spilled VGPR."""
+    exactly the ten kernels of the family, and none of them may have a private segment or a spilled VGPR."""
     from tests.test_codeobj_cpu import LIB, READELF, _field, _kernels
     if not (os.path.exists(LIB) and os.path.exists(READELF)):
         pytest.skip('library or llvm-readelf missing')
-    ks = {n: blk for n, blk in _kernels().items() if any(part in n for part in ('dense_reproj', 'dense_ba', 'reproj_vjp', 'reproj_ift'))}
+    ks = {n: blk for n, blk in _kernels().items() if any(part in n for part in ('dense_reproj', 'dense_ba', 'reproj_vjp', 'reproj_ift', 'joint_adj'))}
     assert len(ks) == len(FAMILY_KERNELS) and all(sum(want in n for n in ks) == 1 for want in FAMILY_KERNELS), sorted(ks)
     for n, blk in ks.items():
         assert _field(blk, 'private_segment_fixed_size') == 0 and _field(blk, 'vgpr_spill_count') == 0, n
