@@ -543,6 +543,52 @@ int islam_dense_ba_vjp(const float* depth, const float* flow, const uint8_t* mas
                        double robust_delta, const double* lambda_p, const double* grad_inv_depth_or_null,
                        const int* status_or_null, float* grad_depth, float* grad_flow, int B, int H, int W, void* stream);
 
+/* Per-pixel prior weights and the posterior variance of the inverse depths.
+ *
+ * Weight map.  prior_scale (B,H,W) float32, m: the prior weight of pixel i of link b is w_i = prior_weight[b] * (double)m_i (one
+ * rounding), and w_i stands wherever the definitions above write w: h_dd = c jd^T jd + w_i, g_d = c jd^T r + w_i (rho - rho0), the
+ * cost term w_i (rho - rho0)^2.  A pixel has a usable prior iff its depth is finite and > 0 AND m_i is finite and > 0; otherwise it
+ * is outside the valid set at every state and carries rho = 0, exactly like a pixel whose depth is <= 0.  BADPRIOR stays the
+ * per-link verdict on prior_weight[b].  islam_dense_ba_normal_map / islam_dense_ba_refine_map are islam_dense_ba_normal / _refine
+ * with prior_scale after prior_weight: the same launches (the partial kernel reads 4 B more per pixel and sweep), outputs, status
+ * words and scratch (islam_dense_ba_scratch_bytes); a NULL prior_scale is ISLAM_EARG beside their other cases.  m = 1 everywhere
+ * gives the sums of the entry points without a map.
+ *
+ * Posterior variance, at a state (motion, inv_depth_or_null; NULL: rho = rho0), in units of sigma_px^2, in the Gauss-Newton
+ * approximation with the robust weight c (the approximation of S as an information):
+ *   h_cam = J_cam^T e (6),  e = c jd,  h_dd = e.jd + w_i
+ *   mode 0, marginal over the pose:    v_i = 1/h_dd + h_cam^T S_cam^-1 h_cam / h_dd^2
+ *   mode 1, conditional on the pose:   v_i = 1/h_dd
+ *   a pixel with a prior that is invalid at the state (c = 0):          v_i = 1/w_i
+ *   no usable prior, or a state rho that is not finite or is <= 0:      v_i = NaN
+ * S_cam: sums[0..20] of the same state (sums (B,30) as islam_dense_ba_normal / _refine return them; no mount transform is needed,
+ * h^T S^-1 h is invariant under A).  var(rho_i) = sigma_px^2 v_i, and to first order sigma_depth,i = sqrt(var(rho_i)) / rho_i^2.  In
+ * exact arithmetic 1/h_dd <= v_i <= 1/w_i.  prior_scale_or_null NULL: w_i = prior_weight[b].
+ * islam_dense_ba_depth_var: two launches, no host wait, no atomics (a repeat gives the same bits).  The first (one workgroup per
+ * link) forms out_status (B): status_or_null's value where that is not 0, ISLAM_DENSE_REPROJ_BADPRIOR where prior_weight is not > 0,
+ * ISLAM_DENSE_REPROJ_NOTPD where one of the 21 sums is not finite or (mode 0) the Cholesky of S_cam meets a non-positive pivot, else
+ * 0; in mode 0 it leaves S_cam^-1 in scratch (islam_dense_ba_depth_var_scratch_bytes(B)).  The second writes out_var (B,H,W)
+ * float64 in full, one store per pixel; a link whose out_status is not 0 gets NaN at every pixel.  ISLAM_EARG before any device
+ * work for a bad shape, an unknown robust kind, robust_delta <= 0, a mode other than 0 / 1, and a NULL pointer other than mask,
+ * rgb2imu, prior_scale_or_null, inv_depth_or_null and status_or_null. */
+int islam_dense_ba_normal_map(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                              const double* rgb2imu, const double* intr4, const double* prior_weight, const float* prior_scale,
+                              const double* inv_depth_or_null, int robust_kind, double robust_delta, double* out_S, double* out_g,
+                              double* out_cost, double* out_l1, double* out_count, double* out_sums, void* scratch, int B, int H,
+                              int W, void* stream);
+int islam_dense_ba_refine_map(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                              const double* rgb2imu, const double* intr4, const double* prior_weight, const float* prior_scale,
+                              int robust_kind, double robust_delta, int iters, double damping, double min_count, double* out_motion,
+                              double* out_inv_depth, double* out_S, double* out_g, double* out_cost, double* out_l1,
+                              double* out_count, double* out_sums, double* out_lambda, int* out_accepted, int* out_rejected,
+                              int* out_status, double* trace, int trace_cap, void* scratch, int B, int H, int W, void* stream);
+size_t islam_dense_ba_depth_var_scratch_bytes(int B);
+int islam_dense_ba_depth_var(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                             const double* rgb2imu, const double* intr4, const double* prior_weight,
+                             const float* prior_scale_or_null, const double* inv_depth_or_null, const double* sums,
+                             const int* status_or_null, int robust_kind, double robust_delta, int mode, double* out_var,
+                             int* out_status, void* scratch, int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

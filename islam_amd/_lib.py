@@ -123,6 +123,11 @@ SIGNATURES = {
     'islam_dense_ba_adjoint_scratch_bytes': (c_size_t, [c_int]),
     'islam_dense_ba_ift_weights': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 3),
     'islam_dense_ba_vjp': (c_int, [c_void_p] * 8 + [c_int, c_double] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_normal_map': (c_int, [c_void_p] * 9 + [c_int, c_double] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_refine_map': (c_int, [c_void_p] * 8 + [c_int, c_double, c_int, c_double, c_double] + [c_void_p] * 13 +
+                                  [c_int, c_void_p] + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_depth_var_scratch_bytes': (c_size_t, [c_int]),
+    'islam_dense_ba_depth_var': (c_int, [c_void_p] * 11 + [c_int, c_double, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     'islam_imu_scratch_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'islam_imu_preint': (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int] + [c_void_p] * 3 + [c_double, c_int] +
                          [c_void_p] * 4 + [c_int, c_void_p]),

@@ -14,7 +14,8 @@
 // pose-only kernel)  Both sweeps call ba_pixel for the per-pixel terms, and the second sweep is the only
 // code that forms sums, so islam_dense_ba_normal at the returned state runs the same instructions on the same bits.
 // Further down: the gradient of the joint refinement in depth and flow (joint_adj_partial_kernel, joint_adj_solve_kernel,
-// joint_adj_vjp_kernel).
+// joint_adj_vjp_kernel), and per-pixel prior weights with the posterior variance of the inverse depths
+// (ba_wmap_partial_kernel beside the partial kernel; depth_var_factor_kernel, depth_var_pixel_kernel at the end; section 3.27).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -68,15 +69,25 @@ ISLAM_DEV void pose_to_lds(const SE3<double>& Ti, double* dst) {
     dst[11] = Ti.t.z;
 }
 
-__global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
-                                                                const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
-                                                                const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
-                                                                const double* __restrict__ prior_weight, double* __restrict__ partial,
-                                                                int H, int W, int kind, double delta, RhoState rs) {
+// a pixel's prior under a weight map (section 3.27): usable iff the depth is AND m_i is finite and > 0, w_i = w_b (double)m_i, one rounding
+ISLAM_DEV bool map_prior(const float* __restrict__ scale, int i, double wb, bool prior, double& w) {
+    const double m = (double)scale[i];
+    w = wb * m;
+    return prior && isfinite(m) && m > 0.0;
+}
+
+// The body of the two partial kernels.  MAP = false is dense_ba_partial_kernel as section 3.25 describes it, one prior weight per link;
+// MAP = true (ba_wmap_partial_kernel, section 3.27) reads prior_scale (B,H,W) float32 beside the depth, and the pixel's w_i = w_b m_i
+// stands wherever w does.  A pixel whose m_i is not finite or is <= 0 has no usable prior, like one whose depth is <= 0.
+template <bool MAP>
+ISLAM_DEV void ba_partial_body(const float* __restrict__ depth, const float* __restrict__ flow, const uint8_t* __restrict__ mask,
+                               const double* __restrict__ pose7, const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                               const double* __restrict__ prior_weight, const float* __restrict__ prior_scale,
+                               double* __restrict__ partial, int H, int W, int kind, double delta, const RhoState& rs) {
     const int b = blockIdx.y;
     const int HW = H * W;
-    const double w = prior_weight[b];
-    const bool wok = w > 0.0;
+    const double wb = prior_weight[b];
+    const bool wok = wb > 0.0;
     // the back-substitution sweep runs at the current pose (Tp[0]), the sums at the pose under evaluation (Tp[1])
     const bool backsub = rs.eval >= 1 && rs.status[b] == ISLAM_DENSE_REPROJ_OK;
     __shared__ double Tp[2][12], dcam[6];
@@ -91,6 +102,7 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
 
     const size_t off = (size_t)b * HW;
     const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
+    const float* ms = MAP ? prior_scale + off : nullptr;
     const double* rcur = nullptr;      // the inverse depths this evaluation starts from (nullptr: the prior)
     double* rnext = nullptr;           // where the state is initialised (evaluation 0) or the trial goes
     if (rs.eval == 0) {
@@ -110,7 +122,9 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
         const V3<double> t{Tp[0][9], Tp[0][10], Tp[0][11]};
         for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
             const PixelIn px = pixel_in(lp, i);
-            const bool prior = isfinite(px.z) && px.z > 0.0;
+            bool prior = isfinite(px.z) && px.z > 0.0;
+            double w = wb;
+            if constexpr (MAP) prior = map_prior(ms, i, wb, prior, w);
             const double rho0 = prior ? 1.0 / px.z : 0.0;
             const double rho = rcur[i];
             double trial = rho0;
@@ -142,7 +156,9 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
     const V3<double> t{Tp[1][9], Tp[1][10], Tp[1][11]};
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
         const PixelIn px = pixel_in(lp, i);
-        const bool prior = isfinite(px.z) && px.z > 0.0;
+        bool prior = isfinite(px.z) && px.z > 0.0;
+        double w = wb;
+        if constexpr (MAP) prior = map_prior(ms, i, wb, prior, w);
         const double rho0 = prior ? 1.0 / px.z : 0.0;
         const double rho = rsrc ? rsrc[i] : rho0;
         if (rs.eval == 0) rnext[i] = rho0;
@@ -174,6 +190,23 @@ __global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __re
     }
     // a link without a usable prior weight has no sums: NaN, which the final kernel reports
     reduce_and_store_row<NS>(acc, partial + ((size_t)b * NBLK + blockIdx.x) * NS, wok, NAN);
+}
+
+__global__ __launch_bounds__(256) void dense_ba_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                                const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                                const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                                const double* __restrict__ prior_weight, double* __restrict__ partial,
+                                                                int H, int W, int kind, double delta, RhoState rs) {
+    ba_partial_body<false>(depth, flow, mask, pose7, rgb2imu, intr4, prior_weight, nullptr, partial, H, W, kind, delta, rs);
+}
+
+__global__ __launch_bounds__(256) void ba_wmap_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                               const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                               const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                               const double* __restrict__ prior_weight,
+                                                               const float* __restrict__ prior_scale, double* __restrict__ partial, int H,
+                                                               int W, int kind, double delta, RhoState rs) {
+    ba_partial_body<true>(depth, flow, mask, pose7, rgb2imu, intr4, prior_weight, prior_scale, partial, H, W, kind, delta, rs);
 }
 
 __global__ __launch_bounds__(64) void dense_ba_final_kernel(const double* __restrict__ partial, const double* __restrict__ rgb2imu,
@@ -217,6 +250,64 @@ JointScratch joint_scratch(void* base, int B, int H, int W, bool refine) {
     return js;
 }
 
+// one launch of the partial kernel: with a weight map the map kernel, else the kernel of section 3.25
+void launch_partial(hipStream_t s, const float* depth, const float* flow, const uint8_t* mask, const double* pose, const double* rgb2imu,
+                    const double* intr4, const double* prior_weight, const float* prior_scale, double* partial, int B, int H, int W, int kind,
+                    double delta, const RhoState& rs) {
+    if (prior_scale)
+        hipLaunchKernelGGL(ba_wmap_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, pose, rgb2imu, intr4, prior_weight,
+                           prior_scale, partial, H, W, kind, delta, rs);
+    else
+        hipLaunchKernelGGL(dense_ba_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, pose, rgb2imu, intr4, prior_weight,
+                           partial, H, W, kind, delta, rs);
+}
+
+// islam_dense_ba_normal and islam_dense_ba_normal_map (map: the entry point takes a weight map, and a NULL one is an error)
+int normal_entry(const char* who, bool map, const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                 const double* rgb2imu, const double* intr4, const double* prior_weight, const float* prior_scale,
+                 const double* inv_depth_or_null, int robust_kind, double robust_delta, const Outputs& o, void* scratch, int B, int H, int W,
+                 void* stream) {
+    if (int rc = check_common(who, depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W, prior_weight != nullptr))
+        return rc;
+    if (map && !prior_scale) return fail(ISLAM_EARG, "%s: NULL prior_scale", who);
+    hipStream_t s = as_stream(stream);
+    const JointScratch js = joint_scratch(scratch, B, H, W, false);
+    RhoState rs{};
+    rs.given = inv_depth_or_null;
+    rs.eval = -1;
+    launch_partial(s, depth, flow, mask, motion, rgb2imu, intr4, prior_weight, prior_scale, js.partial, B, H, W, robust_kind, robust_delta, rs);
+    hipLaunchKernelGGL(dense_ba_final_kernel, dim3(B), dim3(64), 0, s, js.partial, rgb2imu, motion, o, Refine{}, Joint{}, B);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// islam_dense_ba_refine and islam_dense_ba_refine_map; rf as the entry point filled it
+int refine_entry(const char* who, bool map, const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                 const double* rgb2imu, const double* intr4, const double* prior_weight, const float* prior_scale, int robust_kind,
+                 double robust_delta, int iters, Refine rf, const double* trace, double* out_inv_depth, const Outputs& o, void* scratch, int B,
+                 int H, int W, void* stream) {
+    if (int rc = check_common(who, depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W, prior_weight != nullptr))
+        return rc;
+    if (int rc = check_refine(who, iters, rf, trace)) return rc;
+    if (!out_inv_depth) return fail(ISLAM_EARG, "%s: NULL out_inv_depth", who);
+    if (map && !prior_scale) return fail(ISLAM_EARG, "%s: NULL prior_scale", who);
+    hipStream_t s = as_stream(stream);
+    const JointScratch js = joint_scratch(scratch, B, H, W, true);
+    rf.trial = js.trial;
+    const Joint jt{prior_weight, js.step, js.select};
+    RhoState rs{nullptr, js.buf0, js.buf1, js.select, rf.status, rf.motion, js.step, 0};
+    for (int k = 0; k < iters; ++k) {
+        const double* pose = k == 0 ? motion : js.trial;
+        rf.eval = rs.eval = k;
+        rf.last = k == iters - 1;
+        launch_partial(s, depth, flow, mask, pose, rgb2imu, intr4, prior_weight, prior_scale, js.partial, B, H, W, robust_kind, robust_delta, rs);
+        hipLaunchKernelGGL(dense_ba_final_kernel, dim3(B), dim3(64), 0, s, js.partial, rgb2imu, pose, o, rf, jt, B);
+    }
+    hipLaunchKernelGGL(dense_ba_gather_kernel, dim3(NBLK, B), dim3(256), 0, s, js.buf0, js.buf1, js.select, out_inv_depth, H * W);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
 }  // namespace
 
 extern "C" size_t islam_dense_ba_scratch_bytes(int B, int H, int W, int iters_or_0) {
@@ -229,20 +320,18 @@ extern "C" int islam_dense_ba_normal(const float* depth, const float* flow, cons
                                      const double* inv_depth_or_null, int robust_kind, double robust_delta, double* out_S, double* out_g,
                                      double* out_cost, double* out_l1, double* out_count, double* out_sums, void* scratch, int B, int H,
                                      int W, void* stream) {
-    const Outputs o{out_S, out_g, out_cost, out_l1, out_count, out_sums};
-    if (int rc = check_common("islam_dense_ba_normal", depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W,
-                              prior_weight != nullptr))
-        return rc;
-    hipStream_t s = as_stream(stream);
-    const JointScratch js = joint_scratch(scratch, B, H, W, false);
-    RhoState rs{};
-    rs.given = inv_depth_or_null;
-    rs.eval = -1;
-    hipLaunchKernelGGL(dense_ba_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4, prior_weight,
-                       js.partial, H, W, robust_kind, robust_delta, rs);
-    hipLaunchKernelGGL(dense_ba_final_kernel, dim3(B), dim3(64), 0, s, js.partial, rgb2imu, motion, o, Refine{}, Joint{}, B);
-    ISLAM_LAUNCH_CHECK();
-    return ISLAM_OK;
+    return normal_entry("islam_dense_ba_normal", false, depth, flow, mask, motion, rgb2imu, intr4, prior_weight, nullptr, inv_depth_or_null,
+                        robust_kind, robust_delta, Outputs{out_S, out_g, out_cost, out_l1, out_count, out_sums}, scratch, B, H, W, stream);
+}
+
+extern "C" int islam_dense_ba_normal_map(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                         const double* rgb2imu, const double* intr4, const double* prior_weight, const float* prior_scale,
+                                         const double* inv_depth_or_null, int robust_kind, double robust_delta, double* out_S,
+                                         double* out_g, double* out_cost, double* out_l1, double* out_count, double* out_sums, void* scratch,
+                                         int B, int H, int W, void* stream) {
+    return normal_entry("islam_dense_ba_normal_map", true, depth, flow, mask, motion, rgb2imu, intr4, prior_weight, prior_scale,
+                        inv_depth_or_null, robust_kind, robust_delta, Outputs{out_S, out_g, out_cost, out_l1, out_count, out_sums}, scratch, B,
+                        H, W, stream);
 }
 
 extern "C" int islam_dense_ba_refine(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
@@ -251,30 +340,25 @@ extern "C" int islam_dense_ba_refine(const float* depth, const float* flow, cons
                                      double* out_inv_depth, double* out_S, double* out_g, double* out_cost, double* out_l1,
                                      double* out_count, double* out_sums, double* out_lambda, int* out_accepted, int* out_rejected,
                                      int* out_status, double* trace, int trace_cap, void* scratch, int B, int H, int W, void* stream) {
-    const char* who = "islam_dense_ba_refine";
-    const Outputs o{out_S, out_g, out_cost, out_l1, out_count, out_sums};
-    if (int rc = check_common(who, depth, flow, motion, intr4, robust_kind, robust_delta, o, scratch, B, H, W, prior_weight != nullptr))
-        return rc;
-    Refine rf{out_motion, nullptr, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
-              min_count, damping};
-    if (int rc = check_refine(who, iters, rf, trace)) return rc;
-    if (!out_inv_depth) return fail(ISLAM_EARG, "%s: NULL out_inv_depth", who);
-    hipStream_t s = as_stream(stream);
-    const JointScratch js = joint_scratch(scratch, B, H, W, true);
-    rf.trial = js.trial;
-    const Joint jt{prior_weight, js.step, js.select};
-    RhoState rs{nullptr, js.buf0, js.buf1, js.select, out_status, out_motion, js.step, 0};
-    for (int k = 0; k < iters; ++k) {
-        const double* pose = k == 0 ? motion : js.trial;
-        rf.eval = rs.eval = k;
-        rf.last = k == iters - 1;
-        hipLaunchKernelGGL(dense_ba_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, pose, rgb2imu, intr4, prior_weight,
-                           js.partial, H, W, robust_kind, robust_delta, rs);
-        hipLaunchKernelGGL(dense_ba_final_kernel, dim3(B), dim3(64), 0, s, js.partial, rgb2imu, pose, o, rf, jt, B);
-    }
-    hipLaunchKernelGGL(dense_ba_gather_kernel, dim3(NBLK, B), dim3(256), 0, s, js.buf0, js.buf1, js.select, out_inv_depth, H * W);
-    ISLAM_LAUNCH_CHECK();
-    return ISLAM_OK;
+    const Refine rf{out_motion, nullptr, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
+                    min_count, damping};
+    return refine_entry("islam_dense_ba_refine", false, depth, flow, mask, motion, rgb2imu, intr4, prior_weight, nullptr, robust_kind,
+                        robust_delta, iters, rf, trace, out_inv_depth, Outputs{out_S, out_g, out_cost, out_l1, out_count, out_sums}, scratch, B,
+                        H, W, stream);
+}
+
+extern "C" int islam_dense_ba_refine_map(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                         const double* rgb2imu, const double* intr4, const double* prior_weight, const float* prior_scale,
+                                         int robust_kind, double robust_delta, int iters, double damping, double min_count,
+                                         double* out_motion, double* out_inv_depth, double* out_S, double* out_g, double* out_cost,
+                                         double* out_l1, double* out_count, double* out_sums, double* out_lambda, int* out_accepted,
+                                         int* out_rejected, int* out_status, double* trace, int trace_cap, void* scratch, int B, int H, int W,
+                                         void* stream) {
+    const Refine rf{out_motion, nullptr, out_lambda, out_accepted, out_rejected, out_status, trace_cap > 0 ? trace : nullptr, trace_cap, 0, 0,
+                    min_count, damping};
+    return refine_entry("islam_dense_ba_refine_map", true, depth, flow, mask, motion, rgb2imu, intr4, prior_weight, prior_scale, robust_kind,
+                        robust_delta, iters, rf, trace, out_inv_depth, Outputs{out_S, out_g, out_cost, out_l1, out_count, out_sums}, scratch, B,
+                        H, W, stream);
 }
 
 // ------------------------------------------------------------------ the gradient of the joint refinement in depth and flow
@@ -450,6 +534,133 @@ extern "C" int islam_dense_ba_vjp(const float* depth, const float* flow, const u
     hipLaunchKernelGGL(joint_adj_vjp_kernel, dim3(NBLK, B), dim3(256), 0, as_stream(stream), depth, flow, mask, motion, rgb2imu, intr4,
                        prior_weight, inv_depth, lambda_p, grad_inv_depth_or_null, status_or_null, grad_depth, grad_flow, H, W, robust_kind,
                        robust_delta);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// ------------------------------------------------------------------ the posterior variance of the inverse depths
+//   At a state (pose, rho), in units of sigma_px^2 and in the Gauss-Newton approximation with the robust
+// weight c, with h_cam = J_cam^T e (= h_pd), h_dd = e.jd + w_i as ba_pixel forms them and S_cam the first 21 sums of the same state:
+//   marginal over the pose:   v_i = 1 / h_dd + h_cam^T S_cam^-1 h_cam / h_dd^2        conditional on the pose:   v_i = 1 / h_dd
+//   a pixel with a prior that is invalid at the state (c = 0):  v_i = 1 / w_i;   no usable prior, or rho not finite or <= 0:  NaN.
+// depth_var_factor_kernel inverts S_cam per link and forms the link's status, depth_var_pixel_kernel streams the map out: one 8-byte
+// store per pixel, no reduction, no atomics.  (Their names stay clear of the family's ten, which tests/test_dense_reproj_cpu.py pins.)
+namespace {
+
+// One 64-lane workgroup per link.  status: the incoming one if set, BADPRIOR for a prior weight that is not > 0, NOTPD for a sum that
+// is not finite or (marginal mode) a non-positive pivot, else OK.  Marginal mode: lane k solves S_cam x = e_k by the header's Cholesky
+// (six factorisations side by side, everything runtime-indexed in LDS) and the upper triangle of S_cam^-1 goes to sinv (B,21).
+__global__ __launch_bounds__(64) void depth_var_factor_kernel(const double* __restrict__ sums, const double* __restrict__ prior_weight,
+                                                               const int* __restrict__ status_in, int marginal,
+                                                               double* __restrict__ sinv, int* __restrict__ status_out) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    __shared__ double Hn[36], gn[6][6], L[6][6][6], x[6][6];
+    __shared__ int bad;
+    if (i == 0) bad = 0;
+    if (i < 36) {
+        const int r = i / 6, c = i - 6 * r;
+        Hn[i] = sums[(size_t)b * NS + tri(min(r, c), max(r, c))];
+        gn[r][c] = r == c ? -1.0 : 0.0;      // lm_step solves H x = -g
+    }
+    __syncthreads();
+    int s = status_in ? status_in[b] : ISLAM_DENSE_REPROJ_OK;
+    if (s == ISLAM_DENSE_REPROJ_OK && !(prior_weight[b] > 0.0)) s = ISLAM_DENSE_REPROJ_BADPRIOR;
+    if (i < 36 && !isfinite(Hn[i])) bad = 1;
+    if (marginal && s == ISLAM_DENSE_REPROJ_OK && i < 6 && !lm_step(Hn, gn[i], 0.0, L[i], x[i])) bad = 1;
+    __syncthreads();
+    if (s == ISLAM_DENSE_REPROJ_OK && bad) s = ISLAM_DENSE_REPROJ_NOTPD;
+    if (i == 0) status_out[b] = s;
+    if (marginal && i < 36) {
+        const int r = i / 6, c = i - 6 * r;
+        if (r <= c) sinv[(size_t)b * 21 + tri(r, c)] = s == ISLAM_DENSE_REPROJ_OK ? x[c][r] : NAN;
+    }
+}
+
+// grid (NBLK, B) x 256, grid-stride.  A link whose status is set gets NaN at every pixel.
+__global__ __launch_bounds__(256) void depth_var_pixel_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                               const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                               const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                               const double* __restrict__ prior_weight,
+                                                               const float* __restrict__ prior_scale, const double* __restrict__ inv_depth,
+                                                               const double* __restrict__ sinv, const int* __restrict__ status,
+                                                               double* __restrict__ out_var, int H, int W, int kind, double delta,
+                                                               int marginal) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const size_t off = (size_t)b * HW;
+    double* out = out_var + off;
+    if (status[b] != ISLAM_DENSE_REPROJ_OK) {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) out[i] = NAN;
+        return;
+    }
+    __shared__ double Tp[12], Si[21];
+    if (threadIdx.x == 0) pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+    if (marginal && threadIdx.x >= 64 && threadIdx.x < 64 + 21) Si[threadIdx.x - 64] = sinv[(size_t)b * 21 + threadIdx.x - 64];
+    __syncthreads();
+    const M3<double> R = m3_load(Tp);
+    const V3<double> t{Tp[9], Tp[10], Tp[11]};
+    const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
+    const double wb = prior_weight[b];
+    const float* ms = prior_scale ? prior_scale + off : nullptr;
+    const double* rp = inv_depth ? inv_depth + off : nullptr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        const PixelIn px = pixel_in(lp, i);
+        bool prior = isfinite(px.z) && px.z > 0.0;
+        double w = wb;
+        if (ms) prior = map_prior(ms, i, wb, prior, w);
+        const double rho = rp ? rp[i] : (prior ? 1.0 / px.z : 0.0);
+        double v = NAN;
+        if (prior && isfinite(rho) && rho > 0.0) {
+            v = 1.0 / w;      // c = 0: only the prior speaks
+            const BaPixel p = ba_pixel(R, t, rho, px, lp, w);
+            if (p.p.valid) {
+                const double ih = 1.0 / p.hdd;
+                v = ih;
+                if (marginal) {
+                    double h[6];
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) h[q] = p.eu * p.p.ju[q] + p.ev * p.p.jv[q];
+                    double quad = 0.0;      // h^T S_cam^-1 h over the stored upper triangle
+                    int k = 0;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) {
+                        double row = 0.0;
+#pragma unroll
+                        for (int l = q; l < 6; ++l) row += Si[k++] * (l == q ? h[l] : 2.0 * h[l]);
+                        quad += h[q] * row;
+                    }
+                    v = ih + quad * ih * ih;
+                }
+            }
+        }
+        out[i] = v;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t islam_dense_ba_depth_var_scratch_bytes(int B) {
+    if (B < 1) return 0;
+    return align_up((size_t)B * 21 * sizeof(double));
+}
+
+extern "C" int islam_dense_ba_depth_var(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                        const double* rgb2imu, const double* intr4, const double* prior_weight,
+                                        const float* prior_scale_or_null, const double* inv_depth_or_null, const double* sums,
+                                        const int* status_or_null, int robust_kind, double robust_delta, int mode, double* out_var,
+                                        int* out_status, void* scratch, int B, int H, int W, void* stream) {
+    const char* who = "islam_dense_ba_depth_var";
+    if (int rc = check_shape_kind(who, B, H, W, robust_kind, robust_delta)) return rc;
+    if (mode != 0 && mode != 1) return fail(ISLAM_EARG, "%s: mode must be 0 (marginal) or 1 (conditional), got %d", who, mode);
+    if (!depth || !flow || !motion || !intr4) return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 pointer", who);
+    if (!prior_weight) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    if (!sums || !out_var || !out_status || !scratch) return fail(ISLAM_EARG, "%s: NULL sums / out_var / out_status / scratch pointer", who);
+    hipStream_t s = as_stream(stream);
+    double* sinv = static_cast<double*>(scratch);
+    const int marginal = mode == 0;
+    hipLaunchKernelGGL(depth_var_factor_kernel, dim3(B), dim3(64), 0, s, sums, prior_weight, status_or_null, marginal, sinv, out_status);
+    hipLaunchKernelGGL(depth_var_pixel_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4, prior_weight,
+                       prior_scale_or_null, inv_depth_or_null, sinv, out_status, out_var, H, W, robust_kind, robust_delta, marginal);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

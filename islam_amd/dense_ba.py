@@ -11,7 +11,9 @@
     lets a loss on the refined pose reach the stored depth and flow (section 3.24); ``refine_joint`` and
     ``information(sigma_inv_depth=...)`` treat the stored depth as a Gaussian prior on one inverse depth per pixel and refine or
     marginalise it with the pose (csrc/dense_ba.hip, section 3.25); ``refine_joint(differentiable=True)`` lets a loss on the jointly
-    refined pose, inverse depths or depth map reach the stored depth and flow (section 3.26);
+    refined pose, inverse depths or depth map reach the stored depth and flow (section 3.26); both take the prior's standard
+    deviation per pixel as well, and ``depth_uncertainty`` returns the posterior standard deviation of every refined depth
+    (section 3.27);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -23,6 +25,7 @@ import torch
 from . import lietensor as pp
 
 DenseBAJoint = collections.namedtuple('DenseBAJoint', 'motion inv_depth S g cost l1 count sums damping accepted rejected status trace depth')
+DenseBADepthUncertainty = collections.namedtuple('DenseBADepthUncertainty', 'var_inv_depth sigma_inv_depth sigma_depth status')
 
 
 def pixel2point(pixels, depth, intrinsics):
@@ -212,28 +215,37 @@ class DenseReprojectionLoss:
         return sigma_disp / (fx * baseline)
 
     def _prior_weight(self, sigma_inv_depth, sigma_px, who):
-        """w = sigma_px^2 / sigma_inv_depth^2 per link: a number, or a (B,) tensor that is not read back when it lives on the device."""
+        """(w, m): the prior weight per link and the per-pixel factor on it (None without a map).  A number or a (B,) tensor (not read
+        back when it lives on the device): w = sigma_px^2 / sigma_inv_depth^2, m = None.  A (B,H,W) tensor, one standard deviation per
+        pixel: w = sigma_px^2 and m = float32(1 / sigma_i^2) where sigma_i is finite and > 0, 0 elsewhere ("no prior at this pixel", not
+        an error), formed with torch.where and never read back."""
         sigma_px = float(sigma_px)
         if not (sigma_px > 0.0 and sigma_px < float('inf')):
             raise ValueError('%s: sigma_px must be a finite positive number (got %r)' % (who, sigma_px))
         B = self.z.shape[0]
         if torch.is_tensor(sigma_inv_depth):
             sig = sigma_inv_depth.detach().to(torch.float64)
+            if sig.dim() == 3 and tuple(sig.shape) == tuple(self.z.shape):
+                ok = torch.isfinite(sig) & (sig > 0)
+                m = torch.where(ok, 1.0 / torch.where(ok, sig, torch.ones_like(sig)) ** 2, torch.zeros_like(sig))
+                return sigma_px ** 2, m.to(torch.float32)
             if sig.numel() != 1 and tuple(sig.shape) != (B,):
-                raise ValueError('%s: sigma_inv_depth must be a positive number or a (%d,) tensor, got shape %s' % (who, B, tuple(sig.shape)))
+                raise ValueError('%s: sigma_inv_depth must be a positive number, a (%d,) tensor or a %s map, got shape %s' % (
+                    who, B, tuple(self.z.shape), tuple(sig.shape)))
             if not sig.is_cuda and not bool(((sig > 0) & torch.isfinite(sig)).all()):
                 raise ValueError('%s: sigma_inv_depth must be finite and positive (got %s)' % (who, sig.tolist()))
-            return (sigma_px / sig.reshape(-1)) ** 2
+            return (sigma_px / sig.reshape(-1)) ** 2, None
         sig = float(sigma_inv_depth)
         if not (sig > 0.0 and sig < float('inf')):
             raise ValueError('%s: sigma_inv_depth must be a finite positive number (got %r)' % (who, sigma_inv_depth))
-        return (sigma_px / sig) ** 2
+        return (sigma_px / sig) ** 2, None
 
     def refine_joint(self, motion, sigma_inv_depth, sigma_px=1.0, iters=20, kernel=None, damping=1e-4, min_count=16, trace_cap=0,
                      differentiable=False):
         """Joint two-view bundle adjustment of each link: ``iters`` device-side Levenberg-Marquardt evaluations on the pose AND one
-        inverse depth per pixel, the stored depth as a Gaussian prior of standard deviation ``sigma_inv_depth`` (1/m; a positive number
-        or a (B,) tensor; sigma_inv_depth_from_disparity gives the usual stereo value) beside flow errors of ``sigma_px`` pixels
+        inverse depth per pixel, the stored depth as a Gaussian prior of standard deviation ``sigma_inv_depth`` (1/m; a positive number,
+        a (B,) tensor, or a (B,H,W) map with one value per pixel, where an entry that is not finite or not positive means "no prior at
+        this pixel": section 3.27; sigma_inv_depth_from_disparity gives the usual stereo value) beside flow errors of ``sigma_px`` pixels
         (ops.dense_ba_refine).  Returns DenseBAJoint: the fields of ops.DenseBARefined (motion, inv_depth, S,
         g, cost, l1, count, sums, damping, accepted, rejected, status, trace) and ``depth``: 1 / inv_depth where that is positive,
         the stored depth elsewhere.
@@ -249,9 +261,12 @@ class DenseReprojectionLoss:
         elsewhere (with a noisy prior the residuals at the optimum are not zero: section 3.26 measures the error), and the formula
         assumes convergence in pose and depths.  The start ``motion`` gets no gradient (the optimum does not depend on it), nor does
         the prior weight (``sigma_inv_depth``, ``sigma_px``: out of scope); a link whose status is set, or whose S is not positive
-        definite, gets a zero gradient."""
+        definite, gets a zero gradient.  The gradient kernels take no per-pixel map: differentiable=True with a (B,H,W)
+        ``sigma_inv_depth`` raises NotImplementedError."""
         from . import ops
-        w = self._prior_weight(sigma_inv_depth, sigma_px, 'refine_joint')
+        w, m = self._prior_weight(sigma_inv_depth, sigma_px, 'refine_joint')
+        if differentiable and m is not None:
+            raise NotImplementedError('refine_joint: differentiable=True is not implemented for a per-pixel (B,H,W) sigma_inv_depth map')
         if differentiable:
             mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
             out = ops.DenseBARefined(*ops._DenseBARefine.apply(
@@ -260,17 +275,34 @@ class DenseReprojectionLoss:
         else:
             out = ops.dense_ba_refine(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w,
                                       rgb2imu=self.rgb2imu_pose, kernel=kernel, iters=iters, damping=damping, min_count=min_count,
-                                      trace_cap=trace_cap)
+                                      trace_cap=trace_cap, **({} if m is None else {'prior_scale': m}))
         ok = out.inv_depth > 0
         depth = torch.where(ok, (1.0 / torch.where(ok, out.inv_depth, torch.ones_like(out.inv_depth))).to(self.z.dtype), self.z.detach())
         return DenseBAJoint(*out, depth)
+
+    def depth_uncertainty(self, joint, sigma_inv_depth, sigma_px=1.0, kernel=None, marginal=True):
+        """The posterior uncertainty of the depths a ``refine_joint`` returned (``joint``: its result; motion, inv_depth, sums and status
+        are used), in the Gauss-Newton approximation at that state (ops.dense_ba_depth_variance).
+        ``sigma_inv_depth``, ``sigma_px`` and ``kernel`` must be the ones the refinement was given.  marginal=True: the pose is uncertain
+        too (marginal over it); False: the pose taken as known.  Returns DenseBADepthUncertainty, (B,H,W) float64 on the device:
+        var_inv_depth = sigma_px^2 v, sigma_inv_depth = its square root (a valid per-pixel prior for a next refinement), sigma_depth =
+        sigma_inv_depth / inv_depth^2 (first order), all NaN where the pixel has no usable prior or the link's ``status`` (B) is set."""
+        from . import ops
+        w, m = self._prior_weight(sigma_inv_depth, sigma_px, 'depth_uncertainty')
+        out = ops.dense_ba_depth_variance(self.z, self.flow, self.mask, joint.motion, torch.tensor(self.K4, dtype=torch.float64), w,
+                                          inv_depth=joint.inv_depth, sums=joint.sums, status=joint.status, prior_scale=m,
+                                          rgb2imu=self.rgb2imu_pose, kernel=kernel, marginal=marginal)
+        var = float(sigma_px) ** 2 * out.var
+        sig = torch.sqrt(var)
+        return DenseBADepthUncertainty(var, sig, sig / (joint.inv_depth * joint.inv_depth), out.status)
 
     def information(self, motion, sigma_px=1.0, kernel=None, sigma_inv_depth=None):
         """H / sigma_px^2 (B,6,6) float64: the information of each link's VO residual in the frame and row order of PvgoInfo.vo, for
         flow errors of ``sigma_px`` pixels per component (PvgoInfo.from_dense_reproj).  sigma_px='residual' estimates the variance per
         link from the fit itself, sigma^2 = cost / (2 count - 6); a link with 2 count <= 6 gives the zero matrix.
 
-        sigma_inv_depth (a positive number or a (B,) tensor; None: the depth is taken as exact, the path above): the stored depth is
+        sigma_inv_depth (a positive number, a (B,) tensor or a (B,H,W) map as in refine_joint; None: the depth is taken as exact, the
+        path above): the stored depth is
         a Gaussian prior of that standard deviation in inverse depth, and the result is S / sigma_px^2 with S the Schur complement of
         the joint (pose, inverse depth) problem onto the pose, at the prior depths (ops.dense_ba_normal): the
         depth-marginalised information, never larger than H / sigma_px^2.  With sigma_px='residual' the prior weight is formed with
@@ -282,9 +314,9 @@ class DenseReprojectionLoss:
         else:
             from . import ops
             residual = isinstance(sigma_px, str)
-            w = self._prior_weight(sigma_inv_depth, 1.0 if residual else sigma_px, 'information')
+            w, m = self._prior_weight(sigma_inv_depth, 1.0 if residual else sigma_px, 'information')
             ne = ops.dense_ba_normal(self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w,
-                                     rgb2imu=self.rgb2imu_pose, kernel=kernel)
+                                     rgb2imu=self.rgb2imu_pose, kernel=kernel, **({} if m is None else {'prior_scale': m}))
             Hm = ne.S
         if isinstance(sigma_px, str):
             if sigma_px != 'residual':

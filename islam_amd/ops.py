@@ -278,45 +278,100 @@ def _dense_ba_prior_weight(prior_weight, B, dev):
     return w.contiguous()
 
 
-def dense_ba_normal(depth, flow, mask, motion, intr, prior_weight, inv_depth=None, rgb2imu=None, kernel=None):
+def _dense_ba_prior_scale(prior_scale, a, who):
+    """prior_scale (B,H,W) as a contiguous float32 device tensor (None stays None); nothing is read back."""
+    if prior_scale is None:
+        return None
+    require_cuda(prior_scale)
+    if tuple(prior_scale.shape) != (a.B, a.H, a.W):
+        raise ValueError('%s: prior_scale must be (%d,%d,%d), got %s' % (who, a.B, a.H, a.W, tuple(prior_scale.shape)))
+    return _f32c(prior_scale.detach().to(a.dev))
+
+
+def dense_ba_normal(depth, flow, mask, motion, intr, prior_weight, inv_depth=None, rgb2imu=None, kernel=None, prior_scale=None):
     """The depth-marginalised normal equations of the joint (pose, inverse depth) dense reprojection problem per link
     (include/islam_hip.h, islam_dense_ba_normal).  Arguments as dense_reproj_normal, plus prior_weight (a
     positive number or (B,)) = sigma_px^2 / sigma_inv_depth^2 and inv_depth (B,H,W) float64, the state's inverse depths (None: the
-    prior 1/depth).  Returns DenseBANormal(S (B,6,6), g (B,6), cost, l1, count (B), sums (B,30)), float64 on the device; nothing is
-    read back."""
+    prior 1/depth).  prior_scale (B,H,W) on the device or None: a per-pixel factor m on the prior weight, w_i = prior_weight[b] m_i
+    (float32; a pixel whose m is not finite or is <= 0 has no prior; islam_dense_ba_normal_map, section 3.27).  Returns
+    DenseBANormal(S (B,6,6), g (B,6), cost, l1, count (B), sums (B,30)), float64 on the device; nothing is read back."""
     a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
     w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+    m = _dense_ba_prior_scale(prior_scale, a, 'dense_ba_normal')
     if inv_depth is not None:
         require_cuda(inv_depth)
         inv_depth = _dense_ba_state(inv_depth, a, 'dense_ba')
     out = DenseBANormal(*_dense_reproj_outputs(a.B, a.dev))
     scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(a.B, a.H, a.W, 0), dtype=torch.uint8, device=a.dev)
-    check(lib().islam_dense_ba_normal(*a.head(), ptr(w), ptr(inv_depth), a.kind, a.delta, ptr(out.S), ptr(out.g), ptr(out.cost), ptr(out.l1),
-                                      ptr(out.count), ptr(out.sums), ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
+    tail = (ptr(inv_depth), a.kind, a.delta, ptr(out.S), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(scratch),
+            a.B, a.H, a.W, stream_ptr(a.dev))
+    if m is None:
+        check(lib().islam_dense_ba_normal(*a.head(), ptr(w), *tail))
+    else:
+        check(lib().islam_dense_ba_normal_map(*a.head(), ptr(w), ptr(m), *tail))
     return out
 
 
 def dense_ba_refine(depth, flow, mask, motion, intr, prior_weight, rgb2imu=None, kernel=None, iters=20, damping=1e-4, min_count=16,
-                    trace_cap=0):
+                    trace_cap=0, prior_scale=None):
     """``iters`` Levenberg-Marquardt evaluations on the joint (pose, inverse depth) problem of each link, all on the device
-    (include/islam_hip.h, islam_dense_ba_refine).  Arguments as dense_reproj_refine plus prior_weight (see dense_ba_normal).  Returns
+    (include/islam_hip.h, islam_dense_ba_refine).  Arguments as dense_reproj_refine plus prior_weight and prior_scale (see
+    dense_ba_normal; with a map the launch is islam_dense_ba_refine_map).  Returns
     DenseBARefined: motion (B,7), inv_depth (B,H,W) float64 (0 where the depth gives no prior) and S, g, cost, l1, count, sums at
     them, damping, accepted, rejected, status (B) int32 (0, or _lib.DENSE_REPROJ_FEW / _NOTPD / _BADPRIOR) and trace."""
     a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
-    return _dense_ba_refine_launch(a, _dense_ba_prior_weight(prior_weight, a.B, a.dev), iters, damping, min_count, trace_cap)
+    return _dense_ba_refine_launch(a, _dense_ba_prior_weight(prior_weight, a.B, a.dev), iters, damping, min_count, trace_cap,
+                                   _dense_ba_prior_scale(prior_scale, a, 'dense_ba_refine'))
 
 
-def _dense_ba_refine_launch(a, w, iters, damping, min_count, trace_cap):
-    """islam_dense_ba_refine on what _dense_reproj_args and _dense_ba_prior_weight prepared."""
+def _dense_ba_refine_launch(a, w, iters, damping, min_count, trace_cap, m=None):
+    """islam_dense_ba_refine (m (B,H,W) float32: islam_dense_ba_refine_map) on what _dense_reproj_args and _dense_ba_prior_weight prepared."""
     iters, trace_cap = int(iters), int(trace_cap)
     out = _dense_reproj_outputs(a.B, a.dev)
     pose, lam, acc, rej, status, trace = _dense_lm_outputs(a.B, a.dev, trace_cap)
     rho = torch.empty((a.B, a.H, a.W), dtype=torch.float64, device=a.dev)
     scratch = torch.empty(lib().islam_dense_ba_scratch_bytes(a.B, a.H, a.W, max(iters, 1)), dtype=torch.uint8, device=a.dev)
-    check(lib().islam_dense_ba_refine(*a.head(), ptr(w), a.kind, a.delta, iters, float(damping), float(min_count), ptr(pose), ptr(rho),
-                                      ptr(out.H), ptr(out.g), ptr(out.cost), ptr(out.l1), ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc),
-                                      ptr(rej), ptr(status), ptr(trace), trace_cap, ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
+    tail = (a.kind, a.delta, iters, float(damping), float(min_count), ptr(pose), ptr(rho), ptr(out.H), ptr(out.g), ptr(out.cost), ptr(out.l1),
+            ptr(out.count), ptr(out.sums), ptr(lam), ptr(acc), ptr(rej), ptr(status), ptr(trace), trace_cap, ptr(scratch), a.B, a.H, a.W,
+            stream_ptr(a.dev))
+    if m is None:
+        check(lib().islam_dense_ba_refine(*a.head(), ptr(w), *tail))
+    else:
+        check(lib().islam_dense_ba_refine_map(*a.head(), ptr(w), ptr(m), *tail))
     return DenseBARefined(pose, rho, *out, lam, acc, rej, status, trace)
+
+
+DenseBADepthVar = collections.namedtuple('DenseBADepthVar', 'var status')
+
+
+def dense_ba_depth_variance(depth, flow, mask, motion, intr, prior_weight, inv_depth=None, sums=None, status=None, prior_scale=None,
+                            rgb2imu=None, kernel=None, marginal=True):
+    """The posterior variance of every pixel's inverse depth at the state (motion, inv_depth; None: the prior 1/depth), in units of
+    sigma_px^2 (include/islam_hip.h, islam_dense_ba_depth_var): v = 1/h_dd + h_cam^T S_cam^-1 h_cam / h_dd^2
+    marginal over the pose, 1/h_dd conditional on it (marginal=False), 1/w_i at a pixel with a prior that is invalid at the state, NaN
+    at one without a usable prior.  sums (B,30): the camera-frame sums dense_ba_normal / dense_ba_refine returned at this state (None:
+    dense_ba_normal is called here); status (B) int or None: the refinement's status; other arguments as dense_ba_normal.  Returns
+    DenseBADepthVar(var (B,H,W) float64, status (B) int32: the incoming status, _lib.DENSE_REPROJ_BADPRIOR, or _NOTPD for sums that
+    are not finite or an S_cam that is not positive definite; such a link's map is all NaN).  Two launches, nothing is read back."""
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+    m = _dense_ba_prior_scale(prior_scale, a, 'dense_ba_depth_variance')
+    if inv_depth is not None:
+        require_cuda(inv_depth)
+        inv_depth = _dense_ba_state(inv_depth, a, 'dense_ba_depth_variance')
+    if sums is None:
+        sums = dense_ba_normal(a.depth, a.flow, a.mask, a.motion, a.intr, w, inv_depth=inv_depth, rgb2imu=a.rgb2imu, kernel=kernel,
+                               prior_scale=m).sums
+    sums = torch.as_tensor(sums).detach().to(a.dev, torch.float64).contiguous()
+    if tuple(sums.shape) != (a.B, _lib.DENSE_REPROJ_NSUM):
+        raise ValueError('dense_ba_depth_variance: sums must be (%d,%d), got %s' % (a.B, _lib.DENSE_REPROJ_NSUM, tuple(sums.shape)))
+    status = _dense_reproj_status(status, a.B, a.dev)
+    var = torch.empty((a.B, a.H, a.W), dtype=torch.float64, device=a.dev)
+    out = torch.empty(a.B, dtype=torch.int32, device=a.dev)
+    scratch = torch.empty(lib().islam_dense_ba_depth_var_scratch_bytes(a.B), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_ba_depth_var(*a.head(), ptr(w), ptr(m), ptr(inv_depth), ptr(sums), ptr(status), a.kind, a.delta,
+                                         0 if marginal else 1, ptr(var), ptr(out), ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
+    return DenseBADepthVar(var, out)
 
 
 def _dense_reproj_status(status, B, dev):

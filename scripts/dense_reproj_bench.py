@@ -24,6 +24,13 @@ ops.dense_ba_vjp) with and without a gradient on inv_depth, a 20-evaluation refi
 autograd, and what the gradient costs without the kernels: eager float64 torch autograd of the same Phi.
 
     python scripts/dense_reproj_bench.py --joint-grad [--case 448x640] [--out profiles/dense_ba_grad_bench.json]
+
+--uncertainty times the per-pixel prior weights and the posterior depth variance instead: a 20-evaluation
+ops.dense_ba_refine without and with a weight map (the yardstick is the run without the map, in the same process), and
+ops.dense_ba_depth_variance at the refined state with the sums given, marginal over the pose and conditional on it, beside
+ops.dense_ba_vjp on the same tensors, which moves about as many bytes.
+
+    python scripts/dense_reproj_bench.py --uncertainty [--case 448x640] [--out profiles/dense_ba_uncertainty_bench.json]
 """
 import json
 import os
@@ -424,8 +431,87 @@ def main_joint_grad(argv):
         f.write(line + '\n')
 
 
+VAR_PIXEL_BYTES = 33          # the variance pass: the 13 of the pose-only pass, the map (4), rho (8) and one float64 store (8)
+
+
+def run_uncertainty_case(H, W):
+    """--uncertainty: the weight map's cost per refinement evaluation and the cost of the variance pass."""
+    import numpy as np
+    import torch
+    from islam_amd import ops
+    from tests.dense_reproj_f64 import MOUNT, PRIOR_W, make_scene, noisy_prior, right_perturb
+    dev = torch.device('cuda:0')
+    sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    w = torch.full((B,), PRIOR_W, dtype=torch.float64, device=dev)
+    m = d(np.exp2(np.random.default_rng(3).uniform(-1.0, 1.0, (B, H, W))).astype(np.float32))
+    ref = ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20, prior_scale=m)
+    state = (depth, flow, mask, ref.motion, intr, w)
+    lam = torch.zeros((B, 6), dtype=torch.float64, device=dev)
+    var = lambda marginal: ops.dense_ba_depth_variance(*state, inv_depth=ref.inv_depth, sums=ref.sums, status=ref.status, prior_scale=m, rgb2imu=mount,
+                                                       marginal=marginal)
+    fns = {'ba_refine20': lambda: ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20),
+           'ba_refine20_map': lambda: ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20, prior_scale=m),
+           'depth_var_marginal': lambda: var(True), 'depth_var_conditional': lambda: var(False),
+           'ba_vjp': lambda: ops.dense_ba_vjp(*state, ref.inv_depth, lam, grad_inv_depth=ref.inv_depth, rgb2imu=mount, status=ref.status)}
+
+    def median(fn, n=30):
+        us = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        us.sort()
+        return 0.5 * (us[n // 2 - 1] + us[n // 2])
+
+    out = {}
+    for name, fn in fns.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = median(fn)
+    v = var(True)
+    out['status_ok'] = int((v.status == 0).sum())
+    out['finite_fraction'] = float(torch.isfinite(v.var).double().mean())
+    out['map_over_no_map'] = out['ba_refine20_map'] / out['ba_refine20']
+    out['map_us_per_eval'] = (out['ba_refine20_map'] - out['ba_refine20']) / 20
+    out['var_over_ba_vjp'] = out['depth_var_marginal'] / out['ba_vjp']
+    out['var_over_refine_eval'] = out['depth_var_marginal'] / (out['ba_refine20'] / 20)
+    out['MB_moved_var'] = VAR_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_var_marginal'] = VAR_PIXEL_BYTES * B * H * W / (out['depth_var_marginal'] * 1e-6) / 1e9 / HBM_GBS
+    out['hbm_frac_var_conditional'] = VAR_PIXEL_BYTES * B * H * W / (out['depth_var_conditional'] * 1e-6) / 1e9 / HBM_GBS
+    return out
+
+
+def main_uncertainty(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_uncertainty_case(*hw) for case, hw in cases.items()}
+    cols = ('ba_refine20', 'ba_refine20_map', 'map_over_no_map', 'map_us_per_eval', 'depth_var_marginal', 'depth_var_conditional', 'ba_vjp',
+            'var_over_ba_vjp', 'var_over_refine_eval', 'MB_moved_var', 'hbm_frac_var_marginal', 'hbm_frac_var_conditional', 'status_ok',
+            'finite_fraction')
+    print('us per call at B = %d: the median of 30; hbm_frac_var: %d bytes per pixel over the time, of %.0f GB/s' % (B, VAR_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'dense_ba_uncertainty_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--uncertainty' in sys.argv[1:]:
+        return main_uncertainty(sys.argv[1:])
     if '--joint-grad' in sys.argv[1:]:
         return main_joint_grad(sys.argv[1:])
     if '--grad' in sys.argv[1:]:
