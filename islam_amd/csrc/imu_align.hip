@@ -9,7 +9,8 @@
 // For every pair of consecutive intervals i, i + 1 the velocities drop out of (P_i), (P_{i+1}), (V_i) and leave three equations
 // A_i [g; b] = r_i; with the body position p_i = s q_i - R_i t (q_i the camera position, R_i the body rotation) they read
 //   A_i [g; b] + T_i t - s Q_i = m_i.
-// Kernels (float64 arithmetic whatever the I/O type; the term layout is imu_normal.h, the fixed-order sum between them imu_terms.h)
+// Kernels (float64 arithmetic whatever the I/O type; the term layout is imu_normal.h, the fixed-order sum between them and the launch
+// sequence on the host imu_terms.h: one round, the velocities where the Huber solves have their residuals)
 //   ga_pair_kernel     one lane per pair: Y = [A | r] (3 x 7) or [A | T | -Q | rhs] (3 x 11; the columns of unknowns that are not
 //                      solved are exact zeros, and with s = 1 given Q moves to the right-hand side), the pair's covariance
 //                      C_i = L L^T, the whitened L^-1 Y and the pair's terms w Y^T Y: H upper triangle | c | excluded (0 or 1)
@@ -302,20 +303,24 @@ int run(const char* name, const void* rot_v, const void* pos_v, const void* dts_
     const T *rot = (const T*)rot_v, *pos = (const T*)pos_v, *dts = (const T*)dts_v, *dvel = (const T*)dvel_v, *dpos = (const T*)dpos_v;
     const int P = rows > 1 ? rows - 1 : 0;
     const Scratch sc(scratch, NT<NX>, P);
-    if (P > 0)
-        hipLaunchKernelGGL((ga_pair_kernel<NX, T>), dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, cov, weight,
-                           P, lever, scale, sc.terms);
-    if (sc.blocks > 0)
-        hipLaunchKernelGGL(ga_partial_kernel<NX>, dim3(sc.blocks), dim3(BLOCK), 0, s, (const double*)sc.terms, P, sc.blocks, sc.partial);
-    hipLaunchKernelGGL(ga_solve_kernel<NX>, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, jac ? 1 : 0, lever, scale, G, sc.status,
-                       out_x, out_H);
-    if (out_vel)
-        hipLaunchKernelGGL((ga_vel_kernel<NX, T>), dim3(rows / BLOCK + 1), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, rows,
-                           (const double*)out_x, (const int*)sc.status, out_vel);
-    int host[2];
-    if (const int rc = read_status(sc.status, s, host)) return rc;
-    if (host[0] != 0) return fail(ISLAM_ENOTPD, "%s: the normal matrix of %d pairs (%d excluded) is not positive definite", name, P, host[1]);
-    return host[1];
+    return run_rounds(
+        sc, P, ga_partial_kernel<NX>, 0.0, 0, s,
+        [&](const double*) {
+            hipLaunchKernelGGL((ga_pair_kernel<NX, T>), dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, cov,
+                               weight, P, lever, scale, sc.terms);
+        },
+        [&](int, int) {
+            hipLaunchKernelGGL(ga_solve_kernel<NX>, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, jac ? 1 : 0, lever, scale, G,
+                               sc.status, out_x, out_H);
+        },
+        [&] {
+            if (out_vel)
+                hipLaunchKernelGGL((ga_vel_kernel<NX, T>), dim3(rows / BLOCK + 1), dim3(BLOCK), 0, s, rot, pos, dts, dvel, dpos, jac, rows,
+                                   (const double*)out_x, (const int*)sc.status, out_vel);
+        },
+        [&](int excluded) {
+            return fail(ISLAM_ENOTPD, "%s: the normal matrix of %d pairs (%d excluded) is not positive definite", name, P, excluded);
+        });
 }
 
 // What the two entry points check alike, then the call.  poses: the names of the two pose arguments in the messages.
@@ -323,8 +328,7 @@ template <int NX>
 int solve(const char* name, const char* poses, const void* rot, const void* pos, const void* dts, const void* dvel, const void* dpos,
           const double* jac, const double* cov, const double* weight, int rows, int lever, int scale, double gravity_norm, double* out_x,
           double* out_H, double* out_vel, void* scratch, int dtype, void* stream) {
-    if (rows < 0) return fail(ISLAM_EARG, "%s: rows=%d", name, rows);
-    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "%s: dtype %d", name, dtype);
+    if (const int rc = check_entry(name, rows, dtype)) return rc;
     if (!(gravity_norm >= 0.0) || !std::isfinite(gravity_norm))
         return fail(ISLAM_EARG, "%s: gravity_norm %g (0 = free, > 0 = the known magnitude)", name, gravity_norm);
     if (!out_x || !scratch) return fail(ISLAM_EARG, "%s: out_x / scratch is NULL", name);

@@ -394,6 +394,7 @@ __global__ __launch_bounds__(256) void gyro_bias_solve_kernel(const double* __re
             const double w = weight ? weight[i] : 1.0;
             const T* a = rot_imu + 4 * (size_t)i;
             const T* b = rot_ref + 4 * (size_t)i;
+            // (imu_time_offset.hip's row_system copies these lines: behind one shared function some instantiation compiles differently)
             const double ax = -(double)a[0], ay = -(double)a[1], az = -(double)a[2], aw = (double)a[3];       // DR^T
             const double bx = (double)b[0], by = (double)b[1], bz = (double)b[2], bw = (double)b[3];
             double qx = aw * bx + ax * bw + ay * bz - az * by;
@@ -509,8 +510,7 @@ int islam_imu_preint_bias_jac(const void* dt, const void* gyro, const void* acc,
 
 int islam_imu_bias_correct(const double* jac, const void* rot, const void* vel, const void* pos, int rows, const double dbg[3],
                            const double dba[3], void* out_rot, void* out_vel, void* out_pos, int dtype, void* stream) {
-    if (rows < 0) return fail(ISLAM_EARG, "islam_imu_bias_correct: rows=%d", rows);
-    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "islam_imu_bias_correct: dtype %d", dtype);
+    if (const int rc = tsum::check_entry("islam_imu_bias_correct", rows, dtype)) return rc;
     if (!dbg || !dba) return fail(ISLAM_EARG, "islam_imu_bias_correct: dbg / dba are required (three values each, host memory)");
     if (rows > 0 && (!jac || !rot || !vel || !pos || !out_rot || !out_vel || !out_pos))
         return fail(ISLAM_EARG, "islam_imu_bias_correct: jac / rot / vel / pos / out_rot / out_vel / out_pos is NULL (rows=%d)", rows);
@@ -532,8 +532,7 @@ size_t islam_imu_gyro_bias_solve_scratch_bytes(int rows) { return sizeof(double)
 
 int islam_imu_gyro_bias_solve(const double* jac, const void* rot_imu, const void* rot_ref, const double* weight, int rows, double* out_dbg,
                               double* out_H, void* scratch, int dtype, void* stream) {
-    if (rows < 0) return fail(ISLAM_EARG, "islam_imu_gyro_bias_solve: rows=%d", rows);
-    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "islam_imu_gyro_bias_solve: dtype %d", dtype);
+    if (const int rc = tsum::check_entry("islam_imu_gyro_bias_solve", rows, dtype)) return rc;
     if (!out_dbg || !scratch) return fail(ISLAM_EARG, "islam_imu_gyro_bias_solve: out_dbg / scratch is NULL");
     if (rows > 0 && (!jac || !rot_imu || !rot_ref)) return fail(ISLAM_EARG, "islam_imu_gyro_bias_solve: jac / rot_imu / rot_ref is NULL (rows=%d)", rows);
     hipStream_t s = as_stream(stream);

@@ -4,7 +4,7 @@
 //
 // A rigid mount q satisfies qb_i (x) q = q (x) qc_i for every pair, M_i q = 0 with M_i = L(qb_i) - R(qc_i); q is the unit eigenvector of
 // the smallest eigenvalue of A = sum_i w_i rho_i M_i^T M_i.  Kernels (float64 arithmetic whatever the I/O type; the fixed-order sum
-// between them is imu_terms.h)
+// between them and the launch sequence of the rounds on the host are imu_terms.h)
 //   ex_pair_kernel     one lane per pair: the two quaternions normalised with w >= 0, in rounds >= 1 the Huber weight rho_i from the
 //                      previous round's estimate (read from scratch), the pair's terms w rho M^T M (upper triangle, 10) | excluded
 //                      (0 or 1) | takes part (0 or 1)
@@ -26,7 +26,6 @@ using namespace islam::tsum;
 namespace {
 
 constexpr int NT = 12;                // per-pair terms: A upper triangle by rows (10) | excluded (1) | takes part (1)
-constexpr int QHAT = 4;               // the last round's estimate in the scratch head (doubles 4 .. 7), behind the two status words
 constexpr int MAX_SWEEPS = 16;        // cap on the Jacobi sweeps (a 4x4 is at rounding level after 4 to 6)
 constexpr double OFF_REL = 0x1p-56;   // a sweep that finds every off-diagonal entry at or below this share of the largest diagonal ends
 
@@ -213,26 +212,27 @@ __global__ __launch_bounds__(BLOCK) void ex_res_kernel(const T* __restrict__ rot
 }
 
 template <class T>
-int run(const T* rot_imu, const T* rot_cam, const double* weight, int P, double delta, int rounds, double* out_q, double* out_eig,
+int run(const void* rot_imu_v, const void* rot_cam_v, const double* weight, int P, double delta, int rounds, double* out_q, double* out_eig,
         double* out_res, void* scratch, hipStream_t s) {
-    const int K = delta > 0.0 ? rounds : 0;
+    const T *rot_imu = (const T*)rot_imu_v, *rot_cam = (const T*)rot_cam_v;
     const Scratch sc(scratch, NT, P);
-    double* qhat = sc.head + QHAT;
-    for (int r = 0; r <= K; ++r) {
-        if (P > 0)
-            hipLaunchKernelGGL(ex_pair_kernel<T>, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot_imu, rot_cam, weight, P, delta,
-                               r > 0 ? (const double*)qhat : (const double*)nullptr, sc.terms);
-        if (sc.blocks > 0) hipLaunchKernelGGL(ex_partial_kernel, dim3(sc.blocks), dim3(BLOCK), 0, s, (const double*)sc.terms, P, sc.blocks, sc.partial);
-        hipLaunchKernelGGL(ex_solve_kernel, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, r == K ? 1 : 0, sc.status, qhat, out_q, out_eig);
-    }
-    if (out_res && P > 0)
-        hipLaunchKernelGGL(ex_res_kernel<T>, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, rot_imu, rot_cam, P, (const double*)qhat,
-                           (const int*)sc.status, out_res);
-    int host[2];
-    if (const int rc = read_status(sc.status, s, host)) return rc;
-    if (host[0] != 0)
-        return fail(ISLAM_ENOTPD, "islam_imu_extrinsic_rot_solve: no pair of %d takes part (%d excluded)", P, host[1]);
-    return host[1];
+    const dim3 grid((P + BLOCK - 1) / BLOCK);
+    return run_rounds(
+        sc, P, ex_partial_kernel, delta, rounds, s,
+        [&](const double* qhat) {
+            hipLaunchKernelGGL(ex_pair_kernel<T>, grid, dim3(BLOCK), 0, s, rot_imu, rot_cam, weight, P, delta, qhat, sc.terms);
+        },
+        [&](int, int last) {
+            hipLaunchKernelGGL(ex_solve_kernel, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, last, sc.status, sc.est, out_q, out_eig);
+        },
+        [&] {
+            if (out_res && P > 0)
+                hipLaunchKernelGGL(ex_res_kernel<T>, grid, dim3(BLOCK), 0, s, rot_imu, rot_cam, P, (const double*)sc.est, (const int*)sc.status,
+                                   out_res);
+        },
+        [&](int excluded) {
+            return fail(ISLAM_ENOTPD, "islam_imu_extrinsic_rot_solve: no pair of %d takes part (%d excluded)", P, excluded);
+        });
 }
 
 }  // namespace
@@ -245,17 +245,11 @@ size_t islam_imu_extrinsic_rot_solve_scratch_bytes(int rows) {
 
 int islam_imu_extrinsic_rot_solve(const void* rot_imu, const void* rot_cam, const double* weight, int rows, double delta, int rounds,
                                   double* out_q, double* out_eig, double* out_res, void* scratch, int dtype, void* stream) {
-    if (rows < 0) return fail(ISLAM_EARG, "islam_imu_extrinsic_rot_solve: rows=%d", rows);
-    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "islam_imu_extrinsic_rot_solve: dtype %d", dtype);
-    if (!(delta >= 0.0) || !std::isfinite(delta))
-        return fail(ISLAM_EARG, "islam_imu_extrinsic_rot_solve: delta %g (0 = no reweighting, > 0 = the Huber threshold in rad)", delta);
-    if (rounds < 0) return fail(ISLAM_EARG, "islam_imu_extrinsic_rot_solve: rounds=%d", rounds);
+    if (const int rc = check_entry("islam_imu_extrinsic_rot_solve", rows, dtype, delta, rounds)) return rc;
     if (!out_q || !out_eig || !scratch) return fail(ISLAM_EARG, "islam_imu_extrinsic_rot_solve: out_q / out_eig / scratch is NULL");
     if (rows > 0 && (!rot_imu || !rot_cam)) return fail(ISLAM_EARG, "islam_imu_extrinsic_rot_solve: rot_imu / rot_cam is NULL (rows=%d)", rows);
-    hipStream_t s = as_stream(stream);
-    if (dtype == ISLAM_F64)
-        return run<double>((const double*)rot_imu, (const double*)rot_cam, weight, rows, delta, rounds, out_q, out_eig, out_res, scratch, s);
-    return run<float>((const float*)rot_imu, (const float*)rot_cam, weight, rows, delta, rounds, out_q, out_eig, out_res, scratch, s);
+    return (dtype == ISLAM_F64 ? run<double> : run<float>)(rot_imu, rot_cam, weight, rows, delta, rounds, out_q, out_eig, out_res, scratch,
+                                                           as_stream(stream));
 }
 
 }  // extern "C"

@@ -2,9 +2,12 @@
 // by term (terms[q P + i]; a pair that takes no part stores zeros), and one workgroup adds them up in an order that depends on the
 // number of pairs alone, so a second call gives the same bits.  More than REACH pairs: a partial-sum launch first, one workgroup per
 // REACH pairs, and the solve kernel sums the partial sums the same way.  No atomics, no workgroup waits for another.  A solve of this
-// family is a pair kernel, a thin __global__ around partial_sum<NT> and a solve kernel that starts with block_sum<NT>.
+// family is a pair kernel, a thin __global__ around partial_sum<NT> and a solve kernel that starts with block_sum<NT>; on the host it is
+// check_entry, then run_rounds with the three launches of its own: the rounds, the partial-sum launch and the status are run_rounds'.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cmath>
 
 #include "common.h"
 
@@ -14,6 +17,7 @@ namespace tsum {
 constexpr int BLOCK = 256;
 constexpr int REACH = 4 * BLOCK;      // pairs one workgroup sums
 constexpr int HEAD = 32;              // doubles in front of the terms: the two status words first, the rest is the solve's own
+constexpr int EST = 4;                // the last round's estimate in the head (doubles 4 .. 7), behind the two status words
 
 // tot[q] = sum over c in [c0, c1) of src[q ld + c], in an order that depends on c1 - c0 alone: lane-strided partial sums, a shuffle
 // tree inside every wave, the four waves in order.  Ends on a barrier: every lane may read tot afterwards.
@@ -54,6 +58,7 @@ inline int partial_blocks(int P) { return P > REACH ? (P + REACH - 1) / REACH : 
 struct Scratch {
     int* status;                      // two words at the front of the head: solve failed (0 / 1), pairs excluded
     double* head;
+    double* est;                      // the last round's estimate, which the next round's pair kernel reweights by
     double* terms;
     double* partial;
     int blocks;                       // workgroups of the partial-sum launch, 0 = no such launch
@@ -61,7 +66,7 @@ struct Scratch {
     int count;                        // their number, which is also their leading dimension
 
     Scratch(void* scratch, int nt, int P)
-        : status(reinterpret_cast<int*>(scratch)), head(reinterpret_cast<double*>(scratch)), terms(head + HEAD),
+        : status(reinterpret_cast<int*>(scratch)), head(reinterpret_cast<double*>(scratch)), est(head + EST), terms(head + HEAD),
           partial(terms + (size_t)nt * P), blocks(partial_blocks(P)), src(blocks > 0 ? partial : terms), count(blocks > 0 ? blocks : P) {}
 
     static size_t bytes(int nt, int P) { return sizeof(double) * (HEAD + (size_t)nt * P + (size_t)nt * partial_blocks(P)); }
@@ -74,6 +79,36 @@ inline int read_status(const int* status, hipStream_t s, int (&host)[2]) {
     ISLAM_HIP_CHECK(hipMemcpyAsync(host, status, sizeof(host), hipMemcpyDeviceToHost, s));
     ISLAM_HIP_CHECK(hipStreamSynchronize(s));
     return ISLAM_OK;
+}
+
+// What the entry points of the family check alike, under the entry point's name; one that has no Huber rounds leaves delta and rounds out.
+inline int check_entry(const char* name, int rows, int dtype, double delta = 0.0, int rounds = 0) {
+    if (rows < 0) return fail(ISLAM_EARG, "%s: rows=%d", name, rows);
+    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "%s: dtype %d", name, dtype);
+    if (!(delta >= 0.0) || !std::isfinite(delta))
+        return fail(ISLAM_EARG, "%s: delta %g (0 = no reweighting, > 0 = the Huber threshold in rad)", name, delta);
+    if (rounds < 0) return fail(ISLAM_EARG, "%s: rounds=%d", name, rounds);
+    return ISLAM_OK;
+}
+
+// The launches of a solve over P pairs and the end of its call.  The first solve and, with delta > 0, `rounds` reweighted ones; every
+// round is row(prev) (the pair kernel; prev = the estimate of the round before in the scratch head, NULL in the first), the partial-sum
+// kernel `partial` when there are more than REACH pairs, and solve(first, last) (the one-workgroup solve kernel).  tail() enqueues
+// what reads the final estimate (residuals, velocities), under its own condition.  Returns the number of excluded pairs, not_pd(excluded)
+// (the solve's own ISLAM_ENOTPD message) when the solve kernel reports a failure, or the HIP error's code.
+template <class Row, class Solve, class Tail, class NotPd>
+int run_rounds(const Scratch& sc, int P, void (*partial)(const double*, int, int, double*), double delta, int rounds, hipStream_t s, Row row,
+               Solve solve, Tail tail, NotPd not_pd) {
+    const int K = delta > 0.0 ? rounds : 0;
+    for (int r = 0; r <= K; ++r) {
+        if (P > 0) row(r > 0 ? (const double*)sc.est : (const double*)nullptr);
+        if (sc.blocks > 0) hipLaunchKernelGGL(partial, dim3(sc.blocks), dim3(BLOCK), 0, s, (const double*)sc.terms, P, sc.blocks, sc.partial);
+        solve(r == 0 ? 1 : 0, r == K ? 1 : 0);
+    }
+    tail();
+    int host[2];
+    if (const int rc = read_status(sc.status, s, host)) return rc;
+    return host[0] != 0 ? not_pd(host[1]) : host[1];
 }
 
 }  // namespace tsum

@@ -6,7 +6,8 @@
 // i over the moved window is Exp(-ws td) DR_i Exp(we td) = DR_i Exp(u_i td + O(td^2)), u_i = we - DR_i^T ws, with ws, we the samples that
 // start at the row's two boundaries; with DR(b) = DR Exp(J_phig b) that leaves three equations per row, linear in x = [dbg(3); td]:
 //   e_i = Log(DR_i^T DRref_i) = J_phig,i dbg + u_i td.
-// Kernels (float64 arithmetic whatever the I/O type; the fixed-order sum between them is imu_terms.h)
+// Kernels (float64 arithmetic whatever the I/O type; the fixed-order sum between them and the launch sequence of the rounds on the host
+// are imu_terms.h)
 //   td_row_kernel      one lane per row: Y = [J_phig | u | e] (3 x 5; without the bias the columns of J are exact zeros), in rounds >= 1
 //                      the Huber weight rho_i from the previous round's x (read from scratch), the row's terms w rho Y^T Y: upper
 //                      triangle of the 4 x 4 (10) | c (4) | excluded (0 or 1)
@@ -34,7 +35,6 @@ using namespace islam::tsum;
 namespace {
 
 constexpr int NX = 4;                 // the layout of the unknowns: dbg (0..2) | td (3); NT<NX> terms per row (imu_normal.h): 10 | 4 | 1
-constexpr int XHAT = 4;               // the last round's x in the scratch head (doubles 4 .. 7), behind the two status words
 
 // Y = [J_phig | u | e] of row s; jac NULL: the columns of J are exact zeros.  True iff every entry is finite.
 template <class T>
@@ -43,6 +43,7 @@ __device__ __forceinline__ bool row_system(const double* __restrict__ jac, const
     const T* a = rot_imu + 4 * s;
     const T* b = rot_ref + 4 * s;
     // e = Log(DR^T DRref) as islam_imu_gyro_bias_solve takes it: the quaternion with w >= 0, k = 2 atan2(|vec|, w) / |vec|
+    // (a copy of gyro_bias_solve_kernel's lines: behind one shared function some instantiation of the kernels compiles differently)
     const double ax = -(double)a[0], ay = -(double)a[1], az = -(double)a[2], aw = (double)a[3];
     const double bx = (double)b[0], by = (double)b[1], bz = (double)b[2], bw = (double)b[3];
     double qx = aw * bx + ax * bw + ay * bz - az * by;
@@ -177,29 +178,30 @@ __global__ __launch_bounds__(BLOCK) void td_shift_kernel(const T* rot, const T* 
 }
 
 template <class T>
-int run(const double* jac, const T* rot_imu, const T* rot_ref, const T* rate_start, const T* rate_end, const double* weight, int rows,
-        int solve_bias, double delta, int rounds, double* out_x, double* out_H, double* out_res, void* scratch, hipStream_t s) {
-    const int K = delta > 0.0 ? rounds : 0;
+int run(const double* jac, const void* rot_imu_v, const void* rot_ref_v, const void* rate_start_v, const void* rate_end_v, const double* weight,
+        int rows, int solve_bias, double delta, int rounds, double* out_x, double* out_H, double* out_res, void* scratch, hipStream_t s) {
+    const T *rot_imu = (const T*)rot_imu_v, *rot_ref = (const T*)rot_ref_v, *rate_start = (const T*)rate_start_v, *rate_end = (const T*)rate_end_v;
     const Scratch sc(scratch, NT<NX>, rows);
-    double* xhat = sc.head + XHAT;
     const dim3 grid((rows + BLOCK - 1) / BLOCK);
-    for (int r = 0; r <= K; ++r) {
-        if (rows > 0)
-            hipLaunchKernelGGL(td_row_kernel<T>, grid, dim3(BLOCK), 0, s, jac, rot_imu, rot_ref, rate_start, rate_end, weight, rows, delta,
-                               r > 0 ? (const double*)xhat : (const double*)nullptr, sc.terms);
-        if (sc.blocks > 0) hipLaunchKernelGGL(td_partial_kernel, dim3(sc.blocks), dim3(BLOCK), 0, s, (const double*)sc.terms, rows, sc.blocks, sc.partial);
-        hipLaunchKernelGGL(td_solve_kernel, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, solve_bias, r == 0 ? 1 : 0, r == K ? 1 : 0,
-                           sc.status, xhat, out_x, out_H);
-    }
-    if (out_res && rows > 0)
-        hipLaunchKernelGGL(td_res_kernel<T>, grid, dim3(BLOCK), 0, s, jac, rot_imu, rot_ref, rate_start, rate_end, rows, (const double*)xhat,
-                           (const int*)sc.status, out_res);
-    int host[2];
-    if (const int rc = read_status(sc.status, s, host)) return rc;
-    if (host[0] != 0)
-        return fail(ISLAM_ENOTPD, "islam_imu_time_offset_solve: the normal matrix of %d rows (%d excluded) is not positive definite "
-                                  "(the offset needs a changing angular rate)", rows, host[1]);
-    return host[1];
+    return run_rounds(
+        sc, rows, td_partial_kernel, delta, rounds, s,
+        [&](const double* xhat) {
+            hipLaunchKernelGGL(td_row_kernel<T>, grid, dim3(BLOCK), 0, s, jac, rot_imu, rot_ref, rate_start, rate_end, weight, rows, delta, xhat,
+                               sc.terms);
+        },
+        [&](int first, int last) {
+            hipLaunchKernelGGL(td_solve_kernel, dim3(1), dim3(BLOCK), 0, s, sc.src, sc.count, sc.count, solve_bias, first, last, sc.status, sc.est,
+                               out_x, out_H);
+        },
+        [&] {
+            if (out_res && rows > 0)
+                hipLaunchKernelGGL(td_res_kernel<T>, grid, dim3(BLOCK), 0, s, jac, rot_imu, rot_ref, rate_start, rate_end, rows,
+                                   (const double*)sc.est, (const int*)sc.status, out_res);
+        },
+        [&](int excluded) {
+            return fail(ISLAM_ENOTPD, "islam_imu_time_offset_solve: the normal matrix of %d rows (%d excluded) is not positive definite "
+                                      "(the offset needs a changing angular rate)", rows, excluded);
+        });
 }
 
 }  // namespace
@@ -213,29 +215,22 @@ size_t islam_imu_time_offset_solve_scratch_bytes(int rows) {
 int islam_imu_time_offset_solve(const double* jac, const void* rot_imu, const void* rot_ref, const void* rate_start, const void* rate_end,
                                 const double* weight, int rows, int solve_bias, double delta, int rounds, double* out_x, double* out_H,
                                 double* out_res, void* scratch, int dtype, void* stream) {
-    if (rows < 0) return fail(ISLAM_EARG, "islam_imu_time_offset_solve: rows=%d", rows);
-    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "islam_imu_time_offset_solve: dtype %d", dtype);
+    const char* name = "islam_imu_time_offset_solve";
+    if (const int rc = check_entry(name, rows, dtype)) return rc;                     // solve_bias is reported before delta and rounds
     if (solve_bias != 0 && solve_bias != 1) return fail(ISLAM_EARG, "islam_imu_time_offset_solve: solve_bias=%d (0 or 1)", solve_bias);
-    if (!(delta >= 0.0) || !std::isfinite(delta))
-        return fail(ISLAM_EARG, "islam_imu_time_offset_solve: delta %g (0 = no reweighting, > 0 = the Huber threshold in rad)", delta);
-    if (rounds < 0) return fail(ISLAM_EARG, "islam_imu_time_offset_solve: rounds=%d", rounds);
+    if (const int rc = check_entry(name, rows, dtype, delta, rounds)) return rc;
     if (!out_x || !scratch) return fail(ISLAM_EARG, "islam_imu_time_offset_solve: out_x / scratch is NULL");
     if (rows > 0 && (!rot_imu || !rot_ref || !rate_start || !rate_end))
         return fail(ISLAM_EARG, "islam_imu_time_offset_solve: rot_imu / rot_ref / rate_start / rate_end is NULL (rows=%d)", rows);
     if (rows > 0 && solve_bias == 1 && !jac) return fail(ISLAM_EARG, "islam_imu_time_offset_solve: jac is NULL with solve_bias=1 (rows=%d)", rows);
-    hipStream_t s = as_stream(stream);
     const double* j = solve_bias ? jac : nullptr;         // without the bias the Jacobians are not read
-    if (dtype == ISLAM_F64)
-        return run<double>(j, (const double*)rot_imu, (const double*)rot_ref, (const double*)rate_start, (const double*)rate_end, weight, rows,
-                           solve_bias, delta, rounds, out_x, out_H, out_res, scratch, s);
-    return run<float>(j, (const float*)rot_imu, (const float*)rot_ref, (const float*)rate_start, (const float*)rate_end, weight, rows,
-                      solve_bias, delta, rounds, out_x, out_H, out_res, scratch, s);
+    return (dtype == ISLAM_F64 ? run<double> : run<float>)(j, rot_imu, rot_ref, rate_start, rate_end, weight, rows, solve_bias, delta, rounds, out_x,
+                                                           out_H, out_res, scratch, as_stream(stream));
 }
 
 int islam_imu_time_shift(const void* rot, const void* rate_start, const void* rate_end, int rows, double tau, void* out_rot, int dtype,
                          void* stream) {
-    if (rows < 0) return fail(ISLAM_EARG, "islam_imu_time_shift: rows=%d", rows);
-    if (dtype != ISLAM_F64 && dtype != ISLAM_F32) return fail(ISLAM_EARG, "islam_imu_time_shift: dtype %d", dtype);
+    if (const int rc = check_entry("islam_imu_time_shift", rows, dtype)) return rc;
     if (!std::isfinite(tau)) return fail(ISLAM_EARG, "islam_imu_time_shift: tau %g", tau);
     if (rows > 0 && (!rot || !rate_start || !rate_end || !out_rot))
         return fail(ISLAM_EARG, "islam_imu_time_shift: rot / rate_start / rate_end / out_rot is NULL (rows=%d)", rows);

@@ -104,6 +104,56 @@ class IMUModule:
                 gyros = d_gyro.to(self.dtype)
         return b0, dts, gyros, accels
 
+    def _start(self, st, end, b0, init, motion_mode):
+        """What integrate / integrate_both send ahead of the samples: prase_init (imu_integrator.py:11-28) packed into one transfer,
+        [pos(3) | rot(4) | vel(3)] (the motion rows ignore pos / vel: the kernel starts them from zero), and the frame offsets inside the
+        slice that starts at sample b0, on the host and on the device."""
+        np_dt = {torch.float32: np.float32, torch.float64: np.float64}[self.dtype]
+        i10 = np.zeros(10, dtype=np_dt)
+        i10[6] = 1.0
+        if init is not None:
+            i10[3:7] = np.asarray(init['rot'], dtype=np_dt)
+            if not motion_mode:
+                i10[0:3] = np.asarray(init['pos'], dtype=np_dt)
+                i10[7:10] = np.asarray(init['vel'], dtype=np_dt)
+        i10 = torch.from_numpy(i10).to(self.device)
+        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
+        return i10, seg_host, torch.from_numpy(seg_host).to(self.device)
+
+    def _as_device(self, a, dtype):
+        """An SO3, a tensor or an array as a detached tensor of ``dtype`` on the device."""
+        a = a.tensor() if hasattr(a, 'tensor') else torch.as_tensor(np.asarray(a))
+        return a.detach().to(dtype).to(self.device)
+
+    def _weight(self, weight):
+        """The optional weights of a solve as a float64 tensor on the device."""
+        return None if weight is None else torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+
+    def _window(self, st, end, gyro_bias=None, accel_bias=None, k=None):
+        """Frames [st, end] of the stored stream as the samples of a closed-form solve: (seg_host, seg, dts, gyros, accels), the frame
+        offsets inside the slice on the host and on the device and the contiguous slice with the given biases (device tensors, None =
+        none) subtracted, whatever ``optm_bias`` says; the denoiser is not run.  k: the frame boundaries moved by k whole samples and
+        clipped to the stored stream."""
+        sync = np.asarray(self.rgb2imu_sync[st:end + 1], dtype=np.int64)
+        if k is not None:
+            sync = np.clip(sync + k, 0, int(self.dts.shape[0]) - 1)
+        b0, b1 = int(sync[0]), int(sync[-1]) + 1
+        seg_host = np.ascontiguousarray(sync - b0, dtype=np.int64)
+        seg = torch.from_numpy(seg_host).to(self.device)
+        gyros, accels = self.gyros[b0:b1], self.accels[b0:b1]
+        if gyro_bias is not None:
+            gyros = gyros - gyro_bias.view(1, 3)
+        if accel_bias is not None:
+            accels = accels - accel_bias.view(1, 3)
+        return seg_host, seg, self.dts[b0:b1, 0].contiguous(), gyros.contiguous(), accels.contiguous()
+
+    def _motion_rows(self, dts, gyros, accels, seg, seg_host, jac):
+        """The motion rows of a window from the identity at gravity 0: their rotations and, with ``jac``, their bias Jacobians (else None)."""
+        init = torch.zeros(10, dtype=self.dtype, device=self.device)
+        init[6] = 1.0
+        _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
+        return rot, (ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True) if jac else None)
+
     def integrate_both(self, st, end, init=None, init_cov=None):
         """``integrate(st, end, init, motion_mode=False)`` and ``integrate(st, end, init, motion_mode=True)`` -- the pair the
         reference's loop asks for on every batch (train.py:200-215) -- from ONE pass over the samples (islam_imu_preint_both: the
@@ -113,16 +163,7 @@ class IMUModule:
         if self.train_denoiser and self.use_denoise_model:
             return self.integrate(st, end, init, motion_mode=False, init_cov=init_cov), self.integrate(st, end, init, motion_mode=True)
         b0, dts, gyros, accels = self._corrected(st, end)
-        np_dt = {torch.float32: np.float32, torch.float64: np.float64}[self.dtype]
-        i10 = np.zeros(10, dtype=np_dt)
-        i10[6] = 1.0
-        if init is not None:                        # prase_init: the motion rows ignore pos / vel (the kernel starts them from zero)
-            i10[3:7] = np.asarray(init['rot'], dtype=np_dt)
-            i10[0:3] = np.asarray(init['pos'], dtype=np_dt)
-            i10[7:10] = np.asarray(init['vel'], dtype=np_dt)
-        i10 = torch.from_numpy(i10).to(self.device)
-        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
-        seg = torch.from_numpy(seg_host).to(self.device)
+        i10, seg_host, seg = self._start(st, end, b0, init, False)
         with torch.no_grad():
             world, motion, packed = ops.imu_preint_both(dts.contiguous(), gyros.detach().contiguous(), accels.detach().contiguous(), seg,
                                                         seg_host, i10[0:3], i10[3:7], i10[7:10], self.gravity)
@@ -157,18 +198,7 @@ class IMUModule:
         (world mode: row 0 = ``init_cov``, None = zero; accumulated over the whole range in the body frame of its start;
         motion mode: every frame from zero), in the same copy."""
         b0, dts, gyros, accels = self._corrected(st, end)
-        # prase_init (imu_integrator.py:11-28) packed into one transfer: [pos(3) | rot(4) | vel(3)]
-        np_dt = {torch.float32: np.float32, torch.float64: np.float64}[self.dtype]
-        i10 = np.zeros(10, dtype=np_dt)
-        i10[6] = 1.0
-        if init is not None:
-            i10[3:7] = np.asarray(init['rot'], dtype=np_dt)
-            if not motion_mode:
-                i10[0:3] = np.asarray(init['pos'], dtype=np_dt)
-                i10[7:10] = np.asarray(init['vel'], dtype=np_dt)
-        i10 = torch.from_numpy(i10).to(self.device)
-        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
-        seg = torch.from_numpy(seg_host).to(self.device)
+        i10, seg_host, seg = self._start(st, end, b0, init, motion_mode)
         pos, rot, vel = ops.imu_preint(dts.contiguous(), gyros.contiguous(), accels.contiguous(), seg, seg_host,
                                        i10[0:3], i10[3:7], i10[7:10], self.gravity, motion_mode)
         cols = [pos, rot, vel]
@@ -190,22 +220,10 @@ class IMUModule:
         ``gyro_bias`` subtracted (whatever ``optm_bias`` says; the denoiser is not run), their rotations and bias Jacobians give
         dbg = argmin sum_i w_i |Log(DR_i^T ref_i) - J_phig,i dbg|^2 (islam_imu_gyro_bias_solve).  Returns (``gyro_bias + dbg`` (3) and
         the 3x3 normal matrix H, both on the CPU in float64).  The module is not changed."""
-        b0 = int(self.rgb2imu_sync[st])
-        b1 = int(self.rgb2imu_sync[end]) + 1
-        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
-        seg = torch.from_numpy(seg_host).to(self.device)
-        ref = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
-        ref = ref.detach().to(self.dtype).to(self.device)
-        if weight is not None:
-            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
         with torch.no_grad():
-            dts = self.dts[b0:b1, 0].contiguous()
-            gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
-            accels = self.accels[b0:b1].contiguous()
-            init = torch.zeros(10, dtype=self.dtype, device=self.device)
-            init[6] = 1.0
-            _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
-            jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
+            seg_host, seg, dts, gyros, accels = self._window(st, end, self.gyro_bias)
+            ref, weight = self._as_device(ref_rots, self.dtype), self._weight(weight)
+            rot, jac = self._motion_rows(dts, gyros, accels, seg, seg_host, True)
             dbg, H, _ = ops.imu_gyro_bias_solve(jac, rot, ref, weight)
             res = torch.cat((self.gyro_bias.to(torch.float64) + dbg, H.reshape(9))).cpu()
         return res[0:3].contiguous(), res[3:12].view(3, 3).contiguous()
@@ -230,8 +248,7 @@ class IMUModule:
         constant angular rate leaves T undetermined: IslamHipError (ISLAM_ENOTPD).  The module is not changed."""
         sync = np.asarray(self.rgb2imu_sync[st:end + 1], dtype=np.int64)
         n, S = len(sync) - 1, int(self.dts.shape[0])
-        ref = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
-        ref = ref.detach().to(self.dtype).to(self.device)
+        ref = self._as_device(ref_rots, self.dtype)
         w0 = np.ones(n) if weight is None else np.asarray(weight, dtype=np.float64).reshape(n).copy()
         slice_dts = self.dts[int(sync[0]):int(sync[-1]) + 1, 0].to(torch.float64).cpu().numpy()
         dt = float(slice_dts[0])
@@ -244,18 +261,9 @@ class IMUModule:
             for _ in range(1 + int(gn_rounds)):
                 moved = sync + k
                 inside = (moved[:-1] >= 0) & (moved[1:] <= S - 1)          # the window and the sample that starts at its end are stored
-                segc = np.clip(moved, 0, S - 1)
-                b0, b1 = int(segc[0]), int(segc[-1]) + 1
-                seg_host = np.ascontiguousarray(segc - b0, dtype=np.int64)
-                seg = torch.from_numpy(seg_host).to(self.device)
                 w = torch.from_numpy(np.where(inside, w0, 0.0)).to(self.device)
-                dts = self.dts[b0:b1, 0].contiguous()
-                gyros = (self.gyros[b0:b1] - torch.from_numpy(bias).to(self.dtype).to(self.device).view(1, 3)).contiguous()
-                accels = self.accels[b0:b1].contiguous()
-                init = torch.zeros(10, dtype=self.dtype, device=self.device)
-                init[6] = 1.0
-                _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
-                jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
+                seg_host, seg, dts, gyros, accels = self._window(st, end, torch.from_numpy(bias).to(self.dtype).to(self.device), k=k)
+                rot, jac = self._motion_rows(dts, gyros, accels, seg, seg_host, True)
                 rate_start, rate_end = gyros[seg[:-1]].contiguous(), gyros[seg[1:]].contiguous()
                 rot = ops.imu_time_shift(rot, rate_start, rate_end, tau)
                 dbg, td, H, res, _ = ops.imu_time_offset_solve(jac, rot, ref, rate_start, rate_end, w, solve_bias, delta, rounds)
@@ -270,14 +278,8 @@ class IMUModule:
         """The rows of the closed-form alignment solves over frames [st, end], on the device: (n, durations (n), dvel, dpos (n, 3) in the
         start-body frame of their frame, bias Jacobians (n, 9, 6), motion-mode covariances (n, 9, 9) or None).  The motion rows are
         integrated with gravity 0 and the module's current ``gyro_bias`` and ``accel_bias`` subtracted."""
-        b0 = int(self.rgb2imu_sync[st])
-        b1 = int(self.rgb2imu_sync[end]) + 1
-        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
-        seg = torch.from_numpy(seg_host).to(self.device)
+        seg_host, seg, dts, gyros, accels = self._window(st, end, self.gyro_bias, self.accel_bias)
         n = len(seg_host) - 1
-        dts = self.dts[b0:b1, 0].contiguous()
-        gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
-        accels = (self.accels[b0:b1] - self.accel_bias.view(1, 3)).contiguous()
         init = torch.zeros(10, dtype=self.dtype, device=self.device)
         init[6] = 1.0
         world, motion, _ = ops.imu_preint_both(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0)
@@ -289,7 +291,7 @@ class IMUModule:
         maxF = int(np.max(np.diff(seg_host))) if n > 0 else 0
         idx = seg[:-1, None] + torch.arange(max(maxF, 1), device=self.device)[None, :]
         inside = idx < seg[1:, None]
-        dur = torch.where(inside, dts.to(torch.float64)[idx.clamp(max=max(b1 - b0 - 1, 0))], torch.zeros((), dtype=torch.float64,
+        dur = torch.where(inside, dts.to(torch.float64)[idx.clamp(max=max(int(dts.shape[0]) - 1, 0))], torch.zeros((), dtype=torch.float64,
                           device=self.device)).sum(1).to(self.dtype)
         jac = ops.imu_preint_bias_jac(dts, gyros, accels, seg, seg_host, True)
         cov = ops.imu_preint_cov(dts, gyros, accels, seg, seg_host, self.gyro_cov, self.acc_cov, True) if use_cov else None
@@ -306,11 +308,7 @@ class IMUModule:
         of the poses, ``accel_bias + b`` (3), velocities (end - st + 1, 3), the 6x6 normal matrix H), on the CPU in float64.  The
         gravity is the world acceleration (v' = R a + g), about (0, 0, -9.81) in a z-up world.  Run ``estimate_gyro_bias`` first: the
         gyro-bias sensitivity of the increments is not part of this solve.  The module is not changed."""
-        rots = ref_rots.tensor() if hasattr(ref_rots, 'tensor') else torch.as_tensor(np.asarray(ref_rots))
-        rots = rots.detach().to(self.dtype).to(self.device)
-        poss = torch.as_tensor(np.asarray(ref_pos)).detach().to(self.dtype).to(self.device)
-        if weight is not None:
-            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+        rots, poss, weight = self._as_device(ref_rots, self.dtype), self._as_device(ref_pos, self.dtype), self._weight(weight)
         with torch.no_grad():
             n, dur, dvel, dpos, jac, cov = self._alignment_rows(st, end, use_cov)
             g, b, H, vel, _ = ops.imu_gravity_bias_solve(rots, poss, dur, dvel, dpos, jac, cov, weight, gravity_norm)
@@ -331,13 +329,8 @@ class IMUModule:
         between the frames and the scale needs acceleration: a stream without them raises IslamHipError (ISLAM_ENOTPD).  Order of calls:
         ``estimate_extrinsic_rotation``, then ``estimate_gyro_bias`` on the camera rotations conjugated by q, then this.  The module is
         not changed."""
-        cam = cam_rots.tensor() if hasattr(cam_rots, 'tensor') else torch.as_tensor(np.asarray(cam_rots))
-        ext = ext_rot.tensor() if hasattr(ext_rot, 'tensor') else torch.as_tensor(np.asarray(ext_rot))
-        cam = cam.detach().to(torch.float64).to(self.device)
-        ext = ext.detach().to(torch.float64).to(self.device).reshape(4)
-        poss = torch.as_tensor(np.asarray(cam_pos)).detach().to(self.dtype).to(self.device)
-        if weight is not None:
-            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
+        cam, ext = self._as_device(cam_rots, torch.float64), self._as_device(ext_rot, torch.float64).reshape(4)
+        poss, weight = self._as_device(cam_pos, self.dtype), self._weight(weight)
         with torch.no_grad():
             # R_i = Rc_i R_x^T: the quaternion product of cam_i and the conjugate of ext
             x, y, z, w = cam.unbind(-1)
@@ -368,22 +361,11 @@ class IMUModule:
         the lever arm (the translation of T_IL) with gravity, accelerometer bias and velocities (``estimate_gravity_accel_bias`` is the
         solve for a known lever arm).  Out of scope: the joint refinement of rotation and gyro bias; the time offset between the two
         sensors is ``estimate_time_offset``'s.  The module is not changed."""
-        b0 = int(self.rgb2imu_sync[st])
-        b1 = int(self.rgb2imu_sync[end]) + 1
-        seg_host = np.ascontiguousarray(self.rgb2imu_sync[st:end + 1] - b0, dtype=np.int64)
-        seg = torch.from_numpy(seg_host).to(self.device)
-        n = len(seg_host) - 1
-        cam = cam_rots.tensor() if hasattr(cam_rots, 'tensor') else torch.as_tensor(np.asarray(cam_rots))
-        cam = cam.detach().to(self.dtype).to(self.device)
-        if weight is not None:
-            weight = torch.as_tensor(np.asarray(weight), dtype=torch.float64).to(self.device)
         with torch.no_grad():
-            dts = self.dts[b0:b1, 0].contiguous()
-            gyros = (self.gyros[b0:b1] - self.gyro_bias.view(1, 3)).contiguous()
-            accels = self.accels[b0:b1].contiguous()
-            init = torch.zeros(10, dtype=self.dtype, device=self.device)
-            init[6] = 1.0
-            _, rot, _ = ops.imu_preint(dts, gyros, accels, seg, seg_host, init[0:3], init[3:7], init[7:10], 0.0, True)
+            seg_host, seg, dts, gyros, accels = self._window(st, end, self.gyro_bias)
+            n = len(seg_host) - 1
+            cam, weight = self._as_device(cam_rots, self.dtype), self._weight(weight)
+            rot, _ = self._motion_rows(dts, gyros, accels, seg, seg_host, False)
             q, eig, res, _ = ops.imu_extrinsic_rot_solve(rot, cam, weight, delta, rounds)
             host = torch.cat((q, eig, res)).cpu()
         q, eig, res = host[0:4].contiguous(), host[4:8].contiguous(), host[8:8 + n].contiguous()

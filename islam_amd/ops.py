@@ -1113,10 +1113,15 @@ def bn_train_(x, bn, relu=False, res=None):
 
 
 # --------------------------------------------------------------------------- IMU
+def _dtype_code(dtype):
+    """ISLAM_F32 / ISLAM_F64 of include/islam_hip.h; KeyError for any other dtype"""
+    return {torch.float32: 0, torch.float64: 1}[dtype]
+
+
 def _imu_preint_raw(dt, gyro, acc, seg, seg_host, init_pos, init_rot, init_vel, gravity, motion_mode):
     require_cuda(dt, gyro, acc, seg)
     dtype = dt.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    code = _dtype_code(dtype)
     dev = dt.device
     nframes = int(seg_host.shape[0]) - 1
     S = int(dt.shape[0])
@@ -1138,7 +1143,7 @@ def imu_preint_both(dt, gyro, acc, seg, seg_host, init_pos, init_rot, init_vel, 
     nframes + 1 rows, (pos, rot, vel) with nframes rows), bit-identical to two imu_preint calls.  Forward values only."""
     require_cuda(dt, gyro, acc, seg)
     dtype = dt.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    code = _dtype_code(dtype)
     dev = dt.device
     nframes = int(seg_host.shape[0]) - 1
     S = int(dt.shape[0])
@@ -1172,7 +1177,7 @@ class _ImuPreint(torch.autograd.Function):
     def backward(ctx, g_pos, g_rot, g_vel):
         gyro, acc, dt, seg, scratch = ctx.saved_tensors
         nframes, gravity, motion = ctx.meta
-        code = {torch.float32: 0, torch.float64: 1}[dt.dtype]
+        code = _dtype_code(dt.dtype)
         c = lambda g: None if g is None else g.to(dt.dtype).contiguous()
         g_pos, g_rot, g_vel = c(g_pos), c(g_rot), c(g_vel)
         g_gyro, g_acc = torch.zeros_like(gyro), torch.zeros_like(acc)
@@ -1208,7 +1213,7 @@ def imu_preint_cov(dt, gyro, acc, seg, seg_host, gyro_cov, acc_cov, motion_mode,
     gyro_cov_s / acc_cov_s: optional (S, 3) device tensors of per-sample variances in dt's dtype.  Forward values only."""
     require_cuda(dt, gyro, acc, seg, init_cov, gyro_cov_s, acc_cov_s)
     dtype = dt.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    code = _dtype_code(dtype)
     dev = dt.device
     nframes = int(seg_host.shape[0]) - 1
     S = int(dt.shape[0])
@@ -1236,7 +1241,7 @@ def imu_preint_bias_jac(dt, gyro, acc, seg, seg_host, motion_mode, init_jac=None
     include/islam_hip.h): (rows, 9, 6) float64 on the device, rows [dphi, dv, dp], columns [b_g | b_a]; rows = nframes in motion
     mode, nframes + 1 in world mode (row 0 = ``init_jac``, a 9x6 tensor or None = zero).  Forward values only."""
     require_cuda(dt, gyro, acc, seg, init_jac)
-    code = {torch.float32: 0, torch.float64: 1}[dt.dtype]
+    code = _dtype_code(dt.dtype)
     dev = dt.device
     nframes = int(seg_host.shape[0]) - 1
     S = int(dt.shape[0])
@@ -1284,7 +1289,7 @@ def imu_bias_correct(jac, rot, vel, pos, dbg, dba):
     require_cuda(jac, rot, vel, pos)
     rows = _rows_of(jac, rot)
     dtype = rot.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    code = _dtype_code(dtype)
     with torch.no_grad():
         rot = _imu_arg(rot, dtype, (rows, 4), 'rotations')
         vel, pos = (_imu_arg(t, dtype, (rows, 3), 'vel / pos', got=False) for t in (vel, pos))
@@ -1296,6 +1301,26 @@ def imu_bias_correct(jac, rot, vel, pos, dbg, dba):
     return tuple(out)
 
 
+def _imu_solve(symbol, rows, dtype, dev, args, mid, sizes):
+    """The call of a closed-form IMU solve.  args: (tensor or None, dtype, shape, name) in the order of the entry point, made detached,
+    contiguous and shape-checked by _imu_arg; mid: the values between rows and the outputs; sizes: the float64 outputs, carved in this
+    order from one device buffer; the scratch is sized by `symbol`_scratch_bytes(rows).  A negative return code raises IslamHipError.
+    Returns (the outputs as flat views of the buffer, the number of excluded rows)."""
+    code = _dtype_code(dtype)
+    with torch.no_grad():
+        args = [_imu_arg(*a) for a in args]
+        out = torch.empty(sum(sizes), dtype=torch.float64, device=dev)
+        outs, o = [], 0
+        for n in sizes:
+            outs.append(out[o:o + n])
+            o += n
+        scratch = torch.empty(getattr(lib(), symbol + '_scratch_bytes')(rows), dtype=torch.uint8, device=dev)
+        rc = getattr(lib(), symbol)(*[ptr(t) for t in args], rows, *mid, *[ptr(o) for o in outs], ptr(scratch), code, stream_ptr(dev))
+    if rc < 0:
+        check(rc)
+    return outs, int(rc)
+
+
 def imu_gyro_bias_solve(jac, rot_imu, rot_ref, weight=None):
     """Closed-form gyro-bias step (islam_imu_gyro_bias_solve): dbg minimises sum_i w_i |Log(rot_imu_i^T rot_ref_i) - J_phig,i dbg|^2.
     Returns (dbg (3) float64, H (3, 3) float64, number of rows excluded for a non-finite residual); the bias to subtract from the
@@ -1303,44 +1328,24 @@ def imu_gyro_bias_solve(jac, rot_imu, rot_ref, weight=None):
     require_cuda(jac, rot_imu, rot_ref, weight)
     rows = _rows_of(jac, rot_imu)
     dtype = rot_imu.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
-    dev = jac.device
-    with torch.no_grad():
-        rot_imu, rot_ref = _imu_arg(rot_imu, dtype, (rows, 4), 'rotations'), _imu_arg(rot_ref, dtype, (rows, 4), 'rot_ref')
-        weight = _imu_arg(weight, torch.float64, (rows,), 'weight')
-        out = torch.empty(12, dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib().islam_imu_gyro_bias_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
-        rc = lib().islam_imu_gyro_bias_solve(ptr(jac), ptr(rot_imu), ptr(rot_ref), ptr(weight), rows, ptr(out[0:3]), ptr(out[3:12]),
-                                             ptr(scratch), code, stream_ptr(dev))
-    if rc < 0:
-        check(rc)
-    return out[0:3], out[3:12].view(3, 3), int(rc)
+    (dbg, H), bad = _imu_solve('islam_imu_gyro_bias_solve', rows, dtype, jac.device, (
+        (jac, torch.float64, (rows, 9, 6), 'jac'), (rot_imu, dtype, (rows, 4), 'rotations'), (rot_ref, dtype, (rows, 4), 'rot_ref'),
+        (weight, torch.float64, (rows,), 'weight')), (), (3, 9))
+    return dbg, H.view(3, 3), bad
 
 
 def _imu_alignment_solve(symbol, nx, names, rot, pos, dts, dvel, dpos, jac, cov, weight, flags, gravity_norm):
-    """What imu_gravity_bias_solve (nx = 6) and imu_lever_scale_solve (nx = 10) share: the arguments made contiguous, the outputs and the
-    scratch, the call of `symbol` (flags: the ints between rows and gravity_norm), the return code.  Returns (x (nx), H (nx, nx),
-    vel (rows + 1, 3), number of excluded pairs)."""
+    """What imu_gravity_bias_solve (nx = 6) and imu_lever_scale_solve (nx = 10) share: the arguments of `symbol` (flags: the ints between
+    rows and gravity_norm).  Returns (x (nx), H (nx, nx), vel (rows + 1, 3), number of excluded pairs)."""
     require_cuda(rot, pos, dts, dvel, dpos, jac, cov, weight)
     rows = int(dts.shape[0])
     dtype = dts.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
-    dev = dts.device
-    xh = nx + nx * nx
-    with torch.no_grad():
-        io = [_imu_arg(t, dtype, shape, name) for t, shape, name in (
-            (rot, (rows + 1, 4), names[0]), (pos, (rows + 1, 3), names[1]), (dts, (rows,), 'dts'), (dvel, (rows, 3), 'dvel'),
-            (dpos, (rows, 3), 'dpos'))]
-        f64 = [_imu_arg(t, torch.float64, shape, name) for t, shape, name in (
-            (jac, (rows, 9, 6), 'jac'), (cov, (rows, 9, 9), 'cov'), (weight, (max(rows - 1, 0),), 'weight'))]
-        out = torch.empty(xh + 3 * (rows + 1), dtype=torch.float64, device=dev)
-        scratch = torch.empty(getattr(lib(), symbol + '_scratch_bytes')(rows), dtype=torch.uint8, device=dev)
-        rc = getattr(lib(), symbol)(*[ptr(t) for t in io], *[ptr(t) for t in f64], rows, *flags,
-                                    c_double(0.0 if gravity_norm is None else float(gravity_norm)), ptr(out[0:nx]), ptr(out[nx:xh]),
-                                    ptr(out[xh:]), ptr(scratch), code, stream_ptr(dev))
-    if rc < 0:
-        check(rc)
-    return out[0:nx], out[nx:xh].view(nx, nx), out[xh:].view(rows + 1, 3), int(rc)
+    (x, H, vel), bad = _imu_solve(symbol, rows, dtype, dts.device, (
+        (rot, dtype, (rows + 1, 4), names[0]), (pos, dtype, (rows + 1, 3), names[1]), (dts, dtype, (rows,), 'dts'),
+        (dvel, dtype, (rows, 3), 'dvel'), (dpos, dtype, (rows, 3), 'dpos'), (jac, torch.float64, (rows, 9, 6), 'jac'),
+        (cov, torch.float64, (rows, 9, 9), 'cov'), (weight, torch.float64, (max(rows - 1, 0),), 'weight')),
+        (*flags, c_double(0.0 if gravity_norm is None else float(gravity_norm))), (nx, nx * nx, 3 * (rows + 1)))
+    return x, H.view(nx, nx), vel.view(rows + 1, 3), bad
 
 
 def imu_gravity_bias_solve(rot_ref, pos_ref, dts, dvel, dpos, jac=None, cov=None, weight=None, gravity_norm=None):
@@ -1382,18 +1387,10 @@ def imu_extrinsic_rot_solve(rot_imu, rot_cam, weight=None, delta=None, rounds=4)
     require_cuda(rot_imu, rot_cam, weight)
     rows = int(rot_imu.shape[0])
     dtype = rot_imu.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
-    dev = rot_imu.device
-    with torch.no_grad():
-        rot_imu, rot_cam = _imu_arg(rot_imu, dtype, (rows, 4), 'rot_imu'), _imu_arg(rot_cam, dtype, (rows, 4), 'rot_cam')
-        weight = _imu_arg(weight, torch.float64, (rows,), 'weight')
-        out = torch.empty(8 + rows, dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib().islam_imu_extrinsic_rot_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
-        rc = lib().islam_imu_extrinsic_rot_solve(ptr(rot_imu), ptr(rot_cam), ptr(weight), rows, c_double(0.0 if delta is None else float(delta)),
-                                                 int(rounds), ptr(out[0:4]), ptr(out[4:8]), ptr(out[8:]), ptr(scratch), code, stream_ptr(dev))
-    if rc < 0:
-        check(rc)
-    return out[0:4], out[4:8], out[8:], int(rc)
+    (q, eig, res), bad = _imu_solve('islam_imu_extrinsic_rot_solve', rows, dtype, rot_imu.device, (
+        (rot_imu, dtype, (rows, 4), 'rot_imu'), (rot_cam, dtype, (rows, 4), 'rot_cam'), (weight, torch.float64, (rows,), 'weight')),
+        (c_double(0.0 if delta is None else float(delta)), int(rounds)), (4, 4, rows))
+    return q, eig, res, bad
 
 
 def imu_time_offset_solve(jac, rot_imu, rot_ref, rate_start, rate_end, weight=None, solve_bias=True, delta=None, rounds=4):
@@ -1408,23 +1405,13 @@ def imu_time_offset_solve(jac, rot_imu, rot_ref, rate_start, rate_end, weight=No
     require_cuda(jac, rot_imu, rot_ref, rate_start, rate_end, weight)
     rows = int(rot_imu.shape[0])
     dtype = rot_imu.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
-    dev = rot_imu.device
     if solve_bias and jac is None:
         raise ValueError('jac: the (rows, 9, 6) bias Jacobians are required with solve_bias=True')
-    with torch.no_grad():
-        jac = _imu_arg(jac, torch.float64, (rows, 9, 6), 'jac')
-        rot_imu, rot_ref = _imu_arg(rot_imu, dtype, (rows, 4), 'rot_imu'), _imu_arg(rot_ref, dtype, (rows, 4), 'rot_ref')
-        rate_start, rate_end = _imu_arg(rate_start, dtype, (rows, 3), 'rate_start'), _imu_arg(rate_end, dtype, (rows, 3), 'rate_end')
-        weight = _imu_arg(weight, torch.float64, (rows,), 'weight')
-        out = torch.empty(20 + rows, dtype=torch.float64, device=dev)
-        scratch = torch.empty(lib().islam_imu_time_offset_solve_scratch_bytes(rows), dtype=torch.uint8, device=dev)
-        rc = lib().islam_imu_time_offset_solve(ptr(jac), ptr(rot_imu), ptr(rot_ref), ptr(rate_start), ptr(rate_end), ptr(weight), rows,
-                                               int(bool(solve_bias)), c_double(0.0 if delta is None else float(delta)), int(rounds),
-                                               ptr(out[0:4]), ptr(out[4:20]), ptr(out[20:]), ptr(scratch), code, stream_ptr(dev))
-    if rc < 0:
-        check(rc)
-    return out[0:3], out[3], out[4:20].view(4, 4), out[20:], int(rc)
+    (x, H, res), bad = _imu_solve('islam_imu_time_offset_solve', rows, dtype, rot_imu.device, (
+        (jac, torch.float64, (rows, 9, 6), 'jac'), (rot_imu, dtype, (rows, 4), 'rot_imu'), (rot_ref, dtype, (rows, 4), 'rot_ref'),
+        (rate_start, dtype, (rows, 3), 'rate_start'), (rate_end, dtype, (rows, 3), 'rate_end'), (weight, torch.float64, (rows,), 'weight')),
+        (int(bool(solve_bias)), c_double(0.0 if delta is None else float(delta)), int(rounds)), (4, 16, rows))
+    return x[0:3], x[3], H.view(4, 4), res, bad
 
 
 def imu_time_shift(rot, rate_start, rate_end, tau):
@@ -1434,7 +1421,7 @@ def imu_time_shift(rot, rate_start, rate_end, tau):
     require_cuda(rot, rate_start, rate_end)
     rows = int(rot.shape[0])
     dtype = rot.dtype
-    code = {torch.float32: 0, torch.float64: 1}[dtype]
+    code = _dtype_code(dtype)
     with torch.no_grad():
         rot = _imu_arg(rot, dtype, (rows, 4), 'rot')
         rate_start, rate_end = _imu_arg(rate_start, dtype, (rows, 3), 'rate_start'), _imu_arg(rate_end, dtype, (rows, 3), 'rate_end')
