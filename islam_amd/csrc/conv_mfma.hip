@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "../../include/islam_hip.h"
+#include "bn_finalize_dev.h"
 #include "common.h"
 
 // scripts/conv_probe.sh builds experiment variants of this file (never the product library): ISLAM_CONV_PROBE=1 skips the multiply
@@ -852,43 +853,8 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_kernel(const float* _
                                                           float* __restrict__ scale_shift) {
     // FIN_THREADS threads = (FIN_THREADS / C) slices of the partial blocks x C channels (C <= 256); slices are combined in slice
     // order (deterministic).  With 256 threads a 32-channel layer walked 32 blocks per slice: 9 us for a 16 KB reduction.
-    __shared__ double ls[FIN_THREADS], lq[FIN_THREADS];
-    const int nsl = FIN_THREADS / C, c = threadIdx.x % C, sl = threadIdx.x / C;
-    double s = 0.0, q = 0.0;
-    if (sl < nsl) {
-        const int per = (nblk + nsl - 1) / nsl, b0 = sl * per, b1 = min(nblk, b0 + per);
-        int b = b0;
-        for (; b + 4 <= b1; b += 4) {                     // four independent loads in flight per accumulator pair
-            const float s0 = partial[((size_t)b * 2) * C + c], q0 = partial[((size_t)b * 2 + 1) * C + c];
-            const float s1 = partial[((size_t)b * 2 + 2) * C + c], q1 = partial[((size_t)b * 2 + 3) * C + c];
-            const float s2 = partial[((size_t)b * 2 + 4) * C + c], q2 = partial[((size_t)b * 2 + 5) * C + c];
-            const float s3 = partial[((size_t)b * 2 + 6) * C + c], q3 = partial[((size_t)b * 2 + 7) * C + c];
-            s += ((double)s0 + (double)s1) + ((double)s2 + (double)s3);
-            q += ((double)q0 + (double)q1) + ((double)q2 + (double)q3);
-        }
-        for (; b < b1; ++b) {
-            s += (double)partial[((size_t)b * 2) * C + c];
-            q += (double)partial[((size_t)b * 2 + 1) * C + c];
-        }
-    }
-    ls[threadIdx.x] = s;
-    lq[threadIdx.x] = q;
-    __syncthreads();
-    if (threadIdx.x < C) {
-        s = 0.0;
-        q = 0.0;
-        for (int j = 0; j < nsl; ++j) { s += ls[j * C + c]; q += lq[j * C + c]; }
-        const double mean = s / count;
-        const double var = fmax(q / count - mean * mean, 0.0);
-        const double sc = (double)weight[c] / sqrt(var + eps);
-        scale_shift[c] = (float)sc;
-        scale_shift[C + c] = (float)((double)bias[c] - mean * sc);
-        if (running_mean) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-        }
-    }
+    bn_finalize_block<FIN_THREADS>([&](int b, int j, int c) { return partial[((size_t)b * 2 + j) * C + c]; }, nblk, C, count, weight, bias,
+                                   running_mean, running_var, momentum, eps, scale_shift);
     if (threadIdx.x == 0 && num_batches) *num_batches += 1;
 }
 

@@ -25,9 +25,10 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
 
 #include "../../include/islam_hip.h"
+#include "bf16_dev.h"
+#include "bn_finalize_dev.h"
 #include "common.h"
 #include "conv_ws.h"
 
@@ -49,43 +50,9 @@ namespace {
 
 using namespace islam;
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));     // a REAL vector value: copies of HIP's uint4 struct become memcpy
-                                                                 // intrinsics that keep a register array in scratch
-
 constexpr int TW = 32;                               // (KC: input channels per staged chunk, template parameter; PS = KC + 8: bf16
                                                      // elements per LDS pixel / weight row -- 80- or 48-byte stride, conflict-free 16-byte reads)
 constexpr int THREADS = 256;                         // 4 waves x ROWS pixel rows: tile 32 x 4*ROWS pixels
-
-// Compile-time loop: the index is an integral_constant, so the register arrays it indexes are split into scalars as soon as the
-// lambda is inlined.  With `#pragma unroll` the indices only become constant after the (late) unroll pass; an array that is
-// still indexed dynamically when SROA runs is left to AMDGPUPromoteAlloca, which keeps anything above 128 bytes in SCRATCH -- the
-// prefetched weights (nine uint4) then go through scratch_store right after their global loads, which forces a vmcnt wait
-// in front of the multiply phase and serialises the two (found in the ISA; 194 -> see DESIGN.md).
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {      // round-to-nearest-even, one v_cvt_pk_bf16_f32
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float lo16(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float hi16(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-// ReLU of packed bf16: a negative bf16 is a negative int16 (sign-magnitude), so max(., 0) on the int16 lanes is the ReLU: ONE v_pk_max_i16 per pair
-typedef short s16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned relu2(unsigned t) {
-    const s16x2_t z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, t), z));
-}
 
 // Register blocking: a wave owns ROWS pixel rows x TN channels; for a horizontal tap offset s it reads the ROWS + K - 1 halo rows
 // once and reuses each for up to K vertical taps, and a weight operand for all its rows.  ROWS = 4 with TN = 32 (0.75 LDS
@@ -434,7 +401,6 @@ __global__ __launch_bounds__(FF_THREADS) void fold_finalize_kernel(const float* 
                                                                    float* __restrict__ running_mean, float* __restrict__ running_var,
                                                                    long long* __restrict__ num_batches, double momentum, double eps,
                                                                    float* __restrict__ scale_shift, int* __restrict__ counter) {
-    __shared__ double ls[FF_THREADS], lq[FF_THREADS];
     __shared__ int s_last;
     const int j = blockIdx.x, C2 = 2 * C;
     for (int c = threadIdx.x; c < C2; c += FF_THREADS) {
@@ -448,42 +414,8 @@ __global__ __launch_bounds__(FF_THREADS) void fold_finalize_kernel(const float* 
     __syncthreads();
     if (!s_last) return;
     // ---- the last workgroup: bn_finalize_kernel over folded[RED_BLOCKS][2][C], read past this XCD's L2
-    const int nsl = FF_THREADS / C, c = threadIdx.x % C, sl = threadIdx.x / C;
-    double s = 0.0, q = 0.0;
-    if (sl < nsl) {
-        const int per = (RED_BLOCKS + nsl - 1) / nsl, b0 = sl * per, b1 = min(RED_BLOCKS, b0 + per);
-        int b = b0;
-        for (; b + 4 <= b1; b += 4) {
-            const float s0 = ldc_f32(&folded[((size_t)b * 2) * C + c]), q0 = ldc_f32(&folded[((size_t)b * 2 + 1) * C + c]);
-            const float s1 = ldc_f32(&folded[((size_t)b * 2 + 2) * C + c]), q1 = ldc_f32(&folded[((size_t)b * 2 + 3) * C + c]);
-            const float s2 = ldc_f32(&folded[((size_t)b * 2 + 4) * C + c]), q2 = ldc_f32(&folded[((size_t)b * 2 + 5) * C + c]);
-            const float s3 = ldc_f32(&folded[((size_t)b * 2 + 6) * C + c]), q3 = ldc_f32(&folded[((size_t)b * 2 + 7) * C + c]);
-            s += ((double)s0 + (double)s1) + ((double)s2 + (double)s3);
-            q += ((double)q0 + (double)q1) + ((double)q2 + (double)q3);
-        }
-        for (; b < b1; ++b) {
-            s += (double)ldc_f32(&folded[((size_t)b * 2) * C + c]);
-            q += (double)ldc_f32(&folded[((size_t)b * 2 + 1) * C + c]);
-        }
-    }
-    ls[threadIdx.x] = s;
-    lq[threadIdx.x] = q;
-    __syncthreads();
-    if (threadIdx.x < C) {
-        s = 0.0;
-        q = 0.0;
-        for (int k = 0; k < nsl; ++k) { s += ls[k * C + c]; q += lq[k * C + c]; }
-        const double mean = s / count;
-        const double var = fmax(q / count - mean * mean, 0.0);
-        const double sc = (double)weight[c] / sqrt(var + eps);
-        scale_shift[c] = (float)sc;
-        scale_shift[C + c] = (float)((double)bias[c] - mean * sc);
-        if (running_mean) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-        }
-    }
+    bn_finalize_block<FF_THREADS>([&](int b, int j, int c) { return ldc_f32(&folded[((size_t)b * 2 + j) * C + c]); }, RED_BLOCKS, C, count,
+                                  weight, bias, running_mean, running_var, momentum, eps, scale_shift);
     if (threadIdx.x == 0) {
         if (num_batches) *num_batches += 1;
         *counter = 0;
@@ -502,78 +434,131 @@ __global__ __launch_bounds__(FF_THREADS) void finalize_rows_kernel(const float* 
                                                                    float* __restrict__ running_mean, float* __restrict__ running_var,
                                                                    long long* __restrict__ num_batches, double momentum, double eps,
                                                                    float* __restrict__ scale_shift) {
-    __shared__ double ls[FF_THREADS], lq[FF_THREADS];
-    const int nsl = FF_THREADS / C, c = threadIdx.x % C, sl = threadIdx.x / C, C2 = 2 * C;
-    auto row = [&](int b, int which) {                  // folded[b][which][c]
+    const int C2 = 2 * C;
+    auto row = [&](int b, int j, int c) {               // folded[b + j / 2][j % 2][c]
+        const int which = j & 1;
         float v = 0.0f;
 #pragma unroll
         for (int k = 0; k < NF; ++k) {
-            const int r = b + k * RED_BLOCKS;
+            const int r = b + (j >> 1) + k * RED_BLOCKS;
             const float t = partial[(size_t)min(r, nblk - 1) * C2 + which * C + c];      // (always a load, then a select: a branch per
             v += r < nblk ? t : 0.0f;                                                    //  row would serialise the eight loads of a group)
         }
         return v;
     };
-    double s = 0.0, q = 0.0;
-    if (sl < nsl) {
-        const int per = (RED_BLOCKS + nsl - 1) / nsl, b0 = sl * per, b1 = min(RED_BLOCKS, b0 + per);
-        int b = b0;
-        for (; b + 4 <= b1; b += 4) {
-            const float s0 = row(b, 0), q0 = row(b, 1), s1 = row(b + 1, 0), q1 = row(b + 1, 1);
-            const float s2 = row(b + 2, 0), q2 = row(b + 2, 1), s3 = row(b + 3, 0), q3 = row(b + 3, 1);
-            s += ((double)s0 + (double)s1) + ((double)s2 + (double)s3);
-            q += ((double)q0 + (double)q1) + ((double)q2 + (double)q3);
-        }
-        for (; b < b1; ++b) {
-            s += (double)row(b, 0);
-            q += (double)row(b, 1);
-        }
-    }
-    ls[threadIdx.x] = s;
-    lq[threadIdx.x] = q;
-    __syncthreads();
-    if (threadIdx.x < C) {
-        s = 0.0;
-        q = 0.0;
-        for (int k = 0; k < nsl; ++k) { s += ls[k * C + c]; q += lq[k * C + c]; }
-        const double mean = s / count;
-        const double var = fmax(q / count - mean * mean, 0.0);
-        const double sc = (double)weight[c] / sqrt(var + eps);
-        scale_shift[c] = (float)sc;
-        scale_shift[C + c] = (float)((double)bias[c] - mean * sc);
-        if (running_mean) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unb);
-        }
-    }
+    bn_finalize_block<FF_THREADS>(row, RED_BLOCKS, C, count, weight, bias, running_mean, running_var, momentum, eps, scale_shift);
     if (threadIdx.x == 0 && num_batches) *num_batches += 1;
 }
 
+static int tiles_of(int B, int H, int W, int th) { return ((W + TW - 1) / TW) * ((H + th - 1) / th) * B; }
+
+// One call of a convolution, as an entry point describes it: the operands, the shape the kernel runs on (transposed: B * 4 parity-class
+// images; flow with dilation d: B d^2 sub-grid images of H / d x W / d pixels; stride 2: H, W are the OUTPUT's), and the properties the
+// kernel selection (conv_run) reads.  sl.xs == 0: dense tensors; sl.Wf == 0: W.
+struct ConvCall {
+    const unsigned short* x; const unsigned short* wp; const float* in_affine; const float* bias; const unsigned short* res;
+    unsigned short* y; float* partial;
+    int B, Cin, H, W, Cout, relu, in_relu;
+    hipStream_t s;
+    int ksize, stride;
+    Slices sl{0, 0, 0, 0, nullptr, 0, 0, 0.0f, 1, 0, 0, 0, 0};
+    Src2 s2{nullptr, 0, 0};                                  // x2 != nullptr: two sources (the TWO kernels)
+    bool flow = false;                                       // the flow net's epilogue (FLOW kernels)
+    bool persistent = false;                                 // the entry's own rule allows the persistent kernels (conv_ws.hip, conv_ws32.hip)
+    int kc = 32;                                             // input channels per staged chunk of the stride-1 tile kernels (ISLAM_CONV_KC)
+    int CinP() const { return (Cin + 31) / 32 * 32; }
+    int CoutP() const { return (Cout + 63) / 64 * 64; }
+};
+
+// launches one instantiation; rows: the rows of per-workgroup partial sums it writes (one per pixel tile and image)
 template <int TN, int KS, int ROWS, int KC, bool FLOW = false, int S = 1, bool TWO = false>
-int launch(const unsigned short* x, const unsigned short* wp, const float* in_affine, const float* bias, const unsigned short* res,
-           unsigned short* y, float* partial, int B, int Cin, int CinP, int H, int W, int Cout, int CoutP, int relu, int in_relu, hipStream_t s,
-           Slices sl = Slices{0, 0, 0, 0, nullptr, 0, 0, 0.0f, 1, 0, 0, 0, 0}, Src2 s2 = Src2{nullptr, 0, 0}) {
-    if (sl.xs == 0) { sl.xs = Cin; sl.ys = Cout; }           // dense tensors
-    if (sl.Wf == 0) sl.Wf = W;
+int launch(const ConvCall& c, int& rows) {
     constexpr int TH = 4 * ROWS, P = KS / 2, NPIX = ((TH - 1) * S + 1 + 2 * P) * ((TW - 1) * S + 1 + 2 * P), TAPS = KS * KS, PS = KC + 8;
     const size_t conv_lds = ((size_t)NPIX * PS + (size_t)TAPS * TN * PS + 8) * sizeof(unsigned short);
     const size_t epi_lds = std::max((size_t)TW * TH * (TN + 8) * sizeof(unsigned short), (size_t)THREADS * 17 * sizeof(float));
     const size_t lds = std::max(conv_lds, epi_lds);
-    int dev = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr_set[64] = {};
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)conv_nhwc_kernel<TN, KS, ROWS, KC, FLOW, S, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        attr_set[dev] = true;
-    }
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int nblk_n = (Cout + TN - 1) / TN, nwork = tiles_x * tiles_y * B * nblk_n;      // TH = tile_h(Cout): TN = 64 <=> Cout > 32
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)conv_nhwc_kernel<TN, KS, ROWS, KC, FLOW, S, TWO>}, 128 * 1024, lds_set)) return rc;
+    const int tiles_x = (c.W + TW - 1) / TW, tiles_y = (c.H + TH - 1) / TH;
+    const int nblk_n = (c.Cout + TN - 1) / TN, nwork = tiles_x * tiles_y * c.B * nblk_n;
     dim3 grid(nblk_n > 1 ? 8 * ((nwork + 7) / 8) : nwork);
-    hipLaunchKernelGGL((conv_nhwc_kernel<TN, KS, ROWS, KC, FLOW, S, TWO>), grid, dim3(THREADS), lds, s, x, wp, in_affine, bias, res, y, partial, Cin, CinP,
-                       H, W, Cout, CoutP, relu, tiles_x, tiles_x * tiles_y, in_relu, sl, B, nblk_n, s2);
+    hipLaunchKernelGGL((conv_nhwc_kernel<TN, KS, ROWS, KC, FLOW, S, TWO>), grid, dim3(THREADS), lds, c.s, c.x, c.wp, c.in_affine, c.bias, c.res, c.y,
+                       c.partial, c.Cin, c.CinP(), c.H, c.W, c.Cout, c.CoutP(), c.relu, tiles_x, tiles_x * tiles_y, c.in_relu, c.sl, c.B, nblk_n, c.s2);
+    ISLAM_LAUNCH_CHECK();
+    rows = tiles_of(c.B, c.H, c.W, TH);
+    return ISLAM_OK;
+}
+// the 64-channel block with RW rows per wave when Cout > 32, the 32-channel block with RN rows otherwise
+template <int KS, int RW, int RN, int KC, bool FLOW = false, int S = 1, bool TWO = false>
+int launch_wide_or_narrow(const ConvCall& c, int& rows) {
+    return c.Cout > 32 ? launch<64, KS, RW, KC, FLOW, S, TWO>(c, rows) : launch<32, KS, RN, KC, FLOW, S, TWO>(c, rows);
+}
+
+// The 64-channel-block 3x3 kernel with FOUR pixel rows per wave and 16-channel chunks (conv_nhwc_kernel<64, 3, 4, 16>): tile 32 x 16,
+// 0.5 instead of 0.83 LDS operand reads per MFMA, the same MFMAs per barrier pair, 47 KB of LDS and 244 VGPRs (two workgroups per
+// CU as before).  Measured (B = 16, scripts/conv_nhwc_bench.py, alternating runs): 352->128 @224x320 1000 -> 910 us (1.02 PFLOP/s),
+// 128->128 @112x160 110 -> 111 us, 64->128 the same, 64->64 39 -> 44 us: it pays where the chunk loop dominates the workgroup's life,
+// so it serves the layers with at least 256 input channels (ISLAM_CONV_R4=0: never, =1: every 3x3 layer with more than 32 outputs).
+// ... AND enough 32 x 16 tiles to fill the chip twice: on the flow net's DenseNet layers (up to 565 input channels, but maps of
+// 112 x 160 and smaller at B = 8) the larger tile costs parallelism -- flow forward 3.21 -> 3.50 ms with the rule on channels alone.
+bool conv_r4(int Cin, int Cout, int ksize, int B, int H, int W) {
+    static const int mode = [] { const char* e = std::getenv("ISLAM_CONV_R4"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
+    if (ksize != 3 || Cout <= 32 || mode == 0) return false;
+    if (mode == 1) return true;
+    const long long work = (long long)((W + 31) / 32) * ((H + 15) / 16) * B * ((Cout + 63) / 64);
+    static const long long min_work = [] { const char* e = std::getenv("ISLAM_CONV_R4_WORK"); return e ? std::atoll(e) : 1024ll; }();      // (A/B runs)
+    return Cin >= 256 && work >= min_work;
+}
+
+// THE kernel selection, from the properties of the call; every conv_nhwc_kernel instantiation of the library is named here, and each
+// family names only the combinations it launches.  rows: the rows of partial sums the chosen kernel writes into c.partial.
+int conv_run(ConvCall c, int& rows) {
+    if (c.sl.xs == 0) { c.sl.xs = c.Cin; c.sl.ys = c.Cout; }
+    if (c.sl.Wf == 0) c.sl.Wf = c.W;
+    const bool two = c.s2.x2 != nullptr, r4 = conv_r4(c.Cin, c.Cout, c.ksize, c.B, c.H, c.W);
+    if (c.flow) return r4 ? launch<64, 3, 4, 16, true>(c, rows) : launch_wide_or_narrow<3, 2, 4, 32, true>(c, rows);
+    if (c.sl.tc) return two ? launch_wide_or_narrow<2, 2, 4, 32, false, 1, true>(c, rows) : launch_wide_or_narrow<2, 2, 4, 32>(c, rows);
+    if (c.stride == 2) {
+        if (c.ksize == 3) return launch_wide_or_narrow<3, 1, 2, 16, false, 2>(c, rows);
+        if (c.ksize == 1) return launch_wide_or_narrow<1, 2, 2, 16, false, 2>(c, rows);
+        return two ? launch_wide_or_narrow<2, 2, 2, 16, false, 2, true>(c, rows) : launch_wide_or_narrow<2, 2, 2, 16, false, 2>(c, rows);
+    }
+    // stride 1, kernel size 1 or 3.  The persistent kernels take raw bf16 in and out (BatchNorm + ReLU of the input on load at most)
+    if (c.persistent && conv_ws_applies(c.Cin, c.Cout, c.ksize, c.B, c.H, c.W)) {           // weight-stationary 64 / 128 -> 128 (conv_ws.hip)
+        rows = conv_ws_blocks(c.B, c.H, c.W);
+        return conv_ws_launch(c.x, c.wp, c.in_affine, c.y, c.partial, c.B, c.Cin, c.H, c.W, c.Cout, c.CoutP(), c.sl.xs, c.sl.xoff, c.sl.ys, c.sl.yoff, c.s);
+    }
+    if (c.persistent && conv_ws32_applies(c.Cin, c.Cout, c.ksize, c.B, c.H, c.W)) {         // persistent 32 -> 32 (conv_ws32.hip)
+        rows = conv_ws32_blocks(c.B, c.H, c.W);
+        return conv_ws32_launch(c.x, c.wp, c.in_affine, c.y, c.partial, c.B, c.H, c.W, c.CoutP(), c.sl.xs, c.sl.xoff, c.sl.ys, c.sl.yoff, c.s);
+    }
+    if (r4) return launch<64, 3, 4, 16>(c, rows);
+    if (c.kc == 16) return c.ksize == 3 ? launch_wide_or_narrow<3, 2, 4, 16>(c, rows) : launch_wide_or_narrow<1, 2, 4, 16>(c, rows);
+    return c.ksize == 3 ? launch_wide_or_narrow<3, 2, 4, 32>(c, rows) : launch_wide_or_narrow<1, 2, 4, 32>(c, rows);
+}
+int conv_run(const ConvCall& c) { int rows; return conv_run(c, rows); }
+
+// the `rows` rows of partial sums at the head of `stats` -> the RED_BLOCKS folded rows behind the caller's row area of `area_rows` rows
+int fold_stats(float* stats, int rows, int area_rows, int Cout, hipStream_t s) {
+    hipLaunchKernelGGL(partial_fold_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, stats, rows, 2 * Cout, stats + (size_t)area_rows * 2 * Cout);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
+}
+
+// The argument checks the entry points share; fn: the entry's name.  ISLAM_OK or the failure, its message in the error buffer.
+int check_shape(const char* fn, int B, int H, int W, int Cin, int Cout) {
+    if (B < 1 || H < 1 || W < 1 || Cin < 8 || (Cin & 7) || Cout < 8 || (Cout & 7))
+        return fail(ISLAM_EARG, "%s: bad shape (Cin=%d, Cout=%d must be multiples of 8)", fn, Cin, Cout);
+    return ISLAM_OK;
+}
+int check_ksize_1_or_3(const char* fn, int ksize) {
+    return ksize != 1 && ksize != 3 ? fail(ISLAM_EARG, "%s: kernel size %d (1 or 3)", fn, ksize) : ISLAM_OK;
+}
+int check_out_slice(const char* fn, int ytot, int yoff, int Cout) {
+    return (ytot & 7) || (yoff & 7) || yoff < 0 || yoff + Cout > ytot ? fail(ISLAM_EARG, "%s: output slice %d+%d of %d", fn, yoff, Cout, ytot) : ISLAM_OK;
+}
+int check_offsets(const char* fn, size_t pixels, int channels) {          // the kernels index with 32-bit element offsets
+    return pixels * channels >= ((size_t)1 << 31) ? fail(ISLAM_EARG, "%s: tensor too large for 32-bit offsets", fn) : ISLAM_OK;
 }
 
 }  // namespace
@@ -594,25 +579,6 @@ size_t islam_conv_nhwc_packed_elems(int Cin, int Cout, int ksize) {
     return (size_t)ksize * ksize * CoutP * CinP;
 }
 
-// The 64-channel-block 3x3 kernel with FOUR pixel rows per wave and 16-channel chunks (conv_nhwc_kernel<64, 3, 4, 16>): tile 32 x 16,
-// 0.5 instead of 0.83 LDS operand reads per MFMA, the same MFMAs per barrier pair, 47 KB of LDS and 244 VGPRs (two workgroups per
-// CU as before).  Measured (B = 16, scripts/conv_nhwc_bench.py, alternating runs): 352->128 @224x320 1000 -> 910 us (1.02 PFLOP/s),
-// 128->128 @112x160 110 -> 111 us, 64->128 the same, 64->64 39 -> 44 us: it pays where the chunk loop dominates the workgroup's life,
-// so it serves the layers with at least 256 input channels (ISLAM_CONV_R4=0: never, =1: every 3x3 layer with more than 32 outputs).
-// ... AND enough 32 x 16 tiles to fill the chip twice: on the flow net's DenseNet layers (up to 565 input channels, but maps of
-// 112 x 160 and smaller at B = 8) the larger tile costs parallelism -- flow forward 3.21 -> 3.50 ms with the rule on channels alone.
-static bool conv_r4(int Cin, int Cout, int ksize, int B, int H, int W) {
-    static const int mode = [] { const char* e = std::getenv("ISLAM_CONV_R4"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
-    if (ksize != 3 || Cout <= 32 || mode == 0) return false;
-    if (mode == 1) return true;
-    const long long work = (long long)((W + 31) / 32) * ((H + 15) / 16) * B * ((Cout + 63) / 64);
-    static const long long min_work = [] { const char* e = std::getenv("ISLAM_CONV_R4_WORK"); return e ? std::atoll(e) : 1024ll; }();      // (A/B runs)
-    return Cin >= 256 && work >= min_work;
-}
-static int tile_h(int Cout, int Cin = 0, int ksize = 0, int B = 0, int H = 0, int W = 0) {
-    return Cout > 32 ? (conv_r4(Cin, Cout, ksize, B, H, W) ? 16 : 8) : 16;
-}
-static int tiles_of(int B, int H, int W, int th) { return ((W + TW - 1) / TW) * ((H + th - 1) / th) * B; }
 // rows of the per-workgroup partial sums a caller must provide room for (the smallest tile any kernel variant uses for this Cout)
 int islam_conv_nhwc_stat_blocks(int B, int H, int W, int Cout) { return tiles_of(B, H, W, Cout > 32 ? 8 : 16); }
 
@@ -620,44 +586,28 @@ size_t islam_conv_nhwc_stats_floats(int B, int H, int W, int Cout) {
     return (size_t)islam_conv_nhwc_stat_blocks(B, H, W, Cout) * 2 * Cout + (size_t)RED_BLOCKS * 2 * Cout;
 }
 
+// Which calls may go to the persistent kernels is each entry point's own rule, and the three rules DIFFER: islam_conv_nhwc_bf16 and
+// islam_conv_nhwc_bf16_into refuse any in_relu, islam_conv_nhwc_bf16_bn admits in_relu together with in_affine (the kernels apply the
+// BatchNorm + ReLU of the input on load).  On purpose or by accident -- reconciling them changes which kernel runs, so they stay as they
+// are; tests/test_conv_nhwc_gpu.py::test_persistent_kernel_eligibility_per_entry_point records them.
 int islam_conv_nhwc_bf16(const uint16_t* x, const uint16_t* wpacked, const float* in_affine, const float* bias, const uint16_t* res,
                          uint16_t* y, float* stats, int B, int Cin, int H, int W, int Cout, int ksize, int relu, void* stream) {
     const int in_relu = (relu >> 1) & 1;       // bit 1: ReLU of the INPUT while it is staged (hourglass.py:25-33 `self.relu(x)` before conv1)
     relu &= 1;
-    if (B < 1 || H < 1 || W < 1 || Cin < 8 || (Cin & 7) || Cout < 8 || (Cout & 7))
-        return fail(ISLAM_EARG, "islam_conv_nhwc_bf16: bad shape (Cin=%d, Cout=%d must be multiples of 8)", Cin, Cout);
-    if (ksize != 1 && ksize != 3) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16: kernel size %d (1 or 3)", ksize);
+    if (int rc = check_shape(__func__, B, H, W, Cin, Cout)) return rc;
+    if (int rc = check_ksize_1_or_3(__func__, ksize)) return rc;
     if (stats && (bias || res || relu)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16: statistics go with the raw output (no bias / residual / ReLU)");
-    if ((size_t)B * H * W * std::max(Cin, Cout) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-    hipStream_t s = (hipStream_t)stream;
-    const bool wide = Cout > 32;
+    if (int rc = check_offsets(__func__, (size_t)B * H * W, std::max(Cin, Cout))) return rc;
     // input channels per staged chunk: 32.  ISLAM_CONV_KC=16 selects 16-channel chunks (44 KB of LDS: three workgroups per CU
     // instead of two, but twice the barriers) -- measured 10-20 % slower on every shape of the stereo net, kept for A/B runs
     static const bool kc16 = [] { const char* e = std::getenv("ISLAM_CONV_KC"); return e && e[0] == '1'; }();
-    int rc;
-    const bool ws = !bias && !res && !relu && !in_relu && conv_ws_applies(Cin, Cout, ksize, B, H, W);      // weight-stationary persistent kernel (conv_ws.hip)
-    const bool ws32 = !bias && !res && !relu && !in_relu && conv_ws32_applies(Cin, Cout, ksize, B, H, W);  // persistent 32 -> 32 kernel (conv_ws32.hip)
-#define ISLAM_CONV_LAUNCH(TN_, KS_, ROWS_)                                                                                              \
-    (kc16 ? launch<TN_, KS_, ROWS_, 16>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s) \
-          : launch<TN_, KS_, ROWS_, 32>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s))
-    if (ws) rc = conv_ws_launch(x, wpacked, in_affine, y, stats, B, Cin, H, W, Cout, CoutP, Cin, 0, Cout, 0, s);
-    else if (ws32) rc = conv_ws32_launch(x, wpacked, in_affine, y, stats, B, H, W, CoutP, Cin, 0, Cout, 0, s);
-    else if (conv_r4(Cin, Cout, ksize, B, H, W))
-        rc = launch<64, 3, 4, 16>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s);
-    else if (ksize == 3) rc = wide ? ISLAM_CONV_LAUNCH(64, 3, 2) : ISLAM_CONV_LAUNCH(32, 3, 4);
-    else rc = wide ? ISLAM_CONV_LAUNCH(64, 1, 2) : ISLAM_CONV_LAUNCH(32, 1, 4);
-#undef ISLAM_CONV_LAUNCH
-    if (rc != ISLAM_OK) return rc;
-    if (stats) {
-        const int nblk = ws ? conv_ws_blocks(B, H, W) : ws32 ? conv_ws32_blocks(B, H, W) : tiles_of(B, H, W, tile_h(Cout, Cin, ksize, B, H, W));      // rows of partial sums the launch above wrote
-        hipLaunchKernelGGL(partial_fold_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, stats, nblk, 2 * Cout,
-                           stats + (size_t)islam_conv_nhwc_stat_blocks(B, H, W, Cout) * 2 * Cout);
-        ISLAM_LAUNCH_CHECK();
-    }
-    return ISLAM_OK;
+    ConvCall c{x, wpacked, in_affine, bias, res, y, stats, B, Cin, H, W, Cout, relu, in_relu, (hipStream_t)stream, ksize, 1};
+    c.kc = kc16 ? 16 : 32;
+    c.persistent = !bias && !res && !relu && !in_relu;
+    int rows = 0;
+    if (int rc = conv_run(c, rows)) return rc;
+    return stats ? fold_stats(stats, rows, islam_conv_nhwc_stat_blocks(B, H, W, Cout), Cout, c.s) : ISLAM_OK;
 }
-
 
 // islam_conv_nhwc_bf16 with the result written into channels [yoff, yoff + Cout) of a (B,H,W,ytot) bf16 tensor -- straight into a
 // concatenation under construction (Network/StereoNet7.py:103-105: torch.cat((left features, right features, half-resolution image))
@@ -666,24 +616,14 @@ int islam_conv_nhwc_bf16_into(const uint16_t* x, const uint16_t* wpacked, const 
                               int yoff, int B, int Cin, int H, int W, int Cout, int ksize, int relu, void* stream) {
     const int in_relu = (relu >> 1) & 1;
     relu &= 1;
-    if (B < 1 || H < 1 || W < 1 || Cin < 8 || (Cin & 7) || Cout < 8 || (Cout & 7))
-        return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_into: bad shape (Cin=%d, Cout=%d must be multiples of 8)", Cin, Cout);
-    if (ksize != 1 && ksize != 3) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_into: kernel size %d (1 or 3)", ksize);
-    if ((ytot & 7) || (yoff & 7) || yoff < 0 || yoff + Cout > ytot) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_into: output slice %d+%d of %d", yoff, Cout, ytot);
-    if ((size_t)B * H * W * std::max(Cin, ytot) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_into: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-    const Slices sl{Cin, 0, ytot, yoff, nullptr, 0, 0, 0.0f, 1, W, 0, 0, 0};
-    hipStream_t s = (hipStream_t)stream;
-    const bool wide = Cout > 32;
-    if (!bias && !relu && !in_relu && conv_ws_applies(Cin, Cout, ksize, B, H, W))
-        return conv_ws_launch(x, wpacked, in_affine, y, nullptr, B, Cin, H, W, Cout, CoutP, Cin, 0, ytot, yoff, s);
-    if (!bias && !relu && !in_relu && conv_ws32_applies(Cin, Cout, ksize, B, H, W))
-        return conv_ws32_launch(x, wpacked, in_affine, y, nullptr, B, H, W, CoutP, Cin, 0, ytot, yoff, s);
-    if (conv_r4(Cin, Cout, ksize, B, H, W)) return launch<64, 3, 4, 16>(x, wpacked, in_affine, bias, nullptr, y, nullptr, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s, sl);
-    if (ksize == 3) return wide ? launch<64, 3, 2, 32>(x, wpacked, in_affine, bias, nullptr, y, nullptr, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s, sl)
-                                : launch<32, 3, 4, 32>(x, wpacked, in_affine, bias, nullptr, y, nullptr, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s, sl);
-    return wide ? launch<64, 1, 2, 32>(x, wpacked, in_affine, bias, nullptr, y, nullptr, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s, sl)
-                : launch<32, 1, 4, 32>(x, wpacked, in_affine, bias, nullptr, y, nullptr, B, Cin, CinP, H, W, Cout, CoutP, relu, in_relu, s, sl);
+    if (int rc = check_shape(__func__, B, H, W, Cin, Cout)) return rc;
+    if (int rc = check_ksize_1_or_3(__func__, ksize)) return rc;
+    if (int rc = check_out_slice(__func__, ytot, yoff, Cout)) return rc;
+    if (int rc = check_offsets(__func__, (size_t)B * H * W, std::max(Cin, ytot))) return rc;
+    ConvCall c{x, wpacked, in_affine, bias, nullptr, y, nullptr, B, Cin, H, W, Cout, relu, in_relu, (hipStream_t)stream, ksize, 1,
+               Slices{Cin, 0, ytot, yoff, nullptr, 0, 0, 0.0f, 1, W, 0, 0, 0}};
+    c.persistent = !bias && !relu && !in_relu;
+    return conv_run(c);
 }
 
 // Conv2d(Cin, Cout, k, stride = 2, padding = k / 2) on the same kernel (template parameter S = 2): the feature extractor's layer2 opens
@@ -696,37 +636,19 @@ int islam_conv_nhwc_bf16_s2(const uint16_t* x, const uint16_t* wpacked, const fl
                             void* stream) {
     const int in_relu = (relu >> 1) & 1;
     relu &= 1;
-    if (B < 1 || Hi < 1 || Wi < 1 || Cin < 8 || (Cin & 7) || Cout < 8 || (Cout & 7))
-        return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2: bad shape (Cin=%d, Cout=%d must be multiples of 8)", Cin, Cout);
+    if (int rc = check_shape(__func__, B, Hi, Wi, Cin, Cout)) return rc;
     if (ksize < 1 || ksize > 3) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2: kernel size %d (1, 2 or 3)", ksize);
     const int P = ksize / 2, Hmax = (Hi + 2 * P - ksize) / 2 + 1, Wmax = (Wi + 2 * P - ksize) / 2 + 1;
     if (Ho < 1 || Wo < 1 || Ho > Hmax || Wo > Wmax) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2: output %dx%d of at most %dx%d", Ho, Wo, Hmax, Wmax);
     if (stats && (bias || res || relu)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2: statistics go with the raw output (no bias / residual / ReLU)");
-    if ((size_t)B * Hi * Wi * std::max(Cin, Cout) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-    const Slices sl{Cin, 0, Cout, 0, nullptr, 0, 0, 0.0f, 1, Wo, 0, Hi, Wi};
-    hipStream_t s = (hipStream_t)stream;
-    const bool wide = Cout > 32;
-    int rc, th;
-    if (ksize == 3) { th = wide ? 4 : 8;
-        rc = wide ? launch<64, 3, 1, 16, false, 2>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu, in_relu, s, sl)
-                  : launch<32, 3, 2, 16, false, 2>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu, in_relu, s, sl);
-    } else if (ksize == 2) { th = 8;
-        rc = wide ? launch<64, 2, 2, 16, false, 2>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu, in_relu, s, sl)
-                  : launch<32, 2, 2, 16, false, 2>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu, in_relu, s, sl);
-    } else { th = 8;
-        rc = wide ? launch<64, 1, 2, 16, false, 2>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu, in_relu, s, sl)
-                  : launch<32, 1, 2, 16, false, 2>(x, wpacked, in_affine, bias, res, y, stats, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu, in_relu, s, sl);
-    }
-    if (rc != ISLAM_OK) return rc;
-    if (stats) {
-        // (the stride-2 variants use tiles of 4 or 8 rows: islam_conv_nhwc_stats_floats(B, Ho, Wo, Cout) sizes `stats` for 8-row tiles when
-        //  Cout > 32 and 16-row tiles otherwise -- the caller sizes it with islam_conv_nhwc_s2_stats_floats)
-        const int nblk = tiles_of(B, Ho, Wo, th);
-        hipLaunchKernelGGL(partial_fold_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, stats, nblk, 2 * Cout, stats + (size_t)tiles_of(B, Ho, Wo, 4) * 2 * Cout);
-        ISLAM_LAUNCH_CHECK();
-    }
-    return ISLAM_OK;
+    if (int rc = check_offsets(__func__, (size_t)B * Hi * Wi, std::max(Cin, Cout))) return rc;
+    ConvCall c{x, wpacked, in_affine, bias, res, y, stats, B, Cin, Ho, Wo, Cout, relu, in_relu, (hipStream_t)stream, ksize, 2,
+               Slices{Cin, 0, Cout, 0, nullptr, 0, 0, 0.0f, 1, Wo, 0, Hi, Wi}};
+    int rows = 0;
+    if (int rc = conv_run(c, rows)) return rc;
+    // (the stride-2 variants use tiles of 4 or 8 rows: islam_conv_nhwc_stats_floats(B, Ho, Wo, Cout) sizes `stats` for 8-row tiles when
+    //  Cout > 32 and 16-row tiles otherwise -- the caller sizes it with islam_conv_nhwc_s2_stats_floats)
+    return stats ? fold_stats(stats, rows, tiles_of(B, Ho, Wo, 4), Cout, c.s) : ISLAM_OK;
 }
 
 // floats of `stats` for islam_conv_nhwc_bf16_s2 (per-tile partial sums for the smallest tile any of its variants uses + the folded block)
@@ -744,53 +666,38 @@ int islam_conv_nhwc_bf16_bn(const uint16_t* x, const uint16_t* wpacked, const fl
                             int* counter, void* stream) {
     if (B < 1 || H < 1 || W < 1 || Cin < 8 || (Cin & 7) || Cout < 8 || (Cout & 7) || Cout > 256)
         return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_bn: bad shape (Cin=%d, Cout=%d: multiples of 8, Cout <= 256)", Cin, Cout);
-    if (ksize != 1 && ksize != 3) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_bn: kernel size %d (1 or 3)", ksize);
+    if (int rc = check_ksize_1_or_3(__func__, ksize)) return rc;
     if (!stats || !weight || !bias || !scale_shift || !counter) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_bn: null argument");
-    if ((size_t)B * H * W * std::max(Cin, Cout) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_bn: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
+    if (int rc = check_offsets(__func__, (size_t)B * H * W, std::max(Cin, Cout))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool wide = Cout > 32;
-    const int ir = in_relu ? 1 : 0;
-    int rc;
-    const bool ws = (!ir || in_affine) && conv_ws_applies(Cin, Cout, ksize, B, H, W);
-    const bool ws32 = (!ir || in_affine) && conv_ws32_applies(Cin, Cout, ksize, B, H, W);
-    if (ws) rc = conv_ws_launch(x, wpacked, in_affine, y, stats, B, Cin, H, W, Cout, CoutP, Cin, 0, Cout, 0, s);
-    else if (ws32) rc = conv_ws32_launch(x, wpacked, in_affine, y, stats, B, H, W, CoutP, Cin, 0, Cout, 0, s);
-    else if (conv_r4(Cin, Cout, ksize, B, H, W)) rc = launch<64, 3, 4, 16>(x, wpacked, in_affine, nullptr, nullptr, y, stats, B, Cin, CinP, H, W, Cout, CoutP, 0, ir, s);
-    else if (ksize == 3) rc = wide ? launch<64, 3, 2, 32>(x, wpacked, in_affine, nullptr, nullptr, y, stats, B, Cin, CinP, H, W, Cout, CoutP, 0, ir, s)
-                                   : launch<32, 3, 4, 32>(x, wpacked, in_affine, nullptr, nullptr, y, stats, B, Cin, CinP, H, W, Cout, CoutP, 0, ir, s);
-    else rc = wide ? launch<64, 1, 2, 32>(x, wpacked, in_affine, nullptr, nullptr, y, stats, B, Cin, CinP, H, W, Cout, CoutP, 0, ir, s)
-                   : launch<32, 1, 4, 32>(x, wpacked, in_affine, nullptr, nullptr, y, stats, B, Cin, CinP, H, W, Cout, CoutP, 0, ir, s);
-    if (rc != ISLAM_OK) return rc;
-    const int nblk = ws ? conv_ws_blocks(B, H, W) : ws32 ? conv_ws32_blocks(B, H, W) : tiles_of(B, H, W, tile_h(Cout, Cin, ksize, B, H, W));
+    ConvCall c{x, wpacked, in_affine, nullptr, nullptr, y, stats, B, Cin, H, W, Cout, 0, in_relu ? 1 : 0, s, ksize, 1};
+    c.persistent = !in_relu || in_affine;
+    int nblk = 0;
+    if (int rc = conv_run(c, nblk)) return rc;
     // how the statistics get from the per-workgroup rows to [scale | shift]: 0 = fold, then finalize (two launches); 1 = both in one launch
     // with a ticket (fold_finalize_kernel: measured no faster than two launches, kept for A/B runs); default = the persistent kernels' few
     // rows straight into the finalize (one launch, no fold), everything else as 0
     static const int how = [] { const char* e = std::getenv("ISLAM_BN_FINALIZE"); return e ? std::atoi(e) : 2; }();
-    float* folded = stats + (size_t)islam_conv_nhwc_stat_blocks(B, H, W, Cout) * 2 * Cout;
-    if (how != 1) {
-        const double count = (double)B * H * W;
-        if (how == 2 && nblk <= RED_BLOCKS)
-            hipLaunchKernelGGL(finalize_rows_kernel<1>, dim3(1), dim3(FF_THREADS), 0, s, stats, nblk, Cout, count, weight, bias, running_mean, running_var,
-                               num_batches_tracked, momentum, eps, scale_shift);
-        else if (how == 2 && nblk <= 2 * RED_BLOCKS)
-            hipLaunchKernelGGL(finalize_rows_kernel<2>, dim3(1), dim3(FF_THREADS), 0, s, stats, nblk, Cout, count, weight, bias, running_mean, running_var,
-                               num_batches_tracked, momentum, eps, scale_shift);
-        else {
-            hipLaunchKernelGGL(partial_fold_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, stats, nblk, 2 * Cout, folded);
-            hipLaunchKernelGGL(finalize_rows_kernel<1>, dim3(1), dim3(FF_THREADS), 0, s, folded, RED_BLOCKS, Cout, count, weight, bias, running_mean,
-                               running_var, num_batches_tracked, momentum, eps, scale_shift);
-        }
-        ISLAM_LAUNCH_CHECK();
-        return ISLAM_OK;
+    const int area_rows = islam_conv_nhwc_stat_blocks(B, H, W, Cout);
+    float* folded = stats + (size_t)area_rows * 2 * Cout;
+    const double count = (double)B * H * W;
+    if (how == 1)
+        hipLaunchKernelGGL(fold_finalize_kernel, dim3(RED_BLOCKS), dim3(FF_THREADS), 0, s, stats, nblk, Cout, folded, count, weight, bias, running_mean,
+                           running_var, num_batches_tracked, momentum, eps, scale_shift, counter);
+    else if (how == 2 && nblk <= RED_BLOCKS)
+        hipLaunchKernelGGL(finalize_rows_kernel<1>, dim3(1), dim3(FF_THREADS), 0, s, stats, nblk, Cout, count, weight, bias, running_mean, running_var,
+                           num_batches_tracked, momentum, eps, scale_shift);
+    else if (how == 2 && nblk <= 2 * RED_BLOCKS)
+        hipLaunchKernelGGL(finalize_rows_kernel<2>, dim3(1), dim3(FF_THREADS), 0, s, stats, nblk, Cout, count, weight, bias, running_mean, running_var,
+                           num_batches_tracked, momentum, eps, scale_shift);
+    else {
+        if (int rc = fold_stats(stats, nblk, area_rows, Cout, s)) return rc;
+        hipLaunchKernelGGL(finalize_rows_kernel<1>, dim3(1), dim3(FF_THREADS), 0, s, folded, RED_BLOCKS, Cout, count, weight, bias, running_mean,
+                           running_var, num_batches_tracked, momentum, eps, scale_shift);
     }
-    hipLaunchKernelGGL(fold_finalize_kernel, dim3(RED_BLOCKS), dim3(FF_THREADS), 0, s, stats, nblk, Cout,
-                       folded, (double)B * H * W, weight, bias, running_mean,
-                       running_var, num_batches_tracked, momentum, eps, scale_shift, counter);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }
-
 
 // ConvTranspose2d(Cin, Cout, kernel 4, stride 2, padding 1) + bias (+ ReLU) of the frozen stereo net's decoder
 // (Network/StereoNet7.py:78-90 deconv_c7_2 ... deconv_c10, their ReLU and concatenation at :121-136) on the kernel above: four 2x2 convolutions, one per
@@ -805,15 +712,11 @@ size_t islam_deconv_nhwc_packed_elems(int Cin, int Cout) {
 
 int islam_deconv4x4s2_nhwc_bf16(const uint16_t* x, const uint16_t* wpacked, const float* bias, uint16_t* y, int ytot, int yoff, int B, int Cin,
                                 int H, int W, int Cout, int relu, void* stream) {
-    if (B < 1 || H < 1 || W < 1 || Cin < 8 || (Cin & 7) || Cout < 8 || (Cout & 7))
-        return fail(ISLAM_EARG, "islam_deconv4x4s2_nhwc_bf16: bad shape (Cin=%d, Cout=%d must be multiples of 8)", Cin, Cout);
-    if ((ytot & 7) || (yoff & 7) || yoff < 0 || yoff + Cout > ytot) return fail(ISLAM_EARG, "islam_deconv4x4s2_nhwc_bf16: output slice %d+%d of %d", yoff, Cout, ytot);
-    if ((size_t)B * 4 * H * W * std::max(Cin, ytot) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_deconv4x4s2_nhwc_bf16: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-    const Slices sl{Cin, 0, ytot, yoff, nullptr, 0, 0, 0.0f, 2, W, 1, 0, 0};
-    hipStream_t s = (hipStream_t)stream;
-    return Cout > 32 ? launch<64, 2, 2, 32>(x, wpacked, nullptr, bias, nullptr, y, nullptr, B * 4, Cin, CinP, H, W, Cout, CoutP, relu & 1, 0, s, sl)
-                     : launch<32, 2, 4, 32>(x, wpacked, nullptr, bias, nullptr, y, nullptr, B * 4, Cin, CinP, H, W, Cout, CoutP, relu & 1, 0, s, sl);
+    if (int rc = check_shape(__func__, B, H, W, Cin, Cout)) return rc;
+    if (int rc = check_out_slice(__func__, ytot, yoff, Cout)) return rc;
+    if (int rc = check_offsets(__func__, (size_t)B * 4 * H * W, std::max(Cin, ytot))) return rc;
+    return conv_run(ConvCall{x, wpacked, nullptr, bias, nullptr, y, nullptr, B * 4, Cin, H, W, Cout, relu & 1, 0, (hipStream_t)stream, 2, 1,
+                             Slices{Cin, 0, ytot, yoff, nullptr, 0, 0, 0.0f, 2, W, 1, 0, 0}});
 }
 
 // The same with the input given as TWO dense tensors x1 (B,H,W,C1), x2 (B,H,W,C2) whose channel concatenation torch.cat((x1, x2), 1) is
@@ -825,14 +728,10 @@ int islam_deconv4x4s2_nhwc_bf16_cat(const uint16_t* x1, int C1, const uint16_t* 
     const int Cin = C1 + C2;
     if (!x1 || !x2 || B < 1 || H < 1 || W < 1 || C1 < 32 || (C1 & 31) || C2 < 8 || (C2 & 7) || Cout < 8 || (Cout & 7))
         return fail(ISLAM_EARG, "islam_deconv4x4s2_nhwc_bf16_cat: bad shape (C1=%d must be a multiple of 32, C2=%d and Cout=%d of 8)", C1, C2, Cout);
-    if ((ytot & 7) || (yoff & 7) || yoff < 0 || yoff + Cout > ytot) return fail(ISLAM_EARG, "islam_deconv4x4s2_nhwc_bf16_cat: output slice %d+%d of %d", yoff, Cout, ytot);
-    if ((size_t)B * 4 * H * W * std::max(Cin, ytot) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_deconv4x4s2_nhwc_bf16_cat: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-    const Slices sl{C1, 0, ytot, yoff, nullptr, 0, 0, 0.0f, 2, W, 1, 0, 0};
-    const Src2 s2{x2, C2, C1};
-    hipStream_t s = (hipStream_t)stream;
-    return Cout > 32 ? launch<64, 2, 2, 32, false, 1, true>(x1, wpacked, nullptr, bias, nullptr, y, nullptr, B * 4, Cin, CinP, H, W, Cout, CoutP, relu & 1, 0, s, sl, s2)
-                     : launch<32, 2, 4, 32, false, 1, true>(x1, wpacked, nullptr, bias, nullptr, y, nullptr, B * 4, Cin, CinP, H, W, Cout, CoutP, relu & 1, 0, s, sl, s2);
+    if (int rc = check_out_slice(__func__, ytot, yoff, Cout)) return rc;
+    if (int rc = check_offsets(__func__, (size_t)B * 4 * H * W, std::max(Cin, ytot))) return rc;
+    return conv_run(ConvCall{x1, wpacked, nullptr, bias, nullptr, y, nullptr, B * 4, Cin, H, W, Cout, relu & 1, 0, (hipStream_t)stream, 2, 1,
+                             Slices{C1, 0, ytot, yoff, nullptr, 0, 0, 0.0f, 2, W, 1, 0, 0}, Src2{x2, C2, C1}});
 }
 
 // islam_conv_nhwc_bf16_s2 (kernel size 2: the quarter-resolution tail of the stereo net, Network/StereoNet7.py:88-90 through
@@ -845,13 +744,9 @@ int islam_conv_nhwc_bf16_s2_cat(const uint16_t* x1, int C1, const uint16_t* x2, 
     if (ksize != 2) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2_cat: kernel size %d (2)", ksize);
     const int Hmax = Hi / 2 + 1, Wmax = Wi / 2 + 1;                  // padding ksize / 2 = 1: (Hi + 2 - 2) / 2 + 1
     if (Ho < 1 || Wo < 1 || Ho > Hmax || Wo > Wmax) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2_cat: output %dx%d of at most %dx%d", Ho, Wo, Hmax, Wmax);
-    if ((size_t)B * Hi * Wi * std::max(Cin, Cout) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_conv_nhwc_bf16_s2_cat: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-    const Slices sl{C1, 0, Cout, 0, nullptr, 0, 0, 0.0f, 1, Wo, 0, Hi, Wi};
-    const Src2 s2{x2, C2, C1};
-    hipStream_t s = (hipStream_t)stream;
-    return Cout > 32 ? launch<64, 2, 2, 16, false, 2, true>(x1, wpacked, nullptr, bias, nullptr, y, nullptr, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu & 1, (relu >> 1) & 1, s, sl, s2)
-                     : launch<32, 2, 2, 16, false, 2, true>(x1, wpacked, nullptr, bias, nullptr, y, nullptr, B, Cin, CinP, Ho, Wo, Cout, CoutP, relu & 1, (relu >> 1) & 1, s, sl, s2);
+    if (int rc = check_offsets(__func__, (size_t)B * Hi * Wi, std::max(Cin, Cout))) return rc;
+    return conv_run(ConvCall{x1, wpacked, nullptr, bias, nullptr, y, nullptr, B, Cin, Ho, Wo, Cout, relu & 1, (relu >> 1) & 1, (hipStream_t)stream, 2, 2,
+                             Slices{C1, 0, Cout, 0, nullptr, 0, 0, 0.0f, 1, Wo, 0, Hi, Wi}, Src2{x2, C2, C1}});
 }
 
 // 3x3 stride-1 convolution of the flow net's DenseNet blocks (Network/PWC/PWCNet.py:16-20 `conv()` = Conv2d + LeakyReLU(0.1),
@@ -872,15 +767,10 @@ int islam_conv_nhwc_flow(const uint16_t* x, int xtot, int xoff, int Cin, const u
     if ((xtot & 7) || (xoff & 7) || xoff < 0 || xoff + Cin > xtot) return fail(ISLAM_EARG, "islam_conv_nhwc_flow: input slice %d+%d of %d", xoff, Cin, xtot);
     if (y32 && (coff < 0 || coff + Cout > ytot)) return fail(ISLAM_EARG, "islam_conv_nhwc_flow: output slice %d+%d of %d", coff, Cout, ytot);
     if (ymir && ((mtot & 7) || (moff & 7) || moff < 0 || moff + Cout > mtot)) return fail(ISLAM_EARG, "islam_conv_nhwc_flow: mirror slice %d+%d of %d", moff, Cout, mtot);
-    if ((size_t)B * H * W * std::max(std::max(xtot, mtot), ytot) >= ((size_t)1 << 31)) return fail(ISLAM_EARG, "islam_conv_nhwc_flow: tensor too large for 32-bit offsets");
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
+    if (int rc = check_offsets(__func__, (size_t)B * H * W, std::max(std::max(xtot, mtot), ytot))) return rc;
     const int d = dilation;
-    const Slices sl{xtot, xoff, ymir ? mtot : Cout, ymir ? moff : 0, y32, ytot, coff, slope, d, W, 0, 0, 0};
-    hipStream_t s = (hipStream_t)stream;
-    if (conv_r4(Cin, Cout, 3, B * d * d, H / d, W / d))
-        return launch<64, 3, 4, 16, true>(x, wpacked, nullptr, bias, nullptr, ymir, nullptr, B * d * d, Cin, CinP, H / d, W / d, Cout, CoutP, 0, 0, s, sl);
-    return Cout > 32 ? launch<64, 3, 2, 32, true>(x, wpacked, nullptr, bias, nullptr, ymir, nullptr, B * d * d, Cin, CinP, H / d, W / d, Cout, CoutP, 0, 0, s, sl)
-                     : launch<32, 3, 4, 32, true>(x, wpacked, nullptr, bias, nullptr, ymir, nullptr, B * d * d, Cin, CinP, H / d, W / d, Cout, CoutP, 0, 0, s, sl);
+    return conv_run(ConvCall{x, wpacked, nullptr, bias, nullptr, ymir, nullptr, B * d * d, Cin, H / d, W / d, Cout, 0, 0, (hipStream_t)stream, 3, 1,
+                             Slices{xtot, xoff, ymir ? mtot : Cout, ymir ? moff : 0, y32, ytot, coff, slope, d, W, 0, 0, 0}, Src2{nullptr, 0, 0}, /* flow */ true});
 }
 
 // fp32 NCHW channels [soff, soff + C) of src (B,stot,H,W)  ->  bf16 channels [doff, doff + C) of dst (B,H,W,dtot), rounded to

@@ -25,42 +25,17 @@
 #include <type_traits>
 
 #include "../../include/islam_hip.h"
+#include "bf16_dev.h"
 #include "common.h"
 #include "conv_ws.h"
 
 namespace islam {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2_t __attribute__((ext_vector_type(2)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 template <int V> using ic = std::integral_constant<int, V>;
 // The values must exist HERE: sched_barrier fences the machine scheduler only, and the optimiser otherwise sinks a micro-operation's
 // arithmetic to the place its result is finally needed (all eight store items' statistics ended up in one clump of 100 instructions).
 #define PIN4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {      // round-to-nearest-even, one v_cvt_pk_bf16_f32
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float lo16(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float hi16(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-__device__ __forceinline__ unsigned relu2(unsigned t) {            // ReLU of packed bf16 = max on the int16 lanes (sign-magnitude)
-    const s16x2_t z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, t), z));
-}
 
 constexpr int TN = 128, ROWS = 4, TW = 32, THREADS = 256;
 constexpr int IH = ROWS + 2, IW = TW + 2, NPIX = IH * IW;          // 6 x 34 halo pixels
@@ -481,14 +456,8 @@ int conv_ws_balanced(long long ntiles, int slots) {
 template <int CIN>
 static int ws_launch(const unsigned short* x, const unsigned short* wp, const float* in_affine, unsigned short* y, float* partial, int B, int H, int W,
                      int Cout, int CoutP, int xs, int xoff, int ys, int yoff, hipStream_t s) {
-    int dev = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr_set[64] = {};
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)conv3x3_ws_kernel<CIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)conv3x3_ws_kernel<CIN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)conv3x3_ws_kernel<CIN, true>, (const void*)conv3x3_ws_kernel<CIN, false>}, 160 * 1024, lds_set)) return rc;
     const int tiles_x = W / TW, tiles_y = H / ROWS, ntiles = tiles_x * tiles_y * B;
     const int G = conv_ws_blocks(B, H, W);
     if (in_affine)

@@ -191,13 +191,8 @@ extern "C" int islam_edge_mask(const float* img, uint8_t* mask, int B, int H, in
                     EDGE_MAX_PIXELS);
     if (B == 0) return ISLAM_OK;
     const size_t lds = (size_t)((3 * n + 15) & ~15L) + 2 * (size_t)n;
-    int dev = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr_set[64] = {};                                         // per device: the attribute lives in the device's module
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)edge_mask_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)edge_mask_kernel}, 160 * 1024 - 64, lds_set)) return rc;
     hipLaunchKernelGGL(edge_mask_kernel, dim3(B), dim3(EDGE_THREADS), lds, as_stream(stream), img, mask, H, W, downscale, low, high);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "../../include/islam_hip.h"
+#include "bf16_dev.h"
 #include "common.h"
 
 // scripts/hg_probe.sh builds an experiment variant (never the product library) that timestamps the phases of one workgroup
@@ -47,12 +48,6 @@ namespace {
 
 using namespace islam;
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gptr_t;
 
@@ -61,27 +56,6 @@ constexpr int NOUT = TH * TW;                       // 128 output pixels = 4 N t
 
 constexpr int THREADS = 256;
 
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float lo16(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float hi16(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-// ReLU of packed bf16: a negative bf16 is a negative int16 (sign-magnitude), so max(., 0) on the int16 lanes is the ReLU: ONE v_pk_max_i16 per pair
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned relu2(unsigned t) {
-    const s16x2 z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, t), z));
-}
 __device__ __forceinline__ bf16x8 relu8(bf16x8 v) {
     const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     return __builtin_elementwise_max(v, z);
@@ -508,15 +482,12 @@ __global__ __launch_bounds__(THREADS, 2) void hg_residual64_kernel(const unsigne
 
 int launch64(const unsigned short* x, unsigned short* y, const unsigned short* wpk, const float* bias, int B, int H, int W, hipStream_t s) {
     const size_t lds = (size_t)L_LDS_ELEMS * sizeof(unsigned short);
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)hg_residual64_kernel}, 160 * 1024, lds_set)) return rc;
     int dev = 0;
     ISLAM_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr_set[64] = {};
     static int ncu[64] = {};
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)hg_residual64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ISLAM_HIP_CHECK(hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        attr_set[dev] = true;
-    }
+    if (dev >= 0 && dev < 64 && ncu[dev] == 0) ISLAM_HIP_CHECK(hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev));
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH, ntiles = tiles_x * tiles_y * B;
     const int cus = (dev >= 0 && dev < 64 && ncu[dev] > 0) ? ncu[dev] : 256;
     const int grid = std::min(ntiles, 2 * cus);              // persistent: two workgroups per CU walk the tiles
@@ -532,13 +503,8 @@ int launch(const unsigned short* x, const unsigned short* res, unsigned short* y
     const int npiece = (NDP * (Cin / 8 + 1) + 63) / 64;      // whole 1-KiB LDS-DMA pieces of the patch
     const int rx = std::max(npiece * 512, NOUT * G::T1S + NOUT * G::OS - NDP * G::T1S);      // t2 | ... | output tile (ends with t1) must not overlap
     const size_t lds = ((size_t)rx + (size_t)NDP * G::T1S) * sizeof(unsigned short) + (size_t)2 * G::COUT * sizeof(float);
-    int dev = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr_set[64] = {};
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)hg_residual_kernel<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)hg_residual_kernel<MT>}, 160 * 1024, lds_set)) return rc;
     if (lds > 160 * 1024) return fail(ISLAM_EARG, "islam_hg_residual_nhwc_bf16: %zu bytes of LDS for Cin=%d, Cout=%d", lds, Cin, G::COUT);
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     hipLaunchKernelGGL((hg_residual_kernel<MT>), dim3(tiles_x * tiles_y * B), dim3(G::THREADS_), lds, s, x, res, y, wpk, bias, Cin, H, W, tiles_x,

@@ -758,12 +758,6 @@ bool make_plan(int B, int H, int W, Plan& p) {
     return true;
 }
 
-inline int current_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    return dev;
-}
-
 template <int MODE>
 constexpr size_t lds_bytes(int nw) {
     const int a_floats = (MODE == MODE_WGRAD) ? KC * 32 : 32 * LDK, b_floats = (MODE == MODE_FWD) ? 32 * LDK : KC * 32;
@@ -841,12 +835,8 @@ int waves_per_wg() {
 template <int MODE, int NW, bool HAS_DS>
 int launch_single_ds(const Prepared& p, hipStream_t s) {
     constexpr size_t lds = lds_bytes<MODE>(NW);
-    static bool attr_set[64] = {};                           // per device: the attribute lives in the device's code object
-    const int dev = current_device();
-    if (!attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)conv_gemm_kernel<MODE, NW, HAS_DS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)conv_gemm_kernel<MODE, NW, HAS_DS>}, (int)lds, lds_set)) return rc;
     hipLaunchKernelGGL((conv_gemm_kernel<MODE, NW, HAS_DS>), dim3(((p.ntiles + 7) & ~7) * p.KS), dim3(64 * NW), lds, s, p.a, p.ntiles, p.KS);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
@@ -870,12 +860,8 @@ int launch_conv(const ConvArgs& a, int kdim, int kdim2, hipStream_t s, float* pa
 template <int NW, bool HAS_DS>
 int launch_pair_ds(const Prepared& d, const Prepared& w, hipStream_t s) {
     constexpr size_t lds = lds_bytes<MODE_DGRAD>(NW) > lds_bytes<MODE_WGRAD>(NW) ? lds_bytes<MODE_DGRAD>(NW) : lds_bytes<MODE_WGRAD>(NW);
-    static bool attr_set[64] = {};
-    const int dev = current_device();
-    if (!attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)conv_bwd_pair_kernel<NW, HAS_DS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)conv_bwd_pair_kernel<NW, HAS_DS>}, (int)lds, lds_set)) return rc;
     const int grid = ((d.ntiles + 7) & ~7) * d.KS + ((w.ntiles + 7) & ~7) * w.KS;
     hipLaunchKernelGGL((conv_bwd_pair_kernel<NW, HAS_DS>), dim3(grid), dim3(64 * NW), lds, s, d.a, d.ntiles, d.KS, w.a, w.ntiles, w.KS);
     ISLAM_LAUNCH_CHECK();
@@ -1013,14 +999,8 @@ int islam_pose_head_forward(const float* x, const float* const* params, float* o
     }
     float* h1 = ws + p.a_h1;
     float* h2 = ws + p.a_h2;
-    {
-        static bool attr_set[64] = {};
-        const int dev = current_device();
-        if (!attr_set[dev]) {
-            ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)fc1_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FC_MAXB * FC_IN * sizeof(float))));
-            attr_set[dev] = true;
-        }
-    }
+    static bool fc1_lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)fc1_fwd_kernel}, (int)(FC_MAXB * FC_IN * sizeof(float)), fc1_lds_set)) return rc;
     hipLaunchKernelGGL(fc1_fwd_kernel, dim3(2 * FC_H1 / 4), dim3(TS), (size_t)B * FC_IN * sizeof(float), s, cur, params[108], params[109], params[114],
                        params[115], h1, B, p.HWf);
     ISLAM_LAUNCH_CHECK();

@@ -146,16 +146,6 @@ static void write_plan(const SolvePlan& sp, int* out) {
     out[3 * MAXL] = sp.top;
 }
 
-// Kernels that use dynamic LDS above the default limit.  The attribute lives in the device's code object, so it is set once per
-// device: `set` is the static bool[64] the caller keeps for these kernels.
-static int ensure_dynamic_lds(std::initializer_list<const void*> kernels, int bytes, bool (&set)[64]) {
-    int dev_i = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev_i));
-    if (dev_i < 0 || dev_i >= 64 || set[dev_i]) return ISLAM_OK;
-    for (const void* k : kernels) ISLAM_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    set[dev_i] = true;
-    return ISLAM_OK;
-}
 // linbuild_kernel / trial_lin_kernel stage their node blocks in dynamic LDS
 static int ensure_linbuild_lds() {
     static bool set[64] = {};

@@ -190,13 +190,8 @@ int launch_level(const float* x, const unsigned short* wA, const float* bA, cons
     static_assert(lds <= 160 * 1024, "tile does not fit the LDS");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH - 1) / TH;
-    int dev = 0;
-    ISLAM_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr_set[64] = {};
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        ISLAM_HIP_CHECK(hipFuncSetAttribute((const void*)pyr_level_kernel<CIN, SC, C, TH, TW, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {};
+    if (int rc = ensure_dynamic_lds({(const void*)pyr_level_kernel<CIN, SC, C, TH, TW, THREADS>}, (int)lds, lds_set)) return rc;
     hipLaunchKernelGGL((pyr_level_kernel<CIN, SC, C, TH, TW, THREADS>), dim3((unsigned)(tiles_x * tiles_y * B)), dim3(THREADS), lds, s, x, wA, bA, wB, bB,
                        wC, bC, y, H, W, Ho, Wo, slope, tiles_x, tiles_x * tiles_y, pair ? B / 2 : B, (long long)(pair ? 2 : 1) * CIN * H * W,
                        pair ? (long long)CIN * H * W : 0ll);

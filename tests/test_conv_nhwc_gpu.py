@@ -511,3 +511,58 @@ def test_persistent_kernels_on_random_whole_tile_shapes(cuda, ws_mode):
         out = torch.full((B, CO + 40, H, W), 3.0, dtype=torch.bfloat16, device=cuda).contiguous(memory_format=CL)
         ops.conv_nhwc_into(x, wp, CO, 3, out, yoff, in_affine=aff)
         assert torch.equal(out[:, yoff:yoff + CO], y2) and bool((out[:, :yoff] == 3.0).all()) and bool((out[:, yoff + CO:] == 3.0).all())
+
+
+def _ws_counts():
+    """(launches of conv3x3_ws_kernel, of conv3x3_ws32_kernel) so far: islam_conv_ws_launch_counts."""
+    import ctypes
+    from islam_amd._lib import lib
+    c = (ctypes.c_longlong * 2)()
+    assert lib().islam_conv_ws_launch_counts(ctypes.cast(c, ctypes.c_void_p)) == 0
+    return int(c[0]), int(c[1])
+
+
+def test_persistent_kernel_eligibility_per_entry_point(cuda, ws_mode):
+    """Which calls each entry point hands to the persistent kernels, read off the host-side launch counters at the smallest eligible
+    shapes (128 -> 128: one 32 x 4-pixel tile; 32 -> 32: one 32 x 16-pixel tile).  The outputs are the tile kernel's bit for bit either
+    way, so nothing else sees this rule.  islam_conv_nhwc_bf16 and _into: raw output and no ReLU of the input at all (not even beside
+    in_affine); islam_conv_nhwc_bf16_bn: in_relu is admitted together with in_affine.  The rules differ; this is their record."""
+    from islam_amd import ops
+    for which, (C, H, W) in enumerate([(128, 4, 32), (32, 16, 32)]):
+        x, w = _mk(1, C, H, W, C, 3, seed=C)
+        wp = ops.pack_conv_nhwc_weight(w)
+        g = torch.Generator().manual_seed(8)
+        aff = torch.cat((torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1)).to(cuda)
+        bias = torch.randn(C, generator=g).to(cuda)
+        res = torch.randn(1, C, H, W, generator=g).to(cuda).to(torch.bfloat16).contiguous(memory_format=CL)
+        out = torch.zeros((1, C + 8, H, W), dtype=torch.bfloat16, device=cuda).contiguous(memory_format=CL)
+        bn = torch.nn.BatchNorm2d(C).to(cuda).train()
+        calls = [                                                             # (name, call, launches it adds under mode 2)
+            ('conv_nhwc', lambda: ops.conv_nhwc(x, wp, C, 3), 1),
+            ('conv_nhwc stats', lambda: ops.conv_nhwc(x, wp, C, 3, stats=True), 1),
+            ('conv_nhwc in_affine', lambda: ops.conv_nhwc(x, wp, C, 3, in_affine=aff), 1),
+            ('conv_nhwc relu', lambda: ops.conv_nhwc(x, wp, C, 3, relu=True), 0),
+            ('conv_nhwc bias', lambda: ops.conv_nhwc(x, wp, C, 3, bias=bias), 0),
+            ('conv_nhwc res', lambda: ops.conv_nhwc(x, wp, C, 3, res=res), 0),
+            ('conv_nhwc in_relu', lambda: ops.conv_nhwc(x, wp, C, 3, in_relu=True), 0),
+            ('conv_nhwc in_relu in_affine', lambda: ops.conv_nhwc(x, wp, C, 3, in_affine=aff, in_relu=True), 0),
+            ('conv_nhwc_into', lambda: ops.conv_nhwc_into(x, wp, C, 3, out, 8), 1),
+            ('conv_nhwc_into in_affine', lambda: ops.conv_nhwc_into(x, wp, C, 3, out, 8, in_affine=aff), 1),
+            ('conv_nhwc_into relu', lambda: ops.conv_nhwc_into(x, wp, C, 3, out, 8, relu=True), 0),
+            ('conv_nhwc_into bias', lambda: ops.conv_nhwc_into(x, wp, C, 3, out, 8, bias=bias), 0),
+            ('conv_nhwc_into in_relu', lambda: ops.conv_nhwc_into(x, wp, C, 3, out, 8, in_relu=True), 0),
+            ('conv_nhwc_into in_relu in_affine', lambda: ops.conv_nhwc_into(x, wp, C, 3, out, 8, in_affine=aff, in_relu=True), 0),
+            ('conv_nhwc_bn', lambda: ops.conv_nhwc_bn(x, wp, C, 3, bn), 1),
+            ('conv_nhwc_bn in_affine', lambda: ops.conv_nhwc_bn(x, wp, C, 3, bn, in_affine=aff), 1),
+            ('conv_nhwc_bn in_relu', lambda: ops.conv_nhwc_bn(x, wp, C, 3, bn, in_relu=True), 0),
+            ('conv_nhwc_bn in_relu in_affine', lambda: ops.conv_nhwc_bn(x, wp, C, 3, bn, in_affine=aff, in_relu=True), 1),
+        ]
+        for mode in (2, 0):
+            ws_mode(mode)
+            for name, call, adds in calls:
+                before = _ws_counts()
+                call()
+                after = _ws_counts()
+                want = [0, 0]
+                want[which] = adds if mode == 2 else 0
+                assert [after[0] - before[0], after[1] - before[1]] == want, (C, mode, name)
