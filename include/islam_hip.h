@@ -589,6 +589,40 @@ int islam_dense_ba_depth_var(const float* depth, const float* flow, const uint8_
                              const int* status_or_null, int robust_kind, double robust_delta, int mode, double* out_var,
                              int* out_status, void* scratch, int B, int H, int W, void* stream);
 
+/* Depth propagation: the inverse depths rho and variances s (1/m^2, real variances: sigma_px^2 v of
+ * islam_dense_ba_depth_var) of the first frame of link b carried into the pixel grid of its second frame and fused there with that
+ * frame's own measurement.  All device arithmetic is fp64, every operation rounded on its own (nothing is contracted).  With (R, t) =
+ * T^-1 of motion[b] and rgb2imu as above, (fx, fy, cx, cy) = intr4[b] for both frames, source pixel i = v W + u, ray (xh, yh, 1) =
+ * ((u - cx) / fx, (v - cy) / fy, 1), rho = inv_depth[b,i], s = var_inv_depth[b,i]:
+ *   a = R[2,:].ray,  Q = R ray / rho + t,  rho' = 1 / Q.z,  J = a rho'^2 / rho^2 (= drho'/drho),  s' = J^2 s + process_var[b],
+ *   u2 = fx Q.x / Q.z + cx,  v2 = fy Q.y / Q.z + cy,  iu = (int)floor(u2 + 0.5),  iv = (int)floor(v2 + 0.5).
+ * Source i is a candidate for target j = iv W + iu iff the link's incoming status is 0 (or status_or_null is NULL), the mask (if
+ * given) is set at i, rho and s are finite and > 0, Q.z > 0.1, 0 <= iu < W, 0 <= iv < H, and s' is finite.  Z-buffer: the winner at
+ * j is the candidate with the largest key (bits of (float)rho', 0xFFFFFFFF - i), compared lexicographically: the nearest surface, the
+ * smaller source index on equal fp32 keys; key 0: nothing landed.  Measurement (optional; depth_next and var_next (B,H,W) float32, the
+ * depth of the second frame and the variance of its inverse depth, both or neither): present at j iff depth_next and var_next are
+ * finite and > 0; rho_m = 1 / depth_next, s_m = var_next.  Fusion at j:
+ *   both present:  d = rho' - rho_m;  gate > 0 and d^2 > gate^2 (s' + s_m): gated, the measurement alone;  otherwise
+ *                  rho_f = (rho' s_m + rho_m s') / (s' + s_m),  s_f = s' s_m / (s' + s_m);
+ *   one present: that one;  none: rho_f = 0, s_f = NaN ("no prior at this pixel").
+ * Outputs, all written in full: out_inv_depth, out_var (B,H,W) float64 = rho_f, s_f; out_depth (B,H,W) float32 = 1 / rho_f where
+ * rho_f > 0, else the bits of depth_next (0 without one); out_source (B,H,W) int32: the winning source index, -1 for none; out_flags
+ * (B,H,W) uint8: bit 0 propagated present, bit 1 measurement present, bit 2 gated out; out_status (B): status_or_null's value where
+ * that is not 0, ISLAM_DENSE_REPROJ_BADPRIOR where process_var[b] is negative or not finite (formed on the device), else 0; a link
+ * whose out_status is not 0 propagates nothing and gets the measurement alone at every pixel.
+ * islam_depth_propagate: one hipMemsetAsync of the key buffer (scratch, islam_depth_propagate_scratch_bytes(B, H, W) = B H W 8 bytes
+ * rounded up) and two launches on `stream`, no host wait: depth_splat_kernel (one 64-bit atomic maximum per candidate; a maximum does
+ * not depend on the order of arrival, so a repeat gives the same bits) and depth_fuse_kernel (plain stores).  ISLAM_EARG before any
+ * device work for B, H, W < 1 or H*W > 2^30 (which keeps every source index below 2^32 - 1), a NULL pointer other than mask_or_null,
+ * rgb2imu_or_null, status_or_null, depth_next_or_null and var_next_or_null, depth_next without var_next or the reverse, and a gate
+ * that is negative or not finite. */
+size_t islam_depth_propagate_scratch_bytes(int B, int H, int W);
+int islam_depth_propagate(const double* inv_depth, const double* var_inv_depth, const uint8_t* mask_or_null, const double* motion,
+                          const double* rgb2imu_or_null, const double* intr4, const int* status_or_null, const double* process_var,
+                          const float* depth_next_or_null, const float* var_next_or_null, double gate, double* out_inv_depth,
+                          double* out_var, float* out_depth, int* out_source, uint8_t* out_flags, int* out_status, void* scratch,
+                          int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

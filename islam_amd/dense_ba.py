@@ -13,7 +13,8 @@
     marginalise it with the pose (csrc/dense_ba.hip, section 3.25); ``refine_joint(differentiable=True)`` lets a loss on the jointly
     refined pose, inverse depths or depth map reach the stored depth and flow (section 3.26); both take the prior's standard
     deviation per pixel as well, and ``depth_uncertainty`` returns the posterior standard deviation of every refined depth
-    (section 3.27);
+    (section 3.27); ``propagate`` carries both into the next frame's pixel grid and fuses them with that frame's own depth map, the
+    prior of the next link (csrc/depth_prop.hip, section 3.28);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -26,6 +27,7 @@ from . import lietensor as pp
 
 DenseBAJoint = collections.namedtuple('DenseBAJoint', 'motion inv_depth S g cost l1 count sums damping accepted rejected status trace depth')
 DenseBADepthUncertainty = collections.namedtuple('DenseBADepthUncertainty', 'var_inv_depth sigma_inv_depth sigma_depth status')
+DenseBAPrior = collections.namedtuple('DenseBAPrior', 'depth sigma_inv_depth inv_depth var_inv_depth source flags status')
 
 
 def pixel2point(pixels, depth, intrinsics):
@@ -295,6 +297,65 @@ class DenseReprojectionLoss:
         var = float(sigma_px) ** 2 * out.var
         sig = torch.sqrt(var)
         return DenseBADepthUncertainty(var, sig, sig / (joint.inv_depth * joint.inv_depth), out.status)
+
+    def _variance_next(self, sigma, who):
+        """sigma_inv_depth_next as the (B,H,W) float32 variance map of the measurement: sigma^2 where sigma is finite and > 0.  A number
+        or a host-side (B,) tensor is validated here (ValueError); a device tensor is never read back, and an entry that is not finite
+        or not positive becomes NaN, "no measurement at this pixel" (the rule of _prior_weight)."""
+        shape, dev = tuple(self.z.shape), self.z.device
+        if not torch.is_tensor(sigma):
+            sigma = torch.as_tensor(float(sigma), dtype=torch.float64)
+        sig = sigma.detach().to(torch.float64)
+        is_map = sig.dim() == 3 and tuple(sig.shape) == shape
+        if not is_map:
+            if sig.numel() != 1 and tuple(sig.shape) != shape[:1]:
+                raise ValueError('%s: sigma_inv_depth_next must be a positive number, a (%d,) tensor or a %s map, got shape %s' % (
+                    who, shape[0], shape, tuple(sig.shape)))
+            if not sig.is_cuda and not bool(((sig > 0) & torch.isfinite(sig)).all()):
+                raise ValueError('%s: sigma_inv_depth_next must be finite and positive (got %s)' % (who, sig.tolist()))
+            sig = sig.reshape(-1, 1, 1).expand(shape)
+        sig = sig.to(dev)
+        ok = torch.isfinite(sig) & (sig > 0)
+        return torch.where(ok, sig * sig, torch.full_like(sig, float('nan'))).to(torch.float32).contiguous()
+
+    def propagate(self, joint, uncertainty, depth_next=None, sigma_inv_depth_next=None, process_sigma=0.0, gate=3.0):
+        """The step from one link to the next: the inverse depths a ``refine_joint`` returned (``joint``) and their variances
+        (``uncertainty``: the result of ``depth_uncertainty`` for it) are warped through the refined pose into the pixel grid of the
+        link's second frame, the nearest surface winning where several pixels land on one, and fused there with that frame's own depth
+        map (ops.dense_ba_depth_propagate).  The stored mask, intrinsics and mount are used.  depth_next
+        (B,H,W) with sigma_inv_depth_next (1/m: a positive number, a (B,) tensor or a (B,H,W) map, where an entry that is not finite or
+        not positive means "no measurement at this pixel"): the second frame's stereo depth and its inverse-depth standard deviation,
+        both or neither (neither: pure propagation).  process_sigma (1/m, a non-negative number or (B,)): its square is added to every
+        propagated variance, e.g. the discretisation noise of the nearest-pixel warp.  gate: a propagated value more than ``gate``
+        standard deviations from the measurement (an occlusion, a moving object) gives way to it; 0 never gates.  Returns DenseBAPrior:
+        depth (B,H,W) float32 and sigma_inv_depth (B,H,W) float64 (NaN where nothing is known), which go straight into the next
+        DenseReprojectionLoss(depth=...) and refine_joint(sigma_inv_depth=...); inv_depth and var_inv_depth (float64), source (the
+        pixel of the first frame that won, -1 for none), flags (1 propagated, 2 measured, 4 gated out) and status (B) int32: a link
+        whose refinement or uncertainty came with a status propagates nothing and returns the measurement alone."""
+        from . import ops
+        if (depth_next is None) != (sigma_inv_depth_next is None):
+            raise ValueError('propagate: depth_next and sigma_inv_depth_next come together or not at all')
+        var_next = None
+        if depth_next is not None:
+            if tuple(depth_next.shape) != tuple(self.z.shape):
+                raise ValueError('propagate: depth_next must be %s, got %s' % (tuple(self.z.shape), tuple(depth_next.shape)))
+            var_next = self._variance_next(sigma_inv_depth_next, 'propagate')
+            depth_next = depth_next.detach().to(self.z.device)
+        if torch.is_tensor(process_sigma):
+            ps = process_sigma.detach().to(torch.float64)
+            if not ps.is_cuda and not bool(((ps >= 0) & torch.isfinite(ps)).all()):
+                raise ValueError('propagate: process_sigma must be finite and non-negative (got %s)' % (ps.tolist(),))
+            ok = torch.isfinite(ps) & (ps >= 0)
+            process_var = torch.where(ok, ps * ps, torch.full_like(ps, float('nan')))      # NaN: BADPRIOR on the device, no read-back
+        else:
+            ps = float(process_sigma)
+            if not (ps >= 0.0 and ps < float('inf')):
+                raise ValueError('propagate: process_sigma must be a finite non-negative number (got %r)' % (process_sigma,))
+            process_var = ps * ps
+        out = ops.dense_ba_depth_propagate(joint.inv_depth, uncertainty.var_inv_depth, joint.motion, torch.tensor(self.K4, dtype=torch.float64),
+                                           mask=self.mask, status=uncertainty.status, rgb2imu=self.rgb2imu_pose, process_var=process_var,
+                                           depth_next=depth_next, var_next=var_next, gate=gate)
+        return DenseBAPrior(out.depth, torch.sqrt(out.var_inv_depth), out.inv_depth, out.var_inv_depth, out.source, out.flags, out.status)
 
     def information(self, motion, sigma_px=1.0, kernel=None, sigma_inv_depth=None):
         """H / sigma_px^2 (B,6,6) float64: the information of each link's VO residual in the frame and row order of PvgoInfo.vo, for

@@ -167,9 +167,32 @@ class _DenseArgs(collections.namedtuple('_DenseArgs', 'dev B H W depth flow mask
         return ptr(self.depth), ptr(self.flow), ptr(self.mask), ptr(self.motion), ptr(self.rgb2imu), ptr(self.intr)
 
 
+def _dense_link_args(who, dev, B, H, W, mask, motion, intr, rgb2imu):
+    """What every entry point of the family takes per link, checked and on the device: mask (B,H,W) uint8 or None, motion (B,7) and intr
+    (B,4) float64, rgb2imu (7) float64 or None."""
+    from . import lietensor as pp
+    if mask is not None:
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError('%s: mask must be (%d,%d,%d), got %s' % (who, B, H, W, tuple(mask.shape)))
+        mask = (mask.to(dev) != 0).to(torch.uint8).contiguous()
+    f64 = lambda t: pp._plain(torch.as_tensor(t)).detach().to(dev, torch.float64).contiguous()
+    motion = f64(motion)
+    if tuple(motion.shape) != (B, 7):
+        raise ValueError('%s: motion must be (%d,7) [t, q xyzw], got %s' % (who, B, tuple(motion.shape)))
+    intr = f64(intr)
+    if intr.numel() == 4:
+        intr = intr.reshape(1, 4).expand(B, 4).contiguous()
+    if tuple(intr.shape) != (B, 4):
+        raise ValueError('%s: intr must be (4) or (%d,4) = fx, fy, cx, cy, got %s' % (who, B, tuple(intr.shape)))
+    if rgb2imu is not None:
+        rgb2imu = f64(rgb2imu).reshape(-1)
+        if rgb2imu.numel() != 7:
+            raise ValueError('%s: rgb2imu must be one SE3 (7), got %d values' % (who, rgb2imu.numel()))
+    return mask, motion, intr, rgb2imu
+
+
 def _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel):
     """The device tensors and scalars every entry point takes (include/islam_hip.h, "dense reprojection"), as one _DenseArgs."""
-    from . import lietensor as pp
     from .robust import NONE, _Kernel
     require_cuda(depth, flow)
     dev = depth.device
@@ -177,23 +200,7 @@ def _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel):
         raise ValueError('dense_reproj: depth must be (B,H,W) and flow (B,2,H,W), got %s and %s' % (tuple(depth.shape), tuple(flow.shape)))
     B, H, W = depth.shape
     depth, flow = _f32c(depth), _f32c(flow)
-    if mask is not None:
-        if tuple(mask.shape) != (B, H, W):
-            raise ValueError('dense_reproj: mask must be (%d,%d,%d), got %s' % (B, H, W, tuple(mask.shape)))
-        mask = (mask.to(dev) != 0).to(torch.uint8).contiguous()
-    f64 = lambda t: pp._plain(torch.as_tensor(t)).detach().to(dev, torch.float64).contiguous()
-    motion = f64(motion)
-    if tuple(motion.shape) != (B, 7):
-        raise ValueError('dense_reproj: motion must be (%d,7) [t, q xyzw], got %s' % (B, tuple(motion.shape)))
-    intr = f64(intr)
-    if intr.numel() == 4:
-        intr = intr.reshape(1, 4).expand(B, 4).contiguous()
-    if tuple(intr.shape) != (B, 4):
-        raise ValueError('dense_reproj: intr must be (4) or (%d,4) = fx, fy, cx, cy, got %s' % (B, tuple(intr.shape)))
-    if rgb2imu is not None:
-        rgb2imu = f64(rgb2imu).reshape(-1)
-        if rgb2imu.numel() != 7:
-            raise ValueError('dense_reproj: rgb2imu must be one SE3 (7), got %d values' % rgb2imu.numel())
+    mask, motion, intr, rgb2imu = _dense_link_args('dense_reproj', dev, B, H, W, mask, motion, intr, rgb2imu)
     if kernel is not None and not isinstance(kernel, _Kernel):
         raise ValueError('dense_reproj: kernel must be None, Huber(delta) or Cauchy(delta) (got %r)' % (kernel,))
     kind, delta = (NONE, 1.0) if kernel is None else (kernel.kind, kernel.delta)
@@ -381,6 +388,61 @@ def _dense_reproj_status(status, B, dev):
     if tuple(status.shape) != (B,):
         raise ValueError('dense_reproj: status must be (%d), got %s' % (B, tuple(status.shape)))
     return status
+
+
+DenseBAPropagated = collections.namedtuple('DenseBAPropagated', 'inv_depth var_inv_depth depth source flags status')
+
+
+def dense_ba_depth_propagate(inv_depth, var_inv_depth, motion, intr, mask=None, status=None, rgb2imu=None, process_var=0.0, depth_next=None,
+                             var_next=None, gate=0.0):
+    """The inverse depths and variances of the first frame of each link carried into the pixel grid of its second frame and fused
+    there with that frame's own measurement (include/islam_hip.h, islam_depth_propagate).  inv_depth,
+    var_inv_depth (B,H,W): the state a joint refinement returned and its variance in 1/m^2 (sigma_px^2 v of dense_ba_depth_variance; a
+    pixel whose variance is NaN, or not > 0, is not carried over); motion (B,7) SE3 [t, q]; intr (4) or (B,4); mask (B,H,W) or None;
+    status (B) int or None: a link whose status is not 0 propagates nothing; rgb2imu (7) or None; process_var: a non-negative number
+    or (B,), added to every propagated variance (a device tensor is not read back: a negative or non-finite entry marks its link with
+    _lib.DENSE_REPROJ_BADPRIOR on the device); depth_next, var_next (B,H,W) on the device or both None: the second frame's depth and
+    the variance of its inverse depth; gate >= 0: a propagated value further than gate standard deviations from the measurement gives
+    way to it (0: never).  Returns DenseBAPropagated(inv_depth, var_inv_depth (B,H,W) float64: 0 and NaN where nothing is known, depth
+    (B,H,W) float32, source (B,H,W) int32: the source pixel that won the z-buffer or -1, flags (B,H,W) uint8: 1 propagated, 2 measured,
+    4 gated out, status (B) int32).  One memset and two launches, nothing is read back."""
+    dev = inv_depth.device
+    if inv_depth.dim() != 3 or tuple(var_inv_depth.shape) != tuple(inv_depth.shape):
+        raise ValueError('dense_ba_depth_propagate: inv_depth and var_inv_depth must be (B,H,W), got %s and %s' % (
+            tuple(inv_depth.shape), tuple(var_inv_depth.shape)))
+    B, H, W = inv_depth.shape
+    rho, var = (t.detach().to(dev, torch.float64).contiguous() for t in (inv_depth, var_inv_depth))
+    mask, motion, intr, rgb2imu = _dense_link_args('dense_ba_depth_propagate', dev, B, H, W, mask, motion, intr, rgb2imu)
+    if not torch.is_tensor(process_var):
+        process_var = torch.as_tensor(process_var, dtype=torch.float64)
+    if not process_var.is_cuda and not bool(((process_var >= 0) & torch.isfinite(process_var)).all()):
+        raise ValueError('dense_ba_depth_propagate: process_var must be finite and non-negative (got %s)' % (process_var.tolist(),))
+    pv = process_var.detach().to(dev, torch.float64)
+    if pv.numel() == 1:
+        pv = pv.reshape(1).expand(B)
+    if tuple(pv.shape) != (B,):
+        raise ValueError('dense_ba_depth_propagate: process_var must be a number or (%d,), got %s' % (B, tuple(pv.shape)))
+    pv = pv.contiguous()
+    if (depth_next is None) != (var_next is None):
+        raise ValueError('dense_ba_depth_propagate: depth_next and var_next come together or not at all')
+    if depth_next is not None:
+        if tuple(depth_next.shape) != (B, H, W) or tuple(var_next.shape) != (B, H, W):
+            raise ValueError('dense_ba_depth_propagate: depth_next and var_next must be (%d,%d,%d), got %s and %s' % (
+                B, H, W, tuple(depth_next.shape), tuple(var_next.shape)))
+        depth_next, var_next = _f32c(depth_next.detach().to(dev)), _f32c(var_next.detach().to(dev))
+    gate = float(gate)
+    if not (gate >= 0.0 and gate < float('inf')):
+        raise ValueError('dense_ba_depth_propagate: gate must be finite and non-negative (got %r)' % (gate,))
+    status = _dense_reproj_status(status, B, dev)
+    require_cuda(inv_depth, var_inv_depth, depth_next, var_next)      # after the argument rules, which need no device
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    out = DenseBAPropagated(e(torch.float64, B, H, W), e(torch.float64, B, H, W), e(torch.float32, B, H, W), e(torch.int32, B, H, W),
+                            e(torch.uint8, B, H, W), e(torch.int32, B))
+    scratch = torch.empty(lib().islam_depth_propagate_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
+    check(lib().islam_depth_propagate(ptr(rho), ptr(var), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(status), ptr(pv),
+                                      ptr(depth_next), ptr(var_next), gate, ptr(out.inv_depth), ptr(out.var_inv_depth), ptr(out.depth),
+                                      ptr(out.source), ptr(out.flags), ptr(out.status), ptr(scratch), B, H, W, stream_ptr(dev)))
+    return out
 
 
 def dense_reproj_vjp(depth, flow, mask, motion, intr, w, rgb2imu=None, kernel=None, status=None):

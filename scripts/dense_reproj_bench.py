@@ -31,6 +31,12 @@ ops.dense_ba_depth_variance at the refined state with the sums given, marginal o
 ops.dense_ba_vjp on the same tensors, which moves about as many bytes.
 
     python scripts/dense_reproj_bench.py --uncertainty [--case 448x640] [--out profiles/dense_ba_uncertainty_bench.json]
+
+--propagate times the depth propagation instead: ops.dense_ba_depth_propagate of a refined state and its
+variance into the next frame, alone and fused with a measurement at gate 3.  The yardstick is ops.dense_ba_depth_variance on the same
+tensors in the same process, a pixel pass that moves about half as many bytes.
+
+    python scripts/dense_reproj_bench.py --propagate [--case 448x640] [--out profiles/depth_propagate_bench.json]
 """
 import json
 import os
@@ -508,8 +514,86 @@ def main_uncertainty(argv):
         f.write(line + '\n')
 
 
+# the nominal bytes of one pixel in ops.dense_ba_depth_propagate with a measurement: the key cleared (8), the splat's rho, variance and
+# mask (17) and its atomic (8), the fuse pass's key (8), the winner's rho, variance and mask again (17), depth_next and var_next (8), and
+# its five stores (8 + 8 + 4 + 4 + 1); without a measurement 8 fewer
+PROP_PIXEL_BYTES = 91
+
+
+def run_propagate_case(H, W):
+    """--propagate: the cost of carrying a refined state into the next frame."""
+    import numpy as np
+    import torch
+    from islam_amd import ops
+    from tests.dense_reproj_f64 import MOUNT, PRIOR_W, make_scene, noisy_prior, right_perturb
+    dev = torch.device('cuda:0')
+    sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    w = torch.full((B,), PRIOR_W, dtype=torch.float64, device=dev)
+    ref = ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20)
+    state = (depth, flow, mask, ref.motion, intr, w)
+    var_fn = lambda: ops.dense_ba_depth_variance(*state, inv_depth=ref.inv_depth, sums=ref.sums, status=ref.status, rgb2imu=mount)
+    var = 0.09 * var_fn().var
+    depth_next = d(sc['depth'] * (1.0 + 0.02 * np.random.default_rng(4).standard_normal(sc['depth'].shape)).astype(np.float32))
+    var_next = torch.full((B, H, W), 4e-4, dtype=torch.float32, device=dev)
+    pv = torch.full((B,), 1e-6, dtype=torch.float64, device=dev)          # on the device, like w: no host-to-device copy inside the timed call
+    prop = lambda **kw: ops.dense_ba_depth_propagate(ref.inv_depth, var, ref.motion, intr, mask=mask, status=ref.status, rgb2imu=mount, process_var=pv, **kw)
+    fns = {'depth_var_marginal': var_fn, 'propagate': prop, 'propagate_fuse': lambda: prop(depth_next=depth_next, var_next=var_next, gate=3.0)}
+
+    def median(fn, n=30):
+        us = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        us.sort()
+        return 0.5 * (us[n // 2 - 1] + us[n // 2])
+
+    out = {}
+    for name, fn in fns.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = median(fn)
+    p = fns['propagate_fuse']()
+    out['status_ok'] = int((p.status == 0).sum())
+    out['hit_fraction'] = float(((p.flags & 1) != 0).double().mean())
+    out['gated_fraction'] = float(((p.flags & 4) != 0).double().mean())
+    out['propagate_over_var'] = out['propagate'] / out['depth_var_marginal']
+    out['fuse_over_var'] = out['propagate_fuse'] / out['depth_var_marginal']
+    out['MB_moved_fuse'] = PROP_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_fuse'] = PROP_PIXEL_BYTES * B * H * W / (out['propagate_fuse'] * 1e-6) / 1e9 / HBM_GBS
+    return out
+
+
+def main_propagate(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_propagate_case(*hw) for case, hw in cases.items()}
+    cols = ('depth_var_marginal', 'propagate', 'propagate_fuse', 'propagate_over_var', 'fuse_over_var', 'MB_moved_fuse', 'hbm_frac_fuse', 'status_ok',
+            'hit_fraction', 'gated_fraction')
+    print('us per call at B = %d: the median of 30; hbm_frac_fuse: %d bytes per pixel over the time, of %.0f GB/s' % (B, PROP_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'depth_propagate_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--propagate' in sys.argv[1:]:
+        return main_propagate(sys.argv[1:])
     if '--uncertainty' in sys.argv[1:]:
         return main_uncertainty(sys.argv[1:])
     if '--joint-grad' in sys.argv[1:]:
