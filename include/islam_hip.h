@@ -623,6 +623,38 @@ int islam_depth_propagate(const double* inv_depth, const double* var_inv_depth, 
                           double* out_var, float* out_depth, int* out_source, uint8_t* out_flags, int* out_status, void* scratch,
                           int B, int H, int W, void* stream);
 
+/* Regularisation of a propagated map: occlusion removal, hole filling and smoothing of the inverse depths rho
+ * and variances s (B,H,W) float64 that islam_depth_propagate returned without a measurement, then the fusion table above.  All device
+ * arithmetic is fp64, every operation rounded on its own.  A window is the (2r+1)^2 square around a pixel clipped at the image border,
+ * walked row by row, which is the order of every sum.  valid0(k): rho_k and s_k finite and > 0.  compat(k,j): (rho_k - rho_j)^2 <=
+ * reg_gate^2 (s_k + s_j).
+ *   1. removal (occl_radius): for a valid0 j, over k != j in the window, n_sup = #{valid0, compat}, n_occ = #{valid0, not compat,
+ *      rho_k > rho_j}; j is removed iff n_occ >= occl_min and n_occ > n_sup.  valid1 = valid0 and not removed.
+ *   2. filling (fill_radius): for a j in the image that is not valid1, a = the valid1 neighbour with the largest rho (the first in
+ *      the window's order among equals), the cluster = {valid1 k : compat(k,a)}, n its size; if n >= fill_min, with w_k = 1 / s_k,
+ *      Sw = sum w_k:  rho_j = mean = (sum w_k rho_k) / Sw,  s_j = fill_inflate (n / Sw + (sum w_k (rho_k - mean)^2) / Sw), the second
+ *      sum a pass of its own with terms w_k ((rho_k - mean)(rho_k - mean)).  Only stage-1 values are read.  valid2 = valid1 or filled.
+ *   3. smoothing (smooth_radius): for a valid2 j, over the valid2 k of the window (j included) with compat(k,j), on stage-2 values,
+ *      w_k = 1 / (s_k + dist_var[b] (du^2 + dv^2)):  rho_j <- (sum w_k rho_k) / (sum w_k);  s_j stays.
+ *   4. the fusion table of islam_depth_propagate on (rho_j, s_j, present = valid2) with depth_next, var_next and gate.
+ * A radius of 0 leaves its stage out; with the three radii 0 and no measurement a map that holds (0, NaN) at its holes is returned
+ * bit for bit.  Outputs as islam_depth_propagate's, all written in full.  out_flags: bit 0 valid2, bits 1 and 2 as above, bit 3 (8)
+ * filled, bit 4 (16) removed by stage 1 (both where a removed pixel was filled again).  out_source: source_or_null's entry where the
+ * pixel is valid1, else -1 (all -1 without a source map).  out_status (B): status_or_null's value where that is not 0,
+ * ISLAM_DENSE_REPROJ_BADPRIOR where dist_var[b] (1/m^2 per px^2) is negative or not finite (formed on the device), else 0; a link
+ * whose out_status is not 0 gets the measurement alone at every pixel.
+ * One launch on `stream` (depth_regularize_kernel: a 32 x 8 tile with a halo of the three radii in LDS, plain stores, no atomics, so a
+ * repeat gives the same bits), no host wait, no scratch: islam_depth_regularize_scratch_bytes returns 0 and scratch may be NULL.
+ * ISLAM_EARG before any device work for a bad shape (as above), a NULL pointer other than source_or_null, status_or_null,
+ * depth_next_or_null, var_next_or_null and scratch, depth_next without var_next or the reverse, a radius outside 0..2, occl_min or
+ * fill_min < 1, fill_inflate < 1 or not finite, reg_gate not finite or not > 0, and a gate that is negative or not finite. */
+size_t islam_depth_regularize_scratch_bytes(int B, int H, int W);
+int islam_depth_regularize(const double* inv_depth, const double* var_inv_depth, const int* source_or_null, const int* status_or_null,
+                           const double* dist_var, const float* depth_next_or_null, const float* var_next_or_null, double gate,
+                           int occl_radius, int occl_min, int fill_radius, int fill_min, double fill_inflate, int smooth_radius,
+                           double reg_gate, double* out_inv_depth, double* out_var, float* out_depth, int* out_source,
+                           uint8_t* out_flags, int* out_status, void* scratch, int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

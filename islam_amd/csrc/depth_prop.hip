@@ -10,6 +10,10 @@
 // nearest surface wins, the smaller source index on equal fp32 keys, and a maximum does not depend on the order of arrival, so a repeat
 // gives the same bits.  depth_fuse_kernel reads the key of every target, recomputes (rho', s') of the winning source with the same
 // function (prop_pixel) and applies the fusion table; plain stores, no reduction, no atomics.
+//
+// depth_regularize_kernel (islam_depth_regularize) stands between the two when the caller asks for it: on the
+// map a pure propagation returned it removes background seen through the holes of a magnified surface, fills holes from their
+// neighbours and smooths every value over its compatible neighbours, a stencil on an LDS tile, and ends in the same fusion table.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -107,12 +111,40 @@ struct FusedPixel {
     int src, flags;
 };
 
-// One target of a link from its key and its measurement (has_meas: there is one; dn, vn: depth_next and var_next there): the winner's
-// (rho', s') by prop_pixel, the fusion table.  Not contracted either, so the fused values are the individually rounded operations of
-// the header's formulas.  live (uniform over the workgroup): the link propagates at all.
+// The fusion table at one target: the propagated hypothesis (have: there is one; rp, sp; src: what out_source gets) against the
+// measurement (has_meas: the call has one; dn, vn: depth_next and var_next there).  Not contracted, so the fused values are the
+// individually rounded operations of the header's formulas.  The fuse kernel and the regularisation kernel both end here.
+ISLAM_DEV FusedPixel fuse_table(bool have, double rp, double sp, int src, bool has_meas, float dn, float vn, double gate, double g2) {
+#pragma clang fp contract(off)
+    const double sm = has_meas ? (double)vn : NAN;
+    const bool meas = has_meas && isfinite(dn) && dn > 0.0f && isfinite(sm) && sm > 0.0;
+    const double rm = meas ? 1.0 / (double)dn : 0.0;
+    int flags = (have ? FLAG_PROP : 0) | (meas ? FLAG_MEAS : 0);
+    double rf = 0.0, sf = NAN;
+    if (have && meas) {
+        const double d = rp - rm, sum = sp + sm;
+        if (gate > 0.0 && d * d > g2 * sum) {      // the hypotheses conflict: the measurement alone
+            flags |= FLAG_GATED;
+            rf = rm;
+            sf = sm;
+        } else {
+            rf = (rp * sm + rm * sp) / sum;
+            sf = sp * sm / sum;
+        }
+    } else if (have) {
+        rf = rp;
+        sf = sp;
+    } else if (meas) {
+        rf = rm;
+        sf = sm;
+    }
+    return {rf, sf, rf > 0.0 ? (float)(1.0 / rf) : dn, src, flags};      // dn: the bits of depth_next, 0 without one
+}
+
+// One target of a link from its key and its measurement: the winner's (rho', s') by prop_pixel, the fusion table.  live (uniform over
+// the workgroup): the link propagates at all.
 ISLAM_DEV FusedPixel fuse_target(const PropLink& lk, bool live, unsigned long long key, bool has_meas, float dn, float vn, double gate, double g2,
                                  int HW) {
-#pragma clang fp contract(off)
     int src = -1;
     double rp = 0.0, sp = NAN;
     if (live) {
@@ -127,29 +159,7 @@ ISLAM_DEV FusedPixel fuse_target(const PropLink& lk, bool live, unsigned long lo
             sp = p.var;
         }
     }
-    const double sm = has_meas ? (double)vn : NAN;
-    const bool meas = has_meas && isfinite(dn) && dn > 0.0f && isfinite(sm) && sm > 0.0;
-    const double rm = meas ? 1.0 / (double)dn : 0.0;
-    int flags = (src >= 0 ? FLAG_PROP : 0) | (meas ? FLAG_MEAS : 0);
-    double rf = 0.0, sf = NAN;
-    if (src >= 0 && meas) {
-        const double d = rp - rm, sum = sp + sm;
-        if (gate > 0.0 && d * d > g2 * sum) {      // the hypotheses conflict: the measurement alone
-            flags |= FLAG_GATED;
-            rf = rm;
-            sf = sm;
-        } else {
-            rf = (rp * sm + rm * sp) / sum;
-            sf = sp * sm / sum;
-        }
-    } else if (src >= 0) {
-        rf = rp;
-        sf = sp;
-    } else if (meas) {
-        rf = rm;
-        sf = sm;
-    }
-    return {rf, sf, rf > 0.0 ? (float)(1.0 / rf) : dn, src, flags};      // dn: the bits of depth_next, 0 without one
+    return fuse_table(src >= 0, rp, sp, src, has_meas, dn, vn, gate, g2);
 }
 
 // grid (NBLK, B) x 256, grid-stride over the source pixels.  keys (B,H,W) was cleared on the same stream ahead of the launch.
@@ -203,7 +213,223 @@ __global__ __launch_bounds__(256) void depth_fuse_kernel(const double* __restric
     }
 }
 
+// ------------------------------------------------------------------ regularisation of a propagated map
+constexpr int FLAG_FILLED = 8, FLAG_REMOVED = 16;
+constexpr int REG_TW = 32, REG_TH = 8;            // the output tile of a workgroup, one pixel per thread
+constexpr int REG_RMAX = 2, REG_HALO = 3 * REG_RMAX;
+constexpr int REG_CELLS = (REG_TW + 2 * REG_HALO) * (REG_TH + 2 * REG_HALO);      // 44 x 20
+
+// the three stencil stages as the kernel takes them: the radii, the two counts, fill_inflate and reg_gate^2
+struct RegStages {
+    int r1, occl_min, r2, fill_min, r3;
+    double inflate, g2;
+};
+
+// compat(k, j): (rho_k - rho_j)^2 <= reg_gate^2 (s_k + s_j); the same bits with k and j exchanged
+ISLAM_DEV bool reg_compat(double rk, double sk, double rj, double sj, double g2) {
+#pragma clang fp contract(off)
+    const double d = rk - rj;
+    return d * d <= g2 * (sk + sj);
+}
+
+// the status of link b: the incoming one if set, BADPRIOR for a dist_var[b] that is negative or not finite, else OK
+ISLAM_DEV int reg_status(const int* __restrict__ status, const double* __restrict__ dist_var, int b) {
+    const int s = status ? status[b] : ISLAM_DENSE_REPROJ_OK;
+    if (s != ISLAM_DENSE_REPROJ_OK) return s;
+    const double dv = dist_var[b];
+    return (isfinite(dv) && dv >= 0.0) ? ISLAM_DENSE_REPROJ_OK : ISLAM_DENSE_REPROJ_BADPRIOR;
+}
+
+// grid (tiles_x tiles_y, B) x 256.  A workgroup owns a 32 x 8 tile of link b and holds it with a halo of h = r1 + r2 + r3 in LDS: the
+// cell (lx, ly) of the (32 + 2h) x (8 + 2h) region is pixel (x0 - h + lx, y0 - h + ly), and a cell outside the image is not valid, which
+// is all the clipping of a window at the border needs.  Stage 1 marks the removed cells of the region less r1, stage 2 fills the cells
+// of the region less r1 + r2 in place (it writes only cells that are not valid after stage 1 and reads only cells that are, so no
+// thread reads what another writes between two barriers), stages 3 and 4 run on the tile itself and store to global memory.  Every
+// window is walked row by row, which is the order of the sums.
+__global__ __launch_bounds__(256) void depth_regularize_kernel(const double* __restrict__ inv_depth, const double* __restrict__ var_inv_depth,
+                                                                const int* __restrict__ source, const int* __restrict__ status,
+                                                                const double* __restrict__ dist_var, const float* __restrict__ depth_next,
+                                                                const float* __restrict__ var_next, double gate, RegStages rs,
+                                                                double* __restrict__ out_inv_depth, double* __restrict__ out_var,
+                                                                float* __restrict__ out_depth, int* __restrict__ out_source,
+                                                                uint8_t* __restrict__ out_flags, int* __restrict__ out_status, int H, int W,
+                                                                int tiles_x) {
+#pragma clang fp contract(off)
+    __shared__ double srho[REG_CELLS], svar[REG_CELLS];
+    __shared__ uint8_t sv0[REG_CELLS], srem[REG_CELLS], sfil[REG_CELLS];      // valid on input; removed by stage 1; filled by stage 2
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int h = rs.r1 + rs.r2 + rs.r3;
+    const int LW = REG_TW + 2 * h, LH = REG_TH + 2 * h;
+    const int gx0 = tx * REG_TW - h, gy0 = ty * REG_TH - h;      // the pixel of cell (0, 0)
+    const size_t off = (size_t)b * H * W;
+    const int st = reg_status(status, dist_var, b);
+    if (blockIdx.x == 0 && tid == 0) out_status[b] = st;
+    const bool live = st == ISLAM_DENSE_REPROJ_OK;      // (uniform over the workgroup) a link with a status: the measurement only
+    if (live) {
+        for (int c = tid; c < LW * LH; c += 256) {
+            const int ly = c / LW, lx = c - ly * LW;
+            const int gx = gx0 + lx, gy = gy0 + ly;
+            double r = 0.0, s = 0.0;
+            bool ok = false;
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                r = inv_depth[off + gy * W + gx];
+                s = var_inv_depth[off + gy * W + gx];
+                ok = isfinite(r) && r > 0.0 && isfinite(s) && s > 0.0;
+            }
+            srho[c] = r;
+            svar[c] = s;
+            sv0[c] = ok;
+            srem[c] = 0;
+            sfil[c] = 0;
+        }
+        __syncthreads();
+        if (rs.r1 > 0) {      // occlusion removal: a cell with more nearer incompatible neighbours than compatible ones goes
+            const int o = rs.r1, w = LW - 2 * o, n = w * (LH - 2 * o);
+            for (int c = tid; c < n; c += 256) {
+                const int ly = c / w, j = (ly + o) * LW + (c - ly * w) + o;
+                if (!sv0[j]) continue;
+                const double rj = srho[j], sj = svar[j];
+                int nsup = 0, nocc = 0;
+                for (int dv = -rs.r1; dv <= rs.r1; ++dv)
+                    for (int du = -rs.r1; du <= rs.r1; ++du) {
+                        const int k = j + dv * LW + du;
+                        if (k == j || !sv0[k]) continue;
+                        const double rk = srho[k];
+                        if (reg_compat(rk, svar[k], rj, sj, rs.g2))
+                            ++nsup;
+                        else if (rk > rj)
+                            ++nocc;
+                    }
+                if (nocc >= rs.occl_min && nocc > nsup) srem[j] = 1;
+            }
+            __syncthreads();
+        }
+        if (rs.r2 > 0) {      // hole filling: the cluster around the nearest neighbour, its weighted mean, one neighbour's variance
+            const int o = rs.r1 + rs.r2, w = LW - 2 * o, n = w * (LH - 2 * o);
+            for (int c = tid; c < n; c += 256) {
+                const int ly = c / w + o, lx = c - (ly - o) * w + o, j = ly * LW + lx;
+                const int gx = gx0 + lx, gy = gy0 + ly;
+                if (gx < 0 || gx >= W || gy < 0 || gy >= H || (sv0[j] && !srem[j])) continue;
+                int ka = -1;
+                double ra = 0.0;
+                for (int dv = -rs.r2; dv <= rs.r2; ++dv)
+                    for (int du = -rs.r2; du <= rs.r2; ++du) {
+                        const int k = j + dv * LW + du;
+                        if (!sv0[k] || srem[k]) continue;
+                        const double rk = srho[k];
+                        if (ka < 0 || rk > ra) {
+                            ka = k;
+                            ra = rk;
+                        }
+                    }
+                if (ka < 0) continue;
+                const double sa = svar[ka];
+                int cnt = 0;
+                double Sw = 0.0, Swr = 0.0;
+                for (int dv = -rs.r2; dv <= rs.r2; ++dv)
+                    for (int du = -rs.r2; du <= rs.r2; ++du) {
+                        const int k = j + dv * LW + du;
+                        if (!sv0[k] || srem[k]) continue;
+                        const double rk = srho[k], sk = svar[k];
+                        if (!reg_compat(rk, sk, ra, sa, rs.g2)) continue;
+                        const double wk = 1.0 / sk;
+                        Sw = Sw + wk;
+                        Swr = Swr + wk * rk;
+                        ++cnt;
+                    }
+                if (cnt < rs.fill_min) continue;
+                const double mean = Swr / Sw;
+                double Se = 0.0;
+                for (int dv = -rs.r2; dv <= rs.r2; ++dv)
+                    for (int du = -rs.r2; du <= rs.r2; ++du) {
+                        const int k = j + dv * LW + du;
+                        if (!sv0[k] || srem[k]) continue;
+                        const double rk = srho[k], sk = svar[k];
+                        if (!reg_compat(rk, sk, ra, sa, rs.g2)) continue;
+                        const double e = rk - mean;
+                        Se = Se + (1.0 / sk) * (e * e);
+                    }
+                srho[j] = mean;
+                svar[j] = rs.inflate * ((double)cnt / Sw + Se / Sw);
+                sfil[j] = 1;
+            }
+            __syncthreads();
+        }
+    }
+    const int lx = (tid & (REG_TW - 1)) + h, ly = tid / REG_TW + h;
+    const int gx = gx0 + lx, gy = gy0 + ly;
+    if (gx >= W || gy >= H) return;      // past the last barrier
+    const int j = ly * LW + lx, gj = gy * W + gx;
+    bool have = false, kept = false;
+    int extra = 0;
+    double r3 = 0.0, s3 = NAN;
+    if (live) {
+        kept = sv0[j] && !srem[j];
+        have = kept || sfil[j];
+        extra = (sfil[j] ? FLAG_FILLED : 0) | (srem[j] ? FLAG_REMOVED : 0);
+    }
+    if (have) {
+        r3 = srho[j];
+        s3 = svar[j];
+        if (rs.r3 > 0) {      // smoothing: the weighted mean over the compatible neighbours, the variance as it was
+            const double dvar = dist_var[b];
+            double Sw = 0.0, Swr = 0.0;
+            for (int dv = -rs.r3; dv <= rs.r3; ++dv)
+                for (int du = -rs.r3; du <= rs.r3; ++du) {
+                    const int k = j + dv * LW + du;
+                    if (!((sv0[k] && !srem[k]) || sfil[k])) continue;
+                    const double rk = srho[k], sk = svar[k];
+                    if (!reg_compat(rk, sk, r3, s3, rs.g2)) continue;
+                    const double wk = 1.0 / (sk + dvar * (double)(du * du + dv * dv));
+                    Sw = Sw + wk;
+                    Swr = Swr + wk * rk;
+                }
+            r3 = Swr / Sw;      // j itself is in the window and compatible with itself: Sw > 0
+        }
+    }
+    const bool has_meas = depth_next != nullptr;
+    const FusedPixel f = fuse_table(have, r3, s3, kept && source ? source[off + gj] : -1, has_meas, has_meas ? depth_next[off + gj] : 0.0f,
+                                    has_meas ? var_next[off + gj] : 0.0f, gate, gate * gate);
+    out_inv_depth[off + gj] = f.rho;
+    out_var[off + gj] = f.var;
+    out_depth[off + gj] = f.depth;
+    out_source[off + gj] = f.src;
+    out_flags[off + gj] = (uint8_t)(f.flags | extra);
+}
+
 }  // namespace
+
+extern "C" size_t islam_depth_regularize_scratch_bytes(int B, int H, int W) { return 0; }      // one fused launch: nothing in between
+
+extern "C" int islam_depth_regularize(const double* inv_depth, const double* var_inv_depth, const int* source_or_null, const int* status_or_null,
+                                      const double* dist_var, const float* depth_next_or_null, const float* var_next_or_null, double gate,
+                                      int occl_radius, int occl_min, int fill_radius, int fill_min, double fill_inflate, int smooth_radius,
+                                      double reg_gate, double* out_inv_depth, double* out_var, float* out_depth, int* out_source,
+                                      uint8_t* out_flags, int* out_status, void* scratch, int B, int H, int W, void* stream) {
+    const char* who = "islam_depth_regularize";
+    if (int rc = check_shape_kind(who, B, H, W, ISLAM_ROBUST_NONE, 1.0)) return rc;
+    if (!inv_depth || !var_inv_depth || !dist_var) return fail(ISLAM_EARG, "%s: NULL inv_depth / var_inv_depth / dist_var pointer", who);
+    if (!out_inv_depth || !out_var || !out_depth || !out_source || !out_flags || !out_status)
+        return fail(ISLAM_EARG, "%s: NULL output pointer", who);
+    if ((depth_next_or_null == nullptr) != (var_next_or_null == nullptr))
+        return fail(ISLAM_EARG, "%s: depth_next and var_next come together or not at all", who);
+    if (!(std::isfinite(gate) && gate >= 0.0)) return fail(ISLAM_EARG, "%s: gate must be finite and non-negative (got %g)", who, gate);
+    for (int r : {occl_radius, fill_radius, smooth_radius})
+        if (r < 0 || r > REG_RMAX)
+            return fail(ISLAM_EARG, "%s: a radius must be 0..%d (got %d, %d, %d)", who, REG_RMAX, occl_radius, fill_radius, smooth_radius);
+    if (occl_min < 1 || fill_min < 1) return fail(ISLAM_EARG, "%s: occl_min and fill_min must be at least 1 (got %d, %d)", who, occl_min, fill_min);
+    if (!(std::isfinite(fill_inflate) && fill_inflate >= 1.0))
+        return fail(ISLAM_EARG, "%s: fill_inflate must be finite and at least 1 (got %g)", who, fill_inflate);
+    if (!(std::isfinite(reg_gate) && reg_gate > 0.0)) return fail(ISLAM_EARG, "%s: reg_gate must be finite and positive (got %g)", who, reg_gate);
+    const int tiles_x = (W + REG_TW - 1) / REG_TW, tiles_y = (H + REG_TH - 1) / REG_TH;      // H W <= 2^30: at most 2^30 tiles
+    const RegStages rs{occl_radius, occl_min, fill_radius, fill_min, smooth_radius, fill_inflate, reg_gate * reg_gate};
+    hipLaunchKernelGGL(depth_regularize_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, as_stream(stream), inv_depth, var_inv_depth,
+                       source_or_null, status_or_null, dist_var, depth_next_or_null, var_next_or_null, gate, rs, out_inv_depth, out_var,
+                       out_depth, out_source, out_flags, out_status, H, W, tiles_x);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
 
 extern "C" size_t islam_depth_propagate_scratch_bytes(int B, int H, int W) {
     if (B < 1 || H < 1 || W < 1) return 0;

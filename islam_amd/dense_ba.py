@@ -14,7 +14,8 @@
     refined pose, inverse depths or depth map reach the stored depth and flow (section 3.26); both take the prior's standard
     deviation per pixel as well, and ``depth_uncertainty`` returns the posterior standard deviation of every refined depth
     (section 3.27); ``propagate`` carries both into the next frame's pixel grid and fuses them with that frame's own depth map, the
-    prior of the next link (csrc/depth_prop.hip, section 3.28);
+    prior of the next link (csrc/depth_prop.hip, section 3.28), with ``regularize=DepthRegularizer(...)`` after occlusion removal,
+    hole filling and smoothing of the propagated map (section 3.29);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -28,6 +29,20 @@ from . import lietensor as pp
 DenseBAJoint = collections.namedtuple('DenseBAJoint', 'motion inv_depth S g cost l1 count sums damping accepted rejected status trace depth')
 DenseBADepthUncertainty = collections.namedtuple('DenseBADepthUncertainty', 'var_inv_depth sigma_inv_depth sigma_depth status')
 DenseBAPrior = collections.namedtuple('DenseBAPrior', 'depth sigma_inv_depth inv_depth var_inv_depth source flags status')
+
+
+class DepthRegularizer(collections.namedtuple('DepthRegularizer', 'occl_radius occl_min fill_radius fill_min fill_inflate smooth_radius reg_gate dist_sigma',
+                                              defaults=(1, 2, 1, 3, 1.0, 1, 3.0, 0.0))):
+    """What ``DenseReprojectionLoss.propagate(regularize=...)`` does to the propagated map before it is fused with the next frame's
+    measurement (ops.dense_ba_depth_regularize), an immutable record.  occl_radius, occl_min: a pixel with at
+    least occl_min nearer, incompatible neighbours within the radius, and more of them than compatible ones, is removed (background
+    seen through the holes of a magnified surface); fill_radius, fill_min, fill_inflate: a hole with at least fill_min mutually
+    compatible neighbours takes their weighted mean, and fill_inflate times a neighbour's variance plus their scatter; smooth_radius:
+    every value becomes the weighted mean of its compatible neighbours and keeps its variance; reg_gate: two values are compatible
+    within this many standard deviations of their difference; dist_sigma (1/m per pixel, a non-negative number or a (B,) tensor): the
+    expected change of the inverse depth from one pixel to the next, whose square the smoothing adds to a neighbour's variance per
+    squared pixel of distance.  A radius of 0 leaves its stage out."""
+    __slots__ = ()
 
 
 def pixel2point(pixels, depth, intrinsics):
@@ -318,7 +333,23 @@ class DenseReprojectionLoss:
         ok = torch.isfinite(sig) & (sig > 0)
         return torch.where(ok, sig * sig, torch.full_like(sig, float('nan'))).to(torch.float32).contiguous()
 
-    def propagate(self, joint, uncertainty, depth_next=None, sigma_inv_depth_next=None, process_sigma=0.0, gate=3.0):
+    @staticmethod
+    def _link_sigma_squared(sigma, name):
+        """A per-link standard deviation of propagate (a number or a (B,) tensor) as the variance ops takes.  A number or a host tensor
+        is validated here (ValueError); a device tensor is never read back: an entry that is negative or not finite becomes NaN, which
+        the kernel reports as _lib.DENSE_REPROJ_BADPRIOR on that link."""
+        if torch.is_tensor(sigma):
+            ps = sigma.detach().to(torch.float64)
+            if not ps.is_cuda and not bool(((ps >= 0) & torch.isfinite(ps)).all()):
+                raise ValueError('propagate: %s must be finite and non-negative (got %s)' % (name, ps.tolist()))
+            ok = torch.isfinite(ps) & (ps >= 0)
+            return torch.where(ok, ps * ps, torch.full_like(ps, float('nan')))
+        ps = float(sigma)
+        if not (ps >= 0.0 and ps < float('inf')):
+            raise ValueError('propagate: %s must be a finite non-negative number (got %r)' % (name, sigma))
+        return ps * ps
+
+    def propagate(self, joint, uncertainty, depth_next=None, sigma_inv_depth_next=None, process_sigma=0.0, gate=3.0, regularize=None):
         """The step from one link to the next: the inverse depths a ``refine_joint`` returned (``joint``) and their variances
         (``uncertainty``: the result of ``depth_uncertainty`` for it) are warped through the refined pose into the pixel grid of the
         link's second frame, the nearest surface winning where several pixels land on one, and fused there with that frame's own depth
@@ -331,7 +362,13 @@ class DenseReprojectionLoss:
         depth (B,H,W) float32 and sigma_inv_depth (B,H,W) float64 (NaN where nothing is known), which go straight into the next
         DenseReprojectionLoss(depth=...) and refine_joint(sigma_inv_depth=...); inv_depth and var_inv_depth (float64), source (the
         pixel of the first frame that won, -1 for none), flags (1 propagated, 2 measured, 4 gated out) and status (B) int32: a link
-        whose refinement or uncertainty came with a status propagates nothing and returns the measurement alone."""
+        whose refinement or uncertainty came with a status propagates nothing and returns the measurement alone.
+
+        regularize (a DepthRegularizer or None): the propagated map is regularised before the fusion -- the
+        pure propagation, then ops.dense_ba_depth_regularize with the measurement and ``gate``: background seen through the holes of a
+        magnified surface is removed, holes are filled from their neighbours, every value is smoothed over its compatible neighbours.
+        flags then also carries 8 (filled) and 16 (removed), its 1 means "a propagated or filled value is present", and source is -1
+        at filled and removed pixels.  None: the single call above, unchanged."""
         from . import ops
         if (depth_next is None) != (sigma_inv_depth_next is None):
             raise ValueError('propagate: depth_next and sigma_inv_depth_next come together or not at all')
@@ -341,20 +378,19 @@ class DenseReprojectionLoss:
                 raise ValueError('propagate: depth_next must be %s, got %s' % (tuple(self.z.shape), tuple(depth_next.shape)))
             var_next = self._variance_next(sigma_inv_depth_next, 'propagate')
             depth_next = depth_next.detach().to(self.z.device)
-        if torch.is_tensor(process_sigma):
-            ps = process_sigma.detach().to(torch.float64)
-            if not ps.is_cuda and not bool(((ps >= 0) & torch.isfinite(ps)).all()):
-                raise ValueError('propagate: process_sigma must be finite and non-negative (got %s)' % (ps.tolist(),))
-            ok = torch.isfinite(ps) & (ps >= 0)
-            process_var = torch.where(ok, ps * ps, torch.full_like(ps, float('nan')))      # NaN: BADPRIOR on the device, no read-back
+        process_var = self._link_sigma_squared(process_sigma, 'process_sigma')
+        link = (joint.inv_depth, uncertainty.var_inv_depth, joint.motion, torch.tensor(self.K4, dtype=torch.float64))
+        link_kw = dict(mask=self.mask, status=uncertainty.status, rgb2imu=self.rgb2imu_pose, process_var=process_var)
+        if regularize is None:
+            out = ops.dense_ba_depth_propagate(*link, **link_kw, depth_next=depth_next, var_next=var_next, gate=gate)
         else:
-            ps = float(process_sigma)
-            if not (ps >= 0.0 and ps < float('inf')):
-                raise ValueError('propagate: process_sigma must be a finite non-negative number (got %r)' % (process_sigma,))
-            process_var = ps * ps
-        out = ops.dense_ba_depth_propagate(joint.inv_depth, uncertainty.var_inv_depth, joint.motion, torch.tensor(self.K4, dtype=torch.float64),
-                                           mask=self.mask, status=uncertainty.status, rgb2imu=self.rgb2imu_pose, process_var=process_var,
-                                           depth_next=depth_next, var_next=var_next, gate=gate)
+            if not isinstance(regularize, DepthRegularizer):
+                raise ValueError('propagate: regularize must be a DepthRegularizer or None (got %r)' % (regularize,))
+            stages = regularize._asdict()
+            dist_var = self._link_sigma_squared(stages.pop('dist_sigma'), 'dist_sigma')
+            pure = ops.dense_ba_depth_propagate(*link, **link_kw, depth_next=None, var_next=None, gate=0.0)
+            out = ops.dense_ba_depth_regularize(pure.inv_depth, pure.var_inv_depth, source=pure.source, status=pure.status, dist_var=dist_var,
+                                                depth_next=depth_next, var_next=var_next, gate=gate, **stages)
         return DenseBAPrior(out.depth, torch.sqrt(out.var_inv_depth), out.inv_depth, out.var_inv_depth, out.source, out.flags, out.status)
 
     def information(self, motion, sigma_px=1.0, kernel=None, sigma_inv_depth=None):

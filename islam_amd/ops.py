@@ -390,6 +390,37 @@ def _dense_reproj_status(status, B, dev):
     return status
 
 
+def _link_variance(who, name, value, B, dev):
+    """A variance per link (process_var, dist_var) as a contiguous (B,) float64 device tensor.  A number or a host tensor is checked
+    here (finite, non-negative); a device tensor is not read back: its bad entries are marked on the device."""
+    if not torch.is_tensor(value):
+        value = torch.as_tensor(value, dtype=torch.float64)
+    if not value.is_cuda and not bool(((value >= 0) & torch.isfinite(value)).all()):
+        raise ValueError('%s: %s must be finite and non-negative (got %s)' % (who, name, value.tolist()))
+    v = value.detach().to(dev, torch.float64)
+    if v.numel() == 1:
+        v = v.reshape(1).expand(B)
+    if tuple(v.shape) != (B,):
+        raise ValueError('%s: %s must be a number or (%d,), got %s' % (who, name, B, tuple(v.shape)))
+    return v.contiguous()
+
+
+def _next_measurement(who, depth_next, var_next, gate, B, H, W, dev):
+    """The second frame's measurement as the fusion takes it: depth_next and var_next (B,H,W) contiguous float32 on dev, or both None,
+    and gate as a finite non-negative float."""
+    if (depth_next is None) != (var_next is None):
+        raise ValueError('%s: depth_next and var_next come together or not at all' % who)
+    if depth_next is not None:
+        if tuple(depth_next.shape) != (B, H, W) or tuple(var_next.shape) != (B, H, W):
+            raise ValueError('%s: depth_next and var_next must be (%d,%d,%d), got %s and %s' % (
+                who, B, H, W, tuple(depth_next.shape), tuple(var_next.shape)))
+        depth_next, var_next = _f32c(depth_next.detach().to(dev)), _f32c(var_next.detach().to(dev))
+    gate = float(gate)
+    if not (gate >= 0.0 and gate < float('inf')):
+        raise ValueError('%s: gate must be finite and non-negative (got %r)' % (who, gate))
+    return depth_next, var_next, gate
+
+
 DenseBAPropagated = collections.namedtuple('DenseBAPropagated', 'inv_depth var_inv_depth depth source flags status')
 
 
@@ -413,26 +444,8 @@ def dense_ba_depth_propagate(inv_depth, var_inv_depth, motion, intr, mask=None, 
     B, H, W = inv_depth.shape
     rho, var = (t.detach().to(dev, torch.float64).contiguous() for t in (inv_depth, var_inv_depth))
     mask, motion, intr, rgb2imu = _dense_link_args('dense_ba_depth_propagate', dev, B, H, W, mask, motion, intr, rgb2imu)
-    if not torch.is_tensor(process_var):
-        process_var = torch.as_tensor(process_var, dtype=torch.float64)
-    if not process_var.is_cuda and not bool(((process_var >= 0) & torch.isfinite(process_var)).all()):
-        raise ValueError('dense_ba_depth_propagate: process_var must be finite and non-negative (got %s)' % (process_var.tolist(),))
-    pv = process_var.detach().to(dev, torch.float64)
-    if pv.numel() == 1:
-        pv = pv.reshape(1).expand(B)
-    if tuple(pv.shape) != (B,):
-        raise ValueError('dense_ba_depth_propagate: process_var must be a number or (%d,), got %s' % (B, tuple(pv.shape)))
-    pv = pv.contiguous()
-    if (depth_next is None) != (var_next is None):
-        raise ValueError('dense_ba_depth_propagate: depth_next and var_next come together or not at all')
-    if depth_next is not None:
-        if tuple(depth_next.shape) != (B, H, W) or tuple(var_next.shape) != (B, H, W):
-            raise ValueError('dense_ba_depth_propagate: depth_next and var_next must be (%d,%d,%d), got %s and %s' % (
-                B, H, W, tuple(depth_next.shape), tuple(var_next.shape)))
-        depth_next, var_next = _f32c(depth_next.detach().to(dev)), _f32c(var_next.detach().to(dev))
-    gate = float(gate)
-    if not (gate >= 0.0 and gate < float('inf')):
-        raise ValueError('dense_ba_depth_propagate: gate must be finite and non-negative (got %r)' % (gate,))
+    pv = _link_variance('dense_ba_depth_propagate', 'process_var', process_var, B, dev)
+    depth_next, var_next, gate = _next_measurement('dense_ba_depth_propagate', depth_next, var_next, gate, B, H, W, dev)
     status = _dense_reproj_status(status, B, dev)
     require_cuda(inv_depth, var_inv_depth, depth_next, var_next)      # after the argument rules, which need no device
     e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
@@ -442,6 +455,62 @@ def dense_ba_depth_propagate(inv_depth, var_inv_depth, motion, intr, mask=None, 
     check(lib().islam_depth_propagate(ptr(rho), ptr(var), ptr(mask), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(status), ptr(pv),
                                       ptr(depth_next), ptr(var_next), gate, ptr(out.inv_depth), ptr(out.var_inv_depth), ptr(out.depth),
                                       ptr(out.source), ptr(out.flags), ptr(out.status), ptr(scratch), B, H, W, stream_ptr(dev)))
+    return out
+
+
+DenseBARegularized = collections.namedtuple('DenseBARegularized', 'inv_depth var_inv_depth depth source flags status')
+
+
+def dense_ba_depth_regularize(inv_depth, var_inv_depth, source=None, status=None, dist_var=0.0, depth_next=None, var_next=None, gate=0.0,
+                              occl_radius=1, occl_min=2, fill_radius=1, fill_min=3, fill_inflate=1.0, smooth_radius=1, reg_gate=3.0):
+    """Occlusion removal, hole filling and smoothing of a propagated inverse-depth map, then the fusion with the second frame's own
+    measurement (include/islam_hip.h, islam_depth_regularize).  inv_depth, var_inv_depth (B,H,W): what
+    dense_ba_depth_propagate returned without a measurement (a pixel whose values are not finite and > 0 is a hole); source (B,H,W)
+    int or None and status (B) int or None: that call's source map and status (a link whose status is not 0 gets the measurement
+    alone); dist_var: a non-negative number or (B,), the variance a neighbour's value gains per squared pixel of distance in the
+    smoothing (a device tensor is not read back: a negative or non-finite entry marks its link with _lib.DENSE_REPROJ_BADPRIOR on the
+    device); depth_next, var_next, gate as in dense_ba_depth_propagate.  The stages: a pixel with at least occl_min nearer neighbours
+    that are incompatible with it at reg_gate standard deviations within occl_radius, and more of them than compatible ones, is
+    removed; a hole with at least fill_min mutually compatible neighbours around its nearest one within fill_radius takes their
+    weighted mean, and fill_inflate >= 1 times the variance of one of them plus their scatter; every value becomes the weighted mean
+    of its compatible neighbours within smooth_radius and keeps its variance.  A radius is 0 (the stage is left out), 1 or 2.  Returns
+    DenseBARegularized(inv_depth, var_inv_depth (B,H,W) float64, depth (B,H,W) float32, source (B,H,W) int32: -1 at filled and removed
+    pixels, flags (B,H,W) uint8: 1 a value is present, 2 measured, 4 gated out, 8 filled, 16 removed, status (B) int32).  One launch,
+    nothing is read back."""
+    who = 'dense_ba_depth_regularize'
+    dev = inv_depth.device
+    if inv_depth.dim() != 3 or tuple(var_inv_depth.shape) != tuple(inv_depth.shape):
+        raise ValueError('%s: inv_depth and var_inv_depth must be (B,H,W), got %s and %s' % (who, tuple(inv_depth.shape), tuple(var_inv_depth.shape)))
+    B, H, W = inv_depth.shape
+    rho, var = (t.detach().to(dev, torch.float64).contiguous() for t in (inv_depth, var_inv_depth))
+    if source is not None:
+        if tuple(source.shape) != (B, H, W):
+            raise ValueError('%s: source must be (%d,%d,%d), got %s' % (who, B, H, W, tuple(source.shape)))
+        source = source.to(dev, torch.int32).contiguous()
+    dv = _link_variance(who, 'dist_var', dist_var, B, dev)
+    depth_next, var_next, gate = _next_measurement(who, depth_next, var_next, gate, B, H, W, dev)
+    radii = [int(r) for r in (occl_radius, fill_radius, smooth_radius)]
+    if any(r not in (0, 1, 2) or r != x for r, x in zip(radii, (occl_radius, fill_radius, smooth_radius))):
+        raise ValueError('%s: occl_radius, fill_radius and smooth_radius must be 0, 1 or 2 (got %r, %r, %r)' % (
+            who, occl_radius, fill_radius, smooth_radius))
+    if int(occl_min) != occl_min or int(fill_min) != fill_min or occl_min < 1 or fill_min < 1:
+        raise ValueError('%s: occl_min and fill_min must be integers >= 1 (got %r, %r)' % (who, occl_min, fill_min))
+    fill_inflate, reg_gate = float(fill_inflate), float(reg_gate)
+    if not (fill_inflate >= 1.0 and fill_inflate < float('inf')):
+        raise ValueError('%s: fill_inflate must be finite and at least 1 (got %r)' % (who, fill_inflate))
+    if not (reg_gate > 0.0 and reg_gate < float('inf')):
+        raise ValueError('%s: reg_gate must be finite and positive (got %r)' % (who, reg_gate))
+    status = _dense_reproj_status(status, B, dev)
+    require_cuda(inv_depth, var_inv_depth, depth_next, var_next)      # after the argument rules, which need no device
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    out = DenseBARegularized(e(torch.float64, B, H, W), e(torch.float64, B, H, W), e(torch.float32, B, H, W), e(torch.int32, B, H, W),
+                             e(torch.uint8, B, H, W), e(torch.int32, B))
+    nbytes = lib().islam_depth_regularize_scratch_bytes(B, H, W)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    check(lib().islam_depth_regularize(ptr(rho), ptr(var), ptr(source), ptr(status), ptr(dv), ptr(depth_next), ptr(var_next), gate, radii[0],
+                                       int(occl_min), radii[1], int(fill_min), fill_inflate, radii[2], reg_gate, ptr(out.inv_depth),
+                                       ptr(out.var_inv_depth), ptr(out.depth), ptr(out.source), ptr(out.flags), ptr(out.status),
+                                       ptr(scratch), B, H, W, stream_ptr(dev)))
     return out
 
 

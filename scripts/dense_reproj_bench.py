@@ -37,6 +37,12 @@ variance into the next frame, alone and fused with a measurement at gate 3.  The
 tensors in the same process, a pixel pass that moves about half as many bytes.
 
     python scripts/dense_reproj_bench.py --propagate [--case 448x640] [--out profiles/depth_propagate_bench.json]
+
+--regularize times the regularisation of the propagated map instead: ops.dense_ba_depth_regularize with a
+measurement at gate 3 on the pure propagation of the same state, all radii 0, 1 and 2, and the pure propagation followed by it.  The
+yardstick is ops.dense_ba_depth_propagate with the same measurement in the same process, the one call it replaces.
+
+    python scripts/dense_reproj_bench.py --regularize [--case 448x640] [--out profiles/depth_regularize_bench.json]
 """
 import json
 import os
@@ -520,8 +526,10 @@ def main_uncertainty(argv):
 PROP_PIXEL_BYTES = 91
 
 
-def run_propagate_case(H, W):
-    """--propagate: the cost of carrying a refined state into the next frame (DESIGN.md section 3.28)."""
+def propagate_scene(H, W):
+    """What --propagate and --regularize time: a refined state of the scene and its variance, the next frame's measurement, and the
+    calls on them.  Returns (var_fn: ops.dense_ba_depth_variance at the state, prop(**kw): ops.dense_ba_depth_propagate of it,
+    depth_next, var_next)."""
     import numpy as np
     import torch
     from islam_amd import ops
@@ -540,9 +548,17 @@ def run_propagate_case(H, W):
     var_next = torch.full((B, H, W), 4e-4, dtype=torch.float32, device=dev)
     pv = torch.full((B,), 1e-6, dtype=torch.float64, device=dev)          # on the device, like w: no host-to-device copy inside the timed call
     prop = lambda **kw: ops.dense_ba_depth_propagate(ref.inv_depth, var, ref.motion, intr, mask=mask, status=ref.status, rgb2imu=mount, process_var=pv, **kw)
-    fns = {'depth_var_marginal': var_fn, 'propagate': prop, 'propagate_fuse': lambda: prop(depth_next=depth_next, var_next=var_next, gate=3.0)}
+    return var_fn, prop, depth_next, var_next
 
-    def median(fn, n=30):
+
+def timed(fns, n=30):
+    """us per call of every entry of fns: 5 warm-up calls, HIP events around each of n calls, the median."""
+    import torch
+    out = {}
+    for name, fn in fns.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
         us = []
         for _ in range(n):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -552,14 +568,15 @@ def run_propagate_case(H, W):
             torch.cuda.synchronize()
             us.append(e0.elapsed_time(e1) * 1e3)
         us.sort()
-        return 0.5 * (us[n // 2 - 1] + us[n // 2])
+        out[name] = 0.5 * (us[n // 2 - 1] + us[n // 2])
+    return out
 
-    out = {}
-    for name, fn in fns.items():
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        out[name] = median(fn)
+
+def run_propagate_case(H, W):
+    """--propagate: the cost of carrying a refined state into the next frame (DESIGN.md section 3.28)."""
+    var_fn, prop, depth_next, var_next = propagate_scene(H, W)
+    fns = {'depth_var_marginal': var_fn, 'propagate': prop, 'propagate_fuse': lambda: prop(depth_next=depth_next, var_next=var_next, gate=3.0)}
+    out = timed(fns)
     p = fns['propagate_fuse']()
     out['status_ok'] = int((p.status == 0).sum())
     out['hit_fraction'] = float(((p.flags & 1) != 0).double().mean())
@@ -590,8 +607,61 @@ def main_propagate(argv):
         f.write(line + '\n')
 
 
+# the nominal bytes of one pixel in ops.dense_ba_depth_regularize with a measurement: rho and its variance (16), the source index (4),
+# depth_next and var_next (8), and the five stores (25); the halo is read again by the neighbouring tiles (a factor of up to
+# 44 x 20 / (32 x 8) = 3.4 on the first 16 bytes at radii 2, 2, 2, mostly from the L2) and is not counted
+REG_PIXEL_BYTES = 53
+
+
+def run_regularize_case(H, W):
+    """--regularize: the cost of regularising a propagated map beside the propagation that feeds it."""
+    import torch
+    from islam_amd import ops
+    var_fn, prop, depth_next, var_next = propagate_scene(H, W)
+    meas = dict(depth_next=depth_next, var_next=var_next, gate=3.0)
+    pure = prop()
+    dv = torch.full((B,), 1e-8, dtype=torch.float64, device=pure.inv_depth.device)          # on the device: no copy inside the timed call
+    reg = lambda r, **kw: ops.dense_ba_depth_regularize(pure.inv_depth, pure.var_inv_depth, source=pure.source, status=pure.status, dist_var=dv,
+                                                        occl_radius=r, fill_radius=r, smooth_radius=r, **kw)
+    out = timed({'propagate_fuse': lambda: prop(**meas), 'propagate': prop, 'regularize_r1': lambda: reg(1, **meas),
+                 'regularize_r2': lambda: reg(2, **meas), 'regularize_r0': lambda: reg(0, **meas),
+                 'propagate_then_regularize_r1': lambda: (prop(), reg(1, **meas))})
+    p, q = prop(**meas), reg(1, **meas)
+    out['status_ok'] = int((q.status == 0).sum())
+    out['hit_fraction'] = float(((p.flags & 1) != 0).double().mean())
+    out['present_fraction_r1'] = float(((q.flags & 1) != 0).double().mean())
+    out['filled_fraction_r1'] = float(((q.flags & 8) != 0).double().mean())
+    out['removed_fraction_r1'] = float(((q.flags & 16) != 0).double().mean())
+    out['r1_over_fuse'] = out['regularize_r1'] / out['propagate_fuse']
+    out['r2_over_fuse'] = out['regularize_r2'] / out['propagate_fuse']
+    out['chain_over_fuse'] = out['propagate_then_regularize_r1'] / out['propagate_fuse']
+    out['hbm_frac_r1'] = REG_PIXEL_BYTES * B * H * W / (out['regularize_r1'] * 1e-6) / 1e9 / HBM_GBS
+    return out
+
+
+def main_regularize(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_regularize_case(*hw) for case, hw in cases.items()}
+    cols = ('propagate_fuse', 'propagate', 'regularize_r0', 'regularize_r1', 'regularize_r2', 'propagate_then_regularize_r1', 'r1_over_fuse', 'r2_over_fuse',
+            'chain_over_fuse', 'hbm_frac_r1', 'status_ok', 'hit_fraction', 'present_fraction_r1', 'filled_fraction_r1', 'removed_fraction_r1')
+    print('us per call at B = %d: the median of 30; hbm_frac_r1: %d bytes per pixel over the time, of %.0f GB/s' % (B, REG_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'depth_regularize_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--regularize' in sys.argv[1:]:
+        return main_regularize(sys.argv[1:])
     if '--propagate' in sys.argv[1:]:
         return main_propagate(sys.argv[1:])
     if '--uncertainty' in sys.argv[1:]:
