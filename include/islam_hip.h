@@ -589,6 +589,56 @@ int islam_dense_ba_depth_var(const float* depth, const float* flow, const uint8_
                              const int* status_or_null, int robust_kind, double robust_delta, int mode, double* out_var,
                              int* out_status, void* scratch, int B, int H, int W, void* stream);
 
+/* The gradient of the joint refinement with the exact (Newton) Hessian and per-pixel prior weights.  The
+ * adjoint system of islam_dense_ba_ift_weights / islam_dense_ba_vjp above, with the Gauss-Newton blocks replaced by one half of the
+ * Hessian of the cost in the same per-pixel elimination; all fp64.  The state is what islam_dense_ba_refine(_map) returned: T*, rho*;
+ * (R, t) = T^-1 in the camera frame, the chart T* Exp(xi), so Q(xi, rho) = Exp(-xi_cam^)(R ray / rho + t) with xi_cam = A xi exactly.
+ * Per valid pixel, with the quantities defined above:
+ *   J_q = dr/dQ = [[a, 0, bq], [0, cq, dq]]      D_p = [-I, [Q]x] (3x6)      J_cam = J_q D_p
+ *   dR = R ray      d = -dR / rho^2      jd = J_q d
+ *   M  = c I_2 + 2 c' r r^T                      y = c r      n = J_q^T y  (3)
+ *   B  = -iz (n e_z^T + e_z n^T)                 (the Hessian in Q of y^T pi(Q); iz = 1 / Q_z)
+ *   K  = J_q^T M J_q + B                         (3x3, symmetric)
+ *   n_pp = D_p^T K D_p + C      C_rho,phi = [n]x / 2,  C_phi,rho = -[n]x / 2,  C_phi,phi = (n Q^T + Q n^T) / 2 - (n.Q) I_3,  C_rho,rho = 0
+ *   n_pd = D_p^T K d + [0 ; n x d]
+ *   n_dd = d^T K d - (2 / rho) (n.d) + w_i
+ * C comes from the second-order term xi^ xi^ / 2 of Exp(-xi^).  The Gauss-Newton blocks are these with K -> c J_q^T J_q and every term
+ * in n dropped.  w_i = prior_weight[b], or prior_weight[b] * (double)m_i under prior_scale_or_null (B,H,W) float32 with the rule
+ * above: a pixel has a usable prior iff its depth and m_i are finite and > 0.  The valid set and the Huber branch are held fixed.
+ *   S_N,cam = sum_valid ( n_pp - n_pd n_pd^T / n_dd )        u_cam = sum_valid n_pd v_d / n_dd
+ *   S_N = A^T S_N,cam A          S_N lambda_p = -( v_p - A^T u_cam )          lambda_cam = A lambda_p
+ *   valid pixel:                 lambda_d = -( v_d + n_pd^T lambda_cam ) / n_dd
+ *   invalid pixel with a prior:  lambda_d = -v_d / w_i                        no usable prior: no gradient
+ *   q = J_cam lambda_cam + jd lambda_d     e = c q + 2 c' (q.r) r
+ *   dL/dflow = -e  (valid pixels; 0 elsewhere)               dL/ddepth = w_i lambda_d / depth^2  (every pixel with a usable prior)
+ * Fallback: a valid pixel whose n_dd is not > 0 (NaN included) takes its three Gauss-Newton blocks (c J_cam^T J_cam, h_pd, h_dd)
+ * instead, in the reduction and in the streaming pass alike, and is counted per link (fallback_count (B) int32).
+ *
+ * islam_dense_ba_newton_weights: two launches, no host wait, no atomics.  The first reduces 28 sums per link (the 21 of the upper
+ * triangle of S_N,cam, the 6 of u_cam -- zeros when grad_inv_depth_or_null is NULL -- and the fallback count) as NBLK rows by plain
+ * stores into scratch (islam_dense_ba_newton_scratch_bytes(B)); a link whose incoming status is not 0 or whose prior_weight is not > 0
+ * stores zeros without reading its pixels.  The second adds the rows in fixed order and writes lambda_p (B,6), S_newton_or_null
+ * (B,6,6; body frame, symmetric to the bit; NULL: not wanted), fallback_count (B) and status_out (B): status_in_or_null's value where
+ * that is not 0, ISLAM_DENSE_REPROJ_BADPRIOR where prior_weight is not > 0, ISLAM_DENSE_REPROJ_NOTPD where S_N is not finite or its
+ * Cholesky meets a non-positive pivot, else 0; lambda_p is 0 for a link whose status_out is not 0.  S_N is the Hessian of the
+ * marginalised cost, not an information matrix: it need not be positive definite away from a minimum.
+ * islam_dense_ba_newton_vjp: grad_depth (B,H,W) and grad_flow (B,2,H,W), float32, written in full: exactly 0 where the formulas give
+ * 0 and over a whole link whose status_or_null is not 0 or whose prior_weight is not > 0.  One launch, rounded once at the store.
+ * Both return ISLAM_EARG before any device work for B, H, W < 1 (or H*W > 2^30), an unknown robust kind, robust_delta <= 0, and a
+ * NULL pointer other than mask, rgb2imu, prior_scale_or_null, grad_inv_depth_or_null, S_newton_or_null and the incoming status. */
+size_t islam_dense_ba_newton_scratch_bytes(int B);
+int islam_dense_ba_newton_weights(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                  const double* rgb2imu, const double* intr4, const double* prior_weight,
+                                  const float* prior_scale_or_null, const double* inv_depth, int robust_kind, double robust_delta,
+                                  const double* grad_motion, const double* grad_inv_depth_or_null, const int* status_in_or_null,
+                                  void* scratch, int B, int H, int W, double* lambda_p, double* S_newton_or_null,
+                                  int* fallback_count, int* status_out, void* stream);
+int islam_dense_ba_newton_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                              const double* rgb2imu, const double* intr4, const double* prior_weight,
+                              const float* prior_scale_or_null, const double* inv_depth, int robust_kind, double robust_delta,
+                              const double* lambda_p, const double* grad_inv_depth_or_null, const int* status_or_null,
+                              float* grad_depth, float* grad_flow, int B, int H, int W, void* stream);
+
 /* Depth propagation: the inverse depths rho and variances s (1/m^2, real variances: sigma_px^2 v of
  * islam_dense_ba_depth_var) of the first frame of link b carried into the pixel grid of its second frame and fused there with that
  * frame's own measurement.  All device arithmetic is fp64, every operation rounded on its own (nothing is contracted).  With (R, t) =

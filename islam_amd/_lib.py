@@ -126,6 +126,9 @@ SIGNATURES = {
     'islam_dense_ba_normal_map': (c_int, [c_void_p] * 9 + [c_int, c_double] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
     'islam_dense_ba_refine_map': (c_int, [c_void_p] * 8 + [c_int, c_double, c_int, c_double, c_double] + [c_void_p] * 13 +
                                   [c_int, c_void_p] + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_newton_scratch_bytes': (c_size_t, [c_int]),
+    'islam_dense_ba_newton_weights': (c_int, [c_void_p] * 9 + [c_int, c_double] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 5),
+    'islam_dense_ba_newton_vjp': (c_int, [c_void_p] * 9 + [c_int, c_double] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'islam_dense_ba_depth_var_scratch_bytes': (c_size_t, [c_int]),
     'islam_dense_ba_depth_var': (c_int, [c_void_p] * 11 + [c_int, c_double, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     'islam_depth_propagate_scratch_bytes': (c_size_t, [c_int] * 3),

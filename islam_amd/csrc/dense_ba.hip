@@ -15,7 +15,9 @@
 // code that forms sums, so islam_dense_ba_normal at the returned state runs the same instructions on the same bits.
 // Further down: the gradient of the joint refinement in depth and flow (joint_adj_partial_kernel, joint_adj_solve_kernel,
 // joint_adj_vjp_kernel), and per-pixel prior weights with the posterior variance of the inverse depths
-// (ba_wmap_partial_kernel beside the partial kernel; depth_var_factor_kernel, depth_var_pixel_kernel at the end; section 3.27).
+// (ba_wmap_partial_kernel beside the partial kernel; depth_var_factor_kernel, depth_var_pixel_kernel; section 3.27).  At the end: the
+// same gradient with the exact (Newton) Hessian and per-pixel prior weights (ba_newton_partial_kernel, ba_newton_solve_kernel,
+// ba_newton_vjp_kernel; section 3.30).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -661,6 +663,321 @@ extern "C" int islam_dense_ba_depth_var(const float* depth, const float* flow, c
     hipLaunchKernelGGL(depth_var_factor_kernel, dim3(B), dim3(64), 0, s, sums, prior_weight, status_or_null, marginal, sinv, out_status);
     hipLaunchKernelGGL(depth_var_pixel_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4, prior_weight,
                        prior_scale_or_null, inv_depth_or_null, sinv, out_status, out_var, H, W, robust_kind, robust_delta, marginal);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// ------------------------------------------------------------------ the gradient of the joint refinement with the exact Hessian
+// (the formulas: include/islam_hip.h, islam_dense_ba_newton_weights.)  Section 3.26's adjoint system with
+// the Gauss-Newton blocks c J_cam^T J_cam, h_pd, h_dd replaced by one half of the Hessian of the cost, in the same per-pixel
+// elimination.  With J_q = dr/dQ, D_p = [-I, [Q]x], d = dQ/drho = -R ray / rho^2, M = c I + 2 c' r r^T, n = J_q^T c r and
+// K = J_q^T M J_q - (n e_z^T + e_z n^T) / Q_z:
+//   n_pp = D_p^T K D_p + C,   n_pd = D_p^T K d + [0; n x d],   n_dd = d^T K d - (2 / rho) n.d + w_i,
+// C the second-order term of Exp: C_rho,phi = [n]x / 2, C_phi,phi = (n Q^T + Q n^T) / 2 - (n.Q) I.  A valid pixel whose n_dd is not
+// > 0 takes its three Gauss-Newton blocks (K -> c J_q^T J_q, n -> 0) and is counted.  ba_newton_partial_kernel reduces the 21 sums of
+// S_N,cam = sum n_pp - n_pd n_pd^T / n_dd, the 6 of u_cam = sum n_pd v_d / n_dd and the count (one row of 28 per workgroup, plain
+// stores), ba_newton_solve_kernel makes S_N = A^T S_N,cam A and lambda_p, ba_newton_vjp_kernel streams section 3.26's data gradient out
+// with lambda_d from the exact n_pd, n_dd.  MAP: the pixel's prior weight is w_b m_i (map_prior), as in section 3.27.
+namespace {
+
+constexpr int NN = 28, N_U = 21, N_FB = 27;      // the row of the reduction: 21 of S_N,cam, 6 of u_cam, the fallback count
+
+// the pose-depth column and the depth-depth entry of one valid pixel, with what the pose-pose block is formed from: K (xx, xy, xz, yy,
+// yz, zz), n, and K d
+struct NewtonPixel {
+    double K[6];
+    V3<double> n, Kd, d;
+    double npd[6], ndd;
+    bool fallback;
+};
+
+// K and n from the 2x2 M = [[m00, m01], [m01, m11]] and y = c r; then d-dependent terms.  exact = false: the Gauss-Newton blocks
+ISLAM_DEV void newton_terms(const Pixel& p, const V3<double>& d, double zi, double w, bool exact, NewtonPixel& o) {
+    const double c = p.c, ru = p.ru, rv = p.rv;
+    const double k2 = exact ? 2.0 * p.cp : 0.0;
+    const double m00 = c + k2 * ru * ru, m01 = k2 * ru * rv, m11 = c + k2 * rv * rv;
+    const double a = p.a, bq = p.bq, cq = p.cq, dq = p.dq;
+    // n = J_q^T y
+    const double yu = exact ? c * ru : 0.0, yv = exact ? c * rv : 0.0;
+    o.n = {a * yu, cq * yv, bq * yu + dq * yv};
+    // J_q^T M J_q with J_q = [[a, 0, bq], [0, cq, dq]], and B = -iz (n e_z^T + e_z n^T)
+    const double tu = m00 * bq + m01 * dq, tv = m01 * bq + m11 * dq;      // M (bq, dq)
+    o.K[0] = a * a * m00;
+    o.K[1] = a * cq * m01;
+    o.K[2] = a * tu - p.iz * o.n.x;
+    o.K[3] = cq * cq * m11;
+    o.K[4] = cq * tv - p.iz * o.n.y;
+    o.K[5] = bq * tu + dq * tv - 2.0 * p.iz * o.n.z;
+    o.Kd = {o.K[0] * d.x + o.K[1] * d.y + o.K[2] * d.z, o.K[1] * d.x + o.K[3] * d.y + o.K[4] * d.z, o.K[2] * d.x + o.K[4] * d.y + o.K[5] * d.z};
+    o.ndd = dot(d, o.Kd) - 2.0 * zi * dot(o.n, d) + w;
+}
+
+// everything of one VALID pixel; p the front at 1 / rho, dR = R ray
+ISLAM_DEV NewtonPixel newton_pixel(const Pixel& p, const V3<double>& dR, double rho, double w) {
+    NewtonPixel o;
+    const double zi = 1.0 / rho;
+    const double k = -(zi * zi);
+    o.d = {dR.x * k, dR.y * k, dR.z * k};
+    newton_terms(p, o.d, zi, w, true, o);
+    o.fallback = !(o.ndd > 0.0);
+    if (o.fallback) newton_terms(p, o.d, zi, w, false, o);
+    // n_pd = D_p^T K d + [0; n x d] = [-K d; K d x Q + n x d]
+    const V3<double> f = cross(o.Kd, p.Q) + cross(o.n, o.d);
+    o.npd[0] = -o.Kd.x; o.npd[1] = -o.Kd.y; o.npd[2] = -o.Kd.z;
+    o.npd[3] = f.x; o.npd[4] = f.y; o.npd[5] = f.z;
+    return o;
+}
+
+template <bool MAP>
+__global__ __launch_bounds__(256) void ba_newton_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                                 const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                                 const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                                 const double* __restrict__ prior_weight,
+                                                                 const float* __restrict__ prior_scale, const double* __restrict__ inv_depth,
+                                                                 const double* __restrict__ grad_rho, const int* __restrict__ status,
+                                                                 double* __restrict__ partial, int H, int W, int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const double wb = prior_weight[b];
+    // a marked link (or one without a usable prior weight) stores rows of zeros without reading its pixels
+    const bool live = wb > 0.0 && !(status && status[b] != ISLAM_DENSE_REPROJ_OK);
+    double acc[NN] = {};
+    if (live) {
+        __shared__ double Tp[12];
+        if (threadIdx.x == 0) pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+        __syncthreads();
+        const M3<double> R = m3_load(Tp);
+        const V3<double> t{Tp[9], Tp[10], Tp[11]};
+        const size_t off = (size_t)b * HW;
+        const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
+        const float* ms = MAP ? prior_scale + off : nullptr;
+        const double* rp = inv_depth + off;
+        const double* vp = grad_rho ? grad_rho + off : nullptr;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+            const PixelIn px = pixel_in(lp, i);
+            bool prior = isfinite(px.z) && px.z > 0.0;
+            double w = wb;
+            if constexpr (MAP) prior = map_prior(ms, i, wb, prior, w);
+            const double rho = rp[i];
+            if (!(prior && isfinite(rho) && rho > 0.0)) continue;
+            const Pixel p = reproj_pixel(R, t, 1.0 / rho, px, lp);
+            if (!p.valid) continue;
+            const NewtonPixel o = newton_pixel(p, R * V3<double>{px.xh, px.yh, 1.0}, rho, w);
+            const double ih = 1.0 / o.ndd;
+            // the columns of D_p = [-I, [Q]x]: -e_x, -e_y, -e_z, Q x e_x, Q x e_y, Q x e_z, and K times each
+            const V3<double> Q = p.Q;
+            const V3<double> col[6] = {{-1.0, 0.0, 0.0}, {0.0, -1.0, 0.0}, {0.0, 0.0, -1.0}, {0.0, Q.z, -Q.y}, {-Q.z, 0.0, Q.x}, {Q.y, -Q.x, 0.0}};
+            const double* K = o.K;
+            V3<double> Kc[6];
+#pragma unroll
+            for (int l = 0; l < 6; ++l)
+                Kc[l] = {K[0] * col[l].x + K[1] * col[l].y + K[2] * col[l].z, K[1] * col[l].x + K[3] * col[l].y + K[4] * col[l].z,
+                         K[2] * col[l].x + K[4] * col[l].y + K[5] * col[l].z};
+            // C: the second-order term of Exp.  rho-phi block [n]x / 2, phi-phi block (n Q^T + Q n^T) / 2 - (n.Q) I
+            const V3<double> n = o.n;
+            const double nq = dot(n, Q);
+            const double hx = 0.5 * n.x, hy = 0.5 * n.y, hz = 0.5 * n.z;
+            double C[21] = {};
+            C[tri(0, 4)] = -hz; C[tri(0, 5)] = hy; C[tri(1, 3)] = hz; C[tri(1, 5)] = -hx; C[tri(2, 3)] = -hy; C[tri(2, 4)] = hx;
+            C[tri(3, 3)] = n.x * Q.x - nq; C[tri(4, 4)] = n.y * Q.y - nq; C[tri(5, 5)] = n.z * Q.z - nq;
+            C[tri(3, 4)] = hx * Q.y + hy * Q.x; C[tri(3, 5)] = hx * Q.z + hz * Q.x; C[tri(4, 5)] = hy * Q.z + hz * Q.y;
+            int k = 0;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const double fq = o.npd[q] * ih;
+#pragma unroll
+                for (int l = q; l < 6; ++l, ++k) acc[k] += (dot(col[q], Kc[l]) + C[k]) - fq * o.npd[l];
+            }
+            if (vp) {
+                const double kv = vp[i] * ih;      // v_d / n_dd
+#pragma unroll
+                for (int l = 0; l < 6; ++l) acc[N_U + l] += o.npd[l] * kv;
+            }
+            acc[N_FB] += o.fallback ? 1.0 : 0.0;
+        }
+    }
+    reduce_and_store_row<NN>(acc, partial + ((size_t)b * NBLK + blockIdx.x) * NN, live, 0.0);
+}
+
+// S_N and lambda_p per link, one 64-lane workgroup: the NBLK rows in fixed order, S_N = A^T S_N,cam A as the final kernel forms its H
+// ((r, c) and (c, r) run the same operations: symmetric to the bit), v_p from the gradient on [t, q xyzw] (tangent_gradient), A^T u_cam
+// by adjoint_apply<true>.  A link that comes with a status, whose prior weight is not > 0 (BADPRIOR), or whose S_N is not finite or
+// has a non-positive pivot (NOTPD) gets lambda_p = 0 (adjoint_solve_tail).
+__global__ __launch_bounds__(64) void ba_newton_solve_kernel(const double* __restrict__ partial, const double* __restrict__ motion,
+                                                              const double* __restrict__ grad_motion, const double* __restrict__ rgb2imu,
+                                                              const double* __restrict__ prior_weight, const int* __restrict__ status_in,
+                                                              double* __restrict__ lambda_p, double* __restrict__ S_out,
+                                                              int* __restrict__ fallback_count, int* __restrict__ status_out) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    __shared__ double s[NN], Rm[9], Sm[9], A[36], Hn[36], vn[6], L[6][6], x[6];
+    __shared__ int bad;
+    if (i < NN) {
+        double v = 0.0;
+        for (int k = 0; k < NBLK; ++k) v += partial[((size_t)b * NBLK + k) * NN + i];
+        s[i] = v;
+    }
+    if (i == 0) {      // C^-1 = (R, t)
+        bad = 0;
+        M3<double> Rc = m3_identity<double>(), Sc{0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (rgb2imu) {
+            const SE3<double> Ci = se3_inv(se3_load(rgb2imu));
+            Rc = qmat(Ci.q);
+            Sc = skew(Ci.t) * Rc;
+        }
+        m3_store(Rc, Rm);
+        m3_store(Sc, Sm);
+    }
+    __syncthreads();
+    if (i < 36) {      // A = Ad(C^-1) = [[R, [t]x R], [0, R]]
+        const int r = i / 6, c = i - 6 * r;
+        A[i] = r < 3 ? (c < 3 ? Rm[3 * r + c] : Sm[3 * r + c - 3]) : (c < 3 ? 0.0 : Rm[3 * (r - 3) + c - 3]);
+    }
+    __syncthreads();
+    if (i < 36) {
+        const int r0 = i / 6, c0 = i - 6 * r0;
+        const int r = min(r0, c0), c = max(r0, c0);
+        double v = 0.0;
+        for (int k = 0; k < 6; ++k) {
+            double w = 0.0;
+            for (int l = 0; l < 6; ++l) w += s[tri(min(k, l), max(k, l))] * A[l * 6 + c];
+            v += A[k * 6 + r] * w;
+        }
+        Hn[i] = v;
+        if (!isfinite(v)) bad = 1;
+        if (S_out) S_out[(size_t)b * 36 + i] = v;
+    }
+    if (i == 0) {
+        fallback_count[b] = (int)s[N_FB];
+        V3<double> vr, vf;
+        tangent_gradient(motion + (size_t)b * 7, grad_motion + (size_t)b * 7, vr, vf);
+        V3<double> ur{s[N_U], s[N_U + 1], s[N_U + 2]}, uf{s[N_U + 3], s[N_U + 4], s[N_U + 5]};
+        adjoint_apply<true>(rgb2imu, ur, uf);      // A^T u_cam
+        vr = vr - ur;
+        vf = vf - uf;
+        vn[0] = vr.x; vn[1] = vr.y; vn[2] = vr.z; vn[3] = vf.x; vn[4] = vf.y; vn[5] = vf.z;
+    }
+    __syncthreads();
+    int st = status_in ? status_in[b] : ISLAM_DENSE_REPROJ_OK;
+    if (st == ISLAM_DENSE_REPROJ_OK && !(prior_weight[b] > 0.0)) st = ISLAM_DENSE_REPROJ_BADPRIOR;
+    if (st == ISLAM_DENSE_REPROJ_OK && bad) st = ISLAM_DENSE_REPROJ_NOTPD;
+    adjoint_solve_tail(st, Hn, vn, L, x, status_out + b, lambda_p + (size_t)b * 6);
+}
+
+template <bool MAP>
+__global__ __launch_bounds__(256) void ba_newton_vjp_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                             const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                             const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                             const double* __restrict__ prior_weight, const float* __restrict__ prior_scale,
+                                                             const double* __restrict__ inv_depth, const double* __restrict__ lambda_p,
+                                                             const double* __restrict__ grad_rho, const int* __restrict__ status,
+                                                             float* __restrict__ grad_depth, float* __restrict__ grad_flow, int H, int W,
+                                                             int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const size_t off = (size_t)b * HW;
+    const LinkGrads out = link_grads(grad_depth, grad_flow, b, HW);
+    const double wb = prior_weight[b];
+    if (!(wb > 0.0) || (status && status[b] != ISLAM_DENSE_REPROJ_OK)) return grad_zero_link(out, HW);      // a link without a gradient
+    __shared__ double Tp[12], lcam[6];
+    if (threadIdx.x == 0) {
+        pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+        adjoint_to_camera(rgb2imu, lambda_p + 6 * b, lcam);      // lambda_cam = Ad(C^-1) lambda_p
+    }
+    __syncthreads();
+    const M3<double> R = m3_load(Tp);
+    const V3<double> t{Tp[9], Tp[10], Tp[11]};
+    const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
+    const float* ms = MAP ? prior_scale + off : nullptr;
+    const double* rp = inv_depth + off;
+    const double* vp = grad_rho ? grad_rho + off : nullptr;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        const PixelIn px = pixel_in(lp, i);
+        const double z = px.z;
+        bool prior = isfinite(z) && z > 0.0;
+        double w = wb;
+        if constexpr (MAP) prior = map_prior(ms, i, wb, prior, w);
+        double gz = 0.0, gu = 0.0, gv = 0.0;
+        if (prior) {
+            const double rho = rp[i];
+            const double vdi = vp ? vp[i] : 0.0;
+            double ld = -vdi / w;          // an invalid pixel follows its prior
+            if (isfinite(rho) && rho > 0.0) {
+                const Pixel p = reproj_pixel(R, t, 1.0 / rho, px, lp);
+                if (p.valid) {
+                    const NewtonPixel o = newton_pixel(p, R * V3<double>{px.xh, px.yh, 1.0}, rho, w);
+                    const double c = p.c, ru = p.ru, rv = p.rv;
+                    double du = 0.0, dv = 0.0, nl = 0.0;      // J_cam lambda_cam, n_pd . lambda_cam
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) {
+                        du += p.ju[q] * lcam[q];
+                        dv += p.jv[q] * lcam[q];
+                        nl += o.npd[q] * lcam[q];
+                    }
+                    ld = -(vdi + nl) / o.ndd;
+                    // jd = J_q d
+                    const double jdu = p.a * o.d.x + p.bq * o.d.z, jdv = p.cq * o.d.y + p.dq * o.d.z;
+                    const double qu = du + jdu * ld, qv = dv + jdv * ld;
+                    const double k2 = 2.0 * p.cp * (qu * ru + qv * rv);
+                    gu = -(c * qu + k2 * ru);
+                    gv = -(c * qv + k2 * rv);
+                }
+            }
+            gz = w * ld / (z * z);
+        }
+        grad_store(out, i, gz, gu, gv);
+    }
+}
+
+}  // namespace
+
+extern "C" size_t islam_dense_ba_newton_scratch_bytes(int B) {
+    if (B < 1) return 0;
+    return align_up((size_t)B * NBLK * NN * sizeof(double));
+}
+
+extern "C" int islam_dense_ba_newton_weights(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                             const double* rgb2imu, const double* intr4, const double* prior_weight,
+                                             const float* prior_scale_or_null, const double* inv_depth, int robust_kind, double robust_delta,
+                                             const double* grad_motion, const double* grad_inv_depth_or_null, const int* status_in_or_null,
+                                             void* scratch, int B, int H, int W, double* lambda_p, double* S_newton_or_null,
+                                             int* fallback_count, int* status_out, void* stream) {
+    const char* who = "islam_dense_ba_newton_weights";
+    if (int rc = check_joint_adjoint(who, depth, flow, motion, intr4, prior_weight, inv_depth, lambda_p, robust_kind, robust_delta, B, H, W))
+        return rc;
+    if (!grad_motion || !fallback_count || !status_out || !scratch)
+        return fail(ISLAM_EARG, "%s: NULL grad_motion / fallback_count / status_out / scratch pointer", who);
+    hipStream_t s = as_stream(stream);
+    double* partial = static_cast<double*>(scratch);
+    if (prior_scale_or_null)
+        hipLaunchKernelGGL(ba_newton_partial_kernel<true>, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4,
+                           prior_weight, prior_scale_or_null, inv_depth, grad_inv_depth_or_null, status_in_or_null, partial, H, W, robust_kind,
+                           robust_delta);
+    else
+        hipLaunchKernelGGL(ba_newton_partial_kernel<false>, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4,
+                           prior_weight, nullptr, inv_depth, grad_inv_depth_or_null, status_in_or_null, partial, H, W, robust_kind, robust_delta);
+    hipLaunchKernelGGL(ba_newton_solve_kernel, dim3(B), dim3(64), 0, s, partial, motion, grad_motion, rgb2imu, prior_weight, status_in_or_null,
+                       lambda_p, S_newton_or_null, fallback_count, status_out);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+extern "C" int islam_dense_ba_newton_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                         const double* rgb2imu, const double* intr4, const double* prior_weight,
+                                         const float* prior_scale_or_null, const double* inv_depth, int robust_kind, double robust_delta,
+                                         const double* lambda_p, const double* grad_inv_depth_or_null, const int* status_or_null,
+                                         float* grad_depth, float* grad_flow, int B, int H, int W, void* stream) {
+    const char* who = "islam_dense_ba_newton_vjp";
+    if (int rc = check_joint_adjoint(who, depth, flow, motion, intr4, prior_weight, inv_depth, lambda_p, robust_kind, robust_delta, B, H, W))
+        return rc;
+    if (!grad_depth || !grad_flow) return fail(ISLAM_EARG, "%s: NULL grad_depth / grad_flow pointer", who);
+    if (prior_scale_or_null)
+        hipLaunchKernelGGL(ba_newton_vjp_kernel<true>, dim3(NBLK, B), dim3(256), 0, as_stream(stream), depth, flow, mask, motion, rgb2imu, intr4,
+                           prior_weight, prior_scale_or_null, inv_depth, lambda_p, grad_inv_depth_or_null, status_or_null, grad_depth, grad_flow,
+                           H, W, robust_kind, robust_delta);
+    else
+        hipLaunchKernelGGL(ba_newton_vjp_kernel<false>, dim3(NBLK, B), dim3(256), 0, as_stream(stream), depth, flow, mask, motion, rgb2imu, intr4,
+                           prior_weight, nullptr, inv_depth, lambda_p, grad_inv_depth_or_null, status_or_null, grad_depth, grad_flow, H, W,
+                           robust_kind, robust_delta);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

@@ -258,7 +258,7 @@ class DenseReprojectionLoss:
         return (sigma_px / sig) ** 2, None
 
     def refine_joint(self, motion, sigma_inv_depth, sigma_px=1.0, iters=20, kernel=None, damping=1e-4, min_count=16, trace_cap=0,
-                     differentiable=False):
+                     differentiable=False, hessian='gauss_newton'):
         """Joint two-view bundle adjustment of each link: ``iters`` device-side Levenberg-Marquardt evaluations on the pose AND one
         inverse depth per pixel, the stored depth as a Gaussian prior of standard deviation ``sigma_inv_depth`` (1/m; a positive number,
         a (B,) tensor, or a (B,H,W) map with one value per pixel, where an entry that is not finite or not positive means "no prior at
@@ -273,18 +273,34 @@ class DenseReprojectionLoss:
         networks.  The gradient is the implicit-function one of the joint problem at the returned state, not an unrolled LM: the
         adjoint system H_full lambda = -v is solved by the forward pass's per-pixel elimination against the undamped S returned
         here, and the gradient is d(lambda^T G)/d(depth, flow) (ops.dense_ba_ift_weights and ops.dense_ba_vjp, two or three launches,
-        nothing read back).  The input depth enters only through the prior, so that derivative is exact; H_full
-        is the Gauss-Newton matrix: exact where the residual vanishes and rho = rho0, off by terms proportional to the residuals
-        elsewhere (with a noisy prior the residuals at the optimum are not zero: section 3.26 measures the error), and the formula
-        assumes convergence in pose and depths.  The start ``motion`` gets no gradient (the optimum does not depend on it), nor does
-        the prior weight (``sigma_inv_depth``, ``sigma_px``: out of scope); a link whose status is set, or whose S is not positive
-        definite, gets a zero gradient.  The gradient kernels take no per-pixel map: differentiable=True with a (B,H,W)
-        ``sigma_inv_depth`` raises NotImplementedError."""
+        nothing read back).  The input depth enters only through the prior, so that derivative is exact, and the
+        formula assumes convergence in pose and depths.  The start ``motion`` gets no gradient (the optimum does not depend on it), nor
+        does the prior weight (``sigma_inv_depth``, ``sigma_px``: out of scope); a link whose status is set, or whose matrix is not
+        positive definite, gets a zero gradient.
+
+        hessian: which matrix the adjoint system is solved with (it changes the backward pass only; the forward pass, S and the LM stay
+        Gauss-Newton).  'gauss_newton' (the default): H_full is the Gauss-Newton matrix, exact where the residual vanishes and
+        rho = rho0, off by terms proportional to the residuals elsewhere -- with a noisy prior the residuals at the optimum are not zero,
+        and the gradient is off by 2 - 19 % on the planted scenes (section 3.26); its kernels take no per-pixel map, and
+        differentiable=True with a (B,H,W) ``sigma_inv_depth`` raises NotImplementedError.  'exact' (needs differentiable=True): one half
+        of the Hessian of the cost, second-order terms of the projection, the robust kernel and the pose chart included
+        (ops.dense_ba_newton_weights and ops.dense_ba_newton_vjp, three launches; section 3.30); it agrees with re-refinement to 1e-6
+        on those scenes and accepts a number, a (B,) tensor and a (B,H,W) map.  Any other string is a ValueError."""
         from . import ops
+        if hessian not in ('gauss_newton', 'exact'):
+            raise ValueError("refine_joint: hessian must be 'gauss_newton' or 'exact' (got %r)" % (hessian,))
+        if hessian == 'exact' and not differentiable:
+            raise ValueError("refine_joint: hessian='exact' selects the backward pass and needs differentiable=True")
         w, m = self._prior_weight(sigma_inv_depth, sigma_px, 'refine_joint')
-        if differentiable and m is not None:
-            raise NotImplementedError('refine_joint: differentiable=True is not implemented for a per-pixel (B,H,W) sigma_inv_depth map')
-        if differentiable:
+        if differentiable and m is not None and hessian != 'exact':
+            raise NotImplementedError("refine_joint: differentiable=True with the Gauss-Newton adjoint is not implemented for a per-pixel (B,H,W) "
+                                      "sigma_inv_depth map; pass hessian='exact'")
+        if differentiable and hessian == 'exact':
+            mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
+            out = ops.DenseBARefined(*ops._DenseBARefineNewton.apply(
+                self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w, m, mount, kernel, iters,
+                damping, min_count, trace_cap))
+        elif differentiable:
             mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
             out = ops.DenseBARefined(*ops._DenseBARefine.apply(
                 self.z, self.flow, self.mask, self._motion7(motion), torch.tensor(self.K4, dtype=torch.float64), w, mount, kernel, iters,

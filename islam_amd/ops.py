@@ -678,6 +678,107 @@ class _DenseBARefine(torch.autograd.Function):
                 grad_flow.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None) + none[2:]
 
 
+DenseBANewton = collections.namedtuple('DenseBANewton', 'lambda_p S fallback status')
+
+
+def _dense_ba_newton_state(who, depth, flow, mask, motion, intr, prior_weight, inv_depth, grad_inv_depth, rgb2imu, kernel, prior_scale):
+    """What both Newton ops prepare alike: (_DenseArgs, w (B,), m (B,H,W) float32 or None, rho, grad_inv_depth or None)."""
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+    m = _dense_ba_prior_scale(prior_scale, a, who)
+    rho = _dense_ba_state(inv_depth, a, who)
+    if grad_inv_depth is not None:
+        grad_inv_depth = _dense_ba_state(grad_inv_depth, a, who, 'grad_inv_depth')
+    return a, w, m, rho, grad_inv_depth
+
+
+def dense_ba_newton_weights(depth, flow, mask, motion, intr, prior_weight, inv_depth, grad_motion, grad_inv_depth=None, rgb2imu=None,
+                            kernel=None, status=None, prior_scale=None):
+    """lambda_p (B,6) of the joint refinement's implicit gradient with the exact (Newton) Hessian (include/islam_hip.h,
+    islam_dense_ba_newton_weights): S_N lambda_p = -(v_p - A^T u_cam) at the state (motion (B,7), inv_depth
+    (B,H,W)) a dense_ba_refine returned, S_N the pose block of one half of the cost's Hessian with the depths eliminated pixel by
+    pixel, for a loss with gradient grad_motion (B,7) on [t, q xyzw] and grad_inv_depth (B,H,W) or None on inv_depth.  prior_scale
+    (B,H,W) or None: the per-pixel factor on the prior weight the refinement was given; other arguments as dense_ba_ift_weights.
+    Returns DenseBANewton(lambda_p (B,6), S (B,6,6) = S_N, body frame, float64; fallback (B) int32: the valid pixels whose exact n_dd
+    was not > 0 and that took their Gauss-Newton blocks; status (B) int32: the incoming status, _lib.DENSE_REPROJ_BADPRIOR for a prior
+    weight that is not > 0, _NOTPD for an S_N that is not positive definite; lambda_p = 0 for such a link).  Two launches, nothing is
+    read back."""
+    a, w, m, rho, grad_inv_depth = _dense_ba_newton_state('dense_ba_newton_weights', depth, flow, mask, motion, intr, prior_weight, inv_depth,
+                                                          grad_inv_depth, rgb2imu, kernel, prior_scale)
+    grad_motion = torch.as_tensor(grad_motion).detach().to(a.dev, torch.float64).contiguous()
+    if tuple(grad_motion.shape) != (a.B, 7):
+        raise ValueError('dense_ba_newton_weights: grad_motion must be (%d,7), got %s' % (a.B, tuple(grad_motion.shape)))
+    return _dense_ba_newton_launch(a, w, m, rho, grad_motion, grad_inv_depth, _dense_reproj_status(status, a.B, a.dev))
+
+
+def _dense_ba_newton_launch(a, w, m, rho, grad_motion, grad_rho, status):
+    """islam_dense_ba_newton_weights on what _dense_ba_newton_state prepared."""
+    lam, out = _dense_ift_outputs(a.B, a.dev)
+    S = torch.empty((a.B, 6, 6), dtype=torch.float64, device=a.dev)
+    fallback = torch.empty(a.B, dtype=torch.int32, device=a.dev)
+    scratch = torch.empty(lib().islam_dense_ba_newton_scratch_bytes(a.B), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_ba_newton_weights(*a.head(), ptr(w), ptr(m), ptr(rho), a.kind, a.delta, ptr(grad_motion), ptr(grad_rho), ptr(status),
+                                              ptr(scratch), a.B, a.H, a.W, ptr(lam), ptr(S), ptr(fallback), ptr(out), stream_ptr(a.dev)))
+    return DenseBANewton(lam, S, fallback, out)
+
+
+def dense_ba_newton_vjp(depth, flow, mask, motion, intr, prior_weight, inv_depth, lambda_p, grad_inv_depth=None, rgb2imu=None, kernel=None,
+                        status=None, prior_scale=None):
+    """The gradient of a loss on a joint refinement's outputs in depth and flow with the exact Hessian, from lambda_p (B,6)
+    (dense_ba_newton_weights) and the loss's gradient grad_inv_depth (B,H,W) or None on inv_depth (include/islam_hip.h,
+    islam_dense_ba_newton_vjp): dense_ba_vjp's data gradient with lambda_d from the exact n_pd and n_dd, and
+    w_i = prior_weight prior_scale_i under a map.  Returns (grad_depth (B,H,W), grad_flow (B,2,H,W)), float32 on the device; one
+    launch, nothing is read back."""
+    a, w, m, rho, grad_inv_depth = _dense_ba_newton_state('dense_ba_newton_vjp', depth, flow, mask, motion, intr, prior_weight, inv_depth,
+                                                          grad_inv_depth, rgb2imu, kernel, prior_scale)
+    lambda_p = torch.as_tensor(lambda_p).detach().to(a.dev, torch.float64).contiguous()
+    if tuple(lambda_p.shape) != (a.B, 6):
+        raise ValueError('dense_ba_newton_vjp: lambda_p must be (%d,6) [rho, phi], got %s' % (a.B, tuple(lambda_p.shape)))
+    return _dense_ba_newton_vjp_launch(a, w, m, rho, lambda_p, grad_inv_depth, _dense_reproj_status(status, a.B, a.dev))
+
+
+def _dense_ba_newton_vjp_launch(a, w, m, rho, lambda_p, grad_rho, status):
+    """islam_dense_ba_newton_vjp on what _dense_ba_newton_state prepared."""
+    grad_depth, grad_flow = _dense_grad_outputs(a)
+    check(lib().islam_dense_ba_newton_vjp(*a.head(), ptr(w), ptr(m), ptr(rho), a.kind, a.delta, ptr(lambda_p), ptr(grad_rho), ptr(status),
+                                          ptr(grad_depth), ptr(grad_flow), a.B, a.H, a.W, stream_ptr(a.dev)))
+    return grad_depth, grad_flow
+
+
+class _DenseBARefineNewton(torch.autograd.Function):
+    """dense_ba_refine (with prior_scale when given) whose refined motion and inv_depth carry the implicit-function gradient in depth and
+    flow with the exact Hessian: backward is islam_dense_ba_newton_weights (two launches) and
+    islam_dense_ba_newton_vjp at the refined state on the tensors forward prepared, and nothing else.  The start pose, the prior weight
+    and the prior scale get no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth, flow, mask, motion, intr, prior_weight, prior_scale, rgb2imu, kernel, iters, damping, min_count, trace_cap):
+        a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+        w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+        m = _dense_ba_prior_scale(prior_scale, a, 'dense_ba_refine')
+        out = _dense_ba_refine_launch(a, w, iters, damping, min_count, trace_cap, m)
+        ctx.save_for_backward(a.depth, a.flow, a.mask, out.motion, out.inv_depth, out.status, a.intr, a.rgb2imu, w, m)
+        ctx.kind, ctx.delta, ctx.dtypes = a.kind, a.delta, (depth.dtype, flow.dtype)
+        ctx.mark_non_differentiable(*(t for t in out[2:] if t is not None))
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None: no sums of u_cam for it
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_motion, grad_inv_depth, *unused):
+        none = (None,) * 13
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return none
+        depth, flow, mask, motion, rho, status, intr, rgb2imu, w, m = ctx.saved_tensors
+        a = _DenseArgs(depth.device, *depth.shape, depth, flow, mask, motion, intr, rgb2imu, ctx.kind, ctx.delta)      # at the refined state
+        grad_motion = torch.zeros_like(motion) if grad_motion is None else grad_motion.to(torch.float64).contiguous()
+        if grad_inv_depth is not None:
+            grad_inv_depth = grad_inv_depth.to(torch.float64).contiguous()
+        nw = _dense_ba_newton_launch(a, w, m, rho, grad_motion, grad_inv_depth, status)
+        grad_depth, grad_flow = _dense_ba_newton_vjp_launch(a, w, m, rho, nw.lambda_p, grad_inv_depth, nw.status)
+        return (grad_depth.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
+                grad_flow.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None) + none[2:]
+
+
 # --------------------------------------------------------------------------- 3x3 convolution on the matrix cores
 def deconv_to2(x, weight, bias, out=None, coff=0):
     """nn.ConvTranspose2d(C, 2, 4, 2, 1)(x) for fp32 NCHW tensors on islam_deconv4x4s2_to2_f32 (PWC-Net's deconv / upfeat layers), written

@@ -25,6 +25,13 @@ autograd, and what the gradient costs without the kernels: eager float64 torch a
 
     python scripts/dense_reproj_bench.py --joint-grad [--case 448x640] [--out profiles/dense_ba_grad_bench.json]
 
+--joint-grad-exact times the same backward with the exact (Newton) Hessian instead: ops.dense_ba_newton_weights and
+ops.dense_ba_newton_vjp alone, the exact backward (both) with and without a gradient on inv_depth and with a weight map, and a
+20-evaluation refine_joint(differentiable=True, hessian='exact') with its backward through autograd.  The yardstick is the Gauss-Newton
+backward of --joint-grad and its refine_joint(differentiable=True), timed in the same process on the same tensors.
+
+    python scripts/dense_reproj_bench.py --joint-grad-exact [--case 448x640] [--out profiles/dense_ba_newton_bench.json]
+
 --uncertainty times the per-pixel prior weights and the posterior depth variance instead: a 20-evaluation
 ops.dense_ba_refine without and with a weight map (the yardstick is the run without the map, in the same process), and
 ops.dense_ba_depth_variance at the refined state with the sums given, marginal over the pose and conditional on it, beside
@@ -443,6 +450,82 @@ def main_joint_grad(argv):
         f.write(line + '\n')
 
 
+def run_joint_grad_exact_case(H, W):
+    """--joint-grad-exact: the backward of the joint refinement with the exact Hessian beside the Gauss-Newton
+    backward of section 3.26 on the same tensors in the same process."""
+    import numpy as np
+    import torch
+    from islam_amd import lietensor as pp
+    from islam_amd import ops
+    from islam_amd.dense_ba import DenseReprojectionLoss
+    from tests.dense_reproj_f64 import MOUNT, PRIOR_W, SIGMA_RHO, make_scene, noisy_prior, right_perturb
+    dev = torch.device('cuda:0')
+    sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    w = torch.full((B,), PRIOR_W, dtype=torch.float64, device=dev)
+    rng = np.random.default_rng(0)
+    coeff, coeff_depth = d(rng.standard_normal((B, 7))), d(rng.standard_normal((B, H, W)).astype(np.float32))
+    v_d = d(rng.standard_normal((B, H, W)))
+    ones = torch.ones((B, H, W), dtype=torch.float32, device=dev)
+    fx, fy, cx, cy = sc['intr'][0]
+    ref = ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20)
+    state = (depth, flow, mask, ref.motion, intr, w, ref.inv_depth)
+    nw = ops.dense_ba_newton_weights(*state, coeff, grad_inv_depth=v_d, rgb2imu=mount, status=ref.status)
+    zl, fl = depth.clone().requires_grad_(), flow.clone().requires_grad_()
+    loss = DenseReprojectionLoss(zl, fl, fx, fy, cx, cy, mask, pp.SE3(mount), device=dev)
+
+    def refine_backward(**kw):
+        zl.grad = fl.grad = None
+        out = loss.refine_joint(pp.SE3(motion), SIGMA_RHO, sigma_px=0.3, iters=20, differentiable=True, **kw)
+        ((out.motion * coeff).sum() + (out.depth * coeff_depth).sum()).backward()
+
+    def gn_backward(g=v_d):
+        lk, st = ops.dense_ba_ift_weights(*state, ref.S, coeff, grad_inv_depth=g, rgb2imu=mount, status=ref.status)
+        return ops.dense_ba_vjp(*state, lk, grad_inv_depth=g, rgb2imu=mount, status=st)
+
+    def exact_backward(g=v_d, m=None):
+        k = ops.dense_ba_newton_weights(*state, coeff, grad_inv_depth=g, rgb2imu=mount, status=ref.status, prior_scale=m)
+        return ops.dense_ba_newton_vjp(*state, k.lambda_p, grad_inv_depth=g, rgb2imu=mount, status=k.status, prior_scale=m)
+
+    fns = {'gn_backward': gn_backward, 'gn_backward_pose_loss': lambda: gn_backward(None),
+           'newton_weights': lambda: ops.dense_ba_newton_weights(*state, coeff, grad_inv_depth=v_d, rgb2imu=mount, status=ref.status),
+           'newton_vjp': lambda: ops.dense_ba_newton_vjp(*state, nw.lambda_p, grad_inv_depth=v_d, rgb2imu=mount, status=nw.status),
+           'exact_backward': exact_backward, 'exact_backward_pose_loss': lambda: exact_backward(None), 'exact_backward_map': lambda: exact_backward(v_d, ones),
+           'gn_refine_joint20_backward': refine_backward, 'exact_refine_joint20_backward': lambda: refine_backward(hessian='exact')}
+    out = timed(fns)
+    gd, gf = gn_backward()
+    ed, ef = exact_backward()
+    out['exact_over_gn_backward'] = out['exact_backward'] / out['gn_backward']
+    out['exact_over_gn_refine_joint20_backward'] = out['exact_refine_joint20_backward'] / out['gn_refine_joint20_backward']
+    out['grad_depth_exact_vs_gn'] = float((ed - gd).abs().max() / gd.abs().max())
+    out['grad_flow_exact_vs_gn'] = float((ef - gf).abs().max() / gf.abs().max())
+    out['fallback_pixels'] = int(nw.fallback.sum())
+    out['status_ok'] = int((nw.status == 0).sum())
+    return out
+
+
+def main_joint_grad_exact(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_joint_grad_exact_case(*hw) for case, hw in cases.items()}
+    cols = ('gn_backward', 'gn_backward_pose_loss', 'newton_weights', 'newton_vjp', 'exact_backward', 'exact_backward_pose_loss', 'exact_backward_map',
+            'gn_refine_joint20_backward', 'exact_refine_joint20_backward', 'exact_over_gn_backward', 'exact_over_gn_refine_joint20_backward',
+            'grad_depth_exact_vs_gn', 'grad_flow_exact_vs_gn', 'fallback_pixels', 'status_ok')
+    print('us per call at B = %d: the median of 30; the Gauss-Newton backward (gn_*) is the yardstick of the same run' % B)
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'dense_ba_newton_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 VAR_PIXEL_BYTES = 33          # the variance pass: the 13 of the pose-only pass, the map (4), rho (8) and one float64 store (8)
 
 
@@ -666,6 +749,8 @@ def main():
         return main_propagate(sys.argv[1:])
     if '--uncertainty' in sys.argv[1:]:
         return main_uncertainty(sys.argv[1:])
+    if '--joint-grad-exact' in sys.argv[1:]:
+        return main_joint_grad_exact(sys.argv[1:])
     if '--joint-grad' in sys.argv[1:]:
         return main_joint_grad(sys.argv[1:])
     if '--grad' in sys.argv[1:]:
