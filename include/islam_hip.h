@@ -673,6 +673,40 @@ int islam_depth_propagate(const double* inv_depth, const double* var_inv_depth, 
                           double* out_var, float* out_depth, int* out_source, uint8_t* out_flags, int* out_status, void* scratch,
                           int B, int H, int W, void* stream);
 
+/* The vector-Jacobian product of islam_depth_propagate.  The map is piecewise smooth: the target pixel
+ * (iu, iv), the z-buffer winner and the row of the fusion table (the gate decision included) are constant on a piece and get no
+ * derivative; source (out_source) and flags (out_flags) of the forward call say which piece a target is on, and the arithmetic of that
+ * piece is differentiated exactly, in fp64.  Since (u2, v2) only select a target, rho' and s' depend on the pose through a and t_z
+ * (= t[2]) alone:
+ *   drho'/drho = J,  drho'/da = -rho'^2 / rho,  drho'/dt_z = -rho'^2,
+ *   dJ/drho = 2 J (J / rho' - 1 / rho),  dJ/da = (rho'^2 / rho^2)(1 - 2 a rho' / rho),  dJ/dt_z = -2 J rho',
+ *   ds'/ds = J^2,  ds'/dx = 2 J s dJ/dx  for x in (rho, a, t_z);
+ * fusion, with D = s' + s_m and rho_m = 1 / depth_next:
+ *   both, not gated:  drho_f/drho' = s_m / D,  drho_f/drho_m = s' / D,  drho_f/ds' = (rho_m - rho_f) / D,  drho_f/ds_m = (rho' - rho_f) / D,
+ *                     ds_f/ds' = s_m^2 / D^2,  ds_f/ds_m = s'^2 / D^2;
+ *   gated, or measured only:  rho_f = rho_m, s_f = s_m;   propagated only:  rho_f = rho', s_f = s';   nothing: no input is reached;
+ *   drho_m/ddepth_next = -rho_m^2,  ds_m/dvar_next = 1.
+ * Cotangents (float64 (B,H,W), NULL: zero): grad_out_inv_depth on rho_f, grad_out_var on s_f; an entry is read only where flags is not
+ * 0, so it may be NaN where nothing is known.  Outputs, all written in full by plain stores (no memset, no atomics; a repeat gives the
+ * same bits): grad_inv_depth, grad_var_inv_depth (B,H,W) float64 on rho and s, exactly 0 at a source pixel that did not win its target
+ * (read from source, never re-derived); grad_motion (B,7) float64 on the plain components [t, q xyzw] of motion, the cotangent of (R20,
+ * R21, R22, t_z) chained through the matrix of the quaternion, the inverse and the mount conjugation as the forward pass writes them;
+ * grad_depth_next, grad_var_next (B,H,W) float32 (both or neither; rounded once at the store).  out_status: the forward call's; a
+ * link whose entry is not 0 propagated nothing: its grad_inv_depth, grad_var_inv_depth and grad_motion are exact zeros, and its
+ * measurement rows still pass their gradient on.  process_var, gate, intr4, the mount and the mask get no gradient (the mask is not
+ * needed: source carries the winners).  scratch: islam_depth_propagate_vjp_scratch_bytes(B) bytes (B x 64 rows of four partial sums).
+ * Two launches on `stream`, no host wait: depth_prop_vjp_kernel (every pixel as a target and as a source; the four pose sums reduced
+ * in a fixed order) and depth_prop_pose_kernel (one workgroup per link).  ISLAM_EARG before any device work for a bad shape (as
+ * above), a NULL pointer other than rgb2imu_or_null, depth_next_or_null, var_next_or_null, the two cotangents and the two measurement
+ * gradients, depth_next without var_next or the reverse (likewise their gradients), and a measurement gradient without a measurement. */
+size_t islam_depth_propagate_vjp_scratch_bytes(int B);
+int islam_depth_propagate_vjp(const double* inv_depth, const double* var_inv_depth, const double* motion, const double* rgb2imu_or_null,
+                              const double* intr4, const double* process_var, const float* depth_next_or_null,
+                              const float* var_next_or_null, const int* source, const uint8_t* flags, const int* out_status,
+                              const double* grad_out_inv_depth_or_null, const double* grad_out_var_or_null, double* grad_inv_depth,
+                              double* grad_var_inv_depth, double* grad_motion, float* grad_depth_next_or_null,
+                              float* grad_var_next_or_null, void* scratch, int B, int H, int W, void* stream);
+
 /* Regularisation of a propagated map: occlusion removal, hole filling and smoothing of the inverse depths rho
  * and variances s (B,H,W) float64 that islam_depth_propagate returned without a measurement, then the fusion table above.  All device
  * arithmetic is fp64, every operation rounded on its own.  A window is the (2r+1)^2 square around a pixel clipped at the image border,

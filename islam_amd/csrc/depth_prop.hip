@@ -14,6 +14,10 @@
 // depth_regularize_kernel (islam_depth_regularize) stands between the two when the caller asks for it: on the
 // map a pure propagation returned it removes background seen through the holes of a magnified surface, fills holes from their
 // neighbours and smooths every value over its compatible neighbours, a stencil on an LDS tile, and ends in the same fusion table.
+//
+// depth_prop_vjp_kernel and depth_prop_pose_kernel (islam_depth_propagate_vjp) are the vector-Jacobian product
+// of the propagation on the piece its forward pass chose: the target pixel, the z-buffer winner and the row of the fusion table are
+// read from out_source and out_flags, and the arithmetic of that piece is differentiated with plain stores and fixed-order sums.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -398,7 +402,239 @@ __global__ __launch_bounds__(256) void depth_regularize_kernel(const double* __r
     out_flags[off + gj] = (uint8_t)(f.flags | extra);
 }
 
+// ------------------------------------------------------------------ the gradient of the propagation
+// The map is piecewise smooth: the target pixel, the z-buffer winner and the row of the fusion table are constant on a piece, and the
+// forward pass's source and flags say which piece a target is on.  The two kernels below take them as given and differentiate the
+// arithmetic of that piece.  Since (u2, v2) only select a target, rho' and s' see the pose through a = R[2,:].ray and t_z alone.
+
+// the cotangents of (rho', s') and of the measurement at one target
+struct FuseGrad {
+    double g_rp, g_sp, g_dn, g_vn;
+};
+
+// The fusion table differentiated at one target: gr, gs are the cotangents of rho_f and s_f (read by the caller only where flags is not
+// 0), (rp, sp) the winner's hypothesis where flags has FLAG_PROP, (dn, vn) the measurement where it has FLAG_MEAS.
+ISLAM_DEV FuseGrad fuse_grad(int flags, double gr, double gs, double rp, double sp, float dn, float vn) {
+    FuseGrad g{0.0, 0.0, 0.0, 0.0};
+    const bool prop = (flags & FLAG_PROP) != 0, meas = (flags & FLAG_MEAS) != 0, gated = (flags & FLAG_GATED) != 0;
+    double g_rm = 0.0, g_sm = 0.0;
+    if (prop && meas && !gated) {
+        const double sm = (double)vn, rm = 1.0 / (double)dn, D = sp + sm;
+        const double rf = (rp * sm + rm * sp) / D, wp = sm / D, wm = sp / D;
+        g.g_rp = gr * wp;
+        g_rm = gr * wm;
+        g.g_sp = gr * ((rm - rf) / D) + gs * (wp * wp);
+        g_sm = gr * ((rp - rf) / D) + gs * (wm * wm);
+    } else if (meas) {      // measured only, or the gate chose the measurement
+        g_rm = gr;
+        g_sm = gs;
+    } else if (prop) {
+        g.g_rp = gr;
+        g.g_sp = gs;
+    }
+    if (meas) {
+        const double rm = 1.0 / (double)dn;
+        g.g_dn = -(rm * rm) * g_rm;
+        g.g_vn = g_sm;
+    }
+    return g;
+}
+
+// the cotangents of (rho, s) of source pixel i and of (a, t_z), with the ray of i for the pose sums
+struct WarpGrad {
+    double G_rho, G_s, G_a, G_tz, xh, yh;
+};
+
+// rho' = 1 / (a / rho + t_z) and s' = J^2 s + q differentiated at source pixel i (a usable one: the caller read it from source)
+ISLAM_DEV WarpGrad warp_grad(const PropLink& lk, int i, double g_rp, double g_sp) {
+    const int v = i / lk.W, u = i - v * lk.W;
+    const double xh = ((double)u - lk.in.cx) / lk.in.fx, yh = ((double)v - lk.in.cy) / lk.in.fy;
+    const double rho = lk.rho[i], s = lk.var[i];
+    const double a = lk.R[6] * xh + lk.R[7] * yh + lk.R[8];
+    const double rp = 1.0 / (a / rho + lk.t[2]), ir = 1.0 / rho;
+    const double rp2 = rp * rp, J = a * rp2 * (ir * ir);
+    const double g_J = 2.0 * J * s * g_sp;
+    const double dJ_drho = 2.0 * J * (J / rp - ir), dJ_da = rp2 * (ir * ir) * (1.0 - 2.0 * a * rp * ir), dJ_dtz = -2.0 * J * rp;
+    return {g_rp * J + g_J * dJ_drho, J * J * g_sp, g_J * dJ_da - g_rp * rp2 * ir, g_J * dJ_dtz - g_rp * rp2, xh, yh};
+}
+
+// grid (NBLK, B) x 256, grid-stride; every pixel index p is a target (the measurement's gradient, the four pose sums) and a source (its
+// own gradient if it won its target, zeros if not).  partials (B, NBLK, 4): the workgroup's sums of G_a xh, G_a yh, G_a and G_tz.
+__global__ __launch_bounds__(256) void depth_prop_vjp_kernel(const double* __restrict__ inv_depth, const double* __restrict__ var_inv_depth,
+                                                              const double* __restrict__ motion, const double* __restrict__ rgb2imu,
+                                                              const double* __restrict__ intr4, const double* __restrict__ process_var,
+                                                              const float* __restrict__ depth_next, const float* __restrict__ var_next,
+                                                              const int* __restrict__ source, const uint8_t* __restrict__ flags,
+                                                              const int* __restrict__ out_status, const double* __restrict__ gout_rho,
+                                                              const double* __restrict__ gout_var, double* __restrict__ grad_rho,
+                                                              double* __restrict__ grad_var, float* __restrict__ grad_dn,
+                                                              float* __restrict__ grad_vn, double* __restrict__ partials, int H, int W) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const size_t off = (size_t)b * HW;
+    const bool live = out_status[b] == ISLAM_DENSE_REPROJ_OK;      // (uniform over the workgroup) a link with a status propagated nothing
+    PropLink lk{};
+    if (live) lk = prop_link(inv_depth, var_inv_depth, nullptr, motion, rgb2imu, intr4, process_var, b, H, W);
+    const int* sb = source + off;
+    const uint8_t* fb = flags + off;
+    const float* dnb = depth_next ? depth_next + off : nullptr;
+    const float* vnb = depth_next ? var_next + off : nullptr;
+    const double* grb = gout_rho ? gout_rho + off : nullptr;      // a NULL cotangent is zero
+    const double* gsb = gout_var ? gout_var + off : nullptr;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += NBLK * 256) {
+        {      // p as a target
+            int fl = fb[p], src = -1;
+            double rp = 0.0, sp = 0.0;
+            if (live && (fl & FLAG_PROP)) {
+                const int i = sb[p];
+                if (i >= 0 && i < HW) {
+                    const PropPixel w = prop_pixel(lk, i);
+                    src = i;
+                    rp = w.rho;
+                    sp = w.var;
+                }
+            }
+            if (src < 0) fl &= FLAG_MEAS;
+            if (!dnb) fl &= ~(FLAG_MEAS | FLAG_GATED);
+            // a cotangent is read only where the output depends on an input: where nothing is known it may be NaN
+            const FuseGrad g = fuse_grad(fl, fl && grb ? grb[p] : 0.0, fl && gsb ? gsb[p] : 0.0, rp, sp, dnb ? dnb[p] : 0.0f, dnb ? vnb[p] : 0.0f);
+            if (grad_dn) {
+                grad_dn[off + p] = (float)g.g_dn;
+                grad_vn[off + p] = (float)g.g_vn;
+            }
+            if (src >= 0) {
+                const WarpGrad wg = warp_grad(lk, src, g.g_rp, g.g_sp);
+                acc[0] += wg.G_a * wg.xh;
+                acc[1] += wg.G_a * wg.yh;
+                acc[2] += wg.G_a;
+                acc[3] += wg.G_tz;
+            }
+        }
+        double Gr = 0.0, Gs = 0.0;      // p as a source: exact zeros unless source says it won its target
+        if (live) {
+            const PropPixel me = prop_pixel(lk, p);      // me.j lies in [0, HW) where me.cand
+            if (me.cand && sb[me.j] == p) {
+                int fj = fb[me.j];
+                if (!dnb) fj &= ~(FLAG_MEAS | FLAG_GATED);
+                if (fj & FLAG_PROP) {
+                    const FuseGrad g = fuse_grad(fj, grb ? grb[me.j] : 0.0, gsb ? gsb[me.j] : 0.0, me.rho, me.var, dnb ? dnb[me.j] : 0.0f,
+                                                 dnb ? vnb[me.j] : 0.0f);
+                    const WarpGrad wg = warp_grad(lk, p, g.g_rp, g.g_sp);
+                    Gr = wg.G_rho;
+                    Gs = wg.G_s;
+                }
+            }
+        }
+        grad_rho[off + p] = Gr;
+        grad_var[off + p] = Gs;
+    }
+    reduce_and_store_row<4>(acc, partials + ((size_t)b * NBLK + blockIdx.x) * 4, true, 0.0);
+}
+
+// the cotangents of q and p in r = qact(q, p) = p + q.w uv + u x uv, uv = 2 u x p, from the cotangent g of r
+ISLAM_DEV void qact_vjp(Q4<double> q, V3<double> p, V3<double> g, Q4<double>& gq, V3<double>& gp) {
+    const V3<double> u{q.x, q.y, q.z};
+    const V3<double> uv = 2.0 * cross(u, p);
+    const V3<double> guv = q.w * g + cross(g, u);
+    const V3<double> gu = cross(uv, g) + 2.0 * cross(p, guv);
+    gq = {gu.x, gu.y, gu.z, dot(g, uv)};
+    gp = g + 2.0 * cross(guv, u);
+}
+
+// the cotangents of a and b in qmul(a, b) from the cotangent g of the product
+ISLAM_DEV Q4<double> qmul_vjp_a(Q4<double> g, Q4<double> b) {
+    return {g.x * b.w - g.y * b.z + g.z * b.y - g.w * b.x, g.x * b.z + g.y * b.w - g.z * b.x - g.w * b.y,
+            -g.x * b.y + g.y * b.x + g.z * b.w - g.w * b.z, g.x * b.x + g.y * b.y + g.z * b.z + g.w * b.w};
+}
+ISLAM_DEV Q4<double> qmul_vjp_b(Q4<double> a, Q4<double> g) {
+    return {g.x * a.w + g.y * a.z - g.z * a.y - g.w * a.x, -g.x * a.z + g.y * a.w + g.z * a.x - g.w * a.y,
+            g.x * a.y - g.y * a.x + g.z * a.w - g.w * a.z, g.x * a.x + g.y * a.y + g.z * a.z + g.w * a.w};
+}
+ISLAM_DEV Q4<double> operator+(Q4<double> a, Q4<double> b) { return {a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
+
+// grid (B) x 64.  The NBLK rows of a link are summed in index order; lane 0 chains the cotangent of (R20, R21, R22, t_z) back through
+// qmat, the inverse and the mount conjugation of camera_inverse to the plain components [t, q xyzw] of motion[b], every product taken
+// as the forward pass writes it (no unit-norm assumption on a quaternion).  A link with a status gets seven zeros.
+__global__ __launch_bounds__(64) void depth_prop_pose_kernel(const double* __restrict__ partials, const double* __restrict__ motion,
+                                                              const double* __restrict__ rgb2imu, const int* __restrict__ out_status,
+                                                              double* __restrict__ grad_motion) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    __shared__ double s[4];
+    if (i < 4) {
+        double v = 0.0;
+        for (int k = 0; k < NBLK; ++k) v += partials[((size_t)b * NBLK + k) * 4 + i];
+        s[i] = v;
+    }
+    __syncthreads();
+    if (i != 0) return;
+    double* gm = grad_motion + (size_t)b * 7;
+    if (out_status[b] != ISLAM_DENSE_REPROJ_OK) {
+        for (int k = 0; k < 7; ++k) gm[k] = 0.0;
+        return;
+    }
+    // forward: T = C^-1 M C (A = C^-1 M), Ti = T^-1 = (qi, ti), R = qmat(qi)
+    const SE3<double> M = se3_load(motion + 7 * b);
+    SE3<double> T = M, A = M, C{}, Ci{};
+    if (rgb2imu) {
+        C = se3_load(rgb2imu);
+        Ci = se3_inv(C);
+        A = se3_mul(Ci, M);
+        T = se3_mul(A, C);
+    }
+    const Q4<double> qi = qinv(T.q);
+    // R20 = 2 (x z - y w), R21 = 2 (y z + x w), R22 = 1 - 2 (x^2 + y^2) of qi
+    const double g0 = 2.0 * s[0], g1 = 2.0 * s[1], g2 = 2.0 * s[2];
+    Q4<double> gqi{g0 * qi.z + g1 * qi.w - 2.0 * g2 * qi.x, g1 * qi.z - g0 * qi.w - 2.0 * g2 * qi.y, g0 * qi.x + g1 * qi.y,
+                   g1 * qi.x - g0 * qi.y};
+    // ti = -qact(qi, T.t)
+    Q4<double> gq;
+    V3<double> gTt;
+    qact_vjp(qi, T.t, v3(0.0, 0.0, -s[3]), gq, gTt);
+    gqi = gqi + gq;
+    const Q4<double> gTq{-gqi.x, -gqi.y, -gqi.z, gqi.w};
+    V3<double> gMt = gTt;
+    Q4<double> gMq = gTq;
+    if (rgb2imu) {
+        // T.t = A.t + qact(A.q, C.t), T.q = qmul(A.q, C.q);  A.t = Ci.t + qact(Ci.q, M.t), A.q = qmul(Ci.q, M.q)
+        V3<double> unused;
+        qact_vjp(A.q, C.t, gTt, gq, unused);
+        const Q4<double> gAq = gq + qmul_vjp_a(gTq, C.q);
+        qact_vjp(Ci.q, M.t, gTt, gq, gMt);
+        gMq = qmul_vjp_b(Ci.q, gAq);
+    }
+    gm[0] = gMt.x; gm[1] = gMt.y; gm[2] = gMt.z; gm[3] = gMq.x; gm[4] = gMq.y; gm[5] = gMq.z; gm[6] = gMq.w;
+}
+
 }  // namespace
+
+extern "C" size_t islam_depth_propagate_vjp_scratch_bytes(int B) { return B < 1 ? 0 : align_up((size_t)B * NBLK * 4 * sizeof(double)); }
+
+extern "C" int islam_depth_propagate_vjp(const double* inv_depth, const double* var_inv_depth, const double* motion, const double* rgb2imu_or_null,
+                                         const double* intr4, const double* process_var, const float* depth_next_or_null,
+                                         const float* var_next_or_null, const int* source, const uint8_t* flags, const int* out_status,
+                                         const double* grad_out_inv_depth_or_null, const double* grad_out_var_or_null, double* grad_inv_depth,
+                                         double* grad_var_inv_depth, double* grad_motion, float* grad_depth_next_or_null,
+                                         float* grad_var_next_or_null, void* scratch, int B, int H, int W, void* stream) {
+    const char* who = "islam_depth_propagate_vjp";
+    if (int rc = check_shape_kind(who, B, H, W, ISLAM_ROBUST_NONE, 1.0)) return rc;
+    if (!inv_depth || !var_inv_depth || !motion || !intr4 || !process_var || !source || !flags || !out_status)
+        return fail(ISLAM_EARG, "%s: NULL inv_depth / var_inv_depth / motion / intr4 / process_var / source / flags / out_status pointer", who);
+    if (!grad_inv_depth || !grad_var_inv_depth || !grad_motion || !scratch) return fail(ISLAM_EARG, "%s: NULL output / scratch pointer", who);
+    if ((depth_next_or_null == nullptr) != (var_next_or_null == nullptr))
+        return fail(ISLAM_EARG, "%s: depth_next and var_next come together or not at all", who);
+    if ((grad_depth_next_or_null == nullptr) != (grad_var_next_or_null == nullptr))
+        return fail(ISLAM_EARG, "%s: grad_depth_next and grad_var_next come together or not at all", who);
+    if (grad_depth_next_or_null && !depth_next_or_null) return fail(ISLAM_EARG, "%s: a measurement gradient without a measurement", who);
+    hipStream_t s = as_stream(stream);
+    double* partials = static_cast<double*>(scratch);
+    hipLaunchKernelGGL(depth_prop_vjp_kernel, dim3(NBLK, B), dim3(256), 0, s, inv_depth, var_inv_depth, motion, rgb2imu_or_null, intr4,
+                       process_var, depth_next_or_null, var_next_or_null, source, flags, out_status, grad_out_inv_depth_or_null,
+                       grad_out_var_or_null, grad_inv_depth, grad_var_inv_depth, grad_depth_next_or_null, grad_var_next_or_null, partials, H, W);
+    hipLaunchKernelGGL(depth_prop_pose_kernel, dim3(B), dim3(64), 0, s, partials, motion, rgb2imu_or_null, out_status, grad_motion);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
 
 extern "C" size_t islam_depth_regularize_scratch_bytes(int B, int H, int W) { return 0; }      // one fused launch: nothing in between
 

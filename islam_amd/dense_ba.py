@@ -15,7 +15,8 @@
     deviation per pixel as well, and ``depth_uncertainty`` returns the posterior standard deviation of every refined depth
     (section 3.27); ``propagate`` carries both into the next frame's pixel grid and fuses them with that frame's own depth map, the
     prior of the next link (csrc/depth_prop.hip, section 3.28), with ``regularize=DepthRegularizer(...)`` after occlusion removal,
-    hole filling and smoothing of the propagated map (section 3.29);
+    hole filling and smoothing of the propagated map (section 3.29); ``propagate(differentiable=True)`` lets a loss behind the next
+    link's refinement reach this link's state, pose and measurement (section 3.31);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -365,7 +366,8 @@ class DenseReprojectionLoss:
             raise ValueError('propagate: %s must be a finite non-negative number (got %r)' % (name, sigma))
         return ps * ps
 
-    def propagate(self, joint, uncertainty, depth_next=None, sigma_inv_depth_next=None, process_sigma=0.0, gate=3.0, regularize=None):
+    def propagate(self, joint, uncertainty, depth_next=None, sigma_inv_depth_next=None, process_sigma=0.0, gate=3.0, regularize=None,
+                  differentiable=False):
         """The step from one link to the next: the inverse depths a ``refine_joint`` returned (``joint``) and their variances
         (``uncertainty``: the result of ``depth_uncertainty`` for it) are warped through the refined pose into the pixel grid of the
         link's second frame, the nearest surface winning where several pixels land on one, and fused there with that frame's own depth
@@ -384,8 +386,20 @@ class DenseReprojectionLoss:
         pure propagation, then ops.dense_ba_depth_regularize with the measurement and ``gate``: background seen through the holes of a
         magnified surface is removed, holes are filled from their neighbours, every value is smoothed over its compatible neighbours.
         flags then also carries 8 (filled) and 16 (removed), its 1 means "a propagated or filled value is present", and source is -1
-        at filled and removed pixels.  None: the single call above, unchanged."""
+        at filled and removed pixels.  None: the single call above, unchanged.
+
+        differentiable=False (the default): every input is detached and no gradient is attached.  differentiable=True: the same
+        launches and the same bits, and ``inv_depth`` and ``var_inv_depth`` carry a grad_fn over ``joint.inv_depth``,
+        ``joint.motion``, ``uncertainty.var_inv_depth`` and ``depth_next`` (which keeps its graph on this path), with ``depth`` and
+        ``sigma_inv_depth`` formed from them in torch, so a loss on the next link's refinement reaches this link's refinement and the
+        networks behind both (ops._DenseBAPropagate, ops.dense_ba_depth_propagate_vjp, two launches).  The
+        gradient is that of the piece the forward pass chose: the target pixel, the z-buffer winner and the gate decision are held
+        fixed.  ``sigma_inv_depth_next``, ``process_sigma`` and ``gate`` get no gradient; a link with a status gets a zero gradient on
+        its state and pose.  With ``regularize`` it raises NotImplementedError (the stencil is not differentiated)."""
         from . import ops
+        if differentiable and regularize is not None:
+            raise NotImplementedError('propagate: differentiable=True is not implemented with regularize (the gradient of the regularisation '
+                                      'is not available)')
         if (depth_next is None) != (sigma_inv_depth_next is None):
             raise ValueError('propagate: depth_next and sigma_inv_depth_next come together or not at all')
         var_next = None
@@ -393,10 +407,17 @@ class DenseReprojectionLoss:
             if tuple(depth_next.shape) != tuple(self.z.shape):
                 raise ValueError('propagate: depth_next must be %s, got %s' % (tuple(self.z.shape), tuple(depth_next.shape)))
             var_next = self._variance_next(sigma_inv_depth_next, 'propagate')
-            depth_next = depth_next.detach().to(self.z.device)
+            depth_next = (depth_next if differentiable else depth_next.detach()).to(self.z.device)
         process_var = self._link_sigma_squared(process_sigma, 'process_sigma')
         link = (joint.inv_depth, uncertainty.var_inv_depth, joint.motion, torch.tensor(self.K4, dtype=torch.float64))
         link_kw = dict(mask=self.mask, status=uncertainty.status, rgb2imu=self.rgb2imu_pose, process_var=process_var)
+        if differentiable:
+            mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
+            out = ops.DenseBAPropagated(*ops._DenseBAPropagate.apply(*link, self.mask, uncertainty.status, mount, process_var, depth_next, var_next,
+                                                                     gate))
+            ok = out.inv_depth > 0          # the kernel's out_depth, with its graph: the float32 of 1 / rho_f, else the bits it stored
+            depth = torch.where(ok, (1.0 / torch.where(ok, out.inv_depth, torch.ones_like(out.inv_depth))).to(torch.float32), out.depth)
+            return DenseBAPrior(depth, torch.sqrt(out.var_inv_depth), out.inv_depth, out.var_inv_depth, out.source, out.flags, out.status)
         if regularize is None:
             out = ops.dense_ba_depth_propagate(*link, **link_kw, depth_next=depth_next, var_next=var_next, gate=gate)
         else:

@@ -458,6 +458,90 @@ def dense_ba_depth_propagate(inv_depth, var_inv_depth, motion, intr, mask=None, 
     return out
 
 
+DenseBAPropagateGrad = collections.namedtuple('DenseBAPropagateGrad', 'grad_inv_depth grad_var_inv_depth grad_motion grad_depth_next grad_var_next')
+
+
+def dense_ba_depth_propagate_vjp(inv_depth, var_inv_depth, motion, intr, source, flags, status, grad_inv_depth=None, grad_var_inv_depth=None,
+                                 rgb2imu=None, process_var=0.0, depth_next=None, var_next=None):
+    """The vector-Jacobian product of dense_ba_depth_propagate on the piece its forward pass chose (include/islam_hip.h,
+    islam_depth_propagate_vjp).  inv_depth, var_inv_depth, motion, intr, rgb2imu, process_var, depth_next,
+    var_next: what the forward call was given (the mask is not needed); source, flags (B,H,W) and status (B): what it returned;
+    grad_inv_depth, grad_var_inv_depth (B,H,W) or None (zero): the cotangents of its inv_depth and var_inv_depth outputs, read only
+    where flags is not 0 (they may be NaN where nothing is known).  The target pixel, the z-buffer winner and the row of the fusion
+    table are held fixed.  Returns DenseBAPropagateGrad(grad_inv_depth, grad_var_inv_depth (B,H,W) float64: exactly 0 at a source pixel
+    that did not win its target, grad_motion (B,7) float64 on the plain components [t, q xyzw] (what dense_ba_newton_weights and
+    dense_ba_ift_weights take as grad_motion), grad_depth_next, grad_var_next (B,H,W) float32, None without a measurement).  A link
+    whose status is not 0 gets zeros on its state and motion; its measurement still gets its gradient.  Two launches, nothing is read
+    back."""
+    who = 'dense_ba_depth_propagate_vjp'
+    dev = inv_depth.device
+    if inv_depth.dim() != 3 or tuple(var_inv_depth.shape) != tuple(inv_depth.shape):
+        raise ValueError('%s: inv_depth and var_inv_depth must be (B,H,W), got %s and %s' % (who, tuple(inv_depth.shape), tuple(var_inv_depth.shape)))
+    B, H, W = inv_depth.shape
+    rho, var = (t.detach().to(dev, torch.float64).contiguous() for t in (inv_depth, var_inv_depth))
+    _, motion, intr, rgb2imu = _dense_link_args(who, dev, B, H, W, None, motion, intr, rgb2imu)
+    pv = _link_variance(who, 'process_var', process_var, B, dev)
+    depth_next, var_next, _ = _next_measurement(who, depth_next, var_next, 0.0, B, H, W, dev)
+    if tuple(source.shape) != (B, H, W) or tuple(flags.shape) != (B, H, W):
+        raise ValueError('%s: source and flags must be (%d,%d,%d), got %s and %s' % (who, B, H, W, tuple(source.shape), tuple(flags.shape)))
+    source, flags = source.to(dev, torch.int32).contiguous(), flags.to(dev, torch.uint8).contiguous()
+    if status is None:
+        raise ValueError('%s: status must be the (%d,) status the forward call returned' % (who, B))
+    status = _dense_reproj_status(status, B, dev)
+    cots = []
+    for name, g in (('grad_inv_depth', grad_inv_depth), ('grad_var_inv_depth', grad_var_inv_depth)):
+        if g is not None:
+            if tuple(g.shape) != (B, H, W):
+                raise ValueError('%s: %s must be (%d,%d,%d), got %s' % (who, name, B, H, W, tuple(g.shape)))
+            g = g.detach().to(dev, torch.float64).contiguous()
+        cots.append(g)
+    require_cuda(inv_depth, var_inv_depth, depth_next, var_next)      # after the argument rules, which need no device
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    meas = depth_next is not None
+    out = DenseBAPropagateGrad(e(torch.float64, B, H, W), e(torch.float64, B, H, W), e(torch.float64, B, 7),
+                               e(torch.float32, B, H, W) if meas else None, e(torch.float32, B, H, W) if meas else None)
+    scratch = torch.empty(lib().islam_depth_propagate_vjp_scratch_bytes(B), dtype=torch.uint8, device=dev)
+    check(lib().islam_depth_propagate_vjp(ptr(rho), ptr(var), ptr(motion), ptr(rgb2imu), ptr(intr), ptr(pv), ptr(depth_next), ptr(var_next),
+                                          ptr(source), ptr(flags), ptr(status), ptr(cots[0]), ptr(cots[1]), ptr(out.grad_inv_depth),
+                                          ptr(out.grad_var_inv_depth), ptr(out.grad_motion), ptr(out.grad_depth_next),
+                                          ptr(out.grad_var_next), ptr(scratch), B, H, W, stream_ptr(dev)))
+    return out
+
+
+class _DenseBAPropagate(torch.autograd.Function):
+    """dense_ba_depth_propagate whose inv_depth and var_inv_depth outputs carry the gradient of the piece the forward pass chose in
+    inv_depth, var_inv_depth, motion, depth_next and var_next: forward is that call, backward is
+    dense_ba_depth_propagate_vjp on the same tensors with the source, flags and status forward returned, and nothing else.  The mask,
+    the intrinsics, the mount, process_var and the gate get no gradient."""
+
+    @staticmethod
+    def forward(ctx, inv_depth, var_inv_depth, motion, intr, mask, status, rgb2imu, process_var, depth_next, var_next, gate):
+        out = dense_ba_depth_propagate(inv_depth, var_inv_depth, motion, intr, mask=mask, status=status, rgb2imu=rgb2imu, process_var=process_var,
+                                       depth_next=depth_next, var_next=var_next, gate=gate)
+        ctx.save_for_backward(inv_depth, var_inv_depth, motion, intr, rgb2imu, depth_next, var_next, out.source, out.flags, out.status)
+        ctx.process_var = process_var.detach() if torch.is_tensor(process_var) else process_var
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (inv_depth, var_inv_depth, motion, depth_next, var_next))
+        ctx.mark_non_differentiable(out.depth, out.source, out.flags, out.status)
+        ctx.set_materialize_grads(False)          # a cotangent the loss does not give arrives as None: the kernel takes NULL for zero
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_inv_depth, grad_var_inv_depth, *unused):
+        none = (None,) * 11
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1] or need[2] or need[8] or need[9]):
+            return none
+        rho, var, motion, intr, rgb2imu, depth_next, var_next, source, flags, status = ctx.saved_tensors
+        pv = ctx.process_var
+        g = dense_ba_depth_propagate_vjp(rho, var, motion, intr, source, flags, status, grad_inv_depth=grad_inv_depth,
+                                         grad_var_inv_depth=grad_var_inv_depth, rgb2imu=rgb2imu, process_var=pv, depth_next=depth_next,
+                                         var_next=var_next)
+        d = ctx.dtypes
+        return (g.grad_inv_depth.to(d[0]) if need[0] else None, g.grad_var_inv_depth.to(d[1]) if need[1] else None,
+                g.grad_motion.to(d[2]) if need[2] else None, None, None, None, None, None,
+                g.grad_depth_next.to(d[3]) if need[8] else None, g.grad_var_next.to(d[4]) if need[9] else None, None)
+
+
 DenseBARegularized = collections.namedtuple('DenseBARegularized', 'inv_depth var_inv_depth depth source flags status')
 
 

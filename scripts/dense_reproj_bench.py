@@ -50,6 +50,13 @@ measurement at gate 3 on the pure propagation of the same state, all radii 0, 1 
 yardstick is ops.dense_ba_depth_propagate with the same measurement in the same process, the one call it replaces.
 
     python scripts/dense_reproj_bench.py --regularize [--case 448x640] [--out profiles/depth_regularize_bench.json]
+
+--propagate-grad times the gradient of the depth propagation instead: ops.dense_ba_depth_propagate_vjp on the
+source and flags of the propagation fused with a measurement at gate 3, with both cotangents and with the one on the inverse depth
+alone, and the propagation followed by it.  The yardstick is the forward ops.dense_ba_depth_propagate on the same tensors in the same
+process.
+
+    python scripts/dense_reproj_bench.py --propagate-grad [--case 448x640] [--out profiles/depth_propagate_grad_bench.json]
 """
 import json
 import os
@@ -631,6 +638,7 @@ def propagate_scene(H, W):
     var_next = torch.full((B, H, W), 4e-4, dtype=torch.float32, device=dev)
     pv = torch.full((B,), 1e-6, dtype=torch.float64, device=dev)          # on the device, like w: no host-to-device copy inside the timed call
     prop = lambda **kw: ops.dense_ba_depth_propagate(ref.inv_depth, var, ref.motion, intr, mask=mask, status=ref.status, rgb2imu=mount, process_var=pv, **kw)
+    prop.state = dict(inv_depth=ref.inv_depth, var_inv_depth=var, motion=ref.motion, intr=intr, rgb2imu=mount, process_var=pv)      # for --propagate-grad
     return var_fn, prop, depth_next, var_next
 
 
@@ -741,8 +749,64 @@ def main_regularize(argv):
         f.write(line + '\n')
 
 
+# the nominal bytes of one pixel in ops.dense_ba_depth_propagate_vjp with a measurement and both cotangents.  As a target: flags (1),
+# source (4), depth_next and var_next (8), the two cotangents (16), the winner's rho and variance gathered (16), two float32 stores (8).
+# As a source: rho and variance (16), the source index, the flags, the cotangents and the measurement of its target gathered (4 + 1 +
+# 16 + 8), two float64 stores (16)
+PROP_GRAD_PIXEL_BYTES = 114
+
+
+def run_propagate_grad_case(H, W):
+    """--propagate-grad: the cost of the gradient of the propagation beside the propagation itself."""
+    import torch
+    from islam_amd import ops
+    _, prop, depth_next, var_next = propagate_scene(H, W)
+    meas = dict(depth_next=depth_next, var_next=var_next)
+    fwd = prop(gate=3.0, **meas)
+    g = torch.Generator(device='cuda').manual_seed(5)
+    gr = torch.randn((B, H, W), dtype=torch.float64, device='cuda', generator=g)
+    gs = 1e3 * torch.randn((B, H, W), dtype=torch.float64, device='cuda', generator=g)
+    st = prop.state
+    vjp = lambda **kw: ops.dense_ba_depth_propagate_vjp(st['inv_depth'], st['var_inv_depth'], st['motion'], st['intr'], fwd.source, fwd.flags, fwd.status,
+                                                        rgb2imu=st['rgb2imu'], process_var=st['process_var'], **meas, **kw)
+    out = timed({'propagate_fuse': lambda: prop(gate=3.0, **meas), 'vjp': lambda: vjp(grad_inv_depth=gr, grad_var_inv_depth=gs),
+                 'vjp_inv_depth_only': lambda: vjp(grad_inv_depth=gr),
+                 'propagate_then_vjp': lambda: (prop(gate=3.0, **meas), vjp(grad_inv_depth=gr, grad_var_inv_depth=gs))})
+    r = vjp(grad_inv_depth=gr, grad_var_inv_depth=gs)
+    out['status_ok'] = int((fwd.status == 0).sum())
+    out['hit_fraction'] = float(((fwd.flags & 1) != 0).double().mean())
+    out['nonzero_grad_fraction'] = float((r.grad_inv_depth != 0).double().mean())
+    out['finite'] = int(all(bool(torch.isfinite(t).all()) for t in r))
+    out['vjp_over_fuse'] = out['vjp'] / out['propagate_fuse']
+    out['chain_over_fuse'] = out['propagate_then_vjp'] / out['propagate_fuse']
+    out['MB_moved_vjp'] = PROP_GRAD_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_vjp'] = PROP_GRAD_PIXEL_BYTES * B * H * W / (out['vjp'] * 1e-6) / 1e9 / HBM_GBS
+    return out
+
+
+def main_propagate_grad(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_propagate_grad_case(*hw) for case, hw in cases.items()}
+    cols = ('propagate_fuse', 'vjp', 'vjp_inv_depth_only', 'propagate_then_vjp', 'vjp_over_fuse', 'chain_over_fuse', 'MB_moved_vjp', 'hbm_frac_vjp',
+            'status_ok', 'hit_fraction', 'nonzero_grad_fraction', 'finite')
+    print('us per call at B = %d: the median of 30; hbm_frac_vjp: %d bytes per pixel over the time, of %.0f GB/s' % (B, PROP_GRAD_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'depth_propagate_grad_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--propagate-grad' in sys.argv[1:]:
+        return main_propagate_grad(sys.argv[1:])
     if '--regularize' in sys.argv[1:]:
         return main_regularize(sys.argv[1:])
     if '--propagate' in sys.argv[1:]:
