@@ -589,6 +589,42 @@ int islam_dense_ba_depth_var(const float* depth, const float* flow, const uint8_
                              const int* status_or_null, int robust_kind, double robust_delta, int mode, double* out_var,
                              int* out_status, void* scratch, int B, int H, int W, void* stream);
 
+/* The vector-Jacobian product of islam_dense_ba_depth_var: the TOTAL derivative of v in the state rho
+ * (inv_depth), motion and flow.  S_cam is a function of that same state, not an independent input: sums are by contract the sums at
+ * the state (islam_dense_ba_refine returns them bit-equal to islam_dense_ba_normal there), and no gradient on sums is taken or given.
+ * Held fixed and read from the forward evaluation: which pixels are valid (the clauses of the front, a usable prior, rho finite and
+ * > 0) and the branch of the Huber kernel.  prior_weight, prior_scale, intr4, the mount, the mask and the stored depth (which enters
+ * only through "has a prior") get no gradient.
+ * Notation at a valid pixel: (R, t) = T^-1, Q = R ray / rho + t, d = -R ray / rho^2, J_q = dr/dQ = [[a, 0, bq], [0, cq, dq]],
+ * J = J_q [-I, [Q]x] (rows ju, jv), jd = J_q d, s = |r|^2, c = rho_rob'(s), c' = dc/ds, h_dd = c |jd|^2 + w_i.  With g_i the cotangent
+ * of v_i (grad_var (B,H,W) float64; read at a valid pixel only, so it may be NaN elsewhere) and
+ *   a = J^T jd (h_cam = c a),  k = |jd|^2,  q = a^T S_cam^-1 a,  y = c S_cam^-1 a,
+ *   G = -sum_valid g_i y_i y_i^T / h_dd,i^2   (the cotangent of S_cam; mode 0 only, G = 0 in mode 1),   n = a^T G a,   tau = <G, J^T J>,
+ * everything else is the gradient of one scalar per pixel at fixed S_cam^-1 and G,
+ *   phi_i = g_i (1 / h_dd + c^2 q / h_dd^2) + c tau - c^2 n / h_dd      (mode 1: g_i / h_dd),
+ * the last two terms being <G, J^T (c I - e e^T / h_dd) J>, the pixel's own share of S_cam:
+ *   phi_h = -g / h_dd^2 - 2 g c^2 q / h_dd^3 + c^2 n / h_dd^2,   phi_c = 2 g c q / h_dd^2 + tau - 2 c n / h_dd + k phi_h,   phi_k = c phi_h,
+ *   a~ = 2 (g c^2 / h_dd^2 S_cam^-1 - c^2 / h_dd G) a,   J~ = jd a~^T + 2 c J G,   jd~ = J a~ + 2 phi_k jd,   r~ = 2 c' phi_c r,
+ * chained through J, jd and r = pi(Q) - (pixel + flow) to Q~, d~, then rho~ = -(Q~.R ray) / rho^2 + 2 (d~.R ray) / rho^3,
+ * R~ = (Q~ / rho - d~ / rho^2) ray^T, t~ = Q~ (12 sums per link) and the flow cotangent -r~ (identically zero without a robust kernel).
+ * Outputs, all written in full by plain stores (no memset, no atomics; a repeat gives the same bits): grad_inv_depth (B,H,W)
+ * float64; grad_flow (B,2,H,W) float32 (rounded once at the store); grad_motion (B,7) float64 on the plain components [t, q xyzw] of
+ * motion, the cotangent of (R, t) chained through the matrix of the quaternion, the inverse and the mount conjugation as the forward
+ * pass writes them (no unit-norm assumption: the convention of islam_depth_propagate_vjp's grad_motion); out_status (B) as
+ * islam_dense_ba_depth_var forms it.  A pixel whose v is 1 / w_i or NaN reaches no input: exact zeros.  A link whose out_status is
+ * not 0: zeros everywhere, its seven entries of grad_motion included.
+ * At most four launches on `stream`, no host wait: depth_var_factor_kernel on sums (the forward call's bits, so nothing has to be
+ * saved), in mode 0 depth_var_adj_partial_kernel (the 21 sums of G, one row per workgroup), depth_var_vjp_kernel (the pixel pass and the
+ * 12 pose sums), depth_var_pose_kernel (one workgroup per link).  scratch: islam_dense_ba_depth_var_vjp_scratch_bytes(B) bytes.
+ * ISLAM_EARG before any device work under the rules of islam_dense_ba_depth_var, and for a NULL inv_depth, grad_var or output. */
+size_t islam_dense_ba_depth_var_vjp_scratch_bytes(int B);
+int islam_dense_ba_depth_var_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                 const double* rgb2imu_or_null, const double* intr4, const double* prior_weight,
+                                 const float* prior_scale_or_null, const double* inv_depth, const double* sums,
+                                 const int* status_or_null, int robust_kind, double robust_delta, int mode, const double* grad_var,
+                                 double* grad_inv_depth, float* grad_flow, double* grad_motion, int* out_status, void* scratch, int B,
+                                 int H, int W, void* stream);
+
 /* The gradient of the joint refinement with the exact (Newton) Hessian and per-pixel prior weights.  The
  * adjoint system of islam_dense_ba_ift_weights / islam_dense_ba_vjp above, with the Gauss-Newton blocks replaced by one half of the
  * Hessian of the cost in the same per-pixel elimination; all fp64.  The state is what islam_dense_ba_refine(_map) returned: T*, rho*;

@@ -133,6 +133,8 @@ SIGNATURES = {
     'islam_dense_ba_depth_var': (c_int, [c_void_p] * 11 + [c_int, c_double, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     'islam_depth_propagate_scratch_bytes': (c_size_t, [c_int] * 3),
     'islam_depth_propagate': (c_int, [c_void_p] * 10 + [c_double] + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    'islam_dense_ba_depth_var_vjp_scratch_bytes': (c_size_t, [c_int]),
+    'islam_dense_ba_depth_var_vjp': (c_int, [c_void_p] * 11 + [c_int, c_double, c_int] + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     'islam_depth_propagate_vjp_scratch_bytes': (c_size_t, [c_int]),
     'islam_depth_propagate_vjp': (c_int, [c_void_p] * 19 + [c_int] * 3 + [c_void_p]),
     'islam_depth_regularize_scratch_bytes': (c_size_t, [c_int] * 3),

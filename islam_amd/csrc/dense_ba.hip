@@ -17,7 +17,8 @@
 // joint_adj_vjp_kernel), and per-pixel prior weights with the posterior variance of the inverse depths
 // (ba_wmap_partial_kernel beside the partial kernel; depth_var_factor_kernel, depth_var_pixel_kernel; section 3.27).  At the end: the
 // same gradient with the exact (Newton) Hessian and per-pixel prior weights (ba_newton_partial_kernel, ba_newton_solve_kernel,
-// ba_newton_vjp_kernel; section 3.30).
+// ba_newton_vjp_kernel; section 3.30).  Between the two: the gradient of the posterior variance in the state (depth_var_adj_partial_kernel,
+// depth_var_vjp_kernel, depth_var_pose_kernel; section 3.32).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +28,7 @@
 #include "common.h"
 #include "dense_reproj_dev.h"
 #include "lie_dev.h"
+#include "lie_vjp_dev.h"
 
 using namespace islam;
 
@@ -663,6 +665,293 @@ extern "C" int islam_dense_ba_depth_var(const float* depth, const float* flow, c
     hipLaunchKernelGGL(depth_var_factor_kernel, dim3(B), dim3(64), 0, s, sums, prior_weight, status_or_null, marginal, sinv, out_status);
     hipLaunchKernelGGL(depth_var_pixel_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu, intr4, prior_weight,
                        prior_scale_or_null, inv_depth_or_null, sinv, out_status, out_var, H, W, robust_kind, robust_delta, marginal);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
+
+// ------------------------------------------------------------------ the gradient of the posterior variance
+// (the formulas: include/islam_hip.h, islam_dense_ba_depth_var_vjp.)  The total derivative of v in the state
+// (rho, motion, flow), S_cam being a function of the same state: with g_i the cotangent of v_i, a = J^T jd (h_cam = c a), k = |jd|^2,
+// q = a^T S^-1 a, G = -sum g_i y_i y_i^T / h_dd^2 (y = c S^-1 a) the cotangent of S_cam, n = a^T G a and tau = <G, J^T J>, everything is
+// the gradient of one scalar per valid pixel, phi = g (1 / h_dd + c^2 q / h_dd^2) + c tau - c^2 n / h_dd at fixed S^-1 and G.  The valid
+// set and the branch of the Huber kernel are the forward pass's.  depth_var_adj_partial_kernel reduces the 21 sums of G (marginal mode
+// only; one row per workgroup, plain stores), depth_var_vjp_kernel streams the gradients in rho and flow out and reduces the 12 sums of
+// the cotangent of (R, t) = T^-1, depth_var_pose_kernel chains those to the plain components of motion.
+namespace {
+
+// y = S x for a symmetric 6x6 held as its row-major upper triangle (in LDS: every lane reads the same address)
+ISLAM_DEV void symv6(const double* S, const double* x, double* y) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double v = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) v += S[r < c ? tri(r, c) : tri(c, r)] * x[c];
+        y[r] = v;
+    }
+}
+
+ISLAM_DEV double dot6(const double* x, const double* y) {
+    double v = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) v += x[q] * y[q];
+    return v;
+}
+
+// The pixel as depth_var_pixel_kernel takes it.  true: v_i is the valid row of the table (it depends on the state) and p holds its terms;
+// false: v_i is 1 / w_i or NaN, a constant of the state.
+ISLAM_DEV bool var_pixel(const M3<double>& R, const V3<double>& t, const LinkPixels& lp, const float* ms, const double* rp, double wb, int i,
+                         PixelIn& px, double& rho, BaPixel& p) {
+    px = pixel_in(lp, i);
+    bool prior = isfinite(px.z) && px.z > 0.0;
+    double w = wb;
+    if (ms) prior = map_prior(ms, i, wb, prior, w);
+    rho = rp[i];
+    if (!(prior && isfinite(rho) && rho > 0.0)) return false;
+    p = ba_pixel(R, t, rho, px, lp, w);
+    return p.p.valid;
+}
+
+// grid (NBLK, B) x 256, grid-stride (marginal mode).  partial (B, NBLK, 21): the workgroup's sums of -g y y^T / h_dd^2 over its valid
+// pixels, upper triangle.  A link whose status is set writes nothing: nobody reads its rows.
+__global__ __launch_bounds__(256) void depth_var_adj_partial_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                                     const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                                     const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                                     const double* __restrict__ prior_weight,
+                                                                     const float* __restrict__ prior_scale,
+                                                                     const double* __restrict__ inv_depth, const double* __restrict__ sinv,
+                                                                     const int* __restrict__ status, const double* __restrict__ grad_var,
+                                                                     double* __restrict__ partial, int H, int W, int kind, double delta) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const size_t off = (size_t)b * HW;
+    if (status[b] != ISLAM_DENSE_REPROJ_OK) return;
+    __shared__ double Tp[12], Si[21];
+    if (threadIdx.x == 0) pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + 21) Si[threadIdx.x - 64] = sinv[(size_t)b * 21 + threadIdx.x - 64];
+    __syncthreads();
+    const M3<double> R = m3_load(Tp);
+    const V3<double> t{Tp[9], Tp[10], Tp[11]};
+    const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
+    const double wb = prior_weight[b];
+    const float* ms = prior_scale ? prior_scale + off : nullptr;
+    const double* rp = inv_depth + off;
+    const double* gv = grad_var + off;
+    double acc[21] = {};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        PixelIn px;
+        BaPixel p;
+        double rho;
+        if (!var_pixel(R, t, lp, ms, rp, wb, i, px, rho, p)) continue;      // the cotangent is read at a valid pixel only: elsewhere it may be NaN
+        double a[6], y[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) a[q] = p.p.ju[q] * p.jdu + p.p.jv[q] * p.jdv;
+        symv6(Si, a, y);
+        const double ih = 1.0 / p.hdd;
+        const double coef = -(gv[i] * (p.p.c * ih) * (p.p.c * ih));
+        int k = 0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double yq = coef * y[q];
+#pragma unroll
+            for (int l = q; l < 6; ++l) acc[k++] += yq * y[l];
+        }
+    }
+    reduce_and_store_row<21>(acc, partial + ((size_t)b * NBLK + blockIdx.x) * 21, true, 0.0);
+}
+
+// grid (NBLK, B) x 256, grid-stride.  Per pixel: grad_inv_depth (one 8-byte store), grad_flow (two float stores); per workgroup one row
+// of 12 in partial (B, NBLK, 12): the sums of the cotangent of R (row-major, m ray^T with m the cotangent of R ray) and of t.  gpart: the
+// rows depth_var_adj_partial_kernel wrote, summed here in index order (marginal mode; conditional: G = 0 and S^-1 is not read).  A link
+// whose status is set gets zeros at every pixel and writes no row.
+__global__ __launch_bounds__(256) void depth_var_vjp_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                             const uint8_t* __restrict__ mask, const double* __restrict__ pose7,
+                                                             const double* __restrict__ rgb2imu, const double* __restrict__ intr4,
+                                                             const double* __restrict__ prior_weight, const float* __restrict__ prior_scale,
+                                                             const double* __restrict__ inv_depth, const double* __restrict__ sinv,
+                                                             const double* __restrict__ gpart, const int* __restrict__ status,
+                                                             const double* __restrict__ grad_var, double* __restrict__ grad_inv_depth,
+                                                             float* __restrict__ grad_flow, double* __restrict__ partial, int H, int W,
+                                                             int kind, double delta, int marginal) {
+    const int b = blockIdx.y;
+    const int HW = H * W;
+    const size_t off = (size_t)b * HW;
+    double* grho = grad_inv_depth + off;
+    float* gfu = grad_flow + 2 * off;
+    float* gfv = gfu + HW;
+    if (status[b] != ISLAM_DENSE_REPROJ_OK) {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+            grho[i] = 0.0;
+            gfu[i] = gfv[i] = 0.0f;
+        }
+        return;
+    }
+    __shared__ double Tp[12], Si[21], Gb[21];
+    if (threadIdx.x == 0) pose_to_lds(camera_inverse(pose7 + 7 * b, rgb2imu), Tp);
+    if (marginal && threadIdx.x >= 64 && threadIdx.x < 64 + 21) Si[threadIdx.x - 64] = sinv[(size_t)b * 21 + threadIdx.x - 64];
+    if (marginal && threadIdx.x >= 128 && threadIdx.x < 128 + 21) {
+        double v = 0.0;
+        for (int k = 0; k < NBLK; ++k) v += gpart[((size_t)b * NBLK + k) * 21 + threadIdx.x - 128];
+        Gb[threadIdx.x - 128] = v;
+    }
+    __syncthreads();
+    const M3<double> R = m3_load(Tp);
+    const V3<double> t{Tp[9], Tp[10], Tp[11]};
+    const LinkPixels lp = link_pixels(depth, flow, mask, intr4, b, HW, W, kind, delta);
+    const double wb = prior_weight[b];
+    const float* ms = prior_scale ? prior_scale + off : nullptr;
+    const double* rp = inv_depth + off;
+    const double* gv = grad_var + off;
+    double acc[12] = {};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += NBLK * 256) {
+        PixelIn px;
+        BaPixel p;
+        double rho;
+        double g_rho = 0.0, g_fu = 0.0, g_fv = 0.0;      // exact zeros where v is a constant of the state or NaN
+        if (var_pixel(R, t, lp, ms, rp, wb, i, px, rho, p)) {
+            const double g = gv[i];
+            const double* ju = p.p.ju;
+            const double* jv = p.p.jv;
+            const double c = p.p.c, jdu = p.jdu, jdv = p.jdv;
+            const double ih = 1.0 / p.hdd, ih2 = ih * ih, c2 = c * c;
+            const double kk = jdu * jdu + jdv * jdv;
+            // phi and its partials; in conditional mode q = n = tau = 0 and the cotangent of a vanishes
+            double ab[6] = {}, Gu[6] = {}, Gv[6] = {};
+            double qq = 0.0, n = 0.0, tau = 0.0;
+            if (marginal) {
+                double a[6], Sa[6], Ga[6];
+#pragma unroll
+                for (int q = 0; q < 6; ++q) a[q] = ju[q] * jdu + jv[q] * jdv;
+                symv6(Si, a, Sa);
+                symv6(Gb, ju, Gu);
+                symv6(Gb, jv, Gv);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) Ga[q] = jdu * Gu[q] + jdv * Gv[q];
+                qq = dot6(a, Sa);
+                n = dot6(a, Ga);
+                tau = dot6(ju, Gu) + dot6(jv, Gv);
+                const double pq = g * c2 * ih2, pn = -(c2 * ih);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) ab[q] = 2.0 * (pq * Sa[q] + pn * Ga[q]);
+            }
+            const double ph = c2 * n * ih2 - g * ih2 - 2.0 * g * c2 * qq * (ih2 * ih);
+            const double pc = 2.0 * g * c * qq * ih2 + tau - 2.0 * c * n * ih + kk * ph;
+            const double pk = c * ph;
+            // the cotangents of the rows of J_cam and of jd
+            double Ju[6], Jv[6];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                Ju[q] = jdu * ab[q] + 2.0 * c * Gu[q];
+                Jv[q] = jdv * ab[q] + 2.0 * c * Gv[q];
+            }
+            const double bju = dot6(ju, ab) + 2.0 * pk * jdu, bjv = dot6(jv, ab) + 2.0 * pk * jdv;
+            // through J = J_q [-I, [Q]x], jd = J_q d and c(s) to the cotangents of J_q = [[a, 0, bq], [0, cq, dq]], Q, d and r
+            const V3<double> m = R * V3<double>{px.xh, px.yh, 1.0};      // dQ/d(1/rho); d = -m / rho^2
+            const double zi = 1.0 / rho, k2 = -(zi * zi);
+            const V3<double> d{m.x * k2, m.y * k2, m.z * k2};
+            const V3<double> Q = p.p.Q;
+            const double fa = p.p.a, fb = p.p.bq, fc = p.p.cq, fd = p.p.dq, iz = p.p.iz;
+            const double ba = bju * d.x - Ju[0] - Ju[4] * Q.z + Ju[5] * Q.y;
+            const double bb = bju * d.z - Ju[2] - Ju[3] * Q.y + Ju[4] * Q.x;
+            const double bc = bjv * d.y - Jv[1] + Jv[3] * Q.z - Jv[5] * Q.x;
+            const double bd = bjv * d.z - Jv[2] - Jv[3] * Q.y + Jv[4] * Q.x;
+            const double bru = 2.0 * p.p.cp * pc * p.p.ru, brv = 2.0 * p.p.cp * pc * p.p.rv;
+            const V3<double> bQ{Ju[4] * fb + Jv[4] * fd - Jv[5] * fc + fa * bru - fa * iz * bb,
+                                Ju[5] * fa - Ju[3] * fb - Jv[3] * fd + fc * brv - fc * iz * bd,
+                                Jv[3] * fc - Ju[4] * fa + fb * bru + fd * brv - iz * (fa * ba + 2.0 * fb * bb + fc * bc + 2.0 * fd * bd)};
+            const V3<double> bd3{bju * fa, bjv * fc, bju * fb + bjv * fd};
+            // Q = m / rho + t, d = -m / rho^2
+            const V3<double> bm{zi * bQ.x + k2 * bd3.x, zi * bQ.y + k2 * bd3.y, zi * bQ.z + k2 * bd3.z};
+            g_rho = k2 * dot(bQ, m) + 2.0 * (zi * zi * zi) * dot(bd3, m);
+            g_fu = -bru;
+            g_fv = -brv;
+            acc[0] += bm.x * px.xh; acc[1] += bm.x * px.yh; acc[2] += bm.x;
+            acc[3] += bm.y * px.xh; acc[4] += bm.y * px.yh; acc[5] += bm.y;
+            acc[6] += bm.z * px.xh; acc[7] += bm.z * px.yh; acc[8] += bm.z;
+            acc[9] += bQ.x; acc[10] += bQ.y; acc[11] += bQ.z;
+        }
+        grho[i] = g_rho;
+        gfu[i] = (float)g_fu;
+        gfv[i] = (float)g_fv;
+    }
+    reduce_and_store_row<12>(acc, partial + ((size_t)b * NBLK + blockIdx.x) * 12, true, 0.0);
+}
+
+// grid (B) x 64.  The NBLK rows of a link are summed in index order; lane 0 chains the cotangent of (R, t) = T^-1 back through qmat, the
+// inverse and the mount conjugation of camera_inverse to the plain components [t, q xyzw] of motion[b] (no unit-norm assumption, the
+// convention of section 3.31).  A link with a status gets seven zeros.
+__global__ __launch_bounds__(64) void depth_var_pose_kernel(const double* __restrict__ partial, const double* __restrict__ motion,
+                                                             const double* __restrict__ rgb2imu, const int* __restrict__ status,
+                                                             double* __restrict__ grad_motion) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    const bool live = status[b] == ISLAM_DENSE_REPROJ_OK;
+    __shared__ double s[12];
+    if (live && i < 12) {
+        double v = 0.0;
+        for (int k = 0; k < NBLK; ++k) v += partial[((size_t)b * NBLK + k) * 12 + i];
+        s[i] = v;
+    }
+    __syncthreads();
+    if (i != 0) return;
+    double* gm = grad_motion + (size_t)b * 7;
+    if (!live) {
+        for (int k = 0; k < 7; ++k) gm[k] = 0.0;
+        return;
+    }
+    camera_inverse_vjp(motion + 7 * b, rgb2imu, s, v3(s[9], s[10], s[11]), gm);
+}
+
+// the scratch of islam_dense_ba_depth_var_vjp: S_cam^-1 (B,21), the rows of G (B,NBLK,21), the rows of the pose sums (B,NBLK,12)
+struct VarGradScratch {
+    double *sinv, *gpart, *ppart;
+    size_t bytes;
+};
+
+VarGradScratch var_grad_scratch(void* base, int B) {
+    VarGradScratch vs{};
+    auto carve = [&](double*& p, size_t count) {
+        p = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(base) + vs.bytes);
+        vs.bytes += align_up(count * sizeof(double));
+    };
+    carve(vs.sinv, (size_t)B * 21);
+    carve(vs.gpart, (size_t)B * NBLK * 21);
+    carve(vs.ppart, (size_t)B * NBLK * 12);
+    return vs;
+}
+
+}  // namespace
+
+extern "C" size_t islam_dense_ba_depth_var_vjp_scratch_bytes(int B) {
+    if (B < 1) return 0;
+    return var_grad_scratch(nullptr, B).bytes;
+}
+
+extern "C" int islam_dense_ba_depth_var_vjp(const float* depth, const float* flow, const uint8_t* mask, const double* motion,
+                                            const double* rgb2imu_or_null, const double* intr4, const double* prior_weight,
+                                            const float* prior_scale_or_null, const double* inv_depth, const double* sums,
+                                            const int* status_or_null, int robust_kind, double robust_delta, int mode, const double* grad_var,
+                                            double* grad_inv_depth, float* grad_flow, double* grad_motion, int* out_status, void* scratch, int B,
+                                            int H, int W, void* stream) {
+    const char* who = "islam_dense_ba_depth_var_vjp";
+    if (int rc = check_shape_kind(who, B, H, W, robust_kind, robust_delta)) return rc;
+    if (mode != 0 && mode != 1) return fail(ISLAM_EARG, "%s: mode must be 0 (marginal) or 1 (conditional), got %d", who, mode);
+    if (!depth || !flow || !motion || !intr4) return fail(ISLAM_EARG, "%s: NULL depth / flow / motion / intr4 pointer", who);
+    if (!prior_weight) return fail(ISLAM_EARG, "%s: NULL prior_weight", who);
+    if (!inv_depth || !sums || !grad_var) return fail(ISLAM_EARG, "%s: NULL inv_depth / sums / grad_var pointer", who);
+    if (!grad_inv_depth || !grad_flow || !grad_motion || !out_status || !scratch)
+        return fail(ISLAM_EARG, "%s: NULL grad_inv_depth / grad_flow / grad_motion / out_status / scratch pointer", who);
+    hipStream_t s = as_stream(stream);
+    const VarGradScratch vs = var_grad_scratch(scratch, B);
+    const int marginal = mode == 0;
+    // the forward call's first launch on the same sums: the same S_cam^-1 and status, bit for bit, so nothing has to be saved
+    hipLaunchKernelGGL(depth_var_factor_kernel, dim3(B), dim3(64), 0, s, sums, prior_weight, status_or_null, marginal, vs.sinv, out_status);
+    if (marginal)
+        hipLaunchKernelGGL(depth_var_adj_partial_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu_or_null, intr4,
+                           prior_weight, prior_scale_or_null, inv_depth, vs.sinv, out_status, grad_var, vs.gpart, H, W, robust_kind,
+                           robust_delta);
+    hipLaunchKernelGGL(depth_var_vjp_kernel, dim3(NBLK, B), dim3(256), 0, s, depth, flow, mask, motion, rgb2imu_or_null, intr4, prior_weight,
+                       prior_scale_or_null, inv_depth, vs.sinv, vs.gpart, out_status, grad_var, grad_inv_depth, grad_flow, vs.ppart, H, W,
+                       robust_kind, robust_delta, marginal);
+    hipLaunchKernelGGL(depth_var_pose_kernel, dim3(B), dim3(64), 0, s, vs.ppart, motion, rgb2imu_or_null, out_status, grad_motion);
     ISLAM_LAUNCH_CHECK();
     return ISLAM_OK;
 }

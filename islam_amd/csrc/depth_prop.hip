@@ -26,6 +26,7 @@
 #include "common.h"
 #include "dense_reproj_dev.h"
 #include "lie_dev.h"
+#include "lie_vjp_dev.h"
 
 using namespace islam;
 
@@ -531,27 +532,6 @@ __global__ __launch_bounds__(256) void depth_prop_vjp_kernel(const double* __res
     }
     reduce_and_store_row<4>(acc, partials + ((size_t)b * NBLK + blockIdx.x) * 4, true, 0.0);
 }
-
-// the cotangents of q and p in r = qact(q, p) = p + q.w uv + u x uv, uv = 2 u x p, from the cotangent g of r
-ISLAM_DEV void qact_vjp(Q4<double> q, V3<double> p, V3<double> g, Q4<double>& gq, V3<double>& gp) {
-    const V3<double> u{q.x, q.y, q.z};
-    const V3<double> uv = 2.0 * cross(u, p);
-    const V3<double> guv = q.w * g + cross(g, u);
-    const V3<double> gu = cross(uv, g) + 2.0 * cross(p, guv);
-    gq = {gu.x, gu.y, gu.z, dot(g, uv)};
-    gp = g + 2.0 * cross(guv, u);
-}
-
-// the cotangents of a and b in qmul(a, b) from the cotangent g of the product
-ISLAM_DEV Q4<double> qmul_vjp_a(Q4<double> g, Q4<double> b) {
-    return {g.x * b.w - g.y * b.z + g.z * b.y - g.w * b.x, g.x * b.z + g.y * b.w - g.z * b.x - g.w * b.y,
-            -g.x * b.y + g.y * b.x + g.z * b.w - g.w * b.z, g.x * b.x + g.y * b.y + g.z * b.z + g.w * b.w};
-}
-ISLAM_DEV Q4<double> qmul_vjp_b(Q4<double> a, Q4<double> g) {
-    return {g.x * a.w + g.y * a.z - g.z * a.y - g.w * a.x, -g.x * a.z + g.y * a.w + g.z * a.x - g.w * a.y,
-            g.x * a.y - g.y * a.x + g.z * a.w - g.w * a.z, g.x * a.x + g.y * a.y + g.z * a.z + g.w * a.w};
-}
-ISLAM_DEV Q4<double> operator+(Q4<double> a, Q4<double> b) { return {a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
 
 // grid (B) x 64.  The NBLK rows of a link are summed in index order; lane 0 chains the cotangent of (R20, R21, R22, t_z) back through
 // qmat, the inverse and the mount conjugation of camera_inverse to the plain components [t, q xyzw] of motion[b], every product taken

@@ -16,7 +16,8 @@
     (section 3.27); ``propagate`` carries both into the next frame's pixel grid and fuses them with that frame's own depth map, the
     prior of the next link (csrc/depth_prop.hip, section 3.28), with ``regularize=DepthRegularizer(...)`` after occlusion removal,
     hole filling and smoothing of the propagated map (section 3.29); ``propagate(differentiable=True)`` lets a loss behind the next
-    link's refinement reach this link's state, pose and measurement (section 3.31);
+    link's refinement reach this link's state, pose and measurement (section 3.31), and ``depth_uncertainty(differentiable=True)``
+    lets a loss on the variance, or behind the propagation's variance input, reach the state, the pose and the flow (section 3.32);
   * pixel2point / proj / is_inside_image helpers with the reference's semantics;
   * sample_keypoints: device-side choice of ``n`` masked pixels per frame (the reference only declares
     ``--reproj-points``, arguments.py:62; no sampler ships with it).
@@ -314,15 +315,37 @@ class DenseReprojectionLoss:
         depth = torch.where(ok, (1.0 / torch.where(ok, out.inv_depth, torch.ones_like(out.inv_depth))).to(self.z.dtype), self.z.detach())
         return DenseBAJoint(*out, depth)
 
-    def depth_uncertainty(self, joint, sigma_inv_depth, sigma_px=1.0, kernel=None, marginal=True):
+    def depth_uncertainty(self, joint, sigma_inv_depth, sigma_px=1.0, kernel=None, marginal=True, differentiable=False):
         """The posterior uncertainty of the depths a ``refine_joint`` returned (``joint``: its result; motion, inv_depth, sums and status
         are used), in the Gauss-Newton approximation at that state (ops.dense_ba_depth_variance).
         ``sigma_inv_depth``, ``sigma_px`` and ``kernel`` must be the ones the refinement was given.  marginal=True: the pose is uncertain
         too (marginal over it); False: the pose taken as known.  Returns DenseBADepthUncertainty, (B,H,W) float64 on the device:
         var_inv_depth = sigma_px^2 v, sigma_inv_depth = its square root (a valid per-pixel prior for a next refinement), sigma_depth =
-        sigma_inv_depth / inv_depth^2 (first order), all NaN where the pixel has no usable prior or the link's ``status`` (B) is set."""
+        sigma_inv_depth / inv_depth^2 (first order), all NaN where the pixel has no usable prior or the link's ``status`` (B) is set.
+
+        differentiable=False (the default): no gradient is attached.  differentiable=True: the same launches and the same bits, and
+        ``var_inv_depth`` carries a grad_fn over ``joint.inv_depth``, ``joint.motion`` and the stored flow (the tensor given to the
+        constructor keeps its graph); ``sigma_inv_depth`` and ``sigma_depth`` are formed from it in torch as on the default path, so
+        they carry the graph too, ``sigma_depth`` also through ``joint.inv_depth`` itself.  A loss on the uncertainty (a Gaussian
+        negative log-likelihood, say) or on what ``propagate(differentiable=True)`` makes of it then reaches the refinement and the
+        networks behind it (ops._DenseBADepthVariance, ops.dense_ba_depth_variance_vjp, at most four launches; DESIGN.md section
+        3.32).  The gradient is the total derivative in that state: S_cam, which ``joint.sums`` holds, is taken as the function of
+        the same pose, inverse depths and flow that it is, and ``joint.sums`` must be the sums at the state (``refine_joint`` returns
+        them so).  Held fixed, as the forward pass found them: which pixels are valid at the state and which have a usable prior, and
+        the branch of the Huber kernel.  No gradient goes to ``sigma_inv_depth`` and ``sigma_px`` (the prior weights), the intrinsics,
+        the mount, the mask or the stored depth, which enters only through "has a prior".  A pixel whose variance is 1 / w_i (a prior,
+        invalid at the state) or NaN gets an exactly zero gradient, the NaN that torch.sqrt's backward forms there never reaches one,
+        and a link whose status is set gets zeros."""
         from . import ops
         w, m = self._prior_weight(sigma_inv_depth, sigma_px, 'depth_uncertainty')
+        if differentiable:
+            mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
+            out = ops.DenseBADepthVar(*ops._DenseBADepthVariance.apply(
+                self.z, self.flow, self.mask, joint.motion, torch.tensor(self.K4, dtype=torch.float64), w, joint.inv_depth, joint.sums,
+                joint.status, m, mount, kernel, marginal))
+            var = float(sigma_px) ** 2 * out.var
+            sig = torch.sqrt(var)
+            return DenseBADepthUncertainty(var, sig, sig / (joint.inv_depth * joint.inv_depth), out.status)
         out = ops.dense_ba_depth_variance(self.z, self.flow, self.mask, joint.motion, torch.tensor(self.K4, dtype=torch.float64), w,
                                           inv_depth=joint.inv_depth, sums=joint.sums, status=joint.status, prior_scale=m,
                                           rgb2imu=self.rgb2imu_pose, kernel=kernel, marginal=marginal)

@@ -381,6 +381,73 @@ def dense_ba_depth_variance(depth, flow, mask, motion, intr, prior_weight, inv_d
     return DenseBADepthVar(var, out)
 
 
+DenseBADepthVarGrad = collections.namedtuple('DenseBADepthVarGrad', 'grad_inv_depth grad_flow grad_motion status')
+
+
+def dense_ba_depth_variance_vjp(depth, flow, mask, motion, intr, prior_weight, inv_depth, sums, grad_var, status=None, prior_scale=None,
+                                rgb2imu=None, kernel=None, marginal=True):
+    """The vector-Jacobian product of dense_ba_depth_variance: the total derivative of v in the state (inv_depth, motion, flow), S_cam
+    being a function of that same state (include/islam_hip.h, islam_dense_ba_depth_var_vjp).  Arguments as the
+    forward call was given them, with inv_depth (B,H,W) and sums (B,30) (the sums at the state) required; grad_var (B,H,W): the
+    cotangent of var, read only at the pixels that are valid at the state (it may be NaN where var is NaN).  The valid set and the
+    branch of the Huber kernel are held fixed; prior_weight, prior_scale, intr, rgb2imu, the mask and the stored depth get no
+    gradient.  Returns DenseBADepthVarGrad(grad_inv_depth (B,H,W) float64, grad_flow (B,2,H,W) float32, grad_motion (B,7) float64 on the
+    plain components [t, q xyzw] (the convention of dense_ba_depth_propagate_vjp), status (B) int32 as the forward call forms it).  A
+    pixel whose var is 1/w_i or NaN gets exact zeros, and so does every output of a link whose status is not 0.  At most four launches,
+    nothing is read back."""
+    who = 'dense_ba_depth_variance_vjp'
+    a = _dense_reproj_args(depth, flow, mask, motion, intr, rgb2imu, kernel)
+    w = _dense_ba_prior_weight(prior_weight, a.B, a.dev)
+    m = _dense_ba_prior_scale(prior_scale, a, who)
+    if inv_depth is None or sums is None or grad_var is None:
+        raise ValueError('%s: inv_depth, sums and grad_var are required' % who)
+    require_cuda(inv_depth, grad_var)
+    inv_depth = _dense_ba_state(inv_depth, a, who)
+    grad_var = _dense_ba_state(grad_var, a, who, 'grad_var')
+    sums = torch.as_tensor(sums).detach().to(a.dev, torch.float64).contiguous()
+    if tuple(sums.shape) != (a.B, _lib.DENSE_REPROJ_NSUM):
+        raise ValueError('%s: sums must be (%d,%d), got %s' % (who, a.B, _lib.DENSE_REPROJ_NSUM, tuple(sums.shape)))
+    status = _dense_reproj_status(status, a.B, a.dev)
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=a.dev)
+    out = DenseBADepthVarGrad(e(torch.float64, a.B, a.H, a.W), e(torch.float32, a.B, 2, a.H, a.W), e(torch.float64, a.B, 7), e(torch.int32, a.B))
+    scratch = torch.empty(lib().islam_dense_ba_depth_var_vjp_scratch_bytes(a.B), dtype=torch.uint8, device=a.dev)
+    check(lib().islam_dense_ba_depth_var_vjp(*a.head(), ptr(w), ptr(m), ptr(inv_depth), ptr(sums), ptr(status), a.kind, a.delta,
+                                             0 if marginal else 1, ptr(grad_var), ptr(out.grad_inv_depth), ptr(out.grad_flow),
+                                             ptr(out.grad_motion), ptr(out.status), ptr(scratch), a.B, a.H, a.W, stream_ptr(a.dev)))
+    return out
+
+
+class _DenseBADepthVariance(torch.autograd.Function):
+    """dense_ba_depth_variance whose var output carries the total derivative of the variance in flow, motion and inv_depth (DESIGN.md
+    section 3.32): forward is that call (the same launches, the same bits), backward is dense_ba_depth_variance_vjp on the same tensors,
+    and nothing else.  sums is the state's own function and gets no gradient of its own; depth, the mask, the intrinsics, the prior
+    weight and map and the mount get none either."""
+
+    @staticmethod
+    def forward(ctx, depth, flow, mask, motion, intr, prior_weight, inv_depth, sums, status, prior_scale, rgb2imu, kernel, marginal):
+        out = dense_ba_depth_variance(depth, flow, mask, motion, intr, prior_weight, inv_depth=inv_depth, sums=sums, status=status,
+                                      prior_scale=prior_scale, rgb2imu=rgb2imu, kernel=kernel, marginal=marginal)
+        ctx.save_for_backward(depth, flow, mask, motion, intr, inv_depth, sums, status, prior_scale, rgb2imu,
+                              prior_weight if torch.is_tensor(prior_weight) else None)
+        ctx.prior_weight = None if torch.is_tensor(prior_weight) else prior_weight
+        ctx.kernel, ctx.marginal = kernel, marginal
+        ctx.dtypes = (flow.dtype, motion.dtype, inv_depth.dtype)
+        ctx.mark_non_differentiable(out.status)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_var, *unused):
+        need = ctx.needs_input_grad
+        if grad_var is None or not (need[1] or need[3] or need[6]):
+            return (None,) * 13
+        depth, flow, mask, motion, intr, inv_depth, sums, status, prior_scale, rgb2imu, w = ctx.saved_tensors
+        g = dense_ba_depth_variance_vjp(depth, flow, mask, motion, intr, ctx.prior_weight if w is None else w, inv_depth, sums, grad_var,
+                                        status=status, prior_scale=prior_scale, rgb2imu=rgb2imu, kernel=ctx.kernel, marginal=ctx.marginal)
+        d = ctx.dtypes
+        return (None, g.grad_flow.to(d[0]) if need[1] else None, None, g.grad_motion.to(d[1]) if need[3] else None, None, None,
+                g.grad_inv_depth.to(d[2]) if need[6] else None, None, None, None, None, None, None)
+
+
 def _dense_reproj_status(status, B, dev):
     if status is None:
         return None

@@ -57,6 +57,12 @@ alone, and the propagation followed by it.  The yardstick is the forward ops.den
 process.
 
     python scripts/dense_reproj_bench.py --propagate-grad [--case 448x640] [--out profiles/depth_propagate_grad_bench.json]
+
+--uncertainty-grad times the gradient of the posterior variance instead: ops.dense_ba_depth_variance_vjp at
+the refined state of --uncertainty's scene (weight map included) with the sums given, marginal over the pose and conditional on it.
+The yardstick is the forward ops.dense_ba_depth_variance on the same tensors in the same process.
+
+    python scripts/dense_reproj_bench.py --uncertainty-grad [--case 448x640] [--out profiles/dense_ba_uncertainty_grad_bench.json]
 """
 import json
 import os
@@ -803,8 +809,71 @@ def main_propagate_grad(argv):
         f.write(line + '\n')
 
 
+# the nominal bytes of one pixel in ops.dense_ba_depth_variance_vjp: per pixel pass the 25 that the variance pass reads (depth, flow, mask,
+# map, rho) and the cotangent (8); the marginal mode makes two such passes (the sums of G, then the gradients), and the second stores
+# grad_inv_depth (8) and grad_flow (8)
+VAR_GRAD_PIXEL_BYTES = {True: 2 * 33 + 16, False: 33 + 16}
+
+
+def run_uncertainty_grad_case(H, W):
+    """--uncertainty-grad: the cost of the gradient of the variance beside the variance pass itself."""
+    import numpy as np
+    import torch
+    from islam_amd import ops
+    from tests.dense_reproj_f64 import MOUNT, PRIOR_W, make_scene, noisy_prior, right_perturb
+    dev = torch.device('cuda:0')
+    sc = noisy_prior(make_scene(B, H, W, seed=1, noise=0.3, intr0=(0.5 * W, 0.5 * W, 0.5 * W - 0.5, 0.5 * H - 0.5), vary=False), seed=2)
+    start = right_perturb(sc['motion'], [0.01, -0.008, 0.012, 0.006, -0.005, 0.007])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    depth, flow, mask, motion, intr, mount = d(sc['depth']), d(sc['flow']), d(sc['mask']), d(start), d(sc['intr']), d(MOUNT)
+    w = torch.full((B,), PRIOR_W, dtype=torch.float64, device=dev)
+    m = d(np.exp2(np.random.default_rng(3).uniform(-1.0, 1.0, (B, H, W))).astype(np.float32))
+    ref = ops.dense_ba_refine(depth, flow, mask, motion, intr, w, rgb2imu=mount, iters=20, prior_scale=m)
+    state = (depth, flow, mask, ref.motion, intr, w)
+    g = torch.randn((B, H, W), dtype=torch.float64, device=dev, generator=torch.Generator(device='cuda').manual_seed(5))
+    var = lambda marginal: ops.dense_ba_depth_variance(*state, inv_depth=ref.inv_depth, sums=ref.sums, status=ref.status, prior_scale=m, rgb2imu=mount,
+                                                       marginal=marginal)
+    vjp = lambda marginal: ops.dense_ba_depth_variance_vjp(*state, ref.inv_depth, ref.sums, g, status=ref.status, prior_scale=m, rgb2imu=mount,
+                                                           marginal=marginal)
+    out = timed({'depth_var_marginal': lambda: var(True), 'depth_var_conditional': lambda: var(False), 'vjp_marginal': lambda: vjp(True),
+                 'vjp_conditional': lambda: vjp(False), 'var_then_vjp_marginal': lambda: (var(True), vjp(True))})
+    r = vjp(True)
+    out['status_ok'] = int((r.status == 0).sum())
+    out['nonzero_grad_fraction'] = float((r.grad_inv_depth != 0).double().mean())
+    out['finite'] = int(all(bool(torch.isfinite(t.double()).all()) for t in r[:3]))
+    out['vjp_over_var_marginal'] = out['vjp_marginal'] / out['depth_var_marginal']
+    out['vjp_over_var_conditional'] = out['vjp_conditional'] / out['depth_var_conditional']
+    for marginal, name in ((True, 'marginal'), (False, 'conditional')):
+        out['MB_moved_vjp_' + name] = VAR_GRAD_PIXEL_BYTES[marginal] * B * H * W / 1e6
+        out['hbm_frac_vjp_' + name] = VAR_GRAD_PIXEL_BYTES[marginal] * B * H * W / (out['vjp_' + name] * 1e-6) / 1e9 / HBM_GBS
+    return out
+
+
+def main_uncertainty_grad(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_uncertainty_grad_case(*hw) for case, hw in cases.items()}
+    cols = ('depth_var_marginal', 'depth_var_conditional', 'vjp_marginal', 'vjp_conditional', 'var_then_vjp_marginal', 'vjp_over_var_marginal',
+            'vjp_over_var_conditional', 'MB_moved_vjp_marginal', 'hbm_frac_vjp_marginal', 'MB_moved_vjp_conditional', 'hbm_frac_vjp_conditional',
+            'status_ok', 'nonzero_grad_fraction', 'finite')
+    print('us per call at B = %d: the median of 30; hbm_frac_vjp: %d (marginal) / %d (conditional) bytes per pixel over the time, of %.0f GB/s' % (
+        B, VAR_GRAD_PIXEL_BYTES[True], VAR_GRAD_PIXEL_BYTES[False], HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'dense_ba_uncertainty_grad_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 def main():
     import torch
+    if '--uncertainty-grad' in sys.argv[1:]:
+        return main_uncertainty_grad(sys.argv[1:])
     if '--propagate-grad' in sys.argv[1:]:
         return main_propagate_grad(sys.argv[1:])
     if '--regularize' in sys.argv[1:]:
