@@ -775,6 +775,41 @@ int islam_depth_regularize(const double* inv_depth, const double* var_inv_depth,
                            double reg_gate, double* out_inv_depth, double* out_var, float* out_depth, int* out_source,
                            uint8_t* out_flags, int* out_status, void* scratch, int B, int H, int W, void* stream);
 
+/* The vector-Jacobian product of islam_depth_regularize, on the piece its forward pass chose, in fp64.  Held
+ * fixed (piecewise constant, no derivative): valid0 and every compat decision; the removed set of stage 1; for each filled hole j its
+ * anchor a_j, its cluster C_j and n_j = |C_j|; the filled set; each pixel's smoothing set N3(j) (the valid2 k of the window with
+ * compat(k,j) on stage-2 values, j included); the row of the fusion table and the gate decision.  dist_var, gate, the stage arguments
+ * and the prior weights get no gradient.  The sets are recomputed from inv_depth, var_inv_depth and the stage arguments with the
+ * forward's own device functions; the row of the fusion table is read from flags (the forward call's out_flags).  With (g_rho, g_s)
+ * the cotangents of out_inv_depth and out_var, read only where (flags & 3) != 0 (elsewhere they may be NaN), NULL meaning zero:
+ *   4. fusion: the table of islam_depth_propagate_vjp on (rho3_j, s2_j, measurement) gives g3rho_j, g3s_j and grad_depth_next,
+ *      grad_var_next (float32, one rounding each, drho_m/ddepth_next = -rho_m^2).
+ *   3. smoothing: rho3_j = (sum_{k in N3(j)} w_kj rho2_k) / S_j, w_kj = 1 / (s2_k + dist_var (du^2 + dv^2)), S_j = sum w_kj, s passes
+ *      through.  For a valid2 k, over the valid2 j of k's window with compat(k,j) (compat is symmetric on the same bits):
+ *        g2rho_k = sum_j g3rho_j w_kj / S_j,   g2s_k = g3s_k - sum_j g3rho_j w_kj^2 (rho2_k - rho3_j) / S_j;   smooth_radius 0: g2 = g3.
+ *   2. filling: at a filled j, w_k = 1 / s_k, S = sum_{C_j} w_k, e_k = rho_k - rho2_j, f = fill_inflate, s2_j = f (n_j + sum w_k e_k^2) / S:
+ *        drho2_j/drho_k = w_k / S,          drho2_j/ds_k = -w_k^2 e_k / S,
+ *        ds2_j/drho_k = 2 f w_k e_k / S,    ds2_j/ds_k = w_k^2 (s2_j - f e_k^2) / S
+ *      (the terms through the mean inside the scatter carry sum w_k e_k = 0 and are dropped).  For a valid1 k: g1_k = g2_k plus the sum
+ *      of these over the filled j within fill_radius with compat(k, a_j);  fill_radius 0: g1 = g2 on valid1.
+ *   1. removal: grad_inv_depth_k = g1rho_k, grad_var_inv_depth_k = g1s_k at valid1 pixels, exact zeros at every other pixel (holes,
+ *      removed pixels whether refilled or not, inputs that are not finite or not positive).
+ * A link with a status (status_or_null's entry not 0, or dist_var[b] negative or not finite) gets exact zeros on both state gradients;
+ * its measurement rows still pass their gradient (the "measured only" row).  All outputs are written in full by plain stores, every sum
+ * is one thread's over a window in row-major order: no atomics, no memset, a repeat gives the same bits.  scratch:
+ * islam_depth_regularize_vjp_scratch_bytes(B, H, W) bytes (eleven float64 maps and one byte map between the kernels).  At most three
+ * launches on `stream`, no host wait: depth_reg_front_kernel (stages 1-3 recomputed on the forward's tile, the fusion table
+ * differentiated), depth_reg_smooth_adj_kernel (stage 3; left out for smooth_radius 0) and depth_reg_fill_adj_kernel (stages 2 and 1,
+ * the final stores).  ISLAM_EARG before any device work under the rules of islam_depth_regularize, for a NULL flags, output or scratch
+ * pointer, grad_depth_next without grad_var_next or the reverse, and a measurement gradient without a measurement. */
+size_t islam_depth_regularize_vjp_scratch_bytes(int B, int H, int W);
+int islam_depth_regularize_vjp(const double* inv_depth, const double* var_inv_depth, const int* status_or_null, const double* dist_var,
+                               const float* depth_next_or_null, const float* var_next_or_null, double gate, int occl_radius,
+                               int occl_min, int fill_radius, int fill_min, double fill_inflate, int smooth_radius, double reg_gate,
+                               const uint8_t* flags, const double* grad_out_inv_depth_or_null, const double* grad_out_var_or_null,
+                               double* grad_inv_depth, double* grad_var_inv_depth, float* grad_depth_next_or_null,
+                               float* grad_var_next_or_null, void* scratch, int B, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- IMU pre-integration */
 
 /* Replaces the frame loop of imu_integrator.py:116-158 and pp.module.IMUPreintegrator.forward

@@ -140,6 +140,9 @@ SIGNATURES = {
     'islam_depth_regularize_scratch_bytes': (c_size_t, [c_int] * 3),
     'islam_depth_regularize': (c_int, [c_void_p] * 7 + [c_double] + [c_int] * 4 + [c_double, c_int, c_double] + [c_void_p] * 7 + [c_int] * 3 +
                                [c_void_p]),
+    'islam_depth_regularize_vjp_scratch_bytes': (c_size_t, [c_int] * 3),
+    'islam_depth_regularize_vjp': (c_int, [c_void_p] * 6 + [c_double] + [c_int] * 4 + [c_double, c_int, c_double] + [c_void_p] * 8 + [c_int] * 3 +
+                                   [c_void_p]),
     'islam_imu_scratch_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'islam_imu_preint': (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int] + [c_void_p] * 3 + [c_double, c_int] +
                          [c_void_p] * 4 + [c_int, c_void_p]),

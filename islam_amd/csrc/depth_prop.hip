@@ -18,6 +18,10 @@
 // depth_prop_vjp_kernel and depth_prop_pose_kernel (islam_depth_propagate_vjp) are the vector-Jacobian product
 // of the propagation on the piece its forward pass chose: the target pixel, the z-buffer winner and the row of the fusion table are
 // read from out_source and out_flags, and the arithmetic of that piece is differentiated with plain stores and fixed-order sums.
+//
+// depth_reg_front_kernel, depth_reg_smooth_adj_kernel and depth_reg_fill_adj_kernel (islam_depth_regularize_vjp; DESIGN.md section
+// 3.33) are the vector-Jacobian product of the regularisation on the piece its forward pass chose: the stencil's decisions are
+// recomputed with the forward's own stage functions, and each stage's adjoint is a gather over its window.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -245,12 +249,170 @@ ISLAM_DEV int reg_status(const int* __restrict__ status, const double* __restric
     return (isfinite(dv) && dv >= 0.0) ? ISLAM_DENSE_REPROJ_OK : ISLAM_DENSE_REPROJ_BADPRIOR;
 }
 
-// grid (tiles_x tiles_y, B) x 256.  A workgroup owns a 32 x 8 tile of link b and holds it with a halo of h = r1 + r2 + r3 in LDS: the
-// cell (lx, ly) of the (32 + 2h) x (8 + 2h) region is pixel (x0 - h + lx, y0 - h + ly), and a cell outside the image is not valid, which
-// is all the clipping of a window at the border needs.  Stage 1 marks the removed cells of the region less r1, stage 2 fills the cells
-// of the region less r1 + r2 in place (it writes only cells that are not valid after stage 1 and reads only cells that are, so no
-// thread reads what another writes between two barriers), stages 3 and 4 run on the tile itself and store to global memory.  Every
-// window is walked row by row, which is the order of the sums.
+// A workgroup's LDS tile of link b: a 32 x 8 tile with a halo of h = r1 + r2 + r3.  The cell (lx, ly) of the (32 + 2h) x (8 + 2h) region
+// is pixel (gx0 + lx, gy0 + ly), and a cell outside the image is not valid, which is all the clipping of a window at the border needs.
+struct RegTile {
+    double *rho, *var;
+    uint8_t *v0, *rem, *fil;      // valid on input; removed by stage 1; filled by stage 2
+    int h, LW, LH, gx0, gy0;
+};
+
+// The stage functions below are shared by depth_regularize_kernel and depth_reg_front_kernel (the gradient's recomputation): nothing
+// in them is contracted, so both kernels form the same bits and take the same decisions from the same inputs.
+
+// the tile of workgroup (tx, ty) over the LDS arrays of the caller
+ISLAM_DEV RegTile reg_tile(double* srho, double* svar, uint8_t* sv0, uint8_t* srem, uint8_t* sfil, const RegStages& rs, int tx, int ty) {
+    const int h = rs.r1 + rs.r2 + rs.r3;
+    return {srho, svar, sv0, srem, sfil, h, REG_TW + 2 * h, REG_TH + 2 * h, tx * REG_TW - h, ty * REG_TH - h};
+}
+
+// the region from global memory (rho_b, var_b: the maps of the link), ending in a barrier
+ISLAM_DEV void reg_tile_load(const RegTile& t, const double* __restrict__ rho_b, const double* __restrict__ var_b, int H, int W) {
+#pragma clang fp contract(off)
+    for (int c = threadIdx.x; c < t.LW * t.LH; c += 256) {
+        const int ly = c / t.LW, lx = c - ly * t.LW;
+        const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+        double r = 0.0, s = 0.0;
+        bool ok = false;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            r = rho_b[gy * W + gx];
+            s = var_b[gy * W + gx];
+            ok = isfinite(r) && r > 0.0 && isfinite(s) && s > 0.0;
+        }
+        t.rho[c] = r;
+        t.var[c] = s;
+        t.v0[c] = ok;
+        t.rem[c] = 0;
+        t.fil[c] = 0;
+    }
+    __syncthreads();
+}
+
+// stage 1, occlusion removal on the region less r1: a cell with more nearer incompatible neighbours than compatible ones goes.  Ends in
+// a barrier.
+ISLAM_DEV void reg_stage_remove(const RegTile& t, const RegStages& rs) {
+#pragma clang fp contract(off)
+    const int o = rs.r1, w = t.LW - 2 * o, n = w * (t.LH - 2 * o);
+    for (int c = threadIdx.x; c < n; c += 256) {
+        const int ly = c / w, j = (ly + o) * t.LW + (c - ly * w) + o;
+        if (!t.v0[j]) continue;
+        const double rj = t.rho[j], sj = t.var[j];
+        int nsup = 0, nocc = 0;
+        for (int dv = -rs.r1; dv <= rs.r1; ++dv)
+            for (int du = -rs.r1; du <= rs.r1; ++du) {
+                const int k = j + dv * t.LW + du;
+                if (k == j || !t.v0[k]) continue;
+                const double rk = t.rho[k];
+                if (reg_compat(rk, t.var[k], rj, sj, rs.g2))
+                    ++nsup;
+                else if (rk > rj)
+                    ++nocc;
+            }
+        if (nocc >= rs.occl_min && nocc > nsup) t.rem[j] = 1;
+    }
+    __syncthreads();
+}
+
+// the cluster of a hole at cell j: the anchor (ka < 0: none; ra, sa), the members' count and their sums of w and w rho
+struct RegCluster {
+    int ka, cnt;
+    double ra, sa, Sw, Swr;
+};
+
+// The cluster around the nearest valid1 neighbour of cell j within r2.  It reads valid1 cells only, which stage 2 never writes, so it
+// gives the same bits before and after that stage.
+ISLAM_DEV RegCluster reg_cluster(const RegTile& t, const RegStages& rs, int j) {
+#pragma clang fp contract(off)
+    RegCluster c{-1, 0, 0.0, 0.0, 0.0, 0.0};
+    for (int dv = -rs.r2; dv <= rs.r2; ++dv)
+        for (int du = -rs.r2; du <= rs.r2; ++du) {
+            const int k = j + dv * t.LW + du;
+            if (!t.v0[k] || t.rem[k]) continue;
+            const double rk = t.rho[k];
+            if (c.ka < 0 || rk > c.ra) {
+                c.ka = k;
+                c.ra = rk;
+            }
+        }
+    if (c.ka < 0) return c;
+    c.sa = t.var[c.ka];
+    for (int dv = -rs.r2; dv <= rs.r2; ++dv)
+        for (int du = -rs.r2; du <= rs.r2; ++du) {
+            const int k = j + dv * t.LW + du;
+            if (!t.v0[k] || t.rem[k]) continue;
+            const double rk = t.rho[k], sk = t.var[k];
+            if (!reg_compat(rk, sk, c.ra, c.sa, rs.g2)) continue;
+            const double wk = 1.0 / sk;
+            c.Sw = c.Sw + wk;
+            c.Swr = c.Swr + wk * rk;
+            ++c.cnt;
+        }
+    return c;
+}
+
+// stage 2, hole filling on the region less r1 + r2, in place: the cluster's weighted mean, one neighbour's variance plus the scatter.
+// It writes only cells that are not valid after stage 1 and reads only cells that are, so no thread reads what another writes between
+// two barriers.  Ends in a barrier.
+ISLAM_DEV void reg_stage_fill(const RegTile& t, const RegStages& rs, int H, int W) {
+#pragma clang fp contract(off)
+    const int o = rs.r1 + rs.r2, w = t.LW - 2 * o, n = w * (t.LH - 2 * o);
+    for (int c = threadIdx.x; c < n; c += 256) {
+        const int ly = c / w + o, lx = c - (ly - o) * w + o, j = ly * t.LW + lx;
+        const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+        if (gx < 0 || gx >= W || gy < 0 || gy >= H || (t.v0[j] && !t.rem[j])) continue;
+        const RegCluster cl = reg_cluster(t, rs, j);
+        if (cl.ka < 0 || cl.cnt < rs.fill_min) continue;
+        const double mean = cl.Swr / cl.Sw;
+        double Se = 0.0;
+        for (int dv = -rs.r2; dv <= rs.r2; ++dv)
+            for (int du = -rs.r2; du <= rs.r2; ++du) {
+                const int k = j + dv * t.LW + du;
+                if (!t.v0[k] || t.rem[k]) continue;
+                const double rk = t.rho[k], sk = t.var[k];
+                if (!reg_compat(rk, sk, cl.ra, cl.sa, rs.g2)) continue;
+                const double e = rk - mean;
+                Se = Se + (1.0 / sk) * (e * e);
+            }
+        t.rho[j] = mean;
+        t.var[j] = rs.inflate * ((double)cl.cnt / cl.Sw + Se / cl.Sw);
+        t.fil[j] = 1;
+    }
+    __syncthreads();
+}
+
+// the head of both kernels: the region loaded and stages 1 and 2 run on it (every thread of the workgroup calls it)
+ISLAM_DEV void reg_stages_12(const RegTile& t, const RegStages& rs, const double* __restrict__ rho_b, const double* __restrict__ var_b, int H,
+                             int W) {
+    reg_tile_load(t, rho_b, var_b, H, W);
+    if (rs.r1 > 0) reg_stage_remove(t, rs);
+    if (rs.r2 > 0) reg_stage_fill(t, rs, H, W);
+}
+
+// the two sums of stage 3 at a present cell j of the tile with the stage-2 values (r2, s2): Sw = sum w_k, Swr = sum w_k rho_k over the
+// compatible neighbours, j itself among them, so Sw > 0
+struct RegSmooth {
+    double Sw, Swr;
+};
+
+ISLAM_DEV RegSmooth reg_smooth_sums(const RegTile& t, const RegStages& rs, int j, double r2, double s2, double dvar) {
+#pragma clang fp contract(off)
+    RegSmooth m{0.0, 0.0};
+    for (int dv = -rs.r3; dv <= rs.r3; ++dv)
+        for (int du = -rs.r3; du <= rs.r3; ++du) {
+            const int k = j + dv * t.LW + du;
+            if (!((t.v0[k] && !t.rem[k]) || t.fil[k])) continue;
+            const double rk = t.rho[k], sk = t.var[k];
+            if (!reg_compat(rk, sk, r2, s2, rs.g2)) continue;
+            const double wk = 1.0 / (sk + dvar * (double)(du * du + dv * dv));
+            m.Sw = m.Sw + wk;
+            m.Swr = m.Swr + wk * rk;
+        }
+    return m;
+}
+
+// grid (tiles_x tiles_y, B) x 256.  A workgroup owns a 32 x 8 tile of link b and holds it with a halo of h = r1 + r2 + r3 in LDS.
+// Stage 1 marks the removed cells of the region less r1, stage 2 fills the cells of the region less r1 + r2 in place, stages 3 and 4
+// run on the tile itself and store to global memory.  Every window is walked row by row, which is the order of the sums.
 __global__ __launch_bounds__(256) void depth_regularize_kernel(const double* __restrict__ inv_depth, const double* __restrict__ var_inv_depth,
                                                                 const int* __restrict__ source, const int* __restrict__ status,
                                                                 const double* __restrict__ dist_var, const float* __restrict__ depth_next,
@@ -261,111 +423,19 @@ __global__ __launch_bounds__(256) void depth_regularize_kernel(const double* __r
                                                                 int tiles_x) {
 #pragma clang fp contract(off)
     __shared__ double srho[REG_CELLS], svar[REG_CELLS];
-    __shared__ uint8_t sv0[REG_CELLS], srem[REG_CELLS], sfil[REG_CELLS];      // valid on input; removed by stage 1; filled by stage 2
+    __shared__ uint8_t sv0[REG_CELLS], srem[REG_CELLS], sfil[REG_CELLS];
     const int b = blockIdx.y, tid = threadIdx.x;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int h = rs.r1 + rs.r2 + rs.r3;
-    const int LW = REG_TW + 2 * h, LH = REG_TH + 2 * h;
-    const int gx0 = tx * REG_TW - h, gy0 = ty * REG_TH - h;      // the pixel of cell (0, 0)
+    const RegTile t = reg_tile(srho, svar, sv0, srem, sfil, rs, tx, ty);
     const size_t off = (size_t)b * H * W;
     const int st = reg_status(status, dist_var, b);
     if (blockIdx.x == 0 && tid == 0) out_status[b] = st;
     const bool live = st == ISLAM_DENSE_REPROJ_OK;      // (uniform over the workgroup) a link with a status: the measurement only
-    if (live) {
-        for (int c = tid; c < LW * LH; c += 256) {
-            const int ly = c / LW, lx = c - ly * LW;
-            const int gx = gx0 + lx, gy = gy0 + ly;
-            double r = 0.0, s = 0.0;
-            bool ok = false;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                r = inv_depth[off + gy * W + gx];
-                s = var_inv_depth[off + gy * W + gx];
-                ok = isfinite(r) && r > 0.0 && isfinite(s) && s > 0.0;
-            }
-            srho[c] = r;
-            svar[c] = s;
-            sv0[c] = ok;
-            srem[c] = 0;
-            sfil[c] = 0;
-        }
-        __syncthreads();
-        if (rs.r1 > 0) {      // occlusion removal: a cell with more nearer incompatible neighbours than compatible ones goes
-            const int o = rs.r1, w = LW - 2 * o, n = w * (LH - 2 * o);
-            for (int c = tid; c < n; c += 256) {
-                const int ly = c / w, j = (ly + o) * LW + (c - ly * w) + o;
-                if (!sv0[j]) continue;
-                const double rj = srho[j], sj = svar[j];
-                int nsup = 0, nocc = 0;
-                for (int dv = -rs.r1; dv <= rs.r1; ++dv)
-                    for (int du = -rs.r1; du <= rs.r1; ++du) {
-                        const int k = j + dv * LW + du;
-                        if (k == j || !sv0[k]) continue;
-                        const double rk = srho[k];
-                        if (reg_compat(rk, svar[k], rj, sj, rs.g2))
-                            ++nsup;
-                        else if (rk > rj)
-                            ++nocc;
-                    }
-                if (nocc >= rs.occl_min && nocc > nsup) srem[j] = 1;
-            }
-            __syncthreads();
-        }
-        if (rs.r2 > 0) {      // hole filling: the cluster around the nearest neighbour, its weighted mean, one neighbour's variance
-            const int o = rs.r1 + rs.r2, w = LW - 2 * o, n = w * (LH - 2 * o);
-            for (int c = tid; c < n; c += 256) {
-                const int ly = c / w + o, lx = c - (ly - o) * w + o, j = ly * LW + lx;
-                const int gx = gx0 + lx, gy = gy0 + ly;
-                if (gx < 0 || gx >= W || gy < 0 || gy >= H || (sv0[j] && !srem[j])) continue;
-                int ka = -1;
-                double ra = 0.0;
-                for (int dv = -rs.r2; dv <= rs.r2; ++dv)
-                    for (int du = -rs.r2; du <= rs.r2; ++du) {
-                        const int k = j + dv * LW + du;
-                        if (!sv0[k] || srem[k]) continue;
-                        const double rk = srho[k];
-                        if (ka < 0 || rk > ra) {
-                            ka = k;
-                            ra = rk;
-                        }
-                    }
-                if (ka < 0) continue;
-                const double sa = svar[ka];
-                int cnt = 0;
-                double Sw = 0.0, Swr = 0.0;
-                for (int dv = -rs.r2; dv <= rs.r2; ++dv)
-                    for (int du = -rs.r2; du <= rs.r2; ++du) {
-                        const int k = j + dv * LW + du;
-                        if (!sv0[k] || srem[k]) continue;
-                        const double rk = srho[k], sk = svar[k];
-                        if (!reg_compat(rk, sk, ra, sa, rs.g2)) continue;
-                        const double wk = 1.0 / sk;
-                        Sw = Sw + wk;
-                        Swr = Swr + wk * rk;
-                        ++cnt;
-                    }
-                if (cnt < rs.fill_min) continue;
-                const double mean = Swr / Sw;
-                double Se = 0.0;
-                for (int dv = -rs.r2; dv <= rs.r2; ++dv)
-                    for (int du = -rs.r2; du <= rs.r2; ++du) {
-                        const int k = j + dv * LW + du;
-                        if (!sv0[k] || srem[k]) continue;
-                        const double rk = srho[k], sk = svar[k];
-                        if (!reg_compat(rk, sk, ra, sa, rs.g2)) continue;
-                        const double e = rk - mean;
-                        Se = Se + (1.0 / sk) * (e * e);
-                    }
-                srho[j] = mean;
-                svar[j] = rs.inflate * ((double)cnt / Sw + Se / Sw);
-                sfil[j] = 1;
-            }
-            __syncthreads();
-        }
-    }
-    const int lx = (tid & (REG_TW - 1)) + h, ly = tid / REG_TW + h;
-    const int gx = gx0 + lx, gy = gy0 + ly;
+    if (live) reg_stages_12(t, rs, inv_depth + off, var_inv_depth + off, H, W);
+    const int lx = (tid & (REG_TW - 1)) + t.h, ly = tid / REG_TW + t.h;
+    const int gx = t.gx0 + lx, gy = t.gy0 + ly;
     if (gx >= W || gy >= H) return;      // past the last barrier
-    const int j = ly * LW + lx, gj = gy * W + gx;
+    const int j = ly * t.LW + lx, gj = gy * W + gx;
     bool have = false, kept = false;
     int extra = 0;
     double r3 = 0.0, s3 = NAN;
@@ -378,19 +448,8 @@ __global__ __launch_bounds__(256) void depth_regularize_kernel(const double* __r
         r3 = srho[j];
         s3 = svar[j];
         if (rs.r3 > 0) {      // smoothing: the weighted mean over the compatible neighbours, the variance as it was
-            const double dvar = dist_var[b];
-            double Sw = 0.0, Swr = 0.0;
-            for (int dv = -rs.r3; dv <= rs.r3; ++dv)
-                for (int du = -rs.r3; du <= rs.r3; ++du) {
-                    const int k = j + dv * LW + du;
-                    if (!((sv0[k] && !srem[k]) || sfil[k])) continue;
-                    const double rk = srho[k], sk = svar[k];
-                    if (!reg_compat(rk, sk, r3, s3, rs.g2)) continue;
-                    const double wk = 1.0 / (sk + dvar * (double)(du * du + dv * dv));
-                    Sw = Sw + wk;
-                    Swr = Swr + wk * rk;
-                }
-            r3 = Swr / Sw;      // j itself is in the window and compatible with itself: Sw > 0
+            const RegSmooth m = reg_smooth_sums(t, rs, j, r3, s3, dist_var[b]);
+            r3 = m.Swr / m.Sw;
         }
     }
     const bool has_meas = depth_next != nullptr;
@@ -586,7 +645,266 @@ __global__ __launch_bounds__(64) void depth_prop_pose_kernel(const double* __res
     gm[0] = gMt.x; gm[1] = gMt.y; gm[2] = gMt.z; gm[3] = gMq.x; gm[4] = gMq.y; gm[5] = gMq.z; gm[6] = gMq.w;
 }
 
+// ------------------------------------------------------------------ the gradient of the regularisation
+// The stencil is piecewise smooth: valid0, every compat decision, the removed set, each hole's anchor and cluster, the filled set,
+// each pixel's smoothing set and the row of the fusion table are constant on a piece.  depth_reg_front_kernel recomputes stages 1-3
+// with the forward's own functions (the same decisions from the same inputs), differentiates the fusion table and leaves per pixel
+// what the two gathers need; depth_reg_smooth_adj_kernel is the adjoint of stage 3 and depth_reg_fill_adj_kernel that of stage 2 with
+// the mask of stage 1.  Each output is one thread's fixed-order sum over a window, row by row: plain stores, no atomics.
+constexpr int REG_ST_VALID1 = 1, REG_ST_FILLED = 2;      // the state byte of a pixel; 0: nothing present after stage 2
+constexpr int REG_ADJ_CELLS = (REG_TW + 2 * REG_RMAX) * (REG_TH + 2 * REG_RMAX);      // 36 x 12: a gather's tile with a halo of 2
+
+// the per-pixel maps between the three kernels, (B,H,W) each, carved from the caller's scratch
+struct RegVjpMaps {
+    double *rho2, *var2, *rho3, *S3, *g3r, *g3s;      // after stage 2; after stage 3 and its sum of weights; the cotangents of (rho3, s2)
+    double *Sf, *ra, *sa;                             // at filled pixels: the cluster's sum of weights and the anchor
+    double *g2r, *g2s;                                // the cotangents of (rho2, s2) (the g3 maps themselves where stage 3 is left out)
+    uint8_t* state;
+};
+
+__global__ __launch_bounds__(256) void depth_reg_front_kernel(const double* __restrict__ inv_depth, const double* __restrict__ var_inv_depth,
+                                                               const int* __restrict__ status, const double* __restrict__ dist_var,
+                                                               const float* __restrict__ depth_next, const float* __restrict__ var_next,
+                                                               RegStages rs, const uint8_t* __restrict__ flags,
+                                                               const double* __restrict__ gout_rho, const double* __restrict__ gout_var,
+                                                               float* __restrict__ grad_dn, float* __restrict__ grad_vn, RegVjpMaps mp, int H,
+                                                               int W, int tiles_x) {
+    __shared__ double srho[REG_CELLS], svar[REG_CELLS];
+    __shared__ uint8_t sv0[REG_CELLS], srem[REG_CELLS], sfil[REG_CELLS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const RegTile t = reg_tile(srho, svar, sv0, srem, sfil, rs, tx, ty);
+    const size_t off = (size_t)b * H * W;
+    const bool live = reg_status(status, dist_var, b) == ISLAM_DENSE_REPROJ_OK;      // (uniform over the workgroup)
+    if (live) reg_stages_12(t, rs, inv_depth + off, var_inv_depth + off, H, W);
+    const int lx = (tid & (REG_TW - 1)) + t.h, ly = tid / REG_TW + t.h;
+    const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+    if (gx >= W || gy >= H) return;      // past the last barrier
+    const int j = ly * t.LW + lx;
+    const size_t gj = off + (size_t)gy * W + gx;
+    int state = 0;
+    if (live) state = (sv0[j] && !srem[j] ? REG_ST_VALID1 : 0) | (sfil[j] ? REG_ST_FILLED : 0);
+    double r2 = 0.0, s2 = 0.0, r3 = 0.0, S3 = 1.0;
+    if (state) {
+        r2 = srho[j];
+        s2 = svar[j];
+        r3 = r2;
+        if (rs.r3 > 0) {
+            const RegSmooth m = reg_smooth_sums(t, rs, j, r2, s2, dist_var[b]);
+            S3 = m.Sw;
+            r3 = m.Swr / m.Sw;      // the forward's own quotient
+        }
+    }
+    int fl = flags[gj] & (FLAG_PROP | FLAG_MEAS | FLAG_GATED);      // the row the forward pass chose
+    if (!state) fl &= FLAG_MEAS;
+    if (!depth_next) fl &= ~(FLAG_MEAS | FLAG_GATED);
+    // a cotangent is read only where the output depends on an input: where nothing is known it may be NaN
+    const bool known = (fl & (FLAG_PROP | FLAG_MEAS)) != 0;
+    const FuseGrad g = fuse_grad(fl, known && gout_rho ? gout_rho[gj] : 0.0, known && gout_var ? gout_var[gj] : 0.0, r3, s2,
+                                 depth_next ? depth_next[gj] : 0.0f, depth_next ? var_next[gj] : 0.0f);
+    if (grad_dn) {
+        grad_dn[gj] = (float)g.g_dn;
+        grad_vn[gj] = (float)g.g_vn;
+    }
+    mp.state[gj] = (uint8_t)state;
+    if (!state) return;      // the gathers read the other maps only where the state is set
+    mp.rho2[gj] = r2;
+    mp.var2[gj] = s2;
+    mp.rho3[gj] = r3;
+    mp.S3[gj] = S3;
+    mp.g3r[gj] = g.g_rp;
+    mp.g3s[gj] = g.g_sp;
+    if (state & REG_ST_FILLED) {
+        const RegCluster cl = reg_cluster(t, rs, j);      // the cluster stage 2 filled this cell from: the same function, the same cells
+        mp.Sf[gj] = cl.Sw;
+        mp.ra[gj] = cl.ra;
+        mp.sa[gj] = cl.sa;
+    }
+}
+
+// a gather's 32 x 8 tile with a halo of r: cell (lx, ly) is pixel (x0 - r + lx, y0 - r + ly); LW = 32 + 2r
+struct RegAdjTile {
+    int r, LW, n, gx0, gy0;
+};
+
+ISLAM_DEV RegAdjTile reg_adj_tile(int r, int tiles_x) {
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    return {r, REG_TW + 2 * r, (REG_TW + 2 * r) * (REG_TH + 2 * r), tx * REG_TW - r, ty * REG_TH - r};      // n <= REG_ADJ_CELLS for r <= REG_RMAX
+}
+
+// The adjoint of stage 3, gathered at k over the outputs j of k's window that took k into their mean: g2r_k = sum g3r_j w_kj / S_j,
+// g2s_k = g3s_k - sum g3r_j w_kj^2 (rho2_k - rho3_j) / S_j, w_kj = 1 / (s2_k + dist_var (du^2 + dv^2)).  compat gives the same bits with
+// its arguments exchanged, so it is the decision output j took.  Launched only with r3 > 0.
+__global__ __launch_bounds__(256) void depth_reg_smooth_adj_kernel(const double* __restrict__ dist_var, RegStages rs, RegVjpMaps mp, int H, int W,
+                                                                    int tiles_x) {
+    __shared__ double srho[REG_ADJ_CELLS], svar[REG_ADJ_CELLS], sr3[REG_ADJ_CELLS], sS[REG_ADJ_CELLS], sg[REG_ADJ_CELLS];
+    __shared__ uint8_t sst[REG_ADJ_CELLS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const RegAdjTile t = reg_adj_tile(rs.r3, tiles_x);
+    const size_t off = (size_t)b * H * W;
+    for (int c = tid; c < t.n; c += 256) {
+        const int ly = c / t.LW, lx = c - ly * t.LW;
+        const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+        int st = 0;
+        double r = 0.0, s = 0.0, r3 = 0.0, S = 1.0, g = 0.0;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t gj = off + (size_t)gy * W + gx;
+            st = mp.state[gj];
+            if (st) {
+                r = mp.rho2[gj];
+                s = mp.var2[gj];
+                r3 = mp.rho3[gj];
+                S = mp.S3[gj];
+                g = mp.g3r[gj];
+            }
+        }
+        sst[c] = (uint8_t)st;
+        srho[c] = r;
+        svar[c] = s;
+        sr3[c] = r3;
+        sS[c] = S;
+        sg[c] = g;
+    }
+    __syncthreads();
+    const int lx = (tid & (REG_TW - 1)) + t.r, ly = tid / REG_TW + t.r;
+    const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+    if (gx >= W || gy >= H) return;
+    const int k = ly * t.LW + lx;
+    if (!sst[k]) return;      // the next kernel reads g2 only where the state is set
+    const size_t gk = off + (size_t)gy * W + gx;
+    const double rk = srho[k], sk = svar[k], dvar = dist_var[b];
+    double gr = 0.0, gs = mp.g3s[gk];
+    for (int dv = -t.r; dv <= t.r; ++dv)
+        for (int du = -t.r; du <= t.r; ++du) {
+            const int j = k + dv * t.LW + du;
+            if (!sst[j] || !reg_compat(rk, sk, srho[j], svar[j], rs.g2)) continue;
+            const double w = 1.0 / (sk + dvar * (double)(du * du + dv * dv));
+            const double q = sg[j] * w / sS[j];
+            gr += q;
+            gs -= q * w * (rk - sr3[j]);
+        }
+    mp.g2r[gk] = gr;
+    mp.g2s[gk] = gs;
+}
+
+// The adjoint of stage 2 gathered at a valid1 k over the filled j within r2 whose cluster holds k (compat(k, a_j)), the mask of stage
+// 1 and the final stores: with w = 1 / s_k, S the cluster's sum of weights, e = rho_k - rho2_j and f = fill_inflate,
+//   g1r_k = g2r_k + sum (g2r_j w + g2s_j 2 f w e) / S,   g1s_k = g2s_k + sum (-g2r_j w^2 e + g2s_j w^2 (s2_j - f e^2)) / S,
+// and exact zeros at every pixel that is not valid1.
+__global__ __launch_bounds__(256) void depth_reg_fill_adj_kernel(RegStages rs, RegVjpMaps mp, double* __restrict__ grad_rho,
+                                                                  double* __restrict__ grad_var, int H, int W, int tiles_x) {
+    __shared__ double srho[REG_ADJ_CELLS], svar[REG_ADJ_CELLS], sgr[REG_ADJ_CELLS], sgs[REG_ADJ_CELLS], sSf[REG_ADJ_CELLS], sra[REG_ADJ_CELLS],
+        ssa[REG_ADJ_CELLS];
+    __shared__ uint8_t sst[REG_ADJ_CELLS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const RegAdjTile t = reg_adj_tile(rs.r2, tiles_x);
+    const size_t off = (size_t)b * H * W;
+    for (int c = tid; c < t.n; c += 256) {
+        const int ly = c / t.LW, lx = c - ly * t.LW;
+        const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+        int st = 0;
+        double r = 0.0, s = 0.0, gr = 0.0, gs = 0.0, Sf = 1.0, ra = 0.0, sa = 0.0;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t gj = off + (size_t)gy * W + gx;
+            st = mp.state[gj];
+            if (st) {
+                r = mp.rho2[gj];
+                s = mp.var2[gj];
+                gr = mp.g2r[gj];
+                gs = mp.g2s[gj];
+            }
+            if (st & REG_ST_FILLED) {
+                Sf = mp.Sf[gj];
+                ra = mp.ra[gj];
+                sa = mp.sa[gj];
+            }
+        }
+        sst[c] = (uint8_t)st;
+        srho[c] = r;
+        svar[c] = s;
+        sgr[c] = gr;
+        sgs[c] = gs;
+        sSf[c] = Sf;
+        sra[c] = ra;
+        ssa[c] = sa;
+    }
+    __syncthreads();
+    const int lx = (tid & (REG_TW - 1)) + t.r, ly = tid / REG_TW + t.r;
+    const int gx = t.gx0 + lx, gy = t.gy0 + ly;
+    if (gx >= W || gy >= H) return;
+    const int k = ly * t.LW + lx;
+    const size_t gk = off + (size_t)gy * W + gx;
+    double gr = 0.0, gs = 0.0;
+    if (sst[k] & REG_ST_VALID1) {
+        const double rk = srho[k], sk = svar[k], w = 1.0 / sk;      // a valid1 pixel keeps its input through stage 2
+        gr = sgr[k];
+        gs = sgs[k];
+        for (int dv = -t.r; dv <= t.r; ++dv)
+            for (int du = -t.r; du <= t.r; ++du) {
+                const int j = k + dv * t.LW + du;
+                if (!(sst[j] & REG_ST_FILLED) || !reg_compat(rk, sk, sra[j], ssa[j], rs.g2)) continue;
+                const double e = rk - srho[j], wS = w / sSf[j];
+                gr += sgr[j] * wS + sgs[j] * (2.0 * rs.inflate * e * wS);
+                gs += sgs[j] * (w * wS * (svar[j] - rs.inflate * (e * e))) - sgr[j] * (w * wS * e);
+            }
+    }
+    grad_rho[gk] = gr;
+    grad_var[gk] = gs;
+}
+
 }  // namespace
+
+extern "C" size_t islam_depth_regularize_vjp_scratch_bytes(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return 0;
+    const size_t n = (size_t)B * H * W;
+    return 11 * align_up(n * sizeof(double)) + align_up(n);      // the maps of RegVjpMaps
+}
+
+extern "C" int islam_depth_regularize_vjp(const double* inv_depth, const double* var_inv_depth, const int* status_or_null, const double* dist_var,
+                                          const float* depth_next_or_null, const float* var_next_or_null, double gate, int occl_radius,
+                                          int occl_min, int fill_radius, int fill_min, double fill_inflate, int smooth_radius, double reg_gate,
+                                          const uint8_t* flags, const double* grad_out_inv_depth_or_null, const double* grad_out_var_or_null,
+                                          double* grad_inv_depth, double* grad_var_inv_depth, float* grad_depth_next_or_null,
+                                          float* grad_var_next_or_null, void* scratch, int B, int H, int W, void* stream) {
+    const char* who = "islam_depth_regularize_vjp";
+    if (int rc = check_shape_kind(who, B, H, W, ISLAM_ROBUST_NONE, 1.0)) return rc;
+    if (!inv_depth || !var_inv_depth || !dist_var || !flags)
+        return fail(ISLAM_EARG, "%s: NULL inv_depth / var_inv_depth / dist_var / flags pointer", who);
+    if (!grad_inv_depth || !grad_var_inv_depth || !scratch) return fail(ISLAM_EARG, "%s: NULL output / scratch pointer", who);
+    if ((depth_next_or_null == nullptr) != (var_next_or_null == nullptr))
+        return fail(ISLAM_EARG, "%s: depth_next and var_next come together or not at all", who);
+    if ((grad_depth_next_or_null == nullptr) != (grad_var_next_or_null == nullptr))
+        return fail(ISLAM_EARG, "%s: grad_depth_next and grad_var_next come together or not at all", who);
+    if (grad_depth_next_or_null && !depth_next_or_null) return fail(ISLAM_EARG, "%s: a measurement gradient without a measurement", who);
+    if (!(std::isfinite(gate) && gate >= 0.0)) return fail(ISLAM_EARG, "%s: gate must be finite and non-negative (got %g)", who, gate);
+    for (int r : {occl_radius, fill_radius, smooth_radius})
+        if (r < 0 || r > REG_RMAX)
+            return fail(ISLAM_EARG, "%s: a radius must be 0..%d (got %d, %d, %d)", who, REG_RMAX, occl_radius, fill_radius, smooth_radius);
+    if (occl_min < 1 || fill_min < 1) return fail(ISLAM_EARG, "%s: occl_min and fill_min must be at least 1 (got %d, %d)", who, occl_min, fill_min);
+    if (!(std::isfinite(fill_inflate) && fill_inflate >= 1.0))
+        return fail(ISLAM_EARG, "%s: fill_inflate must be finite and at least 1 (got %g)", who, fill_inflate);
+    if (!(std::isfinite(reg_gate) && reg_gate > 0.0)) return fail(ISLAM_EARG, "%s: reg_gate must be finite and positive (got %g)", who, reg_gate);
+    const int tiles_x = (W + REG_TW - 1) / REG_TW, tiles_y = (H + REG_TH - 1) / REG_TH;
+    const RegStages rs{occl_radius, occl_min, fill_radius, fill_min, smooth_radius, fill_inflate, reg_gate * reg_gate};
+    const size_t n = (size_t)B * H * W, step = align_up(n * sizeof(double));
+    char* base = static_cast<char*>(scratch);
+    double* d[11];
+    for (int i = 0; i < 11; ++i) d[i] = reinterpret_cast<double*>(base + i * step);
+    RegVjpMaps mp{d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], reinterpret_cast<uint8_t*>(base + 11 * step)};
+    if (smooth_radius == 0) {      // stage 3 left out: g2 = g3
+        mp.g2r = mp.g3r;
+        mp.g2s = mp.g3s;
+    }
+    hipStream_t s = as_stream(stream);
+    const dim3 grid(tiles_x * tiles_y, B);
+    hipLaunchKernelGGL(depth_reg_front_kernel, grid, dim3(256), 0, s, inv_depth, var_inv_depth, status_or_null, dist_var, depth_next_or_null,
+                       var_next_or_null, rs, flags, grad_out_inv_depth_or_null, grad_out_var_or_null, grad_depth_next_or_null,
+                       grad_var_next_or_null, mp, H, W, tiles_x);
+    if (smooth_radius > 0) hipLaunchKernelGGL(depth_reg_smooth_adj_kernel, grid, dim3(256), 0, s, dist_var, rs, mp, H, W, tiles_x);
+    hipLaunchKernelGGL(depth_reg_fill_adj_kernel, grid, dim3(256), 0, s, rs, mp, grad_inv_depth, grad_var_inv_depth, H, W, tiles_x);
+    ISLAM_LAUNCH_CHECK();
+    return ISLAM_OK;
+}
 
 extern "C" size_t islam_depth_propagate_vjp_scratch_bytes(int B) { return B < 1 ? 0 : align_up((size_t)B * NBLK * 4 * sizeof(double)); }
 

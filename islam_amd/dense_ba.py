@@ -390,7 +390,7 @@ class DenseReprojectionLoss:
         return ps * ps
 
     def propagate(self, joint, uncertainty, depth_next=None, sigma_inv_depth_next=None, process_sigma=0.0, gate=3.0, regularize=None,
-                  differentiable=False):
+                  differentiable=False, regularize_grad=None):
         """The step from one link to the next: the inverse depths a ``refine_joint`` returned (``joint``) and their variances
         (``uncertainty``: the result of ``depth_uncertainty`` for it) are warped through the refined pose into the pixel grid of the
         link's second frame, the nearest surface winning where several pixels land on one, and fused there with that frame's own depth
@@ -418,11 +418,24 @@ class DenseReprojectionLoss:
         networks behind both (ops._DenseBAPropagate, ops.dense_ba_depth_propagate_vjp, two launches).  The
         gradient is that of the piece the forward pass chose: the target pixel, the z-buffer winner and the gate decision are held
         fixed.  ``sigma_inv_depth_next``, ``process_sigma`` and ``gate`` get no gradient; a link with a status gets a zero gradient on
-        its state and pose.  With ``regularize`` it raises NotImplementedError (the stencil is not differentiated)."""
+        its state and pose.  With ``regularize`` it raises NotImplementedError unless ``regularize_grad`` says how the non-smooth
+        stencil is differentiated.
+
+        regularize_grad=None, or 'piecewise' (with differentiable=True and a DepthRegularizer only; anything else is a ValueError): the
+        pure propagation goes through ops._DenseBAPropagate and the regularisation through ops._DenseBARegularize (its backward:
+        ops.dense_ba_depth_regularize_vjp, at most three launches), the same launches and the same bits as
+        the ``differentiable=False`` regularised call.  The gradient is again that of the piece the forward pass chose: every
+        compatibility decision, the removed and filled sets, each hole's cluster, each pixel's smoothing set and the gate decision are
+        held fixed, and a pixel that stage 1 did not keep gets an exactly zero gradient.  ``dist_sigma`` and the stage parameters get
+        no gradient."""
         from . import ops
-        if differentiable and regularize is not None:
-            raise NotImplementedError('propagate: differentiable=True is not implemented with regularize (the gradient of the regularisation '
-                                      'is not available)')
+        if regularize_grad is not None and regularize_grad != 'piecewise':
+            raise ValueError("propagate: regularize_grad must be None or 'piecewise' (got %r)" % (regularize_grad,))
+        if regularize_grad is not None and not (differentiable and regularize is not None):
+            raise ValueError("propagate: regularize_grad='piecewise' needs differentiable=True and a DepthRegularizer in regularize")
+        if differentiable and regularize is not None and regularize_grad is None:
+            raise NotImplementedError("propagate: differentiable=True with regularize needs regularize_grad='piecewise', the gradient of the "
+                                      'piece the regularisation chose (the stencil is not smooth)')
         if (depth_next is None) != (sigma_inv_depth_next is None):
             raise ValueError('propagate: depth_next and sigma_inv_depth_next come together or not at all')
         var_next = None
@@ -436,8 +449,17 @@ class DenseReprojectionLoss:
         link_kw = dict(mask=self.mask, status=uncertainty.status, rgb2imu=self.rgb2imu_pose, process_var=process_var)
         if differentiable:
             mount = None if self.rgb2imu_pose is None else pp._plain(self.rgb2imu_pose).detach()
-            out = ops.DenseBAPropagated(*ops._DenseBAPropagate.apply(*link, self.mask, uncertainty.status, mount, process_var, depth_next, var_next,
-                                                                     gate))
+            if regularize is None:
+                out = ops.DenseBAPropagated(*ops._DenseBAPropagate.apply(*link, self.mask, uncertainty.status, mount, process_var, depth_next,
+                                                                         var_next, gate))
+            else:
+                if not isinstance(regularize, DepthRegularizer):
+                    raise ValueError('propagate: regularize must be a DepthRegularizer or None (got %r)' % (regularize,))
+                stages = regularize._asdict()
+                dist_var = self._link_sigma_squared(stages.pop('dist_sigma'), 'dist_sigma')
+                pure = ops.DenseBAPropagated(*ops._DenseBAPropagate.apply(*link, self.mask, uncertainty.status, mount, process_var, None, None, 0.0))
+                out = ops.DenseBARegularized(*ops._DenseBARegularize.apply(pure.inv_depth, pure.var_inv_depth, pure.source, pure.status, dist_var,
+                                                                           depth_next, var_next, gate, stages))
             ok = out.inv_depth > 0          # the kernel's out_depth, with its graph: the float32 of 1 / rho_f, else the bits it stored
             depth = torch.where(ok, (1.0 / torch.where(ok, out.inv_depth, torch.ones_like(out.inv_depth))).to(torch.float32), out.depth)
             return DenseBAPrior(depth, torch.sqrt(out.var_inv_depth), out.inv_depth, out.var_inv_depth, out.source, out.flags, out.status)

@@ -609,6 +609,23 @@ class _DenseBAPropagate(torch.autograd.Function):
                 g.grad_depth_next.to(d[3]) if need[8] else None, g.grad_var_next.to(d[4]) if need[9] else None, None)
 
 
+def _regularize_stage_args(who, occl_radius, occl_min, fill_radius, fill_min, fill_inflate, smooth_radius, reg_gate):
+    """The stage arguments of the regularisation as the library takes them: ([occl_radius, fill_radius, smooth_radius] as ints,
+    fill_inflate, reg_gate as floats), ValueError for what islam_depth_regularize would refuse."""
+    radii = [int(r) for r in (occl_radius, fill_radius, smooth_radius)]
+    if any(r not in (0, 1, 2) or r != x for r, x in zip(radii, (occl_radius, fill_radius, smooth_radius))):
+        raise ValueError('%s: occl_radius, fill_radius and smooth_radius must be 0, 1 or 2 (got %r, %r, %r)' % (
+            who, occl_radius, fill_radius, smooth_radius))
+    if int(occl_min) != occl_min or int(fill_min) != fill_min or occl_min < 1 or fill_min < 1:
+        raise ValueError('%s: occl_min and fill_min must be integers >= 1 (got %r, %r)' % (who, occl_min, fill_min))
+    fill_inflate, reg_gate = float(fill_inflate), float(reg_gate)
+    if not (fill_inflate >= 1.0 and fill_inflate < float('inf')):
+        raise ValueError('%s: fill_inflate must be finite and at least 1 (got %r)' % (who, fill_inflate))
+    if not (reg_gate > 0.0 and reg_gate < float('inf')):
+        raise ValueError('%s: reg_gate must be finite and positive (got %r)' % (who, reg_gate))
+    return radii, fill_inflate, reg_gate
+
+
 DenseBARegularized = collections.namedtuple('DenseBARegularized', 'inv_depth var_inv_depth depth source flags status')
 
 
@@ -640,17 +657,7 @@ def dense_ba_depth_regularize(inv_depth, var_inv_depth, source=None, status=None
         source = source.to(dev, torch.int32).contiguous()
     dv = _link_variance(who, 'dist_var', dist_var, B, dev)
     depth_next, var_next, gate = _next_measurement(who, depth_next, var_next, gate, B, H, W, dev)
-    radii = [int(r) for r in (occl_radius, fill_radius, smooth_radius)]
-    if any(r not in (0, 1, 2) or r != x for r, x in zip(radii, (occl_radius, fill_radius, smooth_radius))):
-        raise ValueError('%s: occl_radius, fill_radius and smooth_radius must be 0, 1 or 2 (got %r, %r, %r)' % (
-            who, occl_radius, fill_radius, smooth_radius))
-    if int(occl_min) != occl_min or int(fill_min) != fill_min or occl_min < 1 or fill_min < 1:
-        raise ValueError('%s: occl_min and fill_min must be integers >= 1 (got %r, %r)' % (who, occl_min, fill_min))
-    fill_inflate, reg_gate = float(fill_inflate), float(reg_gate)
-    if not (fill_inflate >= 1.0 and fill_inflate < float('inf')):
-        raise ValueError('%s: fill_inflate must be finite and at least 1 (got %r)' % (who, fill_inflate))
-    if not (reg_gate > 0.0 and reg_gate < float('inf')):
-        raise ValueError('%s: reg_gate must be finite and positive (got %r)' % (who, reg_gate))
+    radii, fill_inflate, reg_gate = _regularize_stage_args(who, occl_radius, occl_min, fill_radius, fill_min, fill_inflate, smooth_radius, reg_gate)
     status = _dense_reproj_status(status, B, dev)
     require_cuda(inv_depth, var_inv_depth, depth_next, var_next)      # after the argument rules, which need no device
     e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
@@ -663,6 +670,87 @@ def dense_ba_depth_regularize(inv_depth, var_inv_depth, source=None, status=None
                                        ptr(out.var_inv_depth), ptr(out.depth), ptr(out.source), ptr(out.flags), ptr(out.status),
                                        ptr(scratch), B, H, W, stream_ptr(dev)))
     return out
+
+
+DenseBARegularizeGrad = collections.namedtuple('DenseBARegularizeGrad', 'grad_inv_depth grad_var_inv_depth grad_depth_next grad_var_next')
+
+
+def dense_ba_depth_regularize_vjp(inv_depth, var_inv_depth, flags, status=None, grad_inv_depth=None, grad_var_inv_depth=None, dist_var=0.0,
+                                  depth_next=None, var_next=None, gate=0.0, occl_radius=1, occl_min=2, fill_radius=1, fill_min=3,
+                                  fill_inflate=1.0, smooth_radius=1, reg_gate=3.0):
+    """The vector-Jacobian product of dense_ba_depth_regularize on the piece its forward pass chose (include/islam_hip.h,
+    islam_depth_regularize_vjp).  inv_depth, var_inv_depth, dist_var, depth_next, var_next, gate and the stage
+    arguments: what the forward call was given (the source map is not needed); flags (B,H,W): what it returned; status (B) or None: the
+    status it returned (or the one it was given: dist_var marks its links again on the device); grad_inv_depth, grad_var_inv_depth
+    (B,H,W) or None (zero): the cotangents of its inv_depth and var_inv_depth outputs, read only where flags & 3 is not 0 (they may be
+    NaN where nothing is known).  Every compat decision, the removed and filled sets, each hole's anchor and cluster, each pixel's
+    smoothing set and the row of the fusion table are held fixed.  Returns DenseBARegularizeGrad(grad_inv_depth, grad_var_inv_depth
+    (B,H,W) float64: exactly 0 at every pixel that stage 1 did not keep, grad_depth_next, grad_var_next (B,H,W) float32, None without a
+    measurement).  A link with a status gets zeros on its state; its measurement still gets its gradient.  dist_var, gate and the
+    stage arguments get no gradient.  At most three launches, nothing is read back."""
+    who = 'dense_ba_depth_regularize_vjp'
+    dev = inv_depth.device
+    if inv_depth.dim() != 3 or tuple(var_inv_depth.shape) != tuple(inv_depth.shape):
+        raise ValueError('%s: inv_depth and var_inv_depth must be (B,H,W), got %s and %s' % (who, tuple(inv_depth.shape), tuple(var_inv_depth.shape)))
+    B, H, W = inv_depth.shape
+    rho, var = (t.detach().to(dev, torch.float64).contiguous() for t in (inv_depth, var_inv_depth))
+    if flags is None or tuple(flags.shape) != (B, H, W):
+        raise ValueError('%s: flags must be the (%d,%d,%d) flags the forward call returned, got %s' % (
+            who, B, H, W, None if flags is None else tuple(flags.shape)))
+    flags = flags.to(dev, torch.uint8).contiguous()
+    dv = _link_variance(who, 'dist_var', dist_var, B, dev)
+    depth_next, var_next, gate = _next_measurement(who, depth_next, var_next, gate, B, H, W, dev)
+    radii, fill_inflate, reg_gate = _regularize_stage_args(who, occl_radius, occl_min, fill_radius, fill_min, fill_inflate, smooth_radius, reg_gate)
+    status = _dense_reproj_status(status, B, dev)
+    cots = []
+    for name, g in (('grad_inv_depth', grad_inv_depth), ('grad_var_inv_depth', grad_var_inv_depth)):
+        if g is not None:
+            if tuple(g.shape) != (B, H, W):
+                raise ValueError('%s: %s must be (%d,%d,%d), got %s' % (who, name, B, H, W, tuple(g.shape)))
+            g = g.detach().to(dev, torch.float64).contiguous()
+        cots.append(g)
+    require_cuda(inv_depth, var_inv_depth, depth_next, var_next)      # after the argument rules, which need no device
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    meas = depth_next is not None
+    out = DenseBARegularizeGrad(e(torch.float64, B, H, W), e(torch.float64, B, H, W), e(torch.float32, B, H, W) if meas else None,
+                                e(torch.float32, B, H, W) if meas else None)
+    scratch = torch.empty(lib().islam_depth_regularize_vjp_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
+    check(lib().islam_depth_regularize_vjp(ptr(rho), ptr(var), ptr(status), ptr(dv), ptr(depth_next), ptr(var_next), gate, radii[0], int(occl_min),
+                                           radii[1], int(fill_min), fill_inflate, radii[2], reg_gate, ptr(flags), ptr(cots[0]), ptr(cots[1]),
+                                           ptr(out.grad_inv_depth), ptr(out.grad_var_inv_depth), ptr(out.grad_depth_next),
+                                           ptr(out.grad_var_next), ptr(scratch), B, H, W, stream_ptr(dev)))
+    return out
+
+
+class _DenseBARegularize(torch.autograd.Function):
+    """dense_ba_depth_regularize whose inv_depth and var_inv_depth outputs carry the gradient of the piece the forward pass chose in
+    inv_depth, var_inv_depth, depth_next and var_next: forward is that call, backward is
+    dense_ba_depth_regularize_vjp on the same tensors with the flags and status forward returned, and nothing else.  The source map,
+    the status, dist_var, the gate and ``stages`` (a dict of the stage arguments) get no gradient."""
+
+    @staticmethod
+    def forward(ctx, inv_depth, var_inv_depth, source, status, dist_var, depth_next, var_next, gate, stages):
+        out = dense_ba_depth_regularize(inv_depth, var_inv_depth, source=source, status=status, dist_var=dist_var, depth_next=depth_next,
+                                        var_next=var_next, gate=gate, **stages)
+        ctx.save_for_backward(inv_depth, var_inv_depth, depth_next, var_next, out.flags, out.status)
+        ctx.dist_var = dist_var.detach() if torch.is_tensor(dist_var) else dist_var
+        ctx.gate, ctx.stages = gate, dict(stages)
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (inv_depth, var_inv_depth, depth_next, var_next))
+        ctx.mark_non_differentiable(out.depth, out.source, out.flags, out.status)
+        ctx.set_materialize_grads(False)          # a cotangent the loss does not give arrives as None: the kernel takes NULL for zero
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_inv_depth, grad_var_inv_depth, *unused):
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1] or need[5] or need[6]):
+            return (None,) * 9
+        rho, var, depth_next, var_next, flags, status = ctx.saved_tensors
+        g = dense_ba_depth_regularize_vjp(rho, var, flags, status=status, grad_inv_depth=grad_inv_depth, grad_var_inv_depth=grad_var_inv_depth,
+                                          dist_var=ctx.dist_var, depth_next=depth_next, var_next=var_next, gate=ctx.gate, **ctx.stages)
+        d = ctx.dtypes
+        return (g.grad_inv_depth.to(d[0]) if need[0] else None, g.grad_var_inv_depth.to(d[1]) if need[1] else None, None, None, None,
+                g.grad_depth_next.to(d[2]) if need[5] else None, g.grad_var_next.to(d[3]) if need[6] else None, None, None)
 
 
 def dense_reproj_vjp(depth, flow, mask, motion, intr, w, rgb2imu=None, kernel=None, status=None):

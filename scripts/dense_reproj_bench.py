@@ -63,6 +63,12 @@ the refined state of --uncertainty's scene (weight map included) with the sums g
 The yardstick is the forward ops.dense_ba_depth_variance on the same tensors in the same process.
 
     python scripts/dense_reproj_bench.py --uncertainty-grad [--case 448x640] [--out profiles/dense_ba_uncertainty_grad_bench.json]
+
+--regularize-grad times the gradient of the depth regularisation instead: ops.dense_ba_depth_regularize_vjp on
+the flags of --regularize's regularisation fused with a measurement at gate 3, at radii 1, 2 and 0, with both cotangents and with the
+one on the inverse depth alone.  The yardstick is the forward ops.dense_ba_depth_regularize at the same radii in the same process.
+
+    python scripts/dense_reproj_bench.py --regularize-grad [--case 448x640] [--out profiles/depth_regularize_grad_bench.json]
 """
 import json
 import os
@@ -809,6 +815,67 @@ def main_propagate_grad(argv):
         f.write(line + '\n')
 
 
+# the nominal bytes of one pixel in ops.dense_ba_depth_regularize_vjp with a measurement, both cotangents and every stage on, at a pixel
+# that is present: the front reads rho and its variance (16), flags (1), the measurement (8) and the cotangents (16) and stores two
+# float32 (8), six float64 maps (48) and the state byte (1); the smoothing adjoint reads five maps, g3s and the state (49) and stores
+# two (16); the filling adjoint reads four maps and the state (33) and stores two (16).  The halos and the three maps of the filled
+# pixels are not counted
+REG_GRAD_PIXEL_BYTES = 212
+
+
+def run_regularize_grad_case(H, W):
+    """--regularize-grad: the cost of the gradient of the regularisation beside the regularisation itself."""
+    import torch
+    from islam_amd import ops
+    _, prop, depth_next, var_next = propagate_scene(H, W)
+    meas = dict(depth_next=depth_next, var_next=var_next, gate=3.0)
+    pure = prop()
+    dv = torch.full((B,), 1e-8, dtype=torch.float64, device=pure.inv_depth.device)          # on the device: no copy inside the timed call
+    radii = lambda r: dict(occl_radius=r, fill_radius=r, smooth_radius=r)
+    reg = lambda r: ops.dense_ba_depth_regularize(pure.inv_depth, pure.var_inv_depth, source=pure.source, status=pure.status, dist_var=dv, **radii(r), **meas)
+    fwd = {r: reg(r) for r in (0, 1, 2)}
+    g = torch.Generator(device='cuda').manual_seed(5)
+    gr = torch.randn((B, H, W), dtype=torch.float64, device='cuda', generator=g)
+    gs = 1e3 * torch.randn((B, H, W), dtype=torch.float64, device='cuda', generator=g)
+    vjp = lambda r, **kw: ops.dense_ba_depth_regularize_vjp(pure.inv_depth, pure.var_inv_depth, fwd[r].flags, status=fwd[r].status, dist_var=dv, **radii(r),
+                                                            **meas, **kw)
+    both = dict(grad_inv_depth=gr, grad_var_inv_depth=gs)
+    out = timed({'regularize_r1': lambda: reg(1), 'regularize_r2': lambda: reg(2), 'regularize_r0': lambda: reg(0), 'vjp_r1': lambda: vjp(1, **both),
+                 'vjp_r2': lambda: vjp(2, **both), 'vjp_r0': lambda: vjp(0, **both), 'vjp_r1_inv_depth_only': lambda: vjp(1, grad_inv_depth=gr),
+                 'regularize_then_vjp_r1': lambda: (reg(1), vjp(1, **both))})
+    r = vjp(1, **both)
+    out['status_ok'] = int((fwd[1].status == 0).sum())
+    out['present_fraction_r1'] = float(((fwd[1].flags & 1) != 0).double().mean())
+    out['filled_fraction_r1'] = float(((fwd[1].flags & 8) != 0).double().mean())
+    out['nonzero_grad_fraction'] = float((r.grad_inv_depth != 0).double().mean())
+    out['finite'] = int(all(bool(torch.isfinite(t).all()) for t in r))
+    for k in (0, 1, 2):
+        out['vjp_over_forward_r%d' % k] = out['vjp_r%d' % k] / out['regularize_r%d' % k]
+    out['MB_moved_vjp_r1'] = REG_GRAD_PIXEL_BYTES * B * H * W / 1e6
+    out['hbm_frac_vjp_r1'] = REG_GRAD_PIXEL_BYTES * B * H * W / (out['vjp_r1'] * 1e-6) / 1e9 / HBM_GBS
+    return out
+
+
+def main_regularize_grad(argv):
+    import torch
+    assert torch.cuda.is_available(), 'dense_reproj_bench.py needs the GPU'
+    cases = {argv[argv.index('--case') + 1]: CASES[argv[argv.index('--case') + 1]]} if '--case' in argv else CASES
+    rows = {case: run_regularize_grad_case(*hw) for case, hw in cases.items()}
+    cols = ('regularize_r0', 'regularize_r1', 'regularize_r2', 'vjp_r0', 'vjp_r1', 'vjp_r2', 'vjp_r1_inv_depth_only', 'regularize_then_vjp_r1',
+            'vjp_over_forward_r0', 'vjp_over_forward_r1', 'vjp_over_forward_r2', 'MB_moved_vjp_r1', 'hbm_frac_vjp_r1', 'status_ok',
+            'present_fraction_r1', 'filled_fraction_r1', 'nonzero_grad_fraction', 'finite')
+    print('us per call at B = %d: the median of 30; hbm_frac_vjp_r1: %d bytes per pixel over the time, of %.0f GB/s' % (B, REG_GRAD_PIXEL_BYTES, HBM_GBS))
+    print('| image | ' + ' | '.join(cols) + ' |')
+    print('|---|' + '---|' * len(cols))
+    for case in cases:
+        print('| %s | ' % case + ' | '.join('%.3g' % rows[case][w] for w in cols) + ' |')
+    line = json.dumps(rows)
+    print(line)
+    path = argv[argv.index('--out') + 1] if '--out' in argv else os.path.join(ROOT, 'profiles', 'depth_regularize_grad_bench.json')
+    with open(path, 'w') as f:
+        f.write(line + '\n')
+
+
 # the nominal bytes of one pixel in ops.dense_ba_depth_variance_vjp: per pixel pass the 25 that the variance pass reads (depth, flow, mask,
 # map, rho) and the cotangent (8); the marginal mode makes two such passes (the sums of G, then the gradients), and the second stores
 # grad_inv_depth (8) and grad_flow (8)
@@ -872,6 +939,8 @@ def main_uncertainty_grad(argv):
 
 def main():
     import torch
+    if '--regularize-grad' in sys.argv[1:]:
+        return main_regularize_grad(sys.argv[1:])
     if '--uncertainty-grad' in sys.argv[1:]:
         return main_uncertainty_grad(sys.argv[1:])
     if '--propagate-grad' in sys.argv[1:]:
